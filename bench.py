@@ -14,18 +14,35 @@ Every batch's labels are CONSUMED before its output buffer is reused: the host w
 checksum of the labels that came back with the reference answers of that query set (the last batch of every stream is
 compared label by label), and hs_search_check's counters are sticky, so a capacity failure in any batch is reported.
 Workload: SIFT-1M-like d=128 L2, M=16 efC=200, Slim defaults, k=10; ef_search = the smallest value of the sweep whose
-recall@10 >= 0.95 on this data (all sweep points are reported in `config`).
+recall@10 >= 0.95 on this data (the points evaluated are reported in `config.sweep`; with `--full`, all of them, timed).
 
 Multi-GPU (torchrun, one rank per GPU): the index is replicated; `--scaling strong` (the default for N > 1): ONE 10k batch is
 split into contiguous shards over the ranks (BASELINE.json configs[3]) and the per-rank top-k labels are joined by one RCCL
 all-gather per batch -- this is `value`; the weak figure (every rank searches its own 10k batches) is measured right after on a
-shorter region and reported as a side field.  Only rank 0 sweeps ef and computes ground truth; the ranks share its choice.
+shorter region and reported as a side field (`--full`).  Only rank 0 computes ground truth and chooses ef; the ranks share its choice.
+
+A plain run does only what `value` needs: load the index, ground truth, ef ascending until recall@10 >= 0.95, the reference
+answers of the query sets, warm-up, the timed steps, the result line.  `--full` adds what takes runs of its own: the whole ef
+sweep with per-point launch timing, the weak-scaling side figure, the single-launch / device-resident / synchronous-entry side
+figures with the single-launch roofline, and the CPU baseline (unless `--no-cpu-baseline`).
+
+Data + index: built once into the user's cache directory (`$XDG_CACHE_HOME` or `~/.cache`, under hnsw-slim-amd/bench/) --
+`__graft_entry__.build()` does it through `--prepare-only` -- and loaded from there; `--index-dir` uses (or fills) a directory
+of your choice instead.  The data and the queries are seeded, and the graph is built by the serial addPoint loop (the
+reference's own build order; about ten minutes of one core at 1M), so every build of the index is the same file and every run
+computes the same labels.  (`--build-threads N` builds faster, but a parallel build's graph depends on thread timing.)
+
+`--dump-outputs DIR` writes, after the timed steps, the labels the timed path returned for each query set in its last step as
+DIR/labels_qset<b>.npy (float64, [queries, k]; at most 64 MiB in all, else a fixed row sample plus <name>_rows.npy).
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the roofline accounting.
 """
 import argparse
+import hashlib
+import inspect
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -34,6 +51,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hsutil  # noqa: E402
 from hsutil import headline_data, load_product  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s measured achievable
@@ -42,8 +60,107 @@ DATA_DESC = ("synthetic: tests/hsutil.py::headline_data (4096-component mixture 
              "profiles/r01_calib_isotropic_vs_lowrank.log); base seed 123, query batch b of rank r seed 456+100r+b")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+T0 = time.perf_counter()   # (near) process start: the setup-time marks in the log
+
+
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+def default_threads():
+    """CPU threads for the Slim conversion (deterministic at any thread count): OMP_NUM_THREADS where the job is given a CPU
+    budget, else the usable cores (at most 64)."""
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    return min(len(os.sched_getaffinity(0)) or 8, 64)
+
+
+def graph_tag(build_threads):
+    """The serial build (1 thread, the default) is the reference's addPoint loop and the same graph on every run; a parallel
+    build inserts in whatever order its threads reach the points, so its graph -- and the labels searched on it -- vary."""
+    return "serial" if build_threads == 1 else f"threads{build_threads}"
+
+
+def index_cache_dir(n, d, build_threads=1):
+    """Default home of the bench's data + index, keyed by the shape, the build mode and the code that makes them (generator,
+    builder)."""
+    h = hashlib.sha256()
+    with open(os.path.join(ROOT, "hnsw-slim_amd", "csrc", "host_graph.hpp"), "rb") as f:
+        h.update(f.read())
+    for fn in (hsutil._lowrank_clusters, hsutil.sift_like, hsutil.headline_data):
+        h.update(inspect.getsource(fn).encode())
+    root = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(root, "hnsw-slim-amd", "bench", f"sift-like_n{n}_d{d}_M16_efc200_{graph_tag(build_threads)}_{h.hexdigest()[:12]}")
+
+
+def prepare_index(idir, n, d, build_threads, hs, keep_hnsw=True):
+    """base.npy, slim.bin (and hnsw.bin if keep_hnsw) of the workload in idir; the `ready` marker is written last.
+    Returns (build seconds, convert seconds): zeros when idir was already complete."""
+    hpath, spath, bpath, ready = (os.path.join(idir, f) for f in ("hnsw.bin", "slim.bin", "base.npy", "ready"))
+    if os.path.exists(spath) and os.path.exists(bpath) and os.path.exists(ready):
+        return 0.0, 0.0
+    os.makedirs(idir, exist_ok=True)
+    t0 = time.time()
+    base = headline_data(n, d, 123)
+    log(f"generated base {base.shape} in {time.time() - t0:.1f}s; building HNSW M=16 efC=200 with {build_threads} thread(s)")
+    t0 = time.time()
+    hs.build_hnsw(base, hpath, M=16, ef_construction=200, branching_factor="4", seed=100, threads=build_threads)
+    t_build = time.time() - t0
+    t0 = time.time()
+    hs.convert_slim(hpath, spath, d, threads=default_threads())
+    t_conv = time.time() - t0
+    np.save(bpath, base)
+    if not keep_hnsw:
+        os.remove(hpath)
+    with open(ready, "w") as f:
+        f.write("ok")
+    log(f"build {t_build:.1f}s, convertFromHNSW {t_conv:.1f}s")
+    return t_build, t_conv
+
+
+def prepare_cached(n, d, build_threads, hs):
+    """prepare_index into index_cache_dir(n, d), staged in a sibling directory and renamed into place when complete, so an
+    interrupted build never leaves a directory that looks ready.  Returns (directory, build s, convert s)."""
+    idir = index_cache_dir(n, d, build_threads)
+    if os.path.exists(os.path.join(idir, "ready")):
+        return idir, 0.0, 0.0
+    stage = f"{idir}.part{os.getpid()}"
+    shutil.rmtree(stage, ignore_errors=True)
+    t_build, t_conv = prepare_index(stage, n, d, build_threads, hs, keep_hnsw=False)
+    if os.path.isdir(idir) and not os.path.exists(os.path.join(idir, "ready")):
+        shutil.rmtree(idir, ignore_errors=True)
+    try:
+        os.rename(stage, idir)
+    except OSError:
+        if not os.path.exists(os.path.join(idir, "ready")):
+            raise
+        shutil.rmtree(stage, ignore_errors=True)   # another process completed it first
+    return idir, t_build, t_conv
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every array as outdir/<name>.npy in float64 (labels are integers far below 2**53: exact).  If that would exceed
+    `limit` bytes in all, the same fraction of each array's rows is kept -- a sorted sample drawn with seed 0, so identical
+    from run to run -- and outdir/<name>_rows.npy holds the row numbers kept.  Returns the names written."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    full_bytes = sum(a.size for a in arrays.values()) * 8
+    frac = 1.0
+    if full_bytes > limit:   # sampled: every kept row also costs its row number
+        frac = limit / sum(a.shape[0] * (a.size // max(a.shape[0], 1) + 1) * 8 for a in arrays.values())
+    written = []
+    for name, a in arrays.items():
+        if frac < 1.0:
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(outdir, f"{name}_rows.npy"), rows.astype(np.float64))
+            written.append(f"{name}_rows")
+            a = a[rows]
+        np.save(os.path.join(outdir, f"{name}.npy"), a.astype(np.float64))
+        written.append(name)
+    return written
 
 
 def ground_truth(torch, base_t, q_t, k, hs):
@@ -91,8 +208,9 @@ def main():
     ap.add_argument("--batch", dest="nq", type=int, default=10_000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--ef", type=int, default=0, help="fixed ef_search (0 = smallest sweep value with recall>=0.95)")
-    ap.add_argument("--build-threads", type=int, default=0)
-    ap.add_argument("--index-dir", default="", help="reuse/build index files here instead of a temp dir")
+    ap.add_argument("--build-threads", type=int, default=1, help="threads of the HNSW build: 1 (default) = the serial addPoint loop, the "
+                                                                 "same graph on every run; more are faster, but the graph then varies")
+    ap.add_argument("--index-dir", default="", help="reuse/build index files here instead of the user cache directory")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cand-cap", type=int, default=0)
     ap.add_argument("--hash-slots", type=int, default=0)
@@ -100,7 +218,23 @@ def main():
     ap.add_argument("--batches-per-step", type=int, default=100)
     ap.add_argument("--query-sets", type=int, default=8, help="distinct pre-generated query batches rotated through")
     ap.add_argument("--scaling", choices=("auto", "weak", "strong"), default="auto", help="auto: strong (one batch split over the ranks) when --gpus > 1")
+    ap.add_argument("--full", action="store_true", help="also the whole ef sweep with launch timing, the side figures, the single-launch "
+                                                        "roofline, the weak-scaling side figure and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the labels of the last timed step here (.npy, float64)")
+    ap.add_argument("--prepare-only", action="store_true", help="build the data + index (default cache or --index-dir) and exit; no GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    threads = max(1, args.build_threads)
+    if args.prepare_only:
+        hs = load_product()
+        if args.index_dir:
+            idir = args.index_dir
+            prepare_index(idir, args.n, args.dim, threads, hs)
+        else:
+            idir, _, _ = prepare_cached(args.n, args.dim, threads, hs)
+        log(f"data + index ready in {idir}")
+        return
     hip_queue_hint(args.nq, int(os.environ.get("WORLD_SIZE", "1")), args.scaling)
 
     import torch
@@ -128,43 +262,36 @@ def main():
     _sp = importlib.util.spec_from_file_location('hs_sharded', os.path.join(ROOT, 'hnsw-slim_amd', 'sharded.py'))
     sharded = importlib.util.module_from_spec(_sp)
     _sp.loader.exec_module(sharded)
-    threads = args.build_threads or min(len(os.sched_getaffinity(0)) or 8, 64)
     N, D, NQ, K = args.n, args.dim, args.nq, args.k
     BPS, NB, S = max(1, args.batches_per_step), max(1, args.query_sets), max(1, args.streams)
     strong = world > 1 and args.scaling in ("auto", "strong")
+    full_run = args.full
 
-    # ---- data + index: rank 0 builds once and publishes a marker file; the other ranks generate their query sets
-    #      meanwhile and wait on the file system, not inside a collective --------------------------------------------
+    # ---- data + index: rank 0 builds once (normally already done: the cache) and publishes a marker file; the other ranks
+    #      generate their query sets meanwhile and wait on the file system, not inside a collective ---------------------
     tmp = None
-    if args.index_dir:
-        idir = args.index_dir
-        os.makedirs(idir, exist_ok=True)
-    elif world > 1:
-        idir = os.path.join(tempfile.gettempdir(), f"hs_bench_{os.environ.get('MASTER_PORT', '0')}_{N}_{D}")
-        os.makedirs(idir, exist_ok=True)
-    else:
-        tmp = tempfile.TemporaryDirectory()
-        idir = tmp.name
-    hpath, spath, bpath, ready = (os.path.join(idir, f) for f in ("hnsw.bin", "slim.bin", "base.npy", "ready"))
+    idir = args.index_dir or index_cache_dir(N, D, threads)
     t_build = t_conv = 0.0
-    if rank == 0 and not (os.path.exists(spath) and os.path.exists(bpath) and os.path.exists(ready)):
-        t0 = time.time()
-        base = headline_data(N, D, 123)
-        log(f"generated base {base.shape} in {time.time() - t0:.1f}s; building HNSW M=16 efC=200 with {threads} threads")
-        t0 = time.time()
-        hs.build_hnsw(base, hpath, M=16, ef_construction=200, branching_factor="4", seed=100, threads=threads)
-        t_build = time.time() - t0
-        t0 = time.time()
-        hs.convert_slim(hpath, spath, D, threads=threads)
-        t_conv = time.time() - t0
-        np.save(bpath, base)
-        open(ready, "w").write("ok")
-        log(f"build {t_build:.1f}s, convertFromHNSW {t_conv:.1f}s")
+    if rank == 0:
+        if args.index_dir:
+            t_build, t_conv = prepare_index(idir, N, D, threads, hs)
+        else:
+            try:
+                idir, t_build, t_conv = prepare_cached(N, D, threads, hs)
+            except OSError as e:
+                if world > 1:
+                    raise
+                log(f"index cache not usable ({e}); building in a temporary directory")
+                tmp = tempfile.TemporaryDirectory()
+                idir = tmp.name
+                t_build, t_conv = prepare_index(idir, N, D, threads, hs, keep_hnsw=False)
+    spath, bpath, ready = (os.path.join(idir, f) for f in ("slim.bin", "base.npy", "ready"))
     # query sets: the same global batches on every rank (strong: each rank takes its shard of a batch; weak: each rank searches them whole)
     query_sets = [headline_data(NQ, D, 456 + b) for b in range(NB)]
     while not os.path.exists(ready):
         time.sleep(0.5)
     base = np.load(bpath, mmap_mode="r")
+    log(f"data + index ready ({time.perf_counter() - T0:.1f}s since start)")
 
     ix = hs.Index(spath, hs.HS_KIND_SLIM, D, hs.HS_METRIC_L2, device=local_rank)
     info = ix.info()
@@ -183,7 +310,8 @@ def main():
         ix.check(stream)
 
     # ---- rank 0 only: ground truth, the ef sweep on query set 0 (device-resident, one launch at a time), the operating point:
-    #      the smallest sweep ef whose recall@10 >= 0.95 over ALL the query sets of the timed region --------------------------
+    #      the smallest sweep ef whose recall@10 >= 0.95 over ALL the query sets of the timed region.  A plain run stops the
+    #      sweep at the first ef that passes on set 0 (the one a whole sweep would choose too); --full times every point -----
     sweep, chosen, recall, recalls = {}, 0, 0.0, []
     efs = [args.ef] if args.ef else [32, 48, 64, 68, 70, 72, 80, 96, 128, 192, 256, 384, 512]
     if rank == 0:
@@ -197,22 +325,28 @@ def main():
             lab = d_labels.cpu().numpy().astype(np.uint32)
             st = d_stats.cpu().numpy().astype(np.int64)
             rec = recall_at_k(lab, gts[0])
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            run(ef)
-            e0.record()
-            for _ in range(3):
-                run(ef)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / 3
             bytes_q = st[:, 0] * 4 * D + st[:, 2] * 4 + st[:, 1] * 8
-            sweep[ef] = dict(recall=round(rec, 4), single_launch_qps=round(NQ / ms * 1e3), n_dist=round(float(st[:, 0].mean()), 1),
-                             n_hops=round(float(st[:, 1].mean()), 1), bytes_per_query=round(float(bytes_q.mean())),
-                             fallback=int((st[:, 3] != 0).sum()), alg_GBs=round(float(bytes_q.sum()) / ms / 1e6, 1), kernel=ix.last_kernel())
+            point = dict(recall=round(rec, 4))
+            if full_run:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                run(ef)
+                e0.record()
+                for _ in range(3):
+                    run(ef)
+                e1.record()
+                torch.cuda.synchronize()
+                ms = e0.elapsed_time(e1) / 3
+                point["single_launch_qps"] = round(NQ / ms * 1e3)
+            point.update(n_dist=round(float(st[:, 0].mean()), 1), n_hops=round(float(st[:, 1].mean()), 1),
+                         bytes_per_query=round(float(bytes_q.mean())), fallback=int((st[:, 3] != 0).sum()))
+            if full_run:
+                point["alg_GBs"] = round(float(bytes_q.sum()) / ms / 1e6, 1)
+            point["kernel"] = ix.last_kernel()
+            sweep[ef] = point
             log(f"ef={ef}: {sweep[ef]}")
             if not chosen and rec >= 0.95:
                 chosen = ef
-                if not args.ef and os.environ.get("HS_BENCH_FULL_SWEEP", "1") == "0":
+                if not args.ef and (not full_run or os.environ.get("HS_BENCH_FULL_SWEEP", "1") == "0"):
                     break
         chosen = chosen or efs[-1]
         while True:
@@ -317,9 +451,11 @@ def main():
             events[s].record(streams[s])
             last_on[s] = j % NB
 
-        def finish():
+        def finish(ended=None):
             for s_, st_ in enumerate(streams):
                 consume(s_, full=True)
+                if ended is not None and last_on[s_] >= 0:
+                    ended.append((s_, last_on[s_]))
                 last_on[s_] = -1
                 ix.check(st_.cuda_stream)  # synchronises the stream; the counters are sticky: any batch's capacity failure shows here
 
@@ -330,10 +466,11 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
+        ended = []
         t0 = time.perf_counter()
         for j in range(steps * BPS):
             batch(j)
-        finish()
+        finish(ended)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -342,50 +479,59 @@ def main():
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, steps * BPS, rows
+        finals = {}
+        for s_, b in ended:   # each stream's last batch of the last step: the labels the timed path handed back
+            got, _, sl = mine(s_)
+            finals[b] = got[sl].copy()
+        return el, steps * BPS, rows, finals
 
-    elapsed, n_batches, rows = timed(strong, args.steps, args.warmup)
+    elapsed, n_batches, rows, final_labels = timed(strong, args.steps, args.warmup)
+    log(f"timed region done ({time.perf_counter() - T0:.1f}s since start)")
     total_queries = (NQ if strong else world * NQ) * n_batches
     qps = total_queries / elapsed
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {f"labels_qset{b}": final_labels[b] for b in sorted(final_labels)})
     weak_side = None
-    if strong:   # the weak figure beside it: every rank searches whole 10k batches (a quarter of the steps)
-        w_el, w_nb, _ = timed(False, max(args.steps // 4, 1), max(args.warmup // 4, 1))
+    if strong and full_run:   # the weak figure beside it: every rank searches whole 10k batches (a quarter of the steps)
+        w_el, w_nb, _, _ = timed(False, max(args.steps // 4, 1), max(args.warmup // 4, 1))
         weak_side = round(world * NQ * w_nb / w_el, 1)
 
-    # ---- side figures (never `value`): one launch alone on the GPU, device-resident pipelined rate -------------------
-    def finish_all():
-        for st_ in streams:
-            ix.check(st_.cuda_stream)
+    # ---- side figures (never `value`, --full only): one launch alone on the GPU, device-resident pipelined rate ------
+    kern_ms = dev_resident_qps = sync_host_qps = None
+    if full_run:
+        def finish_all():
+            for st_ in streams:
+                ix.check(st_.cuda_stream)
 
-    ke0, ke1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    kern_ms = []
-    for i in range(max(min(args.steps, 40), 10)):
-        qq = q_sets_t[i % NB]
-        ke0.record()
-        ix.search_ids_dev(qq, K, d_labels, None, d_counts, None, stream)
-        ke1.record()
+        ke0, ke1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        kern_ms = []
+        for i in range(max(min(args.steps, 40), 10)):
+            qq = q_sets_t[i % NB]
+            ke0.record()
+            ix.search_ids_dev(qq, K, d_labels, None, d_counts, None, stream)
+            ke1.record()
+            torch.cuda.synchronize()
+            kern_ms.append(ke0.elapsed_time(ke1))
+        ix.check(stream)
+        kern_ms = float(np.mean(kern_ms))
+        outs = [(torch.empty((NQ, K), dtype=torch.int32, device=dev), torch.empty((NQ,), dtype=torch.int32, device=dev)) for _ in range(S)]
         torch.cuda.synchronize()
-        kern_ms.append(ke0.elapsed_time(ke1))
-    ix.check(stream)
-    kern_ms = float(np.mean(kern_ms))
-    outs = [(torch.empty((NQ, K), dtype=torch.int32, device=dev), torch.empty((NQ,), dtype=torch.int32, device=dev)) for _ in range(S)]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for j in range(16 * S):
-        ix.search_ids_dev(q_sets_t[j % NB], K, outs[j % S][0], None, outs[j % S][1], None, streams[j % S].cuda_stream)
-    finish_all()
-    dev_resident_qps = 16 * S * NQ / (time.perf_counter() - t0)
-    sync_host_qps = None
-    if rank == 0 and world == 1:   # the synchronous host-pointer entry on pageable memory
-        ix.search_ids(query_sets[0], K)
         t0 = time.perf_counter()
-        for i in range(5):
-            ix.search_ids(query_sets[i % NB], K)
-        sync_host_qps = round(5 * NQ / (time.perf_counter() - t0), 1)
+        for j in range(16 * S):
+            ix.search_ids_dev(q_sets_t[j % NB], K, outs[j % S][0], None, outs[j % S][1], None, streams[j % S].cuda_stream)
+        finish_all()
+        dev_resident_qps = 16 * S * NQ / (time.perf_counter() - t0)
+        if rank == 0 and world == 1:   # the synchronous host-pointer entry on pageable memory
+            ix.search_ids(query_sets[0], K)
+            t0 = time.perf_counter()
+            for i in range(5):
+                ix.search_ids(query_sets[i % NB], K)
+            sync_host_qps = round(5 * NQ / (time.perf_counter() - t0), 1)
 
-    # ---- CPU baseline: the oracle (port) on this box's host cores, rank 0, N=1 only ----------------------------------
+    # ---- CPU baseline (--full): the oracle (port) on this box's host cores, rank 0, N=1 only --------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full_run and not args.no_cpu_baseline:
         from hsutil import Oracle
         threads_all = min(len(os.sched_getaffinity(0)) or 1, 64)
         model, phys = "unknown", set()
@@ -432,6 +578,9 @@ def main():
                    ofast={"flags": "-Ofast -flto -march=native -fopenmp (/root/reference/CMakeLists.txt:14)", "value": round(of_par, 1), "serial_qps": round(of_ser, 1),
                           "batches": of_reps, "label_sets_identical_to_gpu": of_same})
 
+    def rnd(x, nd):   # side figures a plain run does not measure stay null
+        return None if x is None else round(x, nd)
+
     if rank == 0:
         # HBM traffic (PMC) cannot be collected from inside this process; the committed profile of this same workload is quoted
         traffic, tsrc = None, None
@@ -445,7 +594,7 @@ def main():
         kname = kernel_name   # the kernel the library chose for this shape (hs_last_kernel)
         step_ms = elapsed / args.steps * 1e3
         batch_ms = elapsed / n_batches * 1e3
-        achieved_single = alg_bytes_launch / (kern_ms * 1e-3) / 1e9   # one launch alone on the GPU
+        achieved_single = alg_bytes_launch / (kern_ms * 1e-3) / 1e9 if full_run else None   # one launch alone on the GPU
         eff = alg_bytes_launch * (1 if strong else world) / (batch_ms * 1e-3) / 1e9
         out = {
             "metric": "QPS @ recall@10>=0.95 (SIFT-1M d=128, k=10)", "value": round(qps, 1), "unit": "queries/s",
@@ -461,21 +610,21 @@ def main():
                        "entry": "hs_search_batch_async (host pointers)" if world == 1 else "hs_search_batch_dev + torch.distributed all_gather_into_tensor" + (" (queries read in place from mapped page-locked memory)" if (strong and 0 < rows * D * 4 <= (2 << 20)) else ""),
                        "ef_search": chosen, "recall_at_10": round(recall, 4), "recall_per_query_set": [round(r, 4) for r in recalls],
                        "sweep": sweep, "index": info, "build_s": round(t_build, 1), "convert_s": round(t_conv, 1), "build_threads": threads,
-                       "device_resident_pipelined_qps": round(dev_resident_qps, 1), "single_launch_qps": round(NQ / kern_ms * 1e3, 1),
+                       "device_resident_pipelined_qps": rnd(dev_resident_qps, 1), "single_launch_qps": rnd(kern_ms and NQ / kern_ms * 1e3, 1),
                        "sync_host_pointer_api_qps_pageable": sync_host_qps,
                        "weak_scaling_qps_side_figure": weak_side},
             # achieved/frac: algorithmic bytes of one 10k-query launch / the HIP-event duration of that launch alone on the GPU
             # (what a rocprofv3 kernel-trace of the search kernel's dispatches adds up to, profiles/r03_kernel_stats_1stream.csv);
             # timed_region_*: the same bytes / the effective per-batch time of the timed region (S batches in flight, PCIe included).
-            "roofline": {"bound": "hbm", "achieved": round(achieved_single, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved_single / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
-                         "kernel": kname, "launch_ms": round(kern_ms, 4),
-                         "launch": f"one 10k-query pass = {kname[4:]} (upper-level descent) + order_kernel (start order) + {kname[4:]} "
+            "roofline": {"bound": "hbm", "achieved": rnd(achieved_single, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": rnd(achieved_single and achieved_single / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
+                         "kernel": kname, "launch_ms": rnd(kern_ms, 4),
+                         "launch": None if not full_run else f"one 10k-query pass = {kname[4:]} (upper-level descent) + order_kernel (start order) + {kname[4:]} "
                                    f"(level-0 search) + the (normally empty) re-run scan; launch_ms spans them, a rocprofv3 kernel trace shows two "
                                    f"{kname[4:]} dispatches per pass whose durations add up to it",
                          "timed_region_achieved": round(eff, 1), "timed_region_frac": round(eff / HBM_PEAK_GBS, 4),
                          "launches_in_flight": S, "algorithmic_bytes_per_launch": alg_bytes_launch},
-            "cpu_baseline": cpu,
+            "cpu_baseline": cpu, "full": full_run, "outputs_dumped": dumped,
         }
         print(json.dumps(out), flush=True)
     if world > 1:

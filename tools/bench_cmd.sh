@@ -3,10 +3,10 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/r2_bench
 mkdir -p $O
-python bench.py --index-dir /tmp/idx > $O/bench_1gpu.json 2> $O/bench_1gpu.log || { tail -20 $O/bench_1gpu.log; exit 1; }
+python bench.py --full --index-dir /tmp/idx > $O/bench_1gpu.json 2> $O/bench_1gpu.log || { tail -20 $O/bench_1gpu.log; exit 1; }
 for M in weak strong; do
   HS_BENCH_ONE_DEVICE=1 HS_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --steps 5 --warmup 1 --ef 68 --index-dir /tmp/idx --scaling $M --no-cpu-baseline > $O/bench_2rank_$M.json 2> $O/bench_2rank_$M.log || { tail -20 $O/bench_2rank_$M.log; exit 1; }
+    bench.py --full --gpus 2 --steps 5 --warmup 1 --ef 68 --index-dir /tmp/idx --scaling $M --no-cpu-baseline > $O/bench_2rank_$M.json 2> $O/bench_2rank_$M.log || { tail -20 $O/bench_2rank_$M.log; exit 1; }
 done
 python - <<'PY'
 import json

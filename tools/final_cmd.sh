@@ -7,7 +7,7 @@ O=gpurun_out/final
 mkdir -p $O
 python bench.py --index-dir /tmp/idx > $O/bench_pipelined.json 2> $O/bench_pipelined.log || exit 1
 EF=$(python -c "import json;print(json.load(open('$O/bench_pipelined.json'))['config']['ef_search'])")
-python bench.py --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > $O/bench_1stream.json 2> $O/bench_1stream.log || exit 1
+python bench.py --full --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > $O/bench_1stream.json 2> $O/bench_1stream.log || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_1stream -- python bench.py --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > /dev/null 2>&1
 find $O -name "*agent_info.csv" -delete
 find $O -name "*kernel_trace.csv" -delete

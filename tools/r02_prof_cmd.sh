@@ -8,9 +8,9 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/r02
 rm -rf $O; mkdir -p $O
-python bench.py --index-dir /tmp/idx > $O/bench_pipelined.json 2> $O/bench_pipelined.log || { tail -5 $O/bench_pipelined.log; exit 1; }
+python bench.py --full --index-dir /tmp/idx > $O/bench_pipelined.json 2> $O/bench_pipelined.log || { tail -5 $O/bench_pipelined.log; exit 1; }
 EF=$(python -c "import json;print(json.load(open('$O/bench_pipelined.json'))['config']['ef_search'])")
-python bench.py --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > $O/bench_1stream.json 2> $O/bench_1stream.log || exit 1
+python bench.py --full --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > $O/bench_1stream.json 2> $O/bench_1stream.log || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_pipelined -- python bench.py --index-dir /tmp/idx --ef $EF --no-cpu-baseline > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_1stream -- python bench.py --index-dir /tmp/idx --ef $EF --streams 1 --no-cpu-baseline > /dev/null 2>&1
 for C in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
