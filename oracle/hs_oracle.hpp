@@ -12,8 +12,10 @@
 //   * HierarchicalNSWSlim (hnswalg_slim.h needs folly, absent here, so the class itself cannot be compiled): the
 //     search, the CHAL slice addressing and the Slim loader are CROSS-PINNED to the compiled vanilla reference's golden
 //     outputs through a verbatim vanilla -> Slim re-encoding of the reference-built graphs (oracle/chal_encode.py,
-//     tests/test_oracle_golden.py::test_slim_search_on_verbatim_encoding_matches_reference); convertFromHNSW's pruning
-//     is restated from source reading only.
+//     tests/test_oracle_golden.py::test_slim_search_on_verbatim_encoding_matches_reference).  convertFromHNSW + saveIndex
+//     are restated in hs_oracle_convert.hpp, from the reference source alone (the product's conversion is a separate reading);
+//     not pinned by a compiled reference, that restatement is checked list for list against a plain-Python reading on
+//     integer-valued rows (tests/test_slim_convert_restated_cpu.py), and the product's files must equal its bytes.
 //
 // All file:line citations are relative to /root/reference/third_party/hnswlib/.
 #pragma once

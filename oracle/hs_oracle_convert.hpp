@@ -1,0 +1,234 @@
+// oracle/hs_oracle_convert.hpp -- TEST INFRASTRUCTURE ONLY.
+//
+// HierarchicalNSWSlim::convertFromHNSW (hnswalg_slim.h:836-1108) followed by saveIndex (:717-751), restated from the reference
+// source alone: the product's conversion (hnsw-slim_amd/csrc/host_graph.hpp, convert_gpu.hip) is a second, separate reading and
+// nothing here is taken from it.  The class needs folly and cannot be compiled here, so this restatement is not pinned by a
+// compiled reference; tests/test_slim_convert_restated_cpu.py checks it against a plain-Python reading on integer rows.
+//
+// Serial by construction: the reference's OpenMP loops only fill per-node slots, and the reverse-edge lists are sorted and
+// deduplicated before anyone reads them (:999-1012), so a serial run is the answer of every schedule.
+//
+// All file:line citations are relative to the reference's third_party/hnswlib/.
+#pragma once
+#include "hs_oracle.hpp"
+
+namespace hso {
+
+struct SlimConvertParams {
+  int threshold_level = 0;
+  float top_pct0 = 0.02f, top_pct = 0.02f;                 // top_degree_percent0_, top_degree_percent_ (:63-64)
+  size_t top_M0 = 32, low_m0 = 8, top_M = 16, low_m = 4;   // top_degree_M0_, low_degree_m0_, top_degree_M_, low_degree_m_ (:65-68)
+};
+
+// What the tests assert their premises with.
+struct SlimConvertStats {
+  std::vector<size_t> thr, hubs, topN;  // per level: degree_threshold[l], lists with size > thr[l] (first pass), topN
+  size_t n_reprune = 0;                 // lists that took the re-prune (:1038-1062)
+  size_t max_union = 0;                 // largest id-sorted, deduplicated union (:1003-1010)
+  size_t n_eqkey_over16 = 0;            // sorted lists longer than 16 with two equal keys (std::sort's tie order beyond insertion sort)
+};
+
+// compare_by_first (:169-175): looks at .first only, so libstdc++'s std::sort decides the order among equal keys, as it does in
+// the reference.
+struct cmp_by_first {
+  bool operator()(const pairfi &a, const pairfi &b) const { return a.first < b.first; }
+};
+
+// PruneByHeuristic (:836-865): `heap` sorted ascending by distance; a candidate is dropped when a neighbour KEPT SO FAR is
+// strictly closer to it than the node is (:850-858); stops at M kept.
+inline void slim_prune(const VanillaIndex &g, const pairfi *heap, size_t heap_size, std::vector<uint32_t> &out, size_t M) {
+  out.clear();
+  for (size_t i = 0; i < heap_size; i++) {
+    if (out.size() >= M) break;
+    const pairfi cur = heap[i];
+    bool good = true;
+    for (size_t j = 0; j < out.size(); j++) {
+      float curdist = dist(g.metric, g.vec(out[j]), g.vec(cur.second), g.dim);  // fstdistfunc_(kept, candidate) (:851-854)
+      if (curdist < cur.first) {
+        good = false;
+        break;
+      }
+    }
+    if (good) out.push_back(cur.second);
+  }
+}
+
+// (dist(v, id), id) for every id, then std::sort by .first (:975-982, :1050-1057).
+inline void slim_sort_by_dist(const VanillaIndex &g, uint32_t v, const uint32_t *ids, size_t n, std::vector<pairfi> &heap,
+                              SlimConvertStats &st) {
+  heap.resize(n);
+  for (size_t j = 0; j < n; j++) heap[j] = pairfi(dist(g.metric, g.vec(v), g.vec(ids[j]), g.dim), ids[j]);
+  std::sort(heap.data(), heap.data() + n, cmp_by_first());
+  if (n > 16)
+    for (size_t j = 1; j < n; j++)
+      if (heap[j].first == heap[j - 1].first) { st.n_eqkey_over16++; break; }
+}
+
+// convertFromHNSW + saveIndex -> the bytes of the Slim file.
+inline std::vector<char> slim_convert(const VanillaIndex &g, const SlimConvertParams &p, SlimConvertStats &st) {
+  const size_t n = g.count;
+  const int maxlevel = g.maxlevel;
+  const size_t maxM0 = g.maxM0, maxM = g.maxM;
+  auto cnt_at = [&](uint32_t i, int l, const uint32_t *&ids) {
+    size_t c;
+    ids = l == 0 ? g.list0(i, c) : g.list(i, l, c);
+    return c;
+  };
+
+  // degree histograms (:904-922).  QUIRK: the loop counts level_cnts[l] for l >= 1 only; level_cnts[0] is never incremented.
+  std::vector<std::vector<size_t>> hist(maxlevel + 1, std::vector<size_t>(maxM0 + 2, 0));
+  std::vector<size_t> level_cnts(maxlevel + 1, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t *ids;
+    for (int l = 1; l <= g.levels[i]; l++) {
+      level_cnts[l]++;
+      size_t c = cnt_at(i, l, ids);
+      if (c > maxM0 + 1) throw std::runtime_error("oracle: list longer than maxM0 + 1");
+      hist[l][c]++;
+    }
+    size_t c = cnt_at(i, 0, ids);
+    if (c > maxM0 + 1) throw std::runtime_error("oracle: list longer than maxM0 + 1");
+    hist[0][c]++;
+  }
+
+  // hub thresholds (:923-945).  QUIRK: topN = static_cast<size_t>(level_cnts[l] * top_degree_percent_ + 0.5) multiplies a size_t
+  // by a float, so the product is a FLOAT product of float(level_cnts[l]) and alpha; only the + 0.5 is done in double.  With
+  // level_cnts[0] == 0, topN is 0 at level 0, `acc >= topN` holds at the first bucket and degree_threshold[0] = maxM0 + 1: no
+  // level-0 list is ever a hub.  A level whose buckets 1.. never reach topN keeps degree_threshold 0.
+  std::vector<size_t> thr(maxlevel + 1, 0);
+  st.thr.assign(maxlevel + 1, 0);
+  st.topN.assign(maxlevel + 1, 0);
+  st.hubs.assign(maxlevel + 1, 0);
+  for (int l = 0; l <= maxlevel; l++) {
+    const float alpha = l == 0 ? p.top_pct0 : p.top_pct;
+    const float prod = (float)level_cnts[l] * alpha;
+    const size_t topN = static_cast<size_t>((double)prod + 0.5);
+    size_t acc = 0;
+    for (size_t d = hist[l].size() - 1; d > 0; --d) {
+      acc += hist[l][d];
+      if (acc >= topN) {
+        thr[l] = d;
+        break;
+      }
+    }
+    st.thr[l] = thr[l];
+    st.topN[l] = topN;
+  }
+
+  // first pass (:947-986): per node and level, sort by distance and prune to M_h / M_l.  QUIRK: the hub test is
+  // `size > degree_threshold[l]`, strictly greater (:969, :971).
+  std::vector<std::vector<std::vector<uint32_t>>> nn(n), rev(n);
+  std::vector<pairfi> heap;
+  for (uint32_t v = 0; v < n; v++) {
+    const int L = g.levels[v];
+    nn[v].resize(L + 1);
+    rev[v].resize(L + 1);
+    for (int l = 0; l <= L; l++) {
+      const uint32_t *ids;
+      const size_t size = cnt_at(v, l, ids);
+      const bool hub = size > thr[l];
+      st.hubs[l] += hub;
+      const size_t M0 = l == 0 ? (hub ? p.top_M0 : p.low_m0) : (hub ? p.top_M : p.low_m);
+      slim_sort_by_dist(g, v, ids, size, heap, st);
+      slim_prune(g, heap.data(), size, nn[v][l], M0);
+    }
+  }
+
+  // reverse edges (:988-998), then union + sort by id + unique (:999-1012)
+  for (uint32_t v = 0; v < n; v++)
+    for (int l = 0; l <= g.levels[v]; l++)
+      for (uint32_t u : nn[v][l]) {
+        if (u >= n || g.levels[u] < l) throw std::runtime_error("oracle: level-l edge to a node below level l");
+        rev[u][l].push_back(v);
+      }
+  for (uint32_t v = 0; v < n; v++)
+    for (int l = 0; l <= g.levels[v]; l++) {
+      auto &a = nn[v][l];
+      a.insert(a.end(), rev[v][l].begin(), rev[v][l].end());
+      std::sort(a.begin(), a.end());
+      a.erase(std::unique(a.begin(), a.end()), a.end());
+      st.max_union = std::max(st.max_union, a.size());
+    }
+
+  // element bytes (:1014-1107) and saveIndex (:717-751).  Element layout (:877-881): [int level][u32 total][u64 label]
+  // [char* neighbours][data].  CANONICAL BYTES: the reference stores a heap pointer in bytes 16..23 (:1092, :1101); the oracle
+  // writes zeros there, the convention of the product's writer.
+  const size_t offsetTotal = 4, label_offset = 8, offsetNeighbor = 16, offsetData = 24;
+  const size_t data_size = 4 * g.dim, size_per_el = offsetData + data_size;
+  std::vector<char> elements(n * size_per_el, 0);
+  std::vector<std::vector<char>> blobs(n);
+  std::vector<uint32_t> nbrs_out;
+  std::vector<uint16_t> offsets;
+  for (uint32_t i = 0; i < n; i++) {
+    char *e = elements.data() + (size_t)i * size_per_el;
+    const int32_t L = g.levels[i];
+    memcpy(e, &L, 4);
+    memcpy(e + offsetData, g.vec(i), data_size);
+    const uint64_t lab = g.label(i);
+    memcpy(e + label_offset, &lab, 8);
+    nbrs_out.clear();
+    offsets.clear();
+    for (int l = 0; l <= L; l++) {
+      auto &nbrs = nn[i][l];
+      const size_t limit = l == 0 ? maxM0 : maxM;
+      if (nbrs.size() > limit) {
+        // QUIRK: the re-prune sorts by distance starting from the id-sorted, deduplicated union (:1038-1062)
+        st.n_reprune++;
+        std::vector<uint32_t> ids = nbrs;
+        slim_sort_by_dist(g, i, ids.data(), ids.size(), heap, st);
+        slim_prune(g, heap.data(), ids.size(), nbrs, limit);
+      }
+      if (l == p.threshold_level) {  // (:1063-1070)
+        nbrs_out.insert(nbrs_out.end(), nbrs.begin(), nbrs.end());
+      } else {
+        // QUIRK: off threshold_level only neighbours whose own top level equals l are kept (:1071-1084)
+        for (uint32_t u : nbrs)
+          if (g.levels[u] == l) nbrs_out.push_back(u);
+      }
+      offsets.push_back((uint16_t)nbrs_out.size());  // offsetint is uint16_t: cumulative counts (:1085)
+    }
+    // QUIRK: total is stored with sizeof(levelsizeint) = 4 bytes (:1088-1089)
+    const uint32_t total = (uint32_t)nbrs_out.size();
+    memcpy(e + offsetTotal, &total, 4);
+    if (total == 0) continue;  // no blob (:1091-1094)
+    // blob: the first L cumulative u16 offsets, then the ids (:1096-1106)
+    blobs[i].resize(2 * (size_t)L + 4 * (size_t)total);
+    memcpy(blobs[i].data(), offsets.data(), 2 * (size_t)L);
+    memcpy(blobs[i].data() + 2 * (size_t)L, nbrs_out.data(), 4 * (size_t)total);
+  }
+
+  std::vector<char> out;
+  auto put = [&](const void *src, size_t nb) { out.insert(out.end(), (const char *)src, (const char *)src + nb); };
+  auto pu64 = [&](uint64_t x) { put(&x, 8); };
+  auto pi32 = [&](int32_t x) { put(&x, 4); };
+  auto pu32 = [&](uint32_t x) { put(&x, 4); };
+  pu64(n);                 // cur_element_count_
+  pu64(size_per_el);       // size_data_per_element_
+  pu64(label_offset);      // label_offset_
+  pu64(offsetTotal);       // offsetTotalNeighbor_
+  pu64(offsetData);        // offsetData_
+  pu64(offsetNeighbor);    // offsetNeighbor_
+  pi32(maxlevel);          // maxlevel_
+  pi32(p.threshold_level); // threshold_level_
+  pu32(g.enterpoint);      // enterpoint_node_
+  // maxM_, maxM0_, M_, ef_construction_ are copied from the vanilla index (:871-874)
+  pu64(g.maxM);
+  pu64(g.maxM0);
+  pu64(g.M);
+  pu64(g.efC);
+  // has_deleted_elements_ = hnsw->num_deleted_ > 0 (:869), the vanilla delete count
+  const uint8_t has_deleted = g.num_deleted > 0;
+  put(&has_deleted, 1);
+  put(elements.data(), elements.size());
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t total;
+    memcpy(&total, elements.data() + (size_t)i * size_per_el + offsetTotal, 4);
+    // QUIRK: get_neighbor_size = 2 L + 4 total (:652-661) is written even when total == 0, and then no blob follows (:745)
+    const uint32_t sz = 2 * (uint32_t)g.levels[i] + 4 * total;
+    pu32(sz);
+    if (sz && total != 0) put(blobs[i].data(), blobs[i].size());
+  }
+  return out;
+}
+
+}  // namespace hso

@@ -1,6 +1,7 @@
 // oracle/oracle_capi.cpp -- TEST INFRASTRUCTURE ONLY: C entry points over hs_oracle.hpp for ctypes
 // (tests/, smoke(), bench.py cpu_baseline).  Never linked into the product library.
 #include "hs_oracle.hpp"
+#include "hs_oracle_convert.hpp"
 #include "hs_oracle_slimq.hpp"
 #include <omp.h>
 
@@ -123,6 +124,34 @@ int hso_search_pq(void *p, const float *q, size_t nq, size_t k, float *out_d, ui
 int hso_dist(int metric, const float *a, const float *b, size_t n, size_t d, float *out) {
   try {
     for (size_t i = 0; i < n; i++) out[i] = dist((Metric)metric, a + i * d, b + i * d, d);
+    return 0;
+  } catch (std::exception &e) { g_err = e.what(); return 1; }
+}
+
+// HierarchicalNSWSlim::convertFromHNSW + saveIndex (hs_oracle_convert.hpp) from a vanilla file.  stats (nullable): u64[4 + 3 * 64]
+// = {levels, re-pruned lists, largest union, sorted lists > 16 with equal keys, then per level l < 64: threshold, hubs, topN}.
+int hso_convert_slim(const char *hnsw_path, const char *out_path, int metric, size_t dim, int threshold_level, float p0, float p,
+                     size_t M0h, size_t m0l, size_t Mh, size_t ml, uint64_t *stats) {
+  try {
+    VanillaIndex g;
+    g.load(hnsw_path, (Metric)metric, dim);
+    SlimConvertParams prm;
+    prm.threshold_level = threshold_level;
+    prm.top_pct0 = p0; prm.top_pct = p;
+    prm.top_M0 = M0h; prm.low_m0 = m0l; prm.top_M = Mh; prm.low_m = ml;
+    SlimConvertStats st;
+    std::vector<char> bytes = slim_convert(g, prm, st);
+    std::ofstream o(out_path, std::ios::binary);
+    if (!o.is_open()) throw std::runtime_error("Cannot open file");
+    o.write(bytes.data(), bytes.size());
+    if (!o) throw std::runtime_error("write failed");
+    if (stats) {
+      std::fill(stats, stats + 4 + 3 * 64, 0);
+      stats[0] = st.thr.size(); stats[1] = st.n_reprune; stats[2] = st.max_union; stats[3] = st.n_eqkey_over16;
+      for (size_t l = 0; l < st.thr.size() && l < 64; l++) {
+        stats[4 + 3 * l] = st.thr[l]; stats[5 + 3 * l] = st.hubs[l]; stats[6 + 3 * l] = st.topN[l];
+      }
+    }
     return 0;
   } catch (std::exception &e) { g_err = e.what(); return 1; }
 }

@@ -85,6 +85,39 @@ def headline_data(n, d, seed):
     return sift_like(n, d, seed, n_clusters=4096, rank=12, sigma_sub=40.0, sigma_iso=4.0)
 
 
+def write_vanilla_level0(path, rows, lists, M, efc=100):
+    """A one-level vanilla index file in HierarchicalNSW::saveIndex's layout (hnswalg.h:748-779), written directly so a test can
+    choose every level-0 list: node i -> lists[i] (at most 2 M ids), label i, enter point 0."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    n, dim = rows.shape
+    maxM0 = 2 * M
+    size_per_el = 4 + 4 * maxM0 + 4 * dim + 8
+    hdr = np.array([0, n, n, size_per_el, 4 + 4 * maxM0 + 4 * dim, 4 + 4 * maxM0], np.uint64).tobytes()
+    hdr += np.array([0], np.int32).tobytes() + np.array([0], np.uint32).tobytes()
+    hdr += np.array([M, maxM0, M], np.uint64).tobytes() + np.array([1.0 / np.log(M)], np.float64).tobytes()
+    hdr += np.array([efc], np.uint64).tobytes()
+    el = np.zeros((n, size_per_el), np.uint8)
+    for i, ids in enumerate(lists):
+        assert len(ids) <= maxM0
+        el[i, 0:2] = np.frombuffer(np.uint16(len(ids)).tobytes(), np.uint8)
+        el[i, 4:4 + 4 * len(ids)] = np.frombuffer(np.asarray(ids, np.uint32).tobytes(), np.uint8)
+        el[i, 4 + 4 * maxM0:4 + 4 * maxM0 + 4 * dim] = np.frombuffer(rows[i].tobytes(), np.uint8)
+        el[i, size_per_el - 8:] = np.frombuffer(np.uint64(i).tobytes(), np.uint8)
+    with open(path, "wb") as f:
+        f.write(hdr + el.tobytes() + np.zeros(n, np.uint32).tobytes())
+
+
+def equal_key_star(n_spokes, dim=16, r=3.0):
+    """Node 0 at the centre, nodes 1..n_spokes at +-r on the axes (every one at squared distance r^2 from node 0, 2 r^2 or 4 r^2
+    from each other): node 0's list holds all spokes, so sorting it by distance is all ties; the spokes' lists are empty, so no
+    reverse edge refills node 0's list after its prune."""
+    assert n_spokes <= 2 * dim
+    rows = np.full((n_spokes + 1, dim), 10.0, np.float32)
+    for s in range(n_spokes):
+        rows[1 + s, s % dim] += r if s < dim else -r
+    return rows, [list(range(1, n_spokes + 1))] + [[] for _ in range(n_spokes)]
+
+
 def load_chal_encode():
     """oracle/chal_encode.py (test infrastructure: the independent Python writer / reader of the Slim file format)."""
     spec = importlib.util.spec_from_file_location("chal_encode", os.path.join(ROOT, "oracle", "chal_encode.py"))
@@ -134,6 +167,8 @@ class Oracle:
         L.hso_dist.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]
         L.hso_brute_force.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_int]
         sz, dbl, ci = ctypes.c_size_t, ctypes.c_double, ctypes.c_int
+        fl = ctypes.c_float
+        L.hso_convert_slim.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ci, sz, ci, fl, fl, sz, sz, sz, sz, vp]
         L.hso_slimq_load.restype = vp
         L.hso_slimq_load.argtypes = [ctypes.c_char_p]
         L.hso_slimq_free.argtypes = [vp]
@@ -183,6 +218,20 @@ class Oracle:
         oi, od = np.empty(cap + 1, np.uint32), np.empty(cap + 1, np.float32)
         sz = self.L.hso_pool_run(cap, op.ctypes.data, ids.ctypes.data, d.ctypes.data, len(op), ev.ctypes.data, oi.ctypes.data, od.ctypes.data)
         return ev, oi[:sz], od[:sz]
+
+    def convert_slim(self, hnsw_path, out_path, dim, metric=0, threshold_level=0, top_degree_percent0=0.02, top_degree_percent=0.02,
+                     top_degree_M0=32, low_degree_m0=8, top_degree_M=16, low_degree_m=4):
+        """HierarchicalNSWSlim::convertFromHNSW + saveIndex (oracle/hs_oracle_convert.hpp), same keywords as the product's
+        convert_slim.  Returns the premise statistics: per-level thr / hubs / topN arrays, n_reprune, max_union, n_eqkey_over16."""
+        st = np.zeros(4 + 3 * 64, np.uint64)
+        rc = self.L.hso_convert_slim(hnsw_path.encode(), out_path.encode(), metric, dim, threshold_level, top_degree_percent0,
+                                     top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, st.ctypes.data)
+        if rc:
+            raise RuntimeError(self.err())
+        nl = int(st[0])
+        per = st[4:4 + 3 * nl].reshape(nl, 3).astype(np.int64)
+        return dict(thr=per[:, 0], hubs=per[:, 1], topN=per[:, 2], n_reprune=int(st[1]), max_union=int(st[2]),
+                    n_eqkey_over16=int(st[3]))
 
     def load_slimq(self, path):
         h = self.L.hso_slimq_load(path.encode())
