@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("HS_LIB", os.path.join(_HERE, "libhnsw_slim_amd.so")) 
 HS_KIND_HNSW, HS_KIND_SLIM, HS_KIND_SLIMQ = 0, 1, 2
 HS_METRIC_L2, HS_METRIC_IP = 0, 1
 HS_MODE_SLIM_IDS, HS_MODE_PQ = 0, 1
+HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8 = 0, 1, 2   # hs_row_format (narrow rows: Index.set_row_format)
 HS_OK, HS_ERR_IO, HS_ERR_CORRUPT, HS_ERR_NOMEM, HS_ERR_INVALID, HS_ERR_UNSUPPORTED, HS_ERR_DEVICE, HS_ERR_CAPACITY = range(8)
 
 EXPORTS = [
@@ -27,7 +28,7 @@ EXPORTS = [
     "hs_slimq_search_batch", "hs_slimq_search_batch_dev", "hs_slimq_trace", "hs_slimq_prepare_debug", "hs_brute_force", "hs_brute_force_dev",
     "hs_search_batch_async", "hs_host_alloc", "hs_host_free", "hs_comm_init", "hs_comm_free", "hs_comm_size", "hs_search_batch_sharded",
     "hs_comm_results_dev", "hs_convert_slim_gpu", "hs_index_patch", "hs_index_from_host_arrays", "hs_build_rabitq_hnsw",
-    "hs_convert_slimq_graph", "hs_host_device_pointer",
+    "hs_convert_slimq_graph", "hs_host_device_pointer", "hs_index_set_row_format", "hs_index_row_format", "hs_rows_representable",
 ]
 
 
@@ -73,6 +74,9 @@ def lib():
     L.hs_index_free.restype = None
     L.hs_set_ef.argtypes = [vp, sz]
     L.hs_index_info.argtypes = [vp, ctypes.POINTER(HsInfo)]
+    L.hs_index_set_row_format.argtypes = [vp, ci]
+    L.hs_index_row_format.argtypes = [vp]
+    L.hs_rows_representable.argtypes = [vp, sz, sz, ci, ctypes.POINTER(ctypes.c_uint64)]
     L.hs_last_kernel.argtypes = [vp]
     L.hs_last_kernel.restype = ctypes.c_char_p
     L.hs_set_capacity.argtypes = [vp, u32, u32]
@@ -174,6 +178,16 @@ def convert_slim_gpu(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_le
                                      top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, device, threads, out_path.encode(),
                                      ctypes.byref(used), ctypes.byref(ms)))
     return bool(used.value), ms.value
+
+
+def rows_representable(rows, fmt):
+    """hs_rows_representable (host only): None when every value of `rows` (n x dim fp32) is exactly representable in the row
+    format `fmt` (HS_ROWS_U8: integers 0..255; HS_ROWS_F16: finite fp16 values), else the index of the first row that is not."""
+    r = np.ascontiguousarray(rows, np.float32)
+    r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
+    bad = ctypes.c_uint64(0)
+    _check(lib().hs_rows_representable(r.ctypes.data, r.shape[0], r.shape[1], int(fmt), ctypes.byref(bad)))
+    return None if bad.value == r.shape[0] else int(bad.value)
 
 
 def debug_flat_plan(n, ef, nq):
@@ -429,6 +443,15 @@ class Index:
     def set_ef(self, ef):
         self.ef = int(ef)
         _check(lib().hs_set_ef(self._h, int(ef)))
+
+    def set_row_format(self, fmt):
+        """hs_index_set_row_format: HS_ROWS_U8 / HS_ROWS_F16 build a narrow copy of the rows that the flat kernel then reads
+        (HsError HS_ERR_UNSUPPORTED, index unchanged, when a stored value is not exactly representable); HS_ROWS_F32 drops it.
+        No answer changes."""
+        _check(lib().hs_index_set_row_format(self._h, int(fmt)))
+
+    def row_format(self):
+        return lib().hs_index_row_format(self._h)
 
     def set_exact_order(self, on=True):
         """True: strict kernel for every query (reference array order); False: fast kernel, sorted output."""

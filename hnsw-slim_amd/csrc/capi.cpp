@@ -19,6 +19,7 @@
 
 #include "../../include/hnsw_slim_amd.h"
 #include "engine.hpp"
+#include "narrow_rows.hpp"
 #define HS_HAVE_GPU_CONVERT 1
 #include "convert_engine.hpp"
 #include "host_graph.hpp"
@@ -90,6 +91,12 @@ struct hs_index {
   DevBuf<uint32_t> row_ptr0, cols, up_base, up_ptr, tile0, uptile;
   DevBuf<uint64_t> labels;
   DevBuf<uint8_t> deleted;
+  // narrow rows (hs_index_set_row_format): a u8 / fp16 copy of `vec` in the flat kernel's lane-major layout (narrow_rows.hip), sized
+  // like `vec` (row capacity x dim values); `vec` stays resident, every kernel but the flat one reads it
+  int row_fmt = ROWS_F32;
+  DevBuf<uint8_t> narrow;
+  DevBuf<uint32_t> narrow_bad;   // the conversion kernel's "first row that does not fit" word
+  size_t narrow_bytes = 0;       // part of info.device_bytes while the copy exists
   // per-stream scratch (grow-only): calls on different HIP streams may be in flight together
   struct StreamWs {
     DevBuf<uint32_t> spill;             // visited-set tier 2, nq x kSpillSlots
@@ -259,6 +266,47 @@ static hipError_t upload_cap(DevBuf<T> &b, const std::vector<T> &v, size_t cap) 
   return v.empty() ? hipSuccess : hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
+// ---- narrow rows ------------------------------------------------------------------------------------------------------------
+template <typename T>
+static size_t first_unfit(const float *x, size_t count) {
+  for (size_t i = 0; i < count; i++)
+    if (!narrow_fits<T>(x[i])) return i;
+  return count;
+}
+static size_t first_unfit(const float *x, size_t count, int fmt) {
+  return fmt == ROWS_U8 ? first_unfit<uint8_t>(x, count) : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : count;
+}
+static const char *row_format_name(int fmt) { return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : "HS_ROWS_F32"; }
+static std::string unfit_message(size_t row, size_t comp, float v, int fmt) {
+  char val[64];
+  snprintf(val, sizeof val, "%.9g", (double)v);
+  return "row " + std::to_string(row) + " holds " + val + " (component " + std::to_string(comp) + "), which " + row_format_name(fmt) +
+         " cannot represent exactly";
+}
+// bytes of the narrow copy: one value of the format per value of `vec`'s row capacity (documented in the header)
+static size_t narrow_copy_bytes(const hs_index *ix, int fmt) {
+  return std::max<size_t>(ix->cap_rows, ix->info.n) * ix->info.dim * narrow_width(fmt);
+}
+// Fills `out` (allocated here) with the narrow copy of all rows of ix->vec.  HS_ERR_UNSUPPORTED, `out` released, when a value does not fit.
+static hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out) {
+  const size_t n = ix->info.n, dim = ix->info.dim;
+  HIP_TRY(out.alloc(std::max<size_t>(narrow_copy_bytes(ix, fmt), 16)));
+  HIP_TRY(ix->narrow_bad.ensure(1));
+  uint32_t bad = 0xFFFFFFFFu;
+  HIP_TRY(hipMemcpy(ix->narrow_bad.p, &bad, 4, hipMemcpyHostToDevice));
+  HIP_TRY(launch_narrow_convert(ix->vec.p, out.p, fmt, 0, (uint32_t)n, (uint32_t)dim, ix->narrow_bad.p, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&bad, ix->narrow_bad.p, 4, hipMemcpyDeviceToHost));
+  if (bad != 0xFFFFFFFFu) {
+    out.release();
+    std::vector<float> row(dim);
+    HIP_TRY(hipMemcpy(row.data(), ix->vec.p + (size_t)bad * dim, dim * 4, hipMemcpyDeviceToHost));
+    const size_t j = std::min(first_unfit(row.data(), dim, fmt), dim - 1);
+    return fail(HS_ERR_UNSUPPORTED, unfit_message(bad, j, row[j], fmt));
+  }
+  return HS_OK;
+}
+
 extern "C" {
 
 const char *hs_last_error(void) { return g_err.c_str(); }
@@ -319,7 +367,7 @@ static hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   i.threshold_level = p.threshold_level; i.enterpoint = p.enterpoint; i.has_deleted = p.has_deleted;
   i.n_edges = p.cols.size(); i.max_degree0 = p.max_deg0; i.index_size = p.index_size;
   i.device_bytes = p.vec.size() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
-                   p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4;
+                   p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4 + ix->narrow_bytes;
   return HS_OK;
 }
 
@@ -521,6 +569,15 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
       if (nsz) r.bytes(rc.blob.data(), nsz);
       if (to_add && rc.is_new) { rc.vec.resize(dim * 4); r.bytes(rc.vec.data(), dim * 4); }
     }
+    // an index with narrow rows takes only rows its format represents (hs_index_set_row_format): checked on the staged records
+    if (ix->row_fmt != ROWS_F32)
+      for (const Rec &rc : recs) {
+        if (rc.vec.empty()) continue;
+        std::vector<float> v(dim);
+        memcpy(v.data(), rc.vec.data(), dim * 4);
+        const size_t j = first_unfit(v.data(), dim, ix->row_fmt);
+        if (j < dim) return fail(HS_ERR_UNSUPPORTED, "patch refused: " + unfit_message(rc.id, j, v[j], ix->row_fmt));
+      }
     g.elements.resize(new_count * spe, 0);
     g.blobs.resize(new_count);
     for (Rec &rc : recs) {
@@ -546,13 +603,19 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
   HIP_TRY(hipSetDevice(ix->device));
   HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
   const uint32_t stride = tile_stride_for(p.max_deg0);
-  if (stride != ix->dev.tile_stride || !ix->dev.tile0) return upload(ix, p);   // a list outgrew the tile stride: re-tile everything
+  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything
+    hs_status us = upload(ix, p);
+    if (us != HS_OK || ix->row_fmt == ROWS_F32) return us;
+    return build_narrow(ix, ix->row_fmt, ix->narrow);   // the fp32 rows were re-allocated: the narrow copy is rebuilt whole
+  }
   std::vector<uint32_t> row(stride);
   for (uint32_t id : changed) {
     std::fill(row.begin(), row.end(), 0xFFFFFFFFu);
     std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], row.begin());
     HIP_TRY(hipMemcpy(ix->tile0.p + (size_t)id * stride, row.data(), stride * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ix->vec.p + (size_t)id * dim, &p.vec[(size_t)id * dim], dim * 4, hipMemcpyHostToDevice));
+    if (ix->row_fmt != ROWS_F32)   // the same row of the narrow copy (its values were validated above)
+      HIP_TRY(launch_narrow_convert(ix->vec.p, ix->narrow.p, ix->row_fmt, id, 1, (uint32_t)dim, ix->narrow_bad.p, nullptr));
     HIP_TRY(hipMemcpy(ix->labels.p + id, &p.labels[id], 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ix->deleted.p + id, &p.deleted[id], 1, hipMemcpyHostToDevice));
   }
@@ -671,6 +734,37 @@ hs_status hs_index_info(const hs_index *ix, hs_info *out) {
   return HS_OK;
 }
 
+hs_status hs_index_set_row_format(hs_index *ix, int format) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
+  if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
+  if (format != ROWS_F32 && (ix->info.dim & 15) != 0)
+    return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(ix->info.dim) + ")");
+  if (format == ix->row_fmt) return HS_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
+  DevBuf<uint8_t> fresh;
+  if (format != ROWS_F32) {
+    hs_status s = build_narrow(ix, format, fresh);   // into a buffer of its own: a refusal leaves the index exactly as it was
+    if (s != HS_OK) return s;
+  }
+  ix->narrow.release();
+  std::swap(ix->narrow.p, fresh.p);
+  std::swap(ix->narrow.n, fresh.n);
+  ix->info.device_bytes -= ix->narrow_bytes;
+  ix->narrow_bytes = format == ROWS_F32 ? 0 : narrow_copy_bytes(ix, format);
+  ix->info.device_bytes += ix->narrow_bytes;
+  ix->row_fmt = format;
+  return HS_OK;
+}
+int hs_index_row_format(const hs_index *ix) { return ix ? ix->row_fmt : ROWS_F32; }
+hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad) {
+  if (!first_bad || (n && dim && !rows)) return fail(HS_ERR_INVALID, "null argument");
+  if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
+  *first_bad = dim ? first_unfit(rows, n * dim, format) / dim : n;
+  return HS_OK;
+}
+
 // One launch group serves at most kMaxLaunchQueries queries: the per-query scratch in global memory (96 KiB each) is
 // sized for that many, larger batches run as consecutive groups on the same stream (counters accumulate).
 static constexpr size_t kMaxLaunchQueries = 32768;
@@ -757,7 +851,9 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   static const bool flatk_off = kernel_env && (!strcmp(kernel_env, "lean") || !strcmp(kernel_env, "fast"));
   const FlatPlan fp = plan_flat(ix, sh.ef, nq);
   const bool flatk = !flatk_off && !lean_forced && fast && fp.ok && flatk_supported(ix->dev, sh.ef, (uint32_t)k);
-  ix->last_kernel = flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel" : fast ? "hs::fast_kernel" : "hs::strict_kernel";
+  const bool narrow = flatk && ix->row_fmt != ROWS_F32;   // the same launch plan over the narrow copy of the rows
+  auto flat_go = [&]() { return narrow ? launch_flatk_narrow(ix->dev, a, ix->narrow.p, ix->row_fmt, stream) : launch_flatk(ix->dev, a, stream); };
+  ix->last_kernel = narrow ? (ix->row_fmt == ROWS_U8 ? "hs::flat_kernel_u8" : "hs::flat_kernel_f16") : flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel" : fast ? "hs::fast_kernel" : "hs::strict_kernel";
   a.queue = w->counters.p + 12;
   a.counters = w->counters.p; a.pass_id = 0;
   static const int order_env = getenv("HS_ORDER") ? atoi(getenv("HS_ORDER")) : -1;   // diagnostic: 0 = never, 1 = always
@@ -771,13 +867,13 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
       HIP_TRY(w->order.ensure(nq));
       a.entry = reinterpret_cast<uint4 *>(w->entry.p); a.order = w->order.p;
       a.phase = 1;
-      HIP_TRY(launch_flatk(ix->dev, a, stream));
+      HIP_TRY(flat_go());
       HIP_TRY(launch_order(a.entry, w->order.p, (uint32_t)nq, stream));
       a.phase = 2;
-      HIP_TRY(launch_flatk(ix->dev, a, stream));
+      HIP_TRY(flat_go());
       a.phase = 0;
     } else {
-      HIP_TRY(launch_flatk(ix->dev, a, stream));
+      HIP_TRY(flat_go());
     }
     a.cand_cap = sh.cand_cap; a.hash_slots = sh.hash_slots; a.vis_bits = 0;
   } else if (lean) {

@@ -99,5 +99,12 @@ hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t str
 hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, uint2 *d_heap, uint2 *d_pops, uint32_t *d_n, int wave_pop,
                          uint32_t lds_slots, hipStream_t stream);
 hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
+// Narrow rows (narrow_rows.hip): `rows` = the index's u8 / fp16 copy of ix.vec in the lane-major layout, fmt = ROWS_U8 | ROWS_F16.
+// launch_flatk_narrow is launch_flatk reading that copy (kernels hs::flat_kernel_u8 / hs::flat_kernel_f16; same shapes, same plan).
+// launch_narrow_convert fills rows [row0, row0 + nrows) of the copy from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to
+// the smallest row that holds a value the format cannot represent.
+hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
+hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
+                                 hipStream_t stream);
 
 }  // namespace hs

@@ -114,9 +114,37 @@ __host__ __device__ constexpr int flat_waves(int s, int d16) {
 
 // One pass of distances: the 8 lanes of group g = lane >> 3 work on row `rowid`; the group's lane OWN (7 for L2, 0 for IP)
 // returns the distance in the reference's summation order (space_l2.h:36-51, space_ip.h:183-197); other lanes: unspecified.
-template <int METRIC, int D16>
-__device__ __forceinline__ float flat_dist8(const float *vec, uint32_t dim, const lds_u8 *qv, uint32_t rowid, int s) {
-  const hs_f2 *row = reinterpret_cast<const hs_f2 *>(vec + (size_t)rowid * dim) + s;
+//
+// ROW = float: the resident fp32 rows.  ROW = uint8_t / _Float16: the index's narrow copy (hs_index_set_row_format; layout and
+// conversion in narrow_rows.hip): row r is stored lane-major, narrow[r * dim + s * (dim / 8) + 2 i + e] = x[r][16 i + 2 s + e],
+// so lane s finds every element it works on in ONE contiguous chunk of dim / 8 values.  Element 16 i + 2 s + e still goes to
+// accumulator e of lane s in step order i, the value is widened exactly (every stored value is representable, that is what
+// the conversion checked), and the arithmetic below is the fp32 one: the distance has the same bits as from the fp32 row.
+template <typename ROW> struct RowKind { static constexpr bool narrow = true; };
+template <> struct RowKind<float> { static constexpr bool narrow = false; };
+typedef uint32_t hs_u4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t hs_u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef _Float16 hs_h2 __attribute__((ext_vector_type(2)));
+// element pair i of a lane's chunk, widened: a u8 pair is half a dword (v_cvt_f32_ubyteN), an f16 pair one dword (v_cvt_f32_f16)
+__device__ __forceinline__ hs_f2 narrow_pair(const uint8_t *, const uint32_t *dw, int i) {
+  const uint32_t w = dw[i >> 1] >> ((i & 1) * 16);
+  return hs_f2{(float)(w & 0xFFu), (float)((w >> 8) & 0xFFu)};
+}
+__device__ __forceinline__ hs_f2 narrow_pair(const _Float16 *, const uint32_t *dw, int i) {
+  const hs_h2 h = __builtin_bit_cast(hs_h2, dw[i]);
+  return hs_f2{(float)h.x, (float)h.y};
+}
+__device__ __forceinline__ hs_f2 narrow_pair_at(const uint8_t *chunk, uint32_t i) {
+  const uint32_t w = *reinterpret_cast<const unsigned short *>(chunk + 2 * i);
+  return hs_f2{(float)(w & 0xFFu), (float)(w >> 8)};
+}
+__device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t i) {
+  const hs_h2 h = *reinterpret_cast<const hs_h2 *>(chunk + 2 * i);
+  return hs_f2{(float)h.x, (float)h.y};
+}
+
+template <int METRIC, int D16, typename ROW>
+__device__ __forceinline__ float flat_dist8(const ROW *vec, uint32_t dim, const lds_u8 *qv, uint32_t rowid, int s) {
   const lds_f2 *qq = reinterpret_cast<const lds_f2 *>(qv) + s;
   hs_f2 acc = {0.f, 0.f};
   auto step = [&](const hs_f2 q2, const hs_f2 x) {
@@ -128,6 +156,48 @@ __device__ __forceinline__ float flat_dist8(const float *vec, uint32_t dim, cons
       acc = __builtin_elementwise_fma(q2, x, acc);
     }
   };
+  if constexpr (RowKind<ROW>::narrow) {
+    const ROW *chunk = vec + (size_t)rowid * dim + (uint32_t)s * (dim >> 3);
+    if constexpr (D16 > 0) {
+      // compile-time dim: the lane's whole chunk in flight (d = 128: one 16-byte load for u8, two for f16; d = 960: 30 / 60
+      // dwords, what the fp32 shape holds per round), as 16-byte loads with what is left over in 8 and 4 bytes.  A chunk starts
+      // s * dim / 8 elements into a 16-byte aligned row: dword aligned for every compiled-in dim, which is all these loads need.
+      constexpr int NDW = D16 * (int)sizeof(ROW) / 2;   // D16 pairs of 2 * sizeof(ROW) bytes
+      static_assert(D16 * sizeof(ROW) % 2 == 0, "a lane's chunk is a whole number of dwords");
+      const uint32_t *cp = reinterpret_cast<const uint32_t *>(chunk);
+      uint32_t dw[NDW];
+#pragma unroll
+      for (int j = 0; j + 4 <= NDW; j += 4) {
+        const hs_u4_a4 v = *reinterpret_cast<const hs_u4_a4 *>(cp + j);
+        dw[j] = v.x; dw[j + 1] = v.y; dw[j + 2] = v.z; dw[j + 3] = v.w;
+      }
+      if constexpr ((NDW & 2) != 0) {
+        const hs_u2_a4 v = *reinterpret_cast<const hs_u2_a4 *>(cp + (NDW & ~3));
+        dw[NDW & ~3] = v.x; dw[(NDW & ~3) + 1] = v.y;
+      }
+      if constexpr ((NDW & 1) != 0) dw[NDW - 1] = cp[NDW - 1];
+#pragma unroll
+      for (int i = 0; i < D16; i++) {
+        if (D16 > 8 && i % 8 == 0) __builtin_amdgcn_sched_barrier(0);   // (as for the fp32 rows: the query's LDS reads stay near their use)
+        step(qq[i * 8], narrow_pair((const ROW *)nullptr, dw, i));
+      }
+    } else {
+      // runtime dim: one element pair per load (2 / 4 bytes: the chunk of d = 16 is no longer than that), in rounds of 8 or 16
+      constexpr uint32_t RB = D16 == 0 ? 8u : 16u;
+      const uint32_t steps = dim >> 4;
+      for (uint32_t r0 = 0; r0 < steps; r0 += RB) {
+        const uint32_t nb = min(RB, steps - r0);
+        hs_f2 buf[RB];
+#pragma unroll
+        for (uint32_t i = 0; i < RB; i++)
+          if (i < nb) buf[i] = narrow_pair_at(chunk, r0 + i);
+#pragma unroll
+        for (uint32_t i = 0; i < RB; i++)
+          if (i < nb) step(qq[(r0 + i) * 8], buf[i]);
+      }
+    }
+  } else {
+  const hs_f2 *row = reinterpret_cast<const hs_f2 *>(vec + (size_t)rowid * dim) + s;
   if (D16 > 0) {
     // compile-time dim: the whole row in flight up to d = 128; longer rows in rounds of up to 32 eight-byte loads per lane.  d = 960
     // (two rounds of 30) is compiled for 2 wavefronts per SIMD (flat_waves()): with 256 VGPRs the compiler issues both rounds'
@@ -171,6 +241,7 @@ __device__ __forceinline__ float flat_dist8(const float *vec, uint32_t dim, cons
       for (uint32_t i = 0; i < RB; i++)
         if (i < nb) step(qq[(r0 + i) * 8], buf[i]);
     }
+  }
   }
   if (METRIC == METRIC_L2) {
     // ((a0 + a1) + a2) + ... + a15: lane s adds its two accumulators to the running sum of lane s - 1.  Every lane runs every
@@ -441,8 +512,8 @@ __device__ __forceinline__ uint32_t rank_id(const uint32_t (&ti)[S], uint32_t r)
   return v;
 }
 
-template <int METRIC, int S, int D16>
-__device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, lds_u8 *smem) {
+template <int METRIC, int S, int D16, typename ROW>
+__device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, lds_u8 *smem, const ROW *rows) {
   const int lane = threadIdx.x;
   constexpr int OWN = METRIC == METRIC_L2 ? 7 : 0;
   const int s8 = lane & 7, grp = lane >> 3;
@@ -534,7 +605,11 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       ovf_n += min(want, room);
       if (want > room) {   // the list is full: the rest (ids that are new by now) go to tier 2
         if (!v2.spilled) {
-          for (uint32_t i = lane; i < v2.slots2; i += 64) v2.t2[i] = kEmpty;
+          // (narrow kernels: the start index of this rare loop is kept out of the prologue -- hoisted there it is the one value the
+          //  d = 96 shapes spill; the fp32 kernels are compiled as they were)
+          uint32_t i0 = lane;
+          if constexpr (RowKind<ROW>::narrow) asm volatile("" : "+v"(i0));
+          for (uint32_t i = i0; i < v2.slots2; i += 64) v2.t2[i] = kEmpty;
           __threadfence_block();
           v2.spilled = true;
           if (lane == 0) atomicAdd(a.counters + 3, 1u);
@@ -560,7 +635,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
     n_nbr = n_dist - 1;
   } else {
     {
-      const float d = flat_dist8<METRIC, D16>(ix.vec, dim, qv, cur, s8);
+      const float d = flat_dist8<METRIC, D16>(rows, dim, qv, cur, s8);
       curdist = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(d), OWN));
     }
     uint32_t cur_b = ix.ep_base;
@@ -582,7 +657,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
         for (uint32_t base = 0; base < m; base += 8) {
           const uint32_t j = base + grp;
           const uint32_t rid = __shfl(pr.x, (int)(j < m ? j : base), 64);
-          const float d = flat_dist8<METRIC, D16>(ix.vec, dim, qv, rid, s8);
+          const float d = flat_dist8<METRIC, D16>(rows, dim, qv, rid, s8);
           const int ky = (s8 == OWN && j < m) ? dkey<METRIC>(d) : INT_MAX;
           const int mn = wave_min_i32_f(ky);
           if (mn < best_key) {
@@ -753,7 +828,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       const uint32_t j = base + grp;
       const bool act = j < cnt;
       const uint32_t rid = nid[act ? j : base];   // idle groups re-read the pass's first row (cache hit) and discard
-      const float d = flat_dist8<METRIC, D16>(ix.vec, dim, qv, rid, s8);   // :395-396
+      const float d = flat_dist8<METRIC, D16>(rows, dim, qv, rid, s8);   // :395-396
       const int my_key = (s8 == OWN && act) ? dkey<METRIC>(d) : kFKeyInf;
 #ifdef HS_FLAT_DIAG
       asm volatile("s_nop 0" : : "v"(my_key) : "memory");
@@ -960,48 +1035,73 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
   return 0;
 }
 
+// The three entry points differ in the rows they read and in nothing else: hs::flat_kernel the resident fp32 rows (ix.vec),
+// hs::flat_kernel_u8 / hs::flat_kernel_f16 the index's narrow copy (hs_index_set_row_format), each compiled as objects of its own
+// (HS_TU_ROWS = 0 | 1 | 2 beside HS_TU_METRIC: Makefile) so that a kernel trace shows them as separate rows.
+#define HS_FLAT_KERNEL_BODY(ROWS)                                                                                        \
+  extern __shared__ __align__(16) unsigned char smem_raw[];                                                              \
+  lds_u8 *smem = (lds_u8 *)smem_raw;                                                                                     \
+  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {                                                           \
+    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;                                                    \
+    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;   /* pass 0 takes every query */            \
+    const int rc = search_one_flat<METRIC, S, D16>(ix, a, qi, smem, ROWS);                                               \
+    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;                                                           \
+    wave_sync();                                                                                                         \
+  }
+#if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
 template <int METRIC, int S, int D16>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel(DevIndex ix, SearchArgs a) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  lds_u8 *smem = (lds_u8 *)smem_raw;
-  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {
-    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;
-    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;   // pass 0 takes every query
-    const int rc = search_one_flat<METRIC, S, D16>(ix, a, qi, smem);
-    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;
-    wave_sync();
-  }
+  HS_FLAT_KERNEL_BODY(ix.vec)
 }
+#define HS_FLAT_KERNEL flat_kernel
+#define HS_FLAT_ROWS_ARG
+#elif HS_TU_ROWS == 1
+template <int METRIC, int S, int D16>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
+  HS_FLAT_KERNEL_BODY(rows)
+}
+#define HS_FLAT_KERNEL flat_kernel_u8
+#define HS_FLAT_ROWS_ARG , reinterpret_cast<const uint8_t *>(rows)
+#else
+template <int METRIC, int S, int D16>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
+  HS_FLAT_KERNEL_BODY(rows)
+}
+#define HS_FLAT_KERNEL flat_kernel_f16
+#define HS_FLAT_ROWS_ARG , reinterpret_cast<const _Float16 *>(rows)
+#endif
 
-template <typename K>
-static hipError_t flat_launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
+// (`rows`: the narrow copy, nullptr in the fp32 objects)
+template <typename K, typename... R>
+static hipError_t flat_launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, R... rows) {
   if (a.nq == 0) return hipSuccess;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a);
+  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a, rows...);
   return hipGetLastError();
 }
 template <int METRIC, int D16>
-static hipError_t flat_launch_d(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+static hipError_t flat_launch_d(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) {
   const size_t lds = flat_layout(ix.dim, a.ef, a.fl_nb).total;
-  if (a.ef <= 64) return flat_launch(flat_kernel<METRIC, 1, D16>, ix, a, lds, stream);
-  if (a.ef <= 128) return flat_launch(flat_kernel<METRIC, 2, D16>, ix, a, lds, stream);
-  if (a.ef <= 192) return flat_launch(flat_kernel<METRIC, 3, D16>, ix, a, lds, stream);   // (three slots instead of four: ef = 160 +5.5 %, 192 +3.5 %)
-  if (a.ef <= 256) return flat_launch(flat_kernel<METRIC, 4, D16>, ix, a, lds, stream);
-  if (a.ef <= 384) return flat_launch(flat_kernel<METRIC, 6, D16>, ix, a, lds, stream);
-  return flat_launch(flat_kernel<METRIC, 8, D16>, ix, a, lds, stream);
+  if (a.ef <= 64) return flat_launch(HS_FLAT_KERNEL<METRIC, 1, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
+  if (a.ef <= 128) return flat_launch(HS_FLAT_KERNEL<METRIC, 2, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
+  if (a.ef <= 192) return flat_launch(HS_FLAT_KERNEL<METRIC, 3, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);   // (three slots instead of four: ef = 160 +5.5 %, 192 +3.5 %)
+  if (a.ef <= 256) return flat_launch(HS_FLAT_KERNEL<METRIC, 4, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
+  if (a.ef <= 384) return flat_launch(HS_FLAT_KERNEL<METRIC, 6, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
+  return flat_launch(HS_FLAT_KERNEL<METRIC, 8, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
 }
 template <int METRIC>
-static hipError_t flat_launch_s(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
-  if (ix.dim == 128) return flat_launch_d<METRIC, 8>(ix, a, stream);
-  if (ix.dim == 96) return flat_launch_d<METRIC, 6>(ix, a, stream);
-  if (ix.dim == 960) return flat_launch_d<METRIC, 60>(ix, a, stream);
-  if (ix.dim > 256) return flat_launch_d<METRIC, -1>(ix, a, stream);
-  return flat_launch_d<METRIC, 0>(ix, a, stream);
+static hipError_t flat_launch_s(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) {
+  if (ix.dim == 128) return flat_launch_d<METRIC, 8>(ix, a, rows, stream);
+  if (ix.dim == 96) return flat_launch_d<METRIC, 6>(ix, a, rows, stream);
+  if (ix.dim == 960) return flat_launch_d<METRIC, 60>(ix, a, rows, stream);
+  if (ix.dim > 256) return flat_launch_d<METRIC, -1>(ix, a, rows, stream);
+  return flat_launch_d<METRIC, 0>(ix, a, rows, stream);
 }
 
+#if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
 // Parity/debug: a sequence of candidate_set operations through this file's heap code (one wavefront; 1024 slots in LDS, the rest
 // in `spill`).  ops: 3 words each {0 = push | 1 = pop, key bits, id}; out_heap: the final array (2 words per element); out_pops:
 // the root each pop removed; out_n[0] = final size, out_n[1] = pops.
@@ -1055,13 +1155,28 @@ uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef) {
   return 4u * (uint32_t)flat_waves(s, d16);
 }
 size_t flatk_lds_bytes(uint32_t dim, uint32_t ef, uint32_t nb) { return flat_layout(dim, ef, nb).total; }
-hipError_t launch_flatk_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, stream); }
+hipError_t launch_flatk_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, nullptr, stream); }
 hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
   return ix.metric == METRIC_L2 ? launch_flatk_l2(ix, a, stream) : launch_flatk_ip(ix, a, stream);
 }
 #endif
 #if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
-hipError_t launch_flatk_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, stream); }
+hipError_t launch_flatk_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, nullptr, stream); }
+#endif
+#elif HS_TU_ROWS == 1   // the narrow objects: one launcher per metric (dispatch: narrow_rows.hip launch_flatk_narrow)
+#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+hipError_t launch_flatk_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, rows, stream); }
+#endif
+#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
+hipError_t launch_flatk_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, rows, stream); }
+#endif
+#else
+#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+hipError_t launch_flatk_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, rows, stream); }
+#endif
+#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
+hipError_t launch_flatk_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, rows, stream); }
+#endif
 #endif
 
 }  // namespace hs

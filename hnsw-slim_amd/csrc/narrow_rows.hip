@@ -1,0 +1,51 @@
+// narrow_rows.hip -- the narrow copy of an index's rows (hs_index_set_row_format): layout, device conversion with the
+// representability check, and the dispatch to the flat kernel's narrow entry points (flat_search_u8.hip / flat_search_f16.hip).
+//
+// Layout (narrow_rows.hpp narrow_slot): row r occupies dim elements at r * dim, lane-major for the flat kernel's 8 lanes per row,
+//   narrow[r * dim + s * (dim / 8) + 2 i + e] = x[r][16 i + 2 s + e]      s = 0..7, i = 0..dim/16 - 1, e = 0..1
+// so the elements lane s multiplies (flat_search.hip flat_dist8) are one contiguous chunk.  dim % 16 == 0, so a u8 row is a
+// multiple of 16 bytes and every row starts 16-byte aligned.
+#include <hip/hip_runtime.h>
+
+#include "engine.hpp"
+#include "narrow_rows.hpp"
+
+namespace hs {
+
+// One thread per element of rows [row0, row0 + nrows): writes the narrow value at its lane-major slot and, where the fp32 value
+// does not survive the round trip, lowers *first_bad to its row (an ordinary vector atomic min).
+template <typename T>
+__global__ void __launch_bounds__(256) narrow_convert_kernel(const float *vec, T *out, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *first_bad) {
+  const uint64_t total = (uint64_t)nrows * dim;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t r = row0 + (uint32_t)(t / dim), j = (uint32_t)(t % dim);
+    const float x = vec[(size_t)r * dim + j];
+    out[(size_t)r * dim + narrow_slot(j, dim)] = narrow_cast<T>(x);
+    if (!narrow_fits<T>(x)) atomicMin(first_bad, r);
+  }
+}
+
+template <typename T>
+static hipError_t convert_t(const float *d_vec, void *d_out, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad, hipStream_t stream) {
+  const uint64_t total = (uint64_t)nrows * dim;
+  if (total == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256u * 64u);
+  hipLaunchKernelGGL(narrow_convert_kernel<T>, dim3(grid), dim3(256), 0, stream, d_vec, reinterpret_cast<T *>(d_out), row0, nrows, dim, d_first_bad);
+  return hipGetLastError();
+}
+hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
+                                 hipStream_t stream) {
+  return fmt == ROWS_U8 ? convert_t<uint8_t>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream)
+                        : convert_t<_Float16>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream);
+}
+
+hipError_t launch_flatk_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
+hipError_t launch_flatk_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
+hipError_t launch_flatk_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
+hipError_t launch_flatk_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
+hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream) {
+  if (fmt == ROWS_U8) return ix.metric == 0 ? launch_flatk_u8_l2(ix, a, rows, stream) : launch_flatk_u8_ip(ix, a, rows, stream);
+  return ix.metric == 0 ? launch_flatk_f16_l2(ix, a, rows, stream) : launch_flatk_f16_ip(ix, a, rows, stream);
+}
+
+}  // namespace hs

@@ -121,6 +121,7 @@ class DeviceIndex {
   std::vector<int> devices_;
   std::vector<hs_index *> replicas_;
   hs_comm *comm_ = nullptr;
+  hs_row_format row_fmt_ = HS_ROWS_F32;   // what setRowFormat asked for: applied to every index this object loads
   void free_replicas() {
     for (size_t r = 1; r < replicas_.size(); r++) hs_index_free(replicas_[r]);
     replicas_.clear();
@@ -145,6 +146,16 @@ class DeviceIndex {
     if (h_) check(hs_set_ef(h_, ef));
     for (size_t r = 1; r < replicas_.size(); r++) check(hs_set_ef(replicas_[r], ef));
   }
+  // Narrow rows (hs_index_set_row_format; no counterpart in the reference): the flat kernel reads a u8 / fp16 copy of the rows.
+  // The data must be representable exactly (integers 0..255 / values already rounded to fp16), and then no answer changes;
+  // otherwise std::runtime_error with the C ABI's message and the index stays as it was.  Holds for later loads of this object too
+  // (an index that is built on first use gets it after that build).
+  void setRowFormat(hs_row_format f) {
+    if (h_) check(hs_index_set_row_format(h_, f));
+    for (size_t r = 1; r < replicas_.size(); r++) check(hs_index_set_row_format(replicas_[r], f));
+    row_fmt_ = f;
+  }
+  hs_row_format rowFormat() const { return h_ ? (hs_row_format)hs_index_row_format(h_) : row_fmt_; }
   bool sharded() const { return comm_ != nullptr; }
   hs_index *handle() const { return h_; }
   const std::string &path() const { return path_; }
@@ -183,6 +194,7 @@ class DeviceIndex {
       check(hs_comm_init((int)devices_.size(), devices_.data(), &comm_));
     }
     ef_ = 10;  // hnswalg.h:864, hnswalg_slim.h:793
+    if (row_fmt_ != HS_ROWS_F32) setRowFormat(row_fmt_);
   }
   mutable BaseFilterFunctor *cached_filter_ = nullptr;
   mutable std::vector<uint8_t> allowed_;
@@ -459,6 +471,7 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   }
   void setDataset(const float *rows, size_t n, size_t d) { detail::check(hs_slimq_set_dataset(h_, rows, n, d)); }
   void setTConst(double t) { detail::check(hs_slimq_set_tconst(h_, t)); }
+  void setRowFormat(hs_row_format) { throw std::runtime_error("narrow rows: a SlimQ index has no flat-kernel rows"); }
   void addPoint(const void *, labeltype, bool = false) override {
     throw std::runtime_error("HierarchicalNSWSlimQ does not support addPoint");  // hnswalg_slimq.h:298-301
   }

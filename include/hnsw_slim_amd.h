@@ -91,6 +91,26 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
  * vectors and level-0 tiles are rewritten in HBM; the small structure arrays are rebuilt.  Like the reference, the stream
  * does not move the enter point.  Not to be called while a search on this index is in flight. */
 hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add);
+/* ---- narrow rows (no counterpart in the reference) -------------------------------------------------------------------
+ * Besides the resident fp32 rows an index can hold a u8 or fp16 copy of them, and the flat kernel -- the default kernel of every
+ * bare index -- then reads that copy (hs::flat_kernel_u8 / hs::flat_kernel_f16) and a quarter / half of the row bytes.  The copy must
+ * represent every stored value exactly: u8 -> fp32 and fp16 -> fp32 are exact, the query stays fp32 and the distance is the same
+ * fp32 recipe in the same order, so distances, labels, counters and tie behaviour are bit-identical to HS_ROWS_F32.  It is an
+ * explicit call because it is a contract on the data: it costs device memory (one value of the format per value of the fp32 array's
+ * row capacity: max(n, max_elements) x dim x 1 or 2 bytes, included in hs_info.device_bytes while it exists) and a later
+ * hs_index_patch may only add representable rows (HS_ERR_UNSUPPORTED otherwise, index untouched).  Every other kernel (strict /
+ * fast: filters, delete marks, exact order, ef > 512, the re-run pass, hs_search_batch_raw) keeps reading the fp32 rows. */
+typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2 } hs_row_format;
+/* Builds (or, for HS_ROWS_F32, drops) the narrow copy of the rows on the index's device.  Not to be called while a search on this
+ * index is in flight (as hs_index_patch).  HS_ERR_UNSUPPORTED, index left exactly as it was, when a stored value is not
+ * representable (the message names the first offending row and the value), for a SlimQ index, and for dim % 16 != 0 (the flat
+ * kernel does not serve those). */
+hs_status hs_index_set_row_format(hs_index *ix, int format);
+int hs_index_row_format(const hs_index *ix);
+/* Host only, no device: *first_bad = n when every value of rows[n x dim] is representable in `format`, else the index of the
+ * first row that is not.  Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255 (and -0.0f, read back
+ * as +0.0f, which cannot change a distance); fp16: every finite fp16 value, subnormals included. */
+hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad);
 void hs_index_free(hs_index *ix);                        /* ~HierarchicalNSW* / clear(): hnswalg_slim.h:154-167 */
 hs_status hs_set_ef(hs_index *ix, size_t ef);            /* setEf: hnswalg.h:184, hnswalg_slim.h:193 */
 hs_status hs_index_info(const hs_index *ix, hs_info *out);
