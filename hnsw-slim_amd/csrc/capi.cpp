@@ -792,12 +792,10 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   // (status needs no clearing: pass 0 takes every query and writes each one's final status)
   // counters[0..12): per-pass overflow / hazard counts.  They are STICKY: they accumulate over the launch groups of a call and
   // over every call issued on this stream until hs_search_check reads and clears them, so a capacity failure in any batch of
-  // a pipelined sequence is reported by the check that follows it.  [12]: the group kernel's query queue head (per launch group)
+  // a pipelined sequence is reported by the check that follows it.
   if (w->counters.n < 48) {
     HIP_TRY(w->counters.ensure(48));
     HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(w->counters.p + 12, 0, sizeof(uint32_t), stream));
   }
   if (first_group) w->last_nq += nq_total;   // queries since the last hs_search_check on this stream
   SearchArgs a{};
@@ -854,7 +852,6 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   const bool narrow = flatk && ix->row_fmt != ROWS_F32;   // the same launch plan over the narrow copy of the rows
   auto flat_go = [&]() { return narrow ? launch_flatk_narrow(ix->dev, a, ix->narrow.p, ix->row_fmt, stream) : launch_flatk(ix->dev, a, stream); };
   ix->last_kernel = narrow ? (ix->row_fmt == ROWS_U8 ? "hs::flat_kernel_u8" : "hs::flat_kernel_f16") : flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel" : fast ? "hs::fast_kernel" : "hs::strict_kernel";
-  a.queue = w->counters.p + 12;
   a.counters = w->counters.p; a.pass_id = 0;
   static const int order_env = getenv("HS_ORDER") ? atoi(getenv("HS_ORDER")) : -1;   // diagnostic: 0 = never, 1 = always
   const bool ordered = fast && (order_env < 0 ? nq >= kOrderMinQueries : order_env != 0);

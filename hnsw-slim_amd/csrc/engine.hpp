@@ -52,7 +52,6 @@ struct SearchArgs {
   uint32_t *status;      // nq
   uint32_t *counters;    // [0] visited-set overflows, [1] candidate-heap overflows, [2] tie hazards, [3] tier-2 spills (this pass)
   uint32_t pass_id;
-  uint32_t *queue;       // device-wide work counter (unused by the shipped kernels; zeroed per launch group)
   uint32_t hash_fill_shift;   // visited-set tier 1 is frozen at 1 - 2^-shift of its slots (0 = the default 2: 75 %)
   uint32_t flat;         // fast kernel: start the level-0 search without the candidate heap (beam_search.hip, FLAT)
   uint32_t hop_cap;      // bytes of the per-expansion accept counts behind the insertion log (one per expansion of the flat start)

@@ -3,7 +3,8 @@
 // matter, and with the heap brought up to date from a log exactly when it can.
 //
 //   * Result set = top_candidates as a SORTED register array of (key, id | expanded-flag), rank r in lane r / S, slot r % S
-//     (interleaved: inserting at rank p is one DPP wave_shr:1 plus per-slot selects, no carries between slots).
+//     (interleaved: an insertion is one DPP wave_shr:1 plus per-slot selects, no carries between slots, and no lane needs to
+//     know the rank the new entry lands on: sorted_insert.hpp).
 //   * With no delete marks every accepted neighbour enters the result set, so the entries of candidate_set that the reference
 //     can still pop (key <= lowerBound) are exactly the unexpanded entries of the result set -- plus, while lowerBound does
 //     not move, unexpanded entries that were evicted at a key EQUAL to it ("ghosts").  The reference pops the minimum of
@@ -37,6 +38,7 @@
 #include "engine.hpp"
 #include "heap_emul.hpp"
 #include "search_common.hpp"
+#include "sorted_insert.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
@@ -500,17 +502,6 @@ __device__ __forceinline__ int rank_key(const int (&tk)[S], uint32_t r) {   // k
   }
   return v;
 }
-template <int S>
-__device__ __forceinline__ uint32_t rank_id(const uint32_t (&ti)[S], uint32_t r) {
-  const uint32_t l = r / S, sl = r % S;
-  uint32_t v = __builtin_amdgcn_readlane(ti[0], l);
-#pragma unroll
-  for (int s = 1; s < S; s++) {
-    const uint32_t t = __builtin_amdgcn_readlane(ti[s], l);
-    v = sl == (uint32_t)s ? t : v;
-  }
-  return v;
-}
 
 template <int METRIC, int S, int D16, typename ROW>
 __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, lds_u8 *smem, const ROW *rows) {
@@ -717,6 +708,17 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
   const uint32_t stride = ix.tile_stride;
   int rc = vfail ? 1 : 0;
 
+  // lowerBound = key of rank ef - 1.  The rank does not move during a query: its lane and slot are chosen here, once.
+  const uint32_t lb_lane = (ef - 1) / S, lb_slot = (ef - 1) % S;
+  auto bound_key = [&]() -> int {
+    int v = __builtin_amdgcn_readlane(tk[0], lb_lane);
+#pragma unroll
+    for (int s = 1; s < S; s++) {
+      const int t = __builtin_amdgcn_readlane(tk[s], lb_lane);
+      v = lb_slot == (uint32_t)s ? t : v;
+    }
+    return v;
+  };
   // nearest unexpanded entry of the result set (ranks < ef): {found, its lane and slot, key, id, how many unexpanded entries share the key}
   struct Near { bool any; int p, slot, key; uint32_t id, same; };
   auto nearest = [&]() -> Near {
@@ -868,6 +870,12 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
         if (have_pre && (uint32_t)lane < stride) pre_tile = ix.tile0[(size_t)pre_id * stride + lane];
       }
       // ---- accept (:403-452), adjacency order (= lane order of the owner lanes).  lowerBound only falls.
+      // The insertion itself is sorted_insert.hpp: every lane rewrites its own slots from the new key and the entry one rank below;
+      // nobody computes the rank the new entry lands on.
+      // (Rows of d = 960 keep the rank path -- ballots, population counts, two v_writelane: their kernels run two waves per SIMD
+      //  on 256 registers with a 30..60-deep load buffer, and five of those 36 shapes pay for the rank-free form's per-slot compare
+      //  masks with 4..8 more bytes of scratch per lane; the accept pass is a small share of a hop of theirs.)
+      constexpr bool kRankFree = D16 <= 8;
       unsigned long long todo = hs_ballot(my_key < lb);
       unsigned long long am = 0;
       while (todo) {
@@ -877,40 +885,47 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
         if (kj < lb) {
           const uint32_t idj = __builtin_amdgcn_readlane(rid, jl) | (jl == b_lane ? kFDone : 0u);   // (the chosen one enters flagged)
           am |= 1ull << jl;
-          uint32_t pos = 0;   // entries with key <= kj stay in front
-#pragma unroll
-          for (int s = 0; s < S; s++) pos += __popcll(hs_ballot(tk[s] <= kj));
-          // without spare ranks behind ef - 1 the entry this insertion pushes out is gone at once: look at it now
-          // (with spare ranks the evicted entries stay in the array and are looked at once per hop, below)
           const int ek = lb;
-          uint32_t ei = 0;
-          if (exact_fit) ei = rank_id<S>(ti, ef - 1);
-          const int upk = __builtin_amdgcn_update_dpp(0, tk[S - 1], 0x138, 0xf, 0xf, false);   // wave_shr:1
+          const uint32_t ei = __builtin_amdgcn_readlane(ti[S - 1], 63);   // (read by the exact-fit case below, before the insertion)
+          const int upk = __builtin_amdgcn_update_dpp(kInsertKeyMin, tk[S - 1], 0x138, 0xf, 0xf, false);   // wave_shr:1
           const uint32_t upi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ti[S - 1], 0x138, 0xf, 0xf, false);
+          if constexpr (kRankFree) {
+            sorted_insert_lane<S>(tk, ti, upk, upi, kj, idj);
+          } else {
+            uint32_t pos = 0;   // entries with key <= kj stay in front
 #pragma unroll
-          for (int s = S - 1; s >= 1; s--) {
-            const bool gt = (uint32_t)(laneS + s) > pos;
-            tk[s] = gt ? tk[s - 1] : tk[s];
-            ti[s] = gt ? ti[s - 1] : ti[s];
-          }
-          {
-            const bool gt = (uint32_t)laneS > pos;
-            tk[0] = gt ? upk : tk[0];
-            ti[0] = gt ? upi : ti[0];
-          }
-          {   // the new entry: one v_writelane per register, in the slot the rank falls in
-            const uint32_t pl = pos / S, ps = pos % S;
+            for (int s = 0; s < S; s++) pos += __popcll(hs_ballot(tk[s] <= kj));
 #pragma unroll
-            for (int s = 0; s < S; s++)
-              if (ps == (uint32_t)s) {
-                tk[s] = (int)write_lane((uint32_t)tk[s], (uint32_t)kj, pl);
-                ti[s] = write_lane(ti[s], idj, pl);
-              }
+            for (int s = S - 1; s >= 1; s--) {
+              const bool gt = (uint32_t)(laneS + s) > pos;
+              tk[s] = gt ? tk[s - 1] : tk[s];
+              ti[s] = gt ? ti[s - 1] : ti[s];
+            }
+            {
+              const bool gt = (uint32_t)laneS > pos;
+              tk[0] = gt ? upk : tk[0];
+              ti[0] = gt ? upi : ti[0];
+            }
+            {   // the new entry: one v_writelane per register, in the slot the rank falls in
+              const uint32_t pl = pos / S, ps = pos % S;
+#pragma unroll
+              for (int s = 0; s < S; s++)
+                if (ps == (uint32_t)s) {
+                  tk[s] = (int)write_lane((uint32_t)tk[s], (uint32_t)kj, pl);
+                  ti[s] = write_lane(ti[s], idj, pl);
+                }
+            }
           }
-          lb = rank_key<S>(tk, ef - 1);   // :450-452
-          if (exact_fit && ek != kFKeyInf && lb == ek) {   // an entry left the set at exactly the new bound
-            btie = true;
-            if ((int)ei >= 0) ghost_key = ek;   // ... unexpanded: the reference may still pop it
+          lb = bound_key();   // :450-452
+          // Without spare ranks behind ef - 1 the entry this insertion pushed out (rank ef - 1 = lane 63, slot S - 1) is gone at
+          // once: it is looked at here.  (With spare ranks the evicted entries stay in the array and are looked at once per hop,
+          // below.)  A branch of its own, taken by the few sets with ef == 64 S: as one condition among the others the compiler
+          // evaluates all of this with scalar selects on every insertion of every set.
+          if (__builtin_expect(exact_fit, 0)) {
+            if (ek != kFKeyInf && lb == ek) {   // an entry left the set at exactly the new bound
+              btie = true;
+              if ((int)ei >= 0) ghost_key = ek;   // ... unexpanded: the reference may still pop it
+            }
           }
         }
       }
