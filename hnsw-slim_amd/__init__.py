@@ -29,6 +29,7 @@ EXPORTS = [
     "hs_search_batch_async", "hs_host_alloc", "hs_host_free", "hs_comm_init", "hs_comm_free", "hs_comm_size", "hs_search_batch_sharded",
     "hs_comm_results_dev", "hs_convert_slim_gpu", "hs_index_patch", "hs_index_from_host_arrays", "hs_build_rabitq_hnsw",
     "hs_convert_slimq_graph", "hs_host_device_pointer", "hs_index_set_row_format", "hs_index_row_format", "hs_rows_representable",
+    "hs_index_set_f32_resident", "hs_index_f32_resident", "hs_rows_to_narrow", "hs_index_load_narrow",
 ]
 
 
@@ -77,6 +78,10 @@ def lib():
     L.hs_index_set_row_format.argtypes = [vp, ci]
     L.hs_index_row_format.argtypes = [vp]
     L.hs_rows_representable.argtypes = [vp, sz, sz, ci, ctypes.POINTER(ctypes.c_uint64)]
+    L.hs_index_set_f32_resident.argtypes = [vp, ci]
+    L.hs_index_f32_resident.argtypes = [vp]
+    L.hs_rows_to_narrow.argtypes = [vp, sz, sz, ci, vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.hs_index_load_narrow.argtypes = [ctypes.c_char_p, ci, ci, sz, sz, ci, ci, ctypes.POINTER(vp)]
     L.hs_last_kernel.argtypes = [vp]
     L.hs_last_kernel.restype = ctypes.c_char_p
     L.hs_set_capacity.argtypes = [vp, u32, u32]
@@ -188,6 +193,22 @@ def rows_representable(rows, fmt):
     bad = ctypes.c_uint64(0)
     _check(lib().hs_rows_representable(r.ctypes.data, r.shape[0], r.shape[1], int(fmt), ctypes.byref(bad)))
     return None if bad.value == r.shape[0] else int(bad.value)
+
+
+def rows_to_narrow(rows, fmt, out=None):
+    """hs_rows_to_narrow (host only): `rows` (n x dim fp32, dim % 16 == 0) in the row format `fmt` and the lane-major layout of the
+    device copy -- (narrow, first_bad): narrow is n x dim uint8 (HS_ROWS_U8) or float16 (HS_ROWS_F16), first_bad None when every
+    value is representable, else the first row that is not (nothing is written from there on; `out`, when given, is the array
+    that is filled)."""
+    r = np.ascontiguousarray(rows, np.float32)
+    r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
+    dt = np.uint8 if int(fmt) == HS_ROWS_U8 else np.float16
+    if out is None:
+        out = np.zeros(r.shape, dt)
+    assert out.dtype == dt and out.shape == r.shape and out.flags.c_contiguous
+    bad = ctypes.c_uint64(0)
+    _check(lib().hs_rows_to_narrow(r.ctypes.data, r.shape[0], r.shape[1], int(fmt), out.ctypes.data, ctypes.byref(bad)))
+    return out, (None if bad.value == r.shape[0] else int(bad.value))
 
 
 def debug_flat_plan(n, ef, nq):
@@ -385,6 +406,16 @@ class Index:
             _check(lib().hs_index_load(path.encode(), kind, metric, dim, max_elements, device, ctypes.byref(self._h)))
 
     @classmethod
+    def load_narrow(cls, path, kind, dim, fmt, metric=HS_METRIC_L2, max_elements=0, device=0):
+        """hs_index_load_narrow: the index of `path` with its rows on the device in `fmt` (HS_ROWS_U8 / HS_ROWS_F16) only -- what
+        Index(path, ...) + set_row_format(fmt) + set_f32_resident(False) gives, without the fp32 array ever being allocated."""
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        self.kind, self.dim, self.metric, self.device, self.ef = kind, dim, metric, device, 10
+        _check(lib().hs_index_load_narrow(path.encode(), kind, metric, dim, max_elements, device, int(fmt), ctypes.byref(self._h)))
+        return self
+
+    @classmethod
     def from_arrays(cls, kind, metric, vectors, levels, lists, enterpoint, maxlevel, labels=None, deleted=None, threshold_level=0, device=0):
         """hs_index_from_host_arrays: lists[i][l] = neighbour ids of node i at level l (l = 0..levels[i])."""
         v = np.ascontiguousarray(vectors, np.float32)
@@ -452,6 +483,15 @@ class Index:
 
     def row_format(self):
         return lib().hs_index_row_format(self._h)
+
+    def set_f32_resident(self, on):
+        """hs_index_set_f32_resident: False frees the fp32 rows of an index in a narrow row format -- every search kernel then reads
+        the narrow copy (hs::flat_kernel_u8, hs::fast_kernel_u8, hs::strict_kernel_u8, ...) -- True re-creates them from it.
+        No answer changes."""
+        _check(lib().hs_index_set_f32_resident(self._h, 1 if on else 0))
+
+    def f32_resident(self):
+        return bool(lib().hs_index_f32_resident(self._h))
 
     def set_exact_order(self, on=True):
         """True: strict kernel for every query (reference array order); False: fast kernel, sorted output."""

@@ -44,6 +44,7 @@
 #include "dist_recipe.hpp"
 #include "engine.hpp"
 #include "heap_emul.hpp"
+#include "narrow_load.hpp"
 #include "search_common.hpp"
 #include "wave_util.hpp"
 
@@ -91,7 +92,12 @@ __host__ __device__ inline FastLds fast_layout(uint32_t dim, uint32_t ef, uint32
 #define HS_TU_HAS_L2 0
 #define HS_TU_HAS_IP 1
 #endif
-#if HS_TU_HAS_L2
+// HS_TU_ROWS = 1 | 2 (beam_search_u8.hip / beam_search_f16.hip): the same kernels over the index's narrow copy of the rows, as
+// objects of their own per row format and metric; those hold the narrow entry points and nothing else.
+#if !defined(HS_TU_ROWS)
+#define HS_TU_ROWS 0
+#endif
+#if HS_TU_HAS_L2 && HS_TU_ROWS == 0
 size_t strict_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots) {
   return strict_layout(dim, ef, cand_cap, hash_slots).total;
 }
@@ -141,11 +147,54 @@ __host__ __device__ constexpr int deep_buffer(int d16) {
 
 // TO_REG: instead of writing nd[j], hand the value of row j to lane j in a register (one cross-lane move,
 // no LDS write/read round trip); returned value is meaningful in lanes < cnt.
-template <int METRIC, int D16 = 0, class Hook = NoHook, bool TO_REG = false>
+// ROW = uint8_t / _Float16 (rs.p = the index's narrow copy, narrow_rows.hip): lane `sub` owns elements 16 i + 4 sub .. + 3 of
+// every step i, which in the lane-major layout are the chunks s = 2 sub (acc[0], acc[1]) and s = 2 sub + 1 (acc[2], acc[3]) --
+// two runs of dim / 8 values that lie one behind the other at row * dim + sub * (dim / 4).  A round takes eight steps of each
+// chunk: one 16-byte load per chunk for u8, two for fp16, where the chunk is dword aligned (fp16 always, u8 when dim / 16 is
+// even); what is left of a chunk after the full rounds goes four pairs per load, then pair by pair (NarrowRound, narrow_load.hpp).
+// Element 16 i + 2 s + e still reaches accumulator 2 (s & 1) + e of lane s / 2 in step order i, widened exactly, and step4 /
+// lane4_reduce are the fp32 ones: the distance has the bits it has from the fp32 row.
+template <int METRIC, int D16 = 0, class Hook = NoHook, bool TO_REG = false, typename ROW = float>
 __device__ __forceinline__ float wave_dists(const DevIndex &ix, const float *qv, const uint32_t *nid, float *nd,
-                                            uint32_t cnt, int lane, Hook between = Hook()) {
+                                            uint32_t cnt, int lane, Hook between = Hook(), RowSrc<ROW> rs = RowSrc<ROW>()) {
   const int sub = lane & 3, grp = lane >> 2;
   float out = FLT_MAX;
+  if constexpr (RowKind<ROW>::narrow) {
+    static_assert(D16 == 0, "narrow rows: the runtime-dim recipe (dim % 16 == 0) only");
+    const float4 *qn = reinterpret_cast<const float4 *>(qv) + sub;
+    const uint32_t steps = ix.dim >> 4;
+    const bool aligned4 = sizeof(ROW) == 2 || !(steps & 1u);   // both of the lane's chunks start on a dword
+    for (uint32_t base = 0; base < cnt; base += 16) {
+      const uint32_t j = base + grp;
+      const bool act = j < cnt;
+      const uint32_t id = nid[act ? j : 0];  // idle groups re-read row 0 of the pass (cache hit) and discard
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      const ROW *ca = rs.p + (size_t)id * ix.dim + (uint32_t)sub * (ix.dim >> 2), *cb = ca + 2 * steps;
+      for (uint32_t r0 = 0; r0 < steps; r0 += 8) {
+        const uint32_t nb = min(8u, steps - r0);
+        const uint32_t nw = aligned4 ? (nb & ~3u) : 0u;   // pairs of this round that come in wide loads
+        NarrowRound<ROW> ra, rb;
+        ra.load(ca + 2 * r0, nb, nw);
+        rb.load(cb + 2 * r0, nb, nw);
+        if (base == 0 && r0 == 0) between();
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++)
+          if (i < nb) {
+            const hs_f2 xa = ra.pair(i, nw), xb = rb.pair(i, nw);
+            step4<METRIC>(acc, qn[(r0 + i) * 4], make_float4(xa.x, xa.y, xb.x, xb.y));
+          }
+      }
+      bool owner;
+      const float r = lane4_reduce<METRIC>(acc, sub, owner);
+      if (TO_REG) {
+        const float got = __shfl(r, ((lane - (int)base) & 15) * 4 + (METRIC == METRIC_L2 ? 3 : 0), 64);
+        if ((uint32_t)lane >= base && (uint32_t)lane < base + 16 && (uint32_t)lane < cnt) out = got;
+      } else {
+        if (act && owner) nd[j] = r;
+      }
+    }
+    return out;
+  } else {
   constexpr uint32_t kQuadDim = D16 < -1 ? (uint32_t)(-D16) * 4u : 0u;   // D16 = -dim/4: a compiled-in dim % 4 == 0 shape
   const uint32_t qdim = kQuadDim ? kQuadDim : ix.dim;
   if (D16 < 0 && (qdim & 15u) && !(qdim & 3u)) {
@@ -293,20 +342,21 @@ __device__ __forceinline__ float wave_dists(const DevIndex &ix, const float *qv,
     }
   }
   return out;
+  }   // fp32 rows
 }
 
 // Shared prologue: stage the query, clear the visited set, entry distance, upper-layer greedy descent
 // (hnswalg_slim.h:2033-2078, hnswalg.h:1385-1415).  Leaves (cur, curdist) = level-0 entry.
-template <int METRIC, int D16 = 0>
+template <int METRIC, int D16 = 0, typename ROW = float>
 __device__ __forceinline__ void descend(const DevIndex &ix, const SearchArgs &a, uint32_t qi, float *qv, Visited &vis,
                                         uint32_t *hash, uint32_t *nid, float *nd, Counters &c, uint32_t &cur,
-                                        float &curdist, int lane) {
+                                        float &curdist, int lane, RowSrc<ROW> rs = RowSrc<ROW>()) {
   for (uint32_t i = lane; i < ix.dim; i += 64) qv[i] = a.queries[(size_t)qi * ix.dim + i];
   vis_init(vis, a, qi, hash, lane);
   cur = ix.enterpoint;
   if (lane == 0) nid[0] = cur;
   wave_sync();
-  wave_dists<METRIC, D16>(ix, qv, nid, nd, 1, lane);
+  wave_dists<METRIC, D16>(ix, qv, nid, nd, 1, lane, NoHook(), rs);
   wave_sync();
   curdist = unif(nd[0]);
   c.n_dist = 1;
@@ -329,7 +379,7 @@ __device__ __forceinline__ void descend(const DevIndex &ix, const SearchArgs &a,
         wave_sync();
         if ((uint32_t)lane < m) nid[lane] = pr.x;
         wave_sync();
-        wave_dists<METRIC, D16>(ix, qv, nid, nd, m, lane);
+        wave_dists<METRIC, D16>(ix, qv, nid, nd, m, lane, NoHook(), rs);
         wave_sync();
         c.n_nbr += m;
         c.n_dist += m;
@@ -352,7 +402,7 @@ __device__ __forceinline__ void descend(const DevIndex &ix, const SearchArgs &a,
         wave_sync();
         if ((uint32_t)lane < m) nid[lane] = ix.cols[base + lane];
         wave_sync();
-        wave_dists<METRIC, D16>(ix, qv, nid, nd, m, lane);
+        wave_dists<METRIC, D16>(ix, qv, nid, nd, m, lane, NoHook(), rs);
         wave_sync();
         c.n_nbr += m;
         c.n_dist += m;
@@ -391,9 +441,12 @@ struct SState { uint32_t top_size, cand_size; float lb; };
 
 // One best-first beam over the `level` slices (level 0: searchBaseLayerST; >0: searchBaseLayer).
 // Returns 0 ok, 1 visited-set overflow, 2 candidate-heap overflow.
-template <int METRIC>
+// (narrow rows exist for dim % 16 == 0 only: their strict kernel takes the runtime-dim recipe without the other dims' branches)
+template <typename ROW> constexpr int strict_d16() { return RowKind<ROW>::narrow ? 0 : -1; }
+template <int METRIC, typename ROW = float>
 __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, bool bare, const float *qv, Pair *top,
-                           Pair *cand, Visited &vis, uint32_t *nid, float *nd, SState &st, Counters &c, int lane) {
+                           Pair *cand, Visited &vis, uint32_t *nid, float *nd, SState &st, Counters &c, int lane,
+                           RowSrc<ROW> rs = RowSrc<ROW>()) {
   const uint32_t ef = a.ef;
   HS_T0();
   while (true) {
@@ -443,7 +496,7 @@ __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, b
       vis_commit(vis, cnt);
       c.n_dist += cnt;
       HS_LAP(c, 2);
-      wave_dists<METRIC, -1>(ix, qv, nid, nd, cnt, lane);  // :395-396
+      wave_dists<METRIC, strict_d16<ROW>()>(ix, qv, nid, nd, cnt, lane, NoHook(), rs);  // :395-396
       wave_sync();
       HS_LAP(c, 3);
       uint32_t ts = st.top_size, cs = st.cand_size;
@@ -480,8 +533,9 @@ __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, b
   return 0;
 }
 
-template <int METRIC>
-__device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem) {
+template <int METRIC, typename ROW = float>
+__device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem,
+                                  RowSrc<ROW> rs = RowSrc<ROW>()) {
   const int lane = threadIdx.x;
   const StrictLds L = strict_layout(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots);
   float *qv = reinterpret_cast<float *>(smem + L.off_q);
@@ -500,7 +554,7 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   uint32_t cur;
   float curdist;
   Visited vis;
-  descend<METRIC, -1>(ix, a, qi, qv, vis, hash, nid, nd, c, cur, curdist, lane);
+  descend<METRIC, strict_d16<ROW>()>(ix, a, qi, qv, vis, hash, nid, nd, c, cur, curdist, lane, rs);
   HS_LAP(c, 5);
 
   // ---- level-0 (and threshold-level) beams ----------------------------------------------------
@@ -531,7 +585,7 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   }
   int rc = 0;
   for (int lvl = min(ix.threshold_level, ix.maxlevel); lvl > 0 && rc == 0; lvl--) {  // hnswalg_slim.h:2108-2113
-    rc = strict_beam<METRIC>(ix, a, lvl, /*bare=*/false, qv, top, cand, vis, nid, nd, st, c, lane);
+    rc = strict_beam<METRIC>(ix, a, lvl, /*bare=*/false, qv, top, cand, vis, nid, nd, st, c, lane, rs);
     // next beam starts from candidate_set <- copy of top_candidates (+ make_heap) (:228-233, :327-332)
     wave_sync();
     if (lane == 0) {
@@ -540,7 +594,7 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
     }
     st.cand_size = st.top_size;
   }
-  if (rc == 0) rc = strict_beam<METRIC>(ix, a, 0, bare, qv, top, cand, vis, nid, nd, st, c, lane);
+  if (rc == 0) rc = strict_beam<METRIC>(ix, a, 0, bare, qv, top, cand, vis, nid, nd, st, c, lane, rs);
   wave_sync();
   if (rc != 0) {
     flag_query(a, qi, ST_OVERFLOW, rc - 1, lane);
@@ -629,8 +683,9 @@ __device__ __forceinline__ void top_insert(float (&tk)[S], uint32_t (&ti)[S], ui
 // pushes, one byte per expansion says how many belong to each, and they are replayed with the pops in between through the
 // same libstdc++ mechanics; the search then continues on the heap path.  Continuous data never leaves the flat path, integer
 // data (SIFT) does in about a quarter of the queries at ef=70, and pays then what the heap would have cost it anyway.
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true, bool FLAT = false>
-__device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem) {
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true, bool FLAT = false, typename ROW = float>
+__device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem,
+                               RowSrc<ROW> rs = RowSrc<ROW>()) {
   static_assert(!FLAT || (BARE && !WB), "the flat start needs an index without delete marks and ef > k");
   const int lane = threadIdx.x;
   const FastLds L = fast_layout(ix.dim, a.ef, a.cand_cap, a.hash_slots);
@@ -672,7 +727,7 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
     }
     wave_sync();
   } else {
-    descend<METRIC, D16>(ix, a, qi, qv, vis, hash, nid, nd, c, cur, curdist, lane);
+    descend<METRIC, D16>(ix, a, qi, qv, vis, hash, nid, nd, c, cur, curdist, lane, rs);
     if (a.phase == 1) {
       if (lane == 0) a.entry[qi] = make_uint4(cur, __float_as_uint(curdist), c.n_dist, c.n_hops);
       return 0;
@@ -843,7 +898,7 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
       wave_sync();
       if (!vis.qbits) vis_commit(vis, cnt);
       c.n_dist += cnt;
-      if (__builtin_expect(cnt > 0, 1)) wave_dists<METRIC, D16>(ix, qv, nid, nd, cnt, lane);  // :395-396
+      if (__builtin_expect(cnt > 0, 1)) wave_dists<METRIC, D16>(ix, qv, nid, nd, cnt, lane, NoHook(), rs);  // :395-396
       wave_sync();
       const float my_d = (uint32_t)lane < cnt ? nd[lane] : FLT_MAX;
       const uint32_t my_id = (uint32_t)lane < cnt ? nid[lane] : 0;
@@ -979,7 +1034,7 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
       if (lane == 0) cand_pop(cand, cand_size);
     };
     if (__builtin_expect(cnt > 0, 1)) {
-      wave_dists<METRIC, D16>(ix, qv, nid, nd, cnt, lane, heap_hook);  // :395-396
+      wave_dists<METRIC, D16>(ix, qv, nid, nd, cnt, lane, heap_hook, rs);  // :395-396
     } else {
       heap_hook();
     }
@@ -1118,33 +1173,59 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
 }
 
 // ---- kernels: grid-stride over the queries selected by status ----------------------------------------
+// The three entry points of each kernel differ in the rows they read and in nothing else: hs::strict_kernel / hs::fast_kernel the
+// resident fp32 rows (ix.vec), hs::*_kernel_u8 / hs::*_kernel_f16 the index's narrow copy, handed over as a kernel argument of
+// its own (DevIndex and SearchArgs are what they were).
+#define HS_STRICT_KERNEL_BODY(RS)                                                                                              \
+  extern __shared__ __align__(16) unsigned char smem[];                                                                        \
+  /* pass 0: one query per workgroup, every query.  Re-run passes: 64 statuses per read, then the (normally zero) flagged */  \
+  /* queries of the block one after the other.  (One call site, so that the search body is inlined and the kernel         */  \
+  /* arguments stay in scalar registers.)                                                                                  */  \
+  const bool scan = a.pass_id != 0;                                                                                            \
+  for (uint32_t it = blockIdx.x;; it += gridDim.x) {                                                                           \
+    const uint32_t base = scan ? it * 64 : it;                                                                                 \
+    if (base >= a.nq) break;                                                                                                   \
+    unsigned long long m = 1ull;                                                                                               \
+    if (scan) {                                                                                                                \
+      const uint32_t q = base + threadIdx.x;                                                                                   \
+      m = hs_ballot(q < a.nq && ((1u << a.status[q]) & a.select_mask));                                                        \
+    }                                                                                                                          \
+    while (m) {                                                                                                                \
+      const uint32_t qi = base + (uint32_t)__ffsll((long long)m) - 1;                                                          \
+      m &= m - 1;                                                                                                              \
+      if (ix.n == 0) {  /* cur_element_count == 0 (hnswalg_slim.h:2031-2032) */                                                \
+        if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                              \
+        continue;                                                                                                              \
+      }                                                                                                                        \
+      search_one_strict<METRIC>(ix, a, qi, smem, RS);                                                                          \
+      wave_sync();                                                                                                             \
+    }                                                                                                                          \
+  }
+#if HS_TU_ROWS == 0
 template <int METRIC>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel(DevIndex ix, SearchArgs a) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  // pass 0: one query per workgroup, every query.  Re-run passes: 64 statuses per read, then the (normally zero) flagged
-  // queries of the block one after the other.  (One call site, so that the search body is inlined and the kernel
-  // arguments stay in scalar registers.)
-  const bool scan = a.pass_id != 0;
-  for (uint32_t it = blockIdx.x;; it += gridDim.x) {
-    const uint32_t base = scan ? it * 64 : it;
-    if (base >= a.nq) break;
-    unsigned long long m = 1ull;
-    if (scan) {
-      const uint32_t q = base + threadIdx.x;
-      m = hs_ballot(q < a.nq && ((1u << a.status[q]) & a.select_mask));
-    }
-    while (m) {
-      const uint32_t qi = base + (uint32_t)__ffsll((long long)m) - 1;
-      m &= m - 1;
-      if (ix.n == 0) {  // cur_element_count == 0 (hnswalg_slim.h:2031-2032)
-        if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
-        continue;
-      }
-      search_one_strict<METRIC>(ix, a, qi, smem);
-      wave_sync();
-    }
-  }
+  HS_STRICT_KERNEL_BODY(RowSrc<float>())
 }
+#define HS_STRICT_KERNEL strict_kernel
+#define HS_FAST_KERNEL fast_kernel
+#define HS_ROWS_ARG
+#elif HS_TU_ROWS == 1
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
+  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows})
+}
+#define HS_STRICT_KERNEL strict_kernel_u8
+#define HS_FAST_KERNEL fast_kernel_u8
+#define HS_ROWS_ARG , reinterpret_cast<const uint8_t *>(rows)
+#else
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
+  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows})
+}
+#define HS_STRICT_KERNEL strict_kernel_f16
+#define HS_FAST_KERNEL fast_kernel_f16
+#define HS_ROWS_ARG , reinterpret_cast<const _Float16 *>(rows)
+#endif
 // Fast kernel.  rc 3 = a tie had to be resolved but the insertion log did not fit: left to the strict pass.
 // Wavefronts per SIMD the register allocation aims at.  A wavefront alone on a CU is only 25 % faster per expansion than one
 // of sixteen (tools/profile_phases.py), so residency pays -- but only while it costs neither spills nor LDS.  At 96 VGPRs
@@ -1158,34 +1239,51 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) st
 __host__ __device__ constexpr int fast_waves(int d16, int s) {
   return (d16 > 16 || (d16 == -1 && s >= 4)) ? 3 : ((d16 == 4 || d16 == 6 || d16 == 8 || d16 == 16) && s <= 2) ? HS_SHORT_WAVES : 4;
 }
+#define HS_FAST_KERNEL_BODY(RS)                                                                                                \
+  extern __shared__ __align__(16) unsigned char smem[];                                                                        \
+  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {                                                                 \
+    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;                                                          \
+    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;  /* pass 0 takes every query */                   \
+    if (ix.n == 0) {                                                                                                           \
+      if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                                \
+      continue;                                                                                                                \
+    }                                                                                                                          \
+    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, RS);                                \
+    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;                                                                 \
+    wave_sync();                                                                                                               \
+  }
+// (Narrow rows keep the budgets of their fp32 twins.  The widest bare shape, S = 8 with the flat start, spills 424-432 B per lane at
+//  128 VGPRs where its fp32 twin spills 40; a 3-wave build of it (166 VGPRs) still spilled 364 B, so it stays at 4.)
+#if HS_TU_ROWS == 0
 template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel(DevIndex ix, SearchArgs a) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {
-    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;
-    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;  // pass 0 takes every query
-    if (ix.n == 0) {
-      if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
-      continue;
-    }
-    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem);
-    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;
-    wave_sync();
-  }
+  HS_FAST_KERNEL_BODY(RowSrc<float>())
 }
+#elif HS_TU_ROWS == 1
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
+  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows})
+}
+#else
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
+  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows})
+}
+#endif
 
-template <typename K>
-static hipError_t launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
+// (`rows`: the narrow copy in the narrow objects, nothing in the fp32 ones)
+template <typename K, typename... R>
+static hipError_t launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, R... rows) {
   if (a.nq == 0) return hipSuccess;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a);
+  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a, rows...);
   return hipGetLastError();
 }
 
-#if HS_TU_HAS_L2
+#if HS_TU_HAS_L2 && HS_TU_ROWS == 0
 // ---- query order for a two-launch fast pass --------------------------------------------------------------------------
 // One workgroup: min / max of the entry distances, a 4096-bin histogram over that range (farthest first), its prefix
 // sums, then each query takes the next free position of its bin.  Order inside a bin is whatever the atomics give: the
@@ -1264,6 +1362,27 @@ hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStr
 }
 #endif
 
+// delete marks / filters: the variant with the reference's !bare_bone branches (runtime-dim and d=128 only)
+template <int METRIC, int D16>
+static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr) {
+  if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 128) return launch(HS_FAST_KERNEL<METRIC, 2, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 256) return launch(HS_FAST_KERNEL<METRIC, 4, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
+  return launch(HS_FAST_KERNEL<METRIC, 8, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
+}
+template <int METRIC, int D16>
+static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr) {
+  if (a.k == a.ef) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
+    if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16, true>, ix, a, lds, stream HS_ROWS_ARG);
+    return launch(HS_FAST_KERNEL<METRIC, 2, D16, true>, ix, a, lds, stream HS_ROWS_ARG);
+  }
+  if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16>, ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 128) return launch(HS_FAST_KERNEL<METRIC, 2, D16>, ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 256) return launch(HS_FAST_KERNEL<METRIC, 4, D16>, ix, a, lds, stream HS_ROWS_ARG);
+  return launch(HS_FAST_KERNEL<METRIC, 8, D16>, ix, a, lds, stream HS_ROWS_ARG);
+}
+
+#if HS_TU_ROWS == 0
 hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
 hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
 hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
@@ -1272,11 +1391,15 @@ hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, h
 hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
   return launch(strict_kernel<METRIC_L2>, ix, a, lds, stream);
 }
+// (an index whose fp32 rows were dropped, hs_index_set_f32_resident(ix, 0), is served by the narrow launchers of narrow_rows.hip:
+//  a launch that would read ix.vec is refused here instead of dereferencing null on the device)
 hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
   const size_t lds = strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots);
   return ix.metric == METRIC_L2 ? launch_strict_l2(ix, a, lds, stream) : launch_strict_ip(ix, a, lds, stream);
 }
 hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
   const size_t lds = fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots);
   return ix.metric == METRIC_L2 ? launch_fast_l2(ix, a, lds, stream) : launch_fast_ip(ix, a, lds, stream);
 }
@@ -1286,26 +1409,6 @@ hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds,
   return launch(strict_kernel<METRIC_IP>, ix, a, lds, stream);
 }
 #endif
-
-// delete marks / filters: the variant with the reference's !bare_bone branches (runtime-dim and d=128 only)
-template <int METRIC, int D16>
-static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  if (a.ef <= 64) return launch(fast_kernel<METRIC, 1, D16, false, false>, ix, a, lds, stream);
-  if (a.ef <= 128) return launch(fast_kernel<METRIC, 2, D16, false, false>, ix, a, lds, stream);
-  if (a.ef <= 256) return launch(fast_kernel<METRIC, 4, D16, false, false>, ix, a, lds, stream);
-  return launch(fast_kernel<METRIC, 8, D16, false, false>, ix, a, lds, stream);
-}
-template <int METRIC, int D16>
-static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  if (a.k == a.ef) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
-    if (a.ef <= 64) return launch(fast_kernel<METRIC, 1, D16, true>, ix, a, lds, stream);
-    return launch(fast_kernel<METRIC, 2, D16, true>, ix, a, lds, stream);
-  }
-  if (a.ef <= 64) return launch(fast_kernel<METRIC, 1, D16>, ix, a, lds, stream);
-  if (a.ef <= 128) return launch(fast_kernel<METRIC, 2, D16>, ix, a, lds, stream);
-  if (a.ef <= 256) return launch(fast_kernel<METRIC, 4, D16>, ix, a, lds, stream);
-  return launch(fast_kernel<METRIC, 8, D16>, ix, a, lds, stream);
-}
 #if HS_TU_HAS_L2
 hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
   if (ix.has_deleted) {
@@ -1342,6 +1445,29 @@ hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, h
     default: return (ix.dim & 15u) ? launch_fast_md<METRIC_IP, -1>(ix, a, lds, stream) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream);
   }
 }
+#endif
+#else   // the narrow objects: one strict and one fast launcher per metric, runtime-dim shapes (dispatch: narrow_rows.hip)
+#if HS_TU_ROWS == 1
+#define HS_NARROW_FN(name, metric) name##_u8_##metric
+#else
+#define HS_NARROW_FN(name, metric) name##_f16_##metric
+#endif
+#if HS_TU_HAS_L2
+hipError_t HS_NARROW_FN(launch_strict, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
+  return launch(HS_STRICT_KERNEL<METRIC_L2>, ix, a, lds, stream HS_ROWS_ARG);
+}
+hipError_t HS_NARROW_FN(launch_fast, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
+  return ix.has_deleted ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, rows) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, rows);
+}
+#endif
+#if HS_TU_HAS_IP
+hipError_t HS_NARROW_FN(launch_strict, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
+  return launch(HS_STRICT_KERNEL<METRIC_IP>, ix, a, lds, stream HS_ROWS_ARG);
+}
+hipError_t HS_NARROW_FN(launch_fast, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
+  return ix.has_deleted ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, rows) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, rows);
+}
+#endif
 #endif
 
 }  // namespace hs

@@ -92,8 +92,12 @@ struct hs_index {
   DevBuf<uint64_t> labels;
   DevBuf<uint8_t> deleted;
   // narrow rows (hs_index_set_row_format): a u8 / fp16 copy of `vec` in the flat kernel's lane-major layout (narrow_rows.hip), sized
-  // like `vec` (row capacity x dim values); `vec` stays resident, every kernel but the flat one reads it
+  // like `vec` (row capacity x dim values).  While `vec` is resident every kernel but the flat one reads it; once it has been dropped
+  // (hs_index_set_f32_resident(ix, 0), hs_index_load_narrow: f32_resident = false, vec.p = dev.vec = null) every search launch goes to
+  // the narrow twin of the chosen kernel and nothing on the device holds fp32 rows
   int row_fmt = ROWS_F32;
+  bool f32_resident = true;
+  size_t f32_gone = 0;           // what info.device_bytes is short of while the fp32 rows are absent
   DevBuf<uint8_t> narrow;
   DevBuf<uint32_t> narrow_bad;   // the conversion kernel's "first row that does not fit" word
   size_t narrow_bytes = 0;       // part of info.device_bytes while the copy exists
@@ -307,6 +311,52 @@ static hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out) {
   return HS_OK;
 }
 
+// Host-side conversion (hs_rows_to_narrow, hs_index_load_narrow, hs_index_patch on an index without fp32 rows): rows[n x dim] into
+// the lane-major layout of the device copy, row by row while the rows fit.  Returns the first row that holds an unrepresentable
+// value (nothing is written from that row on), n when there is none.
+template <typename T>
+static size_t rows_to_narrow_t(const float *rows, size_t n, size_t dim, T *out) {
+  for (size_t r = 0; r < n; r++) {
+    const float *x = rows + r * dim;
+    if (first_unfit<T>(x, dim) < dim) return r;
+    T *o = out + r * dim;
+    for (size_t j = 0; j < dim; j++) o[narrow_slot((uint32_t)j, (uint32_t)dim)] = narrow_cast<T>(x[j]);
+  }
+  return n;
+}
+static size_t rows_to_narrow_host(const float *rows, size_t n, size_t dim, int fmt, void *out) {
+  return fmt == ROWS_U8 ? rows_to_narrow_t<uint8_t>(rows, n, dim, static_cast<uint8_t *>(out))
+                        : rows_to_narrow_t<_Float16>(rows, n, dim, static_cast<_Float16 *>(out));
+}
+// The narrow copy of an index WITHOUT resident fp32 rows, (re)built from host rows: allocated for `cap` rows, converted on the
+// host and uploaded in chunks of at most kNarrowStageBytes -- the fp32 array never exists on the device.
+static constexpr size_t kNarrowStageBytes = 64u << 20;
+static hs_status upload_narrow_from_host(hs_index *ix, const float *rows, size_t n, size_t dim, size_t cap) {
+  const int fmt = ix->row_fmt;
+  const size_t w = narrow_width(fmt), row_bytes = dim * w;
+  DevBuf<uint8_t> fresh;
+  HIP_TRY(fresh.alloc(std::max<size_t>(cap * row_bytes, 16)));
+  const size_t per = std::max<size_t>(kNarrowStageBytes / std::max<size_t>(row_bytes, 1), 1);
+  std::vector<uint8_t> stage(std::min(per, std::max<size_t>(n, 1)) * row_bytes);
+  for (size_t r0 = 0; r0 < n; r0 += per) {
+    const size_t m = std::min(per, n - r0);
+    const size_t bad = rows_to_narrow_host(rows + r0 * dim, m, dim, fmt, stage.data());
+    if (bad < m) {
+      const float *x = rows + (r0 + bad) * dim;
+      const size_t j = std::min(first_unfit(x, dim, fmt), dim - 1);
+      return fail(HS_ERR_UNSUPPORTED, unfit_message(r0 + bad, j, x[j], fmt));
+    }
+    HIP_TRY(hipMemcpy(fresh.p + r0 * row_bytes, stage.data(), m * row_bytes, hipMemcpyHostToDevice));
+  }
+  ix->narrow.release();
+  std::swap(ix->narrow.p, fresh.p);
+  std::swap(ix->narrow.n, fresh.n);
+  ix->narrow_bytes = cap * row_bytes;
+  return HS_OK;
+}
+// bytes of the fp32 array (allocated for the row capacity): what hs_info.device_bytes falls by when it is dropped
+static size_t f32_rows_bytes(const hs_index *ix) { return std::max<size_t>(ix->cap_rows, ix->info.n) * ix->info.dim * 4; }
+
 extern "C" {
 
 const char *hs_last_error(void) { return g_err.c_str(); }
@@ -368,13 +418,22 @@ static hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   i.n_edges = p.cols.size(); i.max_degree0 = p.max_deg0; i.index_size = p.index_size;
   i.device_bytes = p.vec.size() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
                    p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4 + ix->narrow_bytes;
+  // without resident fp32 rows: less what hs_index_set_f32_resident(ix, 0) takes off, the array's whole row capacity (the sum
+  // above counts its n rows; an index with far more capacity than rows would go below zero, so it stops there)
+  if (!ix->f32_resident) { ix->f32_gone = std::min<size_t>(i.device_bytes, f32_rows_bytes(ix)); i.device_bytes -= ix->f32_gone; }
   return HS_OK;
 }
 
 static hs_status upload(hs_index *ix, const PackedIndex &p) {
   HIP_TRY(hipSetDevice(ix->device));
   const size_t cap = std::max(ix->cap_rows, p.n);
-  HIP_TRY(upload_cap(ix->vec, p.vec, cap * p.dim));
+  if (ix->f32_resident) {
+    HIP_TRY(upload_cap(ix->vec, p.vec, cap * p.dim));
+  } else {   // the rows go to the device in the narrow format only
+    ix->vec.release();
+    hs_status ns = upload_narrow_from_host(ix, p.vec.data(), p.n, p.dim, cap);
+    if (ns != HS_OK) return ns;
+  }
   // level-0 adjacency tiles: node i's ids padded with 0xFFFFFFFF to a fixed, 64-byte-multiple stride
   const uint32_t stride = tile_stride_for(p.max_deg0);
   if (stride) {
@@ -497,7 +556,9 @@ static hs_status load_slimq(const BinSource &src, int metric, size_t dim, int de
   return HS_OK;
 }
 
-static hs_status load_from(const BinSource &src, int kind, int metric, size_t dim, size_t max_elements, int device, hs_index **out) {
+// narrow_fmt != ROWS_F32 (hs_index_load_narrow): the index starts without fp32 rows, its rows uploaded in that format only
+static hs_status load_from(const BinSource &src, int kind, int metric, size_t dim, size_t max_elements, int device, hs_index **out,
+                           int narrow_fmt = ROWS_F32) {
   if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
   if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
@@ -526,6 +587,7 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
   hs_index *ix = new hs_index();
   ix->device = device;
   if (keep_slim) { ix->cap_rows = max_elements; ix->host_slim = std::move(keep_slim); }
+  if (narrow_fmt != ROWS_F32) { ix->row_fmt = narrow_fmt; ix->f32_resident = false; }
   hs_status s = upload(ix, p);
   if (s != HS_OK) { delete ix; return s; }
   *out = ix;
@@ -604,18 +666,27 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
   HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
   const uint32_t stride = tile_stride_for(p.max_deg0);
   if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything
-    hs_status us = upload(ix, p);
-    if (us != HS_OK || ix->row_fmt == ROWS_F32) return us;
+    hs_status us = upload(ix, p);   // (an index without fp32 rows: rebuilds the narrow copy from the host image, in chunks)
+    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
     return build_narrow(ix, ix->row_fmt, ix->narrow);   // the fp32 rows were re-allocated: the narrow copy is rebuilt whole
   }
   std::vector<uint32_t> row(stride);
+  std::vector<uint8_t> narrow_row;
   for (uint32_t id : changed) {
     std::fill(row.begin(), row.end(), 0xFFFFFFFFu);
     std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], row.begin());
     HIP_TRY(hipMemcpy(ix->tile0.p + (size_t)id * stride, row.data(), stride * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ix->vec.p + (size_t)id * dim, &p.vec[(size_t)id * dim], dim * 4, hipMemcpyHostToDevice));
-    if (ix->row_fmt != ROWS_F32)   // the same row of the narrow copy (its values were validated above)
-      HIP_TRY(launch_narrow_convert(ix->vec.p, ix->narrow.p, ix->row_fmt, id, 1, (uint32_t)dim, ix->narrow_bad.p, nullptr));
+    if (ix->f32_resident) {
+      HIP_TRY(hipMemcpy(ix->vec.p + (size_t)id * dim, &p.vec[(size_t)id * dim], dim * 4, hipMemcpyHostToDevice));
+      if (ix->row_fmt != ROWS_F32)   // the same row of the narrow copy (its values were validated above)
+        HIP_TRY(launch_narrow_convert(ix->vec.p, ix->narrow.p, ix->row_fmt, id, 1, (uint32_t)dim, ix->narrow_bad.p, nullptr));
+    } else {   // no fp32 rows on the device: the row is converted here and written into the copy
+      const size_t rb = dim * narrow_width(ix->row_fmt);
+      narrow_row.resize(rb);
+      if (rows_to_narrow_host(&p.vec[(size_t)id * dim], 1, dim, ix->row_fmt, narrow_row.data()) != 1)
+        return fail(HS_ERR_UNSUPPORTED, "patch: row " + std::to_string(id) + " is not representable in the index's row format");
+      HIP_TRY(hipMemcpy(ix->narrow.p + (size_t)id * rb, narrow_row.data(), rb, hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipMemcpy(ix->labels.p + id, &p.labels[id], 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ix->deleted.p + id, &p.deleted[id], 1, hipMemcpyHostToDevice));
   }
@@ -741,6 +812,8 @@ hs_status hs_index_set_row_format(hs_index *ix, int format) {
   if (format != ROWS_F32 && (ix->info.dim & 15) != 0)
     return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(ix->info.dim) + ")");
   if (format == ix->row_fmt) return HS_OK;
+  if (!ix->f32_resident)   // every other format is converted from the fp32 rows
+    return fail(HS_ERR_INVALID, "the index holds no fp32 rows: restore the fp32 rows first (hs_index_set_f32_resident(ix, 1))");
   HIP_TRY(hipSetDevice(ix->device));
   HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
   DevBuf<uint8_t> fresh;
@@ -758,11 +831,54 @@ hs_status hs_index_set_row_format(hs_index *ix, int format) {
   return HS_OK;
 }
 int hs_index_row_format(const hs_index *ix) { return ix ? ix->row_fmt : ROWS_F32; }
+
+hs_status hs_index_set_f32_resident(hs_index *ix, int on) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (!on && ix->row_fmt == ROWS_F32) return fail(HS_ERR_INVALID, "the fp32 rows are the only rows of this index: hs_index_set_row_format first");
+  if ((on != 0) == ix->f32_resident) return HS_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
+  const size_t n = ix->info.n, dim = ix->info.dim;
+  if (on) {
+    HIP_TRY(ix->vec.alloc(std::max<size_t>(std::max<size_t>(ix->cap_rows, n) * dim, 1)));
+    HIP_TRY(launch_narrow_widen(ix->narrow.p, ix->vec.p, ix->row_fmt, 0, (uint32_t)n, (uint32_t)dim, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    ix->dev.vec = ix->vec.p;
+    ix->info.device_bytes += ix->f32_gone;
+    ix->f32_gone = 0;
+  } else {
+    ix->vec.release();
+    ix->dev.vec = nullptr;
+    ix->f32_gone = std::min<size_t>(ix->info.device_bytes, f32_rows_bytes(ix));
+    ix->info.device_bytes -= ix->f32_gone;
+  }
+  ix->f32_resident = on != 0;
+  return HS_OK;
+}
+int hs_index_f32_resident(const hs_index *ix) { return ix ? (ix->f32_resident ? 1 : 0) : 1; }
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad) {
   if (!first_bad || (n && dim && !rows)) return fail(HS_ERR_INVALID, "null argument");
   if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
   *first_bad = dim ? first_unfit(rows, n * dim, format) / dim : n;
   return HS_OK;
+}
+
+hs_status hs_rows_to_narrow(const float *rows, size_t n, size_t dim, int format, void *out, uint64_t *first_bad) {
+  if (!first_bad || (n && dim && (!rows || !out))) return fail(HS_ERR_INVALID, "null argument");
+  if (format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
+  if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0");
+  *first_bad = dim ? rows_to_narrow_host(rows, n, dim, format, out) : n;
+  return HS_OK;
+}
+
+hs_status hs_index_load_narrow(const char *path, int kind, int metric, size_t dim, size_t max_elements, int device, int format,
+                               hs_index **out) {
+  if (!path || !out) return fail(HS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
+  if (kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
+  if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(dim) + ")");
+  return load_from(BinSource(path), kind, metric, dim, max_elements, device, out, format);
 }
 
 // One launch group serves at most kMaxLaunchQueries queries: the per-query scratch in global memory (96 KiB each) is
@@ -844,14 +960,23 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   static const bool lean_forced = getenv("HS_LEAN_MIN_EF") != nullptr;
   static const uint32_t lean_min_ef = lean_forced ? (uint32_t)atoi(getenv("HS_LEAN_MIN_EF")) : kLeanMinEf;
   static const bool lean_asked = lean_forced || (kernel_env && !strcmp(kernel_env, "lean"));
-  const bool lean = lean_asked && fast && sh.ef >= lean_min_ef && lean_supported(ix->dev, sh.ef, (uint32_t)k) &&
+  // An index without fp32 rows (hs_index_set_f32_resident): the choice below is what it would be with them, and whichever of flat /
+  // fast / strict it names -- the re-run pass too -- is launched as its narrow twin.  The lean kernel (diagnostic, by environment
+  // only) has none and is never chosen here: its requests fall through to the fast kernel.
+  const bool f32_free = !ix->f32_resident;
+  const int fmt = ix->row_fmt;
+  auto fast_go = [&]() { return f32_free ? launch_fast_narrow(ix->dev, a, ix->narrow.p, fmt, stream) : launch_fast(ix->dev, a, stream); };
+  auto strict_go = [&]() { return f32_free ? launch_strict_narrow(ix->dev, a, ix->narrow.p, fmt, stream) : launch_strict(ix->dev, a, stream); };
+  const bool lean = lean_asked && !f32_free && fast && sh.ef >= lean_min_ef && lean_supported(ix->dev, sh.ef, (uint32_t)k) &&
                     lean_lds_bytes((uint32_t)ix->info.dim, sh.ef, sh.l_cand_cap, sh.q_bits ? sh.q_hash_slots : sh.l_hash_slots) <= kLdsPerCU;
   static const bool flatk_off = kernel_env && (!strcmp(kernel_env, "lean") || !strcmp(kernel_env, "fast"));
   const FlatPlan fp = plan_flat(ix, sh.ef, nq);
   const bool flatk = !flatk_off && !lean_forced && fast && fp.ok && flatk_supported(ix->dev, sh.ef, (uint32_t)k);
   const bool narrow = flatk && ix->row_fmt != ROWS_F32;   // the same launch plan over the narrow copy of the rows
   auto flat_go = [&]() { return narrow ? launch_flatk_narrow(ix->dev, a, ix->narrow.p, ix->row_fmt, stream) : launch_flatk(ix->dev, a, stream); };
-  ix->last_kernel = narrow ? (ix->row_fmt == ROWS_U8 ? "hs::flat_kernel_u8" : "hs::flat_kernel_f16") : flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel" : fast ? "hs::fast_kernel" : "hs::strict_kernel";
+  ix->last_kernel = narrow ? (ix->row_fmt == ROWS_U8 ? "hs::flat_kernel_u8" : "hs::flat_kernel_f16") : flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel"
+                    : f32_free ? (fast ? (fmt == ROWS_U8 ? "hs::fast_kernel_u8" : "hs::fast_kernel_f16") : (fmt == ROWS_U8 ? "hs::strict_kernel_u8" : "hs::strict_kernel_f16"))
+                    : fast ? "hs::fast_kernel" : "hs::strict_kernel";
   a.counters = w->counters.p; a.pass_id = 0;
   static const int order_env = getenv("HS_ORDER") ? atoi(getenv("HS_ORDER")) : -1;   // diagnostic: 0 = never, 1 = always
   const bool ordered = fast && (order_env < 0 ? nq >= kOrderMinQueries : order_env != 0);
@@ -904,14 +1029,14 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
       HIP_TRY(w->order.ensure(nq));
       a.entry = reinterpret_cast<uint4 *>(w->entry.p); a.order = w->order.p;
       a.phase = 1;
-      HIP_TRY(launch_fast(ix->dev, a, stream));
+      HIP_TRY(fast_go());
       if (order_env == 2) a.order = nullptr;   // diagnostic: the split without the ordering
       else HIP_TRY(launch_order(a.entry, w->order.p, (uint32_t)nq, stream));
       a.phase = 2;
-      HIP_TRY(launch_fast(ix->dev, a, stream));
+      HIP_TRY(fast_go());
       a.phase = 0;
     } else {
-      HIP_TRY(fast ? launch_fast(ix->dev, a, stream) : launch_strict(ix->dev, a, stream));
+      HIP_TRY(fast ? fast_go() : strict_go());
     }
     fast_scratch(false);
   }
@@ -924,7 +1049,7 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
     a.cand_cap = sh.fb_cand_cap; a.hash_slots = sh.fb_hash_slots; a.vis_bits = 0; a.hash_fill_shift = 0;
     a.fb_cand = w->fb.p; a.fb_spill = w->fb.p + (size_t)kFbGrid * kFbCand * 2; a.spill_slots = kFbSpill;
     a.counters = w->counters.p + 8; a.pass_id = 2;
-    HIP_TRY(launch_strict(ix->dev, a, stream));
+    HIP_TRY(strict_go());
   }
   return HS_OK;
 }

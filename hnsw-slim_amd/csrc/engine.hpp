@@ -102,8 +102,16 @@ hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stre
 // launch_flatk_narrow is launch_flatk reading that copy (kernels hs::flat_kernel_u8 / hs::flat_kernel_f16; same shapes, same plan).
 // launch_narrow_convert fills rows [row0, row0 + nrows) of the copy from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to
 // the smallest row that holds a value the format cannot represent.
+// launch_strict_narrow / launch_fast_narrow: launch_strict / launch_fast reading that copy (hs::strict_kernel_u8 / _f16,
+// hs::fast_kernel_u8 / _f16; the runtime-dim shapes, dim % 16 == 0).  With them no search kernel needs ix.vec, which an index
+// may then drop (hs_index_set_f32_resident): launch_strict / launch_fast / launch_lean / launch_flatk return
+// hipErrorInvalidDevicePointer instead of launching when ix.vec is null and the index is not empty.
+// launch_narrow_widen is the inverse of the conversion: rows [row0, row0 + nrows) of d_vec from the copy (exact).
 hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
+hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
+hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
 hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
                                  hipStream_t stream);
+hipError_t launch_narrow_widen(const void *d_rows, float *d_vec, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, hipStream_t stream);
 
 }  // namespace hs

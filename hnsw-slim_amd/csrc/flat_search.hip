@@ -37,6 +37,7 @@
 #include "dist_recipe.hpp"
 #include "engine.hpp"
 #include "heap_emul.hpp"
+#include "narrow_load.hpp"
 #include "search_common.hpp"
 #include "sorted_insert.hpp"
 #include "wave_util.hpp"
@@ -122,28 +123,7 @@ __host__ __device__ constexpr int flat_waves(int s, int d16) {
 // so lane s finds every element it works on in ONE contiguous chunk of dim / 8 values.  Element 16 i + 2 s + e still goes to
 // accumulator e of lane s in step order i, the value is widened exactly (every stored value is representable, that is what
 // the conversion checked), and the arithmetic below is the fp32 one: the distance has the same bits as from the fp32 row.
-template <typename ROW> struct RowKind { static constexpr bool narrow = true; };
-template <> struct RowKind<float> { static constexpr bool narrow = false; };
-typedef uint32_t hs_u4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t hs_u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-typedef _Float16 hs_h2 __attribute__((ext_vector_type(2)));
-// element pair i of a lane's chunk, widened: a u8 pair is half a dword (v_cvt_f32_ubyteN), an f16 pair one dword (v_cvt_f32_f16)
-__device__ __forceinline__ hs_f2 narrow_pair(const uint8_t *, const uint32_t *dw, int i) {
-  const uint32_t w = dw[i >> 1] >> ((i & 1) * 16);
-  return hs_f2{(float)(w & 0xFFu), (float)((w >> 8) & 0xFFu)};
-}
-__device__ __forceinline__ hs_f2 narrow_pair(const _Float16 *, const uint32_t *dw, int i) {
-  const hs_h2 h = __builtin_bit_cast(hs_h2, dw[i]);
-  return hs_f2{(float)h.x, (float)h.y};
-}
-__device__ __forceinline__ hs_f2 narrow_pair_at(const uint8_t *chunk, uint32_t i) {
-  const uint32_t w = *reinterpret_cast<const unsigned short *>(chunk + 2 * i);
-  return hs_f2{(float)(w & 0xFFu), (float)(w >> 8)};
-}
-__device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t i) {
-  const hs_h2 h = *reinterpret_cast<const hs_h2 *>(chunk + 2 * i);
-  return hs_f2{(float)h.x, (float)h.y};
-}
+// (RowKind and the widening of stored element pairs, narrow_pair / narrow_pair_at: narrow_load.hpp, shared with beam_search.hip)
 
 template <int METRIC, int D16, typename ROW>
 __device__ __forceinline__ float flat_dist8(const ROW *vec, uint32_t dim, const lds_u8 *qv, uint32_t rowid, int s) {
@@ -1172,6 +1152,7 @@ uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef) {
 size_t flatk_lds_bytes(uint32_t dim, uint32_t ef, uint32_t nb) { return flat_layout(dim, ef, nb).total; }
 hipError_t launch_flatk_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, nullptr, stream); }
 hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;   // fp32 rows dropped: launch_flatk_narrow serves the index
   return ix.metric == METRIC_L2 ? launch_flatk_l2(ix, a, stream) : launch_flatk_ip(ix, a, stream);
 }
 #endif

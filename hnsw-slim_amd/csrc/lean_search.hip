@@ -535,6 +535,7 @@ bool lean_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
 size_t lean_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots) { return lean_layout(dim, ef, cand_cap, hash_slots).total; }
 hipError_t launch_lean_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return lean_launch_s<METRIC_L2>(ix, a, stream); }
 hipError_t launch_lean(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;   // fp32 rows dropped (hs_index_set_f32_resident): this kernel has no narrow twin
   return ix.metric == METRIC_L2 ? launch_lean_l2(ix, a, stream) : launch_lean_ip(ix, a, stream);
 }
 #endif

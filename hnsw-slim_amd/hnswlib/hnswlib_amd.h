@@ -122,6 +122,7 @@ class DeviceIndex {
   std::vector<hs_index *> replicas_;
   hs_comm *comm_ = nullptr;
   hs_row_format row_fmt_ = HS_ROWS_F32;   // what setRowFormat asked for: applied to every index this object loads
+  bool f32_resident_ = true;              // what setF32Resident asked for: likewise
   void free_replicas() {
     for (size_t r = 1; r < replicas_.size(); r++) hs_index_free(replicas_[r]);
     replicas_.clear();
@@ -156,6 +157,15 @@ class DeviceIndex {
     row_fmt_ = f;
   }
   hs_row_format rowFormat() const { return h_ ? (hs_row_format)hs_index_row_format(h_) : row_fmt_; }
+  // fp32-free index (hs_index_set_f32_resident; no counterpart in the reference): false frees the fp32 rows of an index in a narrow
+  // row format, and every search kernel then reads the narrow copy -- a quarter / half of the row bytes in HBM, no answer changes;
+  // true re-creates them.  std::runtime_error in HS_ROWS_F32 format.  Holds for later loads of this object too, after setRowFormat.
+  void setF32Resident(bool on) {
+    if (h_) check(hs_index_set_f32_resident(h_, on ? 1 : 0));
+    for (size_t r = 1; r < replicas_.size(); r++) check(hs_index_set_f32_resident(replicas_[r], on ? 1 : 0));
+    f32_resident_ = on;
+  }
+  bool f32Resident() const { return h_ ? hs_index_f32_resident(h_) != 0 : f32_resident_; }
   bool sharded() const { return comm_ != nullptr; }
   hs_index *handle() const { return h_; }
   const std::string &path() const { return path_; }
@@ -195,6 +205,7 @@ class DeviceIndex {
     }
     ef_ = 10;  // hnswalg.h:864, hnswalg_slim.h:793
     if (row_fmt_ != HS_ROWS_F32) setRowFormat(row_fmt_);
+    if (!f32_resident_) setF32Resident(false);
   }
   mutable BaseFilterFunctor *cached_filter_ = nullptr;
   mutable std::vector<uint8_t> allowed_;
@@ -472,6 +483,7 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   void setDataset(const float *rows, size_t n, size_t d) { detail::check(hs_slimq_set_dataset(h_, rows, n, d)); }
   void setTConst(double t) { detail::check(hs_slimq_set_tconst(h_, t)); }
   void setRowFormat(hs_row_format) { throw std::runtime_error("narrow rows: a SlimQ index has no flat-kernel rows"); }
+  void setF32Resident(bool) { throw std::runtime_error("narrow rows: a SlimQ index has no flat-kernel rows"); }
   void addPoint(const void *, labeltype, bool = false) override {
     throw std::runtime_error("HierarchicalNSWSlimQ does not support addPoint");  // hnswalg_slimq.h:298-301
   }

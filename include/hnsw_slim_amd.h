@@ -98,8 +98,13 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
  * fp32 recipe in the same order, so distances, labels, counters and tie behaviour are bit-identical to HS_ROWS_F32.  It is an
  * explicit call because it is a contract on the data: it costs device memory (one value of the format per value of the fp32 array's
  * row capacity: max(n, max_elements) x dim x 1 or 2 bytes, included in hs_info.device_bytes while it exists) and a later
- * hs_index_patch may only add representable rows (HS_ERR_UNSUPPORTED otherwise, index untouched).  Every other kernel (strict /
- * fast: filters, delete marks, exact order, ef > 512, the re-run pass, hs_search_batch_raw) keeps reading the fp32 rows. */
+ * hs_index_patch may only add representable rows (HS_ERR_UNSUPPORTED otherwise, index untouched).
+ * What reads what: while the fp32 rows are resident (the state after hs_index_set_row_format) the flat kernel reads the copy and
+ * every other kernel (strict / fast: filters, delete marks, exact order, ef > 512, threshold_level > 0, the re-run pass,
+ * hs_search_batch_raw) reads the fp32 rows.  After hs_index_set_f32_resident(ix, 0) the fp32 rows are gone and EVERY search
+ * kernel reads the copy: the kernel choice stays what it was and the narrow twin of the chosen kernel is launched
+ * (hs::flat_kernel_u8 / _f16, hs::fast_kernel_u8 / _f16, hs::strict_kernel_u8 / _f16, the re-run pass included), with the same
+ * bits in every output.  The index then occupies a quarter (u8) or half (fp16) of the row bytes instead of 5/4 or 3/2 of them. */
 typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2 } hs_row_format;
 /* Builds (or, for HS_ROWS_F32, drops) the narrow copy of the rows on the index's device.  Not to be called while a search on this
  * index is in flight (as hs_index_patch).  HS_ERR_UNSUPPORTED, index left exactly as it was, when a stored value is not
@@ -111,6 +116,28 @@ int hs_index_row_format(const hs_index *ix);
  * first row that is not.  Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255 (and -0.0f, read back
  * as +0.0f, which cannot change a distance); fp16: every finite fp16 value, subnormals included. */
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad);
+/* on = 0: free the resident fp32 rows of an index that holds a narrow copy; from then on EVERY search kernel reads the copy.
+ * on = 1: re-create them from the copy (widening is exact; a u8 index reads +0.0f where -0.0f was stored).
+ * hs_info.device_bytes falls / rises by exactly max(n, max_elements) x dim x 4.  Both are idempotent.  on = 0 on an index in
+ * HS_ROWS_F32 format is HS_ERR_INVALID.  While the fp32 rows are absent hs_index_set_row_format to any OTHER format (HS_ROWS_F32
+ * included) is HS_ERR_INVALID, index untouched: restore the fp32 rows first.  hs_index_patch works in both states (the patched
+ * rows go into the copy; a patch that forces a re-tile rebuilds the copy from the host image in bounded chunks and never
+ * allocates the fp32 array).  The lean kernel (diagnostic, chosen by environment only) has no narrow twin: HS_KERNEL=lean and
+ * HS_LEAN_MIN_EF fall through to the fast kernel on such an index.  Not to be called while a search on this index is in
+ * flight (as hs_index_patch). */
+hs_status hs_index_set_f32_resident(hs_index *ix, int on);
+int hs_index_f32_resident(const hs_index *ix);
+/* Host only, no device: out[n x dim] of `format` (HS_ROWS_U8: bytes, HS_ROWS_F16: IEEE half words) in the lane-major layout of
+ * the device copy, out[r * dim + s * (dim / 8) + 2 i + e] = rows[r][16 i + 2 s + e]; *first_bad as hs_rows_representable;
+ * nothing is written beyond row *first_bad.  HS_ERR_INVALID for a format other than U8 / F16, HS_ERR_UNSUPPORTED for
+ * dim % 16 != 0. */
+hs_status hs_rows_to_narrow(const float *rows, size_t n, size_t dim, int format, void *out, uint64_t *first_bad);
+/* hs_index_load, but the rows go to the device in `format` only: the result equals load + set_row_format(format) +
+ * set_f32_resident(0), and the fp32 array is never allocated on the device (the rows are converted on the host,
+ * hs_rows_to_narrow, and uploaded in chunks of at most 64 MiB).  Refusals as hs_index_set_row_format (unrepresentable value with
+ * the first offending row named, SlimQ, dim % 16 != 0); *out stays NULL. */
+hs_status hs_index_load_narrow(const char *path, int kind, int metric, size_t dim, size_t max_elements, int device,
+                               int format, hs_index **out);
 void hs_index_free(hs_index *ix);                        /* ~HierarchicalNSW* / clear(): hnswalg_slim.h:154-167 */
 hs_status hs_set_ef(hs_index *ix, size_t ef);            /* setEf: hnswalg.h:184, hnswalg_slim.h:193 */
 hs_status hs_index_info(const hs_index *ix, hs_info *out);
