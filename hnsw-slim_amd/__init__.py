@@ -30,6 +30,8 @@ EXPORTS = [
     "hs_comm_results_dev", "hs_convert_slim_gpu", "hs_index_patch", "hs_index_from_host_arrays", "hs_build_rabitq_hnsw",
     "hs_convert_slimq_graph", "hs_host_device_pointer", "hs_index_set_row_format", "hs_index_row_format", "hs_rows_representable",
     "hs_index_set_f32_resident", "hs_index_f32_resident", "hs_rows_to_narrow", "hs_index_load_narrow",
+    "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
+    "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
 ]
 
 
@@ -108,6 +110,19 @@ def lib():
     L.hs_search_batch_raw.argtypes = [vp, vp, sz, sz, ci, vp, vp, vp, vp]
     L.hs_search_batch_filtered.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_labels.argtypes = [vp, vp]
+    L.hs_filter_row_words.restype = sz
+    L.hs_filter_row_words.argtypes = [sz]
+    L.hs_filter_pack.argtypes = [vp, sz, sz, vp]
+    L.hs_filter_set_create.argtypes = [vp, sz, ctypes.POINTER(vp)]
+    L.hs_filter_set_free.restype = None
+    L.hs_filter_set_free.argtypes = [vp]
+    L.hs_filter_set_write.argtypes = [vp, sz, sz, vp]
+    L.hs_filter_set_write_bits.argtypes = [vp, sz, sz, vp]
+    L.hs_filter_set_write_dev.argtypes = [vp, sz, sz, vp, vp]
+    L.hs_filter_set_read.argtypes = [vp, sz, vp]
+    L.hs_filter_set_info.argtypes = [vp, vp, vp, vp, vp]
+    L.hs_search_batch_filter_set.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_search_batch_filter_set_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     L.hs_build_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_convert_slimq_graph.argtypes = L.hs_convert_slim.argtypes
@@ -209,6 +224,83 @@ def rows_to_narrow(rows, fmt, out=None):
     bad = ctypes.c_uint64(0)
     _check(lib().hs_rows_to_narrow(r.ctypes.data, r.shape[0], r.shape[1], int(fmt), out.ctypes.data, ctypes.byref(bad)))
     return out, (None if bad.value == r.shape[0] else int(bad.value))
+
+
+def filter_row_words(n):
+    """hs_filter_row_words: 32-bit words per bitmap row of a filter set over n ids (ceil(n / 32) rounded up to a multiple of 4)."""
+    return int(lib().hs_filter_row_words(int(n)))
+
+
+def filter_pack(allowed):
+    """hs_filter_pack (host only): allowed (nf x n, or n: one filter; non-zero = allowed) -> uint32 words nf x filter_row_words(n),
+    bit i & 31 of word i >> 5, padding bits zero."""
+    a = np.ascontiguousarray(allowed, np.uint8)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    nf, n = a.shape
+    out = np.empty((nf, filter_row_words(n)), np.uint32)
+    _check(lib().hs_filter_pack(a.ctypes.data, n, nf, out.ctypes.data))
+    return out
+
+
+class FilterSet:
+    """hs_filter_set: nf filters over the internal ids of one index, resident on its device as bitmaps.  Index.search_filter_set
+    names the set and one filter per query; queries under different filters run in one launch."""
+
+    def __init__(self, index, nf):
+        self._h = ctypes.c_void_p()
+        _check(lib().hs_filter_set_create(index._h, int(nf), ctypes.byref(self._h)))
+
+    @classmethod
+    def create(cls, index, nf):
+        return cls(index, nf)
+
+    def close(self):
+        if self._h:
+            lib().hs_filter_set_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        _check(lib().hs_filter_set_info(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(nf=v[0].value, n=v[1].value, row_words=v[2].value, device_bytes=v[3].value)
+
+    def write(self, first, allowed_bytes):
+        """Rows first.. from host bytes (count x n, or n: one row; non-zero = allowed), packed on the device."""
+        a = np.ascontiguousarray(allowed_bytes, np.uint8)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.shape[1] != self.info()["n"]:
+            raise HsError(HS_ERR_INVALID, f"rows of {a.shape[1]} bytes for a filter set over {self.info()['n']} ids")
+        _check(lib().hs_filter_set_write(self._h, int(first), a.shape[0], a.ctypes.data))
+
+    def write_bits(self, first, words):
+        """Rows first.. from host words in filter_pack's layout (count x row_words uint32)."""
+        w = np.ascontiguousarray(words, np.uint32)
+        w = w.reshape(1, -1) if w.ndim == 1 else w
+        if w.shape[1] != self.info()["row_words"]:
+            raise HsError(HS_ERR_INVALID, f"rows of {w.shape[1]} words for a filter set of {self.info()['row_words']}-word rows")
+        _check(lib().hs_filter_set_write_bits(self._h, int(first), w.shape[0], w.ctypes.data))
+
+    def write_dev(self, first, torch_tensor, stream=0):
+        """Rows first.. from a contiguous torch bool / uint8 tensor on the set's device (count x n, or n); asynchronous on `stream`."""
+        t = torch_tensor
+        if t.element_size() != 1 or not t.is_contiguous():
+            raise HsError(HS_ERR_INVALID, "write_dev takes a contiguous bool / uint8 tensor")
+        count, n = (1, t.shape[0]) if t.dim() == 1 else (t.shape[0], t.shape[1])
+        if n != self.info()["n"]:
+            raise HsError(HS_ERR_INVALID, f"rows of {n} bytes for a filter set over {self.info()['n']} ids")
+        _check(lib().hs_filter_set_write_dev(self._h, int(first), count, t.data_ptr(), stream))
+
+    def read(self, f):
+        """Row f unpacked: n uint8 (0 / 1)."""
+        out = np.empty(self.info()["n"], np.uint8)
+        _check(lib().hs_filter_set_read(self._h, int(f), out.ctypes.data))
+        return out
 
 
 def debug_flat_plan(n, ef, nq):
@@ -567,6 +659,28 @@ class Index:
         _check(lib().hs_search_batch_filtered(self._h, q.ctypes.data, nq, k, a.ctypes.data, labels.ctypes.data, dists.ctypes.data,
                                               cnt.ctypes.data, stats.ctypes.data if want_stats else None))
         return dict(labels=labels, dists=dists, cnt=cnt, stats=stats)
+
+    def search_filter_set(self, queries, k, fs, filter_of_query, want_stats=False):
+        """hs_search_batch_filter_set: search_filtered with query i under filter filter_of_query[i] of the FilterSet `fs`."""
+        q = np.ascontiguousarray(queries, np.float32)
+        foq = np.ascontiguousarray(filter_of_query, np.uint32)
+        nq = q.shape[0]
+        if foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels = np.empty((nq, k), np.uint64)
+        dists = np.empty((nq, k), np.float32)
+        cnt = np.empty(nq, np.uint32)
+        stats = np.empty((nq, 4), np.uint32) if want_stats else None
+        _check(lib().hs_search_batch_filter_set(self._h, fs._h, q.ctypes.data, nq, k, foq.ctypes.data, labels.ctypes.data,
+                                                dists.ctypes.data, cnt.ctypes.data, stats.ctypes.data if want_stats else None))
+        return dict(labels=labels, dists=dists, cnt=cnt, stats=stats)
+
+    def search_filter_set_dev(self, d_queries, k, fs, d_filter_of_query, d_labels, d_dists, d_counts, d_stats=None, stream=0):
+        """hs_search_batch_filter_set_dev: device tensors (queries f32 nq x d, filter indices int32 nq, labels int64 nq x k, dists
+        f32 nq x k, counts int32 nq, stats int32 nq x 4) + HIP stream; asynchronous, pair with check(stream)."""
+        _check(lib().hs_search_batch_filter_set_dev(self._h, fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                                    d_filter_of_query.data_ptr(), d_labels.data_ptr(), d_dists.data_ptr(),
+                                                    d_counts.data_ptr(), d_stats.data_ptr() if d_stats is not None else None, stream))
 
     def search_raw(self, queries, k, mode=HS_MODE_SLIM_IDS):
         q = np.ascontiguousarray(queries, np.float32)

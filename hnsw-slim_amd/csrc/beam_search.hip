@@ -40,6 +40,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 #include "dist_recipe.hpp"
 #include "engine.hpp"
@@ -104,9 +105,9 @@ size_t strict_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t h
 size_t fast_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots) {
   return fast_layout(dim, ef, cand_cap, hash_slots).total;
 }
-bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
+bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k, bool has_filter) {
   // ef == k runs the boundary-watching variant, compiled for ef <= 128 only
-  return ix.tile0 != nullptr && ix.threshold_level == 0 && (ef > k || (ef == k && ef <= 128 && !ix.has_deleted)) && ef <= 512;
+  return ix.tile0 != nullptr && ix.threshold_level == 0 && (ef > k || (ef == k && ef <= 128 && !ix.has_deleted && !has_filter)) && ef <= 512;
 }
 #endif
 
@@ -434,6 +435,58 @@ __device__ __forceinline__ void write_stats(const SearchArgs &a, uint32_t qi, co
   }
 }
 
+// ---- filter sets (engine.hpp FilterArgs) ---------------------------------------------------------------------------------
+// F = NoFilter: the kernels as they are without a filter set (nothing below is compiled in).  F = FilterArgs: the filter-set
+// entry points, hs::strict_kernel / hs::fast_kernel overloads that take the set as a kernel argument of its own.
+struct NoFilter {};
+template <typename F> constexpr bool has_filter() { return !std::is_same<F, NoFilter>::value; }
+// The bitmap row query qi searches under.  bad: its filter index lies outside the set (no row is touched; the caller answers with
+// refuse_query).  qi is the query's index in the launch's arrays, so the ordered pass (order[]), a launch group at an offset and
+// the re-run pass all come to the same row.
+__device__ __forceinline__ const uint32_t *filter_row(const NoFilter &, uint32_t, bool &bad) { bad = false; return nullptr; }
+__device__ __forceinline__ const uint32_t *filter_row(const FilterArgs &f, uint32_t qi, bool &bad) {
+  const uint32_t r = uni(f.of_query[qi]);
+  bad = r >= f.nf;
+  return bad ? nullptr : f.rows + (size_t)r * f.stride;
+}
+__device__ __forceinline__ bool filter_allows(const uint32_t *frow, uint32_t id) {   // id wave-uniform
+  return ((uni(frow[id >> 5]) >> (id & 31u)) & 1u) != 0;
+}
+// Filter index outside the set: count 0, padding labels and distances, the sticky counter hs_search_check reports.
+__device__ __forceinline__ void refuse_query(const SearchArgs &a, const FilterArgs &f, uint32_t qi, int lane) {
+  for (uint32_t i = lane; i < a.k; i += 64) {
+    if (a.out_labels32) a.out_labels32[(size_t)qi * a.k + i] = 0xFFFFFFFFu;
+    if (a.out_labels64) a.out_labels64[(size_t)qi * a.k + i] = ~0ull;
+    if (a.out_dists) a.out_dists[(size_t)qi * a.k + i] = __builtin_inff();
+  }
+  if (lane == 0) {
+    if (a.out_counts) a.out_counts[qi] = 0;
+    Counters c{};
+    write_stats(a, qi, c);
+    a.status[qi] = ST_DONE;
+    atomicAdd(f.bad, 1u);
+  }
+}
+__device__ __forceinline__ void refuse_query(const SearchArgs &, const NoFilter &, uint32_t, int) {}
+// Which of the tile's neighbours nid[0 .. cnt) are excluded (marked deleted, or filter bit clear: hnswalg.h:442-444,
+// hnswalg_slim.h:578-580).  Lane j fetches the bitmap word -- and, on an index with delete marks, the mark -- of ITS neighbour with
+// vector loads, issued as soon as the tile's ids are known so that they travel with the row gathers; after the distances one
+// ballot gives the mask, and the serial accept loop tests bit j of it in registers: no load on that chain.
+struct ExclLoad { uint32_t word, del, bit; };
+__device__ __forceinline__ ExclLoad excl_issue(const DevIndex &ix, const uint32_t *frow, const uint32_t *nid, uint32_t cnt, int lane) {
+  ExclLoad e{0xFFFFFFFFu, 0u, 0u};
+  if ((uint32_t)lane < cnt) {
+    const uint32_t nb = nid[lane];
+    e.bit = nb & 31u;
+    e.word = frow[nb >> 5];
+    if (ix.has_deleted) e.del = ix.deleted[nb];
+  }
+  return e;
+}
+__device__ __forceinline__ unsigned long long excl_mask(const ExclLoad &e) {
+  return hs_ballot(e.del != 0 || !((e.word >> e.bit) & 1u));
+}
+
 // =================================================================================================
 // strict kernel
 // =================================================================================================
@@ -443,10 +496,11 @@ struct SState { uint32_t top_size, cand_size; float lb; };
 // Returns 0 ok, 1 visited-set overflow, 2 candidate-heap overflow.
 // (narrow rows exist for dim % 16 == 0 only: their strict kernel takes the runtime-dim recipe without the other dims' branches)
 template <typename ROW> constexpr int strict_d16() { return RowKind<ROW>::narrow ? 0 : -1; }
-template <int METRIC, typename ROW = float>
+// (frow: the query's filter row in the filter-set kernels, FILT; there `bare` is false)
+template <int METRIC, typename ROW = float, bool FILT = false>
 __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, bool bare, const float *qv, Pair *top,
                            Pair *cand, Visited &vis, uint32_t *nid, float *nd, SState &st, Counters &c, int lane,
-                           RowSrc<ROW> rs = RowSrc<ROW>()) {
+                           RowSrc<ROW> rs = RowSrc<ROW>(), const uint32_t *frow = nullptr) {
   const uint32_t ef = a.ef;
   HS_T0();
   while (true) {
@@ -496,8 +550,12 @@ __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, b
       vis_commit(vis, cnt);
       c.n_dist += cnt;
       HS_LAP(c, 2);
+      ExclLoad ex{0xFFFFFFFFu, 0u, 0u};
+      if constexpr (FILT) ex = excl_issue(ix, frow, nid, cnt, lane);
       wave_dists<METRIC, strict_d16<ROW>()>(ix, qv, nid, nd, cnt, lane, NoHook(), rs);  // :395-396
       wave_sync();
+      unsigned long long excl = 0;
+      if constexpr (FILT) excl = excl_mask(ex);
       HS_LAP(c, 3);
       uint32_t ts = st.top_size, cs = st.cand_size;
       float lb = st.lb;
@@ -510,7 +568,10 @@ __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, b
             cand[cs].id = nb;
             cs++;
             push_heap(cand, (long)cs, GreaterD());
-            if (bare || !ix.deleted[nb]) {  // :418
+            bool keep;
+            if constexpr (FILT) keep = !((excl >> j) & 1ull);
+            else keep = bare || !ix.deleted[nb];
+            if (keep) {  // :418
               top[ts].d = d;
               top[ts].id = nb;
               ts++;
@@ -533,9 +594,10 @@ __device__ int strict_beam(const DevIndex &ix, const SearchArgs &a, int level, b
   return 0;
 }
 
-template <int METRIC, typename ROW = float>
+template <int METRIC, typename ROW = float, typename F = NoFilter>
 __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem,
-                                  RowSrc<ROW> rs = RowSrc<ROW>()) {
+                                  RowSrc<ROW> rs = RowSrc<ROW>(), const F fa = F()) {
+  constexpr bool FILT = has_filter<F>();
   const int lane = threadIdx.x;
   const StrictLds L = strict_layout(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots);
   float *qv = reinterpret_cast<float *>(smem + L.off_q);
@@ -551,6 +613,9 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   for (int i = 0; i < 8; i++) c.t[i] = 0;
 #endif
   HS_T0();
+  bool filt_bad;
+  const uint32_t *frow = filter_row(fa, qi, filt_bad);
+  if (FILT && filt_bad) { refuse_query(a, fa, qi, lane); return; }
   uint32_t cur;
   float curdist;
   Visited vis;
@@ -558,8 +623,9 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   HS_LAP(c, 5);
 
   // ---- level-0 (and threshold-level) beams ----------------------------------------------------
-  const bool bare = !ix.has_deleted;  // hnswalg_slim.h:2114, hnswalg.h:1421 (no filter on this path)
-  const bool ep_deleted = uni(ix.deleted[cur]) != 0;
+  const bool bare = !FILT && !ix.has_deleted;  // hnswalg_slim.h:2114 / :1884, hnswalg.h:1421
+  bool ep_deleted = uni(ix.deleted[cur]) != 0;
+  if constexpr (FILT) ep_deleted = ep_deleted || !filter_allows(frow, cur);
   if (ix.kind == 0 && (bare || !ep_deleted)) c.n_dist++;  // searchBaseLayerST recomputes the entry distance (hnswalg.h:347-351)
   wave_sync();
   if (lane == 0) {
@@ -585,7 +651,7 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   }
   int rc = 0;
   for (int lvl = min(ix.threshold_level, ix.maxlevel); lvl > 0 && rc == 0; lvl--) {  // hnswalg_slim.h:2108-2113
-    rc = strict_beam<METRIC>(ix, a, lvl, /*bare=*/false, qv, top, cand, vis, nid, nd, st, c, lane, rs);
+    rc = strict_beam<METRIC, ROW, FILT>(ix, a, lvl, /*bare=*/false, qv, top, cand, vis, nid, nd, st, c, lane, rs, frow);
     // next beam starts from candidate_set <- copy of top_candidates (+ make_heap) (:228-233, :327-332)
     wave_sync();
     if (lane == 0) {
@@ -594,7 +660,7 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
     }
     st.cand_size = st.top_size;
   }
-  if (rc == 0) rc = strict_beam<METRIC>(ix, a, 0, bare, qv, top, cand, vis, nid, nd, st, c, lane, rs);
+  if (rc == 0) rc = strict_beam<METRIC, ROW, FILT>(ix, a, 0, bare, qv, top, cand, vis, nid, nd, st, c, lane, rs, frow);
   wave_sync();
   if (rc != 0) {
     flag_query(a, qi, ST_OVERFLOW, rc - 1, lane);
@@ -683,10 +749,12 @@ __device__ __forceinline__ void top_insert(float (&tk)[S], uint32_t (&ti)[S], ui
 // pushes, one byte per expansion says how many belong to each, and they are replayed with the pops in between through the
 // same libstdc++ mechanics; the search then continues on the heap path.  Continuous data never leaves the flat path, integer
 // data (SIFT) does in about a quarter of the queries at ef=70, and pays then what the heap would have cost it anyway.
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true, bool FLAT = false, typename ROW = float>
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true, bool FLAT = false, typename ROW = float, typename F = NoFilter>
 __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const uint32_t qi, unsigned char *smem,
-                               RowSrc<ROW> rs = RowSrc<ROW>()) {
+                               RowSrc<ROW> rs = RowSrc<ROW>(), const F fa = F()) {
   static_assert(!FLAT || (BARE && !WB), "the flat start needs an index without delete marks and ef > k");
+  constexpr bool FILT = has_filter<F>();
+  static_assert(!FILT || !BARE, "a filter set takes the !bare_bone branches");
   const int lane = threadIdx.x;
   const FastLds L = fast_layout(ix.dim, a.ef, a.cand_cap, a.hash_slots);
   float *qv = reinterpret_cast<float *>(smem + L.off_q);
@@ -708,6 +776,14 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
   for (int i = 0; i < 8; i++) c.t[i] = 0;
 #endif
   HS_T0();
+  bool filt_bad;
+  const uint32_t *frow = filter_row(fa, qi, filt_bad);
+  if (FILT && filt_bad) {
+    // phase 1 leaves an entry for the order kernel; the launch that would have searched answers
+    if (a.phase == 1) { if (lane == 0) a.entry[qi] = make_uint4(0u, 0u, 0u, 0u); }
+    else refuse_query(a, fa, qi, lane);
+    return 0;
+  }
   uint32_t cur;
   float curdist;
   Visited vis;
@@ -736,7 +812,8 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
   HS_LAP(c, 5);
 
   constexpr bool bare = BARE;   // no delete marks / filter anywhere in the index (own instantiation, see WB)
-  const bool ep_deleted = uni(ix.deleted[cur]) != 0;
+  bool ep_deleted = uni(ix.deleted[cur]) != 0;
+  if constexpr (FILT) ep_deleted = ep_deleted || !filter_allows(frow, cur);
   if (ix.kind == 0 && (bare || !ep_deleted)) c.n_dist++;  // hnswalg.h:347-351
   float tk[S];
   uint32_t ti[S];
@@ -1020,6 +1097,8 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
     if (!vis.qbits) vis_commit(vis, cnt);
     c.n_dist += cnt;
     HS_LAP(c, 2);
+    ExclLoad ex{0xFFFFFFFFu, 0u, 0u};
+    if constexpr (FILT) ex = excl_issue(ix, frow, nid, cnt, lane);
     // row loads go out first; the pushes of the previous expansion (:408-411, adjacency order) and pop_heap (:353-354)
     // work on the LDS heap while they are in flight
     auto heap_hook = [&]() {
@@ -1043,6 +1122,8 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
     HS_LAP(c, 3);
     const float my_d = (uint32_t)lane < cnt ? nd[lane] : FLT_MAX;
     const uint32_t my_id = (uint32_t)lane < cnt ? nid[lane] : 0;
+    unsigned long long excl = 0;
+    if constexpr (FILT) excl = excl_mask(ex);
     {
       // root of candidate_set once this expansion's pushes are in: the nearest new neighbour if it is accepted and
       // strictly nearer than the heap's root, else that root
@@ -1076,7 +1157,10 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
       if (top_size < ef || lb > d) {  // :403-404
         const uint32_t nb = __builtin_amdgcn_readlane(my_id, j);
         pending |= 1ull << j;
-        if (bare || uni(ix.deleted[nb]) == 0) {
+        bool keep;
+        if constexpr (FILT) keep = !((excl >> j) & 1ull);   // register-only: the loads were taken per lane, before the distances
+        else keep = bare || uni(ix.deleted[nb]) == 0;
+        if (keep) {
           const bool evicts = top_size == ef;
           const float evicted = evicts ? top_key_at<S>(tk, ef - 1) : 0.f;   // d < this key (strict), so it is the one dropped
           top_insert<S>(tk, ti, top_size, ef, d, nb, lane);  // :418-448
@@ -1176,7 +1260,7 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
 // The three entry points of each kernel differ in the rows they read and in nothing else: hs::strict_kernel / hs::fast_kernel the
 // resident fp32 rows (ix.vec), hs::*_kernel_u8 / hs::*_kernel_f16 the index's narrow copy, handed over as a kernel argument of
 // its own (DevIndex and SearchArgs are what they were).
-#define HS_STRICT_KERNEL_BODY(RS)                                                                                              \
+#define HS_STRICT_KERNEL_BODY(RS, FA)                                                                                           \
   extern __shared__ __align__(16) unsigned char smem[];                                                                        \
   /* pass 0: one query per workgroup, every query.  Re-run passes: 64 statuses per read, then the (normally zero) flagged */  \
   /* queries of the block one after the other.  (One call site, so that the search body is inlined and the kernel         */  \
@@ -1197,34 +1281,49 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
         if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                              \
         continue;                                                                                                              \
       }                                                                                                                        \
-      search_one_strict<METRIC>(ix, a, qi, smem, RS);                                                                          \
+      search_one_strict<METRIC>(ix, a, qi, smem, RS, FA);                                                                      \
       wave_sync();                                                                                                             \
     }                                                                                                                          \
   }
 #if HS_TU_ROWS == 0
 template <int METRIC>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel(DevIndex ix, SearchArgs a) {
-  HS_STRICT_KERNEL_BODY(RowSrc<float>())
+  HS_STRICT_KERNEL_BODY(RowSrc<float>(), NoFilter())
+}
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel(DevIndex ix, SearchArgs a, FilterArgs f) {
+  HS_STRICT_KERNEL_BODY(RowSrc<float>(), f)
 }
 #define HS_STRICT_KERNEL strict_kernel
 #define HS_FAST_KERNEL fast_kernel
 #define HS_ROWS_ARG
+#define HS_ROWS_PARAM
 #elif HS_TU_ROWS == 1
 template <int METRIC>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
-  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows})
+  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows}, NoFilter())
+}
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows, FilterArgs f) {
+  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows}, f)
 }
 #define HS_STRICT_KERNEL strict_kernel_u8
 #define HS_FAST_KERNEL fast_kernel_u8
 #define HS_ROWS_ARG , reinterpret_cast<const uint8_t *>(rows)
+#define HS_ROWS_PARAM , const uint8_t *
 #else
 template <int METRIC>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
-  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows})
+  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows}, NoFilter())
+}
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows, FilterArgs f) {
+  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows}, f)
 }
 #define HS_STRICT_KERNEL strict_kernel_f16
 #define HS_FAST_KERNEL fast_kernel_f16
 #define HS_ROWS_ARG , reinterpret_cast<const _Float16 *>(rows)
+#define HS_ROWS_PARAM , const _Float16 *
 #endif
 // Fast kernel.  rc 3 = a tie had to be resolved but the insertion log did not fit: left to the strict pass.
 // Wavefronts per SIMD the register allocation aims at.  A wavefront alone on a CU is only 25 % faster per expansion than one
@@ -1239,7 +1338,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) st
 __host__ __device__ constexpr int fast_waves(int d16, int s) {
   return (d16 > 16 || (d16 == -1 && s >= 4)) ? 3 : ((d16 == 4 || d16 == 6 || d16 == 8 || d16 == 16) && s <= 2) ? HS_SHORT_WAVES : 4;
 }
-#define HS_FAST_KERNEL_BODY(RS)                                                                                                \
+#define HS_FAST_KERNEL_BODY(RS, FA)                                                                                            \
   extern __shared__ __align__(16) unsigned char smem[];                                                                        \
   for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {                                                                 \
     const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;                                                          \
@@ -1248,7 +1347,7 @@ __host__ __device__ constexpr int fast_waves(int d16, int s) {
       if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                                \
       continue;                                                                                                                \
     }                                                                                                                          \
-    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, RS);                                \
+    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, RS, FA);                            \
     if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;                                                                 \
     wave_sync();                                                                                                               \
   }
@@ -1257,21 +1356,36 @@ __host__ __device__ constexpr int fast_waves(int d16, int s) {
 #if HS_TU_ROWS == 0
 template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel(DevIndex ix, SearchArgs a) {
-  HS_FAST_KERNEL_BODY(RowSrc<float>())
+  HS_FAST_KERNEL_BODY(RowSrc<float>(), NoFilter())
+}
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel(DevIndex ix, SearchArgs a, FilterArgs f) {
+  HS_FAST_KERNEL_BODY(RowSrc<float>(), f)
 }
 #elif HS_TU_ROWS == 1
 template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
-  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows})
+  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows}, NoFilter())
+}
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows, FilterArgs f) {
+  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows}, f)
 }
 #else
 template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
-  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows})
+  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows}, NoFilter())
+}
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows, FilterArgs f) {
+  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows}, f)
 }
 #endif
 
-// (`rows`: the narrow copy in the narrow objects, nothing in the fp32 ones)
+// Each kernel name is an overload pair: (DevIndex, SearchArgs[, rows]) and the filter-set form with FilterArgs behind it.
+#define HS_KFN(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM)>(k)
+#define HS_KFN_FILT(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM, FilterArgs)>(k)
+// (`rows`: the narrow copy in the narrow objects, nothing in the fp32 ones; then the filter set, in the filter-set form)
 template <typename K, typename... R>
 static hipError_t launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, R... rows) {
   if (a.nq == 0) return hipSuccess;
@@ -1364,56 +1478,63 @@ hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStr
 
 // delete marks / filters: the variant with the reference's !bare_bone branches (runtime-dim and d=128 only)
 template <int METRIC, int D16>
-static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr) {
-  if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 128) return launch(HS_FAST_KERNEL<METRIC, 2, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 256) return launch(HS_FAST_KERNEL<METRIC, 4, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
-  return launch(HS_FAST_KERNEL<METRIC, 8, D16, false, false>, ix, a, lds, stream HS_ROWS_ARG);
+static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr,
+                                  const FilterArgs *f = nullptr) {
+  if (f) {   // under a filter set: the same shapes, the set as a kernel argument
+    if (a.ef <= 64) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+    if (a.ef <= 128) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+    if (a.ef <= 256) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+    return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+  }
+  if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 128) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 256) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+  return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
 }
 template <int METRIC, int D16>
 static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr) {
   if (a.k == a.ef) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
-    if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16, true>, ix, a, lds, stream HS_ROWS_ARG);
-    return launch(HS_FAST_KERNEL<METRIC, 2, D16, true>, ix, a, lds, stream HS_ROWS_ARG);
+    if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+    return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
   }
-  if (a.ef <= 64) return launch(HS_FAST_KERNEL<METRIC, 1, D16>, ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 128) return launch(HS_FAST_KERNEL<METRIC, 2, D16>, ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 256) return launch(HS_FAST_KERNEL<METRIC, 4, D16>, ix, a, lds, stream HS_ROWS_ARG);
-  return launch(HS_FAST_KERNEL<METRIC, 8, D16>, ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 128) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+  if (a.ef <= 256) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+  return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16>)), ix, a, lds, stream HS_ROWS_ARG);
 }
 
 #if HS_TU_ROWS == 0
-hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
-hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
-hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
-hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream);
+hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
+hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
+hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
+hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
 #if HS_TU_HAS_L2
-hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  return launch(strict_kernel<METRIC_L2>, ix, a, lds, stream);
+hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return f ? launch(HS_KFN_FILT(strict_kernel<METRIC_L2>), ix, a, lds, stream, *f) : launch(HS_KFN(strict_kernel<METRIC_L2>), ix, a, lds, stream);
 }
 // (an index whose fp32 rows were dropped, hs_index_set_f32_resident(ix, 0), is served by the narrow launchers of narrow_rows.hip:
 //  a launch that would read ix.vec is refused here instead of dereferencing null on the device)
-hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f) {
   if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
   const size_t lds = strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots);
-  return ix.metric == METRIC_L2 ? launch_strict_l2(ix, a, lds, stream) : launch_strict_ip(ix, a, lds, stream);
+  return ix.metric == METRIC_L2 ? launch_strict_l2(ix, a, lds, stream, f) : launch_strict_ip(ix, a, lds, stream, f);
 }
-hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
+hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f) {
   if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
   const size_t lds = fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots);
-  return ix.metric == METRIC_L2 ? launch_fast_l2(ix, a, lds, stream) : launch_fast_ip(ix, a, lds, stream);
+  return ix.metric == METRIC_L2 ? launch_fast_l2(ix, a, lds, stream, f) : launch_fast_ip(ix, a, lds, stream, f);
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  return launch(strict_kernel<METRIC_IP>, ix, a, lds, stream);
+hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return f ? launch(HS_KFN_FILT(strict_kernel<METRIC_IP>), ix, a, lds, stream, *f) : launch(HS_KFN(strict_kernel<METRIC_IP>), ix, a, lds, stream);
 }
 #endif
 #if HS_TU_HAS_L2
-hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  if (ix.has_deleted) {
-    if (ix.dim == 128) return launch_fast_del<METRIC_L2, 8>(ix, a, lds, stream);
-    return (ix.dim & 15u) ? launch_fast_del<METRIC_L2, -1>(ix, a, lds, stream) : launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream);
+hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  if (ix.has_deleted || f) {   // a filter set is planned as delete marks are
+    if (ix.dim == 128) return launch_fast_del<METRIC_L2, 8>(ix, a, lds, stream, nullptr, f);
+    return (ix.dim & 15u) ? launch_fast_del<METRIC_L2, -1>(ix, a, lds, stream, nullptr, f) : launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, nullptr, f);
   }
   // compile-time dims for the common shapes (the runtime-dim kernel is 1.15-1.7x slower: measured at d=64 and on DEEP-10M, d=96)
   switch (ix.dim) {
@@ -1433,9 +1554,9 @@ hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, h
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  if (ix.has_deleted)
-    return (ix.dim & 15u) ? launch_fast_del<METRIC_IP, -1>(ix, a, lds, stream) : launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream);
+hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  if (ix.has_deleted || f)
+    return (ix.dim & 15u) ? launch_fast_del<METRIC_IP, -1>(ix, a, lds, stream, nullptr, f) : launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, nullptr, f);
   switch (ix.dim) {   // text / image embeddings
     case 768: return launch_fast_md<METRIC_IP, 48>(ix, a, lds, stream);    // COHERE
     case 512: return launch_fast_md<METRIC_IP, 32>(ix, a, lds, stream);
@@ -1453,19 +1574,19 @@ hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, h
 #define HS_NARROW_FN(name, metric) name##_f16_##metric
 #endif
 #if HS_TU_HAS_L2
-hipError_t HS_NARROW_FN(launch_strict, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
-  return launch(HS_STRICT_KERNEL<METRIC_L2>, ix, a, lds, stream HS_ROWS_ARG);
+hipError_t HS_NARROW_FN(launch_strict, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG);
 }
-hipError_t HS_NARROW_FN(launch_fast, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
-  return ix.has_deleted ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, rows) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, rows);
+hipError_t HS_NARROW_FN(launch_fast, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return (ix.has_deleted || f) ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, rows, f) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, rows);
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t HS_NARROW_FN(launch_strict, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
-  return launch(HS_STRICT_KERNEL<METRIC_IP>, ix, a, lds, stream HS_ROWS_ARG);
+hipError_t HS_NARROW_FN(launch_strict, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG);
 }
-hipError_t HS_NARROW_FN(launch_fast, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream) {
-  return ix.has_deleted ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, rows) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, rows);
+hipError_t HS_NARROW_FN(launch_fast, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
+  return (ix.has_deleted || f) ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, rows, f) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, rows);
 }
 #endif
 #endif

@@ -114,6 +114,7 @@ struct hs_index {
     DevBuf<float> aq, adist;
     DevBuf<uint32_t> al32, acnt, astats;
     DevBuf<uint64_t> al64;
+    DevBuf<uint32_t> afoq;              // hs_search_batch_filter_set: the per-query filter indices of the call in flight
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
   std::mutex ws_mu;
@@ -140,6 +141,20 @@ struct hs_index {
   bool has_dataset = false;
   uint32_t *trace_ptr = nullptr;   // hs_slimq_trace only
   uint32_t trace_cap = 0;
+};
+
+// A filter set (hs_filter_set_*): nf bitmap rows over the n internal ids the index had when the set was created (filter_set.hip).
+struct hs_filter_set {
+  int device = 0;
+  size_t n = 0, nf = 0, row_words = 0;
+  DevBuf<uint32_t> bits;     // nf x row_words
+  DevBuf<uint8_t> stage;     // hs_filter_set_write: bounded staging of the host bytes
+  DevBuf<uint8_t> unpacked;  // hs_filter_set_read: one row as bytes
+};
+// What a search under a filter set hands down to the launch plan (null = no filter set).
+struct FilterUse {
+  const hs_filter_set *fs;
+  const uint32_t *d_of_query;   // nq filter indices (device)
 };
 
 static uint32_t next_pow2(uint32_t v) {
@@ -889,7 +904,7 @@ static constexpr size_t kOrderMinQueries = 6144;
 
 static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, size_t k, int mode, uint32_t *l32,
                                   uint64_t *l64, float *dd, uint32_t *cnt, uint32_t *stats, Pair *raw, uint32_t *rawsz,
-                                  hipStream_t stream, bool first_group, size_t nq_total) {
+                                  hipStream_t stream, bool first_group, size_t nq_total, const FilterUse *fu = nullptr) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (k == 0) return fail(HS_ERR_INVALID, "k must be > 0");
   if (mode != HS_MODE_SLIM_IDS && mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "bad mode");
@@ -915,6 +930,10 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   }
   if (first_group) w->last_nq += nq_total;   // queries since the last hs_search_check on this stream
   SearchArgs a{};
+  const bool filt = fu != nullptr;   // a filter set: planned as delete marks are (the reference's !bare_bone branches)
+  FilterArgs fa{};
+  if (filt) fa = FilterArgs{fu->fs->bits.p, fu->d_of_query, w->counters.p + 12, (uint32_t)fu->fs->row_words, (uint32_t)fu->fs->nf};
+  const FilterArgs *fap = filt ? &fa : nullptr;
   a.queries = d_q; a.nq = (uint32_t)nq; a.k = (uint32_t)k; a.ef = sh.ef;
   a.cand_cap = sh.cand_cap; a.hash_slots = sh.hash_slots; a.mode = mode;
   a.mark_ep = (ix->info.kind == HS_KIND_SLIM && mode == HS_MODE_PQ) ? 1 : 0;
@@ -943,7 +962,7 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
     }
   }
   const uint32_t fast_hash = sh.q_bits ? sh.q_hash_slots : sh.hash_slots;
-  const bool fast = !ix->exact_order && !raw && fast_supported(ix->dev, sh.ef, (uint32_t)k) &&
+  const bool fast = !ix->exact_order && !raw && fast_supported(ix->dev, sh.ef, (uint32_t)k, filt) &&
                     fast_lds_bytes((uint32_t)ix->info.dim, sh.ef, sh.cand_cap_fast, fast_hash) <= kLdsPerCU;
   // scratch shares of the fast kernel's launches / of everything else
   auto fast_scratch = [&](bool on) {
@@ -965,13 +984,13 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   // only) has none and is never chosen here: its requests fall through to the fast kernel.
   const bool f32_free = !ix->f32_resident;
   const int fmt = ix->row_fmt;
-  auto fast_go = [&]() { return f32_free ? launch_fast_narrow(ix->dev, a, ix->narrow.p, fmt, stream) : launch_fast(ix->dev, a, stream); };
-  auto strict_go = [&]() { return f32_free ? launch_strict_narrow(ix->dev, a, ix->narrow.p, fmt, stream) : launch_strict(ix->dev, a, stream); };
-  const bool lean = lean_asked && !f32_free && fast && sh.ef >= lean_min_ef && lean_supported(ix->dev, sh.ef, (uint32_t)k) &&
+  auto fast_go = [&]() { return f32_free ? launch_fast_narrow(ix->dev, a, ix->narrow.p, fmt, stream, fap) : launch_fast(ix->dev, a, stream, fap); };
+  auto strict_go = [&]() { return f32_free ? launch_strict_narrow(ix->dev, a, ix->narrow.p, fmt, stream, fap) : launch_strict(ix->dev, a, stream, fap); };
+  const bool lean = lean_asked && !filt && !f32_free && fast && sh.ef >= lean_min_ef && lean_supported(ix->dev, sh.ef, (uint32_t)k) &&
                     lean_lds_bytes((uint32_t)ix->info.dim, sh.ef, sh.l_cand_cap, sh.q_bits ? sh.q_hash_slots : sh.l_hash_slots) <= kLdsPerCU;
   static const bool flatk_off = kernel_env && (!strcmp(kernel_env, "lean") || !strcmp(kernel_env, "fast"));
   const FlatPlan fp = plan_flat(ix, sh.ef, nq);
-  const bool flatk = !flatk_off && !lean_forced && fast && fp.ok && flatk_supported(ix->dev, sh.ef, (uint32_t)k);
+  const bool flatk = !flatk_off && !lean_forced && !filt && fast && fp.ok && flatk_supported(ix->dev, sh.ef, (uint32_t)k);
   const bool narrow = flatk && ix->row_fmt != ROWS_F32;   // the same launch plan over the narrow copy of the rows
   auto flat_go = [&]() { return narrow ? launch_flatk_narrow(ix->dev, a, ix->narrow.p, ix->row_fmt, stream) : launch_flatk(ix->dev, a, stream); };
   ix->last_kernel = narrow ? (ix->row_fmt == ROWS_U8 ? "hs::flat_kernel_u8" : "hs::flat_kernel_f16") : flatk ? "hs::flat_kernel" : lean ? "hs::lean_kernel"
@@ -1056,15 +1075,17 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
 
 static hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k, int mode, uint32_t *l32,
                             uint64_t *l64, float *dd, uint32_t *cnt, uint32_t *stats, Pair *raw, uint32_t *rawsz,
-                            hipStream_t stream) {
+                            hipStream_t stream, const FilterUse *fu = nullptr) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "nq too large");
   const size_t dim = ix->info.dim, ef = std::max(ix->ef, k);
   for (size_t off = 0; off < nq || off == 0; off += kMaxLaunchQueries) {
     const size_t m = std::min(kMaxLaunchQueries, nq - off);
+    // (a group's kernels index every per-query array from the group's first query: so the filter indices too)
+    const FilterUse g{fu ? fu->fs : nullptr, fu ? fu->d_of_query + off : nullptr};
     hs_status s = search_dev_group(ix, d_q + off * dim, m, k, mode, l32 ? l32 + off * k : nullptr, l64 ? l64 + off * k : nullptr,
                                    dd ? dd + off * k : nullptr, cnt ? cnt + off : nullptr, stats ? stats + off * 4 : nullptr,
-                                   raw ? raw + off * ef : nullptr, rawsz ? rawsz + off : nullptr, stream, off == 0, nq);
+                                   raw ? raw + off * ef : nullptr, rawsz ? rawsz + off : nullptr, stream, off == 0, nq, fu ? &g : nullptr);
     if (s != HS_OK || nq == 0) return s;
   }
   return HS_OK;
@@ -1072,7 +1093,7 @@ static hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k,
 
 hs_status hs_search_check(hs_index *ix, void *stream) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
-  uint32_t c[12];
+  uint32_t c[13];   // [12]: queries of filter-set searches whose filter index was outside the set
   HIP_TRY(hipSetDevice(ix->device));
   hs_index::StreamWs *w = ix->stream_ws((hipStream_t)stream);
   if (!w->counters.p) return HS_OK;  // nothing was launched on this stream
@@ -1088,6 +1109,8 @@ hs_status hs_search_check(hs_index *ix, void *stream) {
                        nq, c[0], c[1], c[2], c[3], c[8], c[9], ix->grow_hash, ix->grow_cand);
   if ((size_t)c[3] * 10 > nq && ix->grow_hash < 8 && !ix->user_hash_slots) ix->grow_hash++;
   if ((size_t)(c[1] + c[5]) * 100 > nq && ix->grow_cand < 4 && !ix->user_cand_cap) ix->grow_cand++;
+  if (c[12] > 0)
+    return fail(HS_ERR_INVALID, std::to_string(c[12]) + " queries named a filter index outside the filter set (count 0 returned for them)");
   if (ix->info.kind == HS_KIND_SLIMQ) {
     if (c[8] > 0) return fail(HS_ERR_CAPACITY, std::to_string(c[8]) + " queries expanded more nodes than the 64 KiB on-chip set holds");
     return HS_OK;
@@ -1155,7 +1178,7 @@ static void *mapped_device_pointer(const void *host) {
 // the staging copies (10k-query batches: 13.9 vs 13.6 M q/s in favour of staging).
 static constexpr size_t kZeroCopyQueryBytes = 2u << 20;
 static hs_status search_async(hs_index *ix, const float *queries, size_t nq, size_t k, int mode, uint32_t *l32, uint64_t *l64,
-                              float *dd, uint32_t *cnt, uint32_t *stats, hipStream_t st) {
+                              float *dd, uint32_t *cnt, uint32_t *stats, hipStream_t st, const FilterUse *fu = nullptr) {
   if (!ix || !queries) return fail(HS_ERR_INVALID, "null argument");
   if (k == 0) return fail(HS_ERR_INVALID, "k must be > 0");
   if (nq == 0) return HS_OK;
@@ -1187,7 +1210,7 @@ static hs_status search_async(hs_index *ix, const float *queries, size_t nq, siz
   if (cdd) { HIP_TRY(w->adist.ensure(nq * k)); odd = w->adist.p; }
   if (ccnt) { HIP_TRY(w->acnt.ensure(nq)); ocnt = w->acnt.p; }
   if (cst) { HIP_TRY(w->astats.ensure(nq * 4)); ost = w->astats.p; }
-  hs_status s = search_dev(ix, dq, nq, k, mode, o32, o64, odd, ocnt, ost, nullptr, nullptr, st);
+  hs_status s = search_dev(ix, dq, nq, k, mode, o32, o64, odd, ocnt, ost, nullptr, nullptr, st, fu);
   if (s != HS_OK) return s;
   if (c32 && l32) HIP_TRY(hipMemcpyAsync(l32, w->al32.p, nq * k * 4, hipMemcpyDeviceToHost, st));
   if (c64 && l64) HIP_TRY(hipMemcpyAsync(l64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, st));
@@ -1455,6 +1478,161 @@ hs_status hs_search_batch_filtered(hs_index *ix, const float *queries, size_t nq
                             nullptr, nullptr);
   ix->dev = saved;
   return s;
+}
+
+// ---- filter sets ---------------------------------------------------------------------------------------------------------
+// nf bitmaps over the index's internal ids, resident on the index's device; a search names the set and one row per query, so
+// queries under different filters share a launch and nothing is uploaded or rebuilt per call.  The rows hold the functor's
+// answers only: the kernels test "marked deleted or bit clear" themselves (beam_search.hip), as the reference tests
+// "!isMarkedDeleted(id) && (*isIdAllowed)(label)" (hnswalg.h:348-349, 442-444; hnswalg_slim.h:578-580).
+size_t hs_filter_row_words(size_t n) { return ((n + 31) / 32 + 3) / 4 * 4; }
+
+hs_status hs_filter_pack(const uint8_t *allowed, size_t n, size_t nf, uint32_t *out_words) {
+  if ((!allowed && n * nf > 0) || !out_words) return fail(HS_ERR_INVALID, "null argument");
+  const size_t rw = hs_filter_row_words(n);
+  std::fill(out_words, out_words + nf * rw, 0u);
+  for (size_t f = 0; f < nf; f++)
+    for (size_t i = 0; i < n; i++)
+      if (allowed[f * n + i]) out_words[f * rw + (i >> 5)] |= 1u << (i & 31);
+  return HS_OK;
+}
+
+// The refusals of hs_search_batch_filtered, with its texts (the SlimQ one is search_dev_group's).
+static hs_status filter_index_ok(const hs_index *ix) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_INVALID, "SlimQ index: use hs_slimq_search_batch");
+  if (ix->info.kind == HS_KIND_SLIM && ix->info.threshold_level != 0)
+    return fail(HS_ERR_UNSUPPORTED, "filtered search on a Slim index with threshold_level > 0 is not supported");
+  return HS_OK;
+}
+
+hs_status hs_filter_set_create(hs_index *ix, size_t nf, hs_filter_set **out) {
+  if (!out) return fail(HS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  hs_status s = filter_index_ok(ix);
+  if (s != HS_OK) return s;
+  if (nf == 0) return fail(HS_ERR_INVALID, "a filter set needs at least one filter");
+  const size_t rw = hs_filter_row_words(ix->info.n);
+  if (nf > 0xFFFFFFFFu || nf * rw > (size_t)1 << 40) return fail(HS_ERR_INVALID, "filter set too large");
+  HIP_TRY(hipSetDevice(ix->device));
+  std::unique_ptr<hs_filter_set> fs(new hs_filter_set());
+  fs->device = ix->device; fs->n = ix->info.n; fs->nf = nf; fs->row_words = rw;
+  if (fs->bits.alloc(std::max<size_t>(nf * rw, 1)) != hipSuccess) return fail(HS_ERR_NOMEM, "Not enough memory: filter set of " + std::to_string(nf * rw * 4) + " bytes");
+  HIP_TRY(hipMemset(fs->bits.p, 0, std::max<size_t>(nf * rw, 1) * 4));
+  *out = fs.release();
+  return HS_OK;
+}
+
+void hs_filter_set_free(hs_filter_set *fs) {
+  if (!fs) return;
+  (void)hipSetDevice(fs->device);
+  delete fs;
+}
+
+static hs_status filter_rows_ok(const hs_filter_set *fs, size_t first, size_t count, const void *src) {
+  if (!fs || (!src && count > 0)) return fail(HS_ERR_INVALID, "null argument");
+  if (first > fs->nf || count > fs->nf - first)
+    return fail(HS_ERR_INVALID, "filter rows [" + std::to_string(first) + ", " + std::to_string(first + count) + ") outside a set of " + std::to_string(fs->nf));
+  return HS_OK;
+}
+
+hs_status hs_filter_set_write_dev(hs_filter_set *fs, size_t first, size_t count, const uint8_t *d_allowed, void *stream) {
+  hs_status s = filter_rows_ok(fs, first, count, d_allowed);
+  if (s != HS_OK || count == 0) return s;
+  HIP_TRY(hipSetDevice(fs->device));
+  HIP_TRY(launch_filter_pack(d_allowed, fs->bits.p + first * fs->row_words, (uint32_t)fs->n, (uint32_t)count, (uint32_t)fs->row_words, (hipStream_t)stream));
+  return HS_OK;
+}
+
+// Host bytes go through a device buffer of at most kFilterStageBytes (one row, if a row is longer) and are packed there.
+static constexpr size_t kFilterStageBytes = 8u << 20;
+hs_status hs_filter_set_write(hs_filter_set *fs, size_t first, size_t count, const uint8_t *allowed) {
+  hs_status s = filter_rows_ok(fs, first, count, allowed);
+  if (s != HS_OK || count == 0) return s;
+  HIP_TRY(hipSetDevice(fs->device));
+  if (fs->n == 0) return HS_OK;
+  const size_t per = std::max<size_t>(kFilterStageBytes / fs->n, 1);
+  HIP_TRY(fs->stage.ensure(std::min(per, count) * fs->n));
+  for (size_t r0 = 0; r0 < count; r0 += per) {
+    const size_t m = std::min(per, count - r0);
+    HIP_TRY(hipMemcpyAsync(fs->stage.p, allowed + r0 * fs->n, m * fs->n, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(launch_filter_pack(fs->stage.p, fs->bits.p + (first + r0) * fs->row_words, (uint32_t)fs->n, (uint32_t)m, (uint32_t)fs->row_words, nullptr));
+  }
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return HS_OK;
+}
+
+hs_status hs_filter_set_write_bits(hs_filter_set *fs, size_t first, size_t count, const uint32_t *words) {
+  hs_status s = filter_rows_ok(fs, first, count, words);
+  if (s != HS_OK || count == 0) return s;
+  HIP_TRY(hipSetDevice(fs->device));
+  HIP_TRY(hipMemcpy(fs->bits.p + first * fs->row_words, words, count * fs->row_words * 4, hipMemcpyHostToDevice));
+  return HS_OK;
+}
+
+hs_status hs_filter_set_read(hs_filter_set *fs, size_t f, uint8_t *out_allowed) {
+  if (!fs || !out_allowed) return fail(HS_ERR_INVALID, "null argument");
+  if (f >= fs->nf) return fail(HS_ERR_INVALID, "filter " + std::to_string(f) + " outside a set of " + std::to_string(fs->nf));
+  if (fs->n == 0) return HS_OK;
+  HIP_TRY(hipSetDevice(fs->device));
+  HIP_TRY(fs->unpacked.ensure(fs->n));
+  HIP_TRY(launch_filter_unpack(fs->bits.p + f * fs->row_words, fs->unpacked.p, (uint32_t)fs->n, nullptr));
+  HIP_TRY(hipMemcpy(out_allowed, fs->unpacked.p, fs->n, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+
+hs_status hs_filter_set_info(const hs_filter_set *fs, uint64_t *nf, uint64_t *n, uint64_t *row_words, uint64_t *device_bytes) {
+  if (!fs) return fail(HS_ERR_INVALID, "null argument");
+  if (nf) *nf = fs->nf;
+  if (n) *n = fs->n;
+  if (row_words) *row_words = fs->row_words;
+  if (device_bytes) *device_bytes = (uint64_t)fs->nf * fs->row_words * 4;
+  return HS_OK;
+}
+
+// Everything a search under `fs` is refused for on the host, before anything is launched.
+static hs_status filter_use_ok(const hs_index *ix, const hs_filter_set *fs) {
+  hs_status s = filter_index_ok(ix);
+  if (s != HS_OK) return s;
+  if (!fs) return fail(HS_ERR_INVALID, "null filter set");
+  if (fs->device != ix->device)
+    return fail(HS_ERR_INVALID, "the filter set lives on device " + std::to_string(fs->device) + ", the index on device " + std::to_string(ix->device));
+  if (fs->n != ix->info.n)
+    return fail(HS_ERR_INVALID, "the filter set was created for " + std::to_string(fs->n) + " elements, the index holds " + std::to_string(ix->info.n));
+  return HS_OK;
+}
+
+hs_status hs_search_batch_filter_set_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                         const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                         uint32_t *d_out_counts, uint32_t *d_stats, void *stream) {
+  hs_status s = filter_use_ok(ix, fs);
+  if (s != HS_OK) return s;
+  if (!d_queries || !d_filter_of_query) return fail(HS_ERR_INVALID, "null argument");
+  if (!d_out_labels64 || !d_out_dists || !d_out_counts) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
+  const FilterUse fu{fs, d_filter_of_query};
+  return search_dev(ix, d_queries, nq, k, HS_MODE_PQ, nullptr, d_out_labels64, d_out_dists, d_out_counts, d_stats, nullptr, nullptr,
+                    (hipStream_t)stream, &fu);
+}
+
+hs_status hs_search_batch_filter_set(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                     const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts,
+                                     uint32_t *stats) {
+  hs_status s = filter_use_ok(ix, fs);
+  if (s != HS_OK) return s;
+  if (!queries || !filter_of_query) return fail(HS_ERR_INVALID, "null argument");
+  if (!out_labels64 || !out_dists || !out_counts) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
+  for (size_t i = 0; i < nq; i++)
+    if (filter_of_query[i] >= fs->nf)
+      return fail(HS_ERR_INVALID, "query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) + " of a set of " + std::to_string(fs->nf));
+  if (nq == 0) return HS_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(nullptr);
+  HIP_TRY(w->afoq.ensure(nq));
+  HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
+  const FilterUse fu{fs, w->afoq.p};
+  s = search_async(ix, queries, nq, k, HS_MODE_PQ, nullptr, out_labels64, out_dists, out_counts, stats, nullptr, &fu);
+  if (s != HS_OK) return s;
+  return hs_search_check(ix, nullptr);
 }
 
 hs_status hs_search_batch_raw(hs_index *ix, const float *queries, size_t nq, size_t k, int mode, float *raw_dists,

@@ -73,16 +73,33 @@ struct SearchArgs {
   uint32_t fl_nb, fl_mul, fl_sh;
 };
 
+// Filter set of a search (filter_set.hip; fast and strict kernels).  nf bitmap rows of `stride` words: bit i & 31 of word i >> 5 of
+// row f is set iff filter f allows internal id i; query qi (its index in THIS launch's arrays, whatever order or pass takes it)
+// searches under row of_query[qi].  A node is excluded iff it is marked deleted or its bit is clear.  A query whose filter index
+// is >= nf touches no row: count 0, padding outputs, *bad raised.
+// A kernel ARGUMENT OF ITS OWN of the filter-set entry points (hs::strict_kernel / hs::fast_kernel overloads and their narrow
+// twins), as the narrow rows are: SearchArgs and the kernels that take only it are what they were, instruction for instruction
+// -- their register and scratch lines are pinned (tests/test_f32_free_cpu.py), and SearchArgs' size is part of those lines.
+struct FilterArgs {
+  const uint32_t *rows;
+  const uint32_t *of_query;
+  uint32_t *bad;
+  uint32_t stride, nf;
+};
+
 // Bytes of dynamic LDS one query (one wavefront) needs.
 size_t strict_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots);
 size_t fast_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots);
-// Fast path availability for this shape (level-0 tile present, threshold_level == 0, k < ef <= 512).
-bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k);
+// Fast path availability for this shape (level-0 tile present, threshold_level == 0, k < ef <= 512).  has_filter: the search
+// names a filter set, which counts as delete marks do (the !bare_bone branches).
+bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k, bool has_filter = false);
 
 // Strict kernel: the reference's result/candidate arrays with libstdc++ heap mechanics, reference
 // output order.  Fast kernel: same traversal and candidate mechanics, result set kept as a sorted
 // register array; queries whose answer could depend on the result heap's layout are flagged ST_HAZARD.
-hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
+// f != null (launch_strict, launch_fast and their narrow forms): the search runs under that filter set -- the !bare_bone branches
+// whether or not the index has delete marks (hnswalg.h:1421, hnswalg_slim.h:1884).
+hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f = nullptr);
 // order[] = the queries sorted by decreasing entry[].y (distance of the level-0 entry), bucket-exact: the queries likely
 // to take the most expansions start first, so that a launch does not end on a few late-started long ones.
 hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStream_t stream);
@@ -97,7 +114,7 @@ uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef);
 hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
 hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, uint2 *d_heap, uint2 *d_pops, uint32_t *d_n, int wave_pop,
                          uint32_t lds_slots, hipStream_t stream);
-hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
+hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f = nullptr);
 // Narrow rows (narrow_rows.hip): `rows` = the index's u8 / fp16 copy of ix.vec in the lane-major layout, fmt = ROWS_U8 | ROWS_F16.
 // launch_flatk_narrow is launch_flatk reading that copy (kernels hs::flat_kernel_u8 / hs::flat_kernel_f16; same shapes, same plan).
 // launch_narrow_convert fills rows [row0, row0 + nrows) of the copy from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to
@@ -108,10 +125,14 @@ hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stre
 // hipErrorInvalidDevicePointer instead of launching when ix.vec is null and the index is not empty.
 // launch_narrow_widen is the inverse of the conversion: rows [row0, row0 + nrows) of d_vec from the copy (exact).
 hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
-hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
-hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
+hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f = nullptr);
+hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f = nullptr);
 hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
                                  hipStream_t stream);
 hipError_t launch_narrow_widen(const void *d_rows, float *d_vec, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, hipStream_t stream);
+// Filter sets (filter_set.hip).  launch_filter_pack: rows [0, count) of d_allowed (count x n bytes, non-zero = allowed) into count
+// bitmap rows of row_words words at d_words, padding bits and words zero.  launch_filter_unpack: one bitmap row into n bytes (0 / 1).
+hipError_t launch_filter_pack(const uint8_t *d_allowed, uint32_t *d_words, uint32_t n, uint32_t count, uint32_t row_words, hipStream_t stream);
+hipError_t launch_filter_unpack(const uint32_t *d_row, uint8_t *d_allowed, uint32_t n, hipStream_t stream);
 
 }  // namespace hs

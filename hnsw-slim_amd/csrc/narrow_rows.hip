@@ -73,24 +73,24 @@ hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const vo
 
 // strict / fast kernels over the copy: same LDS layouts and scratch shares as launch_strict / launch_fast
 #define HS_DECL_NARROW(name)                                                                                              \
-  hipError_t name##_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream);     \
-  hipError_t name##_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream);     \
-  hipError_t name##_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream);    \
-  hipError_t name##_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream);    \
-  static hipError_t name##_by(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, size_t lds, hipStream_t stream) { \
+  hipError_t name##_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);     \
+  hipError_t name##_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);     \
+  hipError_t name##_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);    \
+  hipError_t name##_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);    \
+  static hipError_t name##_by(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, size_t lds, hipStream_t stream, const FilterArgs *f) { \
     if (rows == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;                                                 \
     if ((ix.dim & 15u) != 0 || (fmt != ROWS_U8 && fmt != ROWS_F16)) return hipErrorInvalidValue;                          \
-    if (fmt == ROWS_U8) return ix.metric == 0 ? name##_u8_l2(ix, a, rows, lds, stream) : name##_u8_ip(ix, a, rows, lds, stream);     \
-    return ix.metric == 0 ? name##_f16_l2(ix, a, rows, lds, stream) : name##_f16_ip(ix, a, rows, lds, stream);            \
+    if (fmt == ROWS_U8) return ix.metric == 0 ? name##_u8_l2(ix, a, rows, lds, stream, f) : name##_u8_ip(ix, a, rows, lds, stream, f);     \
+    return ix.metric == 0 ? name##_f16_l2(ix, a, rows, lds, stream, f) : name##_f16_ip(ix, a, rows, lds, stream, f);            \
   }
 HS_DECL_NARROW(launch_strict)
 HS_DECL_NARROW(launch_fast)
 #undef HS_DECL_NARROW
-hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream) {
-  return launch_strict_by(ix, a, rows, fmt, strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots), stream);
+hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f) {
+  return launch_strict_by(ix, a, rows, fmt, strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots), stream, f);
 }
-hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream) {
-  return launch_fast_by(ix, a, rows, fmt, fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots), stream);
+hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f) {
+  return launch_fast_by(ix, a, rows, fmt, fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots), stream, f);
 }
 
 }  // namespace hs

@@ -133,6 +133,7 @@ class DeviceIndex {
  public:
   size_t ef_ = 10;
   ~DeviceIndex() {
+    drop_filter_cache();
     free_replicas();
     hs_index_free(h_);
   }
@@ -187,6 +188,7 @@ class DeviceIndex {
 
  protected:
   void load(const std::string &location, int kind, SpaceInterface<float> *s, size_t max_elements) {
+    drop_filter_cache();
     hs_index_free(h_);
     h_ = nullptr;
     metric_ = metric_of(s);
@@ -207,8 +209,28 @@ class DeviceIndex {
     if (row_fmt_ != HS_ROWS_F32) setRowFormat(row_fmt_);
     if (!f32_resident_) setF32Resident(false);
   }
+  // searchKnn(q, k, isIdAllowed): the functor's answers are cached as a ONE-ROW filter set on the device (hs_filter_set_*), so the
+  // second and later calls with the same functor evaluate nothing and upload nothing.  The cache belongs to (functor, loaded index):
+  // dropped when the index is reloaded, and when its element count is no longer the one the set was created for (hs_index_patch on
+  // handle() added elements); rebuilt on the next filtered call.
   mutable BaseFilterFunctor *cached_filter_ = nullptr;
-  mutable std::vector<uint8_t> allowed_;
+  mutable uint64_t cached_n_ = 0;
+  mutable hs_filter_set *filter_set_ = nullptr;
+  void drop_filter_cache() const {
+    hs_filter_set_free(filter_set_);
+    filter_set_ = nullptr;
+    cached_filter_ = nullptr;
+  }
+
+ public:
+  // device bytes of the cached filter set (0 when none): one bitmap row of the index
+  size_t filterCacheBytes() const {
+    uint64_t b = 0;
+    if (filter_set_) check(hs_filter_set_info(filter_set_, nullptr, nullptr, nullptr, &b));
+    return (size_t)b;
+  }
+
+ protected:
   std::priority_queue<std::pair<float, labeltype>> search_pq(const void *q, size_t k, BaseFilterFunctor *f = nullptr) const {
     std::priority_queue<std::pair<float, labeltype>> result;
     if (!h_) return result;
@@ -216,16 +238,21 @@ class DeviceIndex {
     std::vector<float> dists(k);
     uint32_t cnt = 0;
     if (f) {
-      if (f != cached_filter_) {  // evaluate the functor once per element (hs_labels: label of each internal id)
-        hs_info info;
-        check(hs_index_info(h_, &info));
+      hs_info info;
+      check(hs_index_info(h_, &info));
+      if (f != cached_filter_ || !filter_set_ || cached_n_ != info.n) {  // evaluate the functor once per element (hs_labels: label of each internal id)
+        drop_filter_cache();
         std::vector<uint64_t> all(info.n);
         check(hs_labels(h_, all.data()));
-        allowed_.resize(info.n);
-        for (size_t i = 0; i < info.n; i++) allowed_[i] = (*f)((labeltype)all[i]) ? 1 : 0;
+        std::vector<uint8_t> allowed(info.n);
+        for (size_t i = 0; i < info.n; i++) allowed[i] = (*f)((labeltype)all[i]) ? 1 : 0;
+        check(hs_filter_set_create(h_, 1, &filter_set_));
+        check(hs_filter_set_write(filter_set_, 0, 1, allowed.data()));
         cached_filter_ = f;
+        cached_n_ = info.n;
       }
-      check(hs_search_batch_filtered(h_, (const float *)q, 1, k, allowed_.data(), labels.data(), dists.data(), &cnt, nullptr));
+      const uint32_t row = 0;
+      check(hs_search_batch_filter_set(h_, filter_set_, (const float *)q, 1, k, &row, labels.data(), dists.data(), &cnt, nullptr));
     } else
     check(hs_search_batch(h_, (const float *)q, 1, k, HS_MODE_PQ, nullptr, labels.data(), dists.data(), &cnt, nullptr));
     for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);

@@ -180,6 +180,50 @@ hs_status hs_search_batch_filtered(hs_index *ix, const float *queries, size_t nq
 /* External labels by internal id (n entries), to evaluate a filter functor on the host. */
 hs_status hs_labels(const hs_index *ix, uint64_t *out_labels);
 
+/* ---- filter sets: device-resident filters, one per query in one batch (no counterpart in the reference, where a filter is a
+ * host functor handed to one searchKnn call) ------------------------------------------------------------------------------
+ * A filter set is nf filters over the n internal ids of one index, held on the index's device as bitmaps: bit i & 31 of word
+ * i >> 5 of row f is set iff filter f allows internal id i (the "by internal id" convention of allowed[] above); a row is
+ * hs_filter_row_words(n) words -- ceil(n / 32) rounded up to a multiple of 4, so that rows start 16-byte aligned -- and every
+ * padding bit is zero.  A search names the set and one filter index per query: queries under different filters (tenants, ACL
+ * groups, categories) run in ONE launch, and nothing is rebuilt or uploaded per call.
+ * The index's own delete marks still apply and are never folded into the rows: a node is excluded iff it is marked deleted OR
+ * its bit is clear, so a later hs_index_patch that marks nodes deleted needs no rewrite of the set.
+ * A set is bound to the device it was created on and to the n it was created for: a search is refused with HS_ERR_INVALID,
+ * nothing launched, when the index holds another n (it grew through hs_index_patch: create a new set), lives on another device,
+ * or is a SlimQ index. */
+typedef struct hs_filter_set hs_filter_set;
+/* Host only, no device.  hs_filter_pack: allowed[nf x n] bytes (non-zero = allowed) -> out_words[nf x hs_filter_row_words(n)]. */
+size_t hs_filter_row_words(size_t n);
+hs_status hs_filter_pack(const uint8_t *allowed, size_t n, size_t nf, uint32_t *out_words);
+/* nf rows for the index's current n, all bits zero.  Refused as hs_search_batch_filtered refuses (SlimQ: HS_ERR_INVALID; a Slim
+ * index with threshold_level > 0: HS_ERR_UNSUPPORTED), and nf == 0 with HS_ERR_INVALID; *out stays NULL. */
+hs_status hs_filter_set_create(hs_index *ix, size_t nf, hs_filter_set **out);
+void hs_filter_set_free(hs_filter_set *fs);
+/* Rows [first, first + count) from count x n host bytes (staged through a bounded device buffer and packed on the device), from
+ * host words in hs_filter_pack's layout (a plain copy), or from count x n DEVICE bytes (a mask computed on the GPU, e.g. a torch
+ * bool / uint8 tensor; packed asynchronously on `stream`).  Not to be called while a search that reads those rows is in flight on
+ * another stream. */
+hs_status hs_filter_set_write(hs_filter_set *fs, size_t first, size_t count, const uint8_t *allowed);
+hs_status hs_filter_set_write_bits(hs_filter_set *fs, size_t first, size_t count, const uint32_t *words);
+hs_status hs_filter_set_write_dev(hs_filter_set *fs, size_t first, size_t count, const uint8_t *d_allowed, void *stream);
+/* Row f unpacked into out_allowed[n] (0 / 1); the set's shape (every output nullable; device_bytes = nf x row_words x 4). */
+hs_status hs_filter_set_read(hs_filter_set *fs, size_t f, uint8_t *out_allowed);
+hs_status hs_filter_set_info(const hs_filter_set *fs, uint64_t *nf, uint64_t *n, uint64_t *row_words, uint64_t *device_bytes);
+/* hs_search_batch_filtered with query i under row filter_of_query[i] of the set: same outputs (HS_MODE_PQ), same bits as a
+ * hs_search_batch_filtered call with that row's allowed[].  Synchronous, host pointers; a filter index >= nf is HS_ERR_INVALID
+ * before anything is launched. */
+hs_status hs_search_batch_filter_set(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                     const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists,
+                                     uint32_t *out_counts, uint32_t *stats);
+/* The same with DEVICE pointers, asynchronous on `stream`; pair with hs_search_check like the other _dev entries.  The filter
+ * indices cannot be checked on the host: a query whose index is >= nf reads no row, returns count 0 with padding labels and
+ * distances (the other queries of the batch are not disturbed) and raises a sticky per-stream counter that the next
+ * hs_search_check on that stream reports as HS_ERR_INVALID, with the number of such queries in the message. */
+hs_status hs_search_batch_filter_set_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                         const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                         uint32_t *d_out_counts, uint32_t *d_stats, void *stream);
+
 /* Same search with DEVICE pointers, asynchronous on `stream` (a hipStream_t; NULL = default stream).
  * No host synchronisation happens here; call hs_search_check() after synchronising to learn whether
  * any query exhausted the fallback scratch. */
