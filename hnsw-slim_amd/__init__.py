@@ -32,6 +32,7 @@ EXPORTS = [
     "hs_index_set_f32_resident", "hs_index_f32_resident", "hs_rows_to_narrow", "hs_index_load_narrow",
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
+    "hs_index_exact_search", "hs_index_exact_search_dev",
 ]
 
 
@@ -123,6 +124,8 @@ def lib():
     L.hs_filter_set_info.argtypes = [vp, vp, vp, vp, vp]
     L.hs_search_batch_filter_set.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_search_batch_filter_set_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    L.hs_index_exact_search.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_build_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_convert_slimq_graph.argtypes = L.hs_convert_slim.argtypes
@@ -681,6 +684,30 @@ class Index:
         _check(lib().hs_search_batch_filter_set_dev(self._h, fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
                                                     d_filter_of_query.data_ptr(), d_labels.data_ptr(), d_dists.data_ptr(),
                                                     d_counts.data_ptr(), d_stats.data_ptr() if d_stats is not None else None, stream))
+
+    def exact_search(self, queries, k, fs=None, filter_of_query=None):
+        """hs_index_exact_search: exact k-NN over the rows this index holds (fp32 or its narrow copy), under its delete marks and,
+        with a FilterSet `fs`, query i under filter filter_of_query[i].  labels / dists nq x k ascending by (dist, label), ~0 / +inf
+        beyond cnt[i].  ef, exact order and capacity settings do not apply."""
+        q = np.ascontiguousarray(queries, np.float32)
+        nq = q.shape[0]
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels = np.empty((nq, k), np.uint64)
+        dists = np.empty((nq, k), np.float32)
+        cnt = np.empty(nq, np.uint32)
+        _check(lib().hs_index_exact_search(self._h, None if fs is None else fs._h, q.ctypes.data, nq, k,
+                                           None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
+        return dict(labels=labels, dists=dists, cnt=cnt)
+
+    def exact_search_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_dev: device tensors (queries f32 nq x d, labels int64 nq x k, dists f32 nq x k, counts int32 nq,
+        filter indices int32 nq) + HIP stream; asynchronous, pair with check(stream).  Tiles of 8 queries are formed in the order
+        given: group the queries by filter to let a tile skip what its filters exclude."""
+        _check(lib().hs_index_exact_search_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                               None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                               d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
 
     def search_raw(self, queries, k, mode=HS_MODE_SLIM_IDS):
         q = np.ascontiguousarray(queries, np.float32)

@@ -16,40 +16,11 @@
 
 #include <cfloat>
 
+#include "bf_common.hpp"
 #include "bf_engine.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
-
-static constexpr int kQT = 8;       // queries per workgroup tile
-static constexpr int kWaves = 4;    // waves per workgroup
-
-struct BfEntry { float d; uint32_t row; uint64_t label; };   // 16 bytes
-
-__device__ __forceinline__ bool bf_less(float d, uint64_t l, const BfEntry &e) { return d < e.d || (d == e.d && l < e.label); }
-
-// Candidates of one pass (mask m, value d in the owning lane, row = rb + (lane >> SHIFT)) against one query's sorted k-list.
-template <int SHIFT>
-__device__ __forceinline__ void bf_offer(unsigned long long m, float d, uint32_t rb, const uint64_t *labels, BfEntry *L, uint32_t *sz,
-                                         uint32_t k, int lane) {
-  while (m) {
-    const int l = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    const float dj = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(d), l));
-    const uint32_t rj = rb + (uint32_t)(l >> SHIFT);
-    if (lane == 0) {
-      const uint64_t lab = labels ? labels[rj] : (uint64_t)rj;
-      uint32_t cur = *sz;
-      if (cur < k || bf_less(dj, lab, L[k - 1])) {
-        uint32_t pos = cur < k ? cur : k - 1;
-        while (pos > 0 && bf_less(dj, lab, L[pos - 1])) { L[pos] = L[pos - 1]; pos--; }
-        L[pos] = BfEntry{dj, rj, lab};
-        if (cur < k) *sz = cur + 1;
-      }
-    }
-    wave_sync();
-  }
-}
 
 // Sorted runs of this (chunk, wave), padded with +inf, for the merge kernel.
 __device__ __forceinline__ void bf_write_runs(const BfEntry *mine, const uint32_t *msz, BfEntry *partial, uint32_t q0, uint32_t nq, uint32_t k,
@@ -229,6 +200,13 @@ hipError_t launch_brute_force(const float *base, const uint64_t *labels, uint32_
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(bf_merge_kernel, dim3(nq), dim3(64), 0, stream, (const BfEntry *)partial, nq, k, grid_x * kWaves, out_labels, out_dists, out_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_bf_merge(const void *partial, uint32_t nq, uint32_t k, uint32_t nruns, uint64_t *out_labels, float *out_dists,
+                           uint32_t *out_counts, hipStream_t stream) {
+  if (nruns > 16 * 64) return hipErrorInvalidValue;   // 16 runs per merge lane
+  hipLaunchKernelGGL(bf_merge_kernel, dim3(nq), dim3(64), 0, stream, (const BfEntry *)partial, nq, k, nruns, out_labels, out_dists, out_counts);
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include "rabitq_host.hpp"
 #include "slimq_engine.hpp"
 #include "bf_engine.hpp"
+#include "exact_engine.hpp"
 
 using namespace hs;
 
@@ -115,6 +116,8 @@ struct hs_index {
     DevBuf<uint32_t> al32, acnt, astats;
     DevBuf<uint64_t> al64;
     DevBuf<uint32_t> afoq;              // hs_search_batch_filter_set: the per-query filter indices of the call in flight
+    DevBuf<uint8_t> xruns;              // hs_index_exact_search: the sorted runs between the scan and the merge
+    DevBuf<uint32_t> xorder;            // hs_index_exact_search (host entry): the queries grouped by filter
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
   std::mutex ws_mu;
@@ -1805,6 +1808,106 @@ hs_status hs_brute_force(const float *base, size_t n, size_t dim, int metric, co
   HIP_TRY(hipMemcpy(out_labels, dol.p, nq * k * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_dists, dd.p, nq * k * 4, hipMemcpyDeviceToHost));
   if (out_counts) HIP_TRY(hipMemcpy(out_counts, dc.p, nq * 4, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+
+// ---- exact k-NN over the rows a resident index holds (exact_search.hip) -------------------------------------------------
+// One launch group: grid.y is a tile of 8 queries and at most 65535.
+static constexpr size_t kExactGroupQueries = 262144;
+
+// Everything an exact search is refused for on the host, before anything is launched.
+static hs_status exact_use_ok(const hs_index *ix, const hs_filter_set *fs, const void *queries, const void *filter_of_query, size_t nq,
+                              size_t k, const void *out_labels64, const void *out_dists) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (!queries || !out_labels64 || !out_dists) return fail(HS_ERR_INVALID, "null argument");
+  if ((fs != nullptr) != (filter_of_query != nullptr)) return fail(HS_ERR_INVALID, "a filter set and filter_of_query go together: both or neither");
+  if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "exact search on a SlimQ index is not supported (its rows are RaBitQ records)");
+  if (ix->info.dim > 4096) return fail(HS_ERR_UNSUPPORTED, "exact search supports dim <= 4096");
+  if (k == 0 || k > 64) return fail(HS_ERR_UNSUPPORTED, "exact search supports 1 <= k <= 64");
+  if (exact_lds_bytes((uint32_t)ix->info.dim, (uint32_t)k) > kLdsPerCU)
+    return fail(HS_ERR_UNSUPPORTED, "exact search: a tile of 8 queries of dim " + std::to_string(ix->info.dim) + " with k = " + std::to_string(k) + " does not fit the on-chip memory");
+  if (nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "nq too large");
+  if (fs) {
+    if (fs->device != ix->device)
+      return fail(HS_ERR_INVALID, "the filter set lives on device " + std::to_string(fs->device) + ", the index on device " + std::to_string(ix->device));
+    if (fs->n != ix->info.n)
+      return fail(HS_ERR_INVALID, "the filter set was created for " + std::to_string(fs->n) + " elements, the index holds " + std::to_string(ix->info.n));
+  }
+  return HS_OK;
+}
+
+// d_order (nullable): per launch group, a permutation of the group's own query indices.
+static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d_q, size_t nq, size_t k, const uint32_t *d_foq,
+                           const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  if (w->counters.n < 48) {   // (as search_dev_group: sticky until hs_search_check reads and clears them)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  // the narrow copy where the index has one: fewer bytes, the same bits; the only rows of an fp32-free index
+  const int fmt = ix->row_fmt;
+  const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
+  const size_t dim = ix->info.dim;
+  ix->last_kernel = (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+  for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+    const size_t m = std::min(kExactGroupQueries, nq - off);
+    ExactArgs a{};
+    const size_t bytes = bf_partial_bytes(ix->dev.n, (uint32_t)m, (uint32_t)k, &a.grid_x, &a.rows_per_block);
+    HIP_TRY(w->xruns.ensure(std::max<size_t>(bytes, 16)));
+    a.queries = d_q + off * dim; a.nq = (uint32_t)m; a.k = (uint32_t)k; a.order = d_order ? d_order + off : nullptr;
+    a.partial = w->xruns.p;
+    a.out_labels = l64 + off * k; a.out_dists = dd + off * k; a.out_counts = cnt ? cnt + off : nullptr;
+    FilterArgs fa{};
+    if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+    HIP_TRY(launch_exact_search(ix->dev, rows, fmt, a, fs ? &fa : nullptr, stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                    const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                    uint32_t *d_out_counts, void *stream) {
+  hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+  if (s != HS_OK || nq == 0) return s;
+  return exact_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+}
+
+hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
+  if (s != HS_OK) return s;
+  if (fs)
+    for (size_t i = 0; i < nq; i++)
+      if (filter_of_query[i] >= fs->nf)
+        return fail(HS_ERR_INVALID, "query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) + " of a set of " + std::to_string(fs->nf));
+  if (nq == 0) return HS_OK;
+  if (hs_device_count() <= ix->device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(nullptr);
+  const size_t dim = ix->info.dim;
+  HIP_TRY(w->aq.ensure(nq * dim)); HIP_TRY(w->al64.ensure(nq * k)); HIP_TRY(w->adist.ensure(nq * k)); HIP_TRY(w->acnt.ensure(nq));
+  HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
+  std::vector<uint32_t> order;   // (outlives the asynchronous copy: the call synchronises before it returns)
+  if (fs) {
+    // queries of one filter into the same tiles: a tile skips the rows that none of its filters allows
+    order.resize(nq);
+    for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+      const size_t m = std::min(kExactGroupQueries, nq - off);
+      for (size_t i = 0; i < m; i++) order[off + i] = (uint32_t)i;
+      std::stable_sort(order.begin() + off, order.begin() + off + m,
+                       [&](uint32_t x, uint32_t y) { return filter_of_query[off + x] < filter_of_query[off + y]; });
+    }
+    HIP_TRY(w->afoq.ensure(nq)); HIP_TRY(w->xorder.ensure(nq));
+    HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
+  }
+  s = exact_dev(ix, fs, w->aq.p, nq, k, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->al64.p, w->adist.p, w->acnt.p, nullptr);
+  if (s != HS_OK) return s;
+  HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, nq * k * 4, hipMemcpyDeviceToHost, nullptr));
+  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, w->acnt.p, nq * 4, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return HS_OK;
 }
 

@@ -231,6 +231,23 @@ class DeviceIndex {
   }
 
  protected:
+  // the cached one-row filter set of functor f, (re)built when the functor or the element count changed
+  const hs_filter_set *filter_row_set(BaseFilterFunctor *f) const {
+    hs_info info;
+    check(hs_index_info(h_, &info));
+    if (f != cached_filter_ || !filter_set_ || cached_n_ != info.n) {  // evaluate the functor once per element (hs_labels: label of each internal id)
+      drop_filter_cache();
+      std::vector<uint64_t> all(info.n);
+      check(hs_labels(h_, all.data()));
+      std::vector<uint8_t> allowed(info.n);
+      for (size_t i = 0; i < info.n; i++) allowed[i] = (*f)((labeltype)all[i]) ? 1 : 0;
+      check(hs_filter_set_create(h_, 1, &filter_set_));
+      check(hs_filter_set_write(filter_set_, 0, 1, allowed.data()));
+      cached_filter_ = f;
+      cached_n_ = info.n;
+    }
+    return filter_set_;
+  }
   std::priority_queue<std::pair<float, labeltype>> search_pq(const void *q, size_t k, BaseFilterFunctor *f = nullptr) const {
     std::priority_queue<std::pair<float, labeltype>> result;
     if (!h_) return result;
@@ -238,25 +255,34 @@ class DeviceIndex {
     std::vector<float> dists(k);
     uint32_t cnt = 0;
     if (f) {
-      hs_info info;
-      check(hs_index_info(h_, &info));
-      if (f != cached_filter_ || !filter_set_ || cached_n_ != info.n) {  // evaluate the functor once per element (hs_labels: label of each internal id)
-        drop_filter_cache();
-        std::vector<uint64_t> all(info.n);
-        check(hs_labels(h_, all.data()));
-        std::vector<uint8_t> allowed(info.n);
-        for (size_t i = 0; i < info.n; i++) allowed[i] = (*f)((labeltype)all[i]) ? 1 : 0;
-        check(hs_filter_set_create(h_, 1, &filter_set_));
-        check(hs_filter_set_write(filter_set_, 0, 1, allowed.data()));
-        cached_filter_ = f;
-        cached_n_ = info.n;
-      }
+      const hs_filter_set *fs = filter_row_set(f);
       const uint32_t row = 0;
-      check(hs_search_batch_filter_set(h_, filter_set_, (const float *)q, 1, k, &row, labels.data(), dists.data(), &cnt, nullptr));
+      check(hs_search_batch_filter_set(h_, fs, (const float *)q, 1, k, &row, labels.data(), dists.data(), &cnt, nullptr));
     } else
     check(hs_search_batch(h_, (const float *)q, 1, k, HS_MODE_PQ, nullptr, labels.data(), dists.data(), &cnt, nullptr));
     for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);
     return result;
+  }
+  // Exact k-NN over the rows the index holds (hs_index_exact_search; no counterpart in the reference's graph classes): the
+  // min(k, #candidates) smallest (dist, label) pairs among the elements that are not marked deleted and that f, when given,
+  // allows.  Exact under a filter too -- not the reference's BruteforceSearch filtered overload, whose answer depends on the scan
+  // order (bruteforce.h:118-131).  setEf / setExactOrder do not apply.
+  std::priority_queue<std::pair<float, labeltype>> exact_pq(const void *q, size_t k, BaseFilterFunctor *f) const {
+    std::priority_queue<std::pair<float, labeltype>> result;
+    if (!h_) return result;
+    std::vector<uint64_t> labels(k);
+    std::vector<float> dists(k);
+    uint32_t cnt = 0;
+    const uint32_t row = 0;
+    const hs_filter_set *fs = f ? filter_row_set(f) : nullptr;
+    check(hs_index_exact_search(h_, fs, (const float *)q, 1, k, f ? &row : nullptr, labels.data(), dists.data(), &cnt));
+    for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);
+    return result;
+  }
+  // every row of `queries` in one launch; out_* nq x k ascending by (dist, label), UINT64_MAX / +inf beyond out_counts[q] (nullable)
+  void exact_batch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) const {
+    if (!h_) throw std::runtime_error("hnswlib_amd: no index loaded");
+    check(hs_index_exact_search(h_, nullptr, queries, nq, k, nullptr, out_labels, out_dists, out_counts));
   }
 };
 }  // namespace detail
@@ -340,6 +366,15 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     ensure_built();
     return search_pq(query_data, k, isIdAllowed);
   }
+  // Exact answers over the same resident rows (detail::DeviceIndex::exact_pq / exact_batch): ground truth without a second copy.
+  std::priority_queue<std::pair<float, labeltype>> searchKnnExact(const void *query_data, size_t k, BaseFilterFunctor *isIdAllowed = nullptr) const {
+    ensure_built();
+    return exact_pq(query_data, k, isIdAllowed);
+  }
+  void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
+    ensure_built();
+    exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
+  }
   // Batched searchKnn: nq x dim queries; out_labels / out_dists nq x k (unused slots: UINT64_MAX / +inf).
   void searchKnnBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists,
                       uint32_t *out_counts) const {
@@ -419,6 +454,13 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   std::priority_queue<std::pair<float, labeltype>> searchKnn(const void *query_data, size_t k,
                                                              BaseFilterFunctor *isIdAllowed = nullptr) const override {
     return search_pq(query_data, k, isIdAllowed);
+  }
+  // Exact answers over the same resident rows (detail::DeviceIndex::exact_pq / exact_batch): ground truth without a second copy.
+  std::priority_queue<std::pair<float, labeltype>> searchKnnExact(const void *query_data, size_t k, BaseFilterFunctor *isIdAllowed = nullptr) const {
+    return exact_pq(query_data, k, isIdAllowed);
+  }
+  void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
+    exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
   }
   // searchKnn(q, k, tableint* result): hnswalg_slim.h:2030-2131.  k labels; same k-subset as the reference,
   // sorted by distance (call setExactOrder(true) to also reproduce the reference's array order).

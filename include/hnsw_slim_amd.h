@@ -339,6 +339,36 @@ hs_status hs_brute_force_dev(const float *d_base, const uint64_t *d_labels, size
                              const float *d_queries, size_t nq, size_t k, uint64_t *d_out_labels, float *d_out_dists,
                              uint32_t *d_out_counts, void *stream);
 
+/* ---- exact k-NN over the rows a resident index already holds ---------------------------------------------------------
+ * The exhaustive scan above over the index's own rows, in the format it holds them: fp32, or its u8 / fp16 narrow copy
+ * (hs_index_set_row_format; an index that holds both scans the narrow one -- fewer bytes, the same bits -- and an fp32-free
+ * index, hs_index_set_f32_resident(ix, 0) / hs_index_load_narrow, its only one).  No second copy of the rows is uploaded.
+ * Candidates of query i: the internal ids j < n that are not marked deleted and, when a filter set is named, whose bit is set in
+ * row filter_of_query[i] of `fs` (the exclusion rule of hs_search_batch_filter_set).  Result: the min(k, #candidates)
+ * lexicographically smallest (dist, label) pairs, ascending; dist by the index's metric with the fp32 recipes of every other
+ * path, label the external label.  out_labels64 / out_dists nq x k, ~0 / +inf beyond out_counts[q] (nullable).
+ * Without a filter, on an index without delete marks, this is BruteforceSearch::searchKnn (bruteforce.h:106-135) over the index's
+ * (row, label) pairs bit for bit.  With a filter it is deliberately NOT the reference's filtered overload: that code takes
+ * `lastdist` from a queue that may hold fewer than k entries (bruteforce.h:118-131) and then drops nearer allowed rows depending on
+ * the scan order; the answer here is the exact one and does not depend on the order of the rows.
+ * fs NULL iff filter_of_query NULL.  HS_ERR_INVALID before anything is launched: null arguments, fs without filter_of_query or the
+ * reverse, a set of another n or another device, a (host) filter index >= nf.  HS_ERR_UNSUPPORTED: k == 0 or k > 64, dim > 4096 (or
+ * a query tile beyond the on-chip memory: dim 4096 with k above 63), a SlimQ index (its rows are RaBitQ records).  nq == 0: HS_OK.
+ * hs_set_ef, hs_set_exact_order and hs_set_capacity do not apply: nothing here is approximate, ordered by a heap or bounded by a
+ * scratch capacity.  hs_last_kernel: hs::exact_scan_kernel, hs::exact_scan_kernel_u8 or hs::exact_scan_kernel_f16
+ * (hs::exact_scan_general_kernel for dim % 16 != 0, fp32 rows, one lane per row).
+ * The host entry groups the queries by filter (a stable sort of filter_of_query) before it forms tiles of 8: a tile skips every
+ * 32-row unit that none of its filters allows, so a selective filter costs about the rows it allows. */
+hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+/* device pointers + HIP stream; asynchronous (the workspace is cached per index and stream): pair with hs_search_check(ix, stream).
+ * A device filter index >= nf cannot be refused up front: that query gets count 0 and padding outputs and the check returns
+ * HS_ERR_INVALID, as for hs_search_batch_filter_set_dev.  Tiles are formed in the order given: callers who want the skip group
+ * their queries by filter. */
+hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                    const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                    uint32_t *d_out_counts, void *stream);
+
 /* ---- harness (CPU, not accelerated): produce index files in the reference's formats ------------ */
 /* HierarchicalNSW ctor + addPoint loop + saveIndex: hnswalg.h:85-159, 1248-1376, 748-779.
  * labels = row index; threads==1 reproduces the reference's serial build byte for byte. */
