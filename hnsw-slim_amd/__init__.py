@@ -49,6 +49,32 @@ class HsInfo(ctypes.Structure):
                 ("max_degree0", ctypes.c_uint64), ("index_size", ctypes.c_uint64)]
 
 
+_i32, _u32, _u64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
+HS_PLAN_FLAT, HS_PLAN_LEAN, HS_PLAN_FAST, HS_PLAN_STRICT = range(4)   # hs_plan_family
+PLAN_KERNELS = {None: 0, "lean": 1, "fast": 2}                       # hs_plan_kernel (HS_KERNEL)
+
+
+class HsPlanDiag(ctypes.Structure):   # hs_plan_diag: the diagnostic environment knobs
+    _fields_ = [("kernel", _i32), ("lean_forced", _i32), ("lean_min_ef", _u32), ("order", _i32), ("flat", _i32), ("vis16", _i32),
+                ("flat_waves_per_cu", _i32), ("zero_copy", _i32), ("verbose", _i32), ("slimq_fused", _i32)]
+
+
+class HsPlanIn(ctypes.Structure):     # hs_plan_in: everything the launch plan of a search may depend on
+    _fields_ = [("n", _u64), ("dim", _u64), ("has_tile0", _i32), ("has_uptile", _i32), ("maxlevel", _i32), ("threshold_level", _i32),
+                ("has_deleted", _i32), ("kind", _i32), ("ef", _u64), ("k", _u64), ("nq", _u64), ("mode", _i32),
+                ("user_cand_cap", _u32), ("user_hash_slots", _u32), ("grow_cand", _u32), ("grow_hash", _u32),
+                ("exact_order", _i32), ("want_raw", _i32), ("has_filter", _i32), ("row_fmt", _i32), ("f32_resident", _i32),
+                ("diag", HsPlanDiag)]
+
+
+class HsPlanOut(ctypes.Structure):    # hs_plan_out
+    _fields_ = [("family", _i32), ("rows", _i32), ("split", _i32), ("skip_order", _i32), ("ef", _u32), ("mark_ep", _u32),
+                ("cand_cap", _u32), ("hash_slots", _u32), ("vis_bits", _u32), ("hash_fill_shift", _u32), ("flat", _u32), ("lds_bytes", _u32),
+                ("fl_nb", _u32), ("fl_mul", _u32), ("fl_sh", _u32), ("fl_bits", _u32), ("fl_ok", _u32),
+                ("rerun_rows", _i32), ("rerun_select_mask", _u32), ("rerun_cand_cap", _u32), ("rerun_hash_slots", _u32),
+                ("spill_stride", _u32), ("log_cap", _u32), ("hop_cap", _u32), ("name", ctypes.c_char_p)]
+
+
 def build_library(force=False):
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950)."""
     if force or not os.path.exists(LIB_PATH):
@@ -93,7 +119,9 @@ def lib():
     L.hs_search_batch_dev.argtypes = [vp, vp, sz, sz, ci, vp, vp, vp, vp, vp, vp]
     L.hs_search_check.argtypes = [vp, vp]
     L.hs_debug_heap_ops.argtypes = [vp, sz, ci, u32, vp, vp, vp]
-    L.hs_debug_flat_plan.argtypes = [sz, sz, sz, vp]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_debug_search_plan"):   # (a baseline build in an A/B run may predate these two)
+        L.hs_debug_search_plan.argtypes = [ctypes.POINTER(HsPlanIn), ctypes.POINTER(HsPlanOut)]
+        L.hs_debug_plan_input.argtypes = [vp, sz, sz, ci, ci, ctypes.POINTER(HsPlanIn)]
     L.hs_search_batch_async.argtypes = [vp, vp, sz, sz, ci, vp, vp, vp, vp, vp, vp]
     L.hs_host_alloc.restype = vp
     L.hs_host_alloc.argtypes = [sz]
@@ -306,10 +334,34 @@ class FilterSet:
         return out
 
 
-def debug_flat_plan(n, ef, nq):
-    out = np.zeros(5, np.uint32)
-    _check(lib().hs_debug_flat_plan(n, ef, nq, out.ctypes.data))
-    return dict(nb=int(out[0]), mul=int(out[1]), sh=int(out[2]), bits=int(out[3]), ok=bool(out[4]))
+def plan_input(kernel=None, lean_min_ef=None, order=-1, flat=1, vis16=1, flat_waves_per_cu=0, **fields):
+    """An hs_plan_in with the knobs unset and a bare 1M x 128 Slim index (tiles present, fp32 rows resident) searched with ef 70,
+    k 10, 10 000 queries, in HS_MODE_PQ; `fields` overrides members by name, the leading arguments are the knobs as the
+    environment spells them (kernel: None | "lean" | "fast"; lean_min_ef: None = unset)."""
+    p = HsPlanIn(n=1_000_000, dim=128, has_tile0=1, has_uptile=1, maxlevel=3, threshold_level=0, has_deleted=0, kind=HS_KIND_SLIM,
+                 ef=70, k=10, nq=10_000, mode=HS_MODE_PQ, row_fmt=HS_ROWS_F32, f32_resident=1)
+    p.diag = HsPlanDiag(kernel=PLAN_KERNELS[kernel], lean_forced=lean_min_ef is not None, lean_min_ef=64 if lean_min_ef is None else lean_min_ef,
+                        order=order, flat=flat, vis16=vis16, flat_waves_per_cu=flat_waves_per_cu, zero_copy=0, verbose=0, slimq_fused=1)
+    for name, v in fields.items():
+        assert hasattr(p, name), name
+        setattr(p, name, int(v))
+    return p
+
+
+def debug_search_plan(inp):
+    """hs_debug_search_plan (host only): the launch plan for an HsPlanIn, as a dict of hs_plan_out's members (name: str)."""
+    out = HsPlanOut()
+    _check(lib().hs_debug_search_plan(ctypes.byref(inp), ctypes.byref(out)))
+    d = {f: getattr(out, f) for f, _ in HsPlanOut._fields_}
+    d["name"] = out.name.decode()
+    return d
+
+
+def debug_plan_input(index, k, nq, has_filter=False, want_raw=False):
+    """hs_debug_plan_input: the HsPlanIn of a search of nq queries on a live index, knobs from this process's environment."""
+    p = HsPlanIn()
+    _check(lib().hs_debug_plan_input(index._h, int(k), int(nq), int(bool(has_filter)), int(bool(want_raw)), ctypes.byref(p)))
+    return p
 
 
 def debug_heap_ops(ops, wave_pop=True, lds_slots=1024):

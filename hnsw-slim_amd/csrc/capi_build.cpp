@@ -1,0 +1,295 @@
+// capi_build.cpp -- the C ABI (include/hnsw_slim_amd.h): index construction and conversion on the host (and the GPU conversion),
+// brute force, and the exact search over a resident index's rows.
+#include "capi_internal.hpp"
+
+#include "bf_engine.hpp"
+#include "exact_engine.hpp"
+#include "rabitq_host.hpp"
+
+hs_status hs_build_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
+                        const char *branching_factor, size_t seed, int threads, const char *out_path) {
+  return hs_build_hnsw_labeled(base, nullptr, n, dim, metric, M, ef_construction, branching_factor, seed, threads, out_path);
+}
+
+hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M,
+                                size_t ef_construction, const char *branching_factor, size_t seed, int threads,
+                                const char *out_path) {
+  if (!base || !out_path || !branching_factor || n == 0) return fail(HS_ERR_INVALID, "bad argument");
+  try {
+    VanillaGraph g;
+    g.build(base, n, dim, (Metric)metric, M, ef_construction, branching_factor, seed, threads, labels);
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
+                          float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
+                          size_t low_degree_m, int threads, const char *out_path) {
+  if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
+  try {
+    VanillaGraph g;
+    g.load(hnsw_path, (Metric)metric, dim);
+    SlimParams p;
+    p.threshold_level = threshold_level;
+    p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
+    p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
+    SlimGraph s;
+    s.convert(g, p, threads);
+    s.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+// The base graph of HNSW-SlimQ: rabitqlib::hnsw::HierarchicalNSW::construct's edges (RqGraph in host_graph.hpp), stored in the
+// vanilla file layout so that the converters read it like any hnswlib index.
+hs_status hs_build_rabitq_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
+                               int threads, const char *out_path) {
+  if (!base || !out_path || n == 0 || dim == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (M < 2) return fail(HS_ERR_INVALID, "M must be >= 2");   // mult = 1 / ln M
+  try {
+    RqGraph g;
+    g.rq_build(base, n, dim, (Metric)metric, M, ef_construction, seed, threads);
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+// HierarchicalNSWSlimQ::convertFromHNSW's graph passes (hnswalg_slimq.h:1546-1762): Slim's passes with SlimQ's own
+// PruneByHeuristic (:1334-1362) and rabitqlib's raw distance.  Output: a Slim-layout file for hs_convert_slimq.
+hs_status hs_convert_slimq_graph(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
+                                 float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
+                                 size_t low_degree_m, int threads, const char *out_path) {
+  if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
+  try {
+    VanillaGraph g;
+    g.load(hnsw_path, (Metric)metric, dim);
+    SlimParams p;
+    p.threshold_level = threshold_level;
+    p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
+    p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
+    SlimGraph s;
+    s.convert(g, p, threads, true);
+    s.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+// convertFromHNSW with the list-level work on the GPU (convert_gpu.hip); identical output bytes.  Shapes outside the device path
+// (degree capacities above 32, a reverse-edge list that outgrows the on-chip buffers) run the CPU conversion instead.
+hs_status hs_convert_slim_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
+                              float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
+                              size_t low_degree_m, int device, int threads, const char *out_path, int *used_gpu, double *kernel_ms) {
+  if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
+  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device");
+  try {
+    VanillaGraph g;
+    g.load(hnsw_path, (Metric)metric, dim);
+    SlimParams p;
+    p.threshold_level = threshold_level;
+    p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
+    p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
+    SlimGraph s;
+    std::string err;
+    double ms = 0.0;
+    const bool ok = s.convert_gpu(g, p, device, threads, &ms, &err);
+    if (!ok) {
+      if (!err.empty()) return fail(HS_ERR_DEVICE, err);
+      s.convert(g, p, threads);
+    }
+    if (used_gpu) *used_gpu = ok ? 1 : 0;
+    if (kernel_ms) *kernel_ms = ok ? ms : 0.0;
+    s.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+// ---- exhaustive k-NN: hnswlib::BruteforceSearch::searchKnn (bruteforce.h:106-135) for a batch ----------------------
+hs_status hs_brute_force_dev(const float *d_base, const uint64_t *d_labels, size_t n, size_t dim, int metric,
+                             const float *d_queries, size_t nq, size_t k, uint64_t *d_out_labels, float *d_out_dists,
+                             uint32_t *d_out_counts, void *stream_) {
+  if (!d_base || !d_queries || !d_out_labels || !d_out_dists) return fail(HS_ERR_INVALID, "null argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
+  if (dim > 4096) return fail(HS_ERR_UNSUPPORTED, "brute force supports dim <= 4096");
+  if (k == 0 || k > 64) return fail(HS_ERR_UNSUPPORTED, "brute force supports 1 <= k <= 64");
+  if (n > 0xFFFFFFF0u || nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "too many rows / queries");
+  if (nq == 0) return HS_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  hipPointerAttribute_t attr;   // run (and allocate the workspace) on the device that holds the rows
+  if (hipPointerGetAttributes(&attr, d_base) == hipSuccess) HIP_TRY(hipSetDevice(attr.device));
+  uint32_t gx = 0, rpb = 0;
+  const size_t bytes = bf_partial_bytes((uint32_t)n, (uint32_t)nq, (uint32_t)k, &gx, &rpb);
+  void *partial = nullptr;
+  HIP_TRY(hipMalloc(&partial, std::max<size_t>(bytes, 16)));
+  hipError_t e = launch_brute_force(d_base, d_labels, (uint32_t)n, (uint32_t)dim, metric, d_queries, (uint32_t)nq, (uint32_t)k, partial, gx,
+                                    rpb, d_out_labels, d_out_dists, d_out_counts, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(partial);
+  if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("brute force: ") + hipGetErrorString(e));
+  return HS_OK;
+}
+
+hs_status hs_brute_force(const float *base, size_t n, size_t dim, int metric, const uint64_t *labels, const float *queries,
+                         size_t nq, size_t k, int device, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) {
+  if (!base || !queries || !out_labels || !out_dists) return fail(HS_ERR_INVALID, "null argument");
+  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
+  if (nq == 0) return HS_OK;
+  HIP_TRY(hipSetDevice(device));
+  DevBuf<float> db, dq, dd;
+  DevBuf<uint64_t> dl, dol;
+  DevBuf<uint32_t> dc;
+  HIP_TRY(db.alloc(std::max<size_t>(n * dim, 1))); HIP_TRY(dq.alloc(nq * dim)); HIP_TRY(dd.alloc(nq * k)); HIP_TRY(dol.alloc(nq * k));
+  HIP_TRY(dc.alloc(nq));
+  if (labels) { HIP_TRY(dl.alloc(std::max<size_t>(n, 1))); HIP_TRY(hipMemcpy(dl.p, labels, n * 8, hipMemcpyHostToDevice)); }
+  HIP_TRY(hipMemcpy(db.p, base, n * dim * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dq.p, queries, nq * dim * 4, hipMemcpyHostToDevice));
+  hs_status s = hs_brute_force_dev(db.p, labels ? dl.p : nullptr, n, dim, metric, dq.p, nq, k, dol.p, dd.p, dc.p, nullptr);
+  if (s != HS_OK) return s;
+  HIP_TRY(hipMemcpy(out_labels, dol.p, nq * k * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_dists, dd.p, nq * k * 4, hipMemcpyDeviceToHost));
+  if (out_counts) HIP_TRY(hipMemcpy(out_counts, dc.p, nq * 4, hipMemcpyDeviceToHost));
+  return HS_OK;
+}
+
+// ---- exact k-NN over the rows a resident index holds (exact_search.hip) -------------------------------------------------
+// One launch group: grid.y is a tile of 8 queries and at most 65535.
+static constexpr size_t kExactGroupQueries = 262144;
+
+// Everything an exact search is refused for on the host, before anything is launched.
+static hs_status exact_use_ok(const hs_index *ix, const hs_filter_set *fs, const void *queries, const void *filter_of_query, size_t nq,
+                              size_t k, const void *out_labels64, const void *out_dists) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (!queries || !out_labels64 || !out_dists) return fail(HS_ERR_INVALID, "null argument");
+  if ((fs != nullptr) != (filter_of_query != nullptr)) return fail(HS_ERR_INVALID, "a filter set and filter_of_query go together: both or neither");
+  if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "exact search on a SlimQ index is not supported (its rows are RaBitQ records)");
+  if (ix->info.dim > 4096) return fail(HS_ERR_UNSUPPORTED, "exact search supports dim <= 4096");
+  if (k == 0 || k > 64) return fail(HS_ERR_UNSUPPORTED, "exact search supports 1 <= k <= 64");
+  if (exact_lds_bytes((uint32_t)ix->info.dim, (uint32_t)k) > kLdsPerCU)
+    return fail(HS_ERR_UNSUPPORTED, "exact search: a tile of 8 queries of dim " + std::to_string(ix->info.dim) + " with k = " + std::to_string(k) + " does not fit the on-chip memory");
+  if (nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "nq too large");
+  if (fs) {
+    if (fs->device != ix->device)
+      return fail(HS_ERR_INVALID, "the filter set lives on device " + std::to_string(fs->device) + ", the index on device " + std::to_string(ix->device));
+    if (fs->n != ix->info.n)
+      return fail(HS_ERR_INVALID, "the filter set was created for " + std::to_string(fs->n) + " elements, the index holds " + std::to_string(ix->info.n));
+  }
+  return HS_OK;
+}
+
+// d_order (nullable): per launch group, a permutation of the group's own query indices.
+static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d_q, size_t nq, size_t k, const uint32_t *d_foq,
+                           const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  if (w->counters.n < 48) {   // (as search_dev_group: sticky until hs_search_check reads and clears them)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  // the narrow copy where the index has one: fewer bytes, the same bits; the only rows of an fp32-free index
+  const int fmt = ix->row_fmt;
+  const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
+  const size_t dim = ix->info.dim;
+  ix->last_kernel = (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+  for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+    const size_t m = std::min(kExactGroupQueries, nq - off);
+    ExactArgs a{};
+    const size_t bytes = bf_partial_bytes(ix->dev.n, (uint32_t)m, (uint32_t)k, &a.grid_x, &a.rows_per_block);
+    HIP_TRY(w->xruns.ensure(std::max<size_t>(bytes, 16)));
+    a.queries = d_q + off * dim; a.nq = (uint32_t)m; a.k = (uint32_t)k; a.order = d_order ? d_order + off : nullptr;
+    a.partial = w->xruns.p;
+    a.out_labels = l64 + off * k; a.out_dists = dd + off * k; a.out_counts = cnt ? cnt + off : nullptr;
+    FilterArgs fa{};
+    if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+    HIP_TRY(launch_exact_search(ix->dev, rows, fmt, a, fs ? &fa : nullptr, stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                    const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                    uint32_t *d_out_counts, void *stream) {
+  hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+  if (s != HS_OK || nq == 0) return s;
+  return exact_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+}
+
+hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
+  if (s != HS_OK) return s;
+  if (fs)
+    for (size_t i = 0; i < nq; i++)
+      if (filter_of_query[i] >= fs->nf)
+        return fail(HS_ERR_INVALID, "query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) + " of a set of " + std::to_string(fs->nf));
+  if (nq == 0) return HS_OK;
+  if (hs_device_count() <= ix->device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(nullptr);
+  const size_t dim = ix->info.dim;
+  HIP_TRY(w->aq.ensure(nq * dim)); HIP_TRY(w->al64.ensure(nq * k)); HIP_TRY(w->adist.ensure(nq * k)); HIP_TRY(w->acnt.ensure(nq));
+  HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
+  std::vector<uint32_t> order;   // (outlives the asynchronous copy: the call synchronises before it returns)
+  if (fs) {
+    // queries of one filter into the same tiles: a tile skips the rows that none of its filters allows
+    order.resize(nq);
+    for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+      const size_t m = std::min(kExactGroupQueries, nq - off);
+      for (size_t i = 0; i < m; i++) order[off + i] = (uint32_t)i;
+      std::stable_sort(order.begin() + off, order.begin() + off + m,
+                       [&](uint32_t x, uint32_t y) { return filter_of_query[off + x] < filter_of_query[off + y]; });
+    }
+    HIP_TRY(w->afoq.ensure(nq)); HIP_TRY(w->xorder.ensure(nq));
+    HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
+  }
+  s = exact_dev(ix, fs, w->aq.p, nq, k, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->al64.p, w->adist.p, w->acnt.p, nullptr);
+  if (s != HS_OK) return s;
+  HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, nq * k * 4, hipMemcpyDeviceToHost, nullptr));
+  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, w->acnt.p, nq * 4, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return HS_OK;
+}
+
+hs_status hs_convert_slimq(const char *slim_path, int metric, size_t dim, const float *centroids, size_t num_cluster,
+                           const uint32_t *cluster_ids, uint64_t flip_seed, int threads, const char *out_path) {
+  if (!slim_path || !out_path || !centroids || num_cluster == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (dim < 64 || dim >= 4096) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports 64 <= dim < 4096");
+  try {
+    SlimGraph s;
+    s.load(slim_path, (Metric)metric, dim);
+    if (cluster_ids)
+      for (size_t i = 0; i < s.count; i++)
+        if (cluster_ids[i] >= num_cluster) return fail(HS_ERR_INVALID, "cluster id out of range");
+    SlimQGraph q;
+    q.from_slim(s, metric, centroids, num_cluster, cluster_ids, flip_seed, threads);
+    q.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}

@@ -1,0 +1,156 @@
+// capi_internal.hpp -- what the C ABI's translation units (capi_*.cpp) share: error reporting, the device buffer, the index
+// and filter-set objects behind the opaque handles, and the few functions that cross files.  No CPU search path exists in this
+// library: without a HIP device every search call returns HS_ERR_DEVICE.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/hnsw_slim_amd.h"
+#include "engine.hpp"
+#include "narrow_rows.hpp"
+#define HS_HAVE_GPU_CONVERT 1
+#include "convert_engine.hpp"
+#include "host_graph.hpp"
+#include "search_plan.hpp"
+#include "slimq_engine.hpp"
+
+using namespace hs;
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t _e = (expr);                                                                    \
+    if (_e != hipSuccess) return fail(HS_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+template <typename T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  hipError_t alloc(size_t count) {
+    release();
+    if (count == 0) return hipSuccess;
+    const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+    if (e == hipSuccess) n = count;   // (a failed allocation leaves the buffer empty: the next ensure() tries again)
+    else p = nullptr;
+    return e;
+  }
+  hipError_t ensure(size_t count) { return count <= n ? hipSuccess : alloc(count); }
+  hipError_t upload(const std::vector<T> &v) {
+    hipError_t e = alloc(std::max<size_t>(v.size(), 1));
+    if (e != hipSuccess) return e;
+    return v.empty() ? hipSuccess : hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+  ~DevBuf() { release(); }
+};
+
+struct hs_index {
+  int device = 0;
+  hs_info info{};
+  size_t ef = 10;  // hnswalg.h:864, hnswalg_slim.h:793
+  uint32_t user_cand_cap = 0, user_hash_slots = 0;
+  uint32_t grow_cand = 0, grow_hash = 0;  // adaptive: doublings learnt from earlier batches' overflow counts
+  bool exact_order = false;               // always use the strict kernel (reference output order)
+  const char *last_kernel = "";           // the kernel that served pass 0 of the most recent search call (hs_last_kernel)
+  // patching (hs_index_patch): a Slim index loaded with max_elements > count keeps its host image and has row capacity
+  std::unique_ptr<SlimGraph> host_slim;
+  size_t cap_rows = 0;
+  DevIndex dev{};
+  DevBuf<float> vec;
+  DevBuf<uint32_t> row_ptr0, cols, up_base, up_ptr, tile0, uptile;
+  DevBuf<uint64_t> labels;
+  DevBuf<uint8_t> deleted;
+  // narrow rows (hs_index_set_row_format): a u8 / fp16 copy of `vec` in the flat kernel's lane-major layout (narrow_rows.hip), sized
+  // like `vec` (row capacity x dim values).  While `vec` is resident every kernel but the flat one reads it; once it has been dropped
+  // (hs_index_set_f32_resident(ix, 0), hs_index_load_narrow: f32_resident = false, vec.p = dev.vec = null) every search launch goes to
+  // the narrow twin of the chosen kernel and nothing on the device holds fp32 rows
+  int row_fmt = ROWS_F32;
+  bool f32_resident = true;
+  size_t f32_gone = 0;           // what info.device_bytes is short of while the fp32 rows are absent
+  DevBuf<uint8_t> narrow;
+  DevBuf<uint32_t> narrow_bad;   // the conversion kernel's "first row that does not fit" word
+  size_t narrow_bytes = 0;       // part of info.device_bytes while the copy exists
+  // per-stream scratch (grow-only): calls on different HIP streams may be in flight together
+  struct StreamWs {
+    DevBuf<uint32_t> spill;             // visited-set tier 2, nq x kSpillSlots
+    DevBuf<uint32_t> prep;              // SlimQ: per-query preparation records
+    DevBuf<uint32_t> status, counters;  // counters: 3 passes x 4 {visited overflow, candidate overflow, tie hazard, tier-2 spills}
+    DevBuf<uint32_t> entry, order;      // two-launch fast pass: level-0 entries (nq x 4 words) and the start order
+    DevBuf<uint32_t> fb;                // last-resort pass: kFbGrid x (candidate heap + tier-2 visited set)
+    uint32_t oflip = 0;
+    size_t last_nq = 0;
+    // hs_search_batch_async: device staging of the queries and outputs of the call in flight on this stream
+    DevBuf<float> aq, adist;
+    DevBuf<uint32_t> al32, acnt, astats;
+    DevBuf<uint64_t> al64;
+    DevBuf<uint32_t> afoq;              // hs_search_batch_filter_set: the per-query filter indices of the call in flight
+    DevBuf<uint8_t> xruns;              // hs_index_exact_search: the sorted runs between the scan and the merge
+    DevBuf<uint32_t> xorder;            // hs_index_exact_search (host entry): the queries grouped by filter
+  };
+  std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
+  std::mutex ws_mu;
+  StreamWs *stream_ws(hipStream_t st) {
+    std::lock_guard<std::mutex> g(ws_mu);
+    auto &p = ws[st];
+    if (!p) p.reset(new StreamWs());
+    return p.get();
+  }
+  // host-pointer API staging (default stream)
+  DevBuf<float> wq, wdist;
+  DevBuf<uint32_t> wl32, wcnt, wstats, wrawsz;
+  DevBuf<uint64_t> wl64;
+  DevBuf<Pair> wraw;
+  std::vector<uint64_t> host_labels;   // external labels by internal id
+  std::vector<uint8_t> host_deleted;   // delete marks by internal id
+  DevBuf<uint8_t> wexcl;               // deleted | !allowed of the current filtered call
+  // HNSW-SlimQ (kind == HS_KIND_SLIMQ): RaBitQ records, rotated centroids, rotator flips; `vec` then holds the
+  // dataset rows of hs_slimq_set_dataset()
+  DevBuf<uint32_t> q_rec, q_ftile, q_uptile;
+  DevBuf<float> q_cent;
+  DevBuf<uint8_t> q_flips;
+  DevSlimQ sq{};
+  bool has_dataset = false;
+  uint32_t *trace_ptr = nullptr;   // hs_slimq_trace only
+  uint32_t trace_cap = 0;
+};
+
+// A filter set (hs_filter_set_*): nf bitmap rows over the n internal ids the index had when the set was created (filter_set.hip).
+struct hs_filter_set {
+  int device = 0;
+  size_t n = 0, nf = 0, row_words = 0;
+  DevBuf<uint32_t> bits;     // nf x row_words
+  DevBuf<uint8_t> stage;     // hs_filter_set_write: bounded staging of the host bytes
+  DevBuf<uint8_t> unpacked;  // hs_filter_set_read: one row as bytes
+};
+// What a search under a filter set hands down to the launch plan (null = no filter set).
+struct FilterUse {
+  const hs_filter_set *fs;
+  const uint32_t *d_of_query;   // nq filter indices (device)
+};
+
+// The functions that cross files (shared between the library's own objects, not exported).
+#pragma GCC visibility push(hidden)
+// capi_index.cpp; the calling thread's last error text (hs_last_error) is one thread-local there
+hs_status fail(hs_status s, const std::string &msg);
+hs_status from_exception(const std::exception &e);
+hs_status upload(hs_index *ix, const PackedIndex &p);
+// capi_slimq.cpp
+hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, hs_index **out);
+// capi_search.cpp
+hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k, int mode, uint32_t *l32, uint64_t *l64, float *dd,
+                     uint32_t *cnt, uint32_t *stats, Pair *raw, uint32_t *rawsz, hipStream_t stream, const FilterUse *fu = nullptr);
+hs_status search_async(hs_index *ix, const float *queries, size_t nq, size_t k, int mode, uint32_t *l32, uint64_t *l64, float *dd,
+                       uint32_t *cnt, uint32_t *stats, hipStream_t st, const FilterUse *fu = nullptr);
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// engine.hpp -- device-side index view + launch interface shared by beam_search.hip and capi.cpp.
+// engine.hpp -- device-side index view + launch interface shared by the kernels (*.hip), the launch plan (search_plan.cpp) and the C ABI (capi_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

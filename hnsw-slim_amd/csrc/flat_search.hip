@@ -1143,7 +1143,7 @@ bool flatk_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
   return ix.tile0 != nullptr && (ix.maxlevel == 0 || ix.uptile != nullptr) && ix.threshold_level == 0 && !ix.has_deleted && ix.n > 0 &&
          ix.n < kFDone && (ix.dim & 15u) == 0 && ef >= k && ef <= 512 && k <= 64;
 }
-// wavefronts per CU the shape's kernel is resident with (the LDS share of a wave follows from it: capi.cpp plan_flat)
+// wavefronts per CU the shape's kernel is resident with (the LDS share of a wave follows from it: search_plan.cpp plan_flat)
 uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef) {
   const int s = ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 192 ? 3 : ef <= 256 ? 4 : ef <= 384 ? 6 : 8;
   const int d16 = dim == 128 ? 8 : dim == 96 ? 6 : dim == 960 ? 60 : dim > 256 ? -1 : 0;

@@ -1,5 +1,5 @@
 // narrow_rows.hpp -- what "representable" means for a narrow row format, and where an element sits in a narrow row; shared by
-// the conversion kernel (narrow_rows.hip) and the host side (capi.cpp: hs_rows_representable, hs_index_patch).
+// the conversion kernel (narrow_rows.hip) and the host side (capi_index.cpp: hs_rows_representable, hs_index_patch).
 #pragma once
 #include <hip/hip_runtime.h>
 

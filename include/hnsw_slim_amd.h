@@ -235,12 +235,61 @@ hs_status hs_search_check(hs_index *ix, void *stream);
  * hnswalg_slim.h:177-183, 331-332, 353-354, 408-411) through the flat kernel's heap code on the device.  ops: 3 words each
  * {0 = push | 1 = pop, distance bits, id}; wave_pop selects the whole-wave pop; lds_slots: heap slots kept in LDS (the rest
  * in global memory).  out_heap / out_pops: 2 words per entry (n_ops entries of room each); out_n: {final size, pops}. */
-/* Parity/debug entry (host only, no device needed): the flat kernel's visited-set plan for an index of n nodes at (ef, queries per
- * call): out5 = {buckets nb, multiplier m, shift s, id-space bits B, ok}; bucket = h mod nb and remainder = h div nb =
- * umulhi(h, m) >> s must be exact for every h < 2^B and the remainders must fit 15 bits (tests/test_host_cpu.py). */
-hs_status hs_debug_flat_plan(size_t n, size_t ef, size_t nq, uint32_t *out5);
 hs_status hs_debug_heap_ops(const uint32_t *ops, size_t n_ops, int wave_pop, uint32_t lds_slots, uint32_t *out_heap, uint32_t *out_pops,
                             uint32_t *out_n);
+
+/* Parity/debug entries: the launch plan of a search batch -- which kernel serves pass 0, whether the pass is split, every scratch
+ * share -- as the pure function of the three structs below that the search path itself calls (csrc/search_plan.hpp).  The
+ * structs are diagnostic: their layout may change between versions.
+ * hs_plan_diag: the diagnostic environment knobs, as hs_debug_plan_input reads them once per process. */
+typedef enum { HS_PLAN_KERNEL_DEFAULT = 0, HS_PLAN_KERNEL_LEAN = 1, HS_PLAN_KERNEL_FAST = 2 } hs_plan_kernel;   /* HS_KERNEL */
+typedef enum { HS_PLAN_ZERO_COPY_ON = 0, HS_PLAN_ZERO_COPY_OFF = 1, HS_PLAN_ZERO_COPY_IN = 2 } hs_plan_zero_copy; /* HS_ZERO_COPY: unset, "0", "in" */
+typedef struct hs_plan_diag {
+  int32_t kernel;              /* HS_KERNEL=lean|fast (hs_plan_kernel); any other value is the default choice */
+  int32_t lean_forced;         /* HS_LEAN_MIN_EF is set: the lean kernel where it can serve, never the flat one */
+  uint32_t lean_min_ef;        /* ... from this ef upwards (64 when unset) */
+  int32_t order;               /* HS_ORDER: -1 = unset (split pass 0 from 6144 queries), 0 = never, 1 = always, 2 = always, the fast
+                                * kernel without the order launch */
+  int32_t flat;                /* HS_FLAT=0 -> 0: the fast kernel uses its candidate heap from the first expansion; else 1 */
+  int32_t vis16;               /* HS_VIS16=0 -> 0: the fast kernel's visited set in 32-bit slots everywhere; else 1 */
+  int32_t flat_waves_per_cu;   /* HS_FLAT_WAVES_PER_CU: residency the flat kernel's LDS share is planned for (0 = the kernel's own) */
+  int32_t zero_copy;           /* HS_ZERO_COPY (hs_plan_zero_copy); not part of the launch plan */
+  int32_t verbose;             /* HS_VERBOSE is set; not part of the launch plan */
+  int32_t slimq_fused;         /* HS_SLIMQ_FUSED=0 -> 0 (read at every SlimQ load); not part of the launch plan */
+} hs_plan_diag;
+/* Everything the plan may depend on. */
+typedef struct hs_plan_in {
+  uint64_t n, dim;
+  int32_t has_tile0, has_uptile;   /* level-0 / upper-level adjacency tiles exist (max degree <= 64) */
+  int32_t maxlevel, threshold_level, has_deleted, kind;
+  uint64_t ef, k, nq;              /* ef as hs_set_ef left it (the search runs with max(ef, k)); nq: queries of the launch group */
+  int32_t mode;
+  uint32_t user_cand_cap, user_hash_slots;   /* hs_set_capacity */
+  uint32_t grow_cand, grow_hash;             /* doublings hs_search_check learnt from earlier batches */
+  int32_t exact_order, want_raw, has_filter; /* hs_set_exact_order; raw outputs requested; the search names a filter set */
+  int32_t row_fmt, f32_resident;             /* hs_index_set_row_format, hs_index_set_f32_resident */
+  hs_plan_diag diag;
+} hs_plan_in;
+typedef enum { HS_PLAN_FLAT = 0, HS_PLAN_LEAN = 1, HS_PLAN_FAST = 2, HS_PLAN_STRICT = 3 } hs_plan_family;
+typedef struct hs_plan_out {
+  int32_t family, rows;        /* pass 0: kernel family (hs_plan_family) and the row format it reads (hs_row_format) */
+  int32_t split, skip_order;   /* pass 0 runs as descent / order / level-0 search; ... without the order launch */
+  uint32_t ef, mark_ep;
+  uint32_t cand_cap, hash_slots, vis_bits, hash_fill_shift, flat;   /* pass 0 (SearchArgs fields of the same names) */
+  uint32_t lds_bytes;          /* dynamic LDS a pass-0 workgroup asks for (the family's *_lds_bytes) */
+  /* the flat kernel's visited set, planned whether or not that kernel serves pass 0: buckets nb, multiplier m, shift s, id-space
+   * bits B, fits the LDS; bucket = h mod nb and remainder = h div nb = umulhi(h, m) >> s must be exact for every h < 2^B and the
+   * remainders must fit 15 bits (tests/test_host_cpu.py) */
+  uint32_t fl_nb, fl_mul, fl_sh, fl_bits, fl_ok;
+  int32_t rerun_rows;          /* the re-run pass (strict kernel): its row format, statuses, scratch */
+  uint32_t rerun_select_mask, rerun_cand_cap, rerun_hash_slots;
+  uint32_t spill_stride, log_cap, hop_cap;   /* words of tier-2 scratch per query and two of its regions */
+  const char *name;            /* what hs_last_kernel reports after the batch */
+} hs_plan_out;
+/* Host only, no device needed.  HS_ERR_INVALID / HS_ERR_CAPACITY as the search itself would return them. */
+hs_status hs_debug_search_plan(const hs_plan_in *in, hs_plan_out *out);
+/* Fills *in from a live index and the process's knobs, through the function every search launch uses. */
+hs_status hs_debug_plan_input(const hs_index *ix, size_t k, size_t nq, int has_filter, int want_raw, hs_plan_in *in);
 
 /* Host pointers, asynchronous: H2D of the queries, the search and D2H of the requested outputs are enqueued on `stream`
  * and nothing is valid until that stream is synchronised (hs_search_check does it and reports capacity problems).  The

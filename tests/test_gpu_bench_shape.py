@@ -1,5 +1,5 @@
 """The search shape bench.py times, against the oracle: d=128 with the compiled-in flat kernel (flat_kernel<L2, 1 | 2 | 3, 8>,
-flat_search.hip:989-994), batches on both sides of kOrderMinQueries (capi.cpp:678: from 6144 queries a launch runs as descent /
+flat_search.hip:989-994), batches on both sides of kOrderMinQueries (search_plan.hpp: from 6144 queries a launch runs as descent /
 order / level-0 search), the device entry search_ids_dev on non-default streams with two batches in flight.
 
 The index is the bench's: headline_data(50 000, 128, 123), M=16, efC=200, branching factor 4, seed 100, Slim defaults.  For every

@@ -57,7 +57,7 @@ def test_flat_kernel_wide_result_sets_and_long_rows(env, tmp_path, d, metric, in
 
 def test_flat_kernel_long_logs_at_ef_512(env, tmp_path):
     """ef = 512 on a graph small enough that every query visits most of it: the insertion log and the per-hop counts run long
-    (capi.cpp log_cap_for / hop_cap_for) and ties at the bound are frequent on integer rows."""
+    (search_plan.cpp log_cap_for / hop_cap_for) and ties at the bound are frequent on integer rows."""
     P, O = env
     d = 48
     base = np.ascontiguousarray(mixture(20000, d, 5, n_clusters=6, lo=0, hi=4, sigma=1.2, integer=True))

@@ -208,7 +208,7 @@ np.savez(sys.argv[3], **out)
     hs.build_hnsw(base, str(tmp_path / "h.bin"), M=16, ef_construction=100, threads=8)
     hs.convert_slim(str(tmp_path / "h.bin"), str(tmp_path / "s.bin"), 128, threads=8)
     res = {}
-    # (the last two force the descent / order / level-0 launches of large batches, csrc/capi.cpp, onto this 300-query batch)
+    # (the last two force the descent / order / level-0 launches of large batches, csrc/search_plan.cpp, onto this 300-query batch)
     for tag, env in (("fast", {"HS_LEAN_MIN_EF": "100000", "HS_ORDER": "0"}), ("flat", {"HS_KERNEL": "flat", "HS_ORDER": "0"}), ("flat_ordered", {"HS_KERNEL": "flat", "HS_ORDER": "1"}),
                      ("lean", {"HS_LEAN_MIN_EF": "1", "HS_ORDER": "0"}),
                      ("fast_ordered", {"HS_LEAN_MIN_EF": "100000", "HS_ORDER": "1"}), ("lean_ordered", {"HS_LEAN_MIN_EF": "1", "HS_ORDER": "1"}),

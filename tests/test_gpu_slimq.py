@@ -235,7 +235,7 @@ def test_slimq_file_rewritten_by_python(env):
 
 def test_slimq_second_pass_with_starved_expanded_set(env):
     """hs_set_capacity(hash_slots = 32): the first pass's expanded-node set overflows on most queries (ST_OVERFLOW) and the second
-    pass -- the set per workgroup in global memory, capi.cpp kSlimQFbHash -- must give the oracle's answers."""
+    pass -- the set per workgroup in global memory, capi_slimq.cpp kSlimQFbHash -- must give the oracle's answers."""
     P, O, tmp = env
     x = sift_like(5000 + 200, 128, seed=17, n_clusters=32)
     base, q = x[:5000], x[5000:]

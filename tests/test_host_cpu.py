@@ -179,7 +179,8 @@ def test_flat_kernel_visited_set_plan_divides_exactly():
               (100_000_000, 256, 10_000), (2_000_000_000, 128, 10_000)]
     shapes += [(int(rng.integers(2, 1 << 31)), int(rng.integers(1, 257)), int(rng.integers(1, 40_000))) for _ in range(40)]
     for n, ef, nq in shapes:
-        p = hs.debug_flat_plan(n, ef, nq)
+        p = hs.debug_search_plan(hs.plan_input(n=n, dim=128, ef=ef, k=1, nq=nq))
+        p = dict(nb=p["fl_nb"], mul=p["fl_mul"], sh=p["fl_sh"], bits=p["fl_bits"], ok=p["fl_ok"])
         assert (1 << p["bits"]) >= n and p["bits"] <= 31
         if not p["ok"]:
             continue

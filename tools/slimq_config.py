@@ -122,7 +122,7 @@ s = torch.cuda.current_stream().cuda_stream
 streams = [torch.cuda.Stream() for _ in range(4)]
 outs = [(torch.empty_like(lab), torch.empty_like(dd), torch.empty_like(cnt)) for _ in range(4)]
 rec_bytes = 16 + (d + 63) // 64 * 8
-tile = max(16, (int(ix.info()["max_degree0"]) + 15) // 16 * 16)   # ids per adjacency tile (capi.cpp tile_stride_for)
+tile = max(16, (int(ix.info()["max_degree0"]) + 15) // 16 * 16)   # ids per adjacency tile (capi_index.cpp tile_stride_for)
 print("adjacency tile", tile, "ids", flush=True)
 for ef in [int(e) for e in os.environ.get("EFS", "64,128,256,512,1024").split(",")]:
     ix.set_ef(ef); ox.set(ef, ix.slimq_tconst(), base)

@@ -24,7 +24,7 @@ def per_launch(path, kernel_sub, counters):
 
 
 # A 10k-query pass of the fast kernel is two dispatches since round 2 (descent, then level-0 search in entry-distance order,
-# csrc/capi.cpp search_dev_group): "per launch" figures are per PASS, i.e. the per-dispatch average times two.
+# csrc/capi_search.cpp search_dev_group): "per launch" figures are per PASS, i.e. the per-dispatch average times two.
 DISPATCHES_PER_PASS = {"fast_kernel": 2, "lean_kernel": 2, "flat_kernel": 2} if (len(sys.argv) > 1 and sys.argv[1] != "r01") else {}
 
 
