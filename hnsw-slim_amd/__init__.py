@@ -33,6 +33,8 @@ EXPORTS = [
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
     "hs_index_exact_search", "hs_index_exact_search_dev",
+    "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
+    "hs_index_deleted_count", "hs_hnsw_resume",
 ]
 
 
@@ -154,7 +156,18 @@ def lib():
     L.hs_search_batch_filter_set_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     L.hs_index_exact_search.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
+    L.hs_index_seed_levels.argtypes = [vp, sz, sz]
+    L.hs_index_mark_deleted.argtypes = [vp, vp, sz, ci]
+    L.hs_index_save.argtypes = [vp, ctypes.c_char_p]
+    L.hs_index_get_row.argtypes = [vp, ctypes.c_uint64, vp]
+    L.hs_index_capacity.restype = sz
+    L.hs_index_capacity.argtypes = [vp]
+    L.hs_index_deleted_count.restype = sz
+    L.hs_index_deleted_count.argtypes = [vp]
+    L.hs_hnsw_resume.argtypes = [ctypes.c_char_p, ci, sz, sz, vp, vp, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_build_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
+    L.hs_build_hnsw_labeled.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_convert_slimq_graph.argtypes = L.hs_convert_slim.argtypes
     L.hs_host_device_pointer.restype = ctypes.c_void_p
@@ -192,11 +205,30 @@ def device_count():
     return lib().hs_device_count()
 
 
-def build_hnsw(base, out_path, metric=HS_METRIC_L2, M=16, ef_construction=200, branching_factor="4", seed=100, threads=1):
-    """HierarchicalNSW ctor + addPoint loop (labels = row index) + saveIndex, on the CPU (harness)."""
+def build_hnsw(base, out_path, metric=HS_METRIC_L2, M=16, ef_construction=200, branching_factor="4", seed=100, threads=1, labels=None):
+    """HierarchicalNSW ctor + addPoint loop (labels = row index unless given) + saveIndex, on the CPU (harness)."""
     base = np.ascontiguousarray(base, np.float32)
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, np.uint64)
+        if lab.shape != (base.shape[0],):
+            raise HsError(HS_ERR_INVALID, "labels: one per row")
+        _check(lib().hs_build_hnsw_labeled(base.ctypes.data, lab.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction,
+                                           str(branching_factor).encode(), seed, threads, out_path.encode()))
+        return
     _check(lib().hs_build_hnsw(base.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction,
                                str(branching_factor).encode(), seed, threads, out_path.encode()))
+
+
+def hnsw_resume(in_path, out_path, rows, labels, dim=None, metric=HS_METRIC_L2, max_elements=0, seed=100, drawn=0, threads=1):
+    """hs_hnsw_resume (host only): load `in_path` with room for `max_elements`, put the level generator where a build with `seed`
+    that has added `drawn` points left it, addPoint(rows[i], labels[i]) for every row, saveIndex(out_path)."""
+    r = np.ascontiguousarray(rows, np.float32)
+    r = r.reshape(-1, dim) if r.ndim != 2 else r
+    lab = np.ascontiguousarray(labels, np.uint64)
+    if lab.shape != (r.shape[0],):
+        raise HsError(HS_ERR_INVALID, "labels: one per row")
+    _check(lib().hs_hnsw_resume(in_path.encode(), metric, r.shape[1] if dim is None else dim, max_elements, r.ctypes.data,
+                                lab.ctypes.data, r.shape[0], seed, drawn, threads, out_path.encode()))
 
 
 def convert_slim(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_level=0, top_degree_percent0=0.02,
@@ -612,6 +644,41 @@ class Index:
         """patchFromStream: apply a genPatch stream to this device-resident Slim index (loaded with max_elements > count)."""
         b = bytes(stream_bytes)
         _check(lib().hs_index_patch(self._h, b, len(b), 1 if to_add else 0))
+
+    # -- live updates (HS_KIND_HNSW) ----------------------------------------------------------------
+    def add_points(self, rows, labels, threads=1):
+        """hs_index_add_points: addPoint(rows[i], labels[i]) for new labels on an index loaded with max_elements > its count."""
+        r = np.ascontiguousarray(rows, np.float32)
+        r = r.reshape(-1, self.dim) if r.ndim != 2 else r
+        lab = np.ascontiguousarray(labels, np.uint64)
+        if lab.shape != (r.shape[0],) or r.shape[1] != self.dim:
+            raise HsError(HS_ERR_INVALID, "add_points: rows count x dim, one label per row")
+        _check(lib().hs_index_add_points(self._h, r.ctypes.data, lab.ctypes.data, r.shape[0], threads))
+
+    def seed_levels(self, seed, drawn):
+        """hs_index_seed_levels: the level generator as a build with `seed` holds it after `drawn` points."""
+        _check(lib().hs_index_seed_levels(self._h, int(seed), int(drawn)))
+
+    def mark_deleted(self, labels, on=True):
+        """hs_index_mark_deleted: markDelete (on) / unmarkDelete (not on) of every label, all or nothing."""
+        lab = np.ascontiguousarray(np.atleast_1d(labels), np.uint64)
+        _check(lib().hs_index_mark_deleted(self._h, lab.ctypes.data, lab.shape[0], 1 if on else 0))
+
+    def save(self, path):
+        """hs_index_save: saveIndex of the host image (an index loaded with max_elements > its count)."""
+        _check(lib().hs_index_save(self._h, path.encode()))
+
+    def get_row(self, label):
+        """hs_index_get_row: getDataByLabel, read back from the device (dim float32)."""
+        out = np.empty(self.dim, np.float32)
+        _check(lib().hs_index_get_row(self._h, int(label), out.ctypes.data))
+        return out
+
+    def capacity(self):
+        return int(lib().hs_index_capacity(self._h))
+
+    def deleted_count(self):
+        return int(lib().hs_index_deleted_count(self._h))
 
     def info(self):
         i = HsInfo()

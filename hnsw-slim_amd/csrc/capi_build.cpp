@@ -27,6 +27,39 @@ hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_
   return HS_OK;
 }
 
+// Continue a saved build on the host: loadIndex(in_path, space, max_elements), the level generator put where a build that has drawn
+// `drawn` levels from `seed` left it, addPoint for each row, saveIndex.  Refusals (capacity, a label that exists or appears twice)
+// happen before anything is added, and nothing is written.
+hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows, const uint64_t *labels,
+                         size_t count, size_t seed, size_t drawn, int threads, const char *out_path) {
+  if (!in_path || !out_path || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
+  try {
+    VanillaGraph g;
+    g.load(in_path, (Metric)metric, dim, max_elements);
+    if (g.count + count > g.max_elements) return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // hnswalg.h:1274-1277
+    std::unordered_map<uint64_t, size_t> seen;
+    seen.reserve(g.count + count);
+    for (size_t i = 0; i < g.count; i++) seen.emplace(g.label((uint32_t)i), (size_t)-1);
+    for (size_t i = 0; i < count; i++) {
+      auto ins = seen.emplace(labels[i], i);
+      if (ins.second) continue;
+      if (ins.first->second == (size_t)-1)
+        return fail(HS_ERR_UNSUPPORTED, "label " + std::to_string(labels[i]) + " (row " + std::to_string(i) + ") already exists: updatePoint is not supported");
+      return fail(HS_ERR_INVALID, "label " + std::to_string(labels[i]) + " appears twice in the call (rows " + std::to_string(ins.first->second) + " and " + std::to_string(i) + ")");
+    }
+    g.seed_levels(seed, drawn);
+    g.resume(rows, labels, count, threads);
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
 hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
                           float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
                           size_t low_degree_m, int threads, const char *out_path) {

@@ -32,11 +32,11 @@ static size_t first_unfit(const float *x, size_t count) {
     if (!narrow_fits<T>(x[i])) return i;
   return count;
 }
-static size_t first_unfit(const float *x, size_t count, int fmt) {
+size_t first_unfit(const float *x, size_t count, int fmt) {
   return fmt == ROWS_U8 ? first_unfit<uint8_t>(x, count) : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : count;
 }
 static const char *row_format_name(int fmt) { return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : "HS_ROWS_F32"; }
-static std::string unfit_message(size_t row, size_t comp, float v, int fmt) {
+std::string unfit_message(size_t row, size_t comp, float v, int fmt) {
   char val[64];
   snprintf(val, sizeof val, "%.9g", (double)v);
   return "row " + std::to_string(row) + " holds " + val + " (component " + std::to_string(comp) + "), which " + row_format_name(fmt) +
@@ -47,7 +47,7 @@ static size_t narrow_copy_bytes(const hs_index *ix, int fmt) {
   return std::max<size_t>(ix->cap_rows, ix->info.n) * ix->info.dim * narrow_width(fmt);
 }
 // Fills `out` (allocated here) with the narrow copy of all rows of ix->vec.  HS_ERR_UNSUPPORTED, `out` released, when a value does not fit.
-static hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out) {
+hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out) {
   const size_t n = ix->info.n, dim = ix->info.dim;
   HIP_TRY(out.alloc(std::max<size_t>(narrow_copy_bytes(ix, fmt), 16)));
   HIP_TRY(ix->narrow_bad.ensure(1));
@@ -148,10 +148,10 @@ static std::vector<uint32_t> build_uptile(const PackedIndex &p, uint32_t &up_str
   }
   return ut;
 }
-static uint32_t tile_stride_for(size_t max_deg0) { return max_deg0 <= 64 ? std::max<uint32_t>(16, (uint32_t)((max_deg0 + 15) / 16 * 16)) : 0; }
+uint32_t tile_stride_for(size_t max_deg0) { return max_deg0 <= 64 ? std::max<uint32_t>(16, (uint32_t)((max_deg0 + 15) / 16 * 16)) : 0; }
 
 // the graph-structure arrays that are small next to the vectors and tiles: uploaded whole (also after a patch)
-static hs_status upload_small(hs_index *ix, const PackedIndex &p) {
+hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   HIP_TRY(ix->row_ptr0.upload(p.row_ptr0));
   HIP_TRY(ix->cols.upload(p.cols));
   HIP_TRY(upload_cap(ix->up_base, p.up_base, ix->cap_rows));
@@ -169,7 +169,7 @@ static hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   i.n = p.n; i.dim = p.dim; i.kind = p.kind; i.metric = p.metric; i.maxlevel = p.maxlevel;
   i.threshold_level = p.threshold_level; i.enterpoint = p.enterpoint; i.has_deleted = p.has_deleted;
   i.n_edges = p.cols.size(); i.max_degree0 = p.max_deg0; i.index_size = p.index_size;
-  i.device_bytes = p.vec.size() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
+  i.device_bytes = p.row_values() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
                    p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4 + ix->narrow_bytes;
   // without resident fp32 rows: less what hs_index_set_f32_resident(ix, 0) takes off, the array's whole row capacity (the sum
   // above counts its n rows; an index with far more capacity than rows would go below zero, so it stops there)
@@ -213,11 +213,13 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
   if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   PackedIndex p;
   std::unique_ptr<SlimGraph> keep_slim;
+  std::unique_ptr<VanillaGraph> keep_vanilla;
   try {
     if (kind == HS_KIND_HNSW) {
-      VanillaGraph g;
-      g.load(src, (Metric)metric, dim, max_elements);
-      p.from_vanilla(g);
+      std::unique_ptr<VanillaGraph> g(new VanillaGraph());
+      g->load(src, (Metric)metric, dim, max_elements);
+      p.from_vanilla(*g);
+      if (max_elements > g->count) keep_vanilla = std::move(g);   // room for addPoint (hs_index_add_points), a file for hs_index_save
     } else if (kind == HS_KIND_SLIM) {
       std::unique_ptr<SlimGraph> g(new SlimGraph());
       g->load(src, (Metric)metric, dim);
@@ -236,6 +238,7 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
   hs_index *ix = new hs_index();
   ix->device = device;
   if (keep_slim) { ix->cap_rows = max_elements; ix->host_slim = std::move(keep_slim); }
+  if (keep_vanilla) { ix->cap_rows = max_elements; ix->host_vanilla = std::move(keep_vanilla); }
   if (narrow_fmt != ROWS_F32) { ix->row_fmt = narrow_fmt; ix->f32_resident = false; }
   hs_status s = upload(ix, p);
   if (s != HS_OK) { delete ix; return s; }

@@ -11,6 +11,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/hnsw_slim_amd.h"
@@ -67,6 +68,14 @@ struct hs_index {
   // patching (hs_index_patch): a Slim index loaded with max_elements > count keeps its host image and has row capacity
   std::unique_ptr<SlimGraph> host_slim;
   size_t cap_rows = 0;
+  // live updates (capi_update.cpp): a vanilla index loaded with max_elements > count keeps its host image too (addPoint continues
+  // on it, hs_index_save writes it); the label -> internal id map (the reference's label_lookup_) and the number of delete marks
+  // (num_deleted_) are built from host_labels / host_deleted the first time a call needs them
+  std::unique_ptr<VanillaGraph> host_vanilla;
+  std::unordered_map<uint64_t, uint32_t> label_to_id;
+  bool label_map_built = false;
+  size_t num_deleted = 0;
+  DevBuf<uint32_t> upd_stage;    // the records of the update call being applied (grow-only)
   DevIndex dev{};
   DevBuf<float> vec;
   DevBuf<uint32_t> row_ptr0, cols, up_base, up_ptr, tile0, uptile;
@@ -146,6 +155,11 @@ struct FilterUse {
 hs_status fail(hs_status s, const std::string &msg);
 hs_status from_exception(const std::exception &e);
 hs_status upload(hs_index *ix, const PackedIndex &p);
+hs_status upload_small(hs_index *ix, const PackedIndex &p);
+uint32_t tile_stride_for(size_t max_deg0);
+hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out);
+size_t first_unfit(const float *x, size_t count, int fmt);   // first value not representable in the row format, `count` when none
+std::string unfit_message(size_t row, size_t comp, float v, int fmt);
 // capi_slimq.cpp
 hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, hs_index **out);
 // capi_search.cpp

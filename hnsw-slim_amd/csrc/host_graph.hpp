@@ -144,6 +144,11 @@ struct VanillaGraph {
   std::vector<int> levels;
   std::unique_ptr<std::mutex[]> locks;
   std::mutex global;
+  // resume (hs_hnsw_resume, hs_index_add_points): level_generator_ as the reference holds it -- default-constructed after
+  // loadIndex (the loading constructor, hnswalg.h:78-83, seeds nothing), seeded by the building constructor (:113)
+  std::default_random_engine level_gen;
+  std::vector<uint32_t> *touched0 = nullptr;   // when set: every node whose level-0 list connect() wrote (new nodes included)
+  std::mutex touched_mu;
 
   void init(size_t n, size_t d, Metric m, size_t M_, size_t efC_, const std::string &bf) {
     max_elements = n; dim = d; metric = m;
@@ -252,6 +257,11 @@ struct VanillaGraph {
     sel.reserve(M);
     while (!top.empty()) { sel.push_back(top.top().second); top.pop(); }
     uint32_t next_ep = sel.back();
+    if (level == 0 && touched0) {
+      std::lock_guard<std::mutex> g(touched_mu);
+      touched0->push_back(cur_c);
+      touched0->insert(touched0->end(), sel.begin(), sel.end());
+    }
     {
       uint32_t *l = list_at(cur_c, level);
       if (*l) throw std::runtime_error("The newly inserted element should have blank link list");
@@ -358,7 +368,7 @@ struct VanillaGraph {
     if (threads < 1) threads = 1;
     Visited v0;
     size_t serial_head = threads > 1 ? std::min<size_t>(n, 1) : n;
-    for (size_t i = 0; i < serial_head; i++) { count = i + 1; add_point(base + i * d, i, labels ? labels[i] : i, lv[i], v0); }
+    for (size_t i = 0; i < serial_head; i++) { count = i + 1; add_point(base + i * d, labels ? labels[i] : i, (uint32_t)i, lv[i], v0); }
     if (serial_head < n) {
       std::atomic<size_t> next(serial_head);
       std::atomic<bool> failed(false);
@@ -373,7 +383,7 @@ struct VanillaGraph {
             size_t i = next.fetch_add(1);
             if (i >= n || failed) break;
             try {
-              add_point(base + i * d, i, labels ? labels[i] : i, lv[i], vl);
+              add_point(base + i * d, labels ? labels[i] : i, (uint32_t)i, lv[i], vl);
             } catch (std::exception &e) {
               std::lock_guard<std::mutex> g(err_mu);
               err = e.what();
@@ -385,6 +395,62 @@ struct VanillaGraph {
       if (failed) throw std::runtime_error(err);
     }
     count = n;
+  }
+
+  // getRandomLevel (hnswalg.h:217-221): one draw of level_gen
+  int draw_level() {
+    std::uniform_real_distribution<double> distribution(0.0, 1.0);
+    return (int)(-log(distribution(level_gen)) * mult);
+  }
+  // level_generator_.seed(seed) as the building constructor does (hnswalg.h:113), then `drawn` levels discarded: the state of a
+  // build that has added `drawn` points
+  void seed_levels(size_t seed, size_t drawn) {
+    level_gen.seed(seed);
+    for (size_t i = 0; i < drawn; i++) (void)draw_level();
+  }
+  // Continue the addPoint loop (hnswalg.h:1248-1376, new labels only) on a graph with spare capacity -- built here or loaded with
+  // max_elements > count; mult, M and ef_construction are the file header's.  Row i becomes internal id count + i; its level is
+  // drawn from level_gen in row order, so threads == 1 is the reference's serial order bit for bit.  threads > 1 as build():
+  // a first point of an empty graph serially, the rest in parallel.  The caller has checked capacity and labels.
+  void resume(const float *rows, const uint64_t *labels, size_t n_add, int threads) {
+    if (count + n_add > max_elements) throw std::runtime_error("The number of elements exceeds the specified limit");
+    const size_t first = count, d = dim;
+    std::vector<int> lv(n_add);
+    for (size_t i = 0; i < n_add; i++) lv[i] = draw_level();
+    if (threads < 1) threads = 1;
+    Visited v0;
+    const size_t serial_head = threads > 1 ? (first == 0 ? std::min<size_t>(n_add, 1) : 0) : n_add;
+    for (size_t i = 0; i < serial_head; i++) { count = first + i + 1; add_point(rows + i * d, labels[i], (uint32_t)(first + i), lv[i], v0); }
+    if (serial_head < n_add) {
+      std::atomic<size_t> next(serial_head);
+      std::atomic<bool> failed(false);
+      std::string err;
+      std::mutex err_mu;
+      count = first + n_add;
+      std::vector<std::thread> pool;
+      for (int t = 0; t < threads; t++)
+        pool.emplace_back([&]() {
+          Visited vl;
+          while (true) {
+            size_t i = next.fetch_add(1);
+            if (i >= n_add || failed) break;
+            try {
+              add_point(rows + i * d, labels[i], (uint32_t)(first + i), lv[i], vl);
+            } catch (std::exception &e) {
+              std::lock_guard<std::mutex> g(err_mu);
+              err = e.what();
+              failed = true;
+            }
+          }
+        });
+      for (auto &th : pool) th.join();
+      if (failed) throw std::runtime_error(err);
+    }
+    count = first + n_add;
+  }
+  void set_deleted(uint32_t i, bool on) {   // markDeletedInternal / unmarkDeletedInternal's byte (hnswalg.h:946-947, 989-990)
+    unsigned char *b = (unsigned char *)el(i) + 2;
+    *b = on ? (*b | 1) : (*b & ~1);
   }
 
   void save(const std::string &path) const {  // hnswalg.h:748-779
@@ -451,6 +517,7 @@ struct VanillaGraph {
     }
     if (r.in.tellg() != total) throw std::runtime_error("Index seems to be corrupted or unsupported");  // :835-836
     locks.reset(new std::mutex[std::max<size_t>(max_elements, count)]);
+    level_gen = std::default_random_engine();
   }
   size_t num_deleted() const { size_t c = 0; for (size_t i = 0; i < count; i++) c += deleted(i); return c; }
 };
@@ -961,24 +1028,29 @@ struct PackedIndex {
   size_t max_deg0 = 0;
   size_t index_size = 0;   // what the reference's indexSize() reports for this index (graph structure without vectors)
   std::vector<float> vec;
+  bool rows_on_device = false;   // `vec` left empty on purpose: the device already holds the n rows (from_vanilla(g, false))
+  size_t row_values() const { return rows_on_device ? n * dim : vec.size(); }
   std::vector<uint32_t> row_ptr0, cols, up_base, up_ptr;
   std::vector<uint64_t> labels;
   std::vector<uint8_t> deleted;
 
   static constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-  void from_vanilla(const VanillaGraph &g) {
+  // with_rows = false (hs_index_add_points, whose device rows are written record by record): `vec` stays empty
+  void from_vanilla(const VanillaGraph &g, bool with_rows = true) {
     kind = 0; metric = g.metric; n = g.count; dim = g.dim;
     // HierarchicalNSW::indexSize() (hnswalg.h:1533-1547): level-0 block without vectors and labels, element_levels_,
     // one pointer per element + its upper link lists (+1 as malloc'd)
     index_size = g.max_elements * (g.size_per_el - g.dim * 4 - 8) + g.max_elements * sizeof(int);
     for (size_t i = 0; i < g.count; i++) index_size += 8 + (g.levels[i] > 0 ? g.size_links_up * (size_t)g.levels[i] + 1 : 0);
     maxlevel = g.maxlevel; threshold_level = 0; enterpoint = g.enterpoint;
-    vec.resize(n * dim); labels.resize(n); deleted.resize(n);
+    rows_on_device = !with_rows;
+    vec.resize(with_rows ? n * dim : 0); labels.resize(n); deleted.resize(n);
     row_ptr0.assign(n + 1, 0); up_base.assign(n, NONE); up_ptr.clear(); cols.clear();
+    max_deg0 = 0;
     size_t nd = 0;
     for (size_t i = 0; i < n; i++) {
-      memcpy(&vec[i * dim], g.vec(i), 4 * dim);
+      if (with_rows) memcpy(&vec[i * dim], g.vec(i), 4 * dim);
       labels[i] = g.label(i);
       deleted[i] = g.deleted(i);
       nd += deleted[i];

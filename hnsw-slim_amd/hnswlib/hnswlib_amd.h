@@ -14,8 +14,10 @@
 //   hnswalg_slim.h:28-30,83-87,149-152,193,753,867,1907,2030   HierarchicalNSWSlim<float>
 // Filter functors are host callbacks: the facade evaluates one once per element into an allowed-array
 // (cached per functor object) and calls hs_search_batch_filtered.
-// Not provided (outside the search path): addPoint/updatePoint/markDelete, the diff/patch
-// protocol, stop conditions.
+// HierarchicalNSW<float> also changes while resident: addPoint on an index with room, markDelete / unmarkDelete,
+// getDataByLabel, saveIndex (hnswalg.h:896-1001, 1248-1376, 748-779).
+// Not provided: updatePoint / allow_replace_deleted / resizeIndex, the diff/patch protocol (genPatch),
+// stop conditions.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -312,7 +314,17 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     load(location, HS_KIND_HNSW, space_, max_elements_);
     setEf(ef_keep);
     dirty_ = false;
+    // a later addPoint continues this build: the level generator as the constructor's seed left it after these points
+    if (hs_index_capacity(h_) > row_labels_.size())
+      each_replica([&](hs_index *h) { detail::check(hs_index_seed_levels(h, seed_, row_labels_.size())); });
   }
+  // every replica of setDevices (as setExactOrder), or the one index
+  template <class F>
+  void each_replica(F f) {
+    if (replicas_.empty()) f(h_);
+    else for (hs_index *h : replicas_) f(h);
+  }
+  bool resident() const { return h_ && !dirty_; }
   void ensure_built() const {
     if (!dirty_) return;
     char tmpl[] = "/tmp/hnswlib_amd_XXXXXX";
@@ -347,7 +359,15 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     rows_.clear(); row_labels_.clear(); dirty_ = false;
     load(location, HS_KIND_HNSW, s, max_elements_i);
   }
+  // addPoint on a resident index -- loaded with room (loadIndex(path, space, max_elements)), or built here and already searched --
+  // is incremental (hs_index_add_points): the reference's insertion on the host image, the changed rows written in place on the
+  // device.  Before the first search of an index under construction the points are collected as before.
   void addPoint(const void *datapoint, labeltype label, bool = false) override {
+    if (resident()) {
+      const uint64_t l = label;
+      each_replica([&](hs_index *h) { detail::check(hs_index_add_points(h, (const float *)datapoint, &l, 1, 1)); });
+      return;
+    }
     if (!space_ || max_elements_ == 0)
       throw std::runtime_error("hnswlib_amd: addPoint needs the (space, max_elements, M, ef_construction, ..) constructor");
     if (row_labels_.size() >= max_elements_)
@@ -357,9 +377,39 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     row_labels_.push_back(label);
     dirty_ = true;
   }
+  // saveIndex of a resident index that keeps its host image (hs_index_save): marks and added points included
   void saveIndex(const std::string &location) override {
+    if (resident() && hs_index_save(h_, location.c_str()) == HS_OK) return;
     if (row_labels_.empty()) throw std::runtime_error("hnswlib_amd: the device index is read-only; the file it was loaded from is unchanged");
+    if (resident() && hs_index_deleted_count(h_) > 0)
+      throw std::runtime_error("hnswlib_amd: delete marks of an index built without spare capacity cannot be saved (construct it with max_elements above its size)");
     materialize(location);
+  }
+  void markDelete(labeltype label) {   // hnswalg.h:923-936
+    ensure_built();
+    const uint64_t l = label;
+    each_replica([&](hs_index *h) { detail::check(hs_index_mark_deleted(h, &l, 1, 1)); });
+  }
+  void unmarkDelete(labeltype label) {   // hnswalg.h:968-981
+    ensure_built();
+    const uint64_t l = label;
+    each_replica([&](hs_index *h) { detail::check(hs_index_mark_deleted(h, &l, 1, 0)); });
+  }
+  size_t getDeletedCount() const { return h_ ? hs_index_deleted_count(h_) : 0; }
+  size_t getMaxElements() const { return resident() ? hs_index_capacity(h_) : max_elements_; }
+  size_t getCurrentElementCount() const {
+    if (!resident()) return row_labels_.size();
+    hs_info info;
+    detail::check(hs_index_info(h_, &info));
+    return (size_t)info.n;
+  }
+  template <typename data_t>
+  std::vector<data_t> getDataByLabel(labeltype label) const {   // hnswalg.h:896-917
+    ensure_built();
+    if (!h_) throw std::runtime_error("Label not found");
+    std::vector<float> row(dim_);
+    detail::check(hs_index_get_row(h_, label, row.data()));
+    return std::vector<data_t>(row.begin(), row.end());
   }
   std::priority_queue<std::pair<float, labeltype>> searchKnn(const void *query_data, size_t k,
                                                              BaseFilterFunctor *isIdAllowed = nullptr) const override {

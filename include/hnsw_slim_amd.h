@@ -91,6 +91,40 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
  * vectors and level-0 tiles are rewritten in HBM; the small structure arrays are rebuilt.  Like the reference, the stream
  * does not move the enter point.  Not to be called while a search on this index is in flight. */
 hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add);
+/* ---- live updates of a resident vanilla index: addPoint, markDelete, unmarkDelete, saveIndex, getDataByLabel ----------------
+ * A HS_KIND_HNSW index loaded with max_elements > its element count keeps its host image (as a patchable Slim index does) and
+ * device arrays for max_elements rows.  The calls below change such an index in place.  As hs_index_patch: not while a search on the
+ * index is in flight (each call synchronises the device); a filter set created for the old n is refused after an add; filter sets
+ * survive marks untouched (marks are never folded into their rows).
+ *
+ * addPoint(data, label) for `count` NEW labels (hnswalg.h:1248-1376): row i becomes internal id n + i.  The insertion runs on the
+ * host image exactly as the reference's (threads == 1: its serial order; more threads: as hs_build_hnsw, timing dependent); on the
+ * device only the changed nodes are written -- one staging copy, one kernel (csrc/index_update.hip): level-0 tile row, fp32 row
+ * and / or narrow row, label, mark -- and the small structure arrays (CSR, upper levels) are rebuilt whole.  A level-0 list that
+ * outgrows the tile stride re-tiles everything.  All or nothing, checked before anything changes:
+ *   HS_ERR_CAPACITY    "The number of elements exceeds the specified limit" (:1274-1277; also an index loaded without room)
+ *   HS_ERR_UNSUPPORTED a label that already exists (updatePoint is not provided); a row the index's narrow row format cannot
+ *                      represent (the message names the row of the call and the value); a Slim / SlimQ index
+ *   HS_ERR_INVALID     a label that appears twice in the call
+ * Levels come from the index's level generator: after a load it is a default-constructed std::default_random_engine, as the
+ * reference's is (its loading constructor, hnswalg.h:78-83, seeds nothing); hs_index_seed_levels seeds it as the building
+ * constructor does (:113) and discards `drawn` draws, which resumes a build that has added `drawn` points exactly. */
+hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, int threads);
+hs_status hs_index_seed_levels(hs_index *ix, size_t seed, size_t drawn);
+/* markDelete (on != 0, hnswalg.h:923-958) / unmarkDelete (on == 0, :968-1001) of `count` labels of any HS_KIND_HNSW index (no host
+ * image needed).  All or nothing, HS_ERR_INVALID with the reference's texts: "Label not found", "The requested to delete element is
+ * already deleted", "The requested to undelete element is not deleted" (a label named twice in one call meets its own first mark).
+ * hs_info.has_deleted follows num_deleted_ > 0 in both directions (:1421): the first mark moves a bare index from the flat kernel
+ * to the fast / strict kernels, removing the last mark moves it back.  HS_ERR_UNSUPPORTED on Slim / SlimQ indexes. */
+hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t count, int on);
+/* saveIndex (hnswalg.h:748-779) of the host image, marks and added points included.  HS_ERR_INVALID for an index without one. */
+hs_status hs_index_save(const hs_index *ix, const char *path);
+/* getDataByLabel (hnswalg.h:896-917): out[dim], read back from the device -- the fp32 row, or the narrow row of an index without
+ * fp32 rows, widened (exact).  HS_ERR_INVALID "Label not found" for a label that is missing or marked deleted. */
+hs_status hs_index_get_row(hs_index *ix, uint64_t label, float *out);
+size_t hs_index_capacity(const hs_index *ix);        /* getMaxElements: rows the index has room for */
+size_t hs_index_deleted_count(const hs_index *ix);   /* getDeletedCount */
+
 /* ---- narrow rows (no counterpart in the reference) -------------------------------------------------------------------
  * Besides the resident fp32 rows an index can hold a u8 or fp16 copy of them, and the flat kernel -- the default kernel of every
  * bare index -- then reads that copy (hs::flat_kernel_u8 / hs::flat_kernel_f16) and a quarter / half of the row bytes.  The copy must
@@ -427,6 +461,12 @@ hs_status hs_build_hnsw(const float *base, size_t n, size_t dim, int metric, siz
 hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M,
                                 size_t ef_construction, const char *branching_factor, size_t seed, int threads,
                                 const char *out_path);
+/* Host only, no device: loadIndex(in_path, space, max_elements), level generator seeded with `seed` and `drawn` draws discarded
+ * (hs_index_seed_levels), addPoint(rows + i*dim, labels[i]) for i < count, saveIndex(out_path).  threads == 1 is the reference's
+ * serial order: resuming the first n0 rows' build with the remaining rows writes the bytes of the one-shot build.  Refusals as
+ * hs_index_add_points (capacity, existing or repeated label), before anything is added; out_path is then not written. */
+hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows,
+                         const uint64_t *labels, size_t count, size_t seed, size_t drawn, int threads, const char *out_path);
 /* HierarchicalNSWSlim::convertFromHNSW + saveIndex: hnswalg_slim.h:867-1108, 717-751. */
 hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int threshold_level,
                           float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
