@@ -35,6 +35,7 @@ EXPORTS = [
     "hs_index_exact_search", "hs_index_exact_search_dev",
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
+    "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
 ]
 
 
@@ -166,6 +167,10 @@ def lib():
     L.hs_index_deleted_count.restype = sz
     L.hs_index_deleted_count.argtypes = [vp]
     L.hs_hnsw_resume.argtypes = [ctypes.c_char_p, ci, sz, sz, vp, vp, sz, sz, sz, ci, ctypes.c_char_p]
+    L.hs_index_set_replace_deleted.argtypes = [vp, ci]
+    L.hs_index_upsert_points.argtypes = [vp, vp, vp, vp, sz]
+    L.hs_index_resize.argtypes = [vp, sz]
+    L.hs_hnsw_replay.argtypes = [ctypes.c_char_p, ci, sz, sz, ci, vp, sz, vp, ctypes.c_char_p]
     L.hs_build_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_build_hnsw_labeled.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
@@ -229,6 +234,21 @@ def hnsw_resume(in_path, out_path, rows, labels, dim=None, metric=HS_METRIC_L2, 
         raise HsError(HS_ERR_INVALID, "labels: one per row")
     _check(lib().hs_hnsw_resume(in_path.encode(), metric, r.shape[1] if dim is None else dim, max_elements, r.ctypes.data,
                                 lab.ctypes.data, r.shape[0], seed, drawn, threads, out_path.encode()))
+
+
+HS_OP_ADD, HS_OP_MARK, HS_OP_UNMARK, HS_OP_RESIZE = range(4)   # operation kinds of hs_hnsw_replay
+
+
+def hnsw_replay(in_path, out_path, ops, rows, dim, metric=HS_METRIC_L2, max_elements=0, allow_replace_deleted=False):
+    """hs_hnsw_replay (host only): load `in_path`, apply `ops` -- rows of four uint64 {kind, label or new capacity, replace flag,
+    row index into `rows`} -- through the reference's addPoint / markDelete / unmarkDelete / resizeIndex, saveIndex(out_path)."""
+    o = np.ascontiguousarray(ops, np.uint64).reshape(-1, 4)
+    r = np.ascontiguousarray(rows, np.float32).reshape(-1, dim)
+    adds = o[o[:, 0] == HS_OP_ADD]
+    if adds.size and int(adds[:, 3].max()) >= r.shape[0]:
+        raise HsError(HS_ERR_INVALID, "hnsw_replay: an operation names a row beyond `rows`")
+    _check(lib().hs_hnsw_replay(in_path.encode(), metric, dim, max_elements, 1 if allow_replace_deleted else 0, o.ctypes.data, o.shape[0],
+                                r.ctypes.data, out_path.encode()))
 
 
 def convert_slim(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_level=0, top_degree_percent0=0.02,
@@ -654,6 +674,27 @@ class Index:
         if lab.shape != (r.shape[0],) or r.shape[1] != self.dim:
             raise HsError(HS_ERR_INVALID, "add_points: rows count x dim, one label per row")
         _check(lib().hs_index_add_points(self._h, r.ctypes.data, lab.ctypes.data, r.shape[0], threads))
+
+    def upsert_points(self, rows, labels, replace_deleted=None):
+        """hs_index_upsert_points: addPoint(rows[i], labels[i], replace_deleted[i]) serially, as the reference: an existing label is
+        updated, a new label with its flag set takes a deleted slot while one is vacant, anything else is appended."""
+        r = np.ascontiguousarray(rows, np.float32)
+        r = r.reshape(-1, self.dim) if r.ndim != 2 else r
+        lab = np.ascontiguousarray(np.atleast_1d(labels), np.uint64)
+        if lab.shape != (r.shape[0],) or r.shape[1] != self.dim:
+            raise HsError(HS_ERR_INVALID, "upsert_points: rows count x dim, one label per row")
+        fl = None
+        if replace_deleted is not None:
+            fl = np.ascontiguousarray(np.broadcast_to(np.asarray(replace_deleted, bool), lab.shape), np.uint8)
+        _check(lib().hs_index_upsert_points(self._h, r.ctypes.data, lab.ctypes.data, None if fl is None else fl.ctypes.data, r.shape[0]))
+
+    def set_replace_deleted(self, on=True):
+        """hs_index_set_replace_deleted: the constructor's allow_replace_deleted."""
+        _check(lib().hs_index_set_replace_deleted(self._h, 1 if on else 0))
+
+    def resize(self, new_max_elements):
+        """hs_index_resize: resizeIndex; the per-node device arrays move by device-to-device copies."""
+        _check(lib().hs_index_resize(self._h, int(new_max_elements)))
 
     def seed_levels(self, seed, drawn):
         """hs_index_seed_levels: the level generator as a build with `seed` holds it after `drawn` points."""

@@ -1,6 +1,10 @@
-// capi_update.cpp -- the C ABI (include/hnsw_slim_amd.h): a resident vanilla index that changes -- addPoint on its host image with
-// the changed rows written in place on the device (index_update.hip), markDelete / unmarkDelete, saveIndex, getDataByLabel.
+// capi_update.cpp -- the C ABI (include/hnsw_slim_amd.h): a resident vanilla index that changes -- addPoint on its host image, for
+// new labels (hs_index_add_points) and as the reference's upsert with replace_deleted (hs_index_upsert_points), with the changed
+// rows written in place on the device (index_update.hip); markDelete / unmarkDelete, resizeIndex, saveIndex, getDataByLabel; and
+// the host-only replay of an operation list (hs_hnsw_replay).
 #include "capi_internal.hpp"
+
+#include <unordered_set>
 
 #include "index_update.hpp"
 
@@ -13,6 +17,70 @@ static void ensure_update_state(hs_index *ix) {
   ix->num_deleted = 0;
   for (uint8_t d : ix->host_deleted) ix->num_deleted += d != 0;
   ix->label_map_built = true;
+}
+
+// The device side of a call that changed the host image `g` (packed as `p`, without rows): `touched` are the nodes whose level-0
+// list was written, `row_ids` (distinct) the nodes whose row, label or mark changed -- new ids beyond the old count, and ids of
+// existing nodes that an update or a replacement rewrote.  One staging copy and one kernel; the rows come from the host image.
+static hs_status write_changed(hs_index *ix, PackedIndex &p, std::vector<uint32_t> touched, std::vector<uint32_t> row_ids) {
+  const VanillaGraph &g = *ix->host_vanilla;
+  const size_t dim = ix->info.dim;
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
+  const uint32_t stride = tile_stride_for(p.max_deg0);
+  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything (as hs_index_patch)
+    p.vec.resize(p.n * dim);
+    for (size_t i = 0; i < p.n; i++) memcpy(&p.vec[i * dim], g.vec((uint32_t)i), 4 * dim);
+    p.rows_on_device = false;
+    hs_status us = upload(ix, p);
+    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
+    return build_narrow(ix, ix->row_fmt, ix->narrow);
+  }
+  // the changed nodes as records: nodes of which only the level-0 list was written, then the nodes that carry a row
+  std::sort(row_ids.begin(), row_ids.end());
+  std::sort(touched.begin(), touched.end());
+  touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+  std::vector<uint32_t> ids;
+  for (uint32_t t : touched)
+    if (!std::binary_search(row_ids.begin(), row_ids.end(), t)) ids.push_back(t);
+  const uint32_t first_row = (uint32_t)ids.size();
+  ids.insert(ids.end(), row_ids.begin(), row_ids.end());
+  const size_t nrec = ids.size(), nrow = row_ids.size(), row_words = (dim + 3) / 4 * 4;
+  const size_t cap = std::max(ix->cap_rows, p.n);
+  for (uint32_t id : ids)
+    if (id >= p.n || id >= cap) return fail(HS_ERR_INVALID, "internal: changed node outside the index");
+  std::vector<uint32_t> stage(nrec * (4 + (size_t)stride) + nrow * row_words, 0);
+  uint32_t *tiles = stage.data() + nrec * 4;
+  std::fill(tiles, tiles + nrec * stride, 0xFFFFFFFFu);
+  for (size_t r = 0; r < nrec; r++) {
+    const uint32_t id = ids[r];
+    uint32_t *h = stage.data() + r * 4;
+    h[0] = id; h[1] = p.deleted[id]; h[2] = (uint32_t)p.labels[id]; h[3] = (uint32_t)(p.labels[id] >> 32);
+    std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], tiles + r * stride);
+  }
+  for (size_t i = 0; i < nrow; i++) memcpy(stage.data() + nrec * (4 + (size_t)stride) + i * row_words, g.vec(row_ids[i]), 4 * dim);
+  HIP_TRY(ix->upd_stage.ensure(stage.size()));
+  HIP_TRY(hipMemcpy(ix->upd_stage.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
+  UpdateArgs a{};
+  a.stage = ix->upd_stage.p; a.nrec = (uint32_t)nrec; a.first_row = first_row; a.stride = stride;
+  a.dim = (uint32_t)dim; a.row_words = (uint32_t)row_words; a.cap_rows = (uint32_t)cap;
+  a.fmt = ix->row_fmt; a.tile0 = ix->tile0.p;
+  a.vec = ix->f32_resident ? ix->vec.p : nullptr;
+  a.narrow = ix->row_fmt != ROWS_F32 ? (void *)ix->narrow.p : nullptr;
+  a.labels = ix->labels.p; a.deleted = ix->deleted.p;
+  HIP_TRY(launch_index_update(a, nullptr));
+  ix->host_labels = p.labels;
+  ix->host_deleted = p.deleted;
+  hs_status s = upload_small(ix, p);
+  if (s != HS_OK) return s;
+  HIP_TRY(hipDeviceSynchronize());
+  return HS_OK;
+}
+
+// the reference's exception texts with the statuses the header documents
+static hs_status update_exception(const std::exception &e) {
+  if (std::string(e.what()) == "The number of elements exceeds the specified limit") return fail(HS_ERR_CAPACITY, e.what());
+  return from_exception(e);
 }
 
 hs_status hs_index_seed_levels(hs_index *ix, size_t seed, size_t drawn) {
@@ -76,52 +144,9 @@ hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *l
     return from_exception(e);
   }
   for (size_t i = 0; i < count; i++) ix->label_to_id[labels[i]] = (uint32_t)(n0 + i);
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
-  const uint32_t stride = tile_stride_for(p.max_deg0);
-  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything (as hs_index_patch)
-    p.vec.resize(p.n * dim);
-    for (size_t i = 0; i < p.n; i++) memcpy(&p.vec[i * dim], g.vec((uint32_t)i), 4 * dim);
-    p.rows_on_device = false;
-    hs_status us = upload(ix, p);
-    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
-    return build_narrow(ix, ix->row_fmt, ix->narrow);
-  }
-  // the changed nodes as records: existing nodes whose level-0 list was written, then the new nodes
-  std::sort(touched.begin(), touched.end());
-  touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
-  std::vector<uint32_t> ids;
-  for (uint32_t t : touched)
-    if (t < n0) ids.push_back(t);
-  const uint32_t first_new = (uint32_t)ids.size();
-  for (size_t i = 0; i < count; i++) ids.push_back((uint32_t)(n0 + i));
-  const size_t nrec = ids.size(), row_words = (dim + 3) / 4 * 4;
-  std::vector<uint32_t> stage(nrec * (4 + (size_t)stride) + count * row_words, 0);
-  uint32_t *tiles = stage.data() + nrec * 4;
-  std::fill(tiles, tiles + nrec * stride, 0xFFFFFFFFu);
-  for (size_t r = 0; r < nrec; r++) {
-    const uint32_t id = ids[r];
-    uint32_t *h = stage.data() + r * 4;
-    h[0] = id; h[1] = p.deleted[id]; h[2] = (uint32_t)p.labels[id]; h[3] = (uint32_t)(p.labels[id] >> 32);
-    std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], tiles + r * stride);
-  }
-  for (size_t i = 0; i < count; i++) memcpy(stage.data() + nrec * (4 + (size_t)stride) + i * row_words, rows + i * dim, 4 * dim);
-  HIP_TRY(ix->upd_stage.ensure(stage.size()));
-  HIP_TRY(hipMemcpy(ix->upd_stage.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-  UpdateArgs a{};
-  a.stage = ix->upd_stage.p; a.nrec = (uint32_t)nrec; a.first_new = first_new; a.stride = stride;
-  a.dim = (uint32_t)dim; a.row_words = (uint32_t)row_words; a.cap_rows = (uint32_t)std::max(ix->cap_rows, n0);
-  a.fmt = ix->row_fmt; a.tile0 = ix->tile0.p;
-  a.vec = ix->f32_resident ? ix->vec.p : nullptr;
-  a.narrow = ix->row_fmt != ROWS_F32 ? (void *)ix->narrow.p : nullptr;
-  a.labels = ix->labels.p; a.deleted = ix->deleted.p;
-  HIP_TRY(launch_index_update(a, nullptr));
-  ix->host_labels = p.labels;
-  ix->host_deleted = p.deleted;
-  hs_status s = upload_small(ix, p);
-  if (s != HS_OK) return s;
-  HIP_TRY(hipDeviceSynchronize());
-  return HS_OK;
+  std::vector<uint32_t> row_ids(count);
+  for (size_t i = 0; i < count; i++) row_ids[i] = (uint32_t)(n0 + i);
+  return write_changed(ix, p, touched, row_ids);
 }
 
 hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t count, int on) {
@@ -152,12 +177,13 @@ hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t cou
   HIP_TRY(hipMemcpy(ix->upd_stage.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(launch_mark_scatter(ix->upd_stage.p, (uint32_t)count, (uint32_t)ix->info.n, ix->deleted.p, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  for (const auto &kv : pending) {
-    const bool was = ix->host_deleted[kv.first] != 0, now = kv.second != 0;
-    if (was == now) continue;   // (marked and unmarked again inside one call cannot happen: `on` is one value per call)
-    ix->host_deleted[kv.first] = kv.second;
-    if (ix->host_vanilla) ix->host_vanilla->set_deleted(kv.first, now);
-    if (now) ix->num_deleted++; else ix->num_deleted--;
+  // applied in call order (every id occurs once: `on` is one value per call and a repeated label is refused above), which is the
+  // order deleted_elements receives them in when replacement is allowed (hnswalg.h:949-952, 992-995)
+  for (size_t i = 0; i < count; i++) {
+    const uint32_t id = stage[i];
+    ix->host_deleted[id] = on ? 1 : 0;
+    if (ix->host_vanilla) { if (on) ix->host_vanilla->mark(id); else ix->host_vanilla->unmark(id); }
+    if (on) ix->num_deleted++; else ix->num_deleted--;
   }
   // bare_bone_search = !num_deleted_ && !isIdAllowed (hnswalg.h:1421), in both directions
   ix->dev.has_deleted = ix->num_deleted > 0;
@@ -196,6 +222,221 @@ hs_status hs_index_get_row(hs_index *ix, uint64_t label, float *out) {
     const size_t o = narrow_slot((uint32_t)j, (uint32_t)dim);
     if (ix->row_fmt == ROWS_U8) out[j] = (float)raw[o];
     else { _Float16 h; memcpy(&h, raw.data() + 2 * o, 2); out[j] = (float)h; }
+  }
+  return HS_OK;
+}
+
+// ---- upsert, replace_deleted, resizeIndex -------------------------------------------------------------------------------------
+hs_status hs_index_set_replace_deleted(hs_index *ix, int on) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "replace_deleted is supported on a vanilla (HS_KIND_HNSW) index only");
+  if (!ix->host_vanilla) return fail(HS_ERR_INVALID, "index holds no host image to update: load a vanilla index with max_elements > its element count");
+  ix->host_vanilla->set_allow_replace(on != 0);
+  return HS_OK;
+}
+
+// What hs_index_upsert_points would do, played on overlays of the label map, the marks and a copy of deleted_elements (a copy of a
+// libstdc++ unordered_set keeps the bucket count and the element order, so `*begin()` of the copy is the original's at every step).
+// Returns HS_OK when every point of the call will be accepted.
+static hs_status check_upserts(const hs_index *ix, const float *rows, const uint64_t *labels, const uint8_t *flags, size_t count) {
+  const VanillaGraph &g = *ix->host_vanilla;
+  const size_t dim = ix->info.dim;
+  std::unordered_map<uint64_t, int64_t> label_ov;    // label -> internal id, -1: left the map
+  std::unordered_map<uint32_t, uint64_t> id_label;   // labels written by the call
+  std::unordered_map<uint32_t, bool> mark_ov;
+  std::unordered_set<uint32_t> vacant;
+  bool vacant_copied = false;
+  size_t n = g.count;
+  auto find = [&](uint64_t lab) -> int64_t {
+    auto o = label_ov.find(lab);
+    if (o != label_ov.end()) return o->second;
+    auto b = ix->label_to_id.find(lab);
+    return b == ix->label_to_id.end() ? -1 : (int64_t)b->second;
+  };
+  auto marked = [&](uint32_t id) {
+    auto o = mark_ov.find(id);
+    return o != mark_ov.end() ? o->second : (id < g.count && g.deleted(id));
+  };
+  for (size_t i = 0; i < count; i++) {
+    const bool flag = flags && flags[i];
+    if (flag && !g.allow_replace) return fail(HS_ERR_INVALID, "Replacement of deleted elements is disabled in constructor");   // hnswalg.h:1027-1030
+    if (ix->row_fmt != ROWS_F32) {
+      const size_t j = first_unfit(rows + i * dim, dim, ix->row_fmt);
+      if (j < dim) return fail(HS_ERR_UNSUPPORTED, "add refused: " + unfit_message(i, j, rows[i * dim + j], ix->row_fmt));
+    }
+    if (flag && !vacant_copied) { vacant = g.deleted_elements; vacant_copied = true; }
+    if (flag && !vacant.empty()) {
+      const uint32_t id = *vacant.begin();
+      vacant.erase(id);
+      auto il = id_label.find(id);
+      label_ov[il != id_label.end() ? il->second : g.label(id)] = -1;
+      label_ov[labels[i]] = id;
+      id_label[id] = labels[i];
+      mark_ov[id] = false;
+      continue;
+    }
+    const int64_t id = find(labels[i]);
+    if (id >= 0) {
+      if (g.allow_replace && marked((uint32_t)id))   // :1257-1263
+        return fail(HS_ERR_INVALID, "Can't use addPoint to update deleted elements if replacement of deleted elements is enabled.");
+      mark_ov[(uint32_t)id] = false;
+      continue;
+    }
+    if (n >= g.max_elements) return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // :1274-1277
+    label_ov[labels[i]] = (int64_t)n;
+    id_label[(uint32_t)n] = labels[i];
+    n++;
+  }
+  return HS_OK;
+}
+
+hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t *labels, const uint8_t *replace_flags, size_t count) {
+  if (!ix || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "null argument");
+  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "addPoint is supported on a vanilla (HS_KIND_HNSW) index only");
+  if (count && !ix->host_vanilla) {
+    if (replace_flags && std::any_of(replace_flags, replace_flags + count, [](uint8_t f) { return f != 0; }))
+      return fail(HS_ERR_INVALID, "index holds no host image to update: load a vanilla index with max_elements > its element count");
+    return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // an index loaded without room, as hs_index_add_points
+  }
+  if (count == 0) return HS_OK;
+  ensure_update_state(ix);
+  hs_status cs = check_upserts(ix, rows, labels, replace_flags, count);
+  if (cs != HS_OK) return cs;
+  VanillaGraph &g = *ix->host_vanilla;
+  const size_t dim = ix->info.dim;
+  std::vector<uint32_t> touched, row_ids;
+  PackedIndex p;
+  try {
+    g.touched0 = &touched;
+    VanillaGraph::Visited vl;
+    for (size_t i = 0; i < count; i++)
+      row_ids.push_back(g.upsert(rows + i * dim, labels[i], replace_flags && replace_flags[i], ix->label_to_id, vl));
+    g.touched0 = nullptr;
+    p.from_vanilla(g, false);
+  } catch (std::bad_alloc &) {
+    g.touched0 = nullptr;
+    return fail(HS_ERR_NOMEM, "Not enough memory: addPoint failed to allocate linklist");
+  } catch (std::exception &e) {
+    g.touched0 = nullptr;
+    return update_exception(e);
+  }
+  std::sort(row_ids.begin(), row_ids.end());
+  row_ids.erase(std::unique(row_ids.begin(), row_ids.end()), row_ids.end());
+  ix->num_deleted = 0;
+  for (uint8_t d : p.deleted) ix->num_deleted += d != 0;   // upload_small takes has_deleted from the same marks
+  return write_changed(ix, p, touched, row_ids);
+}
+
+// device-to-device move of the first `used` values of a per-node array into an allocation of `cap` values
+template <typename T>
+static hipError_t grow_into(DevBuf<T> &fresh, const DevBuf<T> &old, size_t cap, size_t used) {
+  hipError_t e = fresh.alloc(std::max<size_t>(cap, 1));
+  if (e != hipSuccess) return e;
+  return used && old.p ? hipMemcpy(fresh.p, old.p, used * sizeof(T), hipMemcpyDeviceToDevice) : hipSuccess;
+}
+template <typename T>
+static void take(DevBuf<T> &dst, DevBuf<T> &fresh) {
+  std::swap(dst.p, fresh.p);
+  std::swap(dst.n, fresh.n);
+  fresh.release();
+}
+
+hs_status hs_index_resize(hs_index *ix, size_t new_max_elements) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "resizeIndex is supported on a vanilla (HS_KIND_HNSW) index only");
+  if (new_max_elements < ix->info.n) return fail(HS_ERR_INVALID, "Cannot resize, max element is less than the current number of elements");   // hnswalg.h:690-692
+  if (!ix->host_vanilla) return fail(HS_ERR_INVALID, "index holds no host image to resize: load a vanilla index with max_elements > its element count");
+  if (new_max_elements > 0xFFFFFFFFull) return fail(HS_ERR_INVALID, "max_elements beyond 32-bit internal ids");
+  VanillaGraph &g = *ix->host_vanilla;
+  const size_t n = ix->info.n, dim = ix->info.dim, old_max = g.max_elements;
+  const size_t have = std::max(ix->cap_rows, n);
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its arrays move
+  const bool grow = new_max_elements > have;
+  const size_t w = ix->row_fmt != ROWS_F32 ? narrow_width(ix->row_fmt) : 0;
+  const uint32_t stride = ix->dev.tile_stride;
+  DevBuf<float> vec;
+  DevBuf<uint8_t> narrow, deleted;
+  DevBuf<uint32_t> tile0, up_base;
+  DevBuf<uint64_t> labels;
+  if (grow) {
+    // the new arrays first: a failure here leaves the index as it was
+    const size_t cap = new_max_elements;
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess && ix->f32_resident) e = grow_into(vec, ix->vec, cap * dim, n * dim);
+    if (e == hipSuccess && w) e = grow_into(narrow, ix->narrow, std::max<size_t>(cap * dim * w, 16), n * dim * w);
+    if (e == hipSuccess && ix->tile0.p) e = grow_into(tile0, ix->tile0, cap * stride, n * stride);
+    if (e == hipSuccess) e = grow_into(labels, ix->labels, cap, n);
+    if (e == hipSuccess) e = grow_into(deleted, ix->deleted, cap, n);
+    if (e == hipSuccess) e = grow_into(up_base, ix->up_base, cap, std::min(n, ix->up_base.n));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(HS_ERR_NOMEM, "Not enough memory: resizeIndex failed to allocate the device arrays"); }
+    HIP_TRY(e);
+  }
+  try {
+    g.resize(new_max_elements);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory: resizeIndex failed to allocate base layer");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  if (grow) {
+    if (ix->f32_resident) take(ix->vec, vec);
+    if (w) take(ix->narrow, narrow);
+    if (ix->tile0.p) take(ix->tile0, tile0);
+    take(ix->labels, labels);
+    take(ix->deleted, deleted);
+    take(ix->up_base, up_base);
+    DevIndex &d = ix->dev;
+    d.vec = ix->vec.p; d.labels = ix->labels.p; d.deleted = ix->deleted.p; d.up_base = ix->up_base.p;
+    d.tile0 = stride ? ix->tile0.p : nullptr;
+    // hs_info.device_bytes counts the narrow copy by row capacity (and, without fp32 rows, is short of the fp32 array's capacity)
+    size_t total = ix->info.device_bytes + (ix->f32_resident ? 0 : ix->f32_gone) - ix->narrow_bytes;
+    ix->cap_rows = new_max_elements;
+    ix->narrow_bytes = w ? new_max_elements * dim * w : 0;
+    total += ix->narrow_bytes;
+    if (!ix->f32_resident) { ix->f32_gone = std::min<size_t>(total, new_max_elements * dim * 4); total -= ix->f32_gone; }
+    ix->info.device_bytes = total;
+  }
+  // indexSize() counts the level-0 link block and element_levels_ by max_elements (hnswalg.h:1533-1547)
+  const size_t per = g.size_per_el - dim * 4 - 8 + sizeof(int);
+  ix->info.index_size = ix->info.index_size + new_max_elements * per - old_max * per;
+  return HS_OK;
+}
+
+// ---- host only: loadIndex, a list of operations, saveIndex --------------------------------------------------------------------
+hs_status hs_hnsw_replay(const char *in_path, int metric, size_t dim, size_t max_elements, int allow_replace_deleted, const uint64_t *ops,
+                         size_t n_ops, const float *rows, const char *out_path) {
+  if (!in_path || !out_path || (n_ops && !ops)) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
+  try {
+    VanillaGraph g;
+    g.load(in_path, (Metric)metric, dim, max_elements);
+    g.set_allow_replace(allow_replace_deleted != 0);
+    std::unordered_map<uint64_t, uint32_t> lookup;   // label_lookup_ as loadIndex fills it (hnswalg.h:865-866)
+    for (size_t i = 0; i < g.count; i++) lookup[g.label((uint32_t)i)] = (uint32_t)i;
+    VanillaGraph::Visited vl;
+    for (size_t o = 0; o < n_ops; o++) {
+      const uint64_t kind = ops[4 * o], arg = ops[4 * o + 1], flag = ops[4 * o + 2], row = ops[4 * o + 3];
+      if (kind == HS_OP_ADD) {
+        if (!rows) return fail(HS_ERR_INVALID, "bad argument");
+        g.upsert(rows + row * dim, arg, flag != 0, lookup, vl);
+      } else if (kind == HS_OP_MARK || kind == HS_OP_UNMARK) {
+        auto it = lookup.find(arg);
+        if (it == lookup.end()) return fail(HS_ERR_INVALID, "Label not found");
+        if (kind == HS_OP_MARK) g.mark(it->second); else g.unmark(it->second);
+      } else if (kind == HS_OP_RESIZE) {
+        g.resize(arg);
+      } else {
+        return fail(HS_ERR_INVALID, "bad operation kind " + std::to_string(kind));
+      }
+    }
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return update_exception(e);
   }
   return HS_OK;
 }

@@ -1,7 +1,8 @@
 // host_graph.hpp -- host-side (CPU) index structures around the GPU search path:
 //   * VanillaGraph : hnswlib::HierarchicalNSW memory image; serial-reproducible builder (harness,
 //                    restating hnswalg.h:229-322, 481-687, 1248-1376) + saveIndex/loadIndex
-//                    (hnswalg.h:748-893).  A serial build writes a file byte-identical to the
+//                    (hnswalg.h:748-893) + the update path: updatePoint / repairConnectionsForUpdate,
+//                    addPoint(.., replace_deleted), resizeIndex (hnswalg.h:689-717, 1025-1236).  A serial build writes a file byte-identical to the
 //                    reference's (tests/test_host_graph.py vs tests/golden/*.hnsw.bin).
 //   * SlimGraph    : hnswlib::HierarchicalNSWSlim image: convertFromHNSW (hnswalg_slim.h:836-1108),
 //                    saveIndex/loadIndex (hnswalg_slim.h:717-815).
@@ -22,6 +23,8 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "dist_recipe.hpp"
@@ -147,8 +150,14 @@ struct VanillaGraph {
   // resume (hs_hnsw_resume, hs_index_add_points): level_generator_ as the reference holds it -- default-constructed after
   // loadIndex (the loading constructor, hnswalg.h:78-83, seeds nothing), seeded by the building constructor (:113)
   std::default_random_engine level_gen;
-  std::vector<uint32_t> *touched0 = nullptr;   // when set: every node whose level-0 list connect() wrote (new nodes included)
+  // when set: every node whose level-0 list connect() or update_point() wrote (new and updated nodes included)
+  std::vector<uint32_t> *touched0 = nullptr;
   std::mutex touched_mu;
+  // allow_replace_deleted_ and deleted_elements (hnswalg.h:70-73).  The set is the reference's own container type on purpose:
+  // `*deleted_elements.begin()` decides which slot addPoint(.., true) reuses, and that is a property of libstdc++'s hash table
+  // and of the sequence of inserts and erases, which mark() / unmark() / set_allow_replace() / upsert() keep as the reference's.
+  bool allow_replace = false;
+  std::unordered_set<uint32_t> deleted_elements;
 
   void init(size_t n, size_t d, Metric m, size_t M_, size_t efC_, const std::string &bf) {
     max_elements = n; dim = d; metric = m;
@@ -248,8 +257,10 @@ struct VanillaGraph {
     for (const pairfi &p : keep) top.emplace(-p.first, p.second);
   }
 
-  // mutuallyConnectNewElement (hnswalg.h:549-687), isUpdate == false
-  uint32_t connect(uint32_t cur_c, MaxQ &top, int level) {
+  // mutuallyConnectNewElement (hnswalg.h:549-687).  is_update (:575-577, 584, 591, 624-636): cur_c's list may hold ids -- it is
+  // shortened with the count alone, the old ids stay behind it and saveIndex writes them -- and a neighbour that already lists
+  // cur_c is left as it is.
+  uint32_t connect(uint32_t cur_c, MaxQ &top, int level, bool is_update = false) {
     size_t Mcurmax = level ? maxM : maxM0;
     heuristic(top, M);
     if (top.size() > M) throw std::runtime_error("Should be not be more than M_ candidates returned by the heuristic");
@@ -264,10 +275,10 @@ struct VanillaGraph {
     }
     {
       uint32_t *l = list_at(cur_c, level);
-      if (*l) throw std::runtime_error("The newly inserted element should have blank link list");
+      if (*l && !is_update) throw std::runtime_error("The newly inserted element should have blank link list");
       set_cnt(l, sel.size());
       for (size_t i = 0; i < sel.size(); i++) {
-        if (l[1 + i]) throw std::runtime_error("Possible memory corruption");
+        if (l[1 + i] && !is_update) throw std::runtime_error("Possible memory corruption");
         if (level > levels[sel[i]]) throw std::runtime_error("Trying to make a link on a non-existent level");
         l[1 + i] = sel[i];
       }
@@ -280,6 +291,11 @@ struct VanillaGraph {
       if (sel[i] == cur_c) throw std::runtime_error("Trying to connect an element to itself");
       if (level > levels[sel[i]]) throw std::runtime_error("Trying to make a link on a non-existent level");
       uint32_t *data = lo + 1;
+      bool present = false;
+      if (is_update)
+        for (size_t j = 0; j < sz; j++)
+          if (data[j] == cur_c) { present = true; break; }
+      if (present) continue;
       if (sz < Mcurmax) {
         data[sz] = cur_c;
         set_cnt(lo, sz + 1);
@@ -451,6 +467,167 @@ struct VanillaGraph {
   void set_deleted(uint32_t i, bool on) {   // markDeletedInternal / unmarkDeletedInternal's byte (hnswalg.h:946-947, 989-990)
     unsigned char *b = (unsigned char *)el(i) + 2;
     *b = on ? (*b | 1) : (*b & ~1);
+  }
+
+  // ---- the update path (hnswalg.h:689-717, 943-1001, 1025-1272) ---------------------------------------------------------------
+  // allow_replace_deleted_ as the constructor sets it; turning it on fills deleted_elements from the marks in increasing id, as
+  // loadIndex does (:882-888), into a freshly constructed set
+  void set_allow_replace(bool on) {
+    allow_replace = on;
+    deleted_elements = std::unordered_set<uint32_t>();
+    if (on)
+      for (size_t i = 0; i < count; i++)
+        if (deleted((uint32_t)i)) deleted_elements.insert((uint32_t)i);
+  }
+  void mark(uint32_t i) {     // markDeletedInternal (:943-958)
+    if (deleted(i)) throw std::runtime_error("The requested to delete element is already deleted");
+    set_deleted(i, true);
+    if (allow_replace) deleted_elements.insert(i);
+  }
+  void unmark(uint32_t i) {   // unmarkDeletedInternal (:986-1001)
+    if (!deleted(i)) throw std::runtime_error("The requested to undelete element is not deleted");
+    set_deleted(i, false);
+    if (allow_replace) deleted_elements.erase(i);
+  }
+  std::vector<uint32_t> connections(uint32_t i, int level) const {   // getConnectionsWithLock (:1238-1246)
+    const uint32_t *l = list_at(i, level);
+    return std::vector<uint32_t>(l + 1, l + 1 + cnt_of(l));
+  }
+  void note_touched0(uint32_t i) {
+    if (!touched0) return;
+    std::lock_guard<std::mutex> g(touched_mu);
+    touched0->push_back(i);
+  }
+
+  // updatePoint(dataPoint, internalId, updateNeighborProbability = 1.0) (:1067-1157).  The reference draws
+  // update_probability_generator_ once per one-hop neighbour and skips the neighbour when the draw exceeds the probability; a
+  // draw from [0, 1) never exceeds 1.0 and nothing else reads that generator, so no state is kept for it here.
+  // sCand / sNeigh are std::unordered_set as in the reference: the iteration order of sCand is the insertion order of the
+  // candidate heap, which decides how equal distances are ordered.
+  void update_point(const float *x, uint32_t id, Visited &vl) {
+    memcpy(el(id) + offsetData, x, 4 * dim);
+    note_touched0(id);
+    const int maxLevelCopy = maxlevel;
+    const uint32_t entryPointCopy = enterpoint;
+    if (entryPointCopy == id && count == 1) return;   // :1076-1077
+    const int elemLevel = levels[id];
+    for (int layer = 0; layer <= elemLevel; layer++) {
+      std::unordered_set<uint32_t> sCand, sNeigh;
+      const std::vector<uint32_t> listOneHop = connections(id, layer);
+      if (listOneHop.empty()) continue;
+      sCand.insert(id);
+      for (uint32_t elOneHop : listOneHop) {
+        sCand.insert(elOneHop);
+        sNeigh.insert(elOneHop);
+        for (uint32_t elTwoHop : connections(elOneHop, layer)) sCand.insert(elTwoHop);
+      }
+      for (uint32_t neigh : sNeigh) {
+        MaxQ candidates;
+        const size_t size = sCand.find(neigh) == sCand.end() ? sCand.size() : sCand.size() - 1;
+        const size_t elementsToKeep = std::min(efC, size);
+        for (uint32_t cand : sCand) {
+          if (cand == neigh) continue;
+          const float distance = dist(vec(neigh), vec(cand));
+          if (candidates.size() < elementsToKeep) {
+            candidates.emplace(distance, cand);
+          } else if (distance < candidates.top().first) {
+            candidates.pop();
+            candidates.emplace(distance, cand);
+          }
+        }
+        heuristic(candidates, layer == 0 ? maxM0 : maxM);
+        uint32_t *l = list_at(neigh, layer);
+        const size_t candSize = candidates.size();
+        set_cnt(l, (uint16_t)candSize);   // the count alone: ids behind it stay (and are saved)
+        for (size_t idx = 0; idx < candSize; idx++) { l[1 + idx] = candidates.top().second; candidates.pop(); }
+        if (layer == 0) note_touched0(neigh);
+      }
+    }
+    repair_connections(x, entryPointCopy, id, elemLevel, maxLevelCopy, vl);
+  }
+
+  // repairConnectionsForUpdate (:1159-1236)
+  void repair_connections(const float *x, uint32_t ep, uint32_t id, int dataPointLevel, int maxLevel, Visited &vl) {
+    uint32_t currObj = ep;
+    if (dataPointLevel < maxLevel) {
+      float curdist = dist(x, vec(currObj));
+      for (int level = maxLevel; level > dataPointLevel; level--) {
+        bool changed = true;
+        while (changed) {
+          changed = false;
+          const uint32_t *l = list_at(currObj, level);
+          const int n = cnt_of(l);
+          for (int i = 0; i < n; i++) {
+            const uint32_t cand = l[1 + i];
+            const float d = dist(x, vec(cand));
+            if (d < curdist) { curdist = d; currObj = cand; changed = true; }
+          }
+        }
+      }
+    }
+    if (dataPointLevel > maxLevel) throw std::runtime_error("Level of item to be updated cannot be bigger than max level");
+    for (int level = dataPointLevel; level >= 0; level--) {
+      MaxQ top = search_layer(currObj, x, level, vl);
+      MaxQ filtered;   // the self-filter (:1210-1215)
+      while (!top.empty()) {
+        if (top.top().second != id) filtered.push(top.top());
+        top.pop();
+      }
+      if (filtered.empty()) continue;
+      if (deleted(ep)) {   // epDeleted (:1222-1230)
+        filtered.emplace(dist(x, vec(ep)), ep);
+        if (filtered.size() > efC) filtered.pop();
+      }
+      currObj = connect(id, filtered, level, true);
+    }
+  }
+
+  // addPoint(data_point, label, replace_deleted) (:1025-1065) with the existing-label branch of addPoint(.., level) (:1251-1272),
+  // serial.  `lookup` is label_lookup_, kept by the caller.  Returns the internal id written; *replaced_label (when given) receives
+  // the label that left the index and *reused says whether a deleted slot was taken.
+  uint32_t upsert(const float *x, uint64_t lab, bool replace_deleted, std::unordered_map<uint64_t, uint32_t> &lookup, Visited &vl,
+                  bool *reused = nullptr, uint64_t *replaced_label = nullptr) {
+    if (reused) *reused = false;
+    if (!allow_replace && replace_deleted) throw std::runtime_error("Replacement of deleted elements is disabled in constructor");
+    if (replace_deleted && !deleted_elements.empty()) {
+      const uint32_t id = *deleted_elements.begin();
+      deleted_elements.erase(id);
+      const uint64_t old = label(id);
+      memcpy(el(id) + label_offset, &lab, 8);
+      lookup.erase(old);
+      lookup[lab] = id;
+      unmark(id);
+      update_point(x, id, vl);
+      if (reused) *reused = true;
+      if (replaced_label) *replaced_label = old;
+      return id;
+    }
+    auto it = lookup.find(lab);
+    if (it != lookup.end()) {
+      const uint32_t id = it->second;
+      if (allow_replace && deleted(id))
+        throw std::runtime_error("Can't use addPoint to update deleted elements if replacement of deleted elements is enabled.");
+      if (deleted(id)) unmark(id);
+      update_point(x, id, vl);
+      return id;
+    }
+    if (count >= max_elements) throw std::runtime_error("The number of elements exceeds the specified limit");
+    const uint32_t cur_c = (uint32_t)count;
+    count++;
+    lookup[lab] = cur_c;
+    add_point(x, lab, cur_c, draw_level(), vl);
+    return cur_c;
+  }
+
+  // resizeIndex (:689-717).  The reference reallocs, which leaves the rows beyond the old capacity undefined until addPoint
+  // clears each one; here they are zero.
+  void resize(size_t new_max) {
+    if (new_max < count) throw std::runtime_error("Cannot resize, max element is less than the current number of elements");
+    levels.resize(new_max);
+    locks.reset(new std::mutex[std::max<size_t>(new_max, 1)]);
+    level0.resize(new_max * size_per_el);
+    links.resize(new_max);
+    max_elements = new_max;
   }
 
   void save(const std::string &path) const {  // hnswalg.h:748-779

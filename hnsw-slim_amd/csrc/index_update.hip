@@ -1,12 +1,14 @@
-// index_update.hip -- in-place updates of a resident vanilla index (hs_index_add_points, hs_index_mark_deleted): the changed nodes
-// of a call arrive as records in ONE staging buffer (one host-to-device copy) and one kernel writes them into the index's arrays.
+// index_update.hip -- in-place updates of a resident vanilla index (hs_index_add_points, hs_index_upsert_points,
+// hs_index_mark_deleted): the changed nodes of a call arrive as records in ONE staging buffer (one host-to-device copy) and one
+// kernel writes them into the index's arrays.
 //
-// Staging buffer of a call with nrec records, the first `first_new` of them existing nodes whose level-0 list changed, the rest
-// new nodes (all sections start 16-byte aligned: the header is 16 bytes, the tile stride a multiple of 16 ids, row_words = dim
-// rounded up to a multiple of 4):
+// Staging buffer of a call with nrec records, the first `first_row` of them nodes of which only the level-0 list changed, the rest
+// nodes that carry a row -- new nodes, and existing nodes that an update or a replacement rewrote: a record's id is any id below
+// the row capacity, no id occurs in two records of a call (all sections start 16-byte aligned: the header is 16 bytes, the tile
+// stride a multiple of 16 ids, row_words = dim rounded up to a multiple of 4):
 //   header  nrec x 4 words   {internal id, delete mark (0 / 1), label low word, label high word}
 //   tiles   nrec x stride    the node's level-0 ids padded with 0xFFFFFFFF to the tile stride
-//   rows    (nrec - first_new) x row_words   the fp32 row of each new node
+//   rows    (nrec - first_row) x row_words   the fp32 row of each record from first_row on
 // One wavefront per record: the tile row leaves as 16-byte stores (a row is 64 .. 256 contiguous bytes), the fp32 row -- where the
 // index holds fp32 rows -- as 16-byte loads and stores (4-byte ones for dim % 4 != 0, whose rows are not 16-byte aligned), the
 // narrow row -- where the index holds a narrow copy -- straight in the lane-major layout of narrow_rows.hpp, each lane packing
@@ -51,8 +53,8 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
     uint4 *dst = reinterpret_cast<uint4 *>(a.tile0 + (size_t)id * a.stride);
     if (lane < a.stride / 4) dst[lane] = src[lane];
   }
-  if (r >= a.first_new) {
-    const float *x = reinterpret_cast<const float *>(a.stage + (size_t)a.nrec * (4 + a.stride) + (size_t)(r - a.first_new) * a.row_words);
+  if (r >= a.first_row) {
+    const float *x = reinterpret_cast<const float *>(a.stage + (size_t)a.nrec * (4 + a.stride) + (size_t)(r - a.first_row) * a.row_words);
     if (a.vec) {
       float *dst = a.vec + (size_t)id * a.dim;
       if ((a.dim & 3u) == 0) {
@@ -79,7 +81,7 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
 
 hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream) {
   if (a.nrec == 0) return hipSuccess;
-  if (!a.stage || !a.labels || !a.deleted || a.first_new > a.nrec) return hipErrorInvalidValue;
+  if (!a.stage || !a.labels || !a.deleted || a.first_row > a.nrec) return hipErrorInvalidValue;
   if (a.tile0 && (a.stride == 0 || (a.stride & 15u) != 0 || a.stride > 64)) return hipErrorInvalidValue;
   if (a.narrow && ((a.dim & 15u) != 0 || (a.fmt != ROWS_U8 && a.fmt != ROWS_F16))) return hipErrorInvalidValue;
   const uint32_t per = kUpdateBlock / 64;

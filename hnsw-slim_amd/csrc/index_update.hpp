@@ -11,7 +11,7 @@ constexpr uint32_t kUpdateBlock = 256;   // four records per workgroup, one wave
 
 struct UpdateArgs {
   const uint32_t *stage;   // the uploaded staging buffer (device)
-  uint32_t nrec, first_new;
+  uint32_t nrec, first_row;   // records [first_row, nrec) carry a row
   uint32_t stride;         // tile stride in ids (16 / 32 / 48 / 64); ignored when tile0 is null
   uint32_t dim, row_words; // row_words = dim rounded up to a multiple of 4
   uint32_t cap_rows;       // rows every per-node array below is allocated for

@@ -14,10 +14,11 @@
 //   hnswalg_slim.h:28-30,83-87,149-152,193,753,867,1907,2030   HierarchicalNSWSlim<float>
 // Filter functors are host callbacks: the facade evaluates one once per element into an allowed-array
 // (cached per functor object) and calls hs_search_batch_filtered.
-// HierarchicalNSW<float> also changes while resident: addPoint on an index with room, markDelete / unmarkDelete,
-// getDataByLabel, saveIndex (hnswalg.h:896-1001, 1248-1376, 748-779).
-// Not provided: updatePoint / allow_replace_deleted / resizeIndex, the diff/patch protocol (genPatch),
-// stop conditions.
+// HierarchicalNSW<float> also changes while resident: addPoint on an index with room -- of a new label, of an
+// existing one (the reference's update) and with replace_deleted under the allow_replace_deleted constructor flag -- markDelete /
+// unmarkDelete, resizeIndex, getDataByLabel, saveIndex (hnswalg.h:689-717, 896-1272, 1248-1376, 748-779).
+// Not provided: updateNeighborProbability other than 1.0, updates of Slim / SlimQ indexes, the diff/patch
+// protocol (genPatch), stop conditions.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -25,6 +26,7 @@
 #include <queue>
 #include <stdexcept>
 #include <string>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -305,6 +307,18 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
   std::vector<uint64_t> row_labels_;
   bool dirty_ = false;
   int build_threads_ = 1;
+  bool allow_replace_ = false;                  // the constructors' allow_replace_deleted
+  bool has_image_ = false;                      // the loaded index keeps its host image (loaded with room)
+  bool marks_changed_ = false;                  // markDelete / unmarkDelete since the load
+  std::unordered_set<uint64_t> collected_;      // labels collected before the build: a repeated one is an update
+  // what every (re)load of this object's index is followed by: whether it can change, and the constructor's replacement flag
+  void after_load() {
+    hs_info info;
+    detail::check(hs_index_info(h_, &info));
+    has_image_ = hs_index_capacity(h_) > info.n;
+    marks_changed_ = false;
+    if (allow_replace_ && has_image_) each_replica([&](hs_index *h) { detail::check(hs_index_set_replace_deleted(h, 1)); });
+  }
   std::string tmp_path_;   // index file of a graph that was built here and never saved by the caller
   void materialize(const std::string &location) {
     if (row_labels_.empty()) throw std::runtime_error("hnswlib_amd: nothing to build (no addPoint calls)");
@@ -314,6 +328,7 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     load(location, HS_KIND_HNSW, space_, max_elements_);
     setEf(ef_keep);
     dirty_ = false;
+    after_load();
     // a later addPoint continues this build: the level generator as the constructor's seed left it after these points
     if (hs_index_capacity(h_) > row_labels_.size())
       each_replica([&](hs_index *h) { detail::check(hs_index_seed_levels(h, seed_, row_labels_.size())); });
@@ -343,29 +358,38 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
   size_t indexSize() const { ensure_built(); return detail::DeviceIndex::indexSize(); }
   explicit HierarchicalNSW(SpaceInterface<float> *s) : space_(s) {}
   HierarchicalNSW(SpaceInterface<float> *s, const std::string &location, bool /*nmslib*/ = false, size_t max_elements = 0,
-                  bool /*allow_replace_deleted*/ = false) : space_(s) {
+                  bool allow_replace_deleted = false) : space_(s), allow_replace_(allow_replace_deleted) {
     loadIndex(location, s, max_elements);
   }
   // hnswalg.h:85-159
   HierarchicalNSW(SpaceInterface<float> *s, size_t max_elements, size_t M = 16, size_t ef_construction = 200,
-                  std::string branching_factor = "16", size_t random_seed = 100, bool /*allow_replace_deleted*/ = false)
-      : space_(s), max_elements_(max_elements), M_(M), efc_(ef_construction), seed_(random_seed), branching_(branching_factor) {
+                  std::string branching_factor = "16", size_t random_seed = 100, bool allow_replace_deleted = false)
+      : space_(s), max_elements_(max_elements), M_(M), efc_(ef_construction), seed_(random_seed), branching_(branching_factor),
+        allow_replace_(allow_replace_deleted) {
     rows_.reserve(max_elements * detail::dim_of(s));
     row_labels_.reserve(max_elements);
   }
   void setBuildThreads(int t) { build_threads_ = t < 1 ? 1 : t; }   // 1 = the reference's serial addPoint loop, byte for byte
   void loadIndex(const std::string &location, SpaceInterface<float> *s, size_t max_elements_i = 0) {
     space_ = s;
-    rows_.clear(); row_labels_.clear(); dirty_ = false;
+    rows_.clear(); row_labels_.clear(); collected_.clear(); dirty_ = false;
     load(location, HS_KIND_HNSW, s, max_elements_i);
+    after_load();
   }
   // addPoint on a resident index -- loaded with room (loadIndex(path, space, max_elements)), or built here and already searched --
   // is incremental (hs_index_add_points): the reference's insertion on the host image, the changed rows written in place on the
   // device.  Before the first search of an index under construction the points are collected as before.
-  void addPoint(const void *datapoint, labeltype label, bool = false) override {
+  // On a resident index the call is the reference's addPoint(data, label, replace_deleted) whole (hs_index_upsert_points): an
+  // existing label is updated, a new one with replace_deleted takes a deleted slot while there is one, anything else is appended.
+  // While points are still being collected, a repeated label or replace_deleted = true first forces the build.
+  void addPoint(const void *datapoint, labeltype label, bool replace_deleted = false) override {
+    if (replace_deleted && !allow_replace_) throw std::runtime_error("Replacement of deleted elements is disabled in constructor");  // hnswalg.h:1027-1030
+    if (dirty_ && (replace_deleted || collected_.count(label))) ensure_built();
     if (resident()) {
       const uint64_t l = label;
-      each_replica([&](hs_index *h) { detail::check(hs_index_add_points(h, (const float *)datapoint, &l, 1, 1)); });
+      const uint8_t flag = replace_deleted ? 1 : 0;
+      each_replica([&](hs_index *h) { detail::check(hs_index_upsert_points(h, (const float *)datapoint, &l, &flag, 1)); });
+      drop_filter_cache();   // a cached functor row is per internal id: an update or a replacement may have changed a slot's label
       return;
     }
     if (!space_ || max_elements_ == 0)
@@ -375,7 +399,36 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     const size_t d = detail::dim_of(space_);
     rows_.insert(rows_.end(), (const float *)datapoint, (const float *)datapoint + d);
     row_labels_.push_back(label);
+    collected_.insert(label);
     dirty_ = true;
+  }
+  // resizeIndex (hnswalg.h:689-717).  A resident index that keeps its host image moves its device arrays (hs_index_resize).  One
+  // that was loaded without room has no host image: its file is loaded again with the new capacity -- unless delete marks changed
+  // since the load, which that file does not hold.
+  void resizeIndex(size_t new_max_elements) {
+    if (!resident()) {
+      if (new_max_elements < row_labels_.size())
+        throw std::runtime_error("Cannot resize, max element is less than the current number of elements");
+      max_elements_ = new_max_elements;
+      return;
+    }
+    if (has_image_) {
+      each_replica([&](hs_index *h) { detail::check(hs_index_resize(h, new_max_elements)); });
+      return;
+    }
+    if (new_max_elements < getCurrentElementCount())
+      throw std::runtime_error("Cannot resize, max element is less than the current number of elements");
+    if (marks_changed_)
+      throw std::runtime_error("hnswlib_amd: resizeIndex of an index loaded without spare capacity reloads its file, which does not hold the "
+                               "delete marks set since the load (load it with max_elements above its size)");
+    const size_t ef_keep = ef_;
+    const std::string file = path_;
+    load(file, HS_KIND_HNSW, space_, new_max_elements);
+    setEf(ef_keep);
+    max_elements_ = new_max_elements;
+    after_load();
+    if (!row_labels_.empty() && has_image_)   // built here: the level generator as the constructor's seed left it
+      each_replica([&](hs_index *h) { detail::check(hs_index_seed_levels(h, seed_, row_labels_.size())); });
   }
   // saveIndex of a resident index that keeps its host image (hs_index_save): marks and added points included
   void saveIndex(const std::string &location) override {
@@ -389,11 +442,13 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     ensure_built();
     const uint64_t l = label;
     each_replica([&](hs_index *h) { detail::check(hs_index_mark_deleted(h, &l, 1, 1)); });
+    marks_changed_ = true;
   }
   void unmarkDelete(labeltype label) {   // hnswalg.h:968-981
     ensure_built();
     const uint64_t l = label;
     each_replica([&](hs_index *h) { detail::check(hs_index_mark_deleted(h, &l, 1, 0)); });
+    marks_changed_ = true;
   }
   size_t getDeletedCount() const { return h_ ? hs_index_deleted_count(h_) : 0; }
   size_t getMaxElements() const { return resident() ? hs_index_capacity(h_) : max_elements_; }

@@ -103,7 +103,7 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
  * and / or narrow row, label, mark -- and the small structure arrays (CSR, upper levels) are rebuilt whole.  A level-0 list that
  * outgrows the tile stride re-tiles everything.  All or nothing, checked before anything changes:
  *   HS_ERR_CAPACITY    "The number of elements exceeds the specified limit" (:1274-1277; also an index loaded without room)
- *   HS_ERR_UNSUPPORTED a label that already exists (updatePoint is not provided); a row the index's narrow row format cannot
+ *   HS_ERR_UNSUPPORTED a label that already exists (this entry adds; hs_index_upsert_points updates); a row the index's narrow row format cannot
  *                      represent (the message names the row of the call and the value); a Slim / SlimQ index
  *   HS_ERR_INVALID     a label that appears twice in the call
  * Levels come from the index's level generator: after a load it is a default-constructed std::default_random_engine, as the
@@ -124,6 +124,44 @@ hs_status hs_index_save(const hs_index *ix, const char *path);
 hs_status hs_index_get_row(hs_index *ix, uint64_t label, float *out);
 size_t hs_index_capacity(const hs_index *ix);        /* getMaxElements: rows the index has room for */
 size_t hs_index_deleted_count(const hs_index *ix);   /* getDeletedCount */
+
+/* ---- upsert, replace_deleted and resizeIndex on a resident vanilla index ---------------------------------------------------------
+ * The same kind of index as above (HS_KIND_HNSW, loaded with max_elements > its element count), the same rules about searches in
+ * flight.  Everything runs on the host image exactly as the reference's serial code (updatePoint hnswalg.h:1067-1157,
+ * repairConnectionsForUpdate :1159-1236, addPoint(.., replace_deleted) :1025-1065, deleted_elements as its std::unordered_set), so
+ * hs_index_save writes the reference's bytes; on the device the rewritten nodes -- fp32 row and / or narrow row, label, mark,
+ * level-0 tile row -- and the level-0 neighbours the update touched leave in one staging copy and one kernel, as
+ * hs_index_add_points' records do.  updateNeighborProbability is 1.0.
+ *
+ * hs_index_set_replace_deleted: the constructor's allow_replace_deleted_.  Turning it on fills deleted_elements from the current
+ * marks in increasing id, as loadIndex does (:882-888); from then on hs_index_mark_deleted keeps it.  HS_ERR_INVALID on an index
+ * without a host image, HS_ERR_UNSUPPORTED on Slim / SlimQ.
+ *
+ * hs_index_upsert_points: `count` points serially, in call order, each exactly addPoint(row, label, replace_flags[i]);
+ * replace_flags NULL = all 0.  An existing label is updated (and un-marked first when replacement is not allowed); a new label with
+ * its flag set and a vacancy takes the slot `*deleted_elements.begin()` -- the slot's old label leaves the index, the mark goes;
+ * otherwise the point is appended.  A label may occur more than once in a call: later occurrences are updates.  All or nothing -- a
+ * pre-pass plays labels, vacancies and capacity and refuses before anything changes:
+ *   HS_ERR_INVALID     "Replacement of deleted elements is disabled in constructor" (:1027-1030)
+ *   HS_ERR_INVALID     "Can't use addPoint to update deleted elements if replacement of deleted elements is enabled." (:1257-1263)
+ *   HS_ERR_CAPACITY    "The number of elements exceeds the specified limit" (:1274-1277; also an index loaded without room)
+ *   HS_ERR_UNSUPPORTED a row the index's narrow row format cannot represent (named as hs_index_add_points names it); Slim / SlimQ
+ * No `threads`: the order is the reference's serial one; bulk appends of new labels stay with hs_index_add_points.
+ * hs_info.has_deleted follows the number of marks after every call: a replacement that removes the last mark returns the index
+ * to the flat kernel.  Filter sets are per internal id: updates and replacements leave n unchanged, so an existing set stays valid
+ * and a reused slot KEEPS ITS BIT -- the caller rewrites it (hs_filter_set_write) if the new label's admission differs; after
+ * appends a set is refused, as after hs_index_add_points.
+ *
+ * hs_index_resize: resizeIndex (:689-717).  HS_ERR_INVALID "Cannot resize, max element is less than the current number of
+ * elements"; HS_ERR_INVALID on an index without a host image.  Growing allocates the per-node device arrays (fp32 rows where
+ * resident, narrow rows where present, level-0 tiles, labels, marks) at the new capacity and fills them by device-to-device copies
+ * -- no row crosses the host link -- then frees the old ones; HS_ERR_NOMEM, index as it was, when the new arrays cannot be
+ * allocated.  Shrinking to a value >= the element count lowers only the reported capacity (the device arrays stay).  Search
+ * outputs do not change; filter sets stay valid; hs_index_capacity and hs_info.index_size follow, hs_info.device_bytes changes by
+ * the narrow copy's capacity term only (rows are counted per element, the narrow copy per row of capacity). */
+hs_status hs_index_set_replace_deleted(hs_index *ix, int on);
+hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t *labels, const uint8_t *replace_flags, size_t count);
+hs_status hs_index_resize(hs_index *ix, size_t new_max_elements);
 
 /* ---- narrow rows (no counterpart in the reference) -------------------------------------------------------------------
  * Besides the resident fp32 rows an index can hold a u8 or fp16 copy of them, and the flat kernel -- the default kernel of every
@@ -467,6 +505,15 @@ hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_
  * hs_index_add_points (capacity, existing or repeated label), before anything is added; out_path is then not written. */
 hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows,
                          const uint64_t *labels, size_t count, size_t seed, size_t drawn, int threads, const char *out_path);
+/* Host only, no device: loadIndex(in_path, space, max_elements) with the constructor's allow_replace_deleted, then `n_ops`
+ * operations in order, then saveIndex(out_path).  An operation is four 64-bit words {kind, label or new capacity, replace flag,
+ * row index into `rows`}: HS_OP_ADD = addPoint(rows + row*dim, label, flag) (update, replacement or append as the reference decides),
+ * HS_OP_MARK / HS_OP_UNMARK = markDelete / unmarkDelete(label), HS_OP_RESIZE = resizeIndex(new capacity).  The reference's
+ * refusals come back with the statuses of hs_index_upsert_points / hs_index_mark_deleted / hs_index_resize; out_path is then
+ * not written. */
+enum { HS_OP_ADD = 0, HS_OP_MARK = 1, HS_OP_UNMARK = 2, HS_OP_RESIZE = 3 };
+hs_status hs_hnsw_replay(const char *in_path, int metric, size_t dim, size_t max_elements, int allow_replace_deleted,
+                         const uint64_t *ops, size_t n_ops, const float *rows, const char *out_path);
 /* HierarchicalNSWSlim::convertFromHNSW + saveIndex: hnswalg_slim.h:867-1108, 717-751. */
 hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int threshold_level,
                           float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
