@@ -181,6 +181,19 @@ def lib():
     L.hs_convert_slim_gpu.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ci, ctypes.c_char_p,
                                       ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.hs_convert_slimq.argtypes = [ctypes.c_char_p, ci, sz, vp, sz, vp, ctypes.c_uint64, ci, ctypes.c_char_p]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_slim_convert_diff"):   # (a baseline build in an A/B run may predate these)
+        psz = ctypes.POINTER(sz)
+        L.hs_slim_convert_diff.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.POINTER(vp), ctypes.POINTER(ci),
+                                           ctypes.POINTER(ctypes.c_double)]
+        L.hs_slim_diff_info.argtypes = [vp, psz, psz, psz, psz]
+        L.hs_slim_diff_ids.argtypes = [vp, vp, vp]
+        L.hs_slim_diff_stream.argtypes = [vp, vp, vp, sz, psz]
+        L.hs_slim_diff_next.argtypes = [vp, vp, sz, ci, vp, sz, psz, psz, psz, ctypes.POINTER(ci)]
+        L.hs_slim_diff_free.argtypes = [vp]
+        L.hs_slim_diff_free.restype = None
+        L.hs_slim_index_save.argtypes = [vp, ctypes.c_char_p]
+        L.hs_slim_convert_diff_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci,
+                                                 ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.hs_rabitq_default_tconst.restype = ctypes.c_double
     L.hs_rabitq_default_tconst.argtypes = [sz, ctypes.c_uint64]
     L.hs_slimq_set_dataset.argtypes = [vp, vp, sz, sz]
@@ -281,6 +294,78 @@ def convert_slim_gpu(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_le
                                      top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, device, threads, out_path.encode(),
                                      ctypes.byref(used), ctypes.byref(ms)))
     return bool(used.value), ms.value
+
+
+class SlimDiff:
+    """What one convertFromHNSWWithDiff call found (hs_slim_diff_*): the changed old nodes and the new nodes, the whole stream of
+    the std::ostream overload, and genPatch with its cursors.  `index`: the Slim Index the diff was made on, None for a diff of
+    slim_convert_diff_files (which owns its Slim image)."""
+
+    def __init__(self, handle, index, used_gpu=False, kernel_ms=0.0):
+        self._h, self._ix, self.used_gpu, self.kernel_ms = handle, index, used_gpu, kernel_ms
+
+    def _slim(self):
+        return self._ix._h if self._ix is not None else None
+
+    def close(self):
+        if self._h:
+            lib().hs_slim_diff_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        v = [ctypes.c_size_t(0) for _ in range(4)]
+        _check(lib().hs_slim_diff_info(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(count=v[0].value, n_old=v[1].value, n_new=v[2].value, n_reprune=v[3].value)
+
+    def ids(self):
+        """(changed old ids, new ids), both ascending."""
+        i = self.info()
+        old, new = np.empty(i["n_old"], np.uint32), np.empty(i["n_new"], np.uint32)
+        _check(lib().hs_slim_diff_ids(self._h, old.ctypes.data, new.ctypes.data))
+        return old, new
+
+    def stream(self):
+        """The whole stream (new records without rows): what Index.patch(.., to_add=False) takes."""
+        n = ctypes.c_size_t(0)
+        rc = lib().hs_slim_diff_stream(self._h, self._slim(), None, 0, ctypes.byref(n))
+        if rc not in (HS_OK, HS_ERR_CAPACITY):
+            _check(rc)
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        _check(lib().hs_slim_diff_stream(self._h, self._slim(), buf, n.value, ctypes.byref(n)))
+        return buf.raw[:n.value]
+
+    def next(self, limit, to_add=False, cap=None):
+        """One genPatch call -> (bytes for Index.patch(.., to_add), old_written, new_written, finished).  cap: the buffer size to
+        offer (default: ask first); too small raises HsError(HS_ERR_CAPACITY) and the cursors stay."""
+        n, ow, nw, fin = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
+        if cap is None:
+            rc = lib().hs_slim_diff_next(self._h, self._slim(), limit, 1 if to_add else 0, None, 0, ctypes.byref(n), None, None, None)
+            if rc not in (HS_OK, HS_ERR_CAPACITY):
+                _check(rc)
+            cap = n.value
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        _check(lib().hs_slim_diff_next(self._h, self._slim(), limit, 1 if to_add else 0, buf, cap, ctypes.byref(n), ctypes.byref(ow),
+                                       ctypes.byref(nw), ctypes.byref(fin)))
+        return buf.raw[:n.value], ow.value, nw.value, bool(fin.value)
+
+
+def slim_convert_diff_files(old_slim_path, hnsw_path, out_slim_path, dim, metric=HS_METRIC_L2, threshold_level=0, top_degree_percent0=0.02,
+                            top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16, low_degree_m=4, threads=1,
+                            out_stream_path=None):
+    """hs_slim_convert_diff_files (host only): convertFromHNSWWithDiff of the Slim file `old_slim_path` (None: an empty Slim index)
+    from the vanilla file `hnsw_path`; writes the new Slim file (and the whole stream when asked) and returns the SlimDiff."""
+    h = ctypes.c_void_p()
+    _check(lib().hs_slim_convert_diff_files(None if old_slim_path is None else old_slim_path.encode(), hnsw_path.encode(), metric, dim,
+                                            threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0,
+                                            top_degree_M, low_degree_m, threads, out_slim_path.encode(),
+                                            None if out_stream_path is None else out_stream_path.encode(), ctypes.byref(h)))
+    return SlimDiff(h, None)
 
 
 def rows_representable(rows, fmt):
@@ -664,6 +749,19 @@ class Index:
         """patchFromStream: apply a genPatch stream to this device-resident Slim index (loaded with max_elements > count)."""
         b = bytes(stream_bytes)
         _check(lib().hs_index_patch(self._h, b, len(b), 1 if to_add else 0))
+
+    def convert_diff(self, hnsw, top_degree_percent0=0.02, top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16,
+                     low_degree_m=4, threads=8):
+        """hs_slim_convert_diff: re-derive this resident Slim index from the resident vanilla Index `hnsw` (both loaded with
+        max_elements > count) and return the SlimDiff (its .used_gpu / .kernel_ms say where the list passes ran)."""
+        h, used, ms = ctypes.c_void_p(), ctypes.c_int(0), ctypes.c_double(0.0)
+        _check(lib().hs_slim_convert_diff(self._h, hnsw._h, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0,
+                                          top_degree_M, low_degree_m, threads, ctypes.byref(h), ctypes.byref(used), ctypes.byref(ms)))
+        return SlimDiff(h, self, bool(used.value), ms.value)
+
+    def save_slim(self, path):
+        """hs_slim_index_save: saveIndex of this Slim index's host image (an index loaded with max_elements > its count)."""
+        _check(lib().hs_slim_index_save(self._h, path.encode()))
 
     # -- live updates (HS_KIND_HNSW) ----------------------------------------------------------------
     def add_points(self, rows, labels, threads=1):

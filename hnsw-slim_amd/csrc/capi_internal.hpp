@@ -68,6 +68,11 @@ struct hs_index {
   // patching (hs_index_patch): a Slim index loaded with max_elements > count keeps its host image and has row capacity
   std::unique_ptr<SlimGraph> host_slim;
   size_t cap_rows = 0;
+  // hs_slim_convert_diff: the Slim index's label_lookup_ (hnswalg_slim.h:61), built from the host image by the first call
+  // (buildLabelLookup :216-220) and merged into by every call (:1121)
+  SlimGraph::Lookup slim_lookup;
+  bool slim_lookup_built = false;
+  uint64_t slim_gen = 0;   // counts the calls that re-derived the host image: a diff object belongs to one of them
   // live updates (capi_update.cpp): a vanilla index loaded with max_elements > count keeps its host image too (addPoint continues
   // on it, hs_index_save writes it); the label -> internal id map (the reference's label_lookup_) and the number of delete marks
   // (num_deleted_) are built from host_labels / host_deleted the first time a call needs them

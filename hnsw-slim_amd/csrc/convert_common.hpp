@@ -1,0 +1,98 @@
+// convert_common.hpp -- what the two device conversions share (convert_gpu.hip: convertFromHNSW, convert_diff.hip:
+// convertFromHNSWWithDiff): buffer sizes, the distances of one list, the keep loop of the pruning heuristics, the task index,
+// and the reverse-edge kernels' launchers (the kernels live in convert_gpu.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "dist_recipe.hpp"
+#include "heap_emul.hpp"
+#include "wave_util.hpp"
+
+namespace hs {
+
+static constexpr uint32_t kCvMaxList = 64;     // a source list (level-0 list of the vanilla graph) holds at most this many ids
+static constexpr uint32_t kCvMaxKeep = 32;     // pruned lists hold at most this many ids (top_degree_M0, maxM0 <= 32 .. see host check)
+static constexpr uint32_t kCvUnionCap = 2048;  // own list + reverse edges of one (node, level), in LDS
+
+// distances query (LDS, dim floats) -> rows nid[0..cnt) (LDS) into nd[0..cnt) (LDS)
+template <int METRIC>
+__device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
+  if ((dim & 15u) == 0) {
+    const int sub = lane & 3, grp = lane >> 2;
+    const uint32_t steps = dim >> 4;
+    const float4 *qq = reinterpret_cast<const float4 *>(qv) + sub;
+    for (uint32_t base = 0; base < cnt; base += 16) {
+      const uint32_t j = base + grp;
+      const bool act = j < cnt;
+      const uint32_t id = nid[act ? j : base];
+      const float4 *row = reinterpret_cast<const float4 *>(vec + (size_t)id * dim) + sub;
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      for (uint32_t r0 = 0; r0 < steps; r0 += 8) {
+        const uint32_t nb = min(8u, steps - r0);
+        float4 buf[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++)
+          if (i < nb) buf[i] = row[(r0 + i) * 4];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++)
+          if (i < nb) step4<METRIC>(acc, qq[(r0 + i) * 4], buf[i]);
+      }
+      bool owner;
+      const float r = lane4_reduce<METRIC>(acc, sub, owner);
+      if (act && owner) nd[j] = r;
+    }
+  } else {
+    for (uint32_t base = 0; base < cnt; base += 64) {
+      const uint32_t j = base + lane;
+      if (j < cnt) {
+        const float *row = vec + (size_t)nid[j] * dim;
+        nd[j] = METRIC == METRIC_L2 ? l2_general(qv, row, dim) : ip_general(qv, row, dim);
+      }
+    }
+  }
+}
+
+// PruneByHeuristic (hnswalg_slim.h:836-865) over arr[0..sz) sorted ascending by distance: a candidate is kept unless a kept
+// neighbour is closer to it than the node itself.  Sequential in the candidates, parallel over the kept set.  This is also the
+// keep loop of getNeighborsByHeuristic2 (hnswalg.h:495-517) once arr[] is in ITS candidate order (diff_prune.hpp).
+template <int METRIC>
+__device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
+                                             uint32_t *kept, float *kd, int lane, float *keptd = nullptr) {
+  uint32_t kc = 0;
+  for (uint32_t t = 0; t < sz && kc < mlim; t++) {
+    const float cd = unif(arr[t].d);
+    const uint32_t cid = uni(arr[t].id);
+    bool good = true;
+    if (kc > 0) {
+      for (uint32_t i = lane; i < dim; i += 64) qc[i] = vec[(size_t)cid * dim + i];
+      wave_sync();
+      cv_dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
+      wave_sync();
+      bool bad = false;
+      for (uint32_t i = lane; i < kc; i += 64) bad = bad || kd[i] < cd;
+      good = hs_ballot(bad) == 0;
+    }
+    if (good) {
+      if (lane == 0) {
+        kept[kc] = cid;
+        if (keptd) keptd[kc] = cd;   // (convertFromHNSWWithDiff's re-prune: the kept distances, in kept order)
+      }
+      kc++;
+    }
+    wave_sync();
+  }
+  return kc;
+}
+
+// (node u, level l) -> task index: level 0 = u, level l >= 1 = n + upb[u] + l - 1
+__device__ __forceinline__ uint32_t cv_task_of(uint32_t u, uint32_t l, uint32_t n, const uint32_t *upb) { return l == 0 ? u : n + upb[u] + l - 1; }
+
+// reverse edges (hnswalg_slim.h:988-998 / 1234-1241), counted then filled: nn / cnt = the pruned lists (kCvMaxKeep ids per task)
+hipError_t launch_cv_rev_count(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_level, const uint32_t *upb, uint32_t n, uint32_t ntasks,
+                               uint32_t *rcnt);
+hipError_t launch_cv_rev_fill(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_node, const uint32_t *t_level, const uint32_t *upb, uint32_t n,
+                              uint32_t ntasks, const uint32_t *roff, uint32_t *rcur, uint32_t *rev);
+
+}  // namespace hs

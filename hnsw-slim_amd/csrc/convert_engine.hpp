@@ -26,4 +26,32 @@ struct ConvertInput {
 hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,
                              double *kernel_ms);
 
+// What the diff kernel of convert_diff.hip compares the new lists against and what it hands back.  In: the resident Slim
+// index's own adjacency (level-0 tiles + upper-level CSR), labels and fp32 rows as they are BEFORE the call, the resident HNSW
+// index's labels, the per-node levels of the HNSW index.  Out, each ascending (compacted on the device): the changed old nodes and
+// the new nodes by the rules of hnswalg_slim.h:1360-1378 short of the label lookup (the caller applies it to the few nodes it can
+// concern), the nodes whose image changed in any way, and those of them whose row or label differs; flags (one byte per node:
+// bit 0 lists differ, bit 1 has neighbours, bit 2 row or label differs) only when want_flags.
+struct DiffDev {
+  const uint32_t *s_tile0 = nullptr, *s_up_base = nullptr, *s_up_ptr = nullptr, *s_cols = nullptr;
+  const uint64_t *s_labels = nullptr, *h_labels = nullptr;
+  const float *s_vec = nullptr;
+  uint32_t s_stride = 0, prev_count = 0, n_up = 0;   // n_up: entries of s_up_ptr
+  int32_t threshold_level = 0;
+  std::vector<uint32_t> levels;   // n
+  bool want_flags = false;
+  std::vector<uint32_t> old_ids, new_ids, dirty, stale;
+  std::vector<uint8_t> flags;
+};
+
+// The list passes of convertFromHNSWWithDiff (hnswalg_slim.h:1189-1303; convert_diff.hip) with the rows read from `d_vec`, n x dim
+// fp32 already on `device` (in.vec is not read): both prunes are hnsw->getNeighborsByHeuristic2 (hnswalg.h:481-523) -- candidates by
+// (distance ascending, id descending), lists below their budget untouched -- and a re-pruned list is the pop order of the heap
+// the heuristic returns.  fin / fin_cnt / needs_host as gpu_convert_lists; n_reprune: the lists that were re-pruned.
+// diff (nullable): then the per-node diff kernel and the compaction run on the final lists while they are still on the device.
+// kernel_ms: from the first kernel to the last -- the list kernels and, with `diff`, the diff and compaction kernels -- which
+// includes the two host round trips between them (the reverse-edge prefix sum; the upload of the levels and the scratch of the diff).
+hipError_t gpu_convert_diff_lists(const ConvertInput &in, const float *d_vec, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt,
+                                  bool &needs_host, uint32_t &n_reprune, double *kernel_ms, DiffDev *diff = nullptr);
+
 }  // namespace hs

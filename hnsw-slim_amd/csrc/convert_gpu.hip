@@ -14,82 +14,13 @@
 #include <algorithm>
 #include <vector>
 
+#include "convert_common.hpp"
 #include "convert_engine.hpp"
 #include "dist_recipe.hpp"
 #include "heap_emul.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
-
-static constexpr uint32_t kCvMaxList = 64;     // a source list (level-0 list of the vanilla graph) holds at most this many ids
-static constexpr uint32_t kCvMaxKeep = 32;     // pruned lists hold at most this many ids (top_degree_M0, maxM0 <= 32 .. see host check)
-static constexpr uint32_t kCvUnionCap = 2048;  // own list + reverse edges of one (node, level), in LDS
-
-// distances query (LDS, dim floats) -> rows nid[0..cnt) (LDS) into nd[0..cnt) (LDS)
-template <int METRIC>
-__device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
-  if ((dim & 15u) == 0) {
-    const int sub = lane & 3, grp = lane >> 2;
-    const uint32_t steps = dim >> 4;
-    const float4 *qq = reinterpret_cast<const float4 *>(qv) + sub;
-    for (uint32_t base = 0; base < cnt; base += 16) {
-      const uint32_t j = base + grp;
-      const bool act = j < cnt;
-      const uint32_t id = nid[act ? j : base];
-      const float4 *row = reinterpret_cast<const float4 *>(vec + (size_t)id * dim) + sub;
-      float acc[4] = {0.f, 0.f, 0.f, 0.f};
-      for (uint32_t r0 = 0; r0 < steps; r0 += 8) {
-        const uint32_t nb = min(8u, steps - r0);
-        float4 buf[8];
-#pragma unroll
-        for (uint32_t i = 0; i < 8; i++)
-          if (i < nb) buf[i] = row[(r0 + i) * 4];
-#pragma unroll
-        for (uint32_t i = 0; i < 8; i++)
-          if (i < nb) step4<METRIC>(acc, qq[(r0 + i) * 4], buf[i]);
-      }
-      bool owner;
-      const float r = lane4_reduce<METRIC>(acc, sub, owner);
-      if (act && owner) nd[j] = r;
-    }
-  } else {
-    for (uint32_t base = 0; base < cnt; base += 64) {
-      const uint32_t j = base + lane;
-      if (j < cnt) {
-        const float *row = vec + (size_t)nid[j] * dim;
-        nd[j] = METRIC == METRIC_L2 ? l2_general(qv, row, dim) : ip_general(qv, row, dim);
-      }
-    }
-  }
-}
-
-// PruneByHeuristic (hnswalg_slim.h:836-865) over arr[0..sz) sorted ascending by distance: a candidate is kept unless a kept
-// neighbour is closer to it than the node itself.  Sequential in the candidates, parallel over the kept set.
-template <int METRIC>
-__device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
-                                             uint32_t *kept, float *kd, int lane) {
-  uint32_t kc = 0;
-  for (uint32_t t = 0; t < sz && kc < mlim; t++) {
-    const float cd = unif(arr[t].d);
-    const uint32_t cid = uni(arr[t].id);
-    bool good = true;
-    if (kc > 0) {
-      for (uint32_t i = lane; i < dim; i += 64) qc[i] = vec[(size_t)cid * dim + i];
-      wave_sync();
-      cv_dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
-      wave_sync();
-      bool bad = false;
-      for (uint32_t i = lane; i < kc; i += 64) bad = bad || kd[i] < cd;
-      good = hs_ballot(bad) == 0;
-    }
-    if (good) {
-      if (lane == 0) kept[kc] = cid;
-      kc++;
-    }
-    wave_sync();
-  }
-  return kc;
-}
 
 // by-distance std::sort of (nd[j], nid[j]), j < sz, into arr[]: rank sort when libstdc++'s result is the stable order (sz <= 16:
 // pure insertion sort) or no two keys are equal; otherwise the step-for-step emulation on one lane
@@ -147,9 +78,6 @@ __global__ void __launch_bounds__(64) cv_prune_kernel(const float *vec, uint32_t
   }
 }
 
-// (node u, level l) -> task index: level 0 = u, level l >= 1 = n + upb[u] + l - 1
-__device__ __forceinline__ uint32_t cv_task_of(uint32_t u, uint32_t l, uint32_t n, const uint32_t *upb) { return l == 0 ? u : n + upb[u] + l - 1; }
-
 // ---- phase 2 (hnswalg_slim.h:988-998): reverse edges, counted then filled ---------------------------------------------------
 __global__ void cv_rev_count_kernel(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_level, const uint32_t *upb, uint32_t n,
                                     uint32_t ntasks, uint32_t *rcnt) {
@@ -165,6 +93,18 @@ __global__ void cv_rev_fill_kernel(const uint32_t *nn, const uint32_t *cnt, cons
   if (t >= ntasks || i >= cnt[t]) return;
   const uint32_t tu = cv_task_of(nn[(size_t)t * kCvMaxKeep + i], t_level[t], n, upb);
   rev[roff[tu] + atomicAdd(&rcur[tu], 1u)] = t_node[t];
+}
+
+hipError_t launch_cv_rev_count(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_level, const uint32_t *upb, uint32_t n, uint32_t ntasks,
+                               uint32_t *rcnt) {
+  hipLaunchKernelGGL(cv_rev_count_kernel, dim3((uint32_t)(((size_t)ntasks * kCvMaxKeep + 255) / 256)), dim3(256), 0, nullptr, nn, cnt, t_level, upb, n, ntasks, rcnt);
+  return hipGetLastError();
+}
+hipError_t launch_cv_rev_fill(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_node, const uint32_t *t_level, const uint32_t *upb, uint32_t n,
+                              uint32_t ntasks, const uint32_t *roff, uint32_t *rcur, uint32_t *rev) {
+  hipLaunchKernelGGL(cv_rev_fill_kernel, dim3((uint32_t)(((size_t)ntasks * kCvMaxKeep + 255) / 256)), dim3(256), 0, nullptr, nn, cnt, t_node, t_level, upb, n, ntasks,
+                     roff, rcur, rev);
+  return hipGetLastError();
 }
 
 // ---- phase 3 (hnswalg_slim.h:999-1012, 1038-1062): own list + reverse edges, sorted by id, duplicates removed; a list over

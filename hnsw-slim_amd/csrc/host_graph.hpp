@@ -16,10 +16,12 @@
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <queue>
 #include <random>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -1078,20 +1080,176 @@ struct SlimGraph {
     });
   }
 
-#ifdef HS_HAVE_GPU_CONVERT
-  // The same conversion with the list-level work on the GPU (convert_gpu.hip).  Returns false when the shape is outside the
-  // device path (lists longer than 64 / capacities above 32 ids, or a reverse-edge list that outgrew the on-chip buffers):
-  // the caller then runs convert().  kernel_ms: device time of the kernels.
-  bool convert_gpu(const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
-    if (g.maxM0 > 32 || g.maxM > 32 || p.top_M0 > 32 || p.low_m0 > 32 || p.top_M > 32 || p.low_m > 32) return false;
-    take_header(g, p);
-    const size_t n = count;
+  // ---- convertFromHNSWWithDiff (hnswalg_slim.h:1110-1424, 1478-1751) and genPatch (:1427-1476) --------------------------------
+  // What one call leaves behind: the two changed lists in ascending id (the reference fills them from an OpenMP loop, in any
+  // order), the nodes whose image changed in any way (what a device copy has to rewrite), genPatch's two cursors.
+  struct Diff {
+    size_t count = 0;
+    std::vector<uint32_t> old_ids, new_ids;
+    std::vector<uint32_t> dirty;      // blob, row or label differs from before the call, or the node is beyond the previous count
+    std::vector<uint32_t> stale;      // the part of `dirty` whose row or label differs (or is new): a device copy rewrites the row too
+    size_t n_reprune = 0;             // lists that went through the re-prune (:1279-1303)
+    size_t ind_old = 0, ind_new = 0;  // ind_old_ / ind_new_ (:78-79)
+  };
+  // The final per-level lists of every node, before the hierarchical filter: first prune with getNeighborsByHeuristic2
+  // (:1189-1232; only the kept set matters, the lists are sorted by id at :1269-1273), reverse edges (:1234-1241), union sorted
+  // by id and made unique, and the re-prune of a union above its level's capacity (:1279-1303), whose list is the pop order of
+  // the heap the heuristic returns -- every kept entry, where the reference pops `limit` times whatever was kept.
+  static void diff_lists(const VanillaGraph &g, const SlimParams &p, size_t maxM0_, size_t maxM_, int threads,
+                         std::vector<std::vector<std::vector<uint32_t>>> &nn, size_t &n_reprune) {
+    const size_t n = g.count;
     const std::vector<size_t> thr = hub_thresholds(g, p);
-    ConvertInput in;
-    in.vec = nullptr; in.n = (uint32_t)n; in.dim = (uint32_t)dim; in.metric = (int)metric;
-    std::vector<float> rows(n * dim);
-    for (size_t i = 0; i < n; i++) memcpy(&rows[i * dim], g.vec(i), 4 * dim);
-    in.vec = rows.data();
+    nn.assign(n, {});
+    std::vector<std::vector<std::vector<uint32_t>>> rev(n);
+    auto par = [&](auto fn) {
+      int T = std::max(1, threads);
+      std::atomic<size_t> next(0);
+      std::vector<std::thread> pool;
+      for (int t = 0; t < T; t++)
+        pool.emplace_back([&]() { for (size_t v; (v = next.fetch_add(64)) < n;) for (size_t u = v; u < std::min(n, v + 64); u++) fn(u); });
+      for (auto &th : pool) th.join();
+    };
+    par([&](size_t v) {
+      const int L = g.levels[v];
+      nn[v].resize(L + 1); rev[v].resize(L + 1);
+      for (int l = L; l >= 0; l--) {
+        const uint32_t *ll = g.list_at(v, l);
+        const size_t size = VanillaGraph::cnt_of(ll);
+        const size_t M0 = l == 0 ? (size > thr[l] ? p.top_M0 : p.low_m0) : (size > thr[l] ? p.top_M : p.low_m);
+        MaxQ heap;
+        for (size_t j = 0; j < size; j++) heap.emplace(g.dist(g.vec(v), g.vec(ll[1 + j])), ll[1 + j]);
+        g.heuristic(heap, M0);
+        while (!heap.empty()) { nn[v][l].push_back(heap.top().second); heap.pop(); }
+      }
+    });
+    for (size_t v = 0; v < n; v++)
+      for (int l = 0; l <= g.levels[v]; l++)
+        for (uint32_t u : nn[v][l]) rev[u][l].push_back(v);
+    std::atomic<size_t> reprunes(0);
+    par([&](size_t i) {
+      for (int l = 0; l <= g.levels[i]; l++) {
+        auto &a = nn[i][l];
+        a.insert(a.end(), rev[i][l].begin(), rev[i][l].end());
+        std::sort(a.begin(), a.end());
+        a.erase(std::unique(a.begin(), a.end()), a.end());
+        const size_t limit = l == 0 ? maxM0_ : maxM_;
+        if (a.size() <= limit) continue;
+        MaxQ heap;
+        for (uint32_t u : a) heap.emplace(g.dist(g.vec(i), g.vec(u)), u);
+        g.heuristic(heap, limit);
+        a.clear();
+        while (!heap.empty()) { a.push_back(heap.top().second); heap.pop(); }
+        reprunes++;
+      }
+    });
+    n_reprune = reprunes;
+  }
+  // The head of the call (:1113-1135): counts and entry from the HNSW index, label_lookup_.merge (keys the Slim index already
+  // holds keep their id), room for the new elements -- zero, where the reference's realloc leaves them undefined.
+  void diff_begin(const VanillaGraph &g, std::unordered_map<uint64_t, uint32_t> &lookup) {
+    count = g.count;
+    has_deleted = g.num_deleted() > 0;
+    maxlevel = g.maxlevel; enterpoint = g.enterpoint;
+    for (size_t i = 0; i < g.count; i++) lookup.emplace(g.label((uint32_t)i), (uint32_t)i);
+    elements.resize(count * size_per_el, 0);
+    blobs.resize(count);
+  }
+  // Elements, blobs and the classification (:1243-1379) from the final lists `list_of(v, l, cnt)`.
+  template <class GetList>
+  void diff_assemble(const VanillaGraph &g, size_t prev_count, std::unordered_map<uint64_t, uint32_t> &lookup, int threads, GetList list_of,
+                     Diff &out) {
+    const size_t n = count;
+    std::vector<uint8_t> cls(n, 0);   // bit 0: old-changed, bit 1: new, bit 2: dirty, bit 3: stale
+    int T = std::max(1, threads);
+    std::atomic<size_t> next(0);
+    std::vector<std::thread> pool;
+    for (int t = 0; t < T; t++)
+      pool.emplace_back([&]() {
+        for (size_t v0; (v0 = next.fetch_add(256)) < n;)
+          for (size_t i = v0; i < std::min(n, v0 + 256); i++) {
+            const char *e = el((uint32_t)i);
+            const uint64_t lab = g.label((uint32_t)i);
+            const bool stale = i >= prev_count || label((uint32_t)i) != lab || memcmp(e + 24, g.vec((uint32_t)i), 4 * dim) != 0;
+            std::vector<char> prev = std::move(blobs[i]);
+            blobs[i].clear();
+            assemble_node(g, i, list_of);
+            uint8_t c = stale ? 12 : prev != blobs[i] ? 4 : 0;
+            if (total((uint32_t)i) != 0) {   // (a node without neighbours leaves at the `continue` of :1340-1343)
+              const bool changed = prev.empty() || prev != blobs[i];
+              if (lookup.find(lab)->second != i) c |= 2;
+              else if (changed) c |= i >= prev_count ? 2 : 1;
+            }
+            cls[i] = c;
+          }
+      });
+    for (auto &th : pool) th.join();
+    out.count = n;
+    for (size_t i = 0; i < n; i++) {
+      if (cls[i] & 1) out.old_ids.push_back((uint32_t)i);
+      if (cls[i] & 2) out.new_ids.push_back((uint32_t)i);
+      if (cls[i] & 4) out.dirty.push_back((uint32_t)i);
+      if (cls[i] & 8) out.stale.push_back((uint32_t)i);
+    }
+  }
+  // `lookup` is the Slim index's label_lookup_ (buildLabelLookup :216-220 and what earlier calls merged into it).  The Slim
+  // index keeps its own threshold_level, maxM and maxM0; an empty one takes the capacities of the HNSW index.
+  void convert_diff(const VanillaGraph &g, const SlimParams &p, int threads, std::unordered_map<uint64_t, uint32_t> &lookup, Diff &out) {
+    const size_t prev_count = count;
+    std::vector<std::vector<std::vector<uint32_t>>> nn;
+    diff_lists(g, p, maxM0, maxM, threads, nn, out.n_reprune);
+    diff_begin(g, lookup);
+    diff_assemble(g, prev_count, lookup, threads, [&](size_t v, int l, size_t &cnt) { cnt = nn[v][l].size(); return nn[v][l].data(); }, out);
+  }
+  // One record of the stream (:1390-1402 old, :1406-1422 new; genPatch :1433-1466): id, the element's first 8 (old) or 16 (new)
+  // bytes, the blob's size and the blob, and the row of a new node when `with_row`.
+  void diff_record(std::string &o, uint32_t v, bool is_new, bool with_row) const {
+    o.append((const char *)&v, 4);
+    o.append(el(v), is_new ? 16 : 8);
+    const uint32_t sz = 2 * (uint32_t)level(v) + 4 * total(v);
+    o.append((const char *)&sz, 4);
+    if (sz) o.append(blobs[v].data(), blobs[v].size());
+    if (is_new && with_row) o.append(el(v) + 24, 4 * dim);
+  }
+  size_t diff_record_size(uint32_t v, bool is_new, bool with_row) const {
+    return 4 + (is_new ? 16 : 8) + 4 + (2 * (size_t)level(v) + 4 * (size_t)total(v)) + (is_new && with_row ? 4 * dim : 0);
+  }
+  std::string diff_stream(const Diff &d) const {   // the std::ostream overload's whole output (:1384-1422)
+    std::string o;
+    const uint64_t h[3] = {d.count, d.old_ids.size(), d.new_ids.size()};
+    o.append((const char *)h, 24);
+    for (uint32_t v : d.old_ids) diff_record(o, v, false, false);
+    for (uint32_t v : d.new_ids) diff_record(o, v, true, false);
+    return o;
+  }
+  // genPatch (:1427-1476) from cursors (io, in): the record that reaches `limit` is written and its cursor is NOT advanced (the
+  // `return` skips the loop increment), so the next call sends that node again; `written` counts a new record's row whether or
+  // not `to_add` writes it (:1468-1469).  Returns `finished`.
+  uint32_t gen_patch(const Diff &d, size_t &io, size_t &in, std::string &o, size_t &old_written, size_t &new_written, size_t limit,
+                     bool to_add) const {
+    size_t written = 0;
+    for (; io < d.old_ids.size(); io++) {
+      old_written++;
+      const uint32_t v = d.old_ids[io];
+      diff_record(o, v, false, false);
+      written += 2 * (size_t)level(v) + 4 * (size_t)total(v) + 4 + 8 + 4;
+      if (written >= limit) return 0;
+    }
+    for (; in < d.new_ids.size(); in++) {
+      new_written++;
+      const uint32_t v = d.new_ids[in];
+      diff_record(o, v, true, to_add);
+      written += 2 * (size_t)level(v) + 4 * (size_t)total(v) + 4 + 16 + 4 + 4 * dim;
+      if (written >= limit) return 0;
+    }
+    return 1;
+  }
+
+#ifdef HS_HAVE_GPU_CONVERT
+  // The task lists of the device conversions (convert_engine.hpp), without the rows.  False: a shape outside the device path.
+  static bool make_convert_input(const VanillaGraph &g, const SlimParams &p, const std::vector<size_t> &thr, size_t maxM0, size_t maxM,
+                                 ConvertInput &in) {
+    const size_t n = g.count;
+    in.vec = nullptr; in.n = (uint32_t)n; in.dim = (uint32_t)g.dim; in.metric = (int)g.metric;
     in.upb.assign(n, 0);
     size_t nup = 0;
     for (size_t i = 0; i < n; i++) { in.upb[i] = (uint32_t)nup; nup += g.levels[i]; }
@@ -1121,6 +1279,105 @@ struct SlimGraph {
         if (u >= n || (uint32_t)g.levels[u] < l) return false;
       }
     }
+    return true;
+  }
+  // label_lookup_ of a Slim index that is re-derived on the device: the map, and the nodes i whose label it maps to ANOTHER id
+  // (`lookup[label(i)] != i`, :1360: such a node is new whenever it has neighbours).  Every other node maps to itself, so a call
+  // looks up only the nodes whose label changed or that are new; the set is rebuilt (one pass) after a call that did not keep it.
+  struct Lookup {
+    std::unordered_map<uint64_t, uint32_t> map;
+    std::set<uint32_t> mismatch;
+    bool mismatch_valid = false;
+  };
+  // convert_diff on the device (convert_diff.hip): the list passes read the rows from `d_vec`, the resident fp32 array of the HNSW
+  // index; the diff kernel compares the final lists with the Slim index's resident adjacency (dd) and hands back the compacted
+  // lists; the host then assembles the element and blob of the flagged nodes only and looks up the labels of the nodes whose
+  // label changed.  Returns false, with this object untouched, when the shape is outside the device path (capacities above 32
+  // ids, a source list above 64, a union above 2048): the caller then runs convert_diff().
+  // accept (nullable): called with the nodes whose row or label the call would rewrite, before anything changes; false refuses the
+  // call (*refused set, this object untouched).
+  bool convert_diff_gpu(const VanillaGraph &g, const SlimParams &p, const float *d_vec, int device, int threads, Lookup &lk, DiffDev &dd,
+                        Diff &out, double *kernel_ms, std::string *err, const std::function<bool(const std::vector<uint32_t> &)> *accept = nullptr,
+                        bool *refused = nullptr) {
+    if (g.maxM0 > 32 || g.maxM > 32 || maxM0 > 32 || maxM > 32 || p.top_M0 > 32 || p.low_m0 > 32 || p.top_M > 32 || p.low_m > 32) return false;
+    const size_t prev_count = count, n = g.count;
+    ConvertInput in;
+    if (!make_convert_input(g, p, hub_thresholds(g, p), maxM0, maxM, in)) return false;
+    dd.levels.assign(g.levels.begin(), g.levels.begin() + n);
+    dd.prev_count = (uint32_t)prev_count;
+    dd.threshold_level = threshold_level;
+    dd.want_flags = true;
+    std::vector<uint32_t> fin, fin_cnt;
+    bool needs_host = false;
+    uint32_t n_reprune = 0;
+    hipError_t e = gpu_convert_diff_lists(in, d_vec, device, fin, fin_cnt, needs_host, n_reprune, kernel_ms, &dd);
+    if (e != hipSuccess) {
+      if (err) *err = std::string("GPU convert: ") + hipGetErrorString(e);
+      return false;
+    }
+    if (needs_host) return false;
+    if (accept && !(*accept)(dd.stale)) {
+      if (refused) *refused = true;
+      return false;
+    }
+    if (!lk.mismatch_valid) {
+      lk.mismatch.clear();
+      for (size_t i = 0; i < prev_count; i++)
+        if (lk.map.find(label((uint32_t)i))->second != i) lk.mismatch.insert((uint32_t)i);
+      lk.mismatch_valid = true;
+    }
+    out.n_reprune = n_reprune;
+    count = n;   // the head of the call (:1113-1135); the merge concerns only labels the Slim index does not hold at that id
+    has_deleted = g.num_deleted() > 0;
+    maxlevel = g.maxlevel; enterpoint = g.enterpoint;
+    elements.resize(count * size_per_el, 0);
+    blobs.resize(count);
+    for (uint32_t id : dd.stale) {
+      lk.mismatch.erase(id);
+      if (lk.map.emplace(g.label(id), id).first->second != id) lk.mismatch.insert(id);
+    }
+    out.count = n;
+    out.old_ids = std::move(dd.old_ids); out.new_ids = std::move(dd.new_ids);
+    out.dirty = std::move(dd.dirty); out.stale = std::move(dd.stale);
+    for (uint32_t id : lk.mismatch) {   // :1360-1362: new whatever its blob did, when it has neighbours
+      if (id >= n || !(dd.flags[id] & 2)) continue;
+      auto o = std::lower_bound(out.old_ids.begin(), out.old_ids.end(), id);
+      if (o != out.old_ids.end() && *o == id) out.old_ids.erase(o);
+      auto w = std::lower_bound(out.new_ids.begin(), out.new_ids.end(), id);
+      if (w == out.new_ids.end() || *w != id) out.new_ids.insert(w, id);
+    }
+    const int T = std::max(1, threads);
+    std::atomic<size_t> next(0);
+    std::vector<std::thread> pool;
+    for (int t = 0; t < T; t++)
+      pool.emplace_back([&]() {
+        for (size_t k0; (k0 = next.fetch_add(64)) < out.dirty.size();)
+          for (size_t k = k0; k < std::min(out.dirty.size(), k0 + 64); k++) {
+            const size_t i = out.dirty[k];
+            blobs[i].clear();
+            assemble_node(g, i, [&](size_t v, int l, size_t &cnt) {
+              const size_t t2 = l == 0 ? v : n + in.upb[v] + l - 1;
+              cnt = fin_cnt[t2];
+              return fin.data() + t2 * 32;
+            });
+          }
+      });
+    for (auto &th : pool) th.join();
+    return true;
+  }
+  // The same conversion with the list-level work on the GPU (convert_gpu.hip).  Returns false when the shape is outside the
+  // device path (lists longer than 64 / capacities above 32 ids, or a reverse-edge list that outgrew the on-chip buffers):
+  // the caller then runs convert().  kernel_ms: device time of the kernels.
+  bool convert_gpu(const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
+    if (g.maxM0 > 32 || g.maxM > 32 || p.top_M0 > 32 || p.low_m0 > 32 || p.top_M > 32 || p.low_m > 32) return false;
+    take_header(g, p);
+    const size_t n = count;
+    const std::vector<size_t> thr = hub_thresholds(g, p);
+    ConvertInput in;
+    if (!make_convert_input(g, p, thr, maxM0, maxM, in)) return false;
+    std::vector<float> rows(n * dim);
+    for (size_t i = 0; i < n; i++) memcpy(&rows[i * dim], g.vec(i), 4 * dim);
+    in.vec = rows.data();
     std::vector<uint32_t> fin, fin_cnt;
     bool needs_host = false;
     hipError_t e = gpu_convert_lists(in, device, fin, fin_cnt, needs_host, kernel_ms);
@@ -1293,16 +1550,18 @@ struct PackedIndex {
     if (cols.size() >= NONE) throw std::runtime_error("adjacency too large for 32-bit CSR offsets");
   }
 
-  void from_slim(const SlimGraph &g) {
+  // with_rows = false (hs_slim_convert_diff, whose device rows are written record by record): `vec` stays empty
+  void from_slim(const SlimGraph &g, bool with_rows = true) {
     kind = 1; metric = g.metric; n = g.count; dim = g.dim;
     // HierarchicalNSWSlim::indexSize() (hnswalg_slim.h:2435-2444): 16 bytes per element + every neighbour blob
     index_size = g.count * 16;
     for (size_t i = 0; i < g.count; i++) index_size += 2 * (size_t)g.level((uint32_t)i) + 4 * (size_t)g.total((uint32_t)i);
     maxlevel = g.maxlevel; threshold_level = g.threshold_level; enterpoint = g.enterpoint;
     has_deleted = g.has_deleted;
-    vec.resize(n * dim); labels.resize(n); deleted.resize(n);
+    rows_on_device = !with_rows;
+    vec.resize(with_rows ? n * dim : 0); labels.resize(n); deleted.resize(n);
     for (size_t i = 0; i < n; i++) {
-      memcpy(&vec[i * dim], g.vec(i), 4 * dim);
+      if (with_rows) memcpy(&vec[i * dim], g.vec(i), 4 * dim);
       labels[i] = g.label(i);
       deleted[i] = g.deleted(i);
     }

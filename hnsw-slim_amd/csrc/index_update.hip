@@ -54,7 +54,8 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
     if (lane < a.stride / 4) dst[lane] = src[lane];
   }
   if (r >= a.first_row) {
-    const float *x = reinterpret_cast<const float *>(a.stage + (size_t)a.nrec * (4 + a.stride) + (size_t)(r - a.first_row) * a.row_words);
+    const float *x = a.src_vec ? a.src_vec + (size_t)id * a.dim
+                               : reinterpret_cast<const float *>(a.stage + (size_t)a.nrec * (4 + a.stride) + (size_t)(r - a.first_row) * a.row_words);
     if (a.vec) {
       float *dst = a.vec + (size_t)id * a.dim;
       if ((a.dim & 3u) == 0) {

@@ -21,6 +21,8 @@ struct UpdateArgs {
   void *narrow;            // nullable (an index in HS_ROWS_F32 format)
   uint64_t *labels;
   uint8_t *deleted;
+  const float *src_vec;    // nullable; when set, the row of a record is read from src_vec + id * dim (rows already on the device:
+                           // hs_slim_convert_diff takes them from the resident HNSW index) and the buffer holds no rows section
 };
 
 hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream);

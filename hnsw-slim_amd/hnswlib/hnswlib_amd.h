@@ -17,8 +17,9 @@
 // HierarchicalNSW<float> also changes while resident: addPoint on an index with room -- of a new label, of an
 // existing one (the reference's update) and with replace_deleted under the allow_replace_deleted constructor flag -- markDelete /
 // unmarkDelete, resizeIndex, getDataByLabel, saveIndex (hnswalg.h:689-717, 896-1272, 1248-1376, 748-779).
-// Not provided: updateNeighborProbability other than 1.0, updates of Slim / SlimQ indexes, the diff/patch
-// protocol (genPatch), stop conditions.
+// HierarchicalNSWSlim<float> is also the patch server's index: convertFromHNSWWithDiff from a resident
+// HierarchicalNSW<float> and genPatch (hnswalg_slim.h:1110-1751), feeding patchFromStream clients.
+// Not provided: updateNeighborProbability other than 1.0, addPoint on Slim / SlimQ indexes, stop conditions.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -499,6 +500,19 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   float p0_ = 0.02f, p_ = 0.02f;
   size_t M0h_ = 32, m0l_ = 8, Mh_ = 16, ml_ = 4;
   std::string tmp_path_;
+  hs_slim_diff *diff_ = nullptr;   // the last convertFromHNSWWithDiff: changed_old_nodes_ / changed_new_nodes_ and genPatch's cursors
+  bool diffed_ = false;            // the host image has moved on from the file this object was loaded from
+
+  void run_diff(HierarchicalNSW<float> *hnsw, int threads) {
+    if (!h_ || !hnsw) throw std::runtime_error("hnswlib_amd: convertFromHNSWWithDiff needs a loaded Slim index and a vanilla index");
+    if (replicas_.size() > 1) throw std::runtime_error("hnswlib_amd: convertFromHNSWWithDiff is not provided on a sharded index");
+    hnsw->build();
+    hs_slim_diff *d = nullptr;
+    detail::check(hs_slim_convert_diff(h_, hnsw->handle(), p0_, p_, M0h_, m0l_, Mh_, ml_, threads, &d, nullptr, nullptr));
+    if (diff_) hs_slim_diff_free(diff_);
+    diff_ = d;
+    diffed_ = true;
+  }
 
  public:
   explicit HierarchicalNSWSlim(SpaceInterface<float> *s) : space_(s) {}
@@ -513,7 +527,61 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
                       size_t /*random_seed*/ = 100, bool /*allow_replace_deleted*/ = false)
       : space_(s), thr_((int)threshold_level), p0_(top_degree_percent0), p_(top_degree_percent), M0h_(top_degree_M0),
         m0l_(low_degree_m0), Mh_(top_degree_M), ml_(low_degree_m) {}
-  ~HierarchicalNSWSlim() { if (!tmp_path_.empty()) unlink(tmp_path_.c_str()); }
+  ~HierarchicalNSWSlim() {
+    if (diff_) hs_slim_diff_free(diff_);
+    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
+  }
+  // the pruning parameters of an object that was loaded from a file (the reference's loading constructor takes them too)
+  void setPruning(float top_degree_percent0, float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
+                  size_t low_degree_m) {
+    p0_ = top_degree_percent0; p_ = top_degree_percent; M0h_ = top_degree_M0; m0l_ = low_degree_m0; Mh_ = top_degree_M; ml_ = low_degree_m;
+  }
+  // convertFromHNSWWithDiff(hnsw, output, to_add_data) (hnswalg_slim.h:1110-1424) on two resident indexes, both loaded with
+  // max_elements > their element count: re-derives this index from `hnsw` with the object's pruning parameters, in place on the
+  // device, and writes the whole stream -- count, the two list lengths, the old records, the new records without rows: what
+  // patchFromStream(in, false) takes.  Returns the new ids when to_add_data (the rows the caller ships beside the stream).
+  // The changed lists are ascending (the reference fills them in thread order); see INTEGRATION.md 9 for the other decisions.
+  std::vector<tableint> convertFromHNSWWithDiff(HierarchicalNSW<float> *hnsw, std::ostream &output, bool to_add_data = false, int threads = 8) {
+    run_diff(hnsw, threads);
+    size_t len = 0;
+    (void)hs_slim_diff_stream(diff_, h_, nullptr, 0, &len);
+    std::string buf(len, '\0');
+    detail::check(hs_slim_diff_stream(diff_, h_, &buf[0], buf.size(), &len));
+    output.write(buf.data(), (std::streamsize)len);
+    std::vector<tableint> ids;
+    if (to_add_data) {
+      size_t n_new = 0;
+      detail::check(hs_slim_diff_info(diff_, nullptr, nullptr, &n_new, nullptr));
+      ids.resize(n_new);
+      detail::check(hs_slim_diff_ids(diff_, nullptr, ids.data()));
+    }
+    return ids;
+  }
+  // convertFromHNSWWithDiff(hnsw, changed_old_cnt, changed_new_cnt) (hnswalg_slim.h:1478-1751): the same conversion, the changed
+  // lists kept in the object for genPatch, whose cursors start at the head of the new lists.
+  void convertFromHNSWWithDiff(HierarchicalNSW<float> *hnsw, size_t &changed_old_cnt, size_t &changed_new_cnt, int threads = 8) {
+    run_diff(hnsw, threads);
+    detail::check(hs_slim_diff_info(diff_, nullptr, &changed_old_cnt, &changed_new_cnt, nullptr));
+  }
+  // genPatch (hnswalg_slim.h:1427-1476): the bare records, up to `limit` bytes of them; old_written / new_written are incremented
+  // per record as the reference increments them.  As written there, the record that reaches `limit` is sent and its cursor is not
+  // advanced: the next call sends that node again.  Returns `finished`.
+  uint32_t genPatch(std::ostream &output, size_t &old_written, size_t &new_written, size_t limit, bool to_add = false) {
+    if (!diff_) return 1;   // old_nodes_cnt_ == new_nodes_cnt_ == 0: both loops are empty
+    size_t len = 0, ow = 0, nw = 0;
+    int finished = 0;
+    std::string buf(1 << 16, '\0');
+    hs_status st = hs_slim_diff_next(diff_, h_, limit, to_add ? 1 : 0, &buf[0], buf.size(), &len, &ow, &nw, &finished);
+    if (st == HS_ERR_CAPACITY) {   // the cursors have not moved: once more with the size it asked for
+      buf.resize(len);
+      st = hs_slim_diff_next(diff_, h_, limit, to_add ? 1 : 0, &buf[0], buf.size(), &len, &ow, &nw, &finished);
+    }
+    detail::check(st);
+    output.write(buf.data() + 24, (std::streamsize)(len - 24));
+    old_written += ow;
+    new_written += nw;
+    return (uint32_t)finished;
+  }
   void loadIndex(const std::string &location, SpaceInterface<float> *s, size_t max_elements_i = 0) {
     space_ = s;
     load(location, HS_KIND_SLIM, s, max_elements_i);
@@ -548,6 +616,7 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   }
   // saveIndex (hnswalg_slim.h:717-751): the Slim file this object holds (written by convertFromHNSW or loaded), copied
   void saveIndex(const std::string &location) override {
+    if (diffed_) { detail::check(hs_slim_index_save(h_, location.c_str())); return; }   // after convertFromHNSWWithDiff: the host image
     if (path_.empty()) throw std::runtime_error("hnswlib_amd: nothing to save");
     if (location == path_) return;
     std::ifstream in(path_, std::ios::binary);

@@ -529,6 +529,65 @@ hs_status hs_convert_slim_gpu(const char *hnsw_path, int metric, size_t dim, int
                               size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, int device, int threads,
                               const char *out_path, int *used_gpu, double *kernel_ms);
 
+/* ---- the patch server: convertFromHNSWWithDiff (hnswalg_slim.h:1110-1424, 1478-1751) and genPatch (:1427-1476) -------------
+ * The server of the reference's update experiment (hnsw_slim_server_patch.cc:204-296) keeps a vanilla index growing, re-derives
+ * its Slim index after every batch and ships the difference; its clients apply it with patchFromStream (hs_index_patch).
+ *
+ * hs_slim_convert_diff: `slim` is a HS_KIND_SLIM index and `hnsw` a HS_KIND_HNSW index, both loaded with max_elements > their
+ * element count (so both hold a host image), of the same metric, dim, maxM and maxM0.  The call re-derives `slim` from `hnsw` --
+ * both prunes are hnsw->getNeighborsByHeuristic2 (hnswalg.h:481-523), not PruneByHeuristic -- updates slim's host image and its
+ * device arrays in place (one staged upload and one kernel for the changed nodes; count, maxlevel, enterpoint and has_deleted
+ * follow `hnsw`, :1113-1118) and returns the changed nodes as a diff object.  slim keeps its own threshold_level.
+ * The list passes run on the device when both indexes are on the same device, hnsw holds resident fp32 rows, every degree
+ * capacity and budget is at most 32, no source list exceeds 64 ids and no union 2048; otherwise on `threads` host threads with
+ * the same bytes.  *used_gpu (nullable) says which, *kernel_ms (nullable) the time from the first
+ * kernel to the last -- list, diff and compaction kernels -- which includes the host round trips between them.  On the device path a
+ * diff kernel compares the new lists with slim's resident adjacency, rows and labels and compacts the changed ids; the host
+ * assembles elements and blobs of the flagged nodes only, and their rows are copied from hnsw's resident array.
+ * Where the reference is undefined or timing-dependent this library decides: a re-pruned list holds exactly
+ * the entries the heuristic kept, in pop order; the two changed lists are in ascending id; elements beyond the previous count
+ * start empty.  A node whose lists come out empty is in neither list (:1340-1343).  Delete marks do not reach Slim elements.
+ * Refused before anything changes: HS_ERR_INVALID (null argument, wrong kinds, an index without a host image, metric / dim /
+ * capacities that differ, hnsw holding fewer elements than slim), HS_ERR_CAPACITY when hnsw's element count exceeds slim's
+ * max_elements (the reference reallocs here; load slim with more room), HS_ERR_UNSUPPORTED when slim has narrow rows and a new
+ * row is not representable.  Not while a search on either index is in flight.
+ * A failure after these checks (HS_ERR_NOMEM, HS_ERR_DEVICE while the changed nodes are written) is not rolled back: slim's host
+ * image is then ahead of its device arrays and the index must be freed and loaded again.
+ * A diff object serves until the next hs_slim_convert_diff on the same index; after it the hs_slim_diff_* calls that need the
+ * index refuse the older object (HS_ERR_INVALID). */
+typedef struct hs_slim_diff hs_slim_diff;
+hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_percent0, float top_degree_percent,
+                               size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, int threads,
+                               hs_slim_diff **out, int *used_gpu, double *kernel_ms);
+/* cur_element_count and the lengths of the two changed lists; n_reprune (nullable): lists that went through the re-prune. */
+hs_status hs_slim_diff_info(const hs_slim_diff *d, size_t *count, size_t *n_old, size_t *n_new, size_t *n_reprune);
+/* The changed old nodes and the new nodes, ascending (n_old / n_new ids; either pointer may be NULL). */
+hs_status hs_slim_diff_ids(const hs_slim_diff *d, uint32_t *old_ids, uint32_t *new_ids);
+/* The whole stream of the std::ostream overload (:1384-1422): u64 count, u64 n_old, u64 n_new, the old records (8-byte head),
+ * the new records (16-byte head, no rows) -- what hs_index_patch(.., to_add = 0) takes.  `slim` is the index the diff was made
+ * on (NULL for a diff of hs_slim_convert_diff_files).  *len receives the size; HS_ERR_CAPACITY when cap is smaller (buf may be
+ * NULL with cap 0 to ask). */
+hs_status hs_slim_diff_stream(const hs_slim_diff *d, const hs_index *slim, void *buf, size_t cap, size_t *len);
+/* One genPatch call (:1427-1476) with the cursors kept in the diff object: records until their sizes reach `limit` bytes, new
+ * records with their row when to_add.  Written as the 24-byte header hs_index_patch expects, {u64 count, u64 old_written, u64
+ * new_written} of THIS call, then genPatch's record bytes.  As in the reference the record that reaches `limit` is written and
+ * its cursor is not advanced, so the next call sends that node again.  *finished = genPatch's return value.  HS_ERR_CAPACITY
+ * with the needed *len when cap is too small; the cursors then do not move. */
+hs_status hs_slim_diff_next(hs_slim_diff *d, const hs_index *slim, size_t limit, int to_add, void *buf, size_t cap, size_t *len,
+                            size_t *old_written, size_t *new_written, int *finished);
+void hs_slim_diff_free(hs_slim_diff *d);
+/* saveIndex (hnswalg_slim.h:717-751) of the host image of a Slim index loaded with max_elements > its element count, as
+ * hs_slim_convert_diff and hs_index_patch left it.  HS_ERR_INVALID for any other index (hs_index_save is the vanilla twin). */
+hs_status hs_slim_index_save(const hs_index *slim, const char *path);
+/* Host only, no device: the same call on files.  old_slim_path NULL: an empty Slim index with `threshold_level` and the HNSW
+ * file's capacities (every node with neighbours is then new); otherwise the Slim file's own threshold_level is kept.  Writes the
+ * new Slim file (saveIndex, :717-751) to out_slim_path and, when out_stream_path is given, the whole stream; *out (nullable)
+ * receives a diff object that owns its Slim image (pass slim = NULL to hs_slim_diff_stream / hs_slim_diff_next). */
+hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw_path, int metric, size_t dim, int threshold_level,
+                                     float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
+                                     size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, int threads,
+                                     const char *out_slim_path, const char *out_stream_path, hs_slim_diff **out);
+
 /* The graph HNSW-SlimQ is converted FROM: rabitqlib::hnsw::HierarchicalNSW(num_points, dim, total_bits, M, ef_construction,
  * random_seed, metric) + construct() (third_party/rabitqlib/index/hnsw/hnsw.hpp:427-500, 667-1054), as
  * include/strategy/hnsw_slimq_strategy.h:106-121 drives it with M = 32, ef_construction = 128, seed 100.  Edges come from the RAW

@@ -1,0 +1,199 @@
+"""CPU-only tests of the patch server's host core: hs_slim_convert_diff_files (SlimGraph::convert_diff, csrc/host_graph.hpp) against
+the independent Python reading of convertFromHNSWWithDiff / genPatch in tests/slim_diff_restated.py -- the new Slim file, the two
+changed lists, the whole stream and a chunked genPatch drain -- over three rounds of a growing index (+100 rows, +50 rows, a mark
+plus a replace_deleted add); the streams applied by a Python patchFromStream; and the stand-alone program csrc/diff_prune_test.cpp,
+plain and under AddressSanitizer / UBSan."""
+import copy
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from hsutil import ROOT, load_chal_encode, load_product, write_vanilla_level0
+from slim_diff_restated import SlimState, convert_with_diff, full_stream, gen_patch, patch_from_stream
+from slim_restated import int_rows
+
+DIM = 16
+PARAMS = dict(top_degree_percent0=0.02, top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16, low_degree_m=4)
+RESTATED = (0.02, 0.02, 32, 8, 16, 4)
+# (M, threshold_level, seed of the rows, (alpha_0, alpha, M_h0, M_l0, M_h, M_l)): one cluster of rows and degree budgets close to the
+# capacities, so that own list + reverse edges of the hubs exceed maxM0 / maxM and the re-prune runs, while lists at or above the
+# budget still go through the first prune
+CASES = [(8, 0, 11, (0.02, 0.1, 16, 12, 8, 6)), (16, 0, 12, (0.02, 0.1, 32, 28, 16, 12)), (8, 1, 13, (0.02, 0.1, 16, 12, 8, 6))]
+N0, ADD1, ADD2 = 300, 100, 50
+MARK, ADD = 1, 0
+LIMIT = 1000   # genPatch's byte limit per chunk: several records each, dozens of chunks per round
+
+
+@pytest.fixture(scope="module")
+def hs():
+    m = load_product()
+    m.build_library()
+    return m
+
+
+@pytest.fixture(scope="module")
+def ce():
+    return load_chal_encode()
+
+
+def _drain(diff, state, old_ids, new_ids, to_add):
+    """Every genPatch chunk of the product against the restatement's; returns the product's chunks."""
+    cursors, chunks, records = [0, 0], [], 0
+    for _ in range(10000):
+        got, ow, nw, fin = diff.next(LIMIT, to_add)
+        want, wow, wnw, wfin = gen_patch(state, old_ids, new_ids, cursors, LIMIT, to_add)
+        assert got == struct.pack("<3Q", state.count, wow, wnw) + want and (ow, nw, fin) == (wow, wnw, wfin)
+        chunks.append(got)
+        records += ow + nw
+        if fin:
+            break
+    assert fin
+    return chunks, records
+
+
+@pytest.fixture(scope="module", params=CASES, ids=lambda c: f"M{c[0]}_thr{c[1]}")
+def rounds(request, hs, ce, tmp_path_factory):
+    """The three rounds of one case, product and restatement side by side: a list of dicts, computed once."""
+    M, thr, seed, restated = request.param
+    PARAMS = dict(zip(("top_degree_percent0", "top_degree_percent", "top_degree_M0", "low_degree_m0", "top_degree_M", "low_degree_m"), restated))
+    tmp = tmp_path_factory.mktemp(f"diff_M{M}_t{thr}")
+    rows = int_rows(N0 + ADD1 + ADD2 + 1, DIM, seed, clusters=1)
+    p = lambda name: str(tmp / name)   # noqa: E731
+    hs.build_hnsw(rows[:N0], p("h0.bin"), M=M, ef_construction=60, threads=1)
+    hs.convert_slim(p("h0.bin"), p("s0.bin"), DIM, threshold_level=thr, **PARAMS)
+    cap = N0 + ADD1 + ADD2 + 8
+    hs.hnsw_resume(p("h0.bin"), p("h1.bin"), rows[N0:N0 + ADD1], np.arange(N0, N0 + ADD1), DIM, max_elements=cap, seed=100, drawn=N0)
+    hs.hnsw_resume(p("h1.bin"), p("h2.bin"), rows[N0 + ADD1:N0 + ADD1 + ADD2], np.arange(N0 + ADD1, N0 + ADD1 + ADD2), DIM, seed=100,
+                   drawn=N0 + ADD1)
+    # a mark, then an add that takes the marked slot: the label changes at an old id
+    hs.hnsw_replay(p("h2.bin"), p("h3.bin"), [(MARK, 7, 0, 0), (ADD, 9000, 1, 0)], rows[-1:], DIM, allow_replace_deleted=True)
+    state = SlimState.from_file(open(p("s0.bin"), "rb").read(), DIM)
+    out = []
+    for k in (1, 2, 3):
+        old_file = open(p(f"s{k - 1}.bin"), "rb").read()
+        diff = hs.slim_convert_diff_files(p(f"s{k - 1}.bin"), p(f"h{k}.bin"), p(f"s{k}.bin"), DIM, threshold_level=5, out_stream_path=p(f"p{k}.bin"),
+                                          threads=3, **PARAMS)   # (threshold_level: the old file's own is kept)
+        g = ce.parse_vanilla(open(p(f"h{k}.bin"), "rb").read())
+        old_ids, new_ids, stats = convert_with_diff(state, g, *restated)
+        fresh = (lambda k=k: hs.slim_convert_diff_files(p(f"s{k - 1}.bin"), p(f"h{k}.bin"), p("scratch.bin"), DIM, **PARAMS))
+        out.append(dict(diff=diff, fresh=fresh, state=copy.deepcopy(state), old_ids=old_ids, new_ids=new_ids, stats=stats, old_file=old_file,
+                        new_file=open(p(f"s{k}.bin"), "rb").read(), stream_file=open(p(f"p{k}.bin"), "rb").read(), g=g))
+    return out
+
+
+def test_files_entry_equals_the_restatement(rounds):
+    for k, r in enumerate(rounds):
+        assert r["stats"]["tied"] == 0, "the restatement does not model the heap order among equal distances: choose another seed"
+        assert r["new_file"] == r["state"].file_bytes(), f"round {k + 1}: Slim file"
+        got_old, got_new = r["diff"].ids()
+        assert got_old.tolist() == r["old_ids"] and got_new.tolist() == r["new_ids"], f"round {k + 1}: changed lists"
+        info = r["diff"].info()
+        assert (info["count"], info["n_old"], info["n_new"]) == (r["g"]["count"], len(r["old_ids"]), len(r["new_ids"]))
+        assert info["n_reprune"] == r["stats"]["reprune"]
+        want = full_stream(r["state"], r["old_ids"], r["new_ids"])
+        assert r["diff"].stream() == want and r["stream_file"] == want, f"round {k + 1}: stream"
+    # the premises: hubs beyond maxM0 were re-pruned, new nodes are new, old nodes changed, and most old nodes of the later
+    # rounds did not
+    assert all(r["stats"]["reprune"] > 0 for r in rounds), [r["stats"] for r in rounds]
+    assert rounds[0]["new_ids"] == list(range(N0, N0 + ADD1)) and rounds[1]["new_ids"] == list(range(N0 + ADD1, N0 + ADD1 + ADD2))
+    assert 0 < len(rounds[1]["old_ids"]) < N0 + ADD1
+    # round 3: the reused slot keeps its id; it is no new node, and its old record (if its lists changed) carries no label
+    g3 = rounds[2]["g"]
+    slot = int(np.flatnonzero(g3["labels"] == 9000)[0])
+    assert slot < N0 + ADD1 + ADD2 and rounds[2]["new_ids"] == [] and g3["count"] == N0 + ADD1 + ADD2
+    assert struct.unpack_from("<Q", rounds[2]["state"].heads[slot], 8)[0] == 9000
+    assert not rounds[2]["state"].has_deleted and all(h[6] & 1 == 0 for h in rounds[2]["state"].heads)   # no Slim node is marked
+
+
+def test_chunked_genpatch_resends_the_record_that_reached_the_limit(rounds):
+    for k, r in enumerate(rounds):
+        n = len(r["old_ids"]) + len(r["new_ids"])
+        for to_add in (False, True):
+            chunks, records = _drain(r["fresh"](), r["state"], r["old_ids"], r["new_ids"], to_add)   # (the cursors live in the object)
+            assert n > 0 and records == n + len(chunks) - 1   # every chunk but the last sends its last record again
+            assert len(chunks) >= (3 if k < 2 else 2)         # (round 3 changes a handful of nodes)
+
+
+def test_streams_patch_the_old_image_into_the_new_one(hs, rounds, tmp_path):
+    for k, r in enumerate(rounds):
+        new = SlimState.from_file(r["new_file"], DIM)
+        whole = SlimState.from_file(r["old_file"], DIM)
+        patch_from_stream(whole, r["stream_file"], False)
+        chunked = SlimState.from_file(r["old_file"], DIM)
+        d = r["fresh"]()
+        for _ in range(10000):
+            chunk, _, _, fin = d.next(LIMIT, True)
+            patch_from_stream(chunked, chunk, True)
+            if fin:
+                break
+        relabelled = []
+        for client, with_rows in ((whole, False), (chunked, True)):
+            assert client.count == new.count
+            for i in range(new.count):
+                if new.total(i) == 0:
+                    continue
+                assert client.heads[i][:8] == new.heads[i][:8] and client.blobs[i] == new.blobs[i], (k, i)
+                if client.heads[i][8:16] != new.heads[i][8:16]:
+                    relabelled.append(i)
+                if with_rows and i in r["new_ids"]:
+                    assert client.rows[i] == new.rows[i]
+        # an old node whose label changed on the server is rewritten there only: the old record carries {level, total} alone
+        slot = int(np.flatnonzero(r["g"]["labels"] == 9000)[0]) if k == 2 else None
+        assert sorted(set(relabelled)) == ([slot] if k == 2 else [])
+
+
+def test_a_node_without_neighbours_is_in_neither_list(hs, ce, tmp_path):
+    rows = int_rows(6, DIM, 3)
+    lists = [[1, 2], [0, 2], [0, 1], [4], [3], []]
+    hp, sp, s2 = (str(tmp_path / x) for x in ("h.bin", "s.bin", "s2.bin"))
+    write_vanilla_level0(hp, rows, lists, 8)
+    d = hs.slim_convert_diff_files(None, hp, sp, DIM, **PARAMS)
+    g = ce.parse_vanilla(open(hp, "rb").read())
+    state = SlimState(DIM, 0, g["maxM"], g["maxM0"], g["M"], g["efC"])
+    old_ids, new_ids, _ = convert_with_diff(state, g, *RESTATED)
+    assert (old_ids, new_ids) == ([], [0, 1, 2, 3, 4])
+    got_old, got_new = d.ids()
+    assert got_old.tolist() == [] and got_new.tolist() == [0, 1, 2, 3, 4]
+    assert open(sp, "rb").read() == state.file_bytes() and d.stream() == full_stream(state, old_ids, new_ids)
+    # a fresh cursor and a buffer one byte short: the size comes back, nothing moves, the next call sends everything
+    need = len(d.next(1 << 20, True, cap=1 << 20)[0])
+    d = hs.slim_convert_diff_files(None, hp, sp, DIM, **PARAMS)
+    with pytest.raises(hs.HsError) as e:
+        d.next(1 << 20, True, cap=need - 1)
+    assert e.value.status == hs.HS_ERR_CAPACITY and str(need) in str(e.value)
+    got, ow, nw, fin = d.next(1 << 20, True, cap=need)
+    assert (len(got), ow, nw, fin) == (need, 0, 5, True)
+    # a second round in which nothing changed: both lists empty, the stream is its header
+    d2 = hs.slim_convert_diff_files(sp, hp, s2, DIM, **PARAMS)
+    assert d2.info()["n_old"] == 0 and d2.info()["n_new"] == 0 and d2.stream() == struct.pack("<3Q", 6, 0, 0)
+    assert open(s2, "rb").read() == open(sp, "rb").read()
+
+
+def test_refusals(hs, tmp_path):
+    rows = int_rows(40, DIM, 5)
+    h8, h16, s16 = (str(tmp_path / x) for x in ("h8.bin", "h16.bin", "s16.bin"))
+    hs.build_hnsw(rows, h8, M=8, ef_construction=40)
+    hs.build_hnsw(rows, h16, M=16, ef_construction=40)
+    hs.convert_slim(h16, s16, DIM)
+    out = str(tmp_path / "out.bin")
+    with pytest.raises(hs.HsError) as e:   # capacities differ
+        hs.slim_convert_diff_files(s16, h8, out, DIM, **PARAMS)
+    assert e.value.status == hs.HS_ERR_INVALID and not os.path.exists(out)
+    hs.build_hnsw(rows[:30], h8, M=16, ef_construction=40)
+    with pytest.raises(hs.HsError) as e:   # the vanilla index holds fewer elements
+        hs.slim_convert_diff_files(s16, h8, out, DIM, **PARAMS)
+    assert e.value.status == hs.HS_ERR_INVALID and not os.path.exists(out)
+
+
+@pytest.mark.parametrize("sanitised", [False, True], ids=["plain", "asan_ubsan"])
+def test_diff_prune_program(sanitised):
+    """csrc/diff_prune_test.cpp as its own binary (never inside Python): the candidate order and the pop-order emulation the device
+    kernels share with the host (csrc/diff_prune.hpp) against std::priority_queue, on lists full of equal distances."""
+    d = os.path.join(ROOT, "hnsw-slim_amd")
+    name = "diff_prune_test_san" if sanitised else "diff_prune_test"
+    subprocess.check_call(["make", "-C", d, name])
+    out = subprocess.run([os.path.join(d, name)], capture_output=True, text=True)
+    assert out.returncode == 0 and "diff_prune ok" in out.stdout, out.stdout + out.stderr
