@@ -78,6 +78,10 @@ class HsPlanOut(ctypes.Structure):    # hs_plan_out
                 ("spill_stride", _u32), ("log_cap", _u32), ("hop_cap", _u32), ("name", ctypes.c_char_p)]
 
 
+class HsFastShape(ctypes.Structure):  # hs_fast_shape
+    _fields_ = [("d16", _i32), ("slots", _i32), ("wb", _i32)]
+
+
 def build_library(force=False):
     """Compile the HIP extension in-tree (hipcc --offload-arch=gfx950)."""
     if force or not os.path.exists(LIB_PATH):
@@ -125,6 +129,8 @@ def lib():
     if "HS_LIB" not in os.environ or hasattr(L, "hs_debug_search_plan"):   # (a baseline build in an A/B run may predate these two)
         L.hs_debug_search_plan.argtypes = [ctypes.POINTER(HsPlanIn), ctypes.POINTER(HsPlanOut)]
         L.hs_debug_plan_input.argtypes = [vp, sz, sz, ci, ci, ctypes.POINTER(HsPlanIn)]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_debug_fast_shape"):
+        L.hs_debug_fast_shape.argtypes = [ci, _u64, _u64, _u64, ci, ctypes.POINTER(HsFastShape)]
     L.hs_search_batch_async.argtypes = [vp, vp, sz, sz, ci, vp, vp, vp, vp, vp, vp]
     L.hs_host_alloc.restype = vp
     L.hs_host_alloc.argtypes = [sz]
@@ -492,6 +498,13 @@ def debug_search_plan(inp):
     d = {f: getattr(out, f) for f, _ in HsPlanOut._fields_}
     d["name"] = out.name.decode()
     return d
+
+
+def debug_fast_shape(metric, dim, ef, k, bare=True):
+    """hs_debug_fast_shape (host only): the instantiation of hs::fast_kernel the launchers pick for a call, as dict(d16, slots, wb)."""
+    out = HsFastShape()
+    _check(lib().hs_debug_fast_shape(int(metric), int(dim), int(ef), int(k), int(bool(bare)), ctypes.byref(out)))
+    return {f: getattr(out, f) for f, _ in HsFastShape._fields_}
 
 
 def debug_plan_input(index, k, nq, has_filter=False, want_raw=False):

@@ -1476,31 +1476,47 @@ hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStr
 }
 #endif
 
+// The launchers below dispatch on fast_shape() (engine.hpp, search_plan.cpp) and on nothing else: which dims have a distance pass
+// of their own, the slots per lane and the boundary watch are decided there, and a shape without an instantiation here is refused.
 // delete marks / filters: the variant with the reference's !bare_bone branches (runtime-dim and d=128 only)
 template <int METRIC, int D16>
-static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr,
-                                  const FilterArgs *f = nullptr) {
+static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FastShape &sh,
+                                  const void *rows = nullptr, const FilterArgs *f = nullptr) {
+  if (sh.wb) return hipErrorInvalidValue;
   if (f) {   // under a filter set: the same shapes, the set as a kernel argument
-    if (a.ef <= 64) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-    if (a.ef <= 128) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-    if (a.ef <= 256) return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-    return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+    switch (sh.slots) {
+      case 1: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 2: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 4: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 8: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      default: return hipErrorInvalidValue;
+    }
   }
-  if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 128) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 256) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-  return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+  switch (sh.slots) {
+    case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 4: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 8: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    default: return hipErrorInvalidValue;
+  }
 }
 template <int METRIC, int D16>
-static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const void *rows = nullptr) {
-  if (a.k == a.ef) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
-    if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
-    return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FastShape &sh,
+                                 const void *rows = nullptr) {
+  if (sh.wb) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
+    switch (sh.slots) {
+      case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+      case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+      default: return hipErrorInvalidValue;
+    }
   }
-  if (a.ef <= 64) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 128) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-  if (a.ef <= 256) return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-  return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+  switch (sh.slots) {
+    case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 4: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 8: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 #if HS_TU_ROWS == 0
@@ -1532,38 +1548,52 @@ hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds,
 #endif
 #if HS_TU_HAS_L2
 hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  if (ix.has_deleted || f) {   // a filter set is planned as delete marks are
-    if (ix.dim == 128) return launch_fast_del<METRIC_L2, 8>(ix, a, lds, stream, nullptr, f);
-    return (ix.dim & 15u) ? launch_fast_del<METRIC_L2, -1>(ix, a, lds, stream, nullptr, f) : launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, nullptr, f);
+  const bool bare = !(ix.has_deleted || f);   // a filter set is planned as delete marks are
+  const FastShape sh = fast_shape(METRIC_L2, ix.dim, a.ef, a.k, bare);
+  if (!bare) {
+    switch (sh.d16) {
+      case 8: return launch_fast_del<METRIC_L2, 8>(ix, a, lds, stream, sh, nullptr, f);
+      case -1: return launch_fast_del<METRIC_L2, -1>(ix, a, lds, stream, sh, nullptr, f);
+      case 0: return launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, sh, nullptr, f);
+      default: return hipErrorInvalidValue;
+    }
   }
-  // compile-time dims for the common shapes (the runtime-dim kernel is 1.15-1.7x slower: measured at d=64 and on DEEP-10M, d=96)
-  switch (ix.dim) {
-    case 128: return launch_fast_md<METRIC_L2, 8>(ix, a, lds, stream);    // SIFT
-    case 96: return launch_fast_md<METRIC_L2, 6>(ix, a, lds, stream);     // DEEP
-    case 960: return launch_fast_md<METRIC_L2, 60>(ix, a, lds, stream);   // GIST
-    case 768: return launch_fast_md<METRIC_L2, 48>(ix, a, lds, stream);
-    case 256: return launch_fast_md<METRIC_L2, 16>(ix, a, lds, stream);
-    case 64: return launch_fast_md<METRIC_L2, 4>(ix, a, lds, stream);
-    case 512: return launch_fast_md<METRIC_L2, 32>(ix, a, lds, stream);
-    case 1024: return launch_fast_md<METRIC_L2, 64>(ix, a, lds, stream);
-    // GloVe-100-like: the 4-lane recipes with the dim compiled in (the 25 steps unroll without spills; at 200 / 300 the
-    // unrolled loads spill 80 / 250 B per lane, so those stay on the runtime-dim kernel)
-    case 100: return launch_fast_md<METRIC_L2, -25>(ix, a, lds, stream);
-    default: return (ix.dim & 15u) ? launch_fast_md<METRIC_L2, -1>(ix, a, lds, stream) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream);
+  switch (sh.d16) {   // compile-time dims for the common shapes: the table is fast_shape's
+    case 8: return launch_fast_md<METRIC_L2, 8>(ix, a, lds, stream, sh);    // SIFT
+    case 6: return launch_fast_md<METRIC_L2, 6>(ix, a, lds, stream, sh);    // DEEP
+    case 60: return launch_fast_md<METRIC_L2, 60>(ix, a, lds, stream, sh);  // GIST
+    case 48: return launch_fast_md<METRIC_L2, 48>(ix, a, lds, stream, sh);
+    case 16: return launch_fast_md<METRIC_L2, 16>(ix, a, lds, stream, sh);
+    case 4: return launch_fast_md<METRIC_L2, 4>(ix, a, lds, stream, sh);
+    case 32: return launch_fast_md<METRIC_L2, 32>(ix, a, lds, stream, sh);
+    case 64: return launch_fast_md<METRIC_L2, 64>(ix, a, lds, stream, sh);
+    case -25: return launch_fast_md<METRIC_L2, -25>(ix, a, lds, stream, sh);   // d = 100, the 4-lane recipes
+    case -1: return launch_fast_md<METRIC_L2, -1>(ix, a, lds, stream, sh);
+    case 0: return launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, sh);
+    default: return hipErrorInvalidValue;
   }
 }
 #endif
 #if HS_TU_HAS_IP
 hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  if (ix.has_deleted || f)
-    return (ix.dim & 15u) ? launch_fast_del<METRIC_IP, -1>(ix, a, lds, stream, nullptr, f) : launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, nullptr, f);
-  switch (ix.dim) {   // text / image embeddings
-    case 768: return launch_fast_md<METRIC_IP, 48>(ix, a, lds, stream);    // COHERE
-    case 512: return launch_fast_md<METRIC_IP, 32>(ix, a, lds, stream);
-    case 1024: return launch_fast_md<METRIC_IP, 64>(ix, a, lds, stream);
-    case 1536: return launch_fast_md<METRIC_IP, 96>(ix, a, lds, stream);
-    case 100: return launch_fast_md<METRIC_IP, -25>(ix, a, lds, stream);   // GloVe-100-angular-like, as for L2
-    default: return (ix.dim & 15u) ? launch_fast_md<METRIC_IP, -1>(ix, a, lds, stream) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream);
+  const bool bare = !(ix.has_deleted || f);
+  const FastShape sh = fast_shape(METRIC_IP, ix.dim, a.ef, a.k, bare);
+  if (!bare) {
+    switch (sh.d16) {
+      case -1: return launch_fast_del<METRIC_IP, -1>(ix, a, lds, stream, sh, nullptr, f);
+      case 0: return launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, sh, nullptr, f);
+      default: return hipErrorInvalidValue;
+    }
+  }
+  switch (sh.d16) {   // text / image embeddings
+    case 48: return launch_fast_md<METRIC_IP, 48>(ix, a, lds, stream, sh);    // COHERE
+    case 32: return launch_fast_md<METRIC_IP, 32>(ix, a, lds, stream, sh);
+    case 64: return launch_fast_md<METRIC_IP, 64>(ix, a, lds, stream, sh);
+    case 96: return launch_fast_md<METRIC_IP, 96>(ix, a, lds, stream, sh);
+    case -25: return launch_fast_md<METRIC_IP, -25>(ix, a, lds, stream, sh);   // d = 100, as for L2
+    case -1: return launch_fast_md<METRIC_IP, -1>(ix, a, lds, stream, sh);
+    case 0: return launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, sh);
+    default: return hipErrorInvalidValue;
   }
 }
 #endif
@@ -1578,7 +1608,9 @@ hipError_t HS_NARROW_FN(launch_strict, l2)(const DevIndex &ix, const SearchArgs 
   return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG);
 }
 hipError_t HS_NARROW_FN(launch_fast, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return (ix.has_deleted || f) ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, rows, f) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, rows);
+  const bool bare = !(ix.has_deleted || f);   // (the narrow objects hold the runtime-dim distance pass only: slots and wb of the shape)
+  const FastShape sh = fast_shape(METRIC_L2, ix.dim, a.ef, a.k, bare);
+  return !bare ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, sh, rows, f) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, sh, rows);
 }
 #endif
 #if HS_TU_HAS_IP
@@ -1586,7 +1618,9 @@ hipError_t HS_NARROW_FN(launch_strict, ip)(const DevIndex &ix, const SearchArgs 
   return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG);
 }
 hipError_t HS_NARROW_FN(launch_fast, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return (ix.has_deleted || f) ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, rows, f) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, rows);
+  const bool bare = !(ix.has_deleted || f);
+  const FastShape sh = fast_shape(METRIC_IP, ix.dim, a.ef, a.k, bare);
+  return !bare ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, sh, rows, f) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, sh, rows);
 }
 #endif
 #endif

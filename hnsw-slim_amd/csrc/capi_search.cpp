@@ -166,6 +166,16 @@ hs_status hs_debug_plan_input(const hs_index *ix, size_t k, size_t nq, int has_f
   return HS_OK;
 }
 
+hs_status hs_debug_fast_shape(int metric, uint64_t dim, uint64_t ef, uint64_t k, int bare, hs_fast_shape *out) {
+  if (!out) return fail(HS_ERR_INVALID, "null argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  const uint64_t run_ef = std::max(ef, k);   // the search runs with max(ef, k)
+  if (dim == 0 || dim > UINT32_MAX || run_ef == 0 || run_ef > 512) return fail(HS_ERR_INVALID, "no fast-kernel shape: dim = 0 or max(ef, k) outside 1..512");
+  const FastShape s = fast_shape(metric, (uint32_t)dim, (uint32_t)run_ef, (uint32_t)k, bare != 0);
+  out->d16 = s.d16; out->slots = s.slots; out->wb = s.wb;
+  return HS_OK;
+}
+
 hs_status hs_debug_heap_ops(const uint32_t *ops, size_t n_ops, int wave_pop, uint32_t lds_slots, uint32_t *out_heap, uint32_t *out_pops,
                             uint32_t *out_n) {
   if (!ops || !out_heap || !out_pops || !out_n) return fail(HS_ERR_INVALID, "null argument");

@@ -93,6 +93,16 @@ size_t fast_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t has
 // Fast path availability for this shape (level-0 tile present, threshold_level == 0, k < ef <= 512).  has_filter: the search
 // names a filter set, which counts as delete marks do (the !bare_bone branches).
 bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k, bool has_filter = false);
+// Which instantiation of the fast kernel answers a call that fast_supported() admits: the one table launch_fast_l2 / _ip / _del /
+// _md dispatch on (search_plan.cpp; host only, no HIP call; hs_debug_fast_shape hands it out).
+//   d16  : the distance pass over fp32 rows -- dim / 16 compiled in (> 0), -dim / 4 for a compiled-in dim % 4 == 0 shape off the
+//          SIMD16 path (< -1), 0 = runtime dim with dim % 16 == 0, -1 = any runtime dim.  (The narrow objects hold the d16 = 0
+//          shapes only and take slots / wb from here.)
+//   slots: result-set entries per lane S = 1 | 2 | 4 | 8 for ef <= 64 | 128 | 256 | 512
+//   wb   : ef == k on a bare index: the variant that watches ties across the capacity boundary (S <= 2)
+// bare = no delete marks and no filter set (the reference's bare_bone_search).
+struct FastShape { int32_t d16, slots, wb; };
+FastShape fast_shape(int metric, uint32_t dim, uint32_t ef, uint32_t k, bool bare);
 
 // Strict kernel: the reference's result/candidate arrays with libstdc++ heap mechanics, reference
 // output order.  Fast kernel: same traversal and candidate mechanics, result set kept as a sorted

@@ -42,6 +42,34 @@ const char *kernel_name(int family, int rows) {
   return names[family][rows];
 }
 
+// The fast kernel's shape table (engine.hpp FastShape): every (metric, dim) with a distance pass compiled for it, the runtime-dim
+// shapes for the rest.  A line here and the `case` of the launcher that names the same d16 (beam_search.hip) come and go together:
+// a d16 without its case is refused at launch, and tests/test_search_plan_cpu.py holds this table to the instantiations built.
+FastShape fast_shape(int metric, uint32_t dim, uint32_t ef, uint32_t k, bool bare) {
+  FastShape s{};
+  s.d16 = (dim & 15u) ? -1 : 0;
+  if (!bare) {   // delete marks / a filter set: the runtime-dim shapes and d = 128 (SIFT) for L2
+    if (metric == HS_METRIC_L2 && dim == 128) s.d16 = 8;
+  } else if (metric == HS_METRIC_L2) {
+    switch (dim) {   // (the runtime-dim kernel is 1.15-1.7x slower: measured at d=64 and on DEEP-10M, d=96)
+      case 64: case 96: case 128: case 256: case 512: case 768: case 960: case 1024: s.d16 = (int32_t)(dim / 16); break;   // 96: DEEP, 128: SIFT, 960: GIST
+      // GloVe-100-like: the 4-lane recipes with the dim compiled in (the 25 steps unroll without spills; at 200 / 300 the
+      // unrolled loads spill 80 / 250 B per lane, so those stay on the runtime-dim kernel)
+      case 100: s.d16 = -25; break;
+      default: break;
+    }
+  } else {
+    switch (dim) {   // text / image embeddings
+      case 512: case 768: case 1024: case 1536: s.d16 = (int32_t)(dim / 16); break;   // 768: COHERE
+      case 100: s.d16 = -25; break;   // GloVe-100-angular-like, as for L2
+      default: break;
+    }
+  }
+  s.slots = ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 256 ? 4 : 8;
+  s.wb = bare && k == ef;   // nothing is selected at the end (compiled for S <= 2: fast_supported admits ef == k to 128 only)
+  return s;
+}
+
 namespace {
 
 struct Shape {

@@ -362,6 +362,14 @@ typedef struct hs_plan_out {
 hs_status hs_debug_search_plan(const hs_plan_in *in, hs_plan_out *out);
 /* Fills *in from a live index and the process's knobs, through the function every search launch uses. */
 hs_status hs_debug_plan_input(const hs_index *ix, size_t k, size_t nq, int has_filter, int want_raw, hs_plan_in *in);
+/* Parity/debug entry, host only: which instantiation of the fast kernel (hs::fast_kernel) a call launches once the plan names that
+ * family -- the table the launchers themselves dispatch on (csrc/engine.hpp fast_shape).  bare: no delete marks and no filter set.
+ * d16: the distance pass over fp32 rows, dim / 16 compiled in (> 0) or -dim / 4 for a compiled-in dim off the 16-wide path (< -1);
+ * 0 / -1 are the runtime-dim shapes for dim % 16 == 0 / any dim (the narrow-row twins run 0 at every dim).  slots: result-set
+ * entries per lane, 1 | 2 | 4 | 8 for ef <= 64 | 128 | 256 | 512.  wb: the ef == k variant that watches ties across the capacity
+ * boundary.  HS_ERR_INVALID for a bad metric, dim = 0 or max(ef, k) beyond 512 (no fast shape). */
+typedef struct hs_fast_shape { int32_t d16, slots, wb; } hs_fast_shape;
+hs_status hs_debug_fast_shape(int metric, uint64_t dim, uint64_t ef, uint64_t k, int bare, hs_fast_shape *out);
 
 /* Host pointers, asynchronous: H2D of the queries, the search and D2H of the requested outputs are enqueued on `stream`
  * and nothing is valid until that stream is synchronised (hs_search_check does it and reports capacity problems).  The

@@ -342,6 +342,8 @@ struct Counters {
   uint32_t n_nbr = 0;       // neighbour ids scanned (visited or not)
   uint32_t n_accept = 0;    // candidates pushed into the candidate heap
   uint32_t max_cand = 0;    // peak size of the candidate heap
+  uint32_t n_tie_evict = 0; // level-0 evictions from a full result heap whose key equals the new worst kept one: which of the
+                            // equal entries stays is then decided by the heap's layout (test premise, not a reference quantity)
 };
 
 struct cmp_max { bool operator()(const pairfi &a, const pairfi &b) const { return a.first < b.first; } };  // slim.h:169-175
@@ -397,6 +399,7 @@ inline void beam_level0(const Index &ix, const float *q, size_t ef, bool bare_bo
         }
         while (s.top.size() > ef) {                                // :434-448
           std::pop_heap(s.top.begin(), s.top.end(), cmp_max());
+          if (s.top.size() > 1 && s.top.back().first == s.top.front().first) c.n_tie_evict++;
           s.top.pop_back();
         }
         if (!s.top.empty()) lowerBound = s.top.front().first;      // :450-452

@@ -121,6 +121,35 @@ int hso_search_pq(void *p, const float *q, size_t nq, size_t k, float *out_d, ui
   return rc;
 }
 
+// Test premise, not a reference quantity: per query, the level-0 evictions from a full result heap whose key equals the new worst
+// kept key (Counters::n_tie_evict) -- the event an ef == k search's answer hangs on.  pq = 0: the (q, k, tableint*) overload of a
+// Slim index, 1: the priority_queue overloads (either kind).  out: nq u32.
+int hso_tie_evictions(void *p, const float *q, size_t nq, size_t k, int pq, uint32_t *out, int threads) {
+  auto *h = (Handle *)p;
+  int rc = 0;
+  if (!pq && h->kind == 0) { g_err = "hso_tie_evictions: the id-array overload exists on Slim indexes only"; return 1; }
+  size_t dim = h->kind == 0 ? h->v.dim : h->s.dim;
+#pragma omp parallel num_threads(threads > 0 ? threads : 1)
+  {
+    Scratch s;
+    std::vector<std::pair<float, uint64_t>> res;
+    std::vector<uint32_t> ids(k);
+#pragma omp for schedule(dynamic, 16)
+    for (long i = 0; i < (long)nq; i++) {
+      try {
+        SlimResult r = !pq ? slim_search_ids(h->s, q + i * dim, k, s, ids.data())
+                       : h->kind == 0 ? vanilla_search_pq(h->v, q + i * dim, k, s, res)
+                                      : slim_search_pq(h->s, q + i * dim, k, s, res, h->mark_ep != 0);
+        out[i] = r.c.n_tie_evict;
+      } catch (std::exception &e) {
+#pragma omp critical
+        { g_err = e.what(); rc = 1; }
+      }
+    }
+  }
+  return rc;
+}
+
 int hso_dist(int metric, const float *a, const float *b, size_t n, size_t d, float *out) {
   try {
     for (size_t i = 0; i < n; i++) out[i] = dist((Metric)metric, a + i * d, b + i * d, d);

@@ -165,6 +165,7 @@ class Oracle:
         L.hso_slim_search_ids.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_int]
         L.hso_search_pq.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_int]
         L.hso_dist.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]
+        L.hso_tie_evictions.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_int]
         L.hso_brute_force.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_int]
         sz, dbl, ci = ctypes.c_size_t, ctypes.c_double, ctypes.c_int
         fl = ctypes.c_float
@@ -374,6 +375,15 @@ class OracleIndex:
         if rc:
             raise RuntimeError(self.o.err())
         return dict(labels=out, raw_d=rd, raw_i=ri, raw_sz=rs, counters=cn)
+
+    def tie_evictions(self, q, k, pq, threads=1):
+        """Per query, the evictions from a full result heap whose key equals the new worst kept key, in search_pq (pq=True) or
+        search_ids (pq=False, Slim only): what an ef == k search's answer hangs on (a test premise, not a reference quantity)."""
+        q = np.ascontiguousarray(q, np.float32)
+        out = np.zeros(q.shape[0], np.uint32)
+        if self.o.L.hso_tie_evictions(self.h, q.ctypes.data, q.shape[0], k, 1 if pq else 0, out.ctypes.data, threads):
+            raise RuntimeError(self.o.err())
+        return out
 
     def search_pq(self, q, k, threads=1):
         """priority_queue-returning searchKnn (vanilla or slim): pop order, farthest first."""

@@ -127,7 +127,9 @@ def test_slim_filtered_verbatim_vs_compiled_reference(hs, oracle, tmp_path):
     assert compared >= 0.5 * len(entry_ok) * len(g["efs"])
 
 
-def _slim_case(hs, oracle, tmp_path, base, queries, dim, metric, M, efC, efs, k=10, threads=8, fast=True, **slim_kw):
+def _slim_case(hs, oracle, tmp_path, base, queries, dim, metric, M, efC, efs, k=10, threads=8, fast=True, kernel=None, **slim_kw):
+    """kernel: the family every default-mode call of the case must run (hs_last_kernel), for the callers that name one; under
+    set_exact_order(True) that is hs::strict_kernel for every caller."""
     hp, sp = str(tmp_path / "h.bin"), str(tmp_path / "s.bin")
     hs.build_hnsw(base, hp, metric=metric, M=M, ef_construction=efC, threads=threads)
     hs.convert_slim(hp, sp, dim, metric=metric, threads=threads, **slim_kw)
@@ -140,9 +142,11 @@ def _slim_case(hs, oracle, tmp_path, base, queries, dim, metric, M, efC, efs, k=
         # --- strict kernel: the reference's array ORDER, raw heap arrays, counters ---
         ix.set_exact_order(True)
         r = ix.search_ids(queries, k, want_dists=True, want_stats=True)
+        assert ix.last_kernel() == "hs::strict_kernel", f"ef={ef}: exact order ran {ix.last_kernel()}"
         assert np.array_equal(r["labels"], o["labels"]), f"ef={ef}: labels differ from searchKnn(q,k,tableint*)"
         assert np.array_equal(r["stats"][:, :3], o["counters"][:, :3]), f"ef={ef}: counters differ"
         raw = ix.search_raw(queries, k)
+        assert ix.last_kernel() == "hs::strict_kernel", f"ef={ef}: search_raw ran {ix.last_kernel()}"
         assert np.array_equal(raw["raw_sz"], o["raw_sz"])
         cap = max(ef, k)
         mask = np.arange(cap)[None, :] < raw["raw_sz"][:, None]
@@ -151,11 +155,13 @@ def _slim_case(hs, oracle, tmp_path, base, queries, dim, metric, M, efC, efs, k=
         # priority_queue overload (marks the enter point visited first)
         op = ox.search_pq(queries, k, threads=8)
         rp = ix.search_pq(queries, k)
+        assert ix.last_kernel() == "hs::strict_kernel", f"ef={ef}: exact order (q, k) ran {ix.last_kernel()}"
         assert np.array_equal(rp["cnt"], op["cnt"])
         assert _pq_sorted(rp["dists"], rp["labels"], rp["cnt"]) == _pq_sorted(op["dists"], op["labels"], op["cnt"])
-        # --- default (fast kernel + tie re-runs): identical k-subset per query, sorted by distance ---
+        # --- default (the planned kernel + tie replays): identical k-subset per query, sorted by distance ---
         ix.set_exact_order(False)
         f = ix.search_ids(queries, k, want_dists=True, want_stats=True)
+        assert kernel is None or ix.last_kernel() == kernel, f"ef={ef}: default mode ran {ix.last_kernel()}, not {kernel}"
         assert np.array_equal(np.sort(f["labels"], axis=1), np.sort(o["labels"], axis=1)), f"ef={ef}: fast-path id sets differ"
         assert np.array_equal(f["stats"][:, :3], o["counters"][:, :3]), f"ef={ef}: fast-path counters differ"
         first_pass = f["stats"][:, 3] == 0
@@ -163,6 +169,7 @@ def _slim_case(hs, oracle, tmp_path, base, queries, dim, metric, M, efC, efs, k=
             assert np.all(np.diff(f["dists"][first_pass], axis=1) >= 0)
         assert np.array_equal(np.sort(f["dists"], axis=1).view(np.uint32), np.sort(r["dists"], axis=1).view(np.uint32))
         fp = ix.search_pq(queries, k)
+        assert kernel is None or ix.last_kernel() == kernel, f"ef={ef}: default mode (q, k) ran {ix.last_kernel()}, not {kernel}"
         assert _pq_sorted(fp["dists"], fp["labels"], fp["cnt"]) == _pq_sorted(op["dists"], op["labels"], op["cnt"])
     return ix, ox
 
@@ -187,29 +194,34 @@ def test_slim_from_golden_index(hs, oracle, tmp_path):
 
 
 def test_slim_sift_like_d128(hs, oracle, tmp_path):
+    """SIFT-shaped rows, k = 10, ef 32..256: strict kernel under exact order, the flat kernel by default (k <= 64 on a bare index with
+    dim % 16 == 0; the fast kernel's d = 128 shape is tests/test_gpu_fast_shapes.py's)."""
     base = mixture(20000, 128, 21, n_clusters=64, integer=True)
     q = mixture(400, 128, 22, n_clusters=64, integer=True)
-    _slim_case(hs, oracle, tmp_path, base, q, 128, L2, 16, 200, [32, 64, 128, 256])
+    _slim_case(hs, oracle, tmp_path, base, q, 128, L2, 16, 200, [32, 64, 128, 256], kernel="hs::flat_kernel")
 
 
 def test_slim_continuous_d96(hs, oracle, tmp_path):
+    """DEEP-shaped continuous rows, k = 10: strict kernel under exact order, the flat kernel by default."""
     base = mixture(8000, 96, 23, lo=-1, hi=1, sigma=0.3)
     q = mixture(200, 96, 24, lo=-1, hi=1, sigma=0.3)
-    _slim_case(hs, oracle, tmp_path, base, q, 96, L2, 16, 100, [16, 64])
+    _slim_case(hs, oracle, tmp_path, base, q, 96, L2, 16, 100, [16, 64], kernel="hs::flat_kernel")
 
 
 def test_slim_gist_like_d960(hs, oracle, tmp_path):
+    """GIST-shaped rows (3.8 KB each), k = 10: strict kernel under exact order, the flat kernel by default."""
     base = np.clip(mixture(3000, 960, 25, lo=0.2, hi=0.8, sigma=0.08), 0, 1)
     q = np.clip(mixture(64, 960, 26, lo=0.2, hi=0.8, sigma=0.08), 0, 1)
-    _slim_case(hs, oracle, tmp_path, base, q, 960, L2, 16, 100, [64])
+    _slim_case(hs, oracle, tmp_path, base, q, 960, L2, 16, 100, [64], kernel="hs::flat_kernel")
 
 
 def test_slim_ip_d768(hs, oracle, tmp_path):
+    """COHERE-shaped unit vectors under the inner product, k = 10: strict kernel under exact order, the flat kernel by default."""
     base = mixture(3000, 768, 27, lo=-1, hi=1, sigma=0.5)
     q = mixture(64, 768, 28, lo=-1, hi=1, sigma=0.5)
     base /= np.linalg.norm(base, axis=1, keepdims=True)
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    _slim_case(hs, oracle, tmp_path, base.astype(np.float32), q.astype(np.float32), 768, IP, 16, 100, [64])
+    _slim_case(hs, oracle, tmp_path, base.astype(np.float32), q.astype(np.float32), 768, IP, 16, 100, [64], kernel="hs::flat_kernel")
 
 
 def test_slim_threshold_level(hs, oracle, tmp_path):
@@ -247,14 +259,16 @@ def test_k_larger_than_ef_and_k_equals_n(hs, oracle, tmp_path):
 
 @pytest.mark.parametrize("dim,metric", [(64, L2), (512, L2), (1024, L2), (512, IP), (1024, IP), (1536, IP), (160, L2), (384, IP)])
 def test_slim_compiled_in_and_runtime_dims(hs, oracle, tmp_path, dim, metric):
-    """dim % 16 == 0 shapes: the ones with their own kernel instantiation (64, 512, 1024 / IP 512, 1024, 1536) and two that
-    take the runtime-dim kernel (160, 384)."""
+    """dim % 16 == 0 shapes at k = 10, ef <= 200: the strict kernel under exact order and, by default, the flat kernel -- dims its
+    long-row path treats apart (512, 1024, 1536) next to ordinary ones.  The fast kernel has a distance pass of its own for 64, 512,
+    1024 / IP 512, 1024, 1536 and none for 160, 384, but a bare index reaches it from k = 65 only: those shapes are run by
+    tests/test_gpu_fast_shapes.py."""
     base = mixture(2500, dim, 71, lo=-1, hi=1, sigma=0.5)
     q = mixture(60, dim, 72, lo=-1, hi=1, sigma=0.5)
     if metric == IP:
         base /= np.linalg.norm(base, axis=1, keepdims=True)
         q /= np.linalg.norm(q, axis=1, keepdims=True)
-    _slim_case(hs, oracle, tmp_path, base.astype(np.float32), q.astype(np.float32), dim, metric, 16, 100, [32, 100, 200])
+    _slim_case(hs, oracle, tmp_path, base.astype(np.float32), q.astype(np.float32), dim, metric, 16, 100, [32, 100, 200], kernel="hs::flat_kernel")
 
 
 @pytest.mark.parametrize("dim", (100, 200, 300, 70, 36, 12))
@@ -373,24 +387,32 @@ def test_cpp_facade_matches_oracle(hs, oracle, tmp_path):
 
 def test_ef_equal_k_on_the_fast_kernel(hs, oracle, tmp_path):
     """The reference's defaults (ef_ = 10, K = 10): ef == k, nothing is selected at the end, so ties across the
-    capacity boundary decide the answer -- the fast kernel must notice them and replay (tie-heavy integer data)."""
+    capacity boundary decide the answer -- the kernel must notice them and replay (tie-heavy integer data).  Up to k = 64 a bare
+    index with dim % 16 == 0 is the flat kernel's: (10, 10), (5, 32), (64, 64).  (100, 100) and (128, 128) run the fast kernel's
+    boundary-watching variant (every query of the golden index returns 128), and must replay on their own."""
     g = np.load(os.path.join(GOLDEN, "l2_int_d16.npz"))
     sp = str(tmp_path / "s.bin")
     hs.convert_slim(os.path.join(GOLDEN, "l2_int_d16.hnsw.bin"), sp, 16)
     ix = hs.Index(sp, hs.HS_KIND_SLIM, 16)
     ox = oracle.load(sp, "slim", L2, 16)
-    replays = 0
-    for ef, k in ((10, 10), (5, 32), (64, 64)):
+    replays = {"hs::flat_kernel": 0, "hs::fast_kernel": 0}
+    for ef, k, kernel in ((10, 10, "hs::flat_kernel"), (5, 32, "hs::flat_kernel"), (64, 64, "hs::flat_kernel"),
+                          (100, 100, "hs::fast_kernel"), (128, 128, "hs::fast_kernel")):
         ix.set_ef(ef); ox.set_ef(ef)
         want = ox.search_ids(g["queries"], k)
         ok = want["raw_sz"] >= k
+        if kernel == "hs::fast_kernel":
+            assert ok.all(), (ef, k)
         got = ix.search_ids(g["queries"], k, want_stats=True)
+        assert ix.last_kernel() == kernel, (ef, k, ix.last_kernel())
         assert np.array_equal(np.sort(got["labels"][ok], axis=1), np.sort(want["labels"][ok], axis=1)), (ef, k)
         assert np.array_equal(got["stats"][:, :3], want["counters"][:, :3])
-        replays += int((got["stats"][:, 3] == 1).sum())
+        replays[kernel] += int((got["stats"][:, 3] == 1).sum())
         wp, gp = ox.search_pq(g["queries"], k), ix.search_pq(g["queries"], k)
+        assert ix.last_kernel() == kernel, (ef, k, ix.last_kernel())
         assert _pq_sorted(gp["dists"], gp["labels"], gp["cnt"]) == _pq_sorted(wp["dists"], wp["labels"], wp["cnt"])
-    assert replays > 0, "expected boundary ties on this data"
+    assert replays["hs::flat_kernel"] > 0, "expected boundary ties on this data"
+    assert replays["hs::fast_kernel"] > 0, "expected boundary ties on this data at (100, 100) and (128, 128) alone"
 
 
 def test_large_batch_runs_as_launch_groups(hs, oracle, tmp_path):

@@ -1,6 +1,7 @@
 """The launch plan of a search batch (csrc/search_plan.cpp) through hs_debug_search_plan: which kernel serves pass 0 for every
 combination of index state, call and diagnostic knob, the invariants every plan keeps, and the numbers of the bench shapes
-pinned to recorded values.  Host only: no device is needed to make a plan."""
+pinned to recorded values; and the fast kernel's shape table (hs_debug_fast_shape) against the documented compiled dims and the
+instantiations the build holds.  Host only: no device is needed to make a plan."""
 import json
 import os
 
@@ -136,3 +137,87 @@ def test_flat_plan_is_the_earlier_hook_s():
         p = plan(n=g["n"], ef=g["ef"], nq=g["nq"])
         got = dict(nb=p["fl_nb"], mul=p["fl_mul"], sh=p["fl_sh"], bits=p["fl_bits"], ok=p["fl_ok"])
         assert got == {k: g[k] for k in got}, (g, p)
+
+
+# ---- the fast kernel's shape table (csrc/search_plan.cpp fast_shape, hs_debug_fast_shape) --------------------------------------------
+L2, IP = 0, 1
+# DESIGN.md 4a / the comments of fast_shape: dim -> d16 of every distance pass compiled for a bare index, and for one with delete
+# marks or under a filter set
+COMPILED = {(L2, True): {64: 4, 96: 6, 128: 8, 256: 16, 512: 32, 768: 48, 960: 60, 1024: 64, 100: -25},
+            (IP, True): {512: 32, 768: 48, 1024: 64, 1536: 96, 100: -25},
+            (L2, False): {128: 8},
+            (IP, False): {}}
+# ef classes of the slots per lane, at both ends of each; k = ef where the plan admits the fast kernel with it (bare, ef <= 128)
+EF_SLOTS = [(1, 1), (64, 1), (65, 2), (128, 2), (129, 4), (256, 4), (257, 8), (512, 8)]
+
+
+def fast_shape(metric, dim, ef, k, bare=True):
+    return hs.debug_fast_shape(metric, dim, ef, k, bare)
+
+
+def fast_shapes_reachable():
+    """Every (metric, slots, d16, wb, bare) fast_shape returns over dims 4..1600 for a call the plan hands to the fast kernel:
+    ef > k, or ef == k <= 128 on a bare index (beam_search.hip fast_supported)."""
+    out = set()
+    for metric in (L2, IP):
+        for bare in (True, False):
+            for dim in range(4, 1601):
+                for ef, _ in EF_SLOTS:
+                    for k in ([ef - 1] if ef > 1 else []) + ([ef] if bare and ef <= 128 else []):
+                        s = fast_shape(metric, dim, ef, k, bare)
+                        out.add((metric, s["slots"], s["d16"], s["wb"], int(bare)))
+    return out
+
+
+def test_fast_shape_compiled_dims_are_the_documented_ones():
+    for (metric, bare), table in COMPILED.items():
+        got = {}
+        for dim in range(4, 1601):
+            d16 = fast_shape(metric, dim, 100, 10, bare)["d16"]
+            if d16 not in (0, -1):
+                got[dim] = d16
+                assert (d16 > 0 and 16 * d16 == dim) or (d16 < -1 and dim % 16 != 0 and -4 * d16 == dim), (metric, bare, dim, d16)
+            else:
+                assert d16 == (0 if dim % 16 == 0 else -1), (metric, bare, dim, d16)
+        assert got == table, (metric, bare)
+    # the distance pass is a property of (metric, dim, bare) alone
+    for metric, dim in ((L2, 128), (L2, 100), (IP, 768), (L2, 160), (IP, 77)):
+        for bare in (True, False):
+            assert len({fast_shape(metric, dim, ef, k, bare)["d16"] for ef, _ in EF_SLOTS for k in (1, ef)}) == 1
+
+
+def test_fast_shape_slots_and_boundary_watch_follow_ef_and_k():
+    for metric, dim in ((L2, 128), (L2, 100), (L2, 160), (L2, 33), (IP, 768), (IP, 384)):
+        for bare in (True, False):
+            for ef in range(1, 513):
+                want = 1 if ef <= 64 else 2 if ef <= 128 else 4 if ef <= 256 else 8
+                for k in {1, max(ef - 1, 1), ef}:
+                    s = fast_shape(metric, dim, ef, k, bare)
+                    assert s["slots"] == want and s["wb"] == int(bare and k == ef), (metric, dim, bare, ef, k, s)
+            # the search runs with max(ef, k)
+            assert fast_shape(metric, dim, 10, 100, bare) == fast_shape(metric, dim, 100, 100, bare)
+    for bad in (dict(metric=2), dict(dim=0), dict(ef=513), dict(k=600)):
+        kw = dict(dict(metric=L2, dim=128, ef=100, k=10), **bad)
+        with pytest.raises(hs.HsError) as e:
+            fast_shape(kw["metric"], kw["dim"], kw["ef"], kw["k"])
+        assert e.value.status == hs.HS_ERR_INVALID
+
+
+def test_fast_shape_table_is_the_set_of_instantiations_built():
+    """The launchers of beam_search.hip dispatch on fast_shape and instantiate one kernel per `case`; the compiler's resource
+    report lists every instantiation of the build.  The two sets are equal: a case added to or dropped from a launcher without the
+    table changing (or the reverse) shows as a kernel nobody can launch, or as a shape the launcher refuses."""
+    import re
+
+    from test_f32_free_cpu import _report
+    built, filt = set(), set()
+    num = lambda s: -int(s[1:]) if s.startswith("n") else int(s)
+    for name in _report():
+        m = re.fullmatch(r"_ZN2hs11fast_kernelILi(\d)ELi(\d)ELi(n?\d+)ELb(\d)ELb(\d)EEEvNS_8DevIndexENS_10SearchArgsE(NS_10FilterArgsE)?", name)
+        if m:
+            shape = (int(m.group(1)), int(m.group(2)), num(m.group(3)), int(m.group(4)), int(m.group(5)))
+            (filt if m.group(6) else built).add(shape)
+    want = fast_shapes_reachable()
+    assert built == want, (sorted(built - want), sorted(want - built))
+    assert filt == {s for s in want if not s[4]}, "the filter-set overloads: every !bare shape and nothing else"
+    assert len(built) == 128 and len(filt) == 20
