@@ -29,7 +29,7 @@ __device__ __forceinline__ void bf_write_runs(const BfEntry *mine, const uint32_
   for (int t = 0; t < kQT; t++) {
     if (q0 + t >= nq) break;
     BfEntry *dst = partial + ((size_t)(q0 + t) * nruns + run) * k;
-    for (uint32_t i = lane; i < k; i += 64) dst[i] = i < msz[t] ? mine[(size_t)t * k + i] : BfEntry{FLT_MAX, 0xFFFFFFFFu, ~0ull};
+    for (uint32_t i = lane; i < k; i += 64) dst[i] = i < msz[t] ? mine[(size_t)t * k + i] : BfEntry{INFINITY, 0xFFFFFFFFu, ~0ull};
   }
 }
 
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(64 * kWaves) bf_scan_kernel(const float *base,
       const float d = lane4_reduce<METRIC>(acc[t], sub, owner);
       if (q0 + t >= nq) continue;
       const uint32_t sz = msz[t];
-      const float thr = sz < k ? FLT_MAX : mine[(size_t)t * k + k - 1].d;
+      const float thr = sz < k ? INFINITY : mine[(size_t)t * k + k - 1].d;   // a list that is not full admits +inf too
       bf_offer<2>(hs_ballot(act && owner && d <= thr), d, rb, labels, mine + (size_t)t * k, msz + t, k, lane);   // bruteforce.h:120 `dist <= lastdist`
     }
   }
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(64 * kWaves) bf_scan_general_kernel(const floa
       if (q0 + t >= nq) break;
       const float d = METRIC == METRIC_L2 ? l2_general(q + (size_t)t * dim, x, dim) : ip_general(q + (size_t)t * dim, x, dim);
       const uint32_t sz = msz[t];
-      const float thr = sz < k ? FLT_MAX : mine[(size_t)t * k + k - 1].d;
+      const float thr = sz < k ? INFINITY : mine[(size_t)t * k + k - 1].d;   // a list that is not full admits +inf too
       bf_offer<0>(hs_ballot(act && d <= thr), d, rb, labels, mine + (size_t)t * k, msz + t, k, lane);
     }
   }
@@ -135,7 +135,9 @@ __global__ void __launch_bounds__(64) bf_merge_kernel(const BfEntry *partial, ui
   for (int j = 0; j < 16; j++) head[j] = 0;
   uint32_t found = 0;
   for (uint32_t round = 0; round < k; round++) {
-    float bd = FLT_MAX;
+    // identity +inf, not FLT_MAX: a head whose distance overflowed to +inf is an entry like any other (bruteforce.h:120 keeps
+    // `inf <= inf`); a run's padding is told from it by the row id, never by the value
+    float bd = INFINITY;
     uint64_t bl = ~0ull;
     int bj = -1;
 #pragma unroll
@@ -146,7 +148,7 @@ __global__ void __launch_bounds__(64) bf_merge_kernel(const BfEntry *partial, ui
         if (e.row != 0xFFFFFFFFu && (bj < 0 || e.d < bd || (e.d == bd && e.label < bl))) { bd = e.d; bl = e.label; bj = j; }
       }
     }
-    const float md = wave_min_f32(bj >= 0 ? bd : FLT_MAX);
+    const float md = wave_min_f32<true>(bj >= 0 ? bd : INFINITY);
     unsigned long long m = hs_ballot(bj >= 0 && bd == md);
     if (!m) break;
     int win = __ffsll((long long)m) - 1;

@@ -114,7 +114,7 @@ __device__ __forceinline__ void exact_write_runs(const ExactScan &a, const Exact
     const uint32_t qi = s.slot_q[t];
     if (qi == kNoSlot) continue;
     BfEntry *dst = a.partial + ((size_t)qi * nruns + run) * a.k;
-    for (uint32_t i = lane; i < a.k; i += 64) dst[i] = i < msz[t] ? mine[(size_t)t * a.k + i] : BfEntry{FLT_MAX, 0xFFFFFFFFu, ~0ull};
+    for (uint32_t i = lane; i < a.k; i += 64) dst[i] = i < msz[t] ? mine[(size_t)t * a.k + i] : BfEntry{INFINITY, 0xFFFFFFFFu, ~0ull};
   }
 }
 
@@ -186,7 +186,7 @@ __device__ __forceinline__ void exact_scan_body(const ExactScan &a, unsigned cha
         const float d = lane4_reduce<METRIC>(acc[t], sub, owner);
         if (!((aw[t] >> h) & 0xFFFFu)) continue;   // (wave uniform)
         const uint32_t sz = msz[t];
-        const float thr = sz < k ? FLT_MAX : mine[(size_t)t * k + k - 1].d;
+        const float thr = sz < k ? INFINITY : mine[(size_t)t * k + k - 1].d;
         const bool adm = (aw[t] >> (h + grp)) & 1u;
         bf_offer<2>(hs_ballot(adm && owner && d <= thr), d, rb, a.labels, mine + (size_t)t * k, msz + t, k, lane);   // bruteforce.h:120 `dist <= lastdist`
       }
@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(64 * kWaves) exact_scan_general_kernel(const E
       if (!at) continue;   // (wave uniform)
       const float d = METRIC == METRIC_L2 ? l2_general(s.q + (size_t)t * dim, x, dim) : ip_general(s.q + (size_t)t * dim, x, dim);
       const uint32_t sz = msz[t];
-      const float thr = sz < k ? FLT_MAX : mine[(size_t)t * k + k - 1].d;
+      const float thr = sz < k ? INFINITY : mine[(size_t)t * k + k - 1].d;
       const bool adm = (at >> lane) & 1ull;
       bf_offer<0>(hs_ballot(adm && d <= thr), d, rb, a.labels, mine + (size_t)t * k, msz + t, k, lane);
     }

@@ -53,9 +53,13 @@ __device__ __forceinline__ uint32_t lds_cas(uint32_t *p, uint32_t expected, uint
 }
 
 // Minimum of v over the wave without touching LDS: inclusive min-scan inside each row of 16 lanes with DPP
-// row_shr, then the four row results (lanes 15/31/47/63) are combined through SGPRs.
+// row_shr, then the four row results (lanes 15/31/47/63) are combined through SGPRs.  Lanes a shift reads from outside
+// the row see FLT_MAX, so a wave whose values are all +inf gets FLT_MAX back: the graph kernels' keys are finite (the
+// search entries' contract) and keep that constant; INF_KEYS (the exhaustive scans' merge, whose keys may be +inf)
+// fills with +inf, the identity of min over every float.
+template <bool INF_KEYS = false>
 __device__ __forceinline__ float wave_min_f32(float v) {
-  const uint32_t inf = __float_as_uint(FLT_MAX);
+  const uint32_t inf = __float_as_uint(INF_KEYS ? INFINITY : FLT_MAX);
 #define HS_SHR_MIN(ctrl) v = fminf(v, __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)inf, (int)__float_as_uint(v), ctrl, 0xf, 0xf, false)))
   HS_SHR_MIN(0x111);  // row_shr:1
   HS_SHR_MIN(0x112);  // row_shr:2

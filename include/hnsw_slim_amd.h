@@ -237,7 +237,13 @@ hs_status hs_set_capacity(hs_index *ix, uint32_t cand_cap, uint32_t hash_slots);
  *                          0xFFFFFFFF / UINT64_MAX / +inf.
  *   stats (nullable): nq x 4 uint32 {n_dist, n_hops, n_nbr_read, pass}  (SURVEY.md 8d); pass = 0 first
  *                          pass, 1 tie re-run (strict kernel), 2 scratch-overflow re-run.
- * Synchronous: includes H2D of queries and D2H of results. */
+ * Synchronous: includes H2D of queries and D2H of results.
+ * Value range (every graph search entry: this one, the filtered, filter-set, async, device and SlimQ ones): rows and queries must
+ * be finite.  The answer is the reference's for every FINITE distance, over the whole fp32 range -- subnormal products, sums and
+ * distances are kept as the reference compiled without fast-math keeps them, inner-product distances may change sign inside one
+ * result set, magnitudes up to FLT_MAX (tests/test_gpu_value_range.py).  A distance that is not finite (an L2 sum or an inner
+ * product that overflows, a NaN) makes the outcome unspecified: the kernels use FLT_MAX and +inf as "no value", as the empty
+ * threshold and as reduction identities, and nothing on the hot path checks for it. */
 hs_status hs_search_batch(hs_index *ix, const float *queries, size_t nq, size_t k, int mode,
                           uint32_t *out_labels32, uint64_t *out_labels64, float *out_dists,
                           uint32_t *out_counts, uint32_t *stats);
@@ -460,7 +466,11 @@ hs_status hs_slimq_trace(hs_index *ix, const float *queries, size_t nq, size_t k
 /* ---- exhaustive k-NN (ground truth): hnswlib::BruteforceSearch::searchKnn, bruteforce.h:106-135, for a batch ------
  * Result per query: the k lexicographically smallest (dist, label) pairs -- what the reference's priority_queue of
  * pairs ends up holding whatever the scan order -- sorted ascending; distances by the same fp32 recipes as the
- * graph search.  labels NULL = row index.  dim <= 4096 (dim % 16 == 0 is the tuned kernel), k <= 64.  out_counts[q] = min(k, n). */
+ * graph search.  labels NULL = row index.  dim <= 4096 (dim % 16 == 0 is the tuned kernel), k <= 64.  out_counts[q] = min(k, n).
+ * Value range: rows and queries must be finite.  Every finite distance is the reference's, and so is an L2 distance that overflows
+ * to +inf: the reference keeps such a pair like any other (`inf <= inf`, bruteforce.h:120), so it is counted and returned, ordered
+ * by label among the +inf entries; a returned +inf with a label other than ~0 is an answer, the padding beyond out_counts[q] has
+ * label ~0.  Inner-product distances that overflow (non-finite or NaN) are outside the contract. */
 hs_status hs_brute_force(const float *base, size_t n, size_t dim, int metric, const uint64_t *labels, const float *queries,
                          size_t nq, size_t k, int device, uint64_t *out_labels, float *out_dists, uint32_t *out_counts);
 /* device pointers; synchronises `stream` before returning */
@@ -477,7 +487,7 @@ hs_status hs_brute_force_dev(const float *d_base, const uint64_t *d_labels, size
  * lexicographically smallest (dist, label) pairs, ascending; dist by the index's metric with the fp32 recipes of every other
  * path, label the external label.  out_labels64 / out_dists nq x k, ~0 / +inf beyond out_counts[q] (nullable).
  * Without a filter, on an index without delete marks, this is BruteforceSearch::searchKnn (bruteforce.h:106-135) over the index's
- * (row, label) pairs bit for bit.  With a filter it is deliberately NOT the reference's filtered overload: that code takes
+ * (row, label) pairs bit for bit, L2 distances that overflow to +inf included (the value range of hs_brute_force).  With a filter it is deliberately NOT the reference's filtered overload: that code takes
  * `lastdist` from a queue that may hold fewer than k entries (bruteforce.h:118-131) and then drops nearer allowed rows depending on
  * the scan order; the answer here is the exact one and does not depend on the order of the rows.
  * fs NULL iff filter_of_query NULL.  HS_ERR_INVALID before anything is launched: null arguments, fs without filter_of_query or the

@@ -61,6 +61,28 @@ def ip_odd_dims_fixture(tmp):
     np.savez_compressed(os.path.join(GOLDEN, "dist_ref_ip_odd.npz"), **out)
 
 
+RANGE_EXPONENTS = {"l2": (-70, 50, 62), "ip": (-70, 50)}
+
+
+def dist_range_fixture(tmp):
+    """The recipes at the edges of the fp32 range: the pairs of dist_ref.npz and dist_ref_ip_odd.npz times 2^s (an exact multiply;
+    the inputs are not stored again), s = -70 (L2: subnormal products and sums; IP: 1 - <a, b> with <a, b> far below an ulp of 1),
+    50 (values above 2^100) and, L2 only, 62 (squared differences overflow to +inf).  Holds `ref_hnsw dist` outputs alone, under
+    <metric>_<dim>_s<s>_ref."""
+    out = {}
+    for fname in ("dist_ref.npz", "dist_ref_ip_odd.npz"):
+        g = np.load(os.path.join(GOLDEN, fname))
+        for key in sorted(k for k in g.files if k.endswith("_a")):
+            metric, d = key.split("_")[:2]
+            for s in RANGE_EXPONENTS[metric]:
+                fa, fb, fo = (os.path.join(tmp, f"{x}.bin") for x in "abo")
+                write_fvecs(fa, g[f"{metric}_{d}_a"] * np.float32(2.0 ** s))
+                write_fvecs(fb, g[f"{metric}_{d}_b"] * np.float32(2.0 ** s))
+                run("dist", metric, fa, fb, fo)
+                out[f"{metric}_{d}_s{s}_ref"] = np.fromfile(fo, np.float32)
+    np.savez_compressed(os.path.join(GOLDEN, "dist_ref_range.npz"), **out)
+
+
 def index_fixture(tmp, name, metric, base, queries, M, efC, efs, k=10):
     fb, fq = os.path.join(tmp, "b.fvecs"), os.path.join(tmp, "q.fvecs")
     write_fvecs(fb, base)
@@ -256,6 +278,8 @@ def main():
                 rabitq_cent_fixture(tmp)
             if "rqhnsw" in only:
                 rq_hnsw_fixture(tmp)
+            if "range" in only:
+                dist_range_fixture(tmp)
         print("golden fixtures written:", sorted(only))
         return
     with tempfile.TemporaryDirectory() as tmp:
@@ -286,6 +310,7 @@ def main():
         rq_hnsw_fixture(tmp)
         # inner product off the SIMD16 path: SIMD4ExtAVX (d=20), SIMD16ExtResiduals (d=21), SIMD4ExtResiduals (d=10)
         ip_odd_dims_fixture(tmp)
+        dist_range_fixture(tmp)   # (reads the two distance fixtures written above)
         for d, seed in ((20, 21), (21, 23), (10, 25)):
             b = mixture(600, d, seed, lo=-1, hi=1, sigma=0.5)
             q = mixture(40, d, seed + 1, lo=-1, hi=1, sigma=0.5)

@@ -25,6 +25,34 @@ def test_distance_recipes_bit_exact(oracle):
     assert checked >= 25
 
 
+def range_pairs():
+    """(key in dist_ref_range.npz, metric, a, b): the pairs of the two distance fixtures times 2^s, as make_golden.py scaled them."""
+    for fname in ("dist_ref.npz", "dist_ref_ip_odd.npz"):
+        g = np.load(os.path.join(GOLDEN, fname))
+        for key in sorted(k for k in g.files if k.endswith("_a")):
+            metric, d = key.split("_")[:2]
+            for s in (-70, 50) + ((62,) if metric == "l2" else ()):
+                yield f"{metric}_{d}_s{s}_ref", L2 if metric == "l2" else IP, g[key] * np.float32(2.0 ** s), g[f"{metric}_{d}_b"] * np.float32(2.0 ** s)
+
+
+def test_distance_recipes_bit_exact_at_the_range_edges(oracle):
+    """Subnormal products and sums (2^-70), distances above 2^100 (2^50) and L2 sums that overflow to +inf (2^62): the restated
+    recipes give the compiled reference's bytes there too, so the oracle is a reference over the whole fp32 range."""
+    ref = np.load(os.path.join(GOLDEN, "dist_ref_range.npz"))
+    checked, seen = 0, dict(subnormal=False, inf=False, big=False)
+    for key, metric, a, b in range_pairs():
+        got = oracle.dist(metric, a, b)
+        assert got.tobytes() == ref[key].tobytes(), f"{key}: restated recipe differs from the reference"
+        assert not np.isnan(got).any(), key
+        seen["subnormal"] |= bool(((got != 0) & (np.abs(got) < np.float32(2.0 ** -126))).any())
+        seen["inf"] |= bool(np.isposinf(got).any())
+        seen["big"] |= bool((np.isfinite(got) & (np.abs(got) > np.float32(2.0 ** 100))).any())
+        checked += 1
+    assert checked >= 60 and checked == len(ref.files)
+    assert all(seen.values()), seen
+    assert os.path.getsize(os.path.join(GOLDEN, "dist_ref_range.npz")) <= os.path.getsize(os.path.join(GOLDEN, "dist_ref.npz"))
+
+
 @pytest.mark.parametrize("name,metric,dim", [("l2_cont_d32", L2, 32), ("l2_int_d16", L2, 16), ("ip_d48", IP, 48),
                                              ("l2_cont_d20", L2, 20), ("l2_cont_d21", L2, 21), ("l2_cont_d10", L2, 10),
                                              ("ip_d20", IP, 20), ("ip_d21", IP, 21), ("ip_d10", IP, 10)])
