@@ -4,7 +4,10 @@
 
 #include "bf_engine.hpp"
 #include "exact_engine.hpp"
+#include "host_rq_graph.hpp"
+#include "host_update.hpp"
 #include "rabitq_host.hpp"
+#include "slim_convert_gpu.hpp"
 
 hs_status hs_build_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
                         const char *branching_factor, size_t seed, int threads, const char *out_path) {
@@ -49,8 +52,8 @@ hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max
         return fail(HS_ERR_UNSUPPORTED, "label " + std::to_string(labels[i]) + " (row " + std::to_string(i) + ") already exists: updatePoint is not supported");
       return fail(HS_ERR_INVALID, "label " + std::to_string(labels[i]) + " appears twice in the call (rows " + std::to_string(ins.first->second) + " and " + std::to_string(i) + ")");
     }
-    g.seed_levels(seed, drawn);
-    g.resume(rows, labels, count, threads);
+    seed_levels(g, seed, drawn);
+    resume(g, rows, labels, count, threads);
     g.save(out_path);
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
@@ -82,7 +85,7 @@ hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int thr
   return HS_OK;
 }
 
-// The base graph of HNSW-SlimQ: rabitqlib::hnsw::HierarchicalNSW::construct's edges (RqGraph in host_graph.hpp), stored in the
+// The base graph of HNSW-SlimQ: rabitqlib::hnsw::HierarchicalNSW::construct's edges (RqGraph in host_rq_graph.hpp), stored in the
 // vanilla file layout so that the converters read it like any hnswlib index.
 hs_status hs_build_rabitq_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
                                int threads, const char *out_path) {
@@ -115,7 +118,7 @@ hs_status hs_convert_slimq_graph(const char *hnsw_path, int metric, size_t dim, 
     p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
     p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
     SlimGraph s;
-    s.convert(g, p, threads, true);
+    convert_slimq_graph(s, g, p, threads);
     s.save(out_path);
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
@@ -142,7 +145,7 @@ hs_status hs_convert_slim_gpu(const char *hnsw_path, int metric, size_t dim, int
     SlimGraph s;
     std::string err;
     double ms = 0.0;
-    const bool ok = s.convert_gpu(g, p, device, threads, &ms, &err);
+    const bool ok = convert_gpu(s, g, p, device, threads, &ms, &err);
     if (!ok) {
       if (!err.empty()) return fail(HS_ERR_DEVICE, err);
       s.convert(g, p, threads);

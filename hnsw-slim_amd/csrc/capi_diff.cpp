@@ -1,5 +1,5 @@
 // capi_diff.cpp -- the C ABI (include/hnsw_slim_amd.h): the patch server's side of the update loop -- convertFromHNSWWithDiff on two
-// resident indexes (hs_slim_convert_diff; list passes in convert_diff.hip, element assembly and classification in host_graph.hpp,
+// resident indexes (hs_slim_convert_diff; list passes in convert_diff.hip, element assembly and classification in slim_diff.hpp / slim_convert_gpu.hpp,
 // the changed nodes written in place by index_update.hip), the stream and genPatch (hs_slim_diff_stream, hs_slim_diff_next), and
 // the host-only twin on files (hs_slim_convert_diff_files).
 #include "capi_internal.hpp"
@@ -8,9 +8,10 @@
 #include <functional>
 
 #include "index_update.hpp"
+#include "slim_convert_gpu.hpp"
 
 struct hs_slim_diff {
-  SlimGraph::Diff d;
+  SlimDiff d;
   std::unique_ptr<SlimGraph> own;   // hs_slim_convert_diff_files: the Slim image the records are cut from
   const hs_index *made_on = nullptr;
   uint64_t gen = 0;                 // made_on->slim_gen when the diff was made
@@ -28,7 +29,7 @@ static SlimParams diff_params(float pct0, float pct, size_t top_M0, size_t low_m
 // structure arrays as hs_index_patch rebuilds them.  src_vec (nullable): the resident fp32 rows of the HNSW index on the same
 // device -- the rows are then copied from there by the record kernel and none is uploaded.  A call that changed no node and no
 // header field touches nothing on the device.
-static hs_status write_slim_changed(hs_index *ix, const SlimGraph::Diff &d, const float *src_vec) {
+static hs_status write_slim_changed(hs_index *ix, const SlimDiff &d, const float *src_vec) {
   const SlimGraph &g = *ix->host_slim;
   const size_t dim = g.dim;
   if (d.dirty.empty() && ix->info.n == g.count && ix->info.enterpoint == g.enterpoint && ix->info.maxlevel == g.maxlevel &&
@@ -142,7 +143,7 @@ hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_
       dd.s_labels = slim->labels.p; dd.h_labels = hnsw->labels.p; dd.s_vec = slim->vec.p;
       std::string err;
       bool refused = false;
-      gpu = s.convert_diff_gpu(g, p, hnsw->vec.p, hnsw->device, threads, slim->slim_lookup, dd, df->d, &ms, &err,
+      gpu = convert_diff_gpu(s, g, p, hnsw->vec.p, hnsw->device, threads, slim->slim_lookup, dd, df->d, &ms, &err,
                                slim->row_fmt != ROWS_F32 ? &accept : nullptr, &refused);
       if (refused) return fail(HS_ERR_UNSUPPORTED, unfit);
       if (!gpu && !err.empty()) return fail(HS_ERR_DEVICE, err);
@@ -153,7 +154,7 @@ hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_
           if (i < s.count && memcmp(s.vec((uint32_t)i), g.vec((uint32_t)i), 4 * dim) == 0) continue;
           if (!fits((uint32_t)i)) return fail(HS_ERR_UNSUPPORTED, unfit);
         }
-      s.convert_diff(g, p, threads, slim->slim_lookup.map, df->d);
+      convert_diff(s, g, p, threads, slim->slim_lookup.map, df->d);
       slim->slim_lookup.mismatch_valid = false;
     }
   } catch (std::bad_alloc &) {
@@ -213,7 +214,7 @@ hs_status hs_slim_diff_stream(const hs_slim_diff *d, const hs_index *slim, void 
   const SlimGraph *g = diff_image(d, slim);
   if (!g) return HS_ERR_INVALID;
   try {
-    return hand_out(g->diff_stream(d->d), buf, cap, len);
+    return hand_out(diff_stream(*g, d->d), buf, cap, len);
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
   }
@@ -226,7 +227,7 @@ hs_status hs_slim_diff_next(hs_slim_diff *d, const hs_index *slim, size_t limit,
   try {
     size_t io = d->d.ind_old, in = d->d.ind_new, ow = 0, nw = 0;
     std::string bytes(24, '\0');
-    const uint32_t fin = g->gen_patch(d->d, io, in, bytes, ow, nw, limit, to_add != 0);
+    const uint32_t fin = gen_patch(*g, d->d, io, in, bytes, ow, nw, limit, to_add != 0);
     const uint64_t h[3] = {d->d.count, ow, nw};
     memcpy(&bytes[0], h, 24);
     hs_status st = hand_out(bytes, buf, cap, len);
@@ -281,11 +282,11 @@ hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw
       s.take_header(g, hp);
       s.count = 0;
     }
-    s.convert_diff(g, diff_params(top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m), threads,
+    convert_diff(s, g, diff_params(top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m), threads,
                    lookup, df->d);
     s.save(out_slim_path);
     if (out_stream_path) {
-      const std::string bytes = s.diff_stream(df->d);
+      const std::string bytes = diff_stream(s, df->d);
       std::ofstream o(out_stream_path, std::ios::binary);
       if (!o.is_open()) throw std::runtime_error("Cannot open file");
       o.write(bytes.data(), bytes.size());

@@ -17,10 +17,10 @@
 #include "../../include/hnsw_slim_amd.h"
 #include "engine.hpp"
 #include "narrow_rows.hpp"
-#define HS_HAVE_GPU_CONVERT 1
-#include "convert_engine.hpp"
 #include "host_graph.hpp"
+#include "packed_index.hpp"
 #include "search_plan.hpp"
+#include "slim_diff.hpp"
 #include "slimq_engine.hpp"
 
 using namespace hs;
@@ -70,7 +70,7 @@ struct hs_index {
   size_t cap_rows = 0;
   // hs_slim_convert_diff: the Slim index's label_lookup_ (hnswalg_slim.h:61), built from the host image by the first call
   // (buildLabelLookup :216-220) and merged into by every call (:1121)
-  SlimGraph::Lookup slim_lookup;
+  SlimLookup slim_lookup;
   bool slim_lookup_built = false;
   uint64_t slim_gen = 0;   // counts the calls that re-derived the host image: a diff object belongs to one of them
   // live updates (capi_update.cpp): a vanilla index loaded with max_elements > count keeps its host image too (addPoint continues

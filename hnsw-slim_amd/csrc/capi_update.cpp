@@ -6,6 +6,7 @@
 
 #include <unordered_set>
 
+#include "host_update.hpp"
 #include "index_update.hpp"
 
 // label_lookup_ and num_deleted_ (hnswalg.h:61, loadIndex :866-888), from the arrays every index keeps on the host
@@ -86,7 +87,7 @@ static hs_status update_exception(const std::exception &e) {
 hs_status hs_index_seed_levels(hs_index *ix, size_t seed, size_t drawn) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (!ix->host_vanilla) return fail(HS_ERR_INVALID, "index not growable: load a vanilla index with max_elements > its element count");
-  ix->host_vanilla->seed_levels(seed, drawn);
+  seed_levels(*ix->host_vanilla, seed, drawn);
   return HS_OK;
 }
 
@@ -133,7 +134,7 @@ hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *l
   PackedIndex p;
   try {
     g.touched0 = &touched;
-    g.resume(rows, labels, count, threads);
+    resume(g, rows, labels, count, threads);
     g.touched0 = nullptr;
     p.from_vanilla(g, false);
   } catch (std::bad_alloc &) {
@@ -182,7 +183,7 @@ hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t cou
   for (size_t i = 0; i < count; i++) {
     const uint32_t id = stage[i];
     ix->host_deleted[id] = on ? 1 : 0;
-    if (ix->host_vanilla) { if (on) ix->host_vanilla->mark(id); else ix->host_vanilla->unmark(id); }
+    if (ix->host_vanilla) { if (on) mark(*ix->host_vanilla, id); else unmark(*ix->host_vanilla, id); }
     if (on) ix->num_deleted++; else ix->num_deleted--;
   }
   // bare_bone_search = !num_deleted_ && !isIdAllowed (hnswalg.h:1421), in both directions
@@ -231,7 +232,7 @@ hs_status hs_index_set_replace_deleted(hs_index *ix, int on) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "replace_deleted is supported on a vanilla (HS_KIND_HNSW) index only");
   if (!ix->host_vanilla) return fail(HS_ERR_INVALID, "index holds no host image to update: load a vanilla index with max_elements > its element count");
-  ix->host_vanilla->set_allow_replace(on != 0);
+  set_allow_replace(*ix->host_vanilla, on != 0);
   return HS_OK;
 }
 
@@ -310,7 +311,7 @@ hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t
     g.touched0 = &touched;
     VanillaGraph::Visited vl;
     for (size_t i = 0; i < count; i++)
-      row_ids.push_back(g.upsert(rows + i * dim, labels[i], replace_flags && replace_flags[i], ix->label_to_id, vl));
+      row_ids.push_back(upsert(g, rows + i * dim, labels[i], replace_flags && replace_flags[i], ix->label_to_id, vl));
     g.touched0 = nullptr;
     p.from_vanilla(g, false);
   } catch (std::bad_alloc &) {
@@ -374,7 +375,7 @@ hs_status hs_index_resize(hs_index *ix, size_t new_max_elements) {
     HIP_TRY(e);
   }
   try {
-    g.resize(new_max_elements);
+    resize(g, new_max_elements);
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory: resizeIndex failed to allocate base layer");
   } catch (std::exception &e) {
@@ -413,7 +414,7 @@ hs_status hs_hnsw_replay(const char *in_path, int metric, size_t dim, size_t max
   try {
     VanillaGraph g;
     g.load(in_path, (Metric)metric, dim, max_elements);
-    g.set_allow_replace(allow_replace_deleted != 0);
+    set_allow_replace(g, allow_replace_deleted != 0);
     std::unordered_map<uint64_t, uint32_t> lookup;   // label_lookup_ as loadIndex fills it (hnswalg.h:865-866)
     for (size_t i = 0; i < g.count; i++) lookup[g.label((uint32_t)i)] = (uint32_t)i;
     VanillaGraph::Visited vl;
@@ -421,13 +422,13 @@ hs_status hs_hnsw_replay(const char *in_path, int metric, size_t dim, size_t max
       const uint64_t kind = ops[4 * o], arg = ops[4 * o + 1], flag = ops[4 * o + 2], row = ops[4 * o + 3];
       if (kind == HS_OP_ADD) {
         if (!rows) return fail(HS_ERR_INVALID, "bad argument");
-        g.upsert(rows + row * dim, arg, flag != 0, lookup, vl);
+        upsert(g, rows + row * dim, arg, flag != 0, lookup, vl);
       } else if (kind == HS_OP_MARK || kind == HS_OP_UNMARK) {
         auto it = lookup.find(arg);
         if (it == lookup.end()) return fail(HS_ERR_INVALID, "Label not found");
-        if (kind == HS_OP_MARK) g.mark(it->second); else g.unmark(it->second);
+        if (kind == HS_OP_MARK) mark(g, it->second); else unmark(g, it->second);
       } else if (kind == HS_OP_RESIZE) {
-        g.resize(arg);
+        resize(g, arg);
       } else {
         return fail(HS_ERR_INVALID, "bad operation kind " + std::to_string(kind));
       }

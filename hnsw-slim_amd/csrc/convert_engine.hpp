@@ -1,4 +1,4 @@
-// convert_engine.hpp -- interface between host_graph.hpp (SlimGraph::convert_gpu) and convert_gpu.hip.
+// convert_engine.hpp -- interface between slim_convert_gpu.hpp (convert_gpu, convert_diff_gpu) and convert_gpu.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -2,7 +2,7 @@
 // the step immediately before the search path.  The list-level work -- distances, the by-distance
 // std::sort, the pruning heuristic, the reverse-edge union, the re-prune of over-full lists -- runs on the device, one
 // wavefront per (node, level) list; the degree histograms / hub thresholds (:904-945) and the final assembly of the element
-// array and blobs (hierarchical filter :1063-1084, offsets, labels, vectors) stay on the host (host_graph.hpp), they are a
+// array and blobs (hierarchical filter :1063-1084, offsets, labels, vectors) stay on the host (slim_convert_gpu.hpp), they are a
 // few linear passes.  The output is the same bytes as the CPU harness SlimGraph::convert:
 //   * distances by the same fp32 recipes as the search kernels (dist_recipe.hpp; 4 lanes per row for dim % 16 == 0, the
 //     reference's SIMD4 / residual / scalar recipes one lane per row otherwise),

@@ -26,7 +26,6 @@
 #include <random>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "host_graph.hpp"
@@ -332,30 +331,24 @@ struct SlimQGraph {
     for (size_t c = 0; c < ncl; c++) rot.rotate(cent_raw + c * d, &centroids[c * padded]);
     level.resize(n); label.resize(n); cluster.resize(n); code.resize(n * padded / 64); factors.resize(n * 3);
     blobs = s.blobs;
-    int T = std::max(1, threads);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < T; t++)
-      pool.emplace_back([&, t]() {
-        std::vector<float> rx(padded);
-        for (size_t i = t; i < n; i += T) {
-          level[i] = s.level(i);
-          label[i] = s.label(i);
-          uint32_t cid;
-          if (cluster_ids) cid = cluster_ids[i];
-          else {
-            float best = std::numeric_limits<float>::max();
-            cid = 0;
-            for (size_t c = 0; c < ncl; c++) {
-              float dd = rq_l2sqr(s.vec(i), cent_raw + c * d, d);
-              if (dd < best) { best = dd; cid = (uint32_t)c; }
-            }
-          }
-          cluster[i] = cid;
-          rot.rotate(s.vec(i), rx.data());
-          rq_quantize_data(rx.data(), &centroids[cid * padded], padded, metric, &code[i * padded / 64], &factors[i * 3]);
+    std::vector<std::vector<float>> rx(std::max(1, threads), std::vector<float>(padded));
+    parallel_for(n, threads, 64, [&](size_t i, int tid) {
+      level[i] = s.level(i);
+      label[i] = s.label(i);
+      uint32_t cid;
+      if (cluster_ids) cid = cluster_ids[i];
+      else {
+        float best = std::numeric_limits<float>::max();
+        cid = 0;
+        for (size_t c = 0; c < ncl; c++) {
+          float dd = rq_l2sqr(s.vec(i), cent_raw + c * d, d);
+          if (dd < best) { best = dd; cid = (uint32_t)c; }
         }
-      });
-    for (auto &th : pool) th.join();
+      }
+      cluster[i] = cid;
+      rot.rotate(s.vec(i), rx[tid].data());
+      rq_quantize_data(rx[tid].data(), &centroids[cid * padded], padded, metric, &code[i * padded / 64], &factors[i * 3]);
+    });
   }
 };
 

@@ -1,4 +1,4 @@
-// resume_test.cpp -- host-only test of VanillaGraph::resume (host_graph.hpp), built with AddressSanitizer and UBSan (Makefile
+// resume_test.cpp -- host-only test of resume() (host_update.hpp), built with AddressSanitizer and UBSan (Makefile
 // target resume_test): a graph built in one go against the same graph built as a prefix, saved, loaded with room, its level
 // generator put where the prefix build left it, and resumed -- from 1, 10 and n / 2 points, with delete marks set before the
 // resume, and the refused over-capacity resume.  The saved files must be equal byte for byte.
@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "host_graph.hpp"
+#include "host_update.hpp"
 
 using namespace hs;
 
@@ -46,13 +46,13 @@ int main() {
       VanillaGraph g;
       g.load(part, (Metric)metric, d, n);
       CHECK(g.count == n0 && g.max_elements == n, "load with room: count %zu max %zu", g.count, g.max_elements);
-      g.seed_levels(seed, n0);
+      seed_levels(g, seed, n0);
       std::vector<uint32_t> touched;
       g.touched0 = &touched;
       // in two calls: the generator carries over
       const size_t mid = n0 + (n - n0) / 3;
-      g.resume(base.data() + n0 * d, labels.data() + n0, mid - n0, 1);
-      g.resume(base.data() + mid * d, labels.data() + mid, n - mid, 1);
+      resume(g, base.data() + n0 * d, labels.data() + n0, mid - n0, 1);
+      resume(g, base.data() + mid * d, labels.data() + mid, n - mid, 1);
       g.touched0 = nullptr;
       g.save(out);
       const std::vector<char> got = slurp(out);
@@ -61,7 +61,7 @@ int main() {
       CHECK(!touched.empty(), "no level-0 list recorded as touched");
       compared += got.size();
       bool threw = false;
-      try { g.resume(base.data(), labels.data(), 1, 1); } catch (std::runtime_error &e) { threw = std::string(e.what()) == "The number of elements exceeds the specified limit"; }
+      try { resume(g, base.data(), labels.data(), 1, 1); } catch (std::runtime_error &e) { threw = std::string(e.what()) == "The number of elements exceeds the specified limit"; }
       CHECK(threw, "a resume beyond max_elements must be refused");
     }
     // marks set before the resume: the resumed graph equals the graph that took the same marks at the same point of a single run
@@ -69,19 +69,19 @@ int main() {
       const size_t n0 = n / 2;
       VanillaGraph a;
       a.init(n, d, (Metric)metric, M, efC, "4");
-      a.seed_levels(seed, 0);
-      a.resume(base.data(), labels.data(), n0, 1);
+      seed_levels(a, seed, 0);
+      resume(a, base.data(), labels.data(), n0, 1);
       a.save(part);
       for (uint32_t i = 0; i < n0; i += 3) a.set_deleted(i, true);
       a.set_deleted(a.enterpoint, true);
-      a.resume(base.data() + n0 * d, labels.data() + n0, n - n0, 1);
+      resume(a, base.data() + n0 * d, labels.data() + n0, n - n0, 1);
       a.save(whole);
       VanillaGraph b;
       b.load(part, (Metric)metric, d, n);
       for (uint32_t i = 0; i < n0; i += 3) b.set_deleted(i, true);
       b.set_deleted(b.enterpoint, true);
-      b.seed_levels(seed, n0);
-      b.resume(base.data() + n0 * d, labels.data() + n0, n - n0, 1);
+      seed_levels(b, seed, n0);
+      resume(b, base.data() + n0 * d, labels.data() + n0, n - n0, 1);
       b.save(out);
       CHECK(slurp(out) == slurp(whole), "metric %d: resume over delete marks differs", metric);
       CHECK(b.num_deleted() == a.num_deleted() && b.num_deleted() > 0, "marks lost");

@@ -2,6 +2,7 @@
 // mechanics bit for bit (array layout after every operation), on tie-heavy random sequences.
 // Exit code 0 = identical.  Run by tests/test_heap_emul.py.
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -141,6 +142,47 @@ static int run_loadmem(const char *vanilla, const char *slim, size_t dim) {
   return 0;
 }
 
+// hs::parallel_for (host_parallel.hpp): every index exactly once with tid < threads, whatever the grain; a throwing body reaches
+// the caller with its message once every worker has left the body.
+static int run_parallel() {
+  int calls = 0;
+  hs::parallel_for(0, 8, 64, [&](size_t, int) { calls++; });
+  if (calls) return 1;
+  hs::parallel_for(1, 8, 64, [&](size_t i, int tid) { calls += (i == 0 && tid >= 0 && tid < 8) ? 1 : 100; });
+  if (calls != 1) return 2;
+  for (size_t grain : {1, 64, 256})
+    for (int threads : {1, 8, 0}) {
+      std::vector<std::atomic<int>> seen(1000);
+      std::atomic<int> bad_tid(0);
+      hs::parallel_for(1000, threads, grain, [&](size_t i, int tid) {
+        seen[i]++;
+        if (tid < 0 || tid >= std::max(threads, 1)) bad_tid++;
+      });
+      if (bad_tid) return 3;
+      for (auto &s : seen)
+        if (s != 1) return 4;
+    }
+  for (int threads : {1, 8}) {
+    std::atomic<int> inside(0), ran(0);
+    std::string what;
+    try {
+      hs::parallel_for(1000, threads, 1, [&](size_t i, int) {
+        inside++;
+        ran++;
+        if (i == 500) { inside--; throw std::runtime_error("index 500"); }
+        inside--;
+      });
+      return 5;
+    } catch (std::runtime_error &e) {
+      what = e.what();
+    }
+    if (what != "index 500" || inside != 0 || ran > 1000) return 6;
+    if (threads == 1 && ran != 501) return 7;   // no claim after the throw
+  }
+  printf("parallel_for: every index once at grains 1 / 64 / 256, 1 and 8 threads; a worker's exception reaches the caller\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc == 5 && std::string(argv[1]) == "loadmem") return run_loadmem(argv[2], argv[3], (size_t)atoll(argv[4]));
   int rc = 0;
@@ -152,5 +194,7 @@ int main(int argc, char **argv) {
       if ((rc = run_sort(seed + 300, range))) break;
     }
   printf(rc ? "heap_emul MISMATCH rc=%d\n" : "heap_emul identical to libstdc++ (rc=%d)\n", rc);
+  if (rc) return rc;
+  if ((rc = run_parallel())) printf("parallel_for FAILED rc=%d\n", rc);
   return rc;
 }

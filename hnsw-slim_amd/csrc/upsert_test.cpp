@@ -1,4 +1,4 @@
-// upsert_test.cpp -- host-only test of VanillaGraph's update path (host_graph.hpp: updatePoint, repairConnectionsForUpdate,
+// upsert_test.cpp -- host-only test of VanillaGraph's update path (host_update.hpp: updatePoint, repairConnectionsForUpdate,
 // addPoint with replace_deleted, mark / unmark with deleted_elements, resizeIndex), built with AddressSanitizer and UBSan (Makefile
 // target upsert_test) and run as its own binary.  It replays an operation list as hs_hnsw_replay does -- loadIndex, the operations,
 // saveIndex -- and compares the saved file with the expected one byte for byte; then once more from a fresh load, and the two runs
@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "host_graph.hpp"
+#include "host_update.hpp"
 
 using namespace hs;
 
@@ -43,7 +43,7 @@ static std::vector<char> replay(const char *index, int metric, size_t dim, size_
                                 const std::vector<float> &rows, const std::string &out, size_t *n_touched) {
   VanillaGraph g;
   g.load(index, (Metric)metric, dim, max_elements);
-  g.set_allow_replace(allow);
+  set_allow_replace(g, allow);
   std::unordered_map<uint64_t, uint32_t> lookup;
   for (size_t i = 0; i < g.count; i++) lookup[g.label((uint32_t)i)] = (uint32_t)i;
   std::vector<uint32_t> touched;
@@ -56,16 +56,16 @@ static std::vector<char> replay(const char *index, int metric, size_t dim, size_
     std::set<uint32_t> may_change;
     if (kind == 0) {
       CHECK((row + 1) * dim <= rows.size(), "operation %zu names row %llu beyond the rows", o / 4, (unsigned long long)row);
-      const uint32_t id = g.upsert(rows.data() + row * dim, arg, flag != 0, lookup, vl);
+      const uint32_t id = upsert(g, rows.data() + row * dim, arg, flag != 0, lookup, vl);
       CHECK(id < g.count && g.label(id) == arg && lookup.at(arg) == id && !g.deleted(id), "operation %zu: label %llu not at id %u", o / 4, (unsigned long long)arg, id);
       CHECK(!memcmp(g.vec(id), rows.data() + row * dim, 4 * dim), "operation %zu: row not stored", o / 4);
       may_change.insert(id);
     } else if (kind == 1) {
-      g.mark(lookup.at(arg));
+      mark(g, lookup.at(arg));
     } else if (kind == 2) {
-      g.unmark(lookup.at(arg));
+      unmark(g, lookup.at(arg));
     } else {
-      g.resize(arg);
+      resize(g, arg);
     }
     may_change.insert(touched.begin() + touched_before, touched.end());
     std::vector<std::vector<uint32_t>> after = lists0(g);
@@ -118,20 +118,20 @@ int main(int argc, char **argv) {
     const size_t marks0 = g.num_deleted(), count0 = g.count;
     const uint64_t first = g.label(u);
     CHECK(g.deleted_elements.empty(), "deleted_elements filled although replacement is off");
-    CHECK(text([&]() { g.upsert(rows.data(), first, true, lookup, vl); }) == "Replacement of deleted elements is disabled in constructor", "flag without allow");
-    CHECK(text([&]() { g.upsert(rows.data(), ~0ull, false, lookup, vl); }) == "The number of elements exceeds the specified limit", "append to a full index");
-    CHECK(text([&]() { g.resize(g.count - 1); }) == "Cannot resize, max element is less than the current number of elements", "resize below the count");
-    g.set_allow_replace(true);
+    CHECK(text([&]() { upsert(g, rows.data(), first, true, lookup, vl); }) == "Replacement of deleted elements is disabled in constructor", "flag without allow");
+    CHECK(text([&]() { upsert(g, rows.data(), ~0ull, false, lookup, vl); }) == "The number of elements exceeds the specified limit", "append to a full index");
+    CHECK(text([&]() { resize(g, g.count - 1); }) == "Cannot resize, max element is less than the current number of elements", "resize below the count");
+    set_allow_replace(g, true);
     CHECK(g.deleted_elements.size() == marks0, "deleted_elements holds %zu ids after a load with %zu marks", g.deleted_elements.size(), marks0);
-    g.mark(u);
+    mark(g, u);
     CHECK(g.deleted_elements.size() == marks0 + 1 && g.deleted_elements.count(u), "the new mark is not in deleted_elements");
-    CHECK(text([&]() { g.upsert(rows.data(), first, false, lookup, vl); }) ==
+    CHECK(text([&]() { upsert(g, rows.data(), first, false, lookup, vl); }) ==
               "Can't use addPoint to update deleted elements if replacement of deleted elements is enabled.", "update of a marked label");
-    CHECK(text([&]() { g.mark(u); }) == "The requested to delete element is already deleted", "mark twice");
+    CHECK(text([&]() { mark(g, u); }) == "The requested to delete element is already deleted", "mark twice");
     const uint32_t v = *g.deleted_elements.begin();   // the slot the reference's rule hands out: u itself when u is the only mark
     const uint64_t gone = g.label(v);
     CHECK(marks0 != 0 || v == u, "the only vacancy is not the one just marked");
-    const uint32_t got = g.upsert(rows.data(), ~0ull, true, lookup, vl);   // the full index still takes a replacement
+    const uint32_t got = upsert(g, rows.data(), ~0ull, true, lookup, vl);   // the full index still takes a replacement
     CHECK(got == v && g.label(v) == ~0ull && !g.deleted(v) && g.deleted_elements.size() == marks0 && !g.deleted_elements.count(v) &&
               !lookup.count(gone) && lookup.at(~0ull) == v && g.count == count0 && g.num_deleted() == marks0,
           "replacement on a full index");

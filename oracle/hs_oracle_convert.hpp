@@ -1,7 +1,7 @@
 // oracle/hs_oracle_convert.hpp -- TEST INFRASTRUCTURE ONLY.
 //
 // HierarchicalNSWSlim::convertFromHNSW (hnswalg_slim.h:836-1108) followed by saveIndex (:717-751), restated from the reference
-// source alone: the product's conversion (hnsw-slim_amd/csrc/host_graph.hpp, convert_gpu.hip) is a second, separate reading and
+// source alone: the product's conversion (hnsw-slim_amd/csrc/host_graph.hpp, slim_convert_gpu.hpp, convert_gpu.hip) is a second, separate reading and
 // nothing here is taken from it.  The class needs folly and cannot be compiled here, so this restatement is not pinned by a
 // compiled reference; tests/test_slim_convert_restated_cpu.py checks it against a plain-Python reading on integer rows.
 //

@@ -1,4 +1,4 @@
-"""CPU-only tests of the patch server's host core: hs_slim_convert_diff_files (SlimGraph::convert_diff, csrc/host_graph.hpp) against
+"""CPU-only tests of the patch server's host core: hs_slim_convert_diff_files (convert_diff, csrc/slim_diff.hpp) against
 the independent Python reading of convertFromHNSWWithDiff / genPatch in tests/slim_diff_restated.py -- the new Slim file, the two
 changed lists, the whole stream and a chunked genPatch drain -- over three rounds of a growing index (+100 rows, +50 rows, a mark
 plus a replace_deleted add); the streams applied by a Python patchFromStream; and the stand-alone program csrc/diff_prune_test.cpp,
