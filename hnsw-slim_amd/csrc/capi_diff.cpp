@@ -1,13 +1,12 @@
 // capi_diff.cpp -- the C ABI (include/hnsw_slim_amd.h): the patch server's side of the update loop -- convertFromHNSWWithDiff on two
 // resident indexes (hs_slim_convert_diff; list passes in convert_diff.hip, element assembly and classification in slim_diff.hpp / slim_convert_gpu.hpp,
-// the changed nodes written in place by index_update.hip), the stream and genPatch (hs_slim_diff_stream, hs_slim_diff_next), and
+// the changed nodes written in place by write_changed), the stream and genPatch (hs_slim_diff_stream, hs_slim_diff_next), and
 // the host-only twin on files (hs_slim_convert_diff_files).
 #include "capi_internal.hpp"
 
 #include <fstream>
 #include <functional>
 
-#include "index_update.hpp"
 #include "slim_convert_gpu.hpp"
 
 struct hs_slim_diff {
@@ -22,75 +21,6 @@ static SlimParams diff_params(float pct0, float pct, size_t top_M0, size_t low_m
   p.top_pct0 = pct0; p.top_pct = pct;
   p.top_M0 = top_M0; p.low_m0 = low_m0; p.top_M = top_M; p.low_m = low_m;
   return p;
-}
-
-// The device side: slim's host image `g` has been re-derived; `d.dirty` are the nodes whose tile, row or label changed and
-// `d.stale` those of them that carry a row.  One staging copy and one kernel (index_update.hip's records), then the small
-// structure arrays as hs_index_patch rebuilds them.  src_vec (nullable): the resident fp32 rows of the HNSW index on the same
-// device -- the rows are then copied from there by the record kernel and none is uploaded.  A call that changed no node and no
-// header field touches nothing on the device.
-static hs_status write_slim_changed(hs_index *ix, const SlimDiff &d, const float *src_vec) {
-  const SlimGraph &g = *ix->host_slim;
-  const size_t dim = g.dim;
-  if (d.dirty.empty() && ix->info.n == g.count && ix->info.enterpoint == g.enterpoint && ix->info.maxlevel == g.maxlevel &&
-      (ix->info.has_deleted != 0) == g.has_deleted)
-    return HS_OK;
-  PackedIndex p;
-  try {
-    p.from_slim(g, false);
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
-  const uint32_t stride = tile_stride_for(p.max_deg0);
-  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything (as hs_index_patch)
-    p.vec.resize(p.n * dim);
-    for (size_t i = 0; i < p.n; i++) memcpy(&p.vec[i * dim], g.vec((uint32_t)i), 4 * dim);
-    p.rows_on_device = false;
-    hs_status us = upload(ix, p);
-    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
-    return build_narrow(ix, ix->row_fmt, ix->narrow);
-  }
-  // records: the nodes of which only the lists changed, then the nodes that carry a row (both ascending, `stale` a subset of `dirty`)
-  std::vector<uint32_t> ids;
-  for (uint32_t t : d.dirty)
-    if (!std::binary_search(d.stale.begin(), d.stale.end(), t)) ids.push_back(t);
-  const uint32_t first_row = (uint32_t)ids.size();
-  ids.insert(ids.end(), d.stale.begin(), d.stale.end());
-  const size_t nrec = ids.size(), nrow = src_vec ? 0 : d.stale.size(), row_words = (dim + 3) / 4 * 4;
-  const size_t cap = std::max(ix->cap_rows, p.n);
-  for (uint32_t id : ids)
-    if (id >= p.n || id >= cap) return fail(HS_ERR_INVALID, "internal: changed node outside the index");
-  if (nrec) {
-    std::vector<uint32_t> stage(nrec * (4 + (size_t)stride) + nrow * row_words, 0);
-    uint32_t *tiles = stage.data() + nrec * 4;
-    std::fill(tiles, tiles + nrec * stride, 0xFFFFFFFFu);
-    for (size_t r = 0; r < nrec; r++) {
-      const uint32_t id = ids[r];
-      uint32_t *h = stage.data() + r * 4;
-      h[0] = id; h[1] = p.deleted[id]; h[2] = (uint32_t)p.labels[id]; h[3] = (uint32_t)(p.labels[id] >> 32);
-      std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], tiles + r * stride);
-    }
-    for (size_t i = 0; i < nrow; i++) memcpy(stage.data() + nrec * (4 + (size_t)stride) + i * row_words, g.vec(d.stale[i]), 4 * dim);
-    HIP_TRY(ix->upd_stage.ensure(stage.size()));
-    HIP_TRY(hipMemcpy(ix->upd_stage.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-    UpdateArgs a{};
-    a.stage = ix->upd_stage.p; a.nrec = (uint32_t)nrec; a.first_row = first_row; a.stride = stride;
-    a.dim = (uint32_t)dim; a.row_words = (uint32_t)row_words; a.cap_rows = (uint32_t)cap;
-    a.fmt = ix->row_fmt; a.tile0 = ix->tile0.p;
-    a.vec = ix->f32_resident ? ix->vec.p : nullptr;
-    a.narrow = ix->row_fmt != ROWS_F32 ? (void *)ix->narrow.p : nullptr;
-    a.labels = ix->labels.p; a.deleted = ix->deleted.p;
-    a.src_vec = src_vec;
-    HIP_TRY(launch_index_update(a, nullptr));
-  }
-  ix->host_labels = p.labels;
-  ix->host_deleted = p.deleted;
-  hs_status s = upload_small(ix, p);
-  if (s != HS_OK) return s;
-  HIP_TRY(hipDeviceSynchronize());
-  return HS_OK;
 }
 
 hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
@@ -163,8 +93,19 @@ hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_
     return from_exception(e);
   }
   slim->slim_gen++;
-  hs_status ws = write_slim_changed(slim, df->d, same_device ? hnsw->vec.p : nullptr);
-  if (ws != HS_OK) return ws;
+  // a call that changed no node and no header field touches nothing on the device; otherwise `dirty` are the nodes whose tile, row
+  // or label changed, `stale` those of them that carry a row -- copied from the HNSW index's resident rows when both share a device
+  if (!df->d.dirty.empty() || slim->info.n != s.count || slim->info.enterpoint != s.enterpoint || slim->info.maxlevel != s.maxlevel ||
+      (slim->info.has_deleted != 0) != s.has_deleted) {
+    PackedIndex pk;
+    try {
+      pk.from_slim(s, false);
+    } catch (std::exception &e) {
+      return from_exception(e);
+    }
+    hs_status ws = write_changed(slim, pk, [&s](uint32_t i) { return s.vec(i); }, df->d.dirty, df->d.stale, same_device ? hnsw->vec.p : nullptr);
+    if (ws != HS_OK) return ws;
+  }
   if (used_gpu) *used_gpu = gpu ? 1 : 0;
   if (kernel_ms) *kernel_ms = gpu ? ms : 0.0;
   df->made_on = slim;

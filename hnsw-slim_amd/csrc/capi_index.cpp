@@ -66,7 +66,7 @@ hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out) {
   return HS_OK;
 }
 
-// Host-side conversion (hs_rows_to_narrow, hs_index_load_narrow, hs_index_patch on an index without fp32 rows): rows[n x dim] into
+// Host-side conversion (hs_rows_to_narrow, hs_index_load_narrow, an upload without fp32 rows): rows[n x dim] into
 // the lane-major layout of the device copy, row by row while the rows fit.  Returns the first row that holds an unrepresentable
 // value (nothing is written from that row on), n when there is none.
 template <typename T>
@@ -106,11 +106,8 @@ static hs_status upload_narrow_from_host(hs_index *ix, const float *rows, size_t
   ix->narrow.release();
   std::swap(ix->narrow.p, fresh.p);
   std::swap(ix->narrow.n, fresh.n);
-  ix->narrow_bytes = cap * row_bytes;
   return HS_OK;
 }
-// bytes of the fp32 array (allocated for the row capacity): what hs_info.device_bytes falls by when it is dropped
-static size_t f32_rows_bytes(const hs_index *ix) { return std::max<size_t>(ix->cap_rows, ix->info.n) * ix->info.dim * 4; }
 
 const char *hs_last_error(void) { return g_err.c_str(); }
 
@@ -150,7 +147,8 @@ static std::vector<uint32_t> build_uptile(const PackedIndex &p, uint32_t &up_str
 }
 uint32_t tile_stride_for(size_t max_deg0) { return max_deg0 <= 64 ? std::max<uint32_t>(16, (uint32_t)((max_deg0 + 15) / 16 * 16)) : 0; }
 
-// the graph-structure arrays that are small next to the vectors and tiles: uploaded whole (also after a patch)
+// the graph-structure arrays that are small next to the vectors and tiles: uploaded whole (also after every call that changed
+// nodes, write_changed), and with them what the host keeps of `p`: the label / mark mirrors, the mark counters, hs_info
 hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   HIP_TRY(ix->row_ptr0.upload(p.row_ptr0));
   HIP_TRY(ix->cols.upload(p.cols));
@@ -164,16 +162,17 @@ hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   d.uptile = up_stride ? reinterpret_cast<const uint2 *>(ix->uptile.p) : nullptr; d.up_stride = up_stride;
   d.ep_base = p.n ? p.up_base[p.enterpoint] : 0xFFFFFFFFu;
   d.n = (uint32_t)p.n; d.dim = (uint32_t)p.dim; d.maxlevel = p.maxlevel; d.threshold_level = p.threshold_level;
-  d.enterpoint = p.enterpoint; d.has_deleted = p.has_deleted; d.kind = p.kind; d.metric = p.metric;
+  d.enterpoint = p.enterpoint; d.kind = p.kind; d.metric = p.metric;
+  ix->host_labels = p.labels;
+  ix->host_deleted = p.deleted;
+  set_delete_marks(ix, p.deleted.size() - (size_t)std::count(p.deleted.begin(), p.deleted.end(), 0), p.has_deleted);
   hs_info &i = ix->info;
   i.n = p.n; i.dim = p.dim; i.kind = p.kind; i.metric = p.metric; i.maxlevel = p.maxlevel;
-  i.threshold_level = p.threshold_level; i.enterpoint = p.enterpoint; i.has_deleted = p.has_deleted;
+  i.threshold_level = p.threshold_level; i.enterpoint = p.enterpoint;
   i.n_edges = p.cols.size(); i.max_degree0 = p.max_deg0; i.index_size = p.index_size;
-  i.device_bytes = p.row_values() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
-                   p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4 + ix->narrow_bytes;
-  // without resident fp32 rows: less what hs_index_set_f32_resident(ix, 0) takes off, the array's whole row capacity (the sum
-  // above counts its n rows; an index with far more capacity than rows would go below zero, so it stops there)
-  if (!ix->f32_resident) { ix->f32_gone = std::min<size_t>(i.device_bytes, f32_rows_bytes(ix)); i.device_bytes -= ix->f32_gone; }
+  ix->base_bytes = p.row_values() * 4 + (p.row_ptr0.size() + p.cols.size() + p.up_base.size() + p.up_ptr.size()) * 4 +
+                   p.labels.size() * 8 + p.deleted.size() + (size_t)p.n * ix->dev.tile_stride * 4;
+  refresh_device_bytes(ix);
   return HS_OK;
 }
 
@@ -197,8 +196,6 @@ hs_status upload(hs_index *ix, const PackedIndex &p) {
   }
   HIP_TRY(upload_cap(ix->labels, p.labels, cap));
   HIP_TRY(upload_cap(ix->deleted, p.deleted, cap));
-  ix->host_labels = p.labels;
-  ix->host_deleted = p.deleted;
   DevIndex &d = ix->dev;
   d.vec = ix->vec.p; d.labels = ix->labels.p; d.deleted = ix->deleted.p;
   d.tile0 = stride ? ix->tile0.p : nullptr; d.tile_stride = stride;
@@ -251,15 +248,16 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
 // hnswalg_slim.h:1427-1476):  u64 cur_element_count, u64 changed_old_cnt, u64 changed_new_cnt, then per changed node
 //   u32 id | old node: 8 bytes {i32 level, u32 total_neighbor}; new node: 16 bytes {level, total, u64 label} |
 //   u32 neighborsSize | the neighbour blob | new node and to_add: data_size bytes of vector.
-// The host image takes the records exactly as the reference's does; on the device the two big arrays (vectors, level-0
-// tiles) are rewritten only where a node changed, the small structure arrays (CSR, upper-level tiles) are rebuilt whole.
+// The host image takes the records exactly as the reference's does; on the device the changed nodes go through write_changed:
+// the new nodes with their row as the image holds it (the stream's vector with to_add, zeros without), the old nodes as list-only
+// records (a patch never carries their rows, so the resident row already equals the image's).
 // As in the reference the stream carries no enter point / max level: they stay what they were.
 hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add) {
   if (!ix || !bytes) return fail(HS_ERR_INVALID, "null argument");
   if (!ix->host_slim) return fail(HS_ERR_INVALID, "index not patchable: load a Slim index with max_elements > its element count");
   SlimGraph &g = *ix->host_slim;
   const size_t spe = g.size_per_el, dim = g.dim;
-  std::vector<uint32_t> changed;
+  std::vector<uint32_t> changed, added;
   size_t new_count = 0;
   try {
     BinReader r(BinSource(bytes, len));
@@ -300,7 +298,7 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
       uint32_t total; memcpy(&total, e + 4, 4);
       g.blobs[rc.id] = (rc.blob.empty() || total == 0) ? std::vector<char>() : std::move(rc.blob);
       if (!rc.vec.empty()) memcpy(e + 24, rc.vec.data(), dim * 4);
-      changed.push_back(rc.id);
+      (rc.is_new ? added : changed).push_back(rc.id);
     }
     g.count = new_count;
   } catch (std::bad_alloc &) {
@@ -310,41 +308,11 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
   }
   PackedIndex p;
   try {
-    p.from_slim(g);
+    p.from_slim(g, false);
   } catch (std::exception &e) {
     return from_exception(e);
   }
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
-  const uint32_t stride = tile_stride_for(p.max_deg0);
-  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything
-    hs_status us = upload(ix, p);   // (an index without fp32 rows: rebuilds the narrow copy from the host image, in chunks)
-    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
-    return build_narrow(ix, ix->row_fmt, ix->narrow);   // the fp32 rows were re-allocated: the narrow copy is rebuilt whole
-  }
-  std::vector<uint32_t> row(stride);
-  std::vector<uint8_t> narrow_row;
-  for (uint32_t id : changed) {
-    std::fill(row.begin(), row.end(), 0xFFFFFFFFu);
-    std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], row.begin());
-    HIP_TRY(hipMemcpy(ix->tile0.p + (size_t)id * stride, row.data(), stride * 4, hipMemcpyHostToDevice));
-    if (ix->f32_resident) {
-      HIP_TRY(hipMemcpy(ix->vec.p + (size_t)id * dim, &p.vec[(size_t)id * dim], dim * 4, hipMemcpyHostToDevice));
-      if (ix->row_fmt != ROWS_F32)   // the same row of the narrow copy (its values were validated above)
-        HIP_TRY(launch_narrow_convert(ix->vec.p, ix->narrow.p, ix->row_fmt, id, 1, (uint32_t)dim, ix->narrow_bad.p, nullptr));
-    } else {   // no fp32 rows on the device: the row is converted here and written into the copy
-      const size_t rb = dim * narrow_width(ix->row_fmt);
-      narrow_row.resize(rb);
-      if (rows_to_narrow_host(&p.vec[(size_t)id * dim], 1, dim, ix->row_fmt, narrow_row.data()) != 1)
-        return fail(HS_ERR_UNSUPPORTED, "patch: row " + std::to_string(id) + " is not representable in the index's row format");
-      HIP_TRY(hipMemcpy(ix->narrow.p + (size_t)id * rb, narrow_row.data(), rb, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(ix->labels.p + id, &p.labels[id], 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ix->deleted.p + id, &p.deleted[id], 1, hipMemcpyHostToDevice));
-  }
-  ix->host_labels = p.labels;
-  ix->host_deleted = p.deleted;
-  return upload_small(ix, p);
+  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, changed, added);
 }
 
 // An index the host has already parsed: node i owns levels[i] + 1 consecutive neighbour lists (level 0 first),
@@ -476,10 +444,8 @@ hs_status hs_index_set_row_format(hs_index *ix, int format) {
   ix->narrow.release();
   std::swap(ix->narrow.p, fresh.p);
   std::swap(ix->narrow.n, fresh.n);
-  ix->info.device_bytes -= ix->narrow_bytes;
-  ix->narrow_bytes = format == ROWS_F32 ? 0 : narrow_copy_bytes(ix, format);
-  ix->info.device_bytes += ix->narrow_bytes;
   ix->row_fmt = format;
+  refresh_device_bytes(ix);
   return HS_OK;
 }
 int hs_index_row_format(const hs_index *ix) { return ix ? ix->row_fmt : ROWS_F32; }
@@ -496,15 +462,12 @@ hs_status hs_index_set_f32_resident(hs_index *ix, int on) {
     HIP_TRY(launch_narrow_widen(ix->narrow.p, ix->vec.p, ix->row_fmt, 0, (uint32_t)n, (uint32_t)dim, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     ix->dev.vec = ix->vec.p;
-    ix->info.device_bytes += ix->f32_gone;
-    ix->f32_gone = 0;
   } else {
     ix->vec.release();
     ix->dev.vec = nullptr;
-    ix->f32_gone = std::min<size_t>(ix->info.device_bytes, f32_rows_bytes(ix));
-    ix->info.device_bytes -= ix->f32_gone;
   }
   ix->f32_resident = on != 0;
+  refresh_device_bytes(ix);
   return HS_OK;
 }
 int hs_index_f32_resident(const hs_index *ix) { return ix ? (ix->f32_resident ? 1 : 0) : 1; }

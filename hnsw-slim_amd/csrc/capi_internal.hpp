@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -75,7 +76,7 @@ struct hs_index {
   uint64_t slim_gen = 0;   // counts the calls that re-derived the host image: a diff object belongs to one of them
   // live updates (capi_update.cpp): a vanilla index loaded with max_elements > count keeps its host image too (addPoint continues
   // on it, hs_index_save writes it); the label -> internal id map (the reference's label_lookup_) and the number of delete marks
-  // (num_deleted_) are built from host_labels / host_deleted the first time a call needs them
+  // is built from host_labels the first time a call needs it; the number of delete marks (num_deleted_) follows every upload
   std::unique_ptr<VanillaGraph> host_vanilla;
   std::unordered_map<uint64_t, uint32_t> label_to_id;
   bool label_map_built = false;
@@ -92,10 +93,9 @@ struct hs_index {
   // the narrow twin of the chosen kernel and nothing on the device holds fp32 rows
   int row_fmt = ROWS_F32;
   bool f32_resident = true;
-  size_t f32_gone = 0;           // what info.device_bytes is short of while the fp32 rows are absent
   DevBuf<uint8_t> narrow;
   DevBuf<uint32_t> narrow_bad;   // the conversion kernel's "first row that does not fit" word
-  size_t narrow_bytes = 0;       // part of info.device_bytes while the copy exists
+  size_t base_bytes = 0;         // info.device_bytes without the narrow copy, fp32 rows counted (refresh_device_bytes)
   // per-stream scratch (grow-only): calls on different HIP streams may be in flight together
   struct StreamWs {
     DevBuf<uint32_t> spill;             // visited-set tier 2, nq x kSpillSlots
@@ -163,6 +163,17 @@ hs_status upload(hs_index *ix, const PackedIndex &p);
 hs_status upload_small(hs_index *ix, const PackedIndex &p);
 uint32_t tile_stride_for(size_t max_deg0);
 hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out);
+// capi_resident.cpp
+// The device side of a call that changed the host image (packed as `p`, without rows; row_of(i) reads row i of the image): `changed`
+// are the nodes whose level-0 list, label or mark changed, `row_ids` those that also carry a row -- in any order, repeats allowed.
+// One staging copy and one kernel, then the small structure arrays (upload_small); a list that outgrew the tile stride re-uploads
+// the whole index.  src_vec (nullable): fp32 rows on the same device, indexed like the image -- the kernel copies the rows from
+// there and none is uploaded.
+hs_status write_changed(hs_index *ix, PackedIndex &p, const std::function<const float *(uint32_t)> &row_of, const std::vector<uint32_t> &changed,
+                        const std::vector<uint32_t> &row_ids, const float *src_vec = nullptr);
+// hs_info.device_bytes from the index's state: base_bytes, plus the narrow copy and less the absent fp32 array, both by row capacity
+void refresh_device_bytes(hs_index *ix);
+void set_delete_marks(hs_index *ix, size_t num_deleted, bool has_deleted);   // num_deleted_ and the flag the kernels and hs_info carry
 size_t first_unfit(const float *x, size_t count, int fmt);   // first value not representable in the row format, `count` when none
 std::string unfit_message(size_t row, size_t comp, float v, int fmt);
 // capi_slimq.cpp

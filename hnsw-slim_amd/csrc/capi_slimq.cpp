@@ -109,7 +109,8 @@ hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, h
   d.rec_words = rw; d.padded = (uint32_t)q.padded; d.trunc = (uint32_t)q.rot.trunc; d.ncl = (uint32_t)q.num_cluster;
   d.fht_scale = q.rot.fac;
   d.t_const = rq_default_tconst(q.padded, 1);
-  ix->info.device_bytes += (rec.size() + ft.size() + ut.size()) * 4 + q.centroids.size() * 4 + q.rot.flip.size();
+  ix->base_bytes += (rec.size() + ft.size() + ut.size()) * 4 + q.centroids.size() * 4 + q.rot.flip.size();
+  refresh_device_bytes(ix);
   *out = ix;
   return HS_OK;
 }
@@ -125,7 +126,8 @@ hs_status hs_slimq_set_dataset(hs_index *ix, const float *base, size_t n, size_t
   ix->dev.vec = ix->vec.p;
   ix->sq.raw = ix->vec.p;
   ix->has_dataset = true;
-  ix->info.device_bytes += n * dim * 4;
+  ix->base_bytes += n * dim * 4;
+  refresh_device_bytes(ix);
   return HS_OK;
 }
 hs_status hs_slimq_set_tconst(hs_index *ix, double t_const) {

@@ -1,6 +1,6 @@
 // capi_update.cpp -- the C ABI (include/hnsw_slim_amd.h): a resident vanilla index that changes -- addPoint on its host image, for
 // new labels (hs_index_add_points) and as the reference's upsert with replace_deleted (hs_index_upsert_points), with the changed
-// rows written in place on the device (index_update.hip); markDelete / unmarkDelete, resizeIndex, saveIndex, getDataByLabel; and
+// rows written in place on the device (write_changed, capi_resident.cpp); markDelete / unmarkDelete, resizeIndex, saveIndex, getDataByLabel; and
 // the host-only replay of an operation list (hs_hnsw_replay).
 #include "capi_internal.hpp"
 
@@ -9,73 +9,13 @@
 #include "host_update.hpp"
 #include "index_update.hpp"
 
-// label_lookup_ and num_deleted_ (hnswalg.h:61, loadIndex :866-888), from the arrays every index keeps on the host
+// label_lookup_ (hnswalg.h:61, loadIndex :866-888), from the labels every index keeps on the host
 static void ensure_update_state(hs_index *ix) {
   if (ix->label_map_built) return;
   ix->label_to_id.clear();
   ix->label_to_id.reserve(ix->host_labels.size());
   for (size_t i = 0; i < ix->host_labels.size(); i++) ix->label_to_id[ix->host_labels[i]] = (uint32_t)i;
-  ix->num_deleted = 0;
-  for (uint8_t d : ix->host_deleted) ix->num_deleted += d != 0;
   ix->label_map_built = true;
-}
-
-// The device side of a call that changed the host image `g` (packed as `p`, without rows): `touched` are the nodes whose level-0
-// list was written, `row_ids` (distinct) the nodes whose row, label or mark changed -- new ids beyond the old count, and ids of
-// existing nodes that an update or a replacement rewrote.  One staging copy and one kernel; the rows come from the host image.
-static hs_status write_changed(hs_index *ix, PackedIndex &p, std::vector<uint32_t> touched, std::vector<uint32_t> row_ids) {
-  const VanillaGraph &g = *ix->host_vanilla;
-  const size_t dim = ix->info.dim;
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while it is rewritten
-  const uint32_t stride = tile_stride_for(p.max_deg0);
-  if (stride != ix->dev.tile_stride || !ix->dev.tile0) {   // a list outgrew the tile stride: re-tile everything (as hs_index_patch)
-    p.vec.resize(p.n * dim);
-    for (size_t i = 0; i < p.n; i++) memcpy(&p.vec[i * dim], g.vec((uint32_t)i), 4 * dim);
-    p.rows_on_device = false;
-    hs_status us = upload(ix, p);
-    if (us != HS_OK || ix->row_fmt == ROWS_F32 || !ix->f32_resident) return us;
-    return build_narrow(ix, ix->row_fmt, ix->narrow);
-  }
-  // the changed nodes as records: nodes of which only the level-0 list was written, then the nodes that carry a row
-  std::sort(row_ids.begin(), row_ids.end());
-  std::sort(touched.begin(), touched.end());
-  touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
-  std::vector<uint32_t> ids;
-  for (uint32_t t : touched)
-    if (!std::binary_search(row_ids.begin(), row_ids.end(), t)) ids.push_back(t);
-  const uint32_t first_row = (uint32_t)ids.size();
-  ids.insert(ids.end(), row_ids.begin(), row_ids.end());
-  const size_t nrec = ids.size(), nrow = row_ids.size(), row_words = (dim + 3) / 4 * 4;
-  const size_t cap = std::max(ix->cap_rows, p.n);
-  for (uint32_t id : ids)
-    if (id >= p.n || id >= cap) return fail(HS_ERR_INVALID, "internal: changed node outside the index");
-  std::vector<uint32_t> stage(nrec * (4 + (size_t)stride) + nrow * row_words, 0);
-  uint32_t *tiles = stage.data() + nrec * 4;
-  std::fill(tiles, tiles + nrec * stride, 0xFFFFFFFFu);
-  for (size_t r = 0; r < nrec; r++) {
-    const uint32_t id = ids[r];
-    uint32_t *h = stage.data() + r * 4;
-    h[0] = id; h[1] = p.deleted[id]; h[2] = (uint32_t)p.labels[id]; h[3] = (uint32_t)(p.labels[id] >> 32);
-    std::copy(p.cols.begin() + p.row_ptr0[id], p.cols.begin() + p.row_ptr0[id + 1], tiles + r * stride);
-  }
-  for (size_t i = 0; i < nrow; i++) memcpy(stage.data() + nrec * (4 + (size_t)stride) + i * row_words, g.vec(row_ids[i]), 4 * dim);
-  HIP_TRY(ix->upd_stage.ensure(stage.size()));
-  HIP_TRY(hipMemcpy(ix->upd_stage.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-  UpdateArgs a{};
-  a.stage = ix->upd_stage.p; a.nrec = (uint32_t)nrec; a.first_row = first_row; a.stride = stride;
-  a.dim = (uint32_t)dim; a.row_words = (uint32_t)row_words; a.cap_rows = (uint32_t)cap;
-  a.fmt = ix->row_fmt; a.tile0 = ix->tile0.p;
-  a.vec = ix->f32_resident ? ix->vec.p : nullptr;
-  a.narrow = ix->row_fmt != ROWS_F32 ? (void *)ix->narrow.p : nullptr;
-  a.labels = ix->labels.p; a.deleted = ix->deleted.p;
-  HIP_TRY(launch_index_update(a, nullptr));
-  ix->host_labels = p.labels;
-  ix->host_deleted = p.deleted;
-  hs_status s = upload_small(ix, p);
-  if (s != HS_OK) return s;
-  HIP_TRY(hipDeviceSynchronize());
-  return HS_OK;
 }
 
 // the reference's exception texts with the statuses the header documents
@@ -96,13 +36,7 @@ size_t hs_index_capacity(const hs_index *ix) {
   return ix->host_vanilla ? ix->host_vanilla->max_elements : std::max<size_t>(ix->cap_rows, ix->info.n);
 }
 
-size_t hs_index_deleted_count(const hs_index *ix) {
-  if (!ix) return 0;
-  if (ix->label_map_built) return ix->num_deleted;
-  size_t c = 0;
-  for (uint8_t d : ix->host_deleted) c += d != 0;
-  return c;
-}
+size_t hs_index_deleted_count(const hs_index *ix) { return ix ? ix->num_deleted : 0; }
 
 hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, int threads) {
   if (!ix || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "null argument");
@@ -147,7 +81,7 @@ hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *l
   for (size_t i = 0; i < count; i++) ix->label_to_id[labels[i]] = (uint32_t)(n0 + i);
   std::vector<uint32_t> row_ids(count);
   for (size_t i = 0; i < count; i++) row_ids[i] = (uint32_t)(n0 + i);
-  return write_changed(ix, p, touched, row_ids);
+  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, touched, row_ids);
 }
 
 hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t count, int on) {
@@ -184,11 +118,10 @@ hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t cou
     const uint32_t id = stage[i];
     ix->host_deleted[id] = on ? 1 : 0;
     if (ix->host_vanilla) { if (on) mark(*ix->host_vanilla, id); else unmark(*ix->host_vanilla, id); }
-    if (on) ix->num_deleted++; else ix->num_deleted--;
   }
   // bare_bone_search = !num_deleted_ && !isIdAllowed (hnswalg.h:1421), in both directions
-  ix->dev.has_deleted = ix->num_deleted > 0;
-  ix->info.has_deleted = ix->num_deleted > 0;
+  const size_t nd = on ? ix->num_deleted + count : ix->num_deleted - count;
+  set_delete_marks(ix, nd, nd > 0);
   return HS_OK;
 }
 
@@ -321,11 +254,7 @@ hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t
     g.touched0 = nullptr;
     return update_exception(e);
   }
-  std::sort(row_ids.begin(), row_ids.end());
-  row_ids.erase(std::unique(row_ids.begin(), row_ids.end()), row_ids.end());
-  ix->num_deleted = 0;
-  for (uint8_t d : p.deleted) ix->num_deleted += d != 0;   // upload_small takes has_deleted from the same marks
-  return write_changed(ix, p, touched, row_ids);
+  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, touched, row_ids);
 }
 
 // device-to-device move of the first `used` values of a per-node array into an allocation of `cap` values
@@ -391,13 +320,8 @@ hs_status hs_index_resize(hs_index *ix, size_t new_max_elements) {
     DevIndex &d = ix->dev;
     d.vec = ix->vec.p; d.labels = ix->labels.p; d.deleted = ix->deleted.p; d.up_base = ix->up_base.p;
     d.tile0 = stride ? ix->tile0.p : nullptr;
-    // hs_info.device_bytes counts the narrow copy by row capacity (and, without fp32 rows, is short of the fp32 array's capacity)
-    size_t total = ix->info.device_bytes + (ix->f32_resident ? 0 : ix->f32_gone) - ix->narrow_bytes;
     ix->cap_rows = new_max_elements;
-    ix->narrow_bytes = w ? new_max_elements * dim * w : 0;
-    total += ix->narrow_bytes;
-    if (!ix->f32_resident) { ix->f32_gone = std::min<size_t>(total, new_max_elements * dim * 4); total -= ix->f32_gone; }
-    ix->info.device_bytes = total;
+    refresh_device_bytes(ix);
   }
   // indexSize() counts the level-0 link block and element_levels_ by max_elements (hnswalg.h:1533-1547)
   const size_t per = g.size_per_el - dim * 4 - 8 + sizeof(int);

@@ -38,6 +38,15 @@ def test_heap_emulation_matches_libstdcxx(hs):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_update_record_builder_program():
+    """csrc/update_records_test.cpp under AddressSanitizer + UBSan, as its own binary (never inside Python): the staging buffer of
+    the write path for changed nodes -- ids unsorted and repeated, tile padding, row_words at dim 10 / 20 / 32, refusal, empty set."""
+    d = os.path.join(ROOT, "hnsw-slim_amd")
+    subprocess.check_call(["make", "-C", d, "update_records_test"])
+    out = subprocess.run([os.path.join(d, "update_records_test")], capture_output=True, text=True)
+    assert out.returncode == 0 and "update_records ok: 9 shapes" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("name,metric", [("l2_cont_d32", L2), ("l2_int_d16", L2), ("ip_d48", IP), ("l2_cont_d20", L2),
                                          ("l2_cont_d21", L2), ("l2_cont_d10", L2), ("ip_d20", IP), ("ip_d21", IP),
                                          ("ip_d10", IP)])
