@@ -67,7 +67,7 @@ class HsPlanIn(ctypes.Structure):     # hs_plan_in: everything the launch plan o
                 ("has_deleted", _i32), ("kind", _i32), ("ef", _u64), ("k", _u64), ("nq", _u64), ("mode", _i32),
                 ("user_cand_cap", _u32), ("user_hash_slots", _u32), ("grow_cand", _u32), ("grow_hash", _u32),
                 ("exact_order", _i32), ("want_raw", _i32), ("has_filter", _i32), ("row_fmt", _i32), ("f32_resident", _i32),
-                ("diag", HsPlanDiag)]
+                ("has_dup0", _i32), ("diag", HsPlanDiag)]
 
 
 class HsPlanOut(ctypes.Structure):    # hs_plan_out

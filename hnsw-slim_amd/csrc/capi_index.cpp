@@ -166,6 +166,7 @@ hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   ix->host_labels = p.labels;
   ix->host_deleted = p.deleted;
   set_delete_marks(ix, p.deleted.size() - (size_t)std::count(p.deleted.begin(), p.deleted.end(), 0), p.has_deleted);
+  ix->has_dup0 = p.repeats_id0();
   hs_info &i = ix->info;
   i.n = p.n; i.dim = p.dim; i.kind = p.kind; i.metric = p.metric; i.maxlevel = p.maxlevel;
   i.threshold_level = p.threshold_level; i.enterpoint = p.enterpoint;

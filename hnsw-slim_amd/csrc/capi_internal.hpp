@@ -81,6 +81,7 @@ struct hs_index {
   std::unordered_map<uint64_t, uint32_t> label_to_id;
   bool label_map_built = false;
   size_t num_deleted = 0;
+  bool has_dup0 = false;         // some level-0 list names an id twice (PackedIndex::repeats_id0, refreshed by upload_small)
   DevBuf<uint32_t> upd_stage;    // the records of the update call being applied (grow-only)
   DevIndex dev{};
   DevBuf<float> vec;

@@ -18,9 +18,25 @@ static PlanInput plan_input(const hs_index *ix, size_t k, size_t nq, int mode, b
   in.ef = ix->ef; in.k = k; in.nq = nq; in.mode = mode;
   in.user_cand_cap = ix->user_cand_cap; in.user_hash_slots = ix->user_hash_slots; in.grow_cand = ix->grow_cand; in.grow_hash = ix->grow_hash;
   in.exact_order = ix->exact_order; in.want_raw = want_raw; in.has_filter = has_filter;
-  in.row_fmt = ix->row_fmt; in.f32_resident = ix->f32_resident;
+  in.row_fmt = ix->row_fmt; in.f32_resident = ix->f32_resident; in.has_dup0 = ix->has_dup0;
   in.diag = diag();
   return in;
+}
+
+// An index without elements (cur_element_count == 0: hnswalg.h:1382, hnswalg_slim.h:2031-2032 return an empty result): no kernel
+// is launched -- there is no row 0 and no tile 0 to read -- and every output the caller asked for is filled, in stream order, with
+// what a query that found nothing gets: count 0, labels ~0, distances +inf, counters 0, an empty raw heap.
+static hs_status empty_index_outputs(hs_index *ix, size_t nq, size_t k, uint32_t *l32, uint64_t *l64, float *dd, uint32_t *cnt,
+                                     uint32_t *stats, uint32_t *rawsz, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(ix->device));
+  if (l32) HIP_TRY(hipMemsetAsync(l32, 0xFF, nq * k * sizeof(uint32_t), stream));
+  if (l64) HIP_TRY(hipMemsetAsync(l64, 0xFF, nq * k * sizeof(uint64_t), stream));
+  if (dd) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)dd, 0x7F800000, nq * k, stream));   // +inf
+  if (cnt) HIP_TRY(hipMemsetAsync(cnt, 0, nq * sizeof(uint32_t), stream));
+  if (stats) HIP_TRY(hipMemsetAsync(stats, 0, nq * 4 * sizeof(uint32_t), stream));
+  if (rawsz) HIP_TRY(hipMemsetAsync(rawsz, 0, nq * sizeof(uint32_t), stream));
+  ix->last_kernel = "";
+  return HS_OK;
 }
 
 static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, size_t k, int mode, uint32_t *l32,
@@ -34,6 +50,7 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
     return fail(HS_ERR_INVALID, "HS_MODE_SLIM_IDS needs a Slim index (searchKnn(q,k,tableint*) exists on HierarchicalNSWSlim only)");
   if (nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "nq too large");
   if (nq == 0) return HS_OK;
+  if (ix->info.n == 0) return empty_index_outputs(ix, nq, k, l32, l64, dd, cnt, stats, rawsz, stream);
   SearchPlan p;
   const char *why = "";
   hs_status ps = plan_search(plan_input(ix, k, nq, mode, fu != nullptr, raw != nullptr), p, &why);
@@ -130,7 +147,10 @@ hs_status hs_search_check(hs_index *ix, void *stream) {
   uint32_t c[13];   // [12]: queries of filter-set searches whose filter index was outside the set
   HIP_TRY(hipSetDevice(ix->device));
   hs_index::StreamWs *w = ix->stream_ws((hipStream_t)stream);
-  if (!w->counters.p) return HS_OK;  // nothing was launched on this stream
+  if (!w->counters.p) {   // no kernel was launched on this stream; the padding outputs of an empty index may still be on their way
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return HS_OK;
+  }
   HIP_TRY(hipMemcpyAsync(c, w->counters.p, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipMemsetAsync(w->counters.p, 0, sizeof(c), (hipStream_t)stream));   // read and cleared: see search_dev_group
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));

@@ -26,6 +26,22 @@ struct PackedIndex {
 
   static constexpr uint32_t NONE = 0xFFFFFFFFu;
 
+  // Does some level-0 list name an id twice?  (Legal: the reference skips the second occurrence through its visited array,
+  // hnswalg.h:392-393.  The flat kernel marks the ids of one expansion in all lanes at once and so needs them distinct: the
+  // launch plan keeps an index with such a list off it, search_plan.cpp.)  One pass over the edges: seen[id] = the last list
+  // that named id.
+  bool repeats_id0() const {
+    std::vector<uint32_t> seen(n, NONE);
+    for (size_t i = 0; i < n; i++)
+      for (size_t j = row_ptr0[i]; j < row_ptr0[i + 1]; j++) {
+        const uint32_t c = cols[j];
+        if (c >= n) continue;
+        if (seen[c] == (uint32_t)i) return true;
+        seen[c] = (uint32_t)i;
+      }
+    return false;
+  }
+
   // with_rows = false (hs_index_add_points, whose device rows are written record by record): `vec` stays empty
   void from_vanilla(const VanillaGraph &g, bool with_rows = true) {
     kind = 0; metric = g.metric; n = g.count; dim = g.dim;

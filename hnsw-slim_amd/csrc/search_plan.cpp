@@ -237,7 +237,12 @@ hs_status plan_search(const PlanInput &in, SearchPlan &p, const char **msg) {
   const bool flatk_off = dg.kernel == HS_PLAN_KERNEL_LEAN || dg.kernel == HS_PLAN_KERNEL_FAST;
   const FlatPlan fp = plan_flat(in, sh.ef);
   p.fl_nb = fp.nb; p.fl_mul = fp.mul; p.fl_sh = fp.sh; p.fl_bits = fp.vis_bits; p.fl_ok = fp.ok;
-  const bool flatk = !flatk_off && !dg.lean_forced && !filt && fast && fp.ok && flatk_supported(dev, sh.ef, k);
+  // The flat kernel test-and-marks the ids of one expansion in all lanes at once, every lane reading its bucket before any lane
+  // writes (flat_search.hip vis_mark): two lanes holding the same unvisited id would both find it new.  An index with a level-0
+  // list that repeats an id (has_dup0, found when the lists are packed) therefore stays with the other kernels, whose
+  // compare-and-swap inserts (search_common.hpp) let the first occurrence win and show it to the second.
+  const bool distinct0 = !in.has_dup0;
+  const bool flatk = !flatk_off && !dg.lean_forced && !filt && fast && fp.ok && distinct0 && flatk_supported(dev, sh.ef, k);
 
   p.family = flatk ? HS_PLAN_FLAT : lean ? HS_PLAN_LEAN : fast ? HS_PLAN_FAST : HS_PLAN_STRICT;
   // the flat kernel reads the narrow copy wherever the index has one (the same launch plan), the others only when it is all there is

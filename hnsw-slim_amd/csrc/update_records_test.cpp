@@ -65,7 +65,44 @@ static int run(size_t dim, uint32_t stride) {
   return 0;
 }
 
+// PackedIndex::repeats_id0 (the pack-time scan behind the launch plan's has_dup0): a repeat in neighbouring positions, at both ends of a
+// 64-id list, a self-loop and an id shared by two lists (neither is a repeat), an empty index.
+static int run_repeats() {
+  const size_t dim = 0;
+  auto make = [](const std::vector<std::vector<uint32_t>> &lists) {
+    PackedIndex p;
+    p.n = lists.size();
+    p.row_ptr0.assign(1, 0);
+    for (const auto &l : lists) {
+      p.cols.insert(p.cols.end(), l.begin(), l.end());
+      p.row_ptr0.push_back((uint32_t)p.cols.size());
+    }
+    return p;
+  };
+  std::vector<uint32_t> wide(64);
+  for (uint32_t j = 0; j < 64; j++) wide[j] = j + 1;
+  std::vector<std::vector<uint32_t>> g(70);
+  g[0] = wide;
+  CHECK(!make(g).repeats_id0());
+  g[0][63] = g[0][0];
+  CHECK(make(g).repeats_id0());
+  g[0] = wide;
+  g[5] = {5, 6};          // a self-loop
+  g[6] = {5, 7}; g[7] = {5, 6};   // ids shared between lists
+  CHECK(!make(g).repeats_id0());
+  g[69] = {3, 3};
+  CHECK(make(g).repeats_id0());
+  g[69] = {3, 4, 3};
+  CHECK(make(g).repeats_id0());
+  g[69] = {69, 69};
+  CHECK(make(g).repeats_id0());
+  CHECK(!make({}).repeats_id0() && !make({{}}).repeats_id0() && make({{0, 0}}).repeats_id0());
+  printf("repeats_id0 ok\n");
+  return 0;
+}
+
 int main() {
+  if (run_repeats()) return 1;
   size_t checked = 0;
   for (size_t dim : {10, 20, 32})
     for (uint32_t stride : {16u, 32u, 64u}) {

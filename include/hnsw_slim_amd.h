@@ -78,7 +78,12 @@ hs_status hs_index_load_mem(const void *bytes, size_t len, int kind, int metric,
 /* Upload an index the host has already parsed (no file involved): what a caller that holds the reference's public members
  * (hnswalg_slim.h:30 onwards, all public) or its own graph hands over.  Node i owns levels[i] + 1 consecutive neighbour lists,
  * level 0 first; list t = list_ids[list_ptr[t] .. list_ptr[t+1]).  labels NULL = row index, deleted NULL = none marked.
- * kind: HS_KIND_HNSW or HS_KIND_SLIM (selects the searchKnn overload semantics); threshold_level applies to Slim. */
+ * kind: HS_KIND_HNSW or HS_KIND_SLIM (selects the searchKnn overload semantics); threshold_level applies to Slim.
+ * What a list may hold: any ids < n, in any order -- an id named twice or more, the node's own id (a self-loop), ids of marked nodes,
+ * nothing at all.  The lists are stored as given and answered as the reference answers them: its visited array skips the later
+ * occurrences at level 0 (hnswalg.h:392-393), its upper-level descent has no visited array and evaluates a repeated id again
+ * (:1389-1415), and the counters say so.  (An index with a level-0 list that repeats an id is served by the fast / strict kernels, never
+ * by the flat kernel: hs_plan_in.has_dup0.)  n == 0 is an index without elements: every search on it returns count 0. */
 hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, const float *vectors, const uint64_t *labels,
                                     const uint8_t *deleted, const int32_t *levels, const uint64_t *list_ptr,
                                     const uint32_t *list_ids, uint32_t enterpoint, int32_t maxlevel, int32_t threshold_level,
@@ -346,6 +351,7 @@ typedef struct hs_plan_in {
   uint32_t grow_cand, grow_hash;             /* doublings hs_search_check learnt from earlier batches */
   int32_t exact_order, want_raw, has_filter; /* hs_set_exact_order; raw outputs requested; the search names a filter set */
   int32_t row_fmt, f32_resident;             /* hs_index_set_row_format, hs_index_set_f32_resident */
+  int32_t has_dup0;                          /* some level-0 list names an id twice: such an index is never the flat kernel's */
   hs_plan_diag diag;
 } hs_plan_in;
 typedef enum { HS_PLAN_FLAT = 0, HS_PLAN_LEAN = 1, HS_PLAN_FAST = 2, HS_PLAN_STRICT = 3 } hs_plan_family;

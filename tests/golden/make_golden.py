@@ -265,6 +265,70 @@ def searchbuffer_fixture(tmp):
     np.savez_compressed(os.path.join(GOLDEN, "searchbuffer_ref.npz"), **out)
 
 
+def handmade_fixture(tmp):
+    """tests/handmade_graphs.py: every graph as handmade_<name>.hnsw.bin, and handmade.npz with the compiled reference's searchKnn
+    over those files -- `search`, `searchf` under the all-allowing filter and under each filter the graph names; chain's marked
+    file is also produced by `markdel` and must come out as the bytes written here -- next to the oracle restatement of what the
+    compiled reference does not hold (the Slim overloads; the keys say which: handmade_graphs.key)."""
+    import handmade_graphs as hg
+    from hsutil import Oracle, load_chal_encode
+    ce, oracle = load_chal_encode(), Oracle()
+    out = {}
+    fq, res = os.path.join(tmp, "hq.fvecs"), os.path.join(tmp, "hres.bin")
+    catalogue = hg.graphs()
+    for name, g in catalogue.items():
+        raw = g.vanilla()
+        path = os.path.join(GOLDEN, f"handmade_{name}.hnsw.bin")
+        with open(path, "wb") as f:
+            f.write(raw)
+        write_fvecs(fq, g.queries)
+        out[f"{name}_queries"], out[f"{name}_ks"], out[f"{name}_efs"] = g.queries, np.array(g.ks), np.array(g.efs)
+        slim = {"slim": os.path.join(tmp, "h.slim"), "slimdel": os.path.join(tmp, "hd.slim")}
+        with open(slim["slim"], "wb") as f:
+            f.write(ce.vanilla_to_slim_verbatim(raw))
+        with open(slim["slimdel"], "wb") as f:
+            f.write(ce.vanilla_to_slim_verbatim(raw, has_deleted=True))
+        ox = {kind: oracle.load(p, "slim", 0, g.dim) for kind, p in slim.items()}
+        ox["hnsw"] = oracle.load(path, "hnsw", 0, g.dim)
+        for flt in (None, hg.ALLOW_ALL) + g.filters:
+            for o in ox.values():
+                o.set_filter(None if flt is None else g.allowed(flt))
+            for k in g.ks:
+                if flt is None:
+                    run("search", "l2", path, fq, res, k, *g.efs)
+                else:
+                    run("searchf", flt[0], flt[1], "l2", path, fq, res, k, *g.efs)
+                per_ef = {}   # key -> one array per ef, stacked at the end
+                for ef, r in read_ref_search(res).items():
+                    for field, v in r.items():
+                        per_ef.setdefault(hg.key(name, "ref", k, field, flt), []).append(v)
+                    for o in ox.values():
+                        o.set_ef(ef)
+                    for kind in ("hnsw", "slim") + (("slimdel",) if flt is None else ()):
+                        p = ox[kind].search_pq(g.queries, k)
+                        fields = (("cnt", p["cnt"]), ("dists", p["dists"]), ("labels", p["labels"].astype(np.uint32)))
+                        for field, v in (fields if kind != "hnsw" else ()) + (("counters", p["counters"][:, :3]),):
+                            per_ef.setdefault(hg.key(name, f"oracle_{kind}_pq", k, field, flt), []).append(v)
+                        if kind == "hnsw" or flt is not None or not np.all(p["raw_sz"] >= k):
+                            continue   # searchKnn(q, k, tableint*): Slim only, unfiltered, undefined where fewer than k nodes are reached
+                        s = ox[kind].search_ids(g.queries, k)
+                        dists = np.zeros((16, k), np.float32)
+                        for i in range(16):
+                            sz = int(s["raw_sz"][i])
+                            by_label = {int(g.labels[j]): d for j, d in zip(s["raw_i"][i, :sz], s["raw_d"][i, :sz])}
+                            dists[i] = [by_label[int(l)] for l in s["labels"][i]]
+                        for field, v in (("labels", s["labels"]), ("dists", dists), ("counters", s["counters"][:, :3])):
+                            per_ef.setdefault(hg.key(name, f"oracle_{kind}_ids", k, field), []).append(v)
+                for kk, v in per_ef.items():
+                    assert len(v) == len(g.efs)
+                    out[kk] = np.stack(v)
+    # `markdel` of the compiled reference on chain's file: the same bytes as the catalogue's marked chain
+    marked = os.path.join(tmp, "marked.bin")
+    run("markdel", "l2", hg.DIM, os.path.join(GOLDEN, "handmade_chain.hnsw.bin"), marked, hg.MARKDEL_EVERY)
+    assert open(marked, "rb").read() == catalogue["marks_chain_every7"].vanilla(), "markDelete + saveIndex wrote other bytes than the catalogue"
+    np.savez_compressed(os.path.join(GOLDEN, "handmade.npz"), **out)
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     only = set(sys.argv[1:])   # e.g. `make_golden.py bf buffer`: (re)generate just these, leaving the other files byte-stable
@@ -280,6 +344,8 @@ def main():
                 rq_hnsw_fixture(tmp)
             if "range" in only:
                 dist_range_fixture(tmp)
+            if "handmade" in only:
+                handmade_fixture(tmp)
         print("golden fixtures written:", sorted(only))
         return
     with tempfile.TemporaryDirectory() as tmp:
@@ -317,6 +383,7 @@ def main():
             b /= np.linalg.norm(b, axis=1, keepdims=True)
             q /= np.linalg.norm(q, axis=1, keepdims=True)
             index_fixture(tmp, f"ip_d{d}", "ip", b.astype(np.float32), q.astype(np.float32), 8, 60, [10, 32])
+        handmade_fixture(tmp)
     print("golden fixtures written to", GOLDEN)
 
 

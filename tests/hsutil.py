@@ -85,26 +85,46 @@ def headline_data(n, d, seed):
     return sift_like(n, d, seed, n_clusters=4096, rank=12, sigma_sub=40.0, sigma_iso=4.0)
 
 
-def write_vanilla_level0(path, rows, lists, M, efc=100):
-    """A one-level vanilla index file in HierarchicalNSW::saveIndex's layout (hnswalg.h:748-779), written directly so a test can
-    choose every level-0 list: node i -> lists[i] (at most 2 M ids), label i, enter point 0."""
+def vanilla_bytes(rows, lists, M, efc=100, upper=None, enterpoint=0, maxlevel=0, labels=None, marks=None):
+    """A vanilla index file in HierarchicalNSW::saveIndex's layout (hnswalg.h:748-779), written directly so a test can choose every
+    list: node i -> lists[i] at level 0 (at most 2 M ids), upper[i] = its lists at levels 1, 2, ... (at most M ids each; None = every
+    node on level 0 only), labels (None = the row index), delete marks (byte 2 of the level-0 header, :1012-1014; None = none).
+    linkLists_ follows the elements as u32 size + size bytes per element, size = levels x (4 + 4 M) (:770-776)."""
     rows = np.ascontiguousarray(rows, np.float32)
     n, dim = rows.shape
     maxM0 = 2 * M
     size_per_el = 4 + 4 * maxM0 + 4 * dim + 8
     hdr = np.array([0, n, n, size_per_el, 4 + 4 * maxM0 + 4 * dim, 4 + 4 * maxM0], np.uint64).tobytes()
-    hdr += np.array([0], np.int32).tobytes() + np.array([0], np.uint32).tobytes()
+    hdr += np.array([maxlevel], np.int32).tobytes() + np.array([enterpoint], np.uint32).tobytes()
     hdr += np.array([M, maxM0, M], np.uint64).tobytes() + np.array([1.0 / np.log(M)], np.float64).tobytes()
     hdr += np.array([efc], np.uint64).tobytes()
     el = np.zeros((n, size_per_el), np.uint8)
+    assert len(lists) == n
     for i, ids in enumerate(lists):
         assert len(ids) <= maxM0
         el[i, 0:2] = np.frombuffer(np.uint16(len(ids)).tobytes(), np.uint8)
+        if marks is not None and marks[i]:
+            el[i, 2] = 1
         el[i, 4:4 + 4 * len(ids)] = np.frombuffer(np.asarray(ids, np.uint32).tobytes(), np.uint8)
         el[i, 4 + 4 * maxM0:4 + 4 * maxM0 + 4 * dim] = np.frombuffer(rows[i].tobytes(), np.uint8)
-        el[i, size_per_el - 8:] = np.frombuffer(np.uint64(i).tobytes(), np.uint8)
+        el[i, size_per_el - 8:] = np.frombuffer(np.uint64(i if labels is None else int(labels[i])).tobytes(), np.uint8)
+    links = []
+    for i in range(n):
+        ups = [] if upper is None else upper[i]
+        assert len(ups) <= maxlevel
+        blob = np.zeros((len(ups), 1 + M), np.uint32)
+        for lv, ids in enumerate(ups):
+            assert len(ids) <= M
+            blob[lv, 0] = len(ids)   # u16 count + two zero bytes, as the u32 word reads little-endian
+            blob[lv, 1:1 + len(ids)] = np.asarray(ids, np.uint32)
+        links.append(np.array([blob.nbytes], np.uint32).tobytes() + blob.tobytes())
+    return hdr + el.tobytes() + b"".join(links)
+
+
+def write_vanilla_level0(path, rows, lists, M, efc=100):
+    """A one-level vanilla index file (vanilla_bytes): node i -> lists[i] (at most 2 M ids), label i, enter point 0."""
     with open(path, "wb") as f:
-        f.write(hdr + el.tobytes() + np.zeros(n, np.uint32).tobytes())
+        f.write(vanilla_bytes(rows, lists, M, efc))
 
 
 def equal_key_star(n_spokes, dim=16, r=3.0):

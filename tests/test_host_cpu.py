@@ -40,11 +40,12 @@ def test_heap_emulation_matches_libstdcxx(hs):
 
 def test_update_record_builder_program():
     """csrc/update_records_test.cpp under AddressSanitizer + UBSan, as its own binary (never inside Python): the staging buffer of
-    the write path for changed nodes -- ids unsorted and repeated, tile padding, row_words at dim 10 / 20 / 32, refusal, empty set."""
+    the write path for changed nodes -- ids unsorted and repeated, tile padding, row_words at dim 10 / 20 / 32, refusal, empty set;
+    and PackedIndex::repeats_id0, the scan for a level-0 list that names an id twice."""
     d = os.path.join(ROOT, "hnsw-slim_amd")
     subprocess.check_call(["make", "-C", d, "update_records_test"])
     out = subprocess.run([os.path.join(d, "update_records_test")], capture_output=True, text=True)
-    assert out.returncode == 0 and "update_records ok: 9 shapes" in out.stdout, out.stdout + out.stderr
+    assert out.returncode == 0 and "update_records ok: 9 shapes" in out.stdout and "repeats_id0 ok" in out.stdout, out.stdout + out.stderr
 
 
 @pytest.mark.parametrize("name,metric", [("l2_cont_d32", L2), ("l2_int_d16", L2), ("ip_d48", IP), ("l2_cont_d20", L2),
