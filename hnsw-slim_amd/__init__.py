@@ -36,6 +36,8 @@ EXPORTS = [
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
+    "hs_queue_create", "hs_queue_free", "hs_queue_submit", "hs_queue_submit_dev", "hs_queue_flush", "hs_queue_wait",
+    "hs_queue_join_stream", "hs_queue_drain", "hs_queue_info",
 ]
 
 
@@ -76,6 +78,11 @@ class HsPlanOut(ctypes.Structure):    # hs_plan_out
                 ("fl_nb", _u32), ("fl_mul", _u32), ("fl_sh", _u32), ("fl_bits", _u32), ("fl_ok", _u32),
                 ("rerun_rows", _i32), ("rerun_select_mask", _u32), ("rerun_cand_cap", _u32), ("rerun_hash_slots", _u32),
                 ("spill_stride", _u32), ("log_cap", _u32), ("hop_cap", _u32), ("name", ctypes.c_char_p)]
+
+
+class HsQueueInfo(ctypes.Structure):  # struct hs_queue_info
+    _fields_ = [("submitted", _u64), ("launches", _u64), ("pending", _u64), ("in_flight", _u64), ("largest_launch", _u64),
+                ("device_bytes", _u64)]
 
 
 class HsFastShape(ctypes.Structure):  # hs_fast_shape
@@ -162,6 +169,18 @@ def lib():
     L.hs_search_batch_filter_set.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_search_batch_filter_set_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     L.hs_index_exact_search.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_queue_create"):   # (a baseline build in an A/B run may predate the queue)
+        pu64 = ctypes.POINTER(ctypes.c_uint64)
+        L.hs_queue_create.argtypes = [vp, sz, ci, sz, ci, vp, ctypes.POINTER(vp)]
+        L.hs_queue_free.restype = None
+        L.hs_queue_free.argtypes = [vp]
+        L.hs_queue_submit.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, pu64]
+        L.hs_queue_submit_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, pu64]
+        L.hs_queue_flush.argtypes = [vp]
+        L.hs_queue_wait.argtypes = [vp, ctypes.c_uint64]
+        L.hs_queue_join_stream.argtypes = [vp, ctypes.c_uint64, vp]
+        L.hs_queue_drain.argtypes = [vp]
+        L.hs_queue_info.argtypes = [vp, ctypes.POINTER(HsQueueInfo)]
     L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
     L.hs_index_seed_levels.argtypes = [vp, sz, sz]
@@ -475,6 +494,110 @@ class FilterSet:
         out = np.empty(self.info()["n"], np.uint8)
         _check(lib().hs_filter_set_read(self._h, int(f), out.ctypes.data))
         return out
+
+
+class QueueTicket:
+    """One submission to a SearchQueue: its ticket id and the arrays its answers land in (host submissions: numpy arrays owned
+    here, valid after SearchQueue.wait; device submissions: the caller's tensors, kept alive here)."""
+
+    def __init__(self, id, labels=None, dists=None, cnt=None, stats=None, keep=None, device=False):
+        self.id, self.labels, self.dists, self.cnt, self.stats, self._keep, self.device = id, labels, dists, cnt, stats, keep, device
+
+    def result(self):
+        return dict(labels=self.labels, dists=self.dists, cnt=self.cnt, stats=self.stats)
+
+
+class SearchQueue:
+    """hs_queue: small submissions from any thread, coalesced into one search launch per flush on a resident HNSW / Slim index;
+    every query's answer is bit for bit Index.search_ids / search_pq / search_filter_set of that query.  mode: HS_MODE_SLIM_IDS
+    (labels uint32, as search_ids) or HS_MODE_PQ (labels uint64 + dists + cnt, as search_pq); with a FilterSet `fs`, HS_MODE_PQ and
+    one filter index per query.  The calls release the GIL: Python threads block in wait() side by side."""
+
+    def __init__(self, index, k, mode, max_queries=8192, slots=2, fs=None):
+        self._h = ctypes.c_void_p()
+        self.k, self.mode, self.dim, self._index, self._fs = int(k), int(mode), index.dim, index, fs
+        self._out = {}   # outstanding tickets by id: the queue holds the addresses of their arrays until their launch is done
+        _check(lib().hs_queue_create(index._h, self.k, self.mode, int(max_queries), int(slots), None if fs is None else fs._h,
+                                     ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().hs_queue_free(self._h)   # drains first
+            self._h = ctypes.c_void_p()
+            self._out.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def submit(self, queries, filter_of_query=None, want_dists=False, want_stats=False):
+        """Host rows (nq x dim; pageable is fine: copied before this returns; a view of a PinnedArray is read in place and must stay
+        unchanged until wait) -> QueueTicket.  HS_MODE_SLIM_IDS: labels uint32 nq x k,
+        cnt, dists when asked; HS_MODE_PQ: labels uint64, dists, cnt; stats (nq x 4) when asked."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq, k, ids = q.shape[0], self.k, self.mode == HS_MODE_SLIM_IDS
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels = np.empty((nq, k), np.uint32 if ids else np.uint64)
+        dists = np.empty((nq, k), np.float32) if (want_dists or not ids) else None
+        cnt = np.empty(nq, np.uint32)
+        stats = np.empty((nq, 4), np.uint32) if want_stats else None
+        t = ctypes.c_uint64(0)
+        _check(lib().hs_queue_submit(self._h, q.ctypes.data, nq, None if foq is None else foq.ctypes.data,
+                                     labels.ctypes.data if ids else None, None if ids else labels.ctypes.data,
+                                     None if dists is None else dists.ctypes.data, cnt.ctypes.data,
+                                     None if stats is None else stats.ctypes.data, ctypes.byref(t)))
+        return self._hold(QueueTicket(t.value, labels, dists, cnt, stats, keep=(q, foq)))
+
+    def submit_dev(self, d_queries, d_labels, d_dists=None, d_counts=None, d_stats=None, d_filter_of_query=None, stream=0):
+        """Device tensors (torch, on the index's device; queries f32 nq x dim, contiguous rows, any 4-byte alignment; labels int32
+        nq x k in HS_MODE_SLIM_IDS, int64 in HS_MODE_PQ; dists f32 nq x k; counts int32 nq; stats int32 nq x 4; filter indices
+        int32 nq) -> QueueTicket.  The queue's launch waits for what `stream` holds at this moment."""
+        if not d_queries.is_contiguous():
+            raise HsError(HS_ERR_INVALID, "submit_dev takes contiguous rows")
+        nq, ids = d_queries.shape[0], self.mode == HS_MODE_SLIM_IDS
+        ptr = lambda x: None if x is None else x.data_ptr()
+        t = ctypes.c_uint64(0)
+        _check(lib().hs_queue_submit_dev(self._h, d_queries.data_ptr(), nq, ptr(d_filter_of_query), ptr(d_labels) if ids else None,
+                                         None if ids else ptr(d_labels), ptr(d_dists), ptr(d_counts), ptr(d_stats), stream, ctypes.byref(t)))
+        return self._hold(QueueTicket(t.value, d_labels, d_dists, d_counts, d_stats, keep=(d_queries, d_filter_of_query), device=True))
+
+    def _hold(self, ticket):
+        self._out[ticket.id] = ticket   # a caller may drop the ticket: its arrays live until wait / drain / close
+        return ticket
+
+    def flush(self):
+        """Enqueue one launch for everything pending; does not wait for it."""
+        _check(lib().hs_queue_flush(self._h))
+
+    def wait(self, ticket):
+        """Block until the ticket's answers are in its arrays (flushing if it is still pending) -> dict(labels, dists, cnt, stats).
+        Raises the status of the ticket's launch.  A ticket is waited once."""
+        try:
+            _check(lib().hs_queue_wait(self._h, ticket.id))   # (returns only once the ticket's launch is done, whatever its status)
+        finally:
+            self._out.pop(ticket.id, None)
+        return ticket.result()
+
+    def join_stream(self, ticket, stream=0):
+        """Device tickets: `stream` waits for the ticket's launch, the host does not.  The ticket still wants its wait (or a drain)."""
+        _check(lib().hs_queue_join_stream(self._h, ticket.id, stream))
+
+    def drain(self):
+        ids = list(self._out)   # the tickets this drain completes (later ones stay held)
+        try:
+            _check(lib().hs_queue_drain(self._h))
+        finally:
+            for i in ids:
+                self._out.pop(i, None)
+
+    def info(self):
+        i = HsQueueInfo()
+        _check(lib().hs_queue_info(self._h, ctypes.byref(i)))
+        return {f: int(getattr(i, f)) for f, _ in HsQueueInfo._fields_}
 
 
 def plan_input(kernel=None, lean_min_ef=None, order=-1, flat=1, vis16=1, flat_waves_per_cu=0, **fields):

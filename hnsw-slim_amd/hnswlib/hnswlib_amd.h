@@ -752,4 +752,73 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   }
 };
 
+// A search queue on a loaded HierarchicalNSW<float> / HierarchicalNSWSlim<float> (hs_queue_*; no counterpart in the reference): a
+// server's worker threads each call searchKnn(q, k) -- or submit / wait with their own small batches -- on ONE queue object, and
+// whatever is pending when a thread starts to wait leaves as one search launch.  Every answer is bit for bit the index's own
+// searchKnn(q, k) / searchKnnBatch.  k is fixed per queue; ef is the index's at the moment of a flush.  Every method is safe from
+// any thread (drain() releases the tickets it completes: a wait() that loses that race throws "unknown ticket" with its results
+// already in place -- stop the workers before draining).  Changing the index in place (addPoint, markDelete, resizeIndex on an
+// index loaded with room, setRowFormat, ...) wants drain() first.  Calls that free and reload the index's device handle --
+// loadIndex, setDevices, resizeIndex on an index loaded without room, and the destructor -- want the queue DESTROYED first: it
+// holds that handle.
+template <typename dist_t>
+class SearchQueue;
+
+template <>
+class SearchQueue<float> {
+  hs_queue *q_ = nullptr;
+  size_t k_ = 0;
+
+  void open(hs_index *h, size_t max_queries, int slots) {
+    if (!h) throw std::runtime_error("hnswlib_amd: no index loaded");
+    detail::check(hs_queue_create(h, k_, HS_MODE_PQ, max_queries, slots, nullptr, &q_));
+  }
+
+ public:
+  typedef uint64_t ticket_t;
+  SearchQueue(HierarchicalNSW<float> &index, size_t k, size_t max_queries = 8192, int slots = 2) : k_(k) {
+    index.build();   // (an index still being filled by addPoint is built and uploaded here)
+    open(index.handle(), max_queries, slots);
+  }
+  SearchQueue(HierarchicalNSWSlim<float> &index, size_t k, size_t max_queries = 8192, int slots = 2) : k_(k) {
+    open(index.handle(), max_queries, slots);
+  }
+  SearchQueue(const SearchQueue &) = delete;
+  SearchQueue &operator=(const SearchQueue &) = delete;
+  ~SearchQueue() { hs_queue_free(q_); }   // drains first
+
+  size_t k() const { return k_; }
+  // nq x dim rows (copied before this returns -- unless they lie in page-locked, device-mapped memory: those are read in place and
+  // stay unchanged until wait); out_labels / out_dists nq x k and out_counts nq as searchKnnBatch writes them, valid after wait(ticket)
+  ticket_t submit(const float *queries, size_t nq, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) {
+    ticket_t t = 0;
+    detail::check(hs_queue_submit(q_, queries, nq, nullptr, nullptr, out_labels, out_dists, out_counts, nullptr, &t));
+    return t;
+  }
+  void flush() { detail::check(hs_queue_flush(q_)); }
+  void wait(ticket_t t) { detail::check(hs_queue_wait(q_, t)); }
+  void drain() { detail::check(hs_queue_drain(q_)); }
+  struct hs_queue_info info() const {
+    struct hs_queue_info i;
+    detail::check(hs_queue_info(q_, &i));
+    return i;
+  }
+  // searchKnn(q, k) of the index, thread-safe, by submit + wait: queries of threads that arrive together share a launch.
+  std::priority_queue<std::pair<float, labeltype>> searchKnn(const void *query_data, size_t k) {
+    if (k != k_) throw std::runtime_error("hnswlib_amd: this SearchQueue answers k = " + std::to_string(k_));
+    uint64_t labels[64];
+    float dists[64];
+    std::vector<uint64_t> lv;
+    std::vector<float> dv;
+    uint64_t *lp = labels;
+    float *dp = dists;
+    if (k > 64) { lv.resize(k); dv.resize(k); lp = lv.data(); dp = dv.data(); }
+    uint32_t cnt = 0;
+    wait(submit((const float *)query_data, 1, lp, dp, &cnt));
+    std::priority_queue<std::pair<float, labeltype>> result;
+    for (uint32_t i = 0; i < cnt; i++) result.emplace(dp[i], (labeltype)lp[i]);
+    return result;
+  }
+};
+
 }  // namespace hnswlib

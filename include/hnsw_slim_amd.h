@@ -403,6 +403,67 @@ void hs_host_free(void *p);
  * a caller of hs_search_batch_dev may pass this address as d_queries for the same effect (the kernels read each query once). */
 void *hs_host_device_pointer(const void *host);
 
+/* ---- search queue: small submissions from many callers, one launch (no counterpart in the reference, whose callers run one
+ * searchKnn per query: include/strategy/hnsw_slim_strategy.h:112-114) ---------------------------------------------------------
+ * Every search entry above serves one caller's batch with one launch group, and the engine is fast only when that batch is large.
+ * A queue on a resident HNSW or Slim index takes small batches from any thread, with host or device buffers, gathers everything
+ * pending into one contiguous query array with one kernel (hs::gather_rows_kernel), runs ONE ordinary search launch group over it
+ * -- the plan, the kernels and the bits of hs_search_batch_dev for that many queries -- and hands each query's results to its own
+ * caller's buffers with one kernel (hs::scatter_results_kernel).  Filter sets let queries under different filters share a launch;
+ * a queue lets queries of different callers share one.
+ * Grouping.  k, mode and the filter set are fixed per queue; ef is the index's at the moment of the flush.  max_queries: 1..32768
+ *   (one launch group always suffices); slots: 1..16 launches in flight, each with its own stream and staging; a flush that finds
+ *   every slot busy blocks on the oldest launch.  A submission that would take the pending total past max_queries first flushes
+ *   what is pending and then joins the next launch; one with nq > max_queries is refused (HS_ERR_INVALID, nothing changes);
+ *   nq == 0 returns a ticket that is already complete.
+ * Threads.  Every hs_queue_* call on one queue is safe from any thread; hs_queue_wait blocks outside the queue's lock; several
+ *   queues on one index are allowed.
+ * Answers.  Each query's outputs are bit for bit what hs_search_batch (with a filter set: hs_search_batch_filter_set) writes for
+ *   that query -- labels, distances, counts, the padding of unused slots and all four stats columns -- whatever else shared its
+ *   launch.  Required and nullable outputs follow hs_search_batch for the queue's mode (the other mode's label array is ignored).
+ * Host submissions may be pageable: the queries are copied at submit into page-locked memory of the queue (the caller's query
+ *   buffer is free when submit returns) and the results are copied into the caller's buffers by hs_queue_wait.  Queries in
+ *   page-locked, device-mapped memory (hs_host_alloc, hipHostMalloc, mapped hipHostRegister) are NOT copied: the gather reads
+ *   them in place, so they must stay unchanged until the ticket's wait returns (as for hs_search_batch_async; measured faster
+ *   than staging at 1250- and at 10 000-query submissions).
+ * Device submissions: submit records an event on the caller's `stream` and the queue's launch waits for it; the outputs are valid
+ *   after hs_queue_wait, or on `stream` after hs_queue_join_stream (which does not release the ticket: its wait, or a drain, does).
+ * Errors belong to a launch.  Whoever first completes a launch runs the capacity check of its stream (what hs_search_check does)
+ *   and every ticket of that launch then returns that status -- so a device filter index outside the set gives HS_ERR_INVALID to
+ *   every ticket of its launch, count 0 for the offending query, and the next launch is clean.  A launch that could not be planned
+ *   or enqueued completes all its tickets with the error; nothing ever waits forever.  A ticket is waited once: a second wait, or
+ *   an unknown ticket, is HS_ERR_INVALID.
+ *   hs_queue_drain releases a ticket only once its launch is complete: an hs_queue_wait from another thread that races a drain
+ *   either takes the ticket and returns its launch's status, or finds it released -- HS_ERR_INVALID -- with its outputs already written.
+ * Refused at create (HS_ERR_INVALID): a SlimQ index, HS_MODE_SLIM_IDS on a vanilla index, k == 0, max_queries or slots out of
+ *   range, a filter set with a mode other than HS_MODE_PQ, a filter set of another index size or device.
+ * Index changes (patch, add, upsert, mark, resize, row format) while tickets are outstanding are the caller's to avoid: drain
+ *   first, as for every asynchronous entry; hs_index_free with a live queue is likewise the caller's error.  hs_info.device_bytes
+ *   of the index is not changed by a queue; the queue reports its own in hs_queue_info. */
+typedef struct hs_queue hs_queue;
+struct hs_queue_info {
+  uint64_t submitted;       /* queries taken by submit so far */
+  uint64_t launches;        /* launch groups enqueued so far */
+  uint64_t pending;         /* queries submitted and not yet part of a launch */
+  uint64_t in_flight;       /* launches enqueued and not yet completed */
+  uint64_t largest_launch;  /* queries of the largest launch so far */
+  uint64_t device_bytes;    /* HBM held by the queue (the launch arrays of its slots) */
+};
+hs_status hs_queue_create(hs_index *ix, size_t k, int mode, size_t max_queries, int slots, const hs_filter_set *fs /* nullable */,
+                          hs_queue **out);
+void hs_queue_free(hs_queue *q);   /* drains first */
+hs_status hs_queue_submit(hs_queue *q, const float *queries, size_t nq, const uint32_t *filter_of_query, uint32_t *out_labels32,
+                          uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, uint32_t *stats, uint64_t *ticket);
+hs_status hs_queue_submit_dev(hs_queue *q, const float *d_queries, size_t nq, const uint32_t *d_filter_of_query,
+                              uint32_t *d_out_labels32, uint64_t *d_out_labels64, float *d_out_dists, uint32_t *d_out_counts,
+                              uint32_t *d_stats, void *stream, uint64_t *ticket);
+hs_status hs_queue_flush(hs_queue *q);                  /* enqueue one launch group for everything pending; does not block on it */
+hs_status hs_queue_wait(hs_queue *q, uint64_t ticket);  /* flushes if the ticket is still pending; blocks until its results are in
+                                                           the caller's buffers */
+hs_status hs_queue_join_stream(hs_queue *q, uint64_t ticket, void *stream);   /* device tickets: `stream` waits, the host does not */
+hs_status hs_queue_drain(hs_queue *q);                  /* flush + complete everything, release every ticket; the first error met */
+hs_status hs_queue_info(const hs_queue *q, struct hs_queue_info *out);
+
 /* ---- multi-GPU (no counterpart in the reference, which has no notion of a device) --------------------
  * Queries are independent and the index is read-only during search: the index is REPLICATED (hs_index_load once per
  * device), a batch is split into contiguous shards [r*S, (r+1)*S), S = ceil(nq/n), device r searches shard r, and one
