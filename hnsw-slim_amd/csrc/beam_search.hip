@@ -94,7 +94,7 @@ __host__ __device__ inline FastLds fast_layout(uint32_t dim, uint32_t ef, uint32
 #define HS_TU_HAS_IP 1
 #endif
 // HS_TU_ROWS = 1 | 2 (beam_search_u8.hip / beam_search_f16.hip): the same kernels over the index's narrow copy of the rows, as
-// objects of their own per row format and metric; those hold the narrow entry points and nothing else.
+// objects of their own per row format and metric; those hold the narrow entry points and their launchers, nothing else.
 #if !defined(HS_TU_ROWS)
 #define HS_TU_ROWS 0
 #endif
@@ -1257,74 +1257,86 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
 }
 
 // ---- kernels: grid-stride over the queries selected by status ----------------------------------------
-// The three entry points of each kernel differ in the rows they read and in nothing else: hs::strict_kernel / hs::fast_kernel the
-// resident fp32 rows (ix.vec), hs::*_kernel_u8 / hs::*_kernel_f16 the index's narrow copy, handed over as a kernel argument of
-// its own (DevIndex and SearchArgs are what they were).
-#define HS_STRICT_KERNEL_BODY(RS, FA)                                                                                           \
-  extern __shared__ __align__(16) unsigned char smem[];                                                                        \
-  /* pass 0: one query per workgroup, every query.  Re-run passes: 64 statuses per read, then the (normally zero) flagged */  \
-  /* queries of the block one after the other.  (One call site, so that the search body is inlined and the kernel         */  \
-  /* arguments stay in scalar registers.)                                                                                  */  \
-  const bool scan = a.pass_id != 0;                                                                                            \
-  for (uint32_t it = blockIdx.x;; it += gridDim.x) {                                                                           \
-    const uint32_t base = scan ? it * 64 : it;                                                                                 \
-    if (base >= a.nq) break;                                                                                                   \
-    unsigned long long m = 1ull;                                                                                               \
-    if (scan) {                                                                                                                \
-      const uint32_t q = base + threadIdx.x;                                                                                   \
-      m = hs_ballot(q < a.nq && ((1u << a.status[q]) & a.select_mask));                                                        \
-    }                                                                                                                          \
-    while (m) {                                                                                                                \
-      const uint32_t qi = base + (uint32_t)__ffsll((long long)m) - 1;                                                          \
-      m &= m - 1;                                                                                                              \
-      if (ix.n == 0) {  /* cur_element_count == 0 (hnswalg_slim.h:2031-2032) */                                                \
-        if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                              \
-        continue;                                                                                                              \
-      }                                                                                                                        \
-      search_one_strict<METRIC>(ix, a, qi, smem, RS, FA);                                                                      \
-      wave_sync();                                                                                                             \
-    }                                                                                                                          \
-  }
+// Each kernel once per row format: hs::strict_kernel / hs::fast_kernel read the resident fp32 rows (ix.vec), hs::*_kernel_u8 /
+// hs::*_kernel_f16 the index's narrow copy, handed over as a kernel argument of its own (DevIndex and SearchArgs are what they
+// were); they differ in nothing else.  What differs between the row formats, all of it:
 #if HS_TU_ROWS == 0
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel(DevIndex ix, SearchArgs a) {
-  HS_STRICT_KERNEL_BODY(RowSrc<float>(), NoFilter())
-}
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel(DevIndex ix, SearchArgs a, FilterArgs f) {
-  HS_STRICT_KERNEL_BODY(RowSrc<float>(), f)
-}
-#define HS_STRICT_KERNEL strict_kernel
-#define HS_FAST_KERNEL fast_kernel
-#define HS_ROWS_ARG
-#define HS_ROWS_PARAM
-#elif HS_TU_ROWS == 1
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
-  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows}, NoFilter())
-}
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows, FilterArgs f) {
-  HS_STRICT_KERNEL_BODY(RowSrc<uint8_t>{rows}, f)
-}
-#define HS_STRICT_KERNEL strict_kernel_u8
-#define HS_FAST_KERNEL fast_kernel_u8
-#define HS_ROWS_ARG , reinterpret_cast<const uint8_t *>(rows)
-#define HS_ROWS_PARAM , const uint8_t *
+#define HS_ROWS_ID f32                 // the launchers' names (engine.hpp HS_LAUNCHER)
+#define HS_KERNEL(name) name           // the kernels' names
+#define HS_ROWS_PARAM                  // their trailing parameter (before FilterArgs in the filter-set form)
+#define HS_ROW_SRC RowSrc<float>()     // the rows the search body reads
+#define HS_ROWS_ARG                    // the launcher's `rows` as that parameter
 #else
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
-  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows}, NoFilter())
-}
-template <int METRIC>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) strict_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows, FilterArgs f) {
-  HS_STRICT_KERNEL_BODY(RowSrc<_Float16>{rows}, f)
-}
-#define HS_STRICT_KERNEL strict_kernel_f16
-#define HS_FAST_KERNEL fast_kernel_f16
-#define HS_ROWS_ARG , reinterpret_cast<const _Float16 *>(rows)
-#define HS_ROWS_PARAM , const _Float16 *
+#if HS_TU_ROWS == 1
+#define HS_ROWS_ID u8
+#define HS_KERNEL(name) name##_u8
+typedef uint8_t TuRow;
+#else
+#define HS_ROWS_ID f16
+#define HS_KERNEL(name) name##_f16
+typedef _Float16 TuRow;
 #endif
+#define HS_ROWS_PARAM , const TuRow *rows
+#define HS_ROW_SRC RowSrc<TuRow>{rows}
+#define HS_ROWS_ARG , reinterpret_cast<const TuRow *>(rows)
+#endif
+// Each kernel name is an overload pair: (DevIndex, SearchArgs[, rows]) and the filter-set form with FilterArgs behind it.
+#define HS_KFN(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM)>(k)
+#define HS_KFN_FILT(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM, FilterArgs)>(k)
+
+// Strict kernel.  pass 0: one query per workgroup, every query.  Re-run passes: 64 statuses per read, then the (normally zero)
+// flagged queries of the block one after the other.  (One call site, so that the search body is inlined and the kernel arguments
+// stay in scalar registers.)
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) HS_KERNEL(strict_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const bool scan = a.pass_id != 0;
+  for (uint32_t it = blockIdx.x;; it += gridDim.x) {
+    const uint32_t base = scan ? it * 64 : it;
+    if (base >= a.nq) break;
+    unsigned long long m = 1ull;
+    if (scan) {
+      const uint32_t q = base + threadIdx.x;
+      m = hs_ballot(q < a.nq && ((1u << a.status[q]) & a.select_mask));
+    }
+    while (m) {
+      const uint32_t qi = base + (uint32_t)__ffsll((long long)m) - 1;
+      m &= m - 1;
+      if (ix.n == 0) {  // cur_element_count == 0 (hnswalg_slim.h:2031-2032)
+        if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
+        continue;
+      }
+      search_one_strict<METRIC>(ix, a, qi, smem, HS_ROW_SRC, NoFilter());
+      wave_sync();
+    }
+  }
+}
+// (the filter-set form: the same loop, the set as the search body's filter)
+template <int METRIC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) HS_KERNEL(strict_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM, FilterArgs f) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const bool scan = a.pass_id != 0;
+  for (uint32_t it = blockIdx.x;; it += gridDim.x) {
+    const uint32_t base = scan ? it * 64 : it;
+    if (base >= a.nq) break;
+    unsigned long long m = 1ull;
+    if (scan) {
+      const uint32_t q = base + threadIdx.x;
+      m = hs_ballot(q < a.nq && ((1u << a.status[q]) & a.select_mask));
+    }
+    while (m) {
+      const uint32_t qi = base + (uint32_t)__ffsll((long long)m) - 1;
+      m &= m - 1;
+      if (ix.n == 0) {
+        if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
+        continue;
+      }
+      search_one_strict<METRIC>(ix, a, qi, smem, HS_ROW_SRC, f);
+      wave_sync();
+    }
+  }
+}
+
 // Fast kernel.  rc 3 = a tie had to be resolved but the insertion log did not fit: left to the strict pass.
 // Wavefronts per SIMD the register allocation aims at.  A wavefront alone on a CU is only 25 % faster per expansion than one
 // of sixteen (tools/profile_phases.py), so residency pays -- but only while it costs neither spills nor LDS.  At 96 VGPRs
@@ -1338,63 +1350,37 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) st
 __host__ __device__ constexpr int fast_waves(int d16, int s) {
   return (d16 > 16 || (d16 == -1 && s >= 4)) ? 3 : ((d16 == 4 || d16 == 6 || d16 == 8 || d16 == 16) && s <= 2) ? HS_SHORT_WAVES : 4;
 }
-#define HS_FAST_KERNEL_BODY(RS, FA)                                                                                            \
-  extern __shared__ __align__(16) unsigned char smem[];                                                                        \
-  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {                                                                 \
-    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;                                                          \
-    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;  /* pass 0 takes every query */                   \
-    if (ix.n == 0) {                                                                                                           \
-      if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }                                \
-      continue;                                                                                                                \
-    }                                                                                                                          \
-    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, RS, FA);                            \
-    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;                                                                 \
-    wave_sync();                                                                                                               \
-  }
 // (Narrow rows keep the budgets of their fp32 twins.  The widest bare shape, S = 8 with the flat start, spills 424-432 B per lane at
 //  128 VGPRs where its fp32 twin spills 40; a 3-wave build of it (166 VGPRs) still spilled 364 B, so it stays at 4.)
-#if HS_TU_ROWS == 0
 template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel(DevIndex ix, SearchArgs a) {
-  HS_FAST_KERNEL_BODY(RowSrc<float>(), NoFilter())
-}
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel(DevIndex ix, SearchArgs a, FilterArgs f) {
-  HS_FAST_KERNEL_BODY(RowSrc<float>(), f)
-}
-#elif HS_TU_ROWS == 1
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
-  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows}, NoFilter())
-}
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows, FilterArgs f) {
-  HS_FAST_KERNEL_BODY(RowSrc<uint8_t>{rows}, f)
-}
-#else
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
-  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows}, NoFilter())
-}
-template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) fast_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows, FilterArgs f) {
-  HS_FAST_KERNEL_BODY(RowSrc<_Float16>{rows}, f)
-}
-#endif
-
-// Each kernel name is an overload pair: (DevIndex, SearchArgs[, rows]) and the filter-set form with FilterArgs behind it.
-#define HS_KFN(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM)>(k)
-#define HS_KFN_FILT(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM, FilterArgs)>(k)
-// (`rows`: the narrow copy in the narrow objects, nothing in the fp32 ones; then the filter set, in the filter-set form)
-template <typename K, typename... R>
-static hipError_t launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, R... rows) {
-  if (a.nq == 0) return hipSuccess;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) HS_KERNEL(fast_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {
+    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;
+    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;  // pass 0 takes every query
+    if (ix.n == 0) {
+      if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
+      continue;
+    }
+    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, HS_ROW_SRC, NoFilter());
+    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;
+    wave_sync();
   }
-  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a, rows...);
-  return hipGetLastError();
+}
+template <int METRIC, int S, int D16, bool WB = false, bool BARE = true>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fast_waves(D16, S)))) HS_KERNEL(fast_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM, FilterArgs f) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {
+    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;
+    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;
+    if (ix.n == 0) {
+      if (threadIdx.x == 0) { if (a.out_counts) a.out_counts[qi] = 0; a.status[qi] = ST_DONE; }
+      continue;
+    }
+    const int rc = search_one_fast<METRIC, S, D16, WB, BARE, BARE && !WB>(ix, a, qi, smem, HS_ROW_SRC, f);
+    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;
+    wave_sync();
+  }
 }
 
 #if HS_TU_HAS_L2 && HS_TU_ROWS == 0
@@ -1476,7 +1462,7 @@ hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStr
 }
 #endif
 
-// The launchers below dispatch on fast_shape() (engine.hpp, search_plan.cpp) and on nothing else: which dims have a distance pass
+// The fast launchers below dispatch on fast_shape() (engine.hpp, search_plan.cpp) and on nothing else: which dims have a distance pass
 // of their own, the slots per lane and the boundary watch are decided there, and a shape without an instantiation here is refused.
 // delete marks / filters: the variant with the reference's !bare_bone branches (runtime-dim and d=128 only)
 template <int METRIC, int D16>
@@ -1485,18 +1471,18 @@ static hipError_t launch_fast_del(const DevIndex &ix, const SearchArgs &a, size_
   if (sh.wb) return hipErrorInvalidValue;
   if (f) {   // under a filter set: the same shapes, the set as a kernel argument
     switch (sh.slots) {
-      case 1: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-      case 2: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-      case 4: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
-      case 8: return launch(HS_KFN_FILT((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 1: return launch_kernel(HS_KFN_FILT((HS_KERNEL(fast_kernel)<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 2: return launch_kernel(HS_KFN_FILT((HS_KERNEL(fast_kernel)<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 4: return launch_kernel(HS_KFN_FILT((HS_KERNEL(fast_kernel)<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
+      case 8: return launch_kernel(HS_KFN_FILT((HS_KERNEL(fast_kernel)<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG, *f);
       default: return hipErrorInvalidValue;
     }
   }
   switch (sh.slots) {
-    case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 4: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 8: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 1: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 1, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 2: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 2, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 4: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 4, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 8: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 8, D16, false, false>)), ix, a, lds, stream HS_ROWS_ARG);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1505,51 +1491,50 @@ static hipError_t launch_fast_md(const DevIndex &ix, const SearchArgs &a, size_t
                                  const void *rows = nullptr) {
   if (sh.wb) {  // nothing is selected at the end: the variant that watches ties across the capacity boundary
     switch (sh.slots) {
-      case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
-      case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+      case 1: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 1, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
+      case 2: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 2, D16, true>)), ix, a, lds, stream HS_ROWS_ARG);
       default: return hipErrorInvalidValue;
     }
   }
   switch (sh.slots) {
-    case 1: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 1, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 2: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 2, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 4: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 4, D16>)), ix, a, lds, stream HS_ROWS_ARG);
-    case 8: return launch(HS_KFN((HS_FAST_KERNEL<METRIC, 8, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 1: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 1, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 2: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 2, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 4: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 4, D16>)), ix, a, lds, stream HS_ROWS_ARG);
+    case 8: return launch_kernel(HS_KFN((HS_KERNEL(fast_kernel)<METRIC, 8, D16>)), ix, a, lds, stream HS_ROWS_ARG);
     default: return hipErrorInvalidValue;
   }
 }
 
-#if HS_TU_ROWS == 0
-hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
-hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
-hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
-hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f);
+// ---- this object's launchers (engine.hpp): one strict and one fast per metric it holds ---------------------------------------
+// (`rows`: the narrow copy in the narrow objects, unused in the fp32 ones; launch_search has checked it, and ix.vec, against null:
+//  an index whose fp32 rows were dropped, hs_index_set_f32_resident(ix, 0), is served by the narrow objects)
+template <int METRIC>
+static hipError_t strict_launch(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  const size_t lds = strict_layout(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots).total;   // last-resort pass: the heap is in global memory
+  return f ? launch_kernel(HS_KFN_FILT(HS_KERNEL(strict_kernel)<METRIC>), ix, a, lds, stream HS_ROWS_ARG, *f)
+           : launch_kernel(HS_KFN(HS_KERNEL(strict_kernel)<METRIC>), ix, a, lds, stream HS_ROWS_ARG);
+}
 #if HS_TU_HAS_L2
-hipError_t launch_strict_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return f ? launch(HS_KFN_FILT(strict_kernel<METRIC_L2>), ix, a, lds, stream, *f) : launch(HS_KFN(strict_kernel<METRIC_L2>), ix, a, lds, stream);
-}
-// (an index whose fp32 rows were dropped, hs_index_set_f32_resident(ix, 0), is served by the narrow launchers of narrow_rows.hip:
-//  a launch that would read ix.vec is refused here instead of dereferencing null on the device)
-hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f) {
-  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
-  const size_t lds = strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots);
-  return ix.metric == METRIC_L2 ? launch_strict_l2(ix, a, lds, stream, f) : launch_strict_ip(ix, a, lds, stream, f);
-}
-hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f) {
-  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;
-  const size_t lds = fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots);
-  return ix.metric == METRIC_L2 ? launch_fast_l2(ix, a, lds, stream, f) : launch_fast_ip(ix, a, lds, stream, f);
+hipError_t HS_LAUNCHER(strict, HS_ROWS_ID, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  return strict_launch<METRIC_L2>(ix, a, rows, stream, f);
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t launch_strict_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return f ? launch(HS_KFN_FILT(strict_kernel<METRIC_IP>), ix, a, lds, stream, *f) : launch(HS_KFN(strict_kernel<METRIC_IP>), ix, a, lds, stream);
+hipError_t HS_LAUNCHER(strict, HS_ROWS_ID, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  return strict_launch<METRIC_IP>(ix, a, rows, stream, f);
 }
 #endif
+// The distance pass by the shape's d16.  The narrow objects hold the runtime-dim one only (slots and wb of the shape) ...
+template <int METRIC>
+static hipError_t fast_launch_d16(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FastShape &sh, bool bare,
+                                  const void *rows, const FilterArgs *f) {
+  return !bare ? launch_fast_del<METRIC, 0>(ix, a, lds, stream, sh, rows, f) : launch_fast_md<METRIC, 0>(ix, a, lds, stream, sh, rows);
+}
+#if HS_TU_ROWS == 0   // ... the fp32 objects compile-time dims for the common shapes, per metric: the table is fast_shape's
 #if HS_TU_HAS_L2
-hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  const bool bare = !(ix.has_deleted || f);   // a filter set is planned as delete marks are
-  const FastShape sh = fast_shape(METRIC_L2, ix.dim, a.ef, a.k, bare);
+template <>
+hipError_t fast_launch_d16<METRIC_L2>(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FastShape &sh, bool bare,
+                                      const void *, const FilterArgs *f) {
   if (!bare) {
     switch (sh.d16) {
       case 8: return launch_fast_del<METRIC_L2, 8>(ix, a, lds, stream, sh, nullptr, f);
@@ -1558,7 +1543,7 @@ hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, h
       default: return hipErrorInvalidValue;
     }
   }
-  switch (sh.d16) {   // compile-time dims for the common shapes: the table is fast_shape's
+  switch (sh.d16) {
     case 8: return launch_fast_md<METRIC_L2, 8>(ix, a, lds, stream, sh);    // SIFT
     case 6: return launch_fast_md<METRIC_L2, 6>(ix, a, lds, stream, sh);    // DEEP
     case 60: return launch_fast_md<METRIC_L2, 60>(ix, a, lds, stream, sh);  // GIST
@@ -1575,9 +1560,9 @@ hipError_t launch_fast_l2(const DevIndex &ix, const SearchArgs &a, size_t lds, h
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  const bool bare = !(ix.has_deleted || f);
-  const FastShape sh = fast_shape(METRIC_IP, ix.dim, a.ef, a.k, bare);
+template <>
+hipError_t fast_launch_d16<METRIC_IP>(const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, const FastShape &sh, bool bare,
+                                      const void *, const FilterArgs *f) {
   if (!bare) {
     switch (sh.d16) {
       case -1: return launch_fast_del<METRIC_IP, -1>(ix, a, lds, stream, sh, nullptr, f);
@@ -1597,32 +1582,22 @@ hipError_t launch_fast_ip(const DevIndex &ix, const SearchArgs &a, size_t lds, h
   }
 }
 #endif
-#else   // the narrow objects: one strict and one fast launcher per metric, runtime-dim shapes (dispatch: narrow_rows.hip)
-#if HS_TU_ROWS == 1
-#define HS_NARROW_FN(name, metric) name##_u8_##metric
-#else
-#define HS_NARROW_FN(name, metric) name##_f16_##metric
 #endif
-#if HS_TU_HAS_L2
-hipError_t HS_NARROW_FN(launch_strict, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_L2>), ix, a, lds, stream HS_ROWS_ARG);
+template <int METRIC>
+static hipError_t fast_launch(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  const size_t lds = fast_layout(ix.dim, a.ef, a.cand_cap, a.hash_slots).total;
+  const bool bare = !(ix.has_deleted || f);   // a filter set is planned as delete marks are
+  return fast_launch_d16<METRIC>(ix, a, lds, stream, fast_shape(METRIC, ix.dim, a.ef, a.k, bare), bare, rows, f);
 }
-hipError_t HS_NARROW_FN(launch_fast, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  const bool bare = !(ix.has_deleted || f);   // (the narrow objects hold the runtime-dim distance pass only: slots and wb of the shape)
-  const FastShape sh = fast_shape(METRIC_L2, ix.dim, a.ef, a.k, bare);
-  return !bare ? launch_fast_del<METRIC_L2, 0>(ix, a, lds, stream, sh, rows, f) : launch_fast_md<METRIC_L2, 0>(ix, a, lds, stream, sh, rows);
+#if HS_TU_HAS_L2
+hipError_t HS_LAUNCHER(fast, HS_ROWS_ID, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  return fast_launch<METRIC_L2>(ix, a, rows, stream, f);
 }
 #endif
 #if HS_TU_HAS_IP
-hipError_t HS_NARROW_FN(launch_strict, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  return f ? launch(HS_KFN_FILT(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG, *f) : launch(HS_KFN(HS_STRICT_KERNEL<METRIC_IP>), ix, a, lds, stream HS_ROWS_ARG);
+hipError_t HS_LAUNCHER(fast, HS_ROWS_ID, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *f) {
+  return fast_launch<METRIC_IP>(ix, a, rows, stream, f);
 }
-hipError_t HS_NARROW_FN(launch_fast, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f) {
-  const bool bare = !(ix.has_deleted || f);
-  const FastShape sh = fast_shape(METRIC_IP, ix.dim, a.ef, a.k, bare);
-  return !bare ? launch_fast_del<METRIC_IP, 0>(ix, a, lds, stream, sh, rows, f) : launch_fast_md<METRIC_IP, 0>(ix, a, lds, stream, sh, rows);
-}
-#endif
 #endif
 
 }  // namespace hs

@@ -1,5 +1,6 @@
-// capi_search.cpp -- the C ABI (include/hnsw_slim_amd.h): the graph search of a batch -- planned by search_plan.cpp, launched
-// here -- and the device, staged, zero-copy and raw entry points over it.
+// capi_search.cpp -- the C ABI (include/hnsw_slim_amd.h): the graph search of a batch -- planned by search_plan.cpp, its arguments
+// filled in here, each kernel launched through launch_search (engine.hpp) by the family and row format the plan names -- and the
+// device, staged, zero-copy and raw entry points over it.
 #include "capi_internal.hpp"
 
 #include <cstdio>
@@ -92,28 +93,17 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   if (p.family == HS_PLAN_FLAT) { a.fl_nb = p.fl_nb; a.fl_mul = p.fl_mul; a.fl_sh = p.fl_sh; }
   a.counters = w->counters.p; a.pass_id = 0;
   a.select_mask = 1u << ST_TODO; a.grid = (uint32_t)nq;
-  auto strict_go = [&](int rows) {
-    return rows != ROWS_F32 ? launch_strict_narrow(ix->dev, a, ix->narrow.p, rows, stream, fap) : launch_strict(ix->dev, a, stream, fap);
-  };
-  auto pass0 = [&]() {
-    switch (p.family) {
-      case HS_PLAN_FLAT: return p.rows != ROWS_F32 ? launch_flatk_narrow(ix->dev, a, ix->narrow.p, p.rows, stream) : launch_flatk(ix->dev, a, stream);
-      case HS_PLAN_LEAN: return launch_lean(ix->dev, a, stream);
-      case HS_PLAN_FAST: return p.rows != ROWS_F32 ? launch_fast_narrow(ix->dev, a, ix->narrow.p, p.rows, stream, fap) : launch_fast(ix->dev, a, stream, fap);
-      default: return strict_go(p.rows);
-    }
-  };
   if (p.split) {   // descent / order / level-0 search (why: search_plan.cpp)
     a.entry = reinterpret_cast<uint4 *>(w->entry.p); a.order = w->order.p;
     a.phase = 1;
-    HIP_TRY(pass0());
+    HIP_TRY(launch_search(p.family, p.rows, ix->dev, a, ix->narrow.p, stream, fap));
     if (p.skip_order) a.order = nullptr;
     else HIP_TRY(launch_order(a.entry, w->order.p, (uint32_t)nq, stream));
     a.phase = 2;
-    HIP_TRY(pass0());
+    HIP_TRY(launch_search(p.family, p.rows, ix->dev, a, ix->narrow.p, stream, fap));
     a.phase = 0;
   } else {
-    HIP_TRY(pass0());
+    HIP_TRY(launch_search(p.family, p.rows, ix->dev, a, ix->narrow.p, stream, fap));
   }
   // Re-run pass (normally empty: a launch that scans the statuses and exits): the strict kernel, a few workgroups, candidate heap
   // and a large tier-2 visited set per workgroup in global memory (kFbGrid)
@@ -121,7 +111,7 @@ static hs_status search_dev_group(hs_index *ix, const float *d_q, size_t nq, siz
   a.cand_cap = p.rerun_cand_cap; a.hash_slots = p.rerun_hash_slots; a.vis_bits = 0; a.hash_fill_shift = 0;
   a.fb_cand = w->fb.p; a.fb_spill = w->fb.p + (size_t)kFbGrid * kFbCand * 2; a.spill_slots = kFbSpill;
   a.counters = w->counters.p + 8; a.pass_id = 2;
-  HIP_TRY(strict_go(p.rerun_rows));
+  HIP_TRY(launch_search(HS_PLAN_STRICT, p.rerun_rows, ix->dev, a, ix->narrow.p, stream, fap));
   return HS_OK;
 }
 

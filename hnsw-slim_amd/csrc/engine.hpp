@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "heap_emul.hpp"
 
@@ -93,8 +94,8 @@ size_t fast_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t has
 // Fast path availability for this shape (level-0 tile present, threshold_level == 0, k < ef <= 512).  has_filter: the search
 // names a filter set, which counts as delete marks do (the !bare_bone branches).
 bool fast_supported(const DevIndex &ix, uint32_t ef, uint32_t k, bool has_filter = false);
-// Which instantiation of the fast kernel answers a call that fast_supported() admits: the one table launch_fast_l2 / _ip / _del /
-// _md dispatch on (search_plan.cpp; host only, no HIP call; hs_debug_fast_shape hands it out).
+// Which instantiation of the fast kernel answers a call that fast_supported() admits: the one table the fast launchers and
+// launch_fast_del / _md dispatch on (search_plan.cpp; host only, no HIP call; hs_debug_fast_shape hands it out).
 //   d16  : the distance pass over fp32 rows -- dim / 16 compiled in (> 0), -dim / 4 for a compiled-in dim % 4 == 0 shape off the
 //          SIMD16 path (< -1), 0 = runtime dim with dim % 16 == 0, -1 = any runtime dim.  (The narrow objects hold the d16 = 0
 //          shapes only and take slots / wb from here.)
@@ -107,36 +108,44 @@ FastShape fast_shape(int metric, uint32_t dim, uint32_t ef, uint32_t k, bool bar
 // Strict kernel: the reference's result/candidate arrays with libstdc++ heap mechanics, reference
 // output order.  Fast kernel: same traversal and candidate mechanics, result set kept as a sorted
 // register array; queries whose answer could depend on the result heap's layout are flagged ST_HAZARD.
-// f != null (launch_strict, launch_fast and their narrow forms): the search runs under that filter set -- the !bare_bone branches
-// whether or not the index has delete marks (hnswalg.h:1421, hnswalg_slim.h:1884).
-hipError_t launch_strict(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f = nullptr);
 // order[] = the queries sorted by decreasing entry[].y (distance of the level-0 entry), bucket-exact: the queries likely
 // to take the most expansions start first, so that a launch does not end on a few late-started long ones.
 hipError_t launch_order(const uint4 *entry, uint32_t *order, uint32_t nq, hipStream_t stream);
 // Lean kernel (lean_search.hip): the fast kernel's algorithm with a keys-only result set (no ids, no LDS staging of the merge).
 bool lean_supported(const DevIndex &ix, uint32_t ef, uint32_t k);
 size_t lean_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots);
-hipError_t launch_lean(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
 // Flat kernel (flat_search.hip): lazy candidate heap -- replayed from the insertion log only when its layout decides a pop.
 bool flatk_supported(const DevIndex &ix, uint32_t ef, uint32_t k);
 size_t flatk_lds_bytes(uint32_t dim, uint32_t ef, uint32_t nb);
 uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef);
-hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
 hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, uint2 *d_heap, uint2 *d_pops, uint32_t *d_n, int wave_pop,
                          uint32_t lds_slots, hipStream_t stream);
-hipError_t launch_fast(const DevIndex &ix, const SearchArgs &a, hipStream_t stream, const FilterArgs *f = nullptr);
-// Narrow rows (narrow_rows.hip): `rows` = the index's u8 / fp16 copy of ix.vec in the lane-major layout, fmt = ROWS_U8 | ROWS_F16.
-// launch_flatk_narrow is launch_flatk reading that copy (kernels hs::flat_kernel_u8 / hs::flat_kernel_f16; same shapes, same plan).
-// launch_narrow_convert fills rows [row0, row0 + nrows) of the copy from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to
-// the smallest row that holds a value the format cannot represent.
-// launch_strict_narrow / launch_fast_narrow: launch_strict / launch_fast reading that copy (hs::strict_kernel_u8 / _f16,
-// hs::fast_kernel_u8 / _f16; the runtime-dim shapes, dim % 16 == 0).  With them no search kernel needs ix.vec, which an index
-// may then drop (hs_index_set_f32_resident): launch_strict / launch_fast / launch_lean / launch_flatk return
-// hipErrorInvalidDevicePointer instead of launching when ix.vec is null and the index is not empty.
-// launch_narrow_widen is the inverse of the conversion: rows [row0, row0 + nrows) of d_vec from the copy (exact).
-hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream);
-hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f = nullptr);
-hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f = nullptr);
+
+// ---- launching a search kernel ----------------------------------------------------------------------------------------------
+// launch_search (search_launch.cpp) is the one way in: the kernel family (hs_plan_family) over rows of format row_fmt (ROWS_F32:
+// ix.vec; ROWS_U8 | ROWS_F16: narrow_rows, the index's copy of ix.vec in the lane-major layout of narrow_rows.hip), metric ix.metric.
+// f != null: the search runs under that filter set -- the !bare_bone branches whether or not the index has delete marks
+// (hnswalg.h:1421, hnswalg_slim.h:1884); strict and fast kernels only.  It launches nothing and returns
+//   hipErrorInvalidDevicePointer  when the row array the kernel would read is null and the index is not empty (an index may drop
+//                                 its fp32 rows, hs_index_set_f32_resident: no search kernel dereferences null on the device);
+//   hipErrorInvalidValue          for a narrow format with dim % 16 != 0, for a family / format / metric that does not exist or has
+//                                 no kernel (the lean kernel has no narrow twin), and for a filter set handed to the flat or lean kernel.
+// Behind it is a table [family][row format][metric] of launchers, one per (family, row format, metric), each defined by the
+// object that holds its kernels (beam_search.hip: strict and fast; flat_search.hip: flat; lean_search.hip: lean), each computing
+// its LDS size from its own layout function and picking the instantiation for the shape.  HS_LAUNCHER names them -- here, where
+// they are defined, and in the table -- with rows = f32 | u8 | f16 and metric = l2 | ip.
+using SearchLauncher = hipError_t (*)(const DevIndex &, const SearchArgs &, const void *rows, hipStream_t, const FilterArgs *);
+hipError_t launch_search(int family, int row_fmt, const DevIndex &ix, const SearchArgs &a, const void *narrow_rows, hipStream_t stream,
+                         const FilterArgs *f);
+#define HS_LAUNCHER_(family, rows, metric) launch_##family##_##rows##_##metric
+#define HS_LAUNCHER(family, rows, metric) HS_LAUNCHER_(family, rows, metric)   // (rows may itself be a macro: HS_ROWS_ID of the kernel files)
+#define HS_LAUNCHERS(family, rows) HS_LAUNCHER(family, rows, l2), HS_LAUNCHER(family, rows, ip)
+std::remove_pointer_t<SearchLauncher> HS_LAUNCHERS(strict, f32), HS_LAUNCHERS(strict, f16), HS_LAUNCHERS(strict, u8), HS_LAUNCHERS(fast, f32),
+    HS_LAUNCHERS(fast, f16), HS_LAUNCHERS(fast, u8), HS_LAUNCHERS(flat, f32), HS_LAUNCHERS(flat, f16), HS_LAUNCHERS(flat, u8), HS_LAUNCHERS(lean, f32);
+
+// Narrow rows (narrow_rows.hip): launch_narrow_convert fills rows [row0, row0 + nrows) of the index's u8 / fp16 copy (fmt = ROWS_U8
+// | ROWS_F16) from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to the smallest row that holds a value the format cannot
+// represent.  launch_narrow_widen is the inverse of the conversion: rows [row0, row0 + nrows) of d_vec from the copy (exact).
 hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
                                  hipStream_t stream);
 hipError_t launch_narrow_widen(const void *d_rows, float *d_vec, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, hipStream_t stream);

@@ -1030,70 +1030,73 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
   return 0;
 }
 
-// The three entry points differ in the rows they read and in nothing else: hs::flat_kernel the resident fp32 rows (ix.vec),
-// hs::flat_kernel_u8 / hs::flat_kernel_f16 the index's narrow copy (hs_index_set_row_format), each compiled as objects of its own
-// (HS_TU_ROWS = 0 | 1 | 2 beside HS_TU_METRIC: Makefile) so that a kernel trace shows them as separate rows.
-#define HS_FLAT_KERNEL_BODY(ROWS)                                                                                        \
-  extern __shared__ __align__(16) unsigned char smem_raw[];                                                              \
-  lds_u8 *smem = (lds_u8 *)smem_raw;                                                                                     \
-  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {                                                           \
-    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;                                                    \
-    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;   /* pass 0 takes every query */            \
-    const int rc = search_one_flat<METRIC, S, D16>(ix, a, qi, smem, ROWS);                                               \
-    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;                                                           \
-    wave_sync();                                                                                                         \
-  }
+// The entry point, once per row format: hs::flat_kernel reads the resident fp32 rows (ix.vec), hs::flat_kernel_u8 /
+// hs::flat_kernel_f16 the index's narrow copy (hs_index_set_row_format), handed over as a kernel argument of its own; they differ in
+// nothing else.  Each is compiled as objects of its own (HS_TU_ROWS = 0 | 1 | 2 beside HS_TU_METRIC: Makefile) so that a kernel
+// trace shows them as separate rows.  What differs between the row formats, all of it:
 #if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
-template <int METRIC, int S, int D16>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel(DevIndex ix, SearchArgs a) {
-  HS_FLAT_KERNEL_BODY(ix.vec)
-}
-#define HS_FLAT_KERNEL flat_kernel
-#define HS_FLAT_ROWS_ARG
-#elif HS_TU_ROWS == 1
-template <int METRIC, int S, int D16>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel_u8(DevIndex ix, SearchArgs a, const uint8_t *rows) {
-  HS_FLAT_KERNEL_BODY(rows)
-}
-#define HS_FLAT_KERNEL flat_kernel_u8
-#define HS_FLAT_ROWS_ARG , reinterpret_cast<const uint8_t *>(rows)
+#define HS_ROWS_ID f32               // the launchers' names (engine.hpp HS_LAUNCHER)
+#define HS_KERNEL(name) name         // the kernel's name
+#define HS_ROWS_PARAM                // its trailing parameter
+#define HS_ROWS_READ ix.vec          // the rows the search body reads
+#define HS_ROWS_ARG                  // the launcher's `rows` as that parameter
 #else
-template <int METRIC, int S, int D16>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) flat_kernel_f16(DevIndex ix, SearchArgs a, const _Float16 *rows) {
-  HS_FLAT_KERNEL_BODY(rows)
-}
-#define HS_FLAT_KERNEL flat_kernel_f16
-#define HS_FLAT_ROWS_ARG , reinterpret_cast<const _Float16 *>(rows)
+#if HS_TU_ROWS == 1
+#define HS_ROWS_ID u8
+#define HS_KERNEL(name) name##_u8
+typedef uint8_t TuRow;
+#else
+#define HS_ROWS_ID f16
+#define HS_KERNEL(name) name##_f16
+typedef _Float16 TuRow;
 #endif
-
-// (`rows`: the narrow copy, nullptr in the fp32 objects)
-template <typename K, typename... R>
-static hipError_t flat_launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, R... rows) {
-  if (a.nq == 0) return hipSuccess;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+#define HS_ROWS_PARAM , const TuRow *rows
+#define HS_ROWS_READ rows
+#define HS_ROWS_ARG , reinterpret_cast<const TuRow *>(rows)
+#endif
+template <int METRIC, int S, int D16>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) HS_KERNEL(flat_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  lds_u8 *smem = (lds_u8 *)smem_raw;
+  for (uint32_t it = blockIdx.x; it < a.nq; it += gridDim.x) {
+    const uint32_t qi = (a.phase == 2 && a.order) ? a.order[it] : it;
+    if (a.pass_id != 0 && !((1u << a.status[qi]) & a.select_mask)) continue;   // pass 0 takes every query
+    const int rc = search_one_flat<METRIC, S, D16>(ix, a, qi, smem, HS_ROWS_READ);
+    if (rc == 3 && threadIdx.x == 0) a.status[qi] = ST_HAZARD;
+    wave_sync();
   }
-  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a, rows...);
-  return hipGetLastError();
+}
+
+// Which instantiation answers a shape -- the only place the two ladders are written: result-set slots per lane S from ef, the
+// compiled-in dim / 16 from dim (D16 = 0: runtime dim, -1: runtime dim beyond 256).  The launchers below dispatch on it and the
+// plan sizes a wave's LDS share from it (flatk_waves_per_cu).
+struct FlatShape { int S, D16; };
+constexpr FlatShape flat_shape(uint32_t dim, uint32_t ef) {
+  return {ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 192 ? 3 /* (three slots instead of four: ef = 160 +5.5 %, 192 +3.5 %) */ : ef <= 256 ? 4 : ef <= 384 ? 6 : 8,
+          dim == 128 ? 8 : dim == 96 ? 6 : dim == 960 ? 60 : dim > 256 ? -1 : 0};
 }
 template <int METRIC, int D16>
-static hipError_t flat_launch_d(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) {
+static hipError_t flat_launch_d(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, int s) {
   const size_t lds = flat_layout(ix.dim, a.ef, a.fl_nb).total;
-  if (a.ef <= 64) return flat_launch(HS_FLAT_KERNEL<METRIC, 1, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
-  if (a.ef <= 128) return flat_launch(HS_FLAT_KERNEL<METRIC, 2, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
-  if (a.ef <= 192) return flat_launch(HS_FLAT_KERNEL<METRIC, 3, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);   // (three slots instead of four: ef = 160 +5.5 %, 192 +3.5 %)
-  if (a.ef <= 256) return flat_launch(HS_FLAT_KERNEL<METRIC, 4, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
-  if (a.ef <= 384) return flat_launch(HS_FLAT_KERNEL<METRIC, 6, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
-  return flat_launch(HS_FLAT_KERNEL<METRIC, 8, D16>, ix, a, lds, stream HS_FLAT_ROWS_ARG);
+  switch (s) {
+    case 1: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 1, D16>, ix, a, lds, stream HS_ROWS_ARG);
+    case 2: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 2, D16>, ix, a, lds, stream HS_ROWS_ARG);
+    case 3: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 3, D16>, ix, a, lds, stream HS_ROWS_ARG);
+    case 4: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 4, D16>, ix, a, lds, stream HS_ROWS_ARG);
+    case 6: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 6, D16>, ix, a, lds, stream HS_ROWS_ARG);
+    default: return launch_kernel(HS_KERNEL(flat_kernel)<METRIC, 8, D16>, ix, a, lds, stream HS_ROWS_ARG);
+  }
 }
 template <int METRIC>
 static hipError_t flat_launch_s(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) {
-  if (ix.dim == 128) return flat_launch_d<METRIC, 8>(ix, a, rows, stream);
-  if (ix.dim == 96) return flat_launch_d<METRIC, 6>(ix, a, rows, stream);
-  if (ix.dim == 960) return flat_launch_d<METRIC, 60>(ix, a, rows, stream);
-  if (ix.dim > 256) return flat_launch_d<METRIC, -1>(ix, a, rows, stream);
-  return flat_launch_d<METRIC, 0>(ix, a, rows, stream);
+  const FlatShape sh = flat_shape(ix.dim, a.ef);
+  switch (sh.D16) {
+    case 8: return flat_launch_d<METRIC, 8>(ix, a, rows, stream, sh.S);
+    case 6: return flat_launch_d<METRIC, 6>(ix, a, rows, stream, sh.S);
+    case 60: return flat_launch_d<METRIC, 60>(ix, a, rows, stream, sh.S);
+    case -1: return flat_launch_d<METRIC, -1>(ix, a, rows, stream, sh.S);
+    default: return flat_launch_d<METRIC, 0>(ix, a, rows, stream, sh.S);
+  }
 }
 
 #if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
@@ -1136,8 +1139,6 @@ hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, 
 }
 #endif
 
-hipError_t launch_flatk_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
-hipError_t launch_flatk_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
 #if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
 bool flatk_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
   return ix.tile0 != nullptr && (ix.maxlevel == 0 || ix.uptile != nullptr) && ix.threshold_level == 0 && !ix.has_deleted && ix.n > 0 &&
@@ -1145,34 +1146,23 @@ bool flatk_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
 }
 // wavefronts per CU the shape's kernel is resident with (the LDS share of a wave follows from it: search_plan.cpp plan_flat)
 uint32_t flatk_waves_per_cu(uint32_t dim, uint32_t ef) {
-  const int s = ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 192 ? 3 : ef <= 256 ? 4 : ef <= 384 ? 6 : 8;
-  const int d16 = dim == 128 ? 8 : dim == 96 ? 6 : dim == 960 ? 60 : dim > 256 ? -1 : 0;
-  return 4u * (uint32_t)flat_waves(s, d16);
+  const FlatShape sh = flat_shape(dim, ef);
+  return 4u * (uint32_t)flat_waves(sh.S, sh.D16);
 }
 size_t flatk_lds_bytes(uint32_t dim, uint32_t ef, uint32_t nb) { return flat_layout(dim, ef, nb).total; }
-hipError_t launch_flatk_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, nullptr, stream); }
-hipError_t launch_flatk(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
-  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;   // fp32 rows dropped: launch_flatk_narrow serves the index
-  return ix.metric == METRIC_L2 ? launch_flatk_l2(ix, a, stream) : launch_flatk_ip(ix, a, stream);
+#endif
+#endif
+
+// This object's launchers (engine.hpp), one per metric it holds.  (No filter-set form: launch_search refuses a filter set.)
+#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+hipError_t HS_LAUNCHER(flat, HS_ROWS_ID, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *) {
+  return flat_launch_s<METRIC_L2>(ix, a, rows, stream);
 }
 #endif
 #if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
-hipError_t launch_flatk_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, nullptr, stream); }
-#endif
-#elif HS_TU_ROWS == 1   // the narrow objects: one launcher per metric (dispatch: narrow_rows.hip launch_flatk_narrow)
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
-hipError_t launch_flatk_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, rows, stream); }
-#endif
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
-hipError_t launch_flatk_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, rows, stream); }
-#endif
-#else
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
-hipError_t launch_flatk_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_L2>(ix, a, rows, stream); }
-#endif
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
-hipError_t launch_flatk_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream) { return flat_launch_s<METRIC_IP>(ix, a, rows, stream); }
-#endif
+hipError_t HS_LAUNCHER(flat, HS_ROWS_ID, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *) {
+  return flat_launch_s<METRIC_IP>(ix, a, rows, stream);
+}
 #endif
 
 }  // namespace hs

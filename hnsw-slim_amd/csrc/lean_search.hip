@@ -499,22 +499,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HS_LEAN
   }
 }
 
-template <typename K>
-static hipError_t lean_launch(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream) {
-  if (a.nq == 0) return hipSuccess;
-  if (lds > 64 * 1024) {   // (a large user cand_cap, or the candidate share after hs_search_check doubled it)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a);
-  return hipGetLastError();
-}
 template <int METRIC, int D16>
 static hipError_t lean_launch_d(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
   const size_t lds = lean_layout(ix.dim, a.ef, a.cand_cap, a.hash_slots).total;
-  if (a.ef <= 64) return lean_launch(lean_kernel<METRIC, 1, D16>, ix, a, lds, stream);
-  if (a.ef <= 128) return lean_launch(lean_kernel<METRIC, 2, D16>, ix, a, lds, stream);
-  return lean_launch(lean_kernel<METRIC, 4, D16>, ix, a, lds, stream);
+  if (a.ef <= 64) return launch_kernel(lean_kernel<METRIC, 1, D16>, ix, a, lds, stream);
+  if (a.ef <= 128) return launch_kernel(lean_kernel<METRIC, 2, D16>, ix, a, lds, stream);
+  return launch_kernel(lean_kernel<METRIC, 4, D16>, ix, a, lds, stream);
 }
 template <int METRIC>
 static hipError_t lean_launch_s(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
@@ -523,8 +513,6 @@ static hipError_t lean_launch_s(const DevIndex &ix, const SearchArgs &a, hipStre
   return lean_launch_d<METRIC, 0>(ix, a, stream);
 }
 
-hipError_t launch_lean_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
-hipError_t launch_lean_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream);
 #if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
 bool lean_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
   return ix.tile0 != nullptr && (ix.maxlevel == 0 || ix.uptile != nullptr) && ix.threshold_level == 0 && !ix.has_deleted && ix.n > 0 &&
@@ -533,14 +521,15 @@ bool lean_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
 // Where it is the better kernel: measured only on the shapes it is compiled for with a compile-time dim (L2, d = 96 / 128); every
 // other shape would take its runtime-dim distance loop against the fast kernel's compiled-in one.
 size_t lean_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots) { return lean_layout(dim, ef, cand_cap, hash_slots).total; }
-hipError_t launch_lean_l2(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return lean_launch_s<METRIC_L2>(ix, a, stream); }
-hipError_t launch_lean(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) {
-  if (ix.vec == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;   // fp32 rows dropped (hs_index_set_f32_resident): this kernel has no narrow twin
-  return ix.metric == METRIC_L2 ? launch_lean_l2(ix, a, stream) : launch_lean_ip(ix, a, stream);
+// (fp32 rows only: this kernel has no narrow twin, nor a filter-set form -- launch_search refuses both)
+hipError_t HS_LAUNCHER(lean, f32, l2)(const DevIndex &ix, const SearchArgs &a, const void *, hipStream_t stream, const FilterArgs *) {
+  return lean_launch_s<METRIC_L2>(ix, a, stream);
 }
 #endif
 #if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
-hipError_t launch_lean_ip(const DevIndex &ix, const SearchArgs &a, hipStream_t stream) { return lean_launch_s<METRIC_IP>(ix, a, stream); }
+hipError_t HS_LAUNCHER(lean, f32, ip)(const DevIndex &ix, const SearchArgs &a, const void *, hipStream_t stream, const FilterArgs *) {
+  return lean_launch_s<METRIC_IP>(ix, a, stream);
+}
 #endif
 
 }  // namespace hs

@@ -1,6 +1,6 @@
 // narrow_rows.hip -- the narrow copy of an index's rows (hs_index_set_row_format): layout, device conversion with the
-// representability check, its inverse (widening, exact), and the dispatch to the narrow entry points of the flat kernel
-// (flat_search_u8.hip / flat_search_f16.hip) and of the strict and fast kernels (beam_search_u8.hip / beam_search_f16.hip).
+// representability check, and its inverse (widening, exact).  The kernels that search over the copy are the narrow objects of
+// flat_search.hip and beam_search.hip (flat_search_u8.hip, beam_search_f16.hip, ...), reached through launch_search (engine.hpp).
 //
 // Layout (narrow_rows.hpp narrow_slot): row r occupies dim elements at r * dim, lane-major for the flat kernel's 8 lanes per row,
 //   narrow[r * dim + s * (dim / 8) + 2 i + e] = x[r][16 i + 2 s + e]      s = 0..7, i = 0..dim/16 - 1, e = 0..1
@@ -60,37 +60,6 @@ static hipError_t widen_t(const void *d_rows, float *d_vec, uint32_t row0, uint3
 }
 hipError_t launch_narrow_widen(const void *d_rows, float *d_vec, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, hipStream_t stream) {
   return fmt == ROWS_U8 ? widen_t<uint8_t>(d_rows, d_vec, row0, nrows, dim, stream) : widen_t<_Float16>(d_rows, d_vec, row0, nrows, dim, stream);
-}
-
-hipError_t launch_flatk_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
-hipError_t launch_flatk_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
-hipError_t launch_flatk_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
-hipError_t launch_flatk_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream);
-hipError_t launch_flatk_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream) {
-  if (fmt == ROWS_U8) return ix.metric == 0 ? launch_flatk_u8_l2(ix, a, rows, stream) : launch_flatk_u8_ip(ix, a, rows, stream);
-  return ix.metric == 0 ? launch_flatk_f16_l2(ix, a, rows, stream) : launch_flatk_f16_ip(ix, a, rows, stream);
-}
-
-// strict / fast kernels over the copy: same LDS layouts and scratch shares as launch_strict / launch_fast
-#define HS_DECL_NARROW(name)                                                                                              \
-  hipError_t name##_u8_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);     \
-  hipError_t name##_u8_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);     \
-  hipError_t name##_f16_l2(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);    \
-  hipError_t name##_f16_ip(const DevIndex &ix, const SearchArgs &a, const void *rows, size_t lds, hipStream_t stream, const FilterArgs *f);    \
-  static hipError_t name##_by(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, size_t lds, hipStream_t stream, const FilterArgs *f) { \
-    if (rows == nullptr && ix.n > 0) return hipErrorInvalidDevicePointer;                                                 \
-    if ((ix.dim & 15u) != 0 || (fmt != ROWS_U8 && fmt != ROWS_F16)) return hipErrorInvalidValue;                          \
-    if (fmt == ROWS_U8) return ix.metric == 0 ? name##_u8_l2(ix, a, rows, lds, stream, f) : name##_u8_ip(ix, a, rows, lds, stream, f);     \
-    return ix.metric == 0 ? name##_f16_l2(ix, a, rows, lds, stream, f) : name##_f16_ip(ix, a, rows, lds, stream, f);            \
-  }
-HS_DECL_NARROW(launch_strict)
-HS_DECL_NARROW(launch_fast)
-#undef HS_DECL_NARROW
-hipError_t launch_strict_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f) {
-  return launch_strict_by(ix, a, rows, fmt, strict_lds_bytes(ix.dim, a.ef, a.fb_cand ? 0u : a.cand_cap, a.hash_slots), stream, f);
-}
-hipError_t launch_fast_narrow(const DevIndex &ix, const SearchArgs &a, const void *rows, int fmt, hipStream_t stream, const FilterArgs *f) {
-  return launch_fast_by(ix, a, rows, fmt, fast_lds_bytes(ix.dim, a.ef, a.cand_cap, a.hash_slots), stream, f);
 }
 
 }  // namespace hs

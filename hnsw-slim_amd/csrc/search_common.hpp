@@ -1,7 +1,10 @@
 // search_common.hpp -- device structures shared by the one-query-per-wavefront search kernels (beam_search.hip, lean_search.hip):
-// the exact two-tier visited set and the candidate min-heap with libstdc++ sift mechanics.
+// the exact two-tier visited set and the candidate min-heap with libstdc++ sift mechanics; and the launch helper of all three
+// kernel files (flat_search.hip too).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "engine.hpp"
 #include "wave_util.hpp"
@@ -254,5 +257,17 @@ __device__ __forceinline__ void flag_query(const SearchArgs &a, uint32_t qi, uin
   }
 }
 
+// Launch of a search kernel: one wavefront per workgroup, min(a.grid, a.nq) workgroups, `lds` bytes of dynamic LDS.
+// (`tail`: the kernel's arguments behind (ix, a) -- the narrow rows in the narrow objects, then the filter set in the filter-set form)
+template <typename K, typename... T>
+static hipError_t launch_kernel(K kern, const DevIndex &ix, const SearchArgs &a, size_t lds, hipStream_t stream, T... tail) {
+  if (a.nq == 0) return hipSuccess;
+  if (lds > 64 * 1024) {   // (a large user cand_cap, or the candidate share after hs_search_check doubled it)
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(std::max(1u, std::min(a.grid, a.nq))), dim3(64), lds, stream, ix, a, tail...);
+  return hipGetLastError();
+}
 
 }  // namespace hs

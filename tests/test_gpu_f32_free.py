@@ -271,6 +271,41 @@ def test_forced_fast_kernel_in_a_child_process(hs, oracle, small_int_index, tmp_
             assert np.array_equal(res[f"{state}_{ef}_{k}_stats"][:, :3], o["counters"][:, :3]), (state, ef, k)
 
 
+@pytest.mark.parametrize("fmt_name", ("HS_ROWS_U8", "HS_ROWS_F16"))
+def test_inner_product_strict_and_fast_twins(hs, oracle, tmp_path, fmt_name):
+    """The inner-product strict and fast twins (every other case of sections 2 and 3 is L2) at the smallest shape that reaches them:
+    d = 16, 200 tie-heavy integer rows, 20 queries, k = 3, ef = 10.  Strict: the exact-order mode, the reference's array order.
+    Fast: under a filter (the !bare S = 1 shape), and bare at ef == k = 65 -- the boundary-watching shape, where the flat kernel
+    does not serve a bare index (k > 64; ef == k = 10 would need HS_KERNEL=fast, read once per process)."""
+    n, d = 200, 16
+    fmt = getattr(hs, fmt_name)
+    base, q = _int_rows(n, d, 5), _int_rows(20, d, 6)
+    hp, sp = str(tmp_path / "h.bin"), str(tmp_path / "s.bin")
+    hs.build_hnsw(base, hp, metric=IP, M=8, ef_construction=60, threads=4)
+    hs.convert_slim(hp, sp, d, metric=IP, threads=4)
+    ix, ox = hs.Index(sp, hs.HS_KIND_SLIM, d, metric=IP), oracle.load(sp, "slim", IP, d)
+    ix.set_ef(10); ox.set_ef(10)
+    ix.set_exact_order(True)
+    r = three_states(hs, ix, fmt, ids(ix, q, 3), "IP exact order", "hs::strict_kernel")
+    ix.set_exact_order(False)
+    o = ox.search_ids(q, 3)
+    assert np.array_equal(r["labels"], o["labels"]) and np.array_equal(r["stats"][:, :3], o["counters"][:, :3])
+    allowed = (np.arange(n) % 3 != 0).astype(np.uint8)
+    r = three_states(hs, ix, fmt, lambda: ix.search_filtered(q, 3, allowed, want_stats=True), "IP filtered", "hs::fast_kernel")
+    ox.set_filter(allowed)
+    o = ox.search_pq(q, 3)
+    ox.set_filter(None)
+    assert np.array_equal(r["cnt"], o["cnt"]) and _pq_sorted(r["dists"], r["labels"], r["cnt"]) == _pq_sorted(o["dists"], o["labels"], o["cnt"])
+    ix.set_ef(65); ox.set_ef(65)
+    r = three_states(hs, ix, fmt, lambda: ix.search_pq(q, 65, want_stats=True), "IP bare ef = k = 65", "hs::fast_kernel")
+    o = ox.search_pq(q, 65)
+    assert np.all(o["cnt"] == 65)   # every query reaches k nodes: searchKnn(q, k, tableint*) below is defined
+    assert np.array_equal(r["cnt"], o["cnt"]) and _pq_sorted(r["dists"], r["labels"], r["cnt"]) == _pq_sorted(o["dists"], o["labels"], o["cnt"])
+    r = three_states(hs, ix, fmt, ids(ix, q, 65), "IP bare ids ef = k = 65", "hs::fast_kernel")
+    o = ox.search_ids(q, 65)
+    assert np.array_equal(np.sort(r["labels"], 1), np.sort(o["labels"], 1)) and np.array_equal(r["stats"][:, :3], o["counters"][:, :3])
+
+
 # ---- 4. the re-run pass ---------------------------------------------------------------------------------------------------------
 RERUN_SEED = 31
 

@@ -1,6 +1,6 @@
 """The fast kernel (csrc/beam_search.hip hs::fast_kernel) at every dim it has a distance pass compiled for, through the calls that
 reach it.  The flat kernel answers a bare index with dim % 16 == 0 only up to k = 64, so a plain top-100 call on a SIFT-, DEEP-,
-GIST- or COHERE-shaped index is a fast-kernel call: the compile-time-dim branch of launch_fast_l2 / launch_fast_ip, S = 2, 4, 8
+GIST- or COHERE-shaped index is a fast-kernel call: the compile-time-dim branch of the fp32 fast launchers (fast_launch_d16), S = 2, 4, 8
 slots per lane by ef, the boundary-watching variant when ef == k.
 
 The dims are not typed in: every (metric, dim) hs_debug_fast_shape reports as compiled (the table the launchers dispatch on), one
