@@ -38,6 +38,7 @@ EXPORTS = [
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
     "hs_queue_create", "hs_queue_free", "hs_queue_submit", "hs_queue_submit_dev", "hs_queue_flush", "hs_queue_wait",
     "hs_queue_join_stream", "hs_queue_drain", "hs_queue_info",
+    "hs_build_hnsw_batched", "hs_build_schedule",
 ]
 
 
@@ -83,6 +84,15 @@ class HsPlanOut(ctypes.Structure):    # hs_plan_out
 class HsQueueInfo(ctypes.Structure):  # struct hs_queue_info
     _fields_ = [("submitted", _u64), ("launches", _u64), ("pending", _u64), ("in_flight", _u64), ("largest_launch", _u64),
                 ("device_bytes", _u64)]
+
+
+class HsBatchBuildOpts(ctypes.Structure):    # hs_batch_build_opts
+    _fields_ = [("device", _i32), ("threads", _i32), ("grow_div", _u64), ("batch_max", _u64), ("scratch_ids", _u64)]
+
+
+class HsBatchBuildStats(ctypes.Structure):   # hs_batch_build_stats
+    _fields_ = [("used_gpu", _i32), ("reserved", _u32), ("batches", _u64), ("flagged_rows", _u64), ("kernel_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
 
 
 class HsFastShape(ctypes.Structure):  # hs_fast_shape
@@ -198,6 +208,10 @@ def lib():
     L.hs_hnsw_replay.argtypes = [ctypes.c_char_p, ci, sz, sz, ci, vp, sz, vp, ctypes.c_char_p]
     L.hs_build_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
     L.hs_build_hnsw_labeled.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ci, ctypes.c_char_p]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_build_hnsw_batched"):   # (a baseline build in an A/B run may predate these)
+        L.hs_build_hnsw_batched.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.c_char_p,
+                                            ctypes.POINTER(HsBatchBuildStats)]
+        L.hs_build_schedule.argtypes = [sz, sz, ctypes.c_char_p, sz, sz, sz, sz, vp, vp, vp, ctypes.POINTER(sz)]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_convert_slimq_graph.argtypes = L.hs_convert_slim.argtypes
     L.hs_host_device_pointer.restype = ctypes.c_void_p
@@ -260,6 +274,40 @@ def build_hnsw(base, out_path, metric=HS_METRIC_L2, M=16, ef_construction=200, b
         return
     _check(lib().hs_build_hnsw(base.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction,
                                str(branching_factor).encode(), seed, threads, out_path.encode()))
+
+
+def build_hnsw_batched(base, out_path, metric=HS_METRIC_L2, M=16, ef_construction=200, branching_factor="4", seed=100, device=-1, threads=1,
+                       grow_div=0, batch_max=0, scratch_ids=0, labels=None):
+    """hs_build_hnsw_batched: batched addPoint (DESIGN.md 4m) on HIP device `device`, or on the host twin (device=-1, `threads` workers);
+    both write the same file, and batch_max=1 writes build_hnsw(threads=1)'s.  Returns the stats as a dict: used_gpu, batches,
+    flagged_rows, kernel_ms, total_ms."""
+    base = np.ascontiguousarray(base, np.float32)
+    if base.ndim != 2:
+        raise HsError(HS_ERR_INVALID, "base: rows x dim")
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, np.uint64)
+        if lab.shape != (base.shape[0],):
+            raise HsError(HS_ERR_INVALID, "labels: one per row")
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsBatchBuildStats()
+    _check(lib().hs_build_hnsw_batched(base.ctypes.data, lab.ctypes.data if lab is not None else None, base.shape[0], base.shape[1], metric, M,
+                                       ef_construction, str(branching_factor).encode(), seed, ctypes.byref(opts), out_path.encode(),
+                                       ctypes.byref(st)))
+    return {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows), "kernel_ms": st.kernel_ms,
+            "total_ms": st.total_ms}
+
+
+def build_schedule(n, M=16, branching_factor="4", seed=100, grow_div=0, batch_max=0):
+    """hs_build_schedule (host only): the batches build_hnsw_batched inserts n rows in -- their sizes, and the entry point (0xFFFFFFFF:
+    none yet) and top level (-1) before each."""
+    nb = ctypes.c_size_t(0)
+    bf = str(branching_factor).encode()
+    _check(lib().hs_build_schedule(n, M, bf, seed, grow_div, batch_max, 0, None, None, None, ctypes.byref(nb)))
+    sizes, eps, tops = np.zeros(nb.value, np.uint32), np.zeros(nb.value, np.uint32), np.zeros(nb.value, np.int32)
+    _check(lib().hs_build_schedule(n, M, bf, seed, grow_div, batch_max, nb.value, sizes.ctypes.data, eps.ctypes.data, tops.ctypes.data,
+                                   ctypes.byref(nb)))
+    return {"sizes": sizes, "entry_points": eps, "top_levels": tops}
 
 
 def hnsw_resume(in_path, out_path, rows, labels, dim=None, metric=HS_METRIC_L2, max_elements=0, seed=100, drawn=0, threads=1):

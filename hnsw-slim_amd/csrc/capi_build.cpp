@@ -2,7 +2,10 @@
 // brute force, and the exact search over a resident index's rows.
 #include "capi_internal.hpp"
 
+#include <chrono>
+
 #include "bf_engine.hpp"
+#include "build_engine.hpp"
 #include "exact_engine.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -22,6 +25,104 @@ hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_
     VanillaGraph g;
     g.build(base, n, dim, (Metric)metric, M, ef_construction, branching_factor, seed, threads, labels);
     g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return HS_OK;
+}
+
+// ---- batched addPoint (host_batch_build.hpp; on a device build_gpu.hip) -------------------------------------------------------------
+static bool pow2(uint64_t v) { return v && (v & (v - 1)) == 0; }
+
+// The device build's lists into the image VanillaGraph::save writes: rows and labels as begin_insert lays them out, the level-0 lists
+// in front of them, the upper lists per node, entry point and top level as the schedule ends.
+static void image_from_lists(VanillaGraph &g, const float *base, const uint64_t *labels, const std::vector<int> &lv, const std::vector<BatchStep> &steps,
+                             const std::vector<uint32_t> &l0, const std::vector<uint32_t> &lu, const std::vector<uint32_t> &upb, int threads) {
+  const size_t n = g.max_elements, s0 = g.maxM0 + 1, su = g.maxM + 1;
+  parallel_for(n, threads, 1024, [&](size_t i, int) {
+    char *e = g.el((uint32_t)i);
+    memcpy(e, l0.data() + i * s0, g.size_links0);
+    memcpy(e + g.offsetData, base + i * g.dim, 4 * g.dim);
+    const uint64_t lab = labels ? labels[i] : i;
+    memcpy(e + g.label_offset, &lab, 8);
+    g.levels[i] = lv[i];
+    if (lv[i]) {
+      g.links[i].assign(g.size_links_up * lv[i] + 1, 0);
+      memcpy(g.links[i].data(), lu.data() + (size_t)upb[i] * su, g.size_links_up * lv[i]);
+    }
+  });
+  g.count = n;
+  for (const BatchStep &s : steps)
+    for (uint32_t p = s.begin; p < s.begin + s.size; p++)
+      if (lv[p] > g.maxlevel) { g.maxlevel = lv[p]; g.enterpoint = p; }
+}
+
+hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
+                                const char *branching_factor, size_t seed, const hs_batch_build_opts *opts, const char *out_path,
+                                hs_batch_build_stats *stats) {
+  if (!base || !out_path || !branching_factor || !opts || n == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
+  if (M == 0) return fail(HS_ERR_INVALID, "M must be > 0");
+  if (n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "too many rows");
+  if (opts->device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host twin) or a HIP device");
+  if (opts->scratch_ids && (!pow2(opts->scratch_ids) || opts->scratch_ids < 64 || opts->scratch_ids > 8192))
+    return fail(HS_ERR_INVALID, "scratch_ids: 0 or a power of two from 64 to 8192");
+  if (opts->grow_div > 0xFFFFFFFFu || opts->batch_max > 0xFFFFFFFFu) return fail(HS_ERR_INVALID, "grow_div / batch_max out of range");
+  if (opts->device >= 0 && hs_device_count() <= opts->device) return fail(HS_ERR_DEVICE, "no HIP device");
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_batch_build_stats st{};
+  try {
+    VanillaGraph g;
+    const int threads = std::max(1, (int)opts->threads);
+    bool on_device = false;
+    if (opts->device >= 0) {
+      g.init(n, dim, (Metric)metric, M, ef_construction, branching_factor);
+      on_device = gpu_build_supported((uint32_t)dim, (uint32_t)g.M, (uint32_t)g.efC, (uint32_t)opts->scratch_ids);
+    }
+    if (on_device) {
+      const std::vector<int> lv = draw_levels(n, g.mult, seed);
+      const std::vector<BatchStep> steps = batch_schedule(lv.data(), n, opts->grow_div, opts->batch_max);
+      GpuBuildInput in;
+      in.base = base; in.n = (uint32_t)n; in.dim = (uint32_t)dim; in.metric = metric;
+      in.M = (uint32_t)g.M; in.maxM = (uint32_t)g.maxM; in.maxM0 = (uint32_t)g.maxM0; in.efc = (uint32_t)g.efC;
+      in.levels = lv.data(); in.steps = &steps; in.scratch_ids = (uint32_t)opts->scratch_ids;
+      std::vector<uint32_t> l0, lu, upb;
+      uint64_t flagged = 0;
+      const hipError_t e = gpu_batch_build(in, opts->device, l0, lu, upb, flagged, &st.kernel_ms);
+      if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("batched build: ") + hipGetErrorString(e));
+      image_from_lists(g, base, labels, lv, steps, l0, lu, upb, threads);
+      st.used_gpu = 1; st.batches = steps.size(); st.flagged_rows = flagged;
+    } else {
+      BatchBuildStats bs;
+      batch_build_host(g, base, n, dim, (Metric)metric, M, ef_construction, branching_factor, seed, threads, labels, opts->grow_div, opts->batch_max, &bs);
+      st.batches = bs.batches;
+    }
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (stats) *stats = st;
+  return HS_OK;
+}
+
+hs_status hs_build_schedule(size_t n, size_t M, const char *branching_factor, size_t seed, size_t grow_div, size_t batch_max, size_t cap,
+                            uint32_t *sizes, uint32_t *entry_points, int32_t *top_levels, size_t *n_batches) {
+  if (!branching_factor || !n_batches || n == 0 || M == 0 || n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "bad argument");
+  try {
+    const std::vector<int> lv = draw_levels(n, branching_mult(branching_factor, M), seed);
+    const std::vector<BatchStep> steps = batch_schedule(lv.data(), n, grow_div, batch_max);
+    *n_batches = steps.size();
+    for (size_t b = 0; b < std::min(cap, steps.size()); b++) {
+      if (sizes) sizes[b] = steps[b].size;
+      if (entry_points) entry_points[b] = steps[b].ep;
+      if (top_levels) top_levels[b] = steps[b].top;
+    }
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
   } catch (std::exception &e) {

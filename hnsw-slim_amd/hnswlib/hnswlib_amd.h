@@ -308,6 +308,9 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
   std::vector<uint64_t> row_labels_;
   bool dirty_ = false;
   int build_threads_ = 1;
+  int build_device_ = -1;                       // setBuildOnDevice: the device the deferred build runs on (-1: the host builder)
+  size_t build_batch_max_ = 0;
+  hs_batch_build_stats build_stats_{};
   bool allow_replace_ = false;                  // the constructors' allow_replace_deleted
   bool has_image_ = false;                      // the loaded index keeps its host image (loaded with room)
   bool marks_changed_ = false;                  // markDelete / unmarkDelete since the load
@@ -323,8 +326,15 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
   std::string tmp_path_;   // index file of a graph that was built here and never saved by the caller
   void materialize(const std::string &location) {
     if (row_labels_.empty()) throw std::runtime_error("hnswlib_amd: nothing to build (no addPoint calls)");
-    detail::check(hs_build_hnsw_labeled(rows_.data(), row_labels_.data(), row_labels_.size(), detail::dim_of(space_), detail::metric_of(space_),
-                                        M_, efc_, branching_.c_str(), seed_, build_threads_, location.c_str()));
+    if (build_device_ >= 0) {   // setBuildOnDevice: batched addPoint on the device (hs_build_hnsw_batched)
+      hs_batch_build_opts o{};
+      o.device = build_device_; o.threads = build_threads_; o.batch_max = build_batch_max_;
+      detail::check(hs_build_hnsw_batched(rows_.data(), row_labels_.data(), row_labels_.size(), detail::dim_of(space_), detail::metric_of(space_),
+                                          M_, efc_, branching_.c_str(), seed_, &o, location.c_str(), &build_stats_));
+    } else {
+      detail::check(hs_build_hnsw_labeled(rows_.data(), row_labels_.data(), row_labels_.size(), detail::dim_of(space_), detail::metric_of(space_),
+                                          M_, efc_, branching_.c_str(), seed_, build_threads_, location.c_str()));
+    }
     const size_t ef_keep = ef_;
     load(location, HS_KIND_HNSW, space_, max_elements_);
     setEf(ef_keep);
@@ -371,6 +381,10 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     row_labels_.reserve(max_elements);
   }
   void setBuildThreads(int t) { build_threads_ = t < 1 ? 1 : t; }   // 1 = the reference's serial addPoint loop, byte for byte
+  // The deferred build as batched addPoint on HIP device `device` (hs_build_hnsw_batched; batch_max 0: its default schedule,
+  // 1: the reference's serial order, byte for byte).  A negative device goes back to the host builder.  Not called: nothing changes.
+  void setBuildOnDevice(int device, size_t batch_max = 0) { build_device_ = device < 0 ? -1 : device; build_batch_max_ = batch_max; }
+  const hs_batch_build_stats &buildStats() const { return build_stats_; }   // of the last build that went through setBuildOnDevice
   void loadIndex(const std::string &location, SpaceInterface<float> *s, size_t max_elements_i = 0) {
     space_ = s;
     rows_.clear(); row_labels_.clear(); collected_.clear(); dirty_ = false;

@@ -584,6 +584,38 @@ hs_status hs_build_hnsw(const float *base, size_t n, size_t dim, int metric, siz
 hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M,
                                 size_t ef_construction, const char *branching_factor, size_t seed, int threads,
                                 const char *out_path);
+/* Batched addPoint: the same index file from an insertion order that is parallel and still deterministic.  Points
+ * enter in id order, in batches; every point of a batch runs the search half of addPoint against the graph as it stood when the
+ * batch began, and the writes (mutuallyConnectNewElement) are applied in ascending id.  The next batch holds
+ * min(batch_max, max(1, inserted / grow_div), n - inserted) rows and is cut right after the first row whose level exceeds the top
+ * level so far.  batch_max == 1 is the reference's serial order: the bytes of hs_build_hnsw(threads = 1).  Any other schedule
+ * writes a graph of its own that does not depend on `threads`, on timing, or on where it was built.
+ * device >= 0: the searches, the heuristic and the reverse links run on that HIP device (build_gpu.hip) and write the bytes of the
+ * host twin (device == -1, `threads` workers for the searches).  Shapes outside the device path -- M > 31, ef_construction > 512,
+ * a row that does not fit the on-chip memory -- build on the host twin with used_gpu = 0.  scratch_ids: the ids one row's visited
+ * set may hold on chip (a power of two from 64 to 8192; its candidate heap holds half as many); a row that outgrows it is flagged and searched again with its
+ * scratch in device memory, never answered wrong.  In the options 0 means the default (grow_div 16, batch_max 16384,
+ * scratch_ids 4096). */
+typedef struct hs_batch_build_opts {
+  int32_t device;       /* -1: the host twin */
+  int32_t threads;      /* host workers (< 1: one) */
+  uint64_t grow_div, batch_max, scratch_ids;
+} hs_batch_build_opts;
+typedef struct hs_batch_build_stats {
+  int32_t used_gpu;
+  uint32_t reserved;
+  uint64_t batches, flagged_rows;
+  double kernel_ms;     /* device time from the first kernel to the last (0 on the host twin) */
+  double total_ms;      /* wall time of the call, the file write included */
+} hs_batch_build_stats;
+hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels /* nullable: the row index */, size_t n, size_t dim, int metric,
+                                size_t M, size_t ef_construction, const char *branching_factor, size_t seed,
+                                const hs_batch_build_opts *opts, const char *out_path, hs_batch_build_stats *stats /* nullable */);
+/* Host only.  The schedule hs_build_hnsw_batched follows for these parameters: *n_batches batches, and for batch b < cap its size
+ * (sizes[b]) and the entry point (0xFFFFFFFF: none yet) and top level (-1) before it (entry_points[b], top_levels[b]); the three
+ * arrays are nullable and hold `cap` entries. */
+hs_status hs_build_schedule(size_t n, size_t M, const char *branching_factor, size_t seed, size_t grow_div, size_t batch_max, size_t cap,
+                            uint32_t *sizes, uint32_t *entry_points, int32_t *top_levels, size_t *n_batches);
 /* Host only, no device: loadIndex(in_path, space, max_elements), level generator seeded with `seed` and `drawn` draws discarded
  * (hs_index_seed_levels), addPoint(rows + i*dim, labels[i]) for i < count, saveIndex(out_path).  threads == 1 is the reference's
  * serial order: resuming the first n0 rows' build with the remaining rows writes the bytes of the one-shot build.  Refusals as
