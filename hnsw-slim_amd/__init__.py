@@ -39,6 +39,7 @@ EXPORTS = [
     "hs_queue_create", "hs_queue_free", "hs_queue_submit", "hs_queue_submit_dev", "hs_queue_flush", "hs_queue_wait",
     "hs_queue_join_stream", "hs_queue_drain", "hs_queue_info",
     "hs_build_hnsw_batched", "hs_build_schedule",
+    "hs_index_add_points_batched", "hs_hnsw_resume_batched", "hs_debug_batched_add_changed",
 ]
 
 
@@ -212,6 +213,11 @@ def lib():
         L.hs_build_hnsw_batched.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.c_char_p,
                                             ctypes.POINTER(HsBatchBuildStats)]
         L.hs_build_schedule.argtypes = [sz, sz, ctypes.c_char_p, sz, sz, sz, sz, vp, vp, vp, ctypes.POINTER(sz)]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_index_add_points_batched"):
+        L.hs_index_add_points_batched.argtypes = [vp, vp, vp, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.POINTER(HsBatchBuildStats)]
+        L.hs_debug_batched_add_changed.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.hs_hnsw_resume_batched.argtypes = [ctypes.c_char_p, ci, sz, sz, vp, vp, sz, sz, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.c_char_p,
+                                             ctypes.POINTER(HsBatchBuildStats)]
     L.hs_convert_slim.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.c_char_p]
     L.hs_convert_slimq_graph.argtypes = L.hs_convert_slim.argtypes
     L.hs_host_device_pointer.restype = ctypes.c_void_p
@@ -320,6 +326,27 @@ def hnsw_resume(in_path, out_path, rows, labels, dim=None, metric=HS_METRIC_L2, 
         raise HsError(HS_ERR_INVALID, "labels: one per row")
     _check(lib().hs_hnsw_resume(in_path.encode(), metric, r.shape[1] if dim is None else dim, max_elements, r.ctypes.data,
                                 lab.ctypes.data, r.shape[0], seed, drawn, threads, out_path.encode()))
+
+
+def _batch_stats(st):
+    return {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows), "kernel_ms": st.kernel_ms,
+            "total_ms": st.total_ms}
+
+
+def hnsw_resume_batched(in_path, out_path, rows, labels, dim=None, metric=HS_METRIC_L2, max_elements=0, seed=100, drawn=0, device=-1, threads=1,
+                        grow_div=0, batch_max=0, scratch_ids=0):
+    """hs_hnsw_resume_batched (host only): hnsw_resume with the rows added in the batched order, continued from the
+    loaded graph; always the host twin (`device` is accepted and not used).  Returns the stats dict of build_hnsw_batched."""
+    r = np.ascontiguousarray(rows, np.float32)
+    r = r.reshape(-1, dim) if r.ndim != 2 else r
+    lab = np.ascontiguousarray(labels, np.uint64)
+    if lab.shape != (r.shape[0],):
+        raise HsError(HS_ERR_INVALID, "labels: one per row")
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsBatchBuildStats()
+    _check(lib().hs_hnsw_resume_batched(in_path.encode(), metric, r.shape[1] if dim is None else dim, max_elements, r.ctypes.data,
+                                        lab.ctypes.data, r.shape[0], seed, drawn, ctypes.byref(opts), out_path.encode(), ctypes.byref(st)))
+    return _batch_stats(st)
 
 
 HS_OP_ADD, HS_OP_MARK, HS_OP_UNMARK, HS_OP_RESIZE = range(4)   # operation kinds of hs_hnsw_replay
@@ -956,6 +983,28 @@ class Index:
         if lab.shape != (r.shape[0],) or r.shape[1] != self.dim:
             raise HsError(HS_ERR_INVALID, "add_points: rows count x dim, one label per row")
         _check(lib().hs_index_add_points(self._h, r.ctypes.data, lab.ctypes.data, r.shape[0], threads))
+
+    def add_points_batched(self, rows, labels, device=None, threads=1, grow_div=0, batch_max=0, scratch_ids=0):
+        """hs_index_add_points_batched: add_points in the batched order -- on the index's device (the default) or on the
+        host twin (device=-1), the same bytes either way.  Returns the stats dict of build_hnsw_batched."""
+        r = np.ascontiguousarray(rows, np.float32)
+        r = r.reshape(-1, self.dim) if r.ndim != 2 else r
+        lab = np.ascontiguousarray(labels, np.uint64)
+        if lab.shape != (r.shape[0],) or r.shape[1] != self.dim:
+            raise HsError(HS_ERR_INVALID, "add_points_batched: rows count x dim, one label per row")
+        opts = HsBatchBuildOpts(self.device if device is None else device, threads, grow_div, batch_max, scratch_ids)
+        st = HsBatchBuildStats()
+        _check(lib().hs_index_add_points_batched(self._h, r.ctypes.data, lab.ctypes.data, r.shape[0], ctypes.byref(opts), ctypes.byref(st)))
+        return _batch_stats(st)
+
+    def batched_add_changed(self):
+        """hs_debug_batched_add_changed: (the old internal ids whose lists the last device-side add_points_batched changed, the
+        number of old lists it downloaded)."""
+        n, dl = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _check(lib().hs_debug_batched_add_changed(self._h, None, 0, ctypes.byref(n), ctypes.byref(dl)))
+        ids = np.zeros(n.value, np.uint32)
+        _check(lib().hs_debug_batched_add_changed(self._h, ids.ctypes.data, n.value, ctypes.byref(n), None))
+        return ids, dl.value
 
     def upsert_points(self, rows, labels, replace_deleted=None):
         """hs_index_upsert_points: addPoint(rows[i], labels[i], replace_deleted[i]) serially, as the reference: an existing label is

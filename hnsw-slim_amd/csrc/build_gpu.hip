@@ -14,6 +14,11 @@
 //                      over {new id} + the list at maxM / maxM0, stored in pop order (what it does not overwrite stays, as in
 //                      the reference's memory).
 // Every store is a vector store; nothing is read back between batches.
+// The same batches continued on a resident index (gpu_batch_add): the rows are the index's own array, the lists are
+// seeded from its host image, and between bg_scan and bg_link of every batch
+//   bga_mark_kernel    marks the lists of the old nodes that have incoming ids; after the last batch bga_count / bga_scan /
+//                      bga_scatter compact the marked lists in ascending order and bga_gather_kernel packs their slots and the
+//                      new nodes' slots into one dense buffer: what changed comes back, not everything.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -367,6 +372,70 @@ __global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, ui
   }
 }
 
+// ---- the add into a resident index: which lists of the old nodes changed, and only those come back ------------------------
+// An old task is a list the graph held before the call: the level-0 lists of the n0 old nodes, then their nup0 upper slots.
+struct BgMarks {
+  uint8_t *mark;   // n0 + nup0 bytes, zeroed before the first batch
+  uint32_t n0, nup0;
+};
+// Per batch, between the scan and the link kernel: every old task with incoming ids is marked.
+__global__ void __launch_bounds__(256) bga_mark_kernel(const uint32_t *rcnt, uint32_t begin, uint32_t n, uint32_t nact, BgMarks m) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nact; i += gridDim.x * 256u) {
+    const uint32_t task = bg_active(i, begin, n);
+    if (rcnt[task] == 0) continue;
+    if (task < m.n0) m.mark[task] = 1;
+    else if (task >= n && task - n < m.nup0) m.mark[m.n0 + (task - n)] = 1;
+  }
+}
+// Compaction in ascending order, as cd_count / cd_scan / cd_scatter (convert_diff.hip): one wavefront per 64 consecutive old tasks
+// counts its marks, one workgroup turns the counts into offsets, the wavefronts write their tasks at their rank in the ballot.
+__global__ void __launch_bounds__(256) bga_count_kernel(const uint8_t *mark, uint32_t nold, uint32_t *counts) {
+  const uint32_t lane = threadIdx.x & 63u, w = blockIdx.x * 4u + (threadIdx.x >> 6), i = w * 64u + lane;
+  if (w * 64u >= nold) return;
+  const uint32_t c = __popcll(hs_ballot(i < nold && mark[i] != 0));
+  if (lane == 0) counts[w] = c;
+}
+__global__ void __launch_bounds__(256) bga_scan_kernel(uint32_t *counts, uint32_t nw, uint32_t *total) {
+  __shared__ uint32_t part[256];
+  const uint32_t t = threadIdx.x, per = (nw + 255u) / 256u, lo = min(nw, t * per), hi = min(nw, lo + per);
+  uint32_t sum = 0;
+  for (uint32_t w = lo; w < hi; w++) sum += counts[w];
+  part[t] = sum;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t run = 0;
+    for (uint32_t j = 0; j < 256; j++) { const uint32_t c = part[j]; part[j] = run; run += c; }
+    *total = run;
+  }
+  __syncthreads();
+  sum = part[t];
+  for (uint32_t w = lo; w < hi; w++) { const uint32_t c = counts[w]; counts[w] = sum; sum += c; }
+}
+__global__ void __launch_bounds__(256) bga_scatter_kernel(const uint8_t *mark, uint32_t nold, uint32_t n0, uint32_t n, const uint32_t *offs, uint32_t *ids) {
+  const uint32_t lane = threadIdx.x & 63u, w = blockIdx.x * 4u + (threadIdx.x >> 6), i = w * 64u + lane;
+  if (w * 64u >= nold) return;
+  const bool m = i < nold && mark[i] != 0;
+  const unsigned long long bm = hs_ballot(m);
+  const uint32_t at = offs[w] + __popcll(bm & ((1ull << lane) - 1ull));
+  if (m && at < nold) ids[at] = i < n0 ? i : n + (i - n0);
+}
+// One wavefront per entry of the dense buffer: entry j < nchg is the slot of task ids[j]; then the level-0 slots of the new nodes
+// n0 .. n - 1; then their upper slots nup0 .. nup - 1.  Lane i moves word i: consecutive lanes, consecutive words on both sides (a slot
+// starts at a multiple of maxM0 + 1 or maxM + 1 words -- 4-byte alignment is all a slot has, so the words move one by one).  The task
+// ids follow the nslots entries.
+__global__ void __launch_bounds__(256) bga_gather_kernel(BgDev g, const uint32_t *ids, uint32_t nchg, uint32_t n0, uint32_t nup0, uint32_t nup,
+                                                         uint32_t nslots, uint32_t *out) {
+  const uint32_t lane = threadIdx.x & 63u, j = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (j >= nslots) return;
+  const uint32_t nnew = g.n - n0;
+  const uint32_t task = j < nchg ? ids[j] : (j - nchg < nnew ? n0 + (j - nchg) : g.n + nup0 + (j - nchg - nnew));
+  if (task >= g.n + nup) return;   // (never: the host counts the entries)
+  const uint32_t *src = task < g.n ? g.l0 + (size_t)task * g.s0 : g.lu + (size_t)(task - g.n) * g.su;
+  const uint32_t words = task < g.n ? g.s0 : g.su;
+  if (lane < g.s0) out[(size_t)j * g.s0 + lane] = lane < words ? src[lane] : 0u;
+  if (lane == 0 && j < nchg) out[(size_t)nslots * g.s0 + j] = task;
+}
+
 // ---- host driver ------------------------------------------------------------------------------------------------------------------
 static uint32_t bg_topcap(uint32_t efc) {
   uint32_t c = 64;
@@ -393,15 +462,15 @@ bool gpu_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratc
   } while (0)
 
 template <int METRIC>
-static hipError_t bg_run(const GpuBuildInput &in, const BgDev &g, const std::vector<uint32_t> &upb, uint32_t scratch_ids, uint32_t *d_flagged,
+static hipError_t bg_run(const std::vector<BatchStep> &steps, const BgDev &g, const std::vector<uint32_t> &upb, uint32_t scratch_ids, uint32_t *d_flagged,
                          uint32_t *d_ctr, uint32_t *d_scratch, size_t gstride, uint32_t *d_rcnt, uint32_t *d_roff, uint32_t *d_rcur, uint32_t *d_rev,
-                         uint32_t rev_cap, const uint32_t *d_upnode, const uint32_t *d_uplevel, hipStream_t st) {
+                         uint32_t rev_cap, const uint32_t *d_upnode, const uint32_t *d_uplevel, hipStream_t st, const BgMarks *marks = nullptr) {
   const size_t lds_a = bg_search_lds(g.dpad, g.efc, scratch_ids), lds_r = bg_search_lds(g.dpad, g.efc, 0), lds_l = bg_link_lds(g.dpad);
   hipError_t e;
   if (lds_a > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_search_kernel<METRIC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
   if (lds_r > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_search_kernel<METRIC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r)) != hipSuccess) return e;
   if (lds_l > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_link_kernel<METRIC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l)) != hipSuccess) return e;
-  for (const BatchStep &s : *in.steps) {
+  for (const BatchStep &s : steps) {
     if ((int32_t)s.ep == -1) continue;   // the first row: an empty list, as the zeroed arrays have it
     const uint32_t nact = s.begin + upb[s.begin];
     if ((e = hipMemsetAsync(d_ctr, 0, 4, st)) != hipSuccess) return e;
@@ -412,6 +481,8 @@ static hipError_t bg_run(const GpuBuildInput &in, const BgDev &g, const std::vec
     hipLaunchKernelGGL((bg_rev_kernel<false>), dim3((s.size + 3) / 4), dim3(256), 0, st, g, s.begin, s.size, s.top, d_rcnt, d_roff, d_rcur, d_rev, rev_cap);
     hipLaunchKernelGGL(bg_scan_kernel, dim3(1), dim3(256), 0, st, d_rcnt, d_roff, s.begin, g.n, nact);
     hipLaunchKernelGGL((bg_rev_kernel<true>), dim3((s.size + 3) / 4), dim3(256), 0, st, g, s.begin, s.size, s.top, d_rcnt, d_roff, d_rcur, d_rev, rev_cap);
+    if (marks)   // (before the link kernel, which resets the counts)
+      hipLaunchKernelGGL(bga_mark_kernel, dim3(std::min((nact + 255u) / 256u, 4096u)), dim3(256), 0, st, d_rcnt, s.begin, g.n, nact, *marks);
     hipLaunchKernelGGL((bg_link_kernel<METRIC>), dim3(std::min(nact, 8192u)), dim3(64), lds_l, st, g, s.begin, nact, d_upnode, d_uplevel, d_rcnt, d_roff,
                        d_rcur, d_rev, rev_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -484,9 +555,9 @@ hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint
   BG_TRY(hipEventCreate(&e0)); BG_TRY(hipEventCreate(&e1));
   BG_TRY(hipEventRecord(e0, nullptr));
   if (in.metric == METRIC_L2)
-    BG_TRY(bg_run<METRIC_L2>(in, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
+    BG_TRY(bg_run<METRIC_L2>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
   else
-    BG_TRY(bg_run<METRIC_IP>(in, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
+    BG_TRY(bg_run<METRIC_IP>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
   BG_TRY(hipEventRecord(e1, nullptr));
   BG_TRY(hipEventSynchronize(e1));
   if (kernel_ms) { float ms = 0.f; BG_TRY(hipEventElapsedTime(&ms, e0, e1)); *kernel_ms = ms; }
@@ -499,6 +570,121 @@ hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint
 done:
   for (void *p : {(void *)d_vec, (void *)d_l0, (void *)d_lu, (void *)d_upb, (void *)d_lev, (void *)d_upnode, (void *)d_uplevel, (void *)d_flagged,
                   (void *)d_ctr, (void *)d_scratch, (void *)d_rcnt, (void *)d_roff, (void *)d_rcur, (void *)d_rev})
+    if (p) (void)hipFree(p);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return err;
+}
+
+// gpu_batch_build's batches continued on a resident index: the rows are the index's own array (the new ones copied behind the old --
+// no list names them until a batch has run, so no search sees them), the lists are seeded from the host image, and what comes back
+// is one dense buffer of the changed old slots and the new nodes' slots.
+hipError_t gpu_batch_add(const GpuAddInput &in, int device, GpuAddOutput &out) {
+  hipError_t err = hipSuccess;
+  const uint32_t scratch_ids = in.scratch_ids ? in.scratch_ids : kBgScratchIds;
+  out = GpuAddOutput();
+  if (!gpu_build_supported(in.dim, in.M, in.efc, scratch_ids) || in.maxM != in.M || in.maxM0 != 2 * in.M || in.n0 == 0 || in.count == 0 ||
+      (uint64_t)in.n0 + in.count > 0x7FFFFFF0u || !in.d_vec || !in.rows || !in.lev || !in.steps || !in.upb || !in.lists0 || !in.lists_up)
+    return hipErrorInvalidValue;
+  const uint32_t n0 = in.n0, n = in.n0 + in.count;
+  const std::vector<uint32_t> &upb = *in.upb;
+  BgDev g{};
+  g.n = n; g.dim = in.dim; g.dpad = (in.dim + 3u) & ~3u; g.M = in.M; g.maxM = in.maxM; g.maxM0 = in.maxM0;
+  g.s0 = in.maxM0 + 1; g.su = in.maxM + 1; g.efc = in.efc; g.topcap = bg_topcap(in.efc);
+  if (upb.size() != (size_t)n + 1 || in.lists0->size() != (size_t)n * g.s0 || in.lists_up->size() != (size_t)upb[n] * g.su) return hipErrorInvalidValue;
+  const uint32_t nup = upb[n], nup0 = upb[n0], nold = n0 + nup0, nw = (nold + 63u) / 64u;
+  std::vector<uint32_t> up_node(nup), up_level(nup);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t l = 1; l <= in.lev[i]; l++) { up_node[upb[i] + l - 1] = i; up_level[upb[i] + l - 1] = l; }
+  uint32_t max_batch = 1;
+  size_t rev_cap = 1;   // the most edges one batch can add: M per (row, level it is searched on)
+  for (const BatchStep &s : *in.steps) {
+    if (s.begin < n0 || (uint64_t)s.begin + s.size > n || s.ep >= s.begin || s.top < 0) return hipErrorInvalidValue;
+    max_batch = std::max(max_batch, s.size);
+    size_t edges = 0;
+    for (uint32_t k = 0; k < s.size; k++) edges += (size_t)in.M * (std::min<int64_t>(in.lev[s.begin + k], s.top) + 1);
+    rev_cap = std::max(rev_cap, edges);
+  }
+  if (rev_cap > 0xFFFFFFF0u) return hipErrorInvalidValue;
+  const size_t ntasks = (size_t)n + nup;
+  const size_t gstride = (((size_t)n + 31) / 32 + 1) / 2 * 2 + 2 * (size_t)n;   // words: bitmap (padded to a pair's alignment) + n pairs
+  const uint32_t nnew_slots = in.count + (nup - nup0);
+  uint32_t *d_l0 = nullptr, *d_lu = nullptr, *d_upb = nullptr, *d_lev = nullptr, *d_upnode = nullptr, *d_uplevel = nullptr, *d_flagged = nullptr,
+           *d_ctr = nullptr, *d_scratch = nullptr, *d_rcnt = nullptr, *d_roff = nullptr, *d_rcur = nullptr, *d_rev = nullptr, *d_counts = nullptr,
+           *d_ids = nullptr, *d_out = nullptr;
+  uint8_t *d_mark = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  uint32_t ctr[3] = {0, 0, 0};   // flagged rows of the batch, of the call; changed old tasks
+  uint32_t nchg = 0, nslots = 0;
+  BG_TRY(hipSetDevice(device));
+  BG_TRY(hipMalloc((void **)&d_l0, (size_t)n * g.s0 * 4));
+  BG_TRY(hipMalloc((void **)&d_lu, std::max<size_t>((size_t)nup * g.su, 1) * 4));
+  BG_TRY(hipMalloc((void **)&d_upb, ((size_t)n + 1) * 4));
+  BG_TRY(hipMalloc((void **)&d_lev, (size_t)n * 4));
+  BG_TRY(hipMalloc((void **)&d_upnode, std::max<size_t>(nup, 1) * 4));
+  BG_TRY(hipMalloc((void **)&d_uplevel, std::max<size_t>(nup, 1) * 4));
+  BG_TRY(hipMalloc((void **)&d_flagged, (size_t)max_batch * 4));
+  BG_TRY(hipMalloc((void **)&d_ctr, 12));
+  BG_TRY(hipMalloc((void **)&d_scratch, gstride * 4 * std::min(kBgRerunGrid, max_batch)));
+  BG_TRY(hipMalloc((void **)&d_rcnt, ntasks * 4));
+  BG_TRY(hipMalloc((void **)&d_roff, ntasks * 4));
+  BG_TRY(hipMalloc((void **)&d_rcur, ntasks * 4));
+  BG_TRY(hipMalloc((void **)&d_rev, rev_cap * 4));
+  BG_TRY(hipMalloc((void **)&d_mark, nold));
+  BG_TRY(hipMalloc((void **)&d_counts, (size_t)nw * 4));
+  BG_TRY(hipMalloc((void **)&d_ids, (size_t)nold * 4));
+  BG_TRY(hipMemcpy(in.d_vec + (size_t)n0 * in.dim, in.rows, (size_t)in.count * in.dim * 4, hipMemcpyHostToDevice));
+  BG_TRY(hipMemcpy(d_l0, in.lists0->data(), (size_t)n * g.s0 * 4, hipMemcpyHostToDevice));
+  if (nup) {
+    BG_TRY(hipMemcpy(d_lu, in.lists_up->data(), (size_t)nup * g.su * 4, hipMemcpyHostToDevice));
+    BG_TRY(hipMemcpy(d_upnode, up_node.data(), (size_t)nup * 4, hipMemcpyHostToDevice));
+    BG_TRY(hipMemcpy(d_uplevel, up_level.data(), (size_t)nup * 4, hipMemcpyHostToDevice));
+  }
+  BG_TRY(hipMemcpy(d_upb, upb.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
+  BG_TRY(hipMemcpy(d_lev, in.lev, (size_t)n * 4, hipMemcpyHostToDevice));
+  BG_TRY(hipMemset(d_rcnt, 0, ntasks * 4));
+  BG_TRY(hipMemset(d_roff, 0, ntasks * 4));
+  BG_TRY(hipMemset(d_rcur, 0, ntasks * 4));
+  BG_TRY(hipMemset(d_ctr, 0, 12));
+  BG_TRY(hipMemset(d_mark, 0, nold));
+  BG_TRY(hipDeviceSynchronize());
+  g.vec = in.d_vec; g.l0 = d_l0; g.lu = d_lu; g.upb = d_upb; g.lev = d_lev;
+  {
+    const BgMarks marks{d_mark, n0, nup0};
+    BG_TRY(hipEventCreate(&e0)); BG_TRY(hipEventCreate(&e1));
+    BG_TRY(hipEventRecord(e0, nullptr));
+    if (in.metric == METRIC_L2)
+      BG_TRY(bg_run<METRIC_L2>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr, &marks));
+    else
+      BG_TRY(bg_run<METRIC_IP>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr, &marks));
+    hipLaunchKernelGGL(bga_count_kernel, dim3((nw + 3) / 4), dim3(256), 0, nullptr, d_mark, nold, d_counts);
+    hipLaunchKernelGGL(bga_scan_kernel, dim3(1), dim3(256), 0, nullptr, d_counts, nw, d_ctr + 2);
+    hipLaunchKernelGGL(bga_scatter_kernel, dim3((nw + 3) / 4), dim3(256), 0, nullptr, d_mark, nold, n0, n, d_counts, d_ids);
+    BG_TRY(hipGetLastError());
+    BG_TRY(hipMemcpy(ctr, d_ctr, 12, hipMemcpyDeviceToHost));
+    nchg = std::min(ctr[2], nold);
+    nslots = nchg + nnew_slots;
+    BG_TRY(hipMalloc((void **)&d_out, ((size_t)nslots * g.s0 + std::max(nchg, 1u)) * 4));
+    hipLaunchKernelGGL(bga_gather_kernel, dim3((nslots + 3) / 4), dim3(256), 0, nullptr, g, d_ids, nchg, n0, nup0, nup, nslots, d_out);
+    BG_TRY(hipGetLastError());
+    BG_TRY(hipEventRecord(e1, nullptr));
+    BG_TRY(hipEventSynchronize(e1));
+    float ms = 0.f;
+    BG_TRY(hipEventElapsedTime(&ms, e0, e1));
+    out.kernel_ms = ms;
+  }
+  out.flagged_rows = ctr[1];
+  {
+    std::vector<uint32_t> buf((size_t)nslots * g.s0 + nchg);
+    BG_TRY(hipMemcpy(buf.data(), d_out, buf.size() * 4, hipMemcpyDeviceToHost));   // the one download
+    out.tasks.assign(buf.begin() + (size_t)nslots * g.s0, buf.end());
+    buf.resize((size_t)nslots * g.s0);
+    out.slots.swap(buf);
+  }
+done:
+  for (void *p : {(void *)d_l0, (void *)d_lu, (void *)d_upb, (void *)d_lev, (void *)d_upnode, (void *)d_uplevel, (void *)d_flagged, (void *)d_ctr,
+                  (void *)d_scratch, (void *)d_rcnt, (void *)d_roff, (void *)d_rcur, (void *)d_rev, (void *)d_mark, (void *)d_counts, (void *)d_ids,
+                  (void *)d_out})
     if (p) (void)hipFree(p);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);

@@ -35,6 +35,14 @@ hs_status hs_build_hnsw_labeled(const float *base, const uint64_t *labels, size_
 
 // ---- batched addPoint (host_batch_build.hpp; on a device build_gpu.hip) -------------------------------------------------------------
 static bool pow2(uint64_t v) { return v && (v & (v - 1)) == 0; }
+hs_status batch_opts_ok(const hs_batch_build_opts *opts) {
+  if (!opts) return fail(HS_ERR_INVALID, "bad argument");
+  if (opts->device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host twin) or a HIP device");
+  if (opts->scratch_ids && (!pow2(opts->scratch_ids) || opts->scratch_ids < 64 || opts->scratch_ids > 8192))
+    return fail(HS_ERR_INVALID, "scratch_ids: 0 or a power of two from 64 to 8192");
+  if (opts->grow_div > 0xFFFFFFFFu || opts->batch_max > 0xFFFFFFFFu) return fail(HS_ERR_INVALID, "grow_div / batch_max out of range");
+  return HS_OK;
+}
 
 // The device build's lists into the image VanillaGraph::save writes: rows and labels as begin_insert lays them out, the level-0 lists
 // in front of them, the upper lists per node, entry point and top level as the schedule ends.
@@ -62,15 +70,12 @@ static void image_from_lists(VanillaGraph &g, const float *base, const uint64_t 
 hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
                                 const char *branching_factor, size_t seed, const hs_batch_build_opts *opts, const char *out_path,
                                 hs_batch_build_stats *stats) {
-  if (!base || !out_path || !branching_factor || !opts || n == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (!base || !out_path || !branching_factor || n == 0) return fail(HS_ERR_INVALID, "bad argument");
   if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
   if (M == 0) return fail(HS_ERR_INVALID, "M must be > 0");
   if (n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "too many rows");
-  if (opts->device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host twin) or a HIP device");
-  if (opts->scratch_ids && (!pow2(opts->scratch_ids) || opts->scratch_ids < 64 || opts->scratch_ids > 8192))
-    return fail(HS_ERR_INVALID, "scratch_ids: 0 or a power of two from 64 to 8192");
-  if (opts->grow_div > 0xFFFFFFFFu || opts->batch_max > 0xFFFFFFFFu) return fail(HS_ERR_INVALID, "grow_div / batch_max out of range");
+  if (batch_opts_ok(opts) != HS_OK) return HS_ERR_INVALID;
   if (opts->device >= 0 && hs_device_count() <= opts->device) return fail(HS_ERR_DEVICE, "no HIP device");
   const auto t0 = std::chrono::steady_clock::now();
   hs_batch_build_stats st{};
@@ -131,6 +136,21 @@ hs_status hs_build_schedule(size_t n, size_t M, const char *branching_factor, si
   return HS_OK;
 }
 
+// hs_index_add_points' label refusals against a loaded graph: a label the graph holds, a label twice in the call
+static hs_status new_labels_ok(const VanillaGraph &g, const uint64_t *labels, size_t count) {
+  std::unordered_map<uint64_t, size_t> seen;
+  seen.reserve(g.count + count);
+  for (size_t i = 0; i < g.count; i++) seen.emplace(g.label((uint32_t)i), (size_t)-1);
+  for (size_t i = 0; i < count; i++) {
+    auto ins = seen.emplace(labels[i], i);
+    if (ins.second) continue;
+    if (ins.first->second == (size_t)-1)
+      return fail(HS_ERR_UNSUPPORTED, "label " + std::to_string(labels[i]) + " (row " + std::to_string(i) + ") already exists: updatePoint is not supported");
+    return fail(HS_ERR_INVALID, "label " + std::to_string(labels[i]) + " appears twice in the call (rows " + std::to_string(ins.first->second) + " and " + std::to_string(i) + ")");
+  }
+  return HS_OK;
+}
+
 // Continue a saved build on the host: loadIndex(in_path, space, max_elements), the level generator put where a build that has drawn
 // `drawn` levels from `seed` left it, addPoint for each row, saveIndex.  Refusals (capacity, a label that exists or appears twice)
 // happen before anything is added, and nothing is written.
@@ -143,16 +163,8 @@ hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max
     VanillaGraph g;
     g.load(in_path, (Metric)metric, dim, max_elements);
     if (g.count + count > g.max_elements) return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // hnswalg.h:1274-1277
-    std::unordered_map<uint64_t, size_t> seen;
-    seen.reserve(g.count + count);
-    for (size_t i = 0; i < g.count; i++) seen.emplace(g.label((uint32_t)i), (size_t)-1);
-    for (size_t i = 0; i < count; i++) {
-      auto ins = seen.emplace(labels[i], i);
-      if (ins.second) continue;
-      if (ins.first->second == (size_t)-1)
-        return fail(HS_ERR_UNSUPPORTED, "label " + std::to_string(labels[i]) + " (row " + std::to_string(i) + ") already exists: updatePoint is not supported");
-      return fail(HS_ERR_INVALID, "label " + std::to_string(labels[i]) + " appears twice in the call (rows " + std::to_string(ins.first->second) + " and " + std::to_string(i) + ")");
-    }
+    const hs_status ls = new_labels_ok(g, labels, count);
+    if (ls != HS_OK) return ls;
     seed_levels(g, seed, drawn);
     resume(g, rows, labels, count, threads);
     g.save(out_path);
@@ -161,6 +173,40 @@ hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max
   } catch (std::exception &e) {
     return from_exception(e);
   }
+  return HS_OK;
+}
+
+// hs_hnsw_resume in the batched order, on the host twin: what hs_index_add_points_batched does to a resident index's
+// host image, without a device.  The refusals are those of that call, marks included, before anything is added.
+hs_status hs_hnsw_resume_batched(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows, const uint64_t *labels,
+                                 size_t count, size_t seed, size_t drawn, const hs_batch_build_opts *opts, const char *out_path,
+                                 hs_batch_build_stats *stats) {
+  if (!in_path || !out_path || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
+  if (batch_opts_ok(opts) != HS_OK) return HS_ERR_INVALID;
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_batch_build_stats st{};
+  try {
+    VanillaGraph g;
+    g.load(in_path, (Metric)metric, dim, max_elements);
+    if (g.count + count > g.max_elements) return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // hnswalg.h:1274-1277
+    const hs_status ls = new_labels_ok(g, labels, count);
+    if (ls != HS_OK) return ls;
+    if (count && g.num_deleted() > 0)
+      return fail(HS_ERR_UNSUPPORTED, kBatchedAddMarksRefusal);
+    seed_levels(g, seed, drawn);
+    BatchBuildStats bs;
+    batch_add_host(g, rows, labels, count, std::max(1, (int)opts->threads), opts->grow_div, opts->batch_max, &bs);
+    st.batches = bs.batches;
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (stats) *stats = st;
   return HS_OK;
 }
 

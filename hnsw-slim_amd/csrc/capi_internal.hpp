@@ -83,6 +83,8 @@ struct hs_index {
   size_t num_deleted = 0;
   bool has_dup0 = false;         // some level-0 list names an id twice (PackedIndex::repeats_id0, refreshed by upload_small)
   DevBuf<uint32_t> upd_stage;    // the records of the update call being applied (grow-only)
+  std::vector<uint32_t> last_add_changed;   // hs_debug_batched_add_changed: old nodes whose lists the last device-side batched add changed
+  size_t last_add_downloaded = 0;           // ... and the old lists it downloaded (those that received an id)
   DevIndex dev{};
   DevBuf<float> vec;
   DevBuf<uint32_t> row_ptr0, cols, up_base, up_ptr, tile0, uptile;
@@ -155,6 +157,10 @@ struct FilterUse {
   const uint32_t *d_of_query;   // nq filter indices (device)
 };
 
+// The batched add takes no index with delete marks, on the device or on the host twin.
+static constexpr const char *kBatchedAddMarksRefusal =
+    "batched add refused: the index holds delete marks (the batched insertion has no deleted-element branches); use hs_index_add_points";
+
 // The functions that cross files (shared between the library's own objects, not exported).
 #pragma GCC visibility push(hidden)
 // capi_index.cpp; the calling thread's last error text (hs_last_error) is one thread-local there
@@ -177,6 +183,8 @@ void refresh_device_bytes(hs_index *ix);
 void set_delete_marks(hs_index *ix, size_t num_deleted, bool has_deleted);   // num_deleted_ and the flag the kernels and hs_info carry
 size_t first_unfit(const float *x, size_t count, int fmt);   // first value not representable in the row format, `count` when none
 std::string unfit_message(size_t row, size_t comp, float v, int fmt);
+// capi_build.cpp: what every batched entry refuses in its options (null, a device below -1, scratch_ids, grow_div / batch_max)
+hs_status batch_opts_ok(const hs_batch_build_opts *opts);
 // capi_slimq.cpp
 hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, hs_index **out);
 // capi_search.cpp

@@ -1,11 +1,14 @@
 // capi_update.cpp -- the C ABI (include/hnsw_slim_amd.h): a resident vanilla index that changes -- addPoint on its host image, for
-// new labels (hs_index_add_points) and as the reference's upsert with replace_deleted (hs_index_upsert_points), with the changed
+// new labels (hs_index_add_points; in the batched order, on the index's device, hs_index_add_points_batched) and as the reference's
+// upsert with replace_deleted (hs_index_upsert_points), with the changed
 // rows written in place on the device (write_changed, capi_resident.cpp); markDelete / unmarkDelete, resizeIndex, saveIndex, getDataByLabel; and
 // the host-only replay of an operation list (hs_hnsw_replay).
 #include "capi_internal.hpp"
 
+#include <chrono>
 #include <unordered_set>
 
+#include "build_engine.hpp"
 #include "host_update.hpp"
 #include "index_update.hpp"
 
@@ -38,14 +41,14 @@ size_t hs_index_capacity(const hs_index *ix) {
 
 size_t hs_index_deleted_count(const hs_index *ix) { return ix ? ix->num_deleted : 0; }
 
-hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, int threads) {
-  if (!ix || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "null argument");
-  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "addPoint is supported on a vanilla (HS_KIND_HNSW) index only");
-  // everything is validated before anything changes
+// What hs_index_add_points and hs_index_add_points_batched refuse, all of it before anything changes: capacity, a label that exists or
+// appears twice in the call, a row the narrow format cannot represent.  *empty: count == 0 passed the capacity check (nothing to do).
+static hs_status check_new_points(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, bool *empty) {
   const size_t n0 = ix->info.n, dim = ix->info.dim;
+  *empty = false;
   if (count && (!ix->host_vanilla || n0 + count > ix->host_vanilla->max_elements))
     return fail(HS_ERR_CAPACITY, "The number of elements exceeds the specified limit");   // hnswalg.h:1274-1277
-  if (count == 0) return HS_OK;
+  if (count == 0) { *empty = true; return HS_OK; }
   ensure_update_state(ix);
   {
     std::unordered_map<uint64_t, size_t> seen;
@@ -63,14 +66,41 @@ hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *l
       const size_t j = first_unfit(rows + i * dim, dim, ix->row_fmt);
       if (j < dim) return fail(HS_ERR_UNSUPPORTED, "add refused: " + unfit_message(i, j, rows[i * dim + j], ix->row_fmt));
     }
+  return HS_OK;
+}
+
+// After the host image took `count` new nodes from id n0 on: the label map, then the device through the one write path.
+static hs_status publish_new_points(hs_index *ix, const uint64_t *labels, size_t n0, size_t count, const std::vector<uint32_t> &touched,
+                                    const float *src_vec) {
+  VanillaGraph &g = *ix->host_vanilla;
+  PackedIndex p;
+  try {
+    p.from_vanilla(g, false);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory: addPoint failed to allocate linklist");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  for (size_t i = 0; i < count; i++) ix->label_to_id[labels[i]] = (uint32_t)(n0 + i);
+  std::vector<uint32_t> row_ids(count);
+  for (size_t i = 0; i < count; i++) row_ids[i] = (uint32_t)(n0 + i);
+  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, touched, row_ids, src_vec);
+}
+
+hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, int threads) {
+  if (!ix || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "null argument");
+  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "addPoint is supported on a vanilla (HS_KIND_HNSW) index only");
+  // everything is validated before anything changes
+  bool empty = false;
+  const hs_status cs = check_new_points(ix, rows, labels, count, &empty);
+  if (cs != HS_OK || empty) return cs;
+  const size_t n0 = ix->info.n;
   VanillaGraph &g = *ix->host_vanilla;
   std::vector<uint32_t> touched;
-  PackedIndex p;
   try {
     g.touched0 = &touched;
     resume(g, rows, labels, count, threads);
     g.touched0 = nullptr;
-    p.from_vanilla(g, false);
   } catch (std::bad_alloc &) {
     g.touched0 = nullptr;
     return fail(HS_ERR_NOMEM, "Not enough memory: addPoint failed to allocate linklist");
@@ -78,10 +108,153 @@ hs_status hs_index_add_points(hs_index *ix, const float *rows, const uint64_t *l
     g.touched0 = nullptr;
     return from_exception(e);
   }
-  for (size_t i = 0; i < count; i++) ix->label_to_id[labels[i]] = (uint32_t)(n0 + i);
-  std::vector<uint32_t> row_ids(count);
-  for (size_t i = 0; i < count; i++) row_ids[i] = (uint32_t)(n0 + i);
-  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, touched, row_ids);
+  return publish_new_points(ix, labels, n0, count, touched, nullptr);
+}
+
+// ---- batched addPoint into a resident index (host_batch_build.hpp, on the device build_gpu.hip) -------------------------
+// The device run: on success the host image holds the new nodes and the changed old lists, `touched` the level-0 lists that changed.
+// Nothing of the host image changes before the download has arrived.
+static hs_status batched_add_device(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, const hs_batch_build_opts *opts,
+                                    hs_batch_build_stats &st, std::vector<uint32_t> &touched) {
+  VanillaGraph &g = *ix->host_vanilla;
+  const size_t n0 = g.count, n = n0 + count, s0 = g.maxM0 + 1;
+  const int threads = std::max(1, (int)opts->threads);
+  const std::default_random_engine gen0 = g.level_gen;   // (put back when the device fails: the call then changed nothing)
+  try {
+    std::vector<int> lv(count);
+    for (size_t i = 0; i < count; i++) lv[i] = draw_level(g);
+    const std::vector<BatchStep> steps = batch_schedule_from(lv.data(), count, n0, g.enterpoint, g.maxlevel, opts->grow_div, opts->batch_max);
+    std::vector<uint32_t> lev(n), upb, l0, lu;
+    for (size_t i = 0; i < n0; i++) lev[i] = (uint32_t)g.levels[i];
+    for (size_t i = 0; i < count; i++) lev[n0 + i] = (uint32_t)lv[i];
+    build_form_lists(g, n0, n, lev.data(), threads, upb, l0, lu);
+    GpuAddInput in;
+    in.d_vec = ix->vec.p; in.rows = rows; in.n0 = (uint32_t)n0; in.count = (uint32_t)count; in.dim = (uint32_t)g.dim; in.metric = (int)g.metric;
+    in.M = (uint32_t)g.M; in.maxM = (uint32_t)g.maxM; in.maxM0 = (uint32_t)g.maxM0; in.efc = (uint32_t)g.efC;
+    in.lev = lev.data(); in.steps = &steps; in.scratch_ids = (uint32_t)opts->scratch_ids;
+    in.upb = &upb; in.lists0 = &l0; in.lists_up = &lu;
+    GpuAddOutput out;
+    const hipError_t e = gpu_batch_add(in, ix->device, out);
+    const size_t nchg = out.tasks.size(), nup0 = upb[n0];
+    bool sane = e == hipSuccess && out.slots.size() == (nchg + count + (upb[n] - nup0)) * s0;
+    for (size_t j = 0; sane && j < nchg; j++) sane = out.tasks[j] < n0 || (out.tasks[j] >= n && out.tasks[j] - n < nup0);
+    if (!sane) {
+      g.level_gen = gen0;
+      if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("batched add: ") + hipGetErrorString(e));
+      return fail(HS_ERR_DEVICE, "batched add: the device returned lists outside the index");
+    }
+    std::vector<uint32_t>().swap(l0);
+    std::vector<uint32_t>().swap(lu);
+    // the new nodes as begin_insert lays them out, their lists from the download
+    const uint32_t *slot = out.slots.data();
+    for (size_t i = 0; i < count; i++) {
+      const uint32_t id = (uint32_t)(n0 + i);
+      char *el = g.el(id);
+      memset(el, 0, g.size_per_el);
+      memcpy(el, slot + (nchg + i) * s0, g.size_links0);
+      memcpy(el + g.offsetData, rows + i * g.dim, 4 * g.dim);
+      memcpy(el + g.label_offset, &labels[i], 8);
+      g.levels[id] = lv[i];
+      if (lv[i]) {
+        g.links[id].assign(g.size_links_up * lv[i] + 1, 0);
+        for (int l = 1; l <= lv[i]; l++)
+          memcpy(g.links[id].data() + (size_t)(l - 1) * g.size_links_up, slot + (nchg + count + (upb[id] - nup0) + l - 1) * s0, g.size_links_up);
+      }
+      touched.push_back(id);
+    }
+    // the old lists that received an id, whole slots (what stands behind the count is saved too).  A full list whose re-prune
+    // turned the new id away and kept its order comes back with the bytes it had: it is left alone.
+    ix->last_add_changed.clear();
+    ix->last_add_downloaded = nchg;
+    for (size_t j = 0; j < nchg; j++) {
+      const uint32_t task = out.tasks[j];
+      uint32_t u = task;
+      if (task < n0) {
+        if (memcmp(g.el(u), slot + j * s0, g.size_links0) == 0) continue;
+        memcpy(g.el(u), slot + j * s0, g.size_links0);
+        touched.push_back(u);
+      } else {
+        const uint32_t us = task - (uint32_t)n;   // upper slot: node u's level us - upb[u] + 1
+        u = (uint32_t)(std::upper_bound(upb.begin(), upb.begin() + n0 + 1, us) - upb.begin() - 1);
+        uint32_t *l = g.list_at(u, (int)(us - upb[u] + 1));
+        if (memcmp(l, slot + j * s0, g.size_links_up) == 0) continue;
+        memcpy(l, slot + j * s0, g.size_links_up);
+      }
+      ix->last_add_changed.push_back(u);
+    }
+    std::sort(ix->last_add_changed.begin(), ix->last_add_changed.end());
+    ix->last_add_changed.erase(std::unique(ix->last_add_changed.begin(), ix->last_add_changed.end()), ix->last_add_changed.end());
+    g.count = n;
+    for (size_t i = 0; i < count; i++)   // (adopt_entry: a row above the top level becomes the entry point)
+      if (lv[i] > g.maxlevel) { g.maxlevel = lv[i]; g.enterpoint = (uint32_t)(n0 + i); }
+    st.used_gpu = 1; st.batches = steps.size(); st.flagged_rows = out.flagged_rows; st.kernel_ms = out.kernel_ms;
+    return HS_OK;
+  } catch (...) {
+    g.level_gen = gen0;
+    throw;
+  }
+}
+
+hs_status hs_index_add_points_batched(hs_index *ix, const float *rows, const uint64_t *labels, size_t count, const hs_batch_build_opts *opts,
+                                      hs_batch_build_stats *stats) {
+  if (!ix || (count && (!rows || !labels))) return fail(HS_ERR_INVALID, "null argument");
+  if (ix->info.kind != HS_KIND_HNSW) return fail(HS_ERR_UNSUPPORTED, "addPoint is supported on a vanilla (HS_KIND_HNSW) index only");
+  hs_status cs = batch_opts_ok(opts);
+  if (cs != HS_OK) return cs;
+  if (opts->device != -1 && opts->device != ix->device)
+    return fail(HS_ERR_INVALID, "device: -1 (the host twin) or the index's own device (" + std::to_string(ix->device) + ")");
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_batch_build_stats st{};
+  bool empty = false;
+  cs = check_new_points(ix, rows, labels, count, &empty);
+  if (cs != HS_OK) return cs;
+  if (empty) { if (stats) *stats = st; return HS_OK; }
+  if (ix->num_deleted > 0) return fail(HS_ERR_UNSUPPORTED, kBatchedAddMarksRefusal);
+  VanillaGraph &g = *ix->host_vanilla;
+  const size_t n0 = g.count;
+  // the device takes the build's shapes, on an index that holds fp32 rows with room behind them; anything else is the host twin's
+  const bool on_device = opts->device >= 0 && n0 > 0 && n0 + count <= 0x7FFFFFF0u && ix->f32_resident && ix->vec.p &&
+                         ix->vec.n >= (n0 + count) * g.dim && g.maxM == g.M && g.maxM0 == 2 * g.M &&
+                         gpu_build_supported((uint32_t)g.dim, (uint32_t)g.M, (uint32_t)g.efC, (uint32_t)opts->scratch_ids);
+  std::vector<uint32_t> touched;
+  ix->last_add_changed.clear();
+  ix->last_add_downloaded = 0;
+  try {
+    if (on_device) {
+      HIP_TRY(hipSetDevice(ix->device));
+      HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows grow
+      cs = batched_add_device(ix, rows, labels, count, opts, st, touched);
+      if (cs != HS_OK) return cs;
+    } else {
+      BatchBuildStats bs;
+      g.touched0 = &touched;
+      batch_add_host(g, rows, labels, count, std::max(1, (int)opts->threads), opts->grow_div, opts->batch_max, &bs);
+      g.touched0 = nullptr;
+      st.batches = bs.batches;
+    }
+  } catch (std::bad_alloc &) {
+    g.touched0 = nullptr;
+    return fail(HS_ERR_NOMEM, "Not enough memory: addPoint failed to allocate linklist");
+  } catch (std::exception &e) {
+    g.touched0 = nullptr;
+    return from_exception(e);
+  }
+  cs = publish_new_points(ix, labels, n0, count, touched, on_device ? ix->vec.p : nullptr);
+  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (stats) *stats = st;
+  return cs;
+}
+
+// Diagnostic: what the device path of the last hs_index_add_points_batched brought back beside the new nodes -- *lists_downloaded
+// (nullable) old lists that received an id, and the old nodes (internal ids below the element count before the call, ascending)
+// among them whose level-0 or upper list bytes changed.  Both empty after a call the host twin served.  ids nullable; at most `cap`
+// are written, *count receives how many there are.
+hs_status hs_debug_batched_add_changed(const hs_index *ix, uint32_t *ids, size_t cap, size_t *count, size_t *lists_downloaded) {
+  if (!ix || !count) return fail(HS_ERR_INVALID, "null argument");
+  *count = ix->last_add_changed.size();
+  if (lists_downloaded) *lists_downloaded = ix->last_add_downloaded;
+  if (ids) std::copy_n(ix->last_add_changed.begin(), std::min(cap, ix->last_add_changed.size()), ids);
+  return HS_OK;
 }
 
 hs_status hs_index_mark_deleted(hs_index *ix, const uint64_t *labels, size_t count, int on) {

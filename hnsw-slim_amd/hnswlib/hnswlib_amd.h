@@ -417,6 +417,23 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     collected_.insert(label);
     dirty_ = true;
   }
+  // addPoint for a block of n new labels.  On a resident index with setBuildOnDevice in force (and one device) it is the batched add
+  // (hs_index_add_points_batched: the batched order of the deferred build continued on the graph the index holds, on the index's
+  // own device, with setBuildOnDevice's batch_max; buildStats() then reports this call); all or nothing, and an index that holds
+  // delete marks is refused.  Otherwise it is a loop of addPoint.
+  void addPoints(const float *rows, const labeltype *labels, size_t n) {
+    if (build_device_ >= 0 && dirty_) ensure_built();
+    if (build_device_ >= 0 && resident() && replicas_.size() <= 1) {
+      std::vector<uint64_t> l(labels, labels + n);
+      hs_batch_build_opts o{};
+      o.device = device_; o.threads = build_threads_; o.batch_max = build_batch_max_;
+      detail::check(hs_index_add_points_batched(h_, rows, l.data(), n, &o, &build_stats_));
+      drop_filter_cache();
+      return;
+    }
+    const size_t d = detail::dim_of(space_);
+    for (size_t i = 0; i < n; i++) addPoint(rows + i * d, labels[i]);
+  }
   // resizeIndex (hnswalg.h:689-717).  A resident index that keeps its host image moves its device arrays (hs_index_resize).  One
   // that was loaded without room has no host image: its file is loaded again with the new capacity -- unless delete marks changed
   // since the load, which that file does not hold.

@@ -622,6 +622,34 @@ hs_status hs_build_schedule(size_t n, size_t M, const char *branching_factor, si
  * hs_index_add_points (capacity, existing or repeated label), before anything is added; out_path is then not written. */
 hs_status hs_hnsw_resume(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows,
                          const uint64_t *labels, size_t count, size_t seed, size_t drawn, int threads, const char *out_path);
+/* Batched addPoint into a resident vanilla index: hs_index_add_points in the order of hs_build_hnsw_batched, continued
+ * from the graph the index holds -- fast and still deterministic.  Row i becomes internal id n + i with a level from the index's level
+ * generator (hs_index_seed_levels works as for hs_index_add_points); the schedule is hs_build_hnsw_batched's rule started at
+ * inserted = n with the index's entry point and top level, so a build split at a batch boundary of hs_build_schedule -- the prefix
+ * built, loaded with room, seeded with (seed, prefix), the rest added here -- holds the bytes of the whole build, and batch_max == 1 is
+ * hs_index_add_points(threads = 1).  M, ef_construction and the level multiplier are the file header's.
+ * opts->device: -1 (the host twin: the searches on `threads` workers over the host image) or the index's own device (anything else:
+ * HS_ERR_INVALID).  On the device the new rows are copied behind the resident fp32 rows (nothing is uploaded twice), the lists are
+ * seeded from the host image, the insertion searches and reverse links run there (build_gpu.hip), and only the lists that changed and
+ * the new nodes' lists are downloaded (one dense buffer); the host image is updated from them and the device arrays through the same
+ * write path as hs_index_add_points (tiles re-tiled when a list outgrows the stride, small structure arrays rebuilt, a filter set made
+ * for the old n refused afterwards).  Both paths leave the same bytes for hs_index_save.  Shapes outside the device build (M > 31,
+ * ef_construction > 512, a row that does not fit the on-chip memory), an index without resident fp32 rows, and an empty index run the
+ * host twin with used_gpu = 0.  Refusals, all before anything changes: those of hs_index_add_points, and HS_ERR_UNSUPPORTED for an
+ * index that holds delete marks (the batched insertion has no deleted-element branches; hs_index_add_points takes such an index). */
+hs_status hs_index_add_points_batched(hs_index *ix, const float *rows, const uint64_t *labels, size_t count,
+                                      const hs_batch_build_opts *opts, hs_batch_build_stats *stats /* nullable */);
+/* Diagnostic: what the device path of the last hs_index_add_points_batched brought back beside the new nodes: *lists_downloaded
+ * (nullable) old lists that received an id, and the old nodes (internal ids below the element count before the call, ascending)
+ * among them whose level-0 or upper list bytes changed -- a full list whose re-prune turns the new id away and keeps its order
+ * comes back as it was.  Both empty after a call the host twin served.  ids nullable, at most cap written. */
+hs_status hs_debug_batched_add_changed(const hs_index *ix, uint32_t *ids, size_t cap, size_t *count, size_t *lists_downloaded);
+/* Host only, no device: hs_hnsw_resume with the rows added in the batched order above, always on the host twin (opts->device is not
+ * used; used_gpu = 0) -- what hs_index_add_points_batched leaves for hs_index_save.  Refusals as that call (capacity, existing or
+ * repeated label, delete marks), before anything is added; out_path is then not written. */
+hs_status hs_hnsw_resume_batched(const char *in_path, int metric, size_t dim, size_t max_elements, const float *rows,
+                                 const uint64_t *labels, size_t count, size_t seed, size_t drawn, const hs_batch_build_opts *opts,
+                                 const char *out_path, hs_batch_build_stats *stats /* nullable */);
 /* Host only, no device: loadIndex(in_path, space, max_elements) with the constructor's allow_replace_deleted, then `n_ops`
  * operations in order, then saveIndex(out_path).  An operation is four 64-bit words {kind, label or new capacity, replace flag,
  * row index into `rows`}: HS_OP_ADD = addPoint(rows + row*dim, label, flag) (update, replacement or append as the reference decides),
