@@ -276,7 +276,7 @@ hs_status hs_convert_slimq_graph(const char *hnsw_path, int metric, size_t dim, 
 }
 
 // convertFromHNSW with the list-level work on the GPU (convert_gpu.hip); identical output bytes.  Shapes outside the device path
-// (degree capacities above 32, a reverse-edge list that outgrows the on-chip buffers) run the CPU conversion instead.
+// (degree capacities or budgets above 64, a source list above 64 ids, a reverse-edge list that outgrows the on-chip buffers) run the CPU conversion instead.
 hs_status hs_convert_slim_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
                               float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
                               size_t low_degree_m, int device, int threads, const char *out_path, int *used_gpu, double *kernel_ms) {

@@ -13,8 +13,12 @@
 namespace hs {
 
 static constexpr uint32_t kCvMaxList = 64;     // a source list (level-0 list of the vanilla graph) holds at most this many ids
-static constexpr uint32_t kCvMaxKeep = 32;     // pruned lists hold at most this many ids (top_degree_M0, maxM0 <= 32 .. see host check)
+static constexpr uint32_t kCvMaxKeep = 64;     // pruned / final lists hold at most this many ids (every capacity and budget <= 64 .. see host check)
 static constexpr uint32_t kCvUnionCap = 2048;  // own list + reverse edges of one (node, level), in LDS
+
+// `keep` in the kernels and launchers below and in the two .hip files is ConvertInput::keep (convert_engine.hpp): the slots per task of
+// the pruned (nn) and final (fin) lists of one call and the entries of the kernels' kept / keptd / kd arrays in LDS, 32 or kCvMaxKeep.
+// A wavefront handles a kept or final list with one lane per entry, which holds because keep <= 64.
 
 // distances query (LDS, dim floats) -> rows nid[0..cnt) (LDS) into nd[0..cnt) (LDS)
 template <int METRIC>
@@ -60,7 +64,7 @@ __device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const f
 template <int METRIC>
 __device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
                                              uint32_t *kept, float *kd, int lane, float *keptd = nullptr) {
-  uint32_t kc = 0;
+  uint32_t kc = 0;   // (kept / kd / keptd hold `keep` entries: the caller passes mlim <= keep)
   for (uint32_t t = 0; t < sz && kc < mlim; t++) {
     const float cd = unif(arr[t].d);
     const uint32_t cid = uni(arr[t].id);
@@ -89,10 +93,10 @@ __device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, con
 // (node u, level l) -> task index: level 0 = u, level l >= 1 = n + upb[u] + l - 1
 __device__ __forceinline__ uint32_t cv_task_of(uint32_t u, uint32_t l, uint32_t n, const uint32_t *upb) { return l == 0 ? u : n + upb[u] + l - 1; }
 
-// reverse edges (hnswalg_slim.h:988-998 / 1234-1241), counted then filled: nn / cnt = the pruned lists (kCvMaxKeep ids per task)
+// reverse edges (hnswalg_slim.h:988-998 / 1234-1241), counted then filled: nn / cnt = the pruned lists (`keep` ids per task, 32 or 64)
 hipError_t launch_cv_rev_count(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_level, const uint32_t *upb, uint32_t n, uint32_t ntasks,
-                               uint32_t *rcnt);
+                               uint32_t keep, uint32_t *rcnt);
 hipError_t launch_cv_rev_fill(const uint32_t *nn, const uint32_t *cnt, const uint32_t *t_node, const uint32_t *t_level, const uint32_t *upb, uint32_t n,
-                              uint32_t ntasks, const uint32_t *roff, uint32_t *rcur, uint32_t *rev);
+                              uint32_t ntasks, uint32_t keep, const uint32_t *roff, uint32_t *rcur, uint32_t *rev);
 
 }  // namespace hs

@@ -13,6 +13,9 @@
 //            heuristic returns: descending distance, and where two kept entries are at the same distance the push_heap /
 //            pop_heap mechanics of libstdc++ on one lane (heap_emul.hpp).  The list holds every kept entry (the reference pops
 //            `limit` entries whatever was kept, which reads an empty queue when fewer were).
+// The pruned and final lists have `keep` slots per task (ConvertInput::keep, 32 or 64), which these kernels take as an argument;
+// kept / keptd / kd in LDS hold as many entries.  (convert_gpu.hip's kernels, whose names and registers are pinned, take it as a
+// template parameter instead.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,7 +33,7 @@ static constexpr uint32_t kCdPad = 0xFFFFFFFFu;   // id of a padding entry of th
 template <int METRIC>
 __global__ void __launch_bounds__(64) cd_prune_kernel(const float *vec, uint32_t dim, const uint32_t *t_node, const uint32_t *t_off,
                                                       const uint32_t *t_size, const uint32_t *t_mlim, const uint32_t *lists, uint32_t ntasks,
-                                                      uint32_t *out_nn, uint32_t *out_cnt) {
+                                                      uint32_t keep, uint32_t *out_nn, uint32_t *out_cnt) {
   extern __shared__ __align__(16) unsigned char smem[];
   float *qv = reinterpret_cast<float *>(smem);
   float *qc = qv + dim;
@@ -38,15 +41,15 @@ __global__ void __launch_bounds__(64) cd_prune_kernel(const float *vec, uint32_t
   float *nd = reinterpret_cast<float *>(nid + kCvMaxList);
   Pair *arr = reinterpret_cast<Pair *>(nd + kCvMaxList);
   uint32_t *kept = reinterpret_cast<uint32_t *>(arr + kCvMaxList);
-  float *keptd = reinterpret_cast<float *>(kept + kCvMaxKeep);
-  float *kd = keptd + kCvMaxKeep;
+  float *keptd = reinterpret_cast<float *>(kept + keep);
+  float *kd = keptd + keep;
   const int lane = threadIdx.x;
   for (uint32_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
-    const uint32_t v = t_node[t], sz = min(t_size[t], kCvMaxList), mlim = min(t_mlim[t], kCvMaxKeep);
+    const uint32_t v = t_node[t], sz = min(t_size[t], kCvMaxList), mlim = min(t_mlim[t], keep);
     wave_sync();
     if ((uint32_t)lane < sz) nid[lane] = lists[t_off[t] + lane];
     if (sz < mlim) {   // `if (top_candidates.size() < M) return;` (hnswalg.h:484-486)
-      if ((uint32_t)lane < sz) out_nn[(size_t)t * kCvMaxKeep + lane] = nid[lane];
+      if ((uint32_t)lane < sz) out_nn[(size_t)t * keep + lane] = nid[lane];   // sz < mlim <= keep <= 64: one lane per entry
       if (lane == 0) out_cnt[t] = sz;
       continue;
     }
@@ -63,7 +66,7 @@ __global__ void __launch_bounds__(64) cd_prune_kernel(const float *vec, uint32_t
     }
     wave_sync();
     const uint32_t kc = cv_prune<METRIC>(vec, dim, arr, sz, mlim, qc, kept, kd, lane, keptd);
-    if ((uint32_t)lane < kc) out_nn[(size_t)t * kCvMaxKeep + lane] = kept[lane];
+    if ((uint32_t)lane < kc) out_nn[(size_t)t * keep + lane] = kept[lane];
     if (lane == 0) out_cnt[t] = kc;
   }
 }
@@ -73,7 +76,8 @@ __global__ void __launch_bounds__(64) cd_prune_kernel(const float *vec, uint32_t
 template <int METRIC>
 __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t dim, const uint32_t *t_node, const uint32_t *t_limit,
                                                       const uint32_t *nn, const uint32_t *cnt, const uint32_t *roff, const uint32_t *rcnt,
-                                                      const uint32_t *rev, uint32_t ntasks, uint32_t *fin, uint32_t *fin_cnt, uint32_t *flags) {
+                                                      const uint32_t *rev, uint32_t ntasks, uint32_t keep, uint32_t *fin, uint32_t *fin_cnt,
+                                                      uint32_t *flags) {
   extern __shared__ __align__(16) unsigned char smem[];
   float *qv = reinterpret_cast<float *>(smem);
   float *qc = qv + dim;
@@ -81,11 +85,11 @@ __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t
   float *nd = reinterpret_cast<float *>(ids + kCvUnionCap);
   Pair *arr = reinterpret_cast<Pair *>(nd + kCvUnionCap);
   uint32_t *kept = reinterpret_cast<uint32_t *>(arr + kCvUnionCap);
-  float *keptd = reinterpret_cast<float *>(kept + kCvMaxKeep);
-  float *kd = keptd + kCvMaxKeep;
+  float *keptd = reinterpret_cast<float *>(kept + keep);
+  float *kd = keptd + keep;
   const int lane = threadIdx.x;
   for (uint32_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
-    const uint32_t m1 = min(cnt[t], kCvMaxKeep), r = rcnt[t], total = m1 + r, limit = t_limit[t];
+    const uint32_t m1 = min(cnt[t], keep), r = rcnt[t], total = m1 + r, limit = t_limit[t];
     wave_sync();
     if (total > kCvUnionCap) {
       if (lane == 0) { atomicAdd(flags, 1u); fin_cnt[t] = 0; }
@@ -94,7 +98,7 @@ __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t
     uint32_t N = 64;
     while (N < total) N <<= 1;
     for (uint32_t i = lane; i < N; i += 64)
-      ids[i] = i < m1 ? nn[(size_t)t * kCvMaxKeep + i] : (i < total ? rev[roff[t] + (i - m1)] : 0xFFFFFFFFu);
+      ids[i] = i < m1 ? nn[(size_t)t * keep + i] : (i < total ? rev[roff[t] + (i - m1)] : 0xFFFFFFFFu);
     wave_sync();
     for (uint32_t k = 2; k <= N; k <<= 1)   // std::sort of plain ids (:1269): any correct sort gives the same array
       for (uint32_t j = k >> 1; j > 0; j >>= 1) {
@@ -120,10 +124,10 @@ __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t
       wave_sync();
     }
     if (m <= limit) {   // not re-pruned: ascending id (:1305-1307)
-      if (m <= kCvMaxKeep) {
-        if ((uint32_t)lane < m) fin[(size_t)t * kCvMaxKeep + lane] = ids[lane];
+      if (m <= keep) {   // (keep <= 64: one lane per entry, here and below)
+        if ((uint32_t)lane < m) fin[(size_t)t * keep + lane] = ids[lane];
         if (lane == 0) fin_cnt[t] = m;
-      } else if (lane == 0) { atomicAdd(flags, 1u); fin_cnt[t] = 0; }   // capacity above 32 ids: host path
+      } else if (lane == 0) { atomicAdd(flags, 1u); fin_cnt[t] = 0; }   // capacity above `keep` ids: host path
       continue;
     }
     const uint32_t v = t_node[t];
@@ -148,17 +152,17 @@ __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t
         }
         wave_sync();
       }
-    const uint32_t kc = cv_prune<METRIC>(vec, dim, arr, m, min(limit, kCvMaxKeep), qc, kept, kd, lane, keptd);
+    const uint32_t kc = cv_prune<METRIC>(vec, dim, arr, m, min(limit, keep), qc, kept, kd, lane, keptd);
     // pop order of the returned heap: kept order is ascending distance, so without equal distances it is the kept order reversed
     const bool eq = (uint32_t)lane + 1 < kc && keptd[lane] == keptd[lane + 1];
     if (hs_ballot(eq) == 0) {
-      if ((uint32_t)lane < kc) fin[(size_t)t * kCvMaxKeep + lane] = kept[kc - 1 - lane];
+      if ((uint32_t)lane < kc) fin[(size_t)t * keep + lane] = kept[kc - 1 - lane];
     } else {
       if ((uint32_t)lane < kc) arr[lane] = Pair{keptd[lane], kept[lane]};
       wave_sync();
       if (lane == 0) h2_pop_order(arr, (long)kc);
       wave_sync();
-      if ((uint32_t)lane < kc) fin[(size_t)t * kCvMaxKeep + lane] = arr[kc - 1 - lane].id;
+      if ((uint32_t)lane < kc) fin[(size_t)t * keep + lane] = arr[kc - 1 - lane].id;
     }
     if (lane == 0) { fin_cnt[t] = kc; atomicAdd(flags + 1, 1u); }
   }
@@ -170,8 +174,8 @@ __global__ void __launch_bounds__(64) cd_union_kernel(const float *vec, uint32_t
 // :1369-1371 without a second copy of the old graph; and its row and label in the Slim index against the HNSW index's.
 // flags[i]: bit 0 some level differs, bit 1 the node has neighbours, bit 2 row or label differs (or the node is beyond the previous
 // count, whose slots count as empty).
-__global__ void __launch_bounds__(256) cd_diff_kernel(const uint32_t *fin, const uint32_t *fin_cnt, const uint32_t *levels, const uint32_t *upb,
-                                                      uint32_t n, uint32_t prev, int32_t thr, const uint32_t *s_tile0, uint32_t stride,
+__global__ void __launch_bounds__(256) cd_diff_kernel(const uint32_t *fin, const uint32_t *fin_cnt, uint32_t fstride, const uint32_t *levels,
+                                                      const uint32_t *upb, uint32_t n, uint32_t prev, int32_t thr, const uint32_t *s_tile0, uint32_t stride,
                                                       const uint32_t *s_up_base, const uint32_t *s_up_ptr, uint32_t n_up, const uint32_t *s_cols,
                                                       const uint64_t *s_labels, const uint64_t *h_labels, const float *s_vec, const float *h_vec,
                                                       uint32_t dim, uint8_t *flags) {
@@ -185,8 +189,8 @@ __global__ void __launch_bounds__(256) cd_diff_kernel(const uint32_t *fin, const
   uint32_t total = 0;
   for (uint32_t l = 0; l <= L; l++) {
     const uint32_t t = cv_task_of(i, l, n, upb);
-    const uint32_t cnt = min(fin_cnt[t], kCvMaxKeep);
-    const uint32_t my = lane < cnt ? fin[(size_t)t * kCvMaxKeep + lane] : 0xFFFFFFFFu;
+    const uint32_t cnt = min(fin_cnt[t], fstride);   // fstride = the call's slots per task <= 64: one lane per entry of a final list
+    const uint32_t my = lane < cnt ? fin[(size_t)t * fstride + lane] : 0xFFFFFFFFu;
     const bool keep = lane < cnt && ((int32_t)l == thr || (my < n && levels[my] == l));
     const unsigned long long km = hs_ballot(keep);
     const uint32_t nk = __popcll(km), pos = __popcll(km & ((1ull << lane) - 1ull));
@@ -289,19 +293,21 @@ hipError_t gpu_convert_diff_lists(const ConvertInput &in, const float *d_vec, in
   std::vector<uint32_t> rcnt(nt), roff(nt + 1, 0);
   uint32_t flags[2] = {0, 0};
   bool timed = false;
-  const size_t lds1 = (size_t)in.dim * 8 + kCvMaxList * 16 + kCvMaxKeep * 12;
-  const size_t lds3 = (size_t)in.dim * 8 + (size_t)kCvUnionCap * 16 + kCvMaxKeep * 12;
+  const uint32_t keep = in.keep;   // slots per task of nn / fin, entries of kept / keptd / kd in LDS
+  const size_t lds1 = (size_t)in.dim * 8 + kCvMaxList * 16 + keep * 12;
+  const size_t lds3 = (size_t)in.dim * 8 + (size_t)kCvUnionCap * 16 + keep * 12;
   const uint32_t grid = 256 * 16;
   if (nt == 0) return hipSuccess;
   if (!d_vec) return hipErrorInvalidDevicePointer;
+  if (keep != 32 && keep != kCvMaxKeep) return hipErrorInvalidValue;
   if (lds3 > 160 * 1024) { needs_host = true; return hipSuccess; }   // rows too long for the on-chip buffers
   CD_TRY(hipSetDevice(device));
   CD_TRY(cd_upload(&d_node, in.t_node)); CD_TRY(cd_upload(&d_off, in.t_off)); CD_TRY(cd_upload(&d_size, in.t_size));
   CD_TRY(cd_upload(&d_mlim, in.t_mlim)); CD_TRY(cd_upload(&d_limit, in.t_limit)); CD_TRY(cd_upload(&d_level, in.t_level));
   CD_TRY(cd_upload(&d_lists, in.lists)); CD_TRY(cd_upload(&d_upb, in.upb));
-  CD_TRY(hipMalloc((void **)&d_nn, (size_t)nt * kCvMaxKeep * 4)); CD_TRY(hipMalloc((void **)&d_cnt, (size_t)nt * 4));
+  CD_TRY(hipMalloc((void **)&d_nn, (size_t)nt * keep * 4)); CD_TRY(hipMalloc((void **)&d_cnt, (size_t)nt * 4));
   CD_TRY(hipMalloc((void **)&d_rcnt, (size_t)nt * 4)); CD_TRY(hipMalloc((void **)&d_roff, (size_t)(nt + 1) * 4)); CD_TRY(hipMalloc((void **)&d_rcur, (size_t)nt * 4));
-  CD_TRY(hipMalloc((void **)&d_fin, (size_t)nt * kCvMaxKeep * 4)); CD_TRY(hipMalloc((void **)&d_fcnt, (size_t)nt * 4)); CD_TRY(hipMalloc((void **)&d_flags, 8));
+  CD_TRY(hipMalloc((void **)&d_fin, (size_t)nt * keep * 4)); CD_TRY(hipMalloc((void **)&d_fcnt, (size_t)nt * 4)); CD_TRY(hipMalloc((void **)&d_flags, 8));
   CD_TRY(hipMemset(d_rcnt, 0, (size_t)nt * 4)); CD_TRY(hipMemset(d_rcur, 0, (size_t)nt * 4)); CD_TRY(hipMemset(d_flags, 0, 8));
   CD_TRY(hipEventCreate(&e0)); CD_TRY(hipEventCreate(&e1));
   if (lds3 > 64 * 1024) {
@@ -313,17 +319,17 @@ hipError_t gpu_convert_diff_lists(const ConvertInput &in, const float *d_vec, in
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
   }
   CD_TRY(hipEventRecord(e0, nullptr));
-  if (in.metric == METRIC_L2) hipLaunchKernelGGL(cd_prune_kernel<METRIC_L2>, dim3(std::min(grid, nt)), dim3(64), lds1, nullptr, d_vec, in.dim, d_node, d_off, d_size, d_mlim, d_lists, nt, d_nn, d_cnt);
-  else hipLaunchKernelGGL(cd_prune_kernel<METRIC_IP>, dim3(std::min(grid, nt)), dim3(64), lds1, nullptr, d_vec, in.dim, d_node, d_off, d_size, d_mlim, d_lists, nt, d_nn, d_cnt);
+  if (in.metric == METRIC_L2) hipLaunchKernelGGL(cd_prune_kernel<METRIC_L2>, dim3(std::min(grid, nt)), dim3(64), lds1, nullptr, d_vec, in.dim, d_node, d_off, d_size, d_mlim, d_lists, nt, keep, d_nn, d_cnt);
+  else hipLaunchKernelGGL(cd_prune_kernel<METRIC_IP>, dim3(std::min(grid, nt)), dim3(64), lds1, nullptr, d_vec, in.dim, d_node, d_off, d_size, d_mlim, d_lists, nt, keep, d_nn, d_cnt);
   CD_TRY(hipGetLastError());
-  CD_TRY(launch_cv_rev_count(d_nn, d_cnt, d_level, d_upb, in.n, nt, d_rcnt));
+  CD_TRY(launch_cv_rev_count(d_nn, d_cnt, d_level, d_upb, in.n, nt, keep, d_rcnt));
   CD_TRY(hipMemcpy(rcnt.data(), d_rcnt, (size_t)nt * 4, hipMemcpyDeviceToHost));
   for (uint32_t t = 0; t < nt; t++) roff[t + 1] = roff[t] + rcnt[t];
   CD_TRY(hipMemcpy(d_roff, roff.data(), (size_t)(nt + 1) * 4, hipMemcpyHostToDevice));
   CD_TRY(hipMalloc((void **)&d_rev, std::max<size_t>(roff[nt], 1) * 4));
-  CD_TRY(launch_cv_rev_fill(d_nn, d_cnt, d_node, d_level, d_upb, in.n, nt, d_roff, d_rcur, d_rev));
-  if (in.metric == METRIC_L2) hipLaunchKernelGGL(cd_union_kernel<METRIC_L2>, dim3(std::min(grid, nt)), dim3(64), lds3, nullptr, d_vec, in.dim, d_node, d_limit, d_nn, d_cnt, d_roff, d_rcnt, d_rev, nt, d_fin, d_fcnt, d_flags);
-  else hipLaunchKernelGGL(cd_union_kernel<METRIC_IP>, dim3(std::min(grid, nt)), dim3(64), lds3, nullptr, d_vec, in.dim, d_node, d_limit, d_nn, d_cnt, d_roff, d_rcnt, d_rev, nt, d_fin, d_fcnt, d_flags);
+  CD_TRY(launch_cv_rev_fill(d_nn, d_cnt, d_node, d_level, d_upb, in.n, nt, keep, d_roff, d_rcur, d_rev));
+  if (in.metric == METRIC_L2) hipLaunchKernelGGL(cd_union_kernel<METRIC_L2>, dim3(std::min(grid, nt)), dim3(64), lds3, nullptr, d_vec, in.dim, d_node, d_limit, d_nn, d_cnt, d_roff, d_rcnt, d_rev, nt, keep, d_fin, d_fcnt, d_flags);
+  else hipLaunchKernelGGL(cd_union_kernel<METRIC_IP>, dim3(std::min(grid, nt)), dim3(64), lds3, nullptr, d_vec, in.dim, d_node, d_limit, d_nn, d_cnt, d_roff, d_rcnt, d_rev, nt, keep, d_fin, d_fcnt, d_flags);
   CD_TRY(hipGetLastError());
   CD_TRY(hipMemcpy(flags, d_flags, 8, hipMemcpyDeviceToHost));
   needs_host = flags[0] != 0;
@@ -335,7 +341,7 @@ hipError_t gpu_convert_diff_lists(const ConvertInput &in, const float *d_vec, in
     CD_TRY(cd_upload(&d_lev, diff->levels));
     CD_TRY(hipMalloc((void **)&d_nf, n)); CD_TRY(hipMalloc((void **)&d_counts, (size_t)nw * 16)); CD_TRY(hipMalloc((void **)&d_tot, 16));
     CD_TRY(hipMalloc((void **)&d_ids, (size_t)n * 16));
-    hipLaunchKernelGGL(cd_diff_kernel, dim3((n + 3) / 4), dim3(256), 0, nullptr, d_fin, d_fcnt, d_lev, d_upb, n, diff->prev_count, diff->threshold_level,
+    hipLaunchKernelGGL(cd_diff_kernel, dim3((n + 3) / 4), dim3(256), 0, nullptr, d_fin, d_fcnt, keep, d_lev, d_upb, n, diff->prev_count, diff->threshold_level,
                        diff->s_tile0, diff->s_stride, diff->s_up_base, diff->s_up_ptr, diff->n_up, diff->s_cols, diff->s_labels, diff->h_labels, diff->s_vec, d_vec,
                        in.dim, d_nf);
     CD_TRY(hipGetLastError());
@@ -365,7 +371,7 @@ hipError_t gpu_convert_diff_lists(const ConvertInput &in, const float *d_vec, in
     CD_TRY(hipEventSynchronize(e1));
   }
   if (kernel_ms) { float ms = 0.f; CD_TRY(hipEventElapsedTime(&ms, e0, e1)); *kernel_ms = ms; }
-  fin.resize((size_t)nt * kCvMaxKeep);
+  fin.resize((size_t)nt * keep);
   fin_cnt.resize(nt);
   CD_TRY(hipMemcpy(fin.data(), d_fin, fin.size() * 4, hipMemcpyDeviceToHost));
   CD_TRY(hipMemcpy(fin_cnt.data(), d_fcnt, (size_t)nt * 4, hipMemcpyDeviceToHost));

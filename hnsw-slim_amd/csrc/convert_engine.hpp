@@ -18,9 +18,12 @@ struct ConvertInput {
   std::vector<uint32_t> t_limit;                          // capacity of the level (maxM0 / maxM, :1037)
   std::vector<uint32_t> lists;                            // concatenated source lists
   std::vector<uint32_t> upb;                              // n: index of the node's first upper-level task
+  // slots per task of the pruned and final lists: 32 when every capacity (t_limit) and budget (t_mlim) of the call is at most 32,
+  // 64 when one is above (none may exceed 64)
+  uint32_t keep = 32;
 };
 
-// Phases 1-3 of convertFromHNSW on device `device`: fin[t * 32 .. + fin_cnt[t]) = the final list of task t (after the reverse-edge
+// Phases 1-3 of convertFromHNSW on device `device`: fin[t * in.keep .. + fin_cnt[t]) = the final list of task t (after the reverse-edge
 // union and the re-prune, before the hierarchical filter).  needs_host: some list exceeded the on-chip buffers -- the caller
 // falls back to the CPU conversion.  kernel_ms (nullable): device time of the kernels.
 hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,

@@ -13,6 +13,9 @@ inline bool make_convert_input(const VanillaGraph &g, const SlimParams &p, const
                                ConvertInput &in) {
   const size_t n = g.count;
   in.vec = nullptr; in.n = (uint32_t)n; in.dim = (uint32_t)g.dim; in.metric = (int)g.metric;
+  // the stride of the pruned / final lists: 32 slots, as for every graph up to M = 16 with budgets up to 32, unless a capacity or
+  // a degree budget needs more (the callers have checked that none exceeds 64)
+  in.keep = std::max({maxM0, maxM, p.top_M0, p.low_m0, p.top_M, p.low_m}) <= 32 ? 32 : 64;
   in.upb.assign(n, 0);
   size_t nup = 0;
   for (size_t i = 0; i < n; i++) { in.upb[i] = (uint32_t)nup; nup += g.levels[i]; }
@@ -33,8 +36,8 @@ inline bool make_convert_input(const VanillaGraph &g, const SlimParams &p, const
   for (size_t t = 0; t < nt; t++)
     if (in.t_size[t] > 64) return false;
   // what the device kernels index with: every list entry a node of at least the list's level (the reverse-edge kernels address
-  // task n + upb[u] + l - 1 for a level-l edge to u), 32-bit prefix sums.  A file that breaks this takes the CPU conversion.
-  if (nt >= 0xFFFFFFFFull || in.lists.size() >= 0xFFFFFFFFull || 2 * in.lists.size() >= 0xFFFFFFFFull) return false;
+  // task n + upb[u] + l - 1 for a level-l edge to u), 32-bit prefix sums and slot numbers (nt * keep).  A file that breaks this takes the CPU conversion.
+  if (nt * in.keep >= 0xFFFFFFFFull || in.lists.size() >= 0xFFFFFFFFull || 2 * in.lists.size() >= 0xFFFFFFFFull) return false;
   for (size_t t = 0; t < nt; t++) {
     const uint32_t l = in.t_level[t];
     for (uint32_t j = 0; j < in.t_size[t]; j++) {
@@ -44,28 +47,28 @@ inline bool make_convert_input(const VanillaGraph &g, const SlimParams &p, const
   }
   return true;
 }
-// The final lists as the device hands them back: 32 slots per task, task (v, l) where make_convert_input() put it.
+// The final lists as the device hands them back: in.keep slots per task, task (v, l) where make_convert_input() put it.
 struct DeviceLists {
   const ConvertInput &in;
   std::vector<uint32_t> fin, fin_cnt;
   const uint32_t *operator()(size_t v, int l, size_t &cnt) const {
     const size_t t = l == 0 ? v : (size_t)in.n + in.upb[v] + l - 1;
     cnt = fin_cnt[t];
-    return fin.data() + t * 32;
+    return fin.data() + t * in.keep;
   }
 };
 
 // convert_diff() on the device (convert_diff.hip): the list passes read the rows from `d_vec`, the resident fp32 array of the HNSW
 // index; the diff kernel compares the final lists with the Slim index's resident adjacency (dd) and hands back the compacted
 // lists; the host then assembles the element and blob of the flagged nodes only and looks up the labels of the nodes whose
-// label changed.  Returns false, with `s` untouched, when the shape is outside the device path (capacities above 32
-// ids, a source list above 64, a union above 2048): the caller then runs convert_diff().
+// label changed.  Returns false, with `s` untouched, when the shape is outside the device path (capacities or
+// degree budgets above 64 ids, a source list above 64, a union above 2048): the caller then runs convert_diff().
 // accept (nullable): called with the nodes whose row or label the call would rewrite, before anything changes; false refuses the
 // call (*refused set, `s` untouched).
 inline bool convert_diff_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, const float *d_vec, int device, int threads,
                              SlimLookup &lk, DiffDev &dd, SlimDiff &out, double *kernel_ms, std::string *err,
                              const std::function<bool(const std::vector<uint32_t> &)> *accept = nullptr, bool *refused = nullptr) {
-  if (g.maxM0 > 32 || g.maxM > 32 || s.maxM0 > 32 || s.maxM > 32 || p.top_M0 > 32 || p.low_m0 > 32 || p.top_M > 32 || p.low_m > 32) return false;
+  if (g.maxM0 > 64 || g.maxM > 64 || s.maxM0 > 64 || s.maxM > 64 || p.top_M0 > 64 || p.low_m0 > 64 || p.top_M > 64 || p.low_m > 64) return false;
   const size_t prev_count = s.count, n = g.count;
   ConvertInput in;
   if (!make_convert_input(g, p, SlimGraph::hub_thresholds(g, p), s.maxM0, s.maxM, in)) return false;
@@ -120,10 +123,10 @@ inline bool convert_diff_gpu(SlimGraph &s, const VanillaGraph &g, const SlimPara
   return true;
 }
 // convert() with the list-level work on the GPU (convert_gpu.hip).  Returns false when the shape is outside the
-// device path (lists longer than 64 / capacities above 32 ids, or a reverse-edge list that outgrew the on-chip buffers):
+// device path (lists longer than 64 / capacities or degree budgets above 64 ids, or a reverse-edge list that outgrew the on-chip buffers):
 // the caller then runs convert().  kernel_ms: device time of the kernels.
 inline bool convert_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
-  if (g.maxM0 > 32 || g.maxM > 32 || p.top_M0 > 32 || p.low_m0 > 32 || p.top_M > 32 || p.low_m > 32) return false;
+  if (g.maxM0 > 64 || g.maxM > 64 || p.top_M0 > 64 || p.low_m0 > 64 || p.top_M > 64 || p.low_m > 64) return false;
   s.take_header(g, p);
   const size_t n = s.count;
   const std::vector<size_t> thr = SlimGraph::hub_thresholds(g, p);

@@ -667,7 +667,8 @@ hs_status hs_convert_slim(const char *hnsw_path, int metric, size_t dim, int thr
 /* The same conversion with the per-list work on HIP device `device` (per-node distances, the by-distance
  * std::sort with libstdc++'s tie order, PruneByHeuristic :836-865, the reverse-edge union :988-1012, the re-prune
  * :1038-1062); histograms, hub thresholds and the final assembly run on `threads` host threads.  The file is byte-identical
- * to hs_convert_slim's.  Shapes outside the device path (degree capacities above 32, a reverse-edge list beyond 2048 ids)
+ * to hs_convert_slim's.  Shapes outside the device path (degree capacities or budgets above 64 -- a graph built with M > 32 --, a source
+ * list above 64 ids, a reverse-edge union beyond 2048 ids)
  * are converted on the CPU; *used_gpu (nullable) says which path ran, *kernel_ms (nullable) the device time. */
 hs_status hs_convert_slim_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level,
                               float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
