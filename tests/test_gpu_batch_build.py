@@ -1,11 +1,13 @@
 """Batched addPoint on the GPU (hs_build_hnsw_batched with a device, csrc/build_gpu.hip) against its host twin
-(csrc/host_batch_build.hpp): whole files, byte for byte; at batch_max = 1 against the reference-equal serial builder."""
+(csrc/host_batch_build.hpp): whole files, byte for byte; at batch_max = 1 against the reference-equal serial builder; at the edges
+of the device path's envelope and of the fp32 range.  (Against an independent reading: tests/test_gpu_batch_build_restated.py.)"""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import batch_build_cases as C
 from hsutil import GOLDEN, ROOT, Oracle, load_product, mixture
 
 pytestmark = pytest.mark.gpu
@@ -151,3 +153,57 @@ def test_facade_build(hs, tmp_path):
     assert outs[0] == outs[1] and saved[0] == saved[1]
     labels = np.frombuffer(outs[0], np.uint64, 40 * 10).reshape(40, 10)
     assert labels.min() >= 1000 and labels.max() < 1800
+
+
+# ---- the edges of the device path's envelope, and of the fp32 range (device against twin: these need fp32 rows) -------------------------
+def device_supported(dim, M, efc, scratch_ids=0):
+    """gpu_build_supported of csrc/build_gpu.hip, restated from its text: M <= kBgMaxM = 31, max(efc, M) <= kBgMaxEfc = 512, and the LDS
+    of one row -- bg_search_lds = 8 dpad + 8 topcap + 5 * 256 + 12 scratch_ids with dpad = dim rounded up to 4 and topcap the power of
+    two (64 at least) that holds efc + 1 entries; bg_link_lds = 8 dpad + 64 * 8 + 7 * 256 -- within kBgLdsLimit = 160 KiB."""
+    s, e = scratch_ids or 4096, max(efc, M)
+    if M == 0 or M > 31 or e > 512:
+        return False
+    dpad, topcap = (dim + 3) // 4 * 4, 64
+    while topcap < e + 1:
+        topcap *= 2
+    return 8 * dpad + 8 * topcap + 5 * 256 + 12 * s <= 160 * 1024 and 8 * dpad + 64 * 8 + 7 * 256 <= 160 * 1024
+
+
+# The LDS limit: at scratch_ids = 8192 (98304 bytes) and ef_construction = 100 (topcap 128: 1024 bytes) bg_search_lds is
+# 8 dpad + 100608, which is 160 KiB = 163840 exactly at dpad = 7904 and above it at the next dpad, 7908.
+LDS_EDGE_DIM = 7904
+ENVELOPE = {
+    "M31_efc512": (lambda: mixture(1500, 32, 11), dict(M=31, ef_construction=512), True),
+    "M31_efc31": (lambda: mixture(1500, 32, 11), dict(M=31, ef_construction=31), True),
+    "M2": (lambda: mixture(1000, 16, 11), dict(M=2, ef_construction=10), True),
+    "dim1": (lambda: mixture(600, 1, 11), dict(M=8, ef_construction=40), True),
+    "dim3": (lambda: mixture(600, 3, 11), dict(M=8, ef_construction=40), True),
+    "dim23": (lambda: mixture(600, 23, 11), dict(M=8, ef_construction=40), True),
+    "dim960": (lambda: mixture(600, 960, 11), dict(M=8, ef_construction=40), True),
+    "scratch8192": (lambda: mixture(1000, 32, 11), dict(M=8, ef_construction=100, scratch_ids=8192), True),
+    "lds_at_the_limit": (lambda: mixture(200, LDS_EDGE_DIM, 11), dict(M=8, ef_construction=100, scratch_ids=8192), True),
+    "lds_above_the_limit": (lambda: mixture(200, LDS_EDGE_DIM + 4, 11), dict(M=8, ef_construction=100, scratch_ids=8192), False),
+    "M32": (lambda: mixture(400, 16, 8), dict(M=32, ef_construction=64), False),
+    "efc513": (lambda: mixture(600, 16, 8), dict(M=8, ef_construction=513), False),
+}
+
+
+@pytest.mark.parametrize("name", list(ENVELOPE))
+def test_envelope(hs, tmp_path, name):
+    make, kw, on_device = ENVELOPE[name]
+    base = make()
+    assert device_supported(base.shape[1], kw["M"], kw["ef_construction"], kw.get("scratch_ids", 0)) == on_device
+    t, d, st = both(hs, tmp_path, base, **kw)
+    assert bool(st["used_gpu"]) == on_device
+    assert t == d
+
+
+@pytest.mark.parametrize("batch_max", [0, 64])
+@pytest.mark.parametrize("case", C.vr_cases(), ids=C.vr_name)
+def test_value_range(hs, oracle, tmp_path, case, batch_max):
+    """The families of tests/value_range.py as a build meets them: distances above 2^100, subnormal, all equal, of both signs,
+    +inf.  600 rows at M 8, ef_construction 60; the family's premise holds on the rows' own distance table (asserted)."""
+    rows = C.vr_rows(case)
+    C.vr_check_premise(oracle, case, rows)
+    t, d, st = both(hs, tmp_path, rows, metric=case[1], M=C.VR_M, ef_construction=C.VR_EFC, batch_max=batch_max)
+    assert st["used_gpu"] and t == d

@@ -1,7 +1,8 @@
 """GPU tests (MI355X) of the batched add into a resident vanilla index (hs_index_add_points_batched): the device path
 against its host twin (hs_hnsw_resume_batched) byte for byte through Index.save(), a split build against the whole device build,
 batch_max = 1 against add_points(threads=1) and the compiled reference's file, the resident index against its own saved file loaded
-afresh, the re-run / long-segment / re-tile paths, tiny inputs, the compaction of the changed lists, refusals, and the facade."""
+afresh, the re-run / long-segment / re-tile paths, tiny inputs, the compaction of the changed lists, refusals, the facade, and the
+edges of the device path's envelope and of the fp32 range."""
 import os
 import struct
 import subprocess
@@ -9,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import batch_build_cases as C
 from hsutil import GOLDEN, ROOT, load_product, mixture
 
 pytestmark = pytest.mark.gpu
@@ -343,3 +345,40 @@ def test_facade_batched_add(hs, tmp_path):
     assert run.returncode == 0, run.stdout + run.stderr
     w = run.stdout.split()
     assert w[:2] == ["add:", "1"] and 1 < int(w[2]) < 300 and w[4] == "800", run.stdout
+
+
+# ---- the edges of the device path's envelope, and of the fp32 range (device against twin: these need fp32 rows) -------------------------
+@pytest.mark.parametrize("name,M,efc,dim,scratch_ids", [("M31_efc512", 31, 512, 32, 0), ("M31_efc31", 31, 31, 32, 0), ("M2", 2, 10, 16, 0),
+                                                        ("dim1", 8, 40, 1, 0), ("dim23", 8, 40, 23, 0), ("dim960", 8, 40, 960, 0),
+                                                        ("scratch8192", 8, 100, 32, 8192)])
+def test_envelope(hs, tmp_path, name, M, efc, dim, scratch_ids):
+    """The edges of gpu_build_supported (M = kBgMaxM, ef_construction = kBgMaxEfc and = M, M = 2, odd and large dims, the largest
+    scratch_ids) as an add of the second half of 1000 rows."""
+    base = mixture(1000, dim, 11)
+    part = str(tmp_path / "part.bin")
+    hs.build_hnsw_batched(base[:500], part, M=M, ef_construction=efc, seed=SEED, device=-1, threads=16)
+    kw = dict(scratch_ids=scratch_ids) if scratch_ids else {}
+    t, ix, st = add_both(hs, tmp_path, part, base, 500, **kw)
+    assert st["used_gpu"] and ix.info()["n"] == 1000
+    assert saved(ix, tmp_path) == t
+
+
+def test_envelope_fallback_at_M_32(hs, tmp_path):
+    base = mixture(400, 16, 8)
+    part = str(tmp_path / "part.bin")
+    hs.build_hnsw_batched(base[:200], part, M=32, ef_construction=64, seed=SEED, device=-1, threads=16)
+    t, ix, st = add_both(hs, tmp_path, part, base, 200)
+    assert not st["used_gpu"] and saved(ix, tmp_path) == t
+
+
+@pytest.mark.parametrize("batch_max", [0, 64])
+@pytest.mark.parametrize("case", C.vr_cases(), ids=C.vr_name)
+def test_value_range(hs, oracle, tmp_path, case, batch_max):
+    """The families of tests/value_range.py as an add of the second half of 600 rows meets them (M 8, ef_construction 60); the
+    family's premise holds on the rows' own distance table (asserted)."""
+    rows = C.vr_rows(case)
+    C.vr_check_premise(oracle, case, rows)
+    part = str(tmp_path / "part.bin")
+    hs.build_hnsw_batched(rows[:300], part, metric=case[1], M=C.VR_M, ef_construction=C.VR_EFC, seed=SEED, device=-1, threads=16)
+    t, ix, st = add_both(hs, tmp_path, part, rows, 300, metric=case[1], batch_max=batch_max)
+    assert st["used_gpu"] and saved(ix, tmp_path) == t
