@@ -40,6 +40,7 @@ EXPORTS = [
     "hs_queue_join_stream", "hs_queue_drain", "hs_queue_info",
     "hs_build_hnsw_batched", "hs_build_schedule",
     "hs_index_add_points_batched", "hs_hnsw_resume_batched", "hs_debug_batched_add_changed",
+    "hs_build_rabitq_hnsw_batched", "hs_debug_rq_raw_dist",
 ]
 
 
@@ -223,6 +224,10 @@ def lib():
     L.hs_host_device_pointer.restype = ctypes.c_void_p
     L.hs_host_device_pointer.argtypes = [vp]
     L.hs_build_rabitq_hnsw.argtypes = [vp, sz, sz, ci, sz, sz, sz, ci, ctypes.c_char_p]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_build_rabitq_hnsw_batched"):   # (a baseline build in an A/B run may predate these)
+        L.hs_build_rabitq_hnsw_batched.argtypes = [vp, sz, sz, ci, sz, sz, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.c_char_p,
+                                                   ctypes.POINTER(HsBatchBuildStats)]
+        L.hs_debug_rq_raw_dist.argtypes = [vp, vp, sz, sz, ci, ci, vp]
     L.hs_convert_slim_gpu.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ci, ctypes.c_char_p,
                                       ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.hs_convert_slimq.argtypes = [ctypes.c_char_p, ci, sz, vp, sz, vp, ctypes.c_uint64, ci, ctypes.c_char_p]
@@ -377,6 +382,33 @@ def build_rabitq_hnsw(base, out_path, metric=HS_METRIC_L2, M=32, ef_construction
     base = np.ascontiguousarray(base, np.float32)
     _check(lib().hs_build_rabitq_hnsw(base.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction, seed, threads,
                                       out_path.encode()))
+
+
+def build_rabitq_hnsw_batched(base, out_path, metric=HS_METRIC_L2, M=32, ef_construction=128, seed=100, device=-1, threads=1, grow_div=0,
+                              batch_max=0, scratch_ids=0):
+    """hs_build_rabitq_hnsw_batched: build_rabitq_hnsw's graph from the batched insertion order on HIP device `device`,
+    or on the host twin (device=-1, `threads` workers); both write the same file, and batch_max=1 writes build_rabitq_hnsw(threads=1)'s.
+    Returns the stats dict of build_hnsw_batched."""
+    base = np.ascontiguousarray(base, np.float32)
+    if base.ndim != 2:
+        raise HsError(HS_ERR_INVALID, "base: rows x dim")
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsBatchBuildStats()
+    _check(lib().hs_build_rabitq_hnsw_batched(base.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction, seed, ctypes.byref(opts),
+                                              out_path.encode(), ctypes.byref(st)))
+    return {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows), "kernel_ms": st.kernel_ms,
+            "total_ms": st.total_ms}
+
+
+def rq_raw_dist(a, b, metric=HS_METRIC_L2, device=-1):
+    """hs_debug_rq_raw_dist: rabitqlib's raw distance of rows a[i] and b[i] -- the host recipe (device=-1) or the wavefront recipe of
+    the build kernels on a HIP device.  Returns float32[n_pairs]."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise HsError(HS_ERR_INVALID, "a, b: n_pairs x dim each")
+    out = np.empty(a.shape[0], np.float32)
+    _check(lib().hs_debug_rq_raw_dist(a.ctypes.data, b.ctypes.data, a.shape[0], a.shape[1], metric, device, out.ctypes.data))
+    return out
 
 
 def convert_slimq_graph(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_level=0, top_degree_percent0=0.02,

@@ -10,6 +10,7 @@
 namespace hs {
 
 static constexpr uint32_t kBgMaxM = 31;          // maxM0 + 1 candidates of a full level-0 list fit one wavefront
+static constexpr uint32_t kRqMaxM = 32;          // rabitqlib's builder: maxM0 + 1 = 65 candidates, two per lane
 static constexpr uint32_t kBgMaxEfc = 512;
 static constexpr uint32_t kBgScratchIds = 4096;  // default on-chip share of one row: visited ids (candidates: half of it)
 
@@ -21,10 +22,16 @@ struct GpuBuildInput {
   const int *levels = nullptr;                    // n
   const std::vector<BatchStep> *steps = nullptr;
   uint32_t scratch_ids = 0;                       // 0: kBgScratchIds; else a power of two >= 64
+  bool rq = false;                                // rabitqlib's builder: RqGraph's rules, labels are the row index
 };
 
 // Whether the device path serves the shape (otherwise the host twin builds it): M, ef_construction, and the on-chip memory of a row.
 bool gpu_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratch_ids);
+
+// The same for rabitqlib's builder (GpuBuildInput::rq): M from 2 to 32.
+bool gpu_rq_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratch_ids);
+// rabitq_raw_dist (rq_dist.hpp) as the kernels of that builder compute it: out[i] = the distance of rows a[i] and b[i] (host arrays).
+hipError_t gpu_rq_raw_dist(const float *a, const float *b, size_t n_pairs, uint32_t dim, int metric, int device, float *out);
 
 // Batched addPoint on `device`.  Out: the level-0 lists (n x (maxM0 + 1) words, hnswlib's [u16 count][u16][ids] form), the upper
 // lists ((maxM + 1) words each, node i's level l at slot upb[i] + l - 1), upb (n + 1 prefix sums of the levels), the rows that

@@ -14,6 +14,8 @@
 //                      over {new id} + the list at maxM / maxM0, stored in pop order (what it does not overwrite stays, as in
 //                      the reference's memory).
 // Every store is a vector store; nothing is read back between batches.
+// The same batches for rabitqlib's builder, the graph HNSW-SlimQ converts from: rq_search_kernel / rq_link_kernel,
+// between the same bg_rev / bg_scan launches (GpuBuildInput::rq).
 // The same batches continued on a resident index (gpu_batch_add): the rows are the index's own array, the lists are
 // seeded from its host image, and between bg_scan and bg_link of every batch
 //   bga_mark_kernel    marks the lists of the old nodes that have incoming ids; after the last batch bga_count / bga_scan /
@@ -27,6 +29,7 @@
 #include "build_engine.hpp"
 #include "convert_common.hpp"
 #include "diff_prune.hpp"
+#include "rq_dist.hpp"
 
 namespace hs {
 
@@ -372,6 +375,331 @@ __global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, ui
   }
 }
 
+// ---- rabitqlib's builder (the host twin is host_rq_batch_build.hpp) ---------------------------------------------------
+// The same batches for the graph HNSW-SlimQ converts from (RqGraph, host_rq_graph.hpp), at M up to 32.  Kernels of their own, with
+// the signatures of the two above, so that the vanilla instantiations stay what they were: every distance is rq_dists (rq_dist.hpp),
+// both heaps order (distance, id) pairs -- a total order, so libstdc++'s heap mechanics decide nothing and any correct heap or sort
+// serves -- the heuristic takes its candidates by ascending pair and what it keeps leaves the max-heap in descending pair order,
+// i.e. reversed; a list that already names the new id is left alone.  bg_rev_kernel and bg_scan_kernel serve both flavours.
+__device__ __forceinline__ bool rq_less(const Pair &a, const Pair &b) { return a.d < b.d || (a.d == b.d && a.id < b.id); }
+struct RqLess { __device__ __forceinline__ bool operator()(const Pair &a, const Pair &b) const { return rq_less(a, b); } };      // maxheap (hnsw.hpp:33-34)
+struct RqGreater { __device__ __forceinline__ bool operator()(const Pair &a, const Pair &b) const { return rq_less(b, a); } };   // minheap (:35-36)
+
+// ascending (distance, id) sort of arr[0..N) (N a power of two, padding entries behind every candidate)
+__device__ __forceinline__ void rq_sort_asc(Pair *arr, uint32_t N, int lane) {
+  for (uint32_t k = 2; k <= N; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = lane; i < N; i += 64) {
+        const uint32_t p = i ^ j;
+        if (p > i) {
+          const Pair a = arr[i], b = arr[p];
+          const bool a_after_b = b.id != kBgPad && (a.id == kBgPad || rq_less(b, a));
+          const bool up = (i & k) == 0;
+          if (a_after_b == up) { arr[i] = b; arr[p] = a; }
+        }
+      }
+      wave_sync();
+    }
+}
+
+// The keep loop of get_neighbors_by_heuristic2 (hnsw.hpp:1016-1054) over arr[0..sz) in ascending pair order: a candidate is kept
+// unless a kept one is closer to it than the node is.  kept / kd hold mlim <= 64 entries.
+template <int METRIC>
+__device__ __forceinline__ uint32_t rq_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
+                                             uint32_t *kept, float *kd, int lane) {
+  uint32_t kc = 0;
+  for (uint32_t t = 0; t < sz && kc < mlim; t++) {
+    const float cd = unif(arr[t].d);
+    const uint32_t cid = uni(arr[t].id);
+    bool good = true;
+    if (kc > 0) {
+      for (uint32_t i = lane; i < dim; i += 64) qc[i] = vec[(size_t)cid * dim + i];
+      wave_sync();
+      rq_dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
+      wave_sync();
+      good = hs_ballot((uint32_t)lane < kc && kd[lane] < cd) == 0;
+    }
+    if (good) {
+      if (lane == 0) kept[kc] = cid;
+      kc++;
+    }
+    wave_sync();
+  }
+  return kc;
+}
+
+// phase A: bg_search_kernel's grid, flags and scratch; the LDS layout is rq_search_lds.
+template <int METRIC, bool ONCHIP>
+__global__ void __launch_bounds__(64) rq_search_kernel(BgDev g, uint32_t begin, uint32_t count, uint32_t ep, int32_t top, uint32_t scratch_ids,
+                                                       uint32_t *flagged, uint32_t *ctr, uint32_t *gscratch, size_t gstride) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  float *qv = reinterpret_cast<float *>(smem);
+  float *qc = qv + g.dpad;
+  Pair *topq = reinterpret_cast<Pair *>(qc + g.dpad);
+  uint32_t *nid = reinterpret_cast<uint32_t *>(topq + g.topcap);
+  float *nd = reinterpret_cast<float *>(nid + 64);
+  uint32_t *kept = reinterpret_cast<uint32_t *>(nd + 64);
+  float *kd = reinterpret_cast<float *>(kept + 64);
+  uint32_t *hash = reinterpret_cast<uint32_t *>(kd + 64);                      // ONCHIP: 2 * scratch_ids slots
+  const uint32_t hmask = 2 * scratch_ids - 1;
+  uint32_t *bitmap = gscratch + (size_t)blockIdx.x * gstride;                   // !ONCHIP
+  Pair *cand = ONCHIP ? reinterpret_cast<Pair *>(hash + 2 * (size_t)scratch_ids) : reinterpret_cast<Pair *>(bitmap + (((size_t)g.n + 31) / 32 + 1) / 2 * 2);
+  const uint32_t candcap = ONCHIP ? scratch_ids / 2 : g.n;
+  const int lane = threadIdx.x;
+  const uint32_t nrows = ONCHIP ? count : min(ctr[0], count);
+  for (uint32_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+    const uint32_t p = ONCHIP ? begin + r : flagged[r];
+    if (p < begin || p >= begin + count) continue;
+    const uint32_t lp = g.lev[p];
+    wave_sync();
+    for (uint32_t i = lane; i < g.dim; i += 64) qv[i] = g.vec[(size_t)p * g.dim + i];
+    uint32_t cur = ep;
+    wave_sync();
+    if ((int32_t)lp < top) {   // the greedy walk of the upper levels (hnsw.hpp:733-760)
+      if (lane == 0) nid[0] = cur;
+      wave_sync();
+      rq_dists<METRIC>(g.vec, g.dim, qv, nid, nd, 1, lane);
+      wave_sync();
+      float curdist = nd[0];
+      for (int32_t level = top; level > (int32_t)lp; level--) {
+        bool changed = true;
+        while (changed) {
+          changed = false;
+          const uint32_t *l = bg_list(g, cur, (uint32_t)level);
+          const uint32_t cnt = min(uni(l[0]) & 0xFFFFu, g.maxM);
+          wave_sync();
+          if ((uint32_t)lane < cnt) nid[lane] = min(l[1 + lane], begin - 1);
+          wave_sync();
+          rq_dists<METRIC>(g.vec, g.dim, qv, nid, nd, cnt, lane);
+          wave_sync();
+          for (uint32_t i = 0; i < cnt; i++) {   // every lane the same walk over LDS
+            const float d = nd[i];
+            if (d < curdist) { curdist = d; cur = nid[i]; changed = true; }
+          }
+          cur = uni(cur);
+          curdist = unif(curdist);
+          changed = hs_ballot(changed) != 0;
+        }
+      }
+    }
+    bool ok = true;
+    for (int32_t level = min((int32_t)lp, top); level >= 0 && ok; level--) {
+      // ---- search_base_layer (hnsw.hpp:827-905) -------------------------------------------------------------------------------
+      wave_sync();
+      if (ONCHIP) for (uint32_t i = lane; i <= hmask; i += 64) hash[i] = kBgPad;
+      else for (uint32_t i = lane; i < (begin + 31) / 32; i += 64) bitmap[i] = 0;
+      if (lane == 0) nid[0] = cur;
+      if (!ONCHIP) __syncthreads();   // (one wavefront per workgroup: orders the bitmap's plain stores before its atomics)
+      wave_sync();
+      rq_dists<METRIC>(g.vec, g.dim, qv, nid, nd, 1, lane);
+      wave_sync();
+      uint32_t topn = 1, candn = 1, nvis = 1;
+      float lower = nd[0];
+      if (lane == 0) {
+        topq[0] = Pair{lower, cur};
+        cand[0] = Pair{lower, cur};
+        if (ONCHIP) hash[(cur * 2654435761u) & hmask] = cur;
+        else bitmap[cur >> 5] = 1u << (cur & 31);
+      }
+      if (!ONCHIP) __syncthreads();
+      wave_sync();
+      while (candn > 0) {
+        Pair c{0.f, 0u};
+        if (lane == 0) c = cand[0];   // (the lane that maintains the heap reads it: program order, whichever memory holds it)
+        const uint32_t node = uni(c.id);
+        if (unif(c.d) > lower && topn == g.efc) break;
+        if (lane == 0) pop_heap(cand, (long)candn, RqGreater());
+        candn--;
+        const uint32_t lim = level ? g.maxM : g.maxM0;
+        const uint32_t *l = bg_list(g, node, (uint32_t)level);
+        const uint32_t cnt = min(uni(l[0]) & 0xFFFFu, lim);
+        const uint32_t id = (uint32_t)lane < cnt ? l[1 + lane] : kBgPad;
+        bool isnew = false;
+        if (id < begin) {   // (every id of the graph so far is; the test keeps a damaged list inside the arrays)
+          if (ONCHIP) {
+            uint32_t slot = (id * 2654435761u) & hmask;
+            while (true) {   // at most scratch_ids + 64 <= 2 * scratch_ids distinct ids ever reach the table: every probe sequence
+              const uint32_t old = lds_cas(&hash[slot], kBgPad, id);   // meets an empty slot or its own id
+              if (old == kBgPad) { isnew = true; break; }
+              if (old == id) break;
+              slot = (slot + 1) & hmask;
+            }
+          } else {
+            const uint32_t bit = 1u << (id & 31);
+            isnew = (atomicOr(&bitmap[id >> 5], bit) & bit) == 0;
+          }
+        }
+        const unsigned long long nm = hs_ballot(isnew);
+        const uint32_t nnew = __popcll(nm);
+        wave_sync();
+        if (isnew) nid[__popcll(nm & ((1ull << lane) - 1ull))] = id;   // adjacency order
+        nvis += nnew;
+        if (ONCHIP && nvis > scratch_ids) { ok = false; break; }
+        wave_sync();
+        rq_dists<METRIC>(g.vec, g.dim, qv, nid, nd, nnew, lane);
+        wave_sync();
+        uint32_t ovf = 0;
+        if (lane == 0) {
+          for (uint32_t j = 0; j < nnew; j++) {
+            const float d = nd[j];
+            if (topn < g.efc || lower > d) {
+              if (candn >= candcap) { ovf = 1; break; }
+              cand[candn++] = Pair{d, nid[j]};
+              push_heap(cand, (long)candn, RqGreater());
+              topq[topn++] = Pair{d, nid[j]};
+              push_heap(topq, (long)topn, RqLess());
+              if (topn > g.efc) { pop_heap(topq, (long)topn, RqLess()); topn--; }
+              lower = topq[0].d;
+            }
+          }
+        }
+        topn = uni(topn); candn = uni(candn); lower = unif(lower); ovf = uni(ovf);
+        wave_sync();
+        if (ovf) { ok = false; break; }
+      }
+      if (!ok) break;
+      // ---- get_neighbors_by_heuristic2(top, M) (:1016-1054: nothing below M entries), then the pop order of :917-922 -----------------
+      uint32_t N = 64;
+      while (N < topn) N <<= 1;
+      for (uint32_t i = topn + lane; i < N; i += 64) topq[i] = Pair{0.f, kBgPad};
+      wave_sync();
+      rq_sort_asc(topq, N, lane);
+      uint32_t kc = topn;
+      if (topn < g.M) {
+        if ((uint32_t)lane < kc) kept[lane] = topq[lane].id;
+      } else {
+        kc = rq_prune<METRIC>(g.vec, g.dim, topq, topn, g.M, qc, kept, kd, lane);
+      }
+      wave_sync();
+      uint32_t *own = bg_list(g, p, (uint32_t)level);
+      if ((uint32_t)lane < kc) own[1 + lane] = kept[kc - 1 - lane];   // descending pair order: the max-heap's pops
+      if (lane == 0) own[0] = kc;
+      cur = uni(kept[0]);   // sel.back()
+    }
+    if (!ok && ONCHIP && lane == 0) {
+      flagged[atomicAdd(&ctr[0], 1u)] = p;
+      atomicAdd(&ctr[1], 1u);
+    }
+  }
+}
+
+// phase B: bg_link_kernel's tasks and segments; a full level-0 list at M = 32 plus the new id is 65 candidates, so the candidate
+// arrays hold 128 entries, the rank sort takes two entries per lane and the keep loop keeps at most 64, one lane per kept entry.
+template <int METRIC>
+__global__ void __launch_bounds__(64) rq_link_kernel(BgDev g, uint32_t begin, uint32_t nact, const uint32_t *up_node, const uint32_t *up_level,
+                                                     uint32_t *rcnt, const uint32_t *roff, uint32_t *rcur, uint32_t *rev, uint32_t rev_cap) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  float *qv = reinterpret_cast<float *>(smem);
+  float *qc = qv + g.dpad;
+  Pair *arr = reinterpret_cast<Pair *>(qc + g.dpad);
+  uint32_t *nid = reinterpret_cast<uint32_t *>(arr + 128);
+  float *nd = reinterpret_cast<float *>(nid + 128);
+  uint32_t *kept = reinterpret_cast<uint32_t *>(nd + 128);
+  float *kd = reinterpret_cast<float *>(kept + 64);
+  uint32_t *curl = reinterpret_cast<uint32_t *>(kd + 64);
+  uint32_t *inc = curl + 64;
+  const int lane = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < nact; i += gridDim.x) {
+    const uint32_t task = bg_active(i, begin, g.n);
+    const uint32_t k = uni(rcnt[task]);
+    if (k == 0) continue;
+    const uint32_t off = uni(roff[task]);
+    if (off >= rev_cap || k > rev_cap - off) continue;   // (never: the host sizes rev for every edge of the batch)
+    const uint32_t u = task < g.n ? task : up_node[task - g.n], level = task < g.n ? 0u : up_level[task - g.n];
+    const uint32_t lim = level ? g.maxM : g.maxM0;   // <= 64
+    uint32_t *seg = rev + off;
+    wave_sync();
+    if (k <= 64) {   // the incoming ids in ascending order: distinct, so the rank of each is its place
+      const uint32_t mine = (uint32_t)lane < k ? seg[lane] : kBgPad;
+      if ((uint32_t)lane < k) inc[lane] = mine;
+      wave_sync();
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < k; j++) rank += inc[j] < mine ? 1u : 0u;
+      wave_sync();
+      if ((uint32_t)lane < k) inc[rank] = mine;
+    } else {   // bitonic network whose exchanges all put the smaller id first: the places beyond k count as +inf and never move
+      uint32_t N = 128;
+      while (N < k) N <<= 1;
+      for (uint32_t kk = 2; kk <= N; kk <<= 1) {
+        for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+          const bool flip = j == (kk >> 1);
+          __syncthreads();   // (one wavefront per workgroup; uniform: orders the segment's stores before the next step's loads)
+          for (uint32_t x = lane; x < N; x += 64) {
+            const uint32_t y = flip ? (x ^ (kk - 1)) : (x ^ j);
+            if (y > x && y < k) {
+              const uint32_t a = seg[x], b = seg[y];
+              if (a > b) { seg[x] = b; seg[y] = a; }
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+    uint32_t *lst = bg_list(g, u, level);
+    uint32_t cnt = min(uni(lst[0]) & 0xFFFFu, lim);
+    if ((uint32_t)lane < lim) curl[lane] = lst[1 + lane];
+    bool have_row = false;
+    wave_sync();
+    for (uint32_t e = 0; e < k; e++) {
+      const uint32_t p = k <= 64 ? inc[e] : uni(seg[e]);
+      if (hs_ballot((uint32_t)lane < cnt && curl[lane] == p) != 0) continue;   // the list names p already (hnsw.hpp:973-980)
+      if (cnt < lim) {
+        if (lane == 0) curl[cnt] = p;
+        cnt++;
+        wave_sync();
+        continue;
+      }
+      if (!have_row) {
+        for (uint32_t c = lane; c < g.dim; c += 64) qv[c] = g.vec[(size_t)u * g.dim + c];
+        have_row = true;
+      }
+      const uint32_t sz = cnt + 1;   // <= 65: {p} + the full list
+      if (lane == 0) nid[0] = p;
+      if ((uint32_t)lane < cnt) nid[1 + lane] = curl[lane];
+      wave_sync();
+      rq_dists<METRIC>(g.vec, g.dim, qv, nid, nd, sz, lane);
+      wave_sync();
+      for (uint32_t x = lane; x < sz; x += 64) {   // ascending pair order by rank; equal pairs (a damaged list) by their place
+        const Pair mine{nd[x], nid[x]};
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < sz; j++) {
+          const Pair o{nd[j], nid[j]};
+          rank += (rq_less(o, mine) || (!rq_less(mine, o) && j < x)) ? 1u : 0u;
+        }
+        arr[rank] = mine;
+      }
+      wave_sync();
+      const uint32_t kc = rq_prune<METRIC>(g.vec, g.dim, arr, sz, lim, qc, kept, kd, lane);
+      wave_sync();
+      if ((uint32_t)lane < kc) curl[lane] = kept[kc - 1 - lane];   // pop order; what it does not overwrite stays
+      cnt = kc;
+      wave_sync();
+    }
+    if ((uint32_t)lane < lim) lst[1 + lane] = curl[lane];
+    if (lane == 0) { lst[0] = cnt; rcnt[task] = 0; rcur[task] = 0; }
+  }
+}
+
+// hs_debug_rq_raw_dist: pair i is a[i] against b[i]; the row is measured five times in one call of rq_dists, so that pairs land in
+// every sixteen-lane group and in the second pass.
+template <int METRIC>
+__global__ void __launch_bounds__(64) rq_dist_debug_kernel(const float *a, const float *b, uint32_t n_pairs, uint32_t dim, uint32_t dpad, float *out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  float *qv = reinterpret_cast<float *>(smem);
+  uint32_t *nid = reinterpret_cast<uint32_t *>(qv + dpad);
+  float *nd = reinterpret_cast<float *>(nid + 8);
+  const int lane = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < n_pairs; i += gridDim.x) {
+    wave_sync();
+    for (uint32_t c = lane; c < dim; c += 64) qv[c] = a[(size_t)i * dim + c];
+    if (lane < 5) nid[lane] = i;
+    wave_sync();
+    rq_dists<METRIC>(b, dim, qv, nid, nd, 5, lane);
+    wave_sync();
+    if (lane == 0) out[i] = nd[i % 5u];
+  }
+}
+
 // ---- the add into a resident index: which lists of the old nodes changed, and only those come back ------------------------
 // An old task is a list the graph held before the call: the level-0 lists of the n0 old nodes, then their nup0 upper slots.
 struct BgMarks {
@@ -446,6 +774,10 @@ static size_t bg_search_lds(uint32_t dpad, uint32_t efc, uint32_t scratch_ids) {
   return (size_t)dpad * 8 + (size_t)bg_topcap(efc) * 8 + 5 * 256 + (size_t)scratch_ids * 12;
 }
 static size_t bg_link_lds(uint32_t dpad) { return (size_t)dpad * 8 + 64 * 8 + 7 * 256; }
+static size_t rq_search_lds(uint32_t dpad, uint32_t efc, uint32_t scratch_ids) {
+  return (size_t)dpad * 8 + (size_t)bg_topcap(efc) * 8 + 4 * 256 + (size_t)scratch_ids * 12;
+}
+static size_t rq_link_lds(uint32_t dpad) { return (size_t)dpad * 8 + 128 * 8 + 2 * 512 + 4 * 256; }
 
 bool gpu_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratch_ids) {
   if (scratch_ids == 0) scratch_ids = kBgScratchIds;
@@ -455,35 +787,48 @@ bool gpu_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratc
   return bg_search_lds(dpad, std::max(efc, M), scratch_ids) <= kBgLdsLimit && bg_link_lds(dpad) <= kBgLdsLimit;
 }
 
+bool gpu_rq_build_supported(uint32_t dim, uint32_t M, uint32_t efc, uint32_t scratch_ids) {
+  if (scratch_ids == 0) scratch_ids = kBgScratchIds;
+  if (M < 2 || M > kRqMaxM || std::max(efc, M) > kBgMaxEfc || dim == 0) return false;
+  if (scratch_ids < 64 || (scratch_ids & (scratch_ids - 1)) != 0 || scratch_ids > 8192) return false;
+  const uint32_t dpad = (dim + 3u) & ~3u;
+  return rq_search_lds(dpad, std::max(efc, M), scratch_ids) <= kBgLdsLimit && rq_link_lds(dpad) <= kBgLdsLimit;
+}
+
 #define BG_TRY(expr)                               \
   do {                                             \
     hipError_t _e = (expr);                        \
     if (_e != hipSuccess) { err = _e; goto done; } \
   } while (0)
 
-template <int METRIC>
+template <int METRIC, bool RQ = false>
 static hipError_t bg_run(const std::vector<BatchStep> &steps, const BgDev &g, const std::vector<uint32_t> &upb, uint32_t scratch_ids, uint32_t *d_flagged,
                          uint32_t *d_ctr, uint32_t *d_scratch, size_t gstride, uint32_t *d_rcnt, uint32_t *d_roff, uint32_t *d_rcur, uint32_t *d_rev,
                          uint32_t rev_cap, const uint32_t *d_upnode, const uint32_t *d_uplevel, hipStream_t st, const BgMarks *marks = nullptr) {
-  const size_t lds_a = bg_search_lds(g.dpad, g.efc, scratch_ids), lds_r = bg_search_lds(g.dpad, g.efc, 0), lds_l = bg_link_lds(g.dpad);
+  // the flavour's three kernels (the rq ones have the vanilla signatures)
+  const auto search_chip = RQ ? rq_search_kernel<METRIC, true> : bg_search_kernel<METRIC, true>;
+  const auto search_mem = RQ ? rq_search_kernel<METRIC, false> : bg_search_kernel<METRIC, false>;
+  const auto link = RQ ? rq_link_kernel<METRIC> : bg_link_kernel<METRIC>;
+  const size_t lds_a = RQ ? rq_search_lds(g.dpad, g.efc, scratch_ids) : bg_search_lds(g.dpad, g.efc, scratch_ids);
+  const size_t lds_r = RQ ? rq_search_lds(g.dpad, g.efc, 0) : bg_search_lds(g.dpad, g.efc, 0), lds_l = RQ ? rq_link_lds(g.dpad) : bg_link_lds(g.dpad);
   hipError_t e;
-  if (lds_a > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_search_kernel<METRIC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
-  if (lds_r > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_search_kernel<METRIC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r)) != hipSuccess) return e;
-  if (lds_l > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(bg_link_kernel<METRIC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l)) != hipSuccess) return e;
+  if (lds_a > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(search_chip), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
+  if (lds_r > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(search_mem), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r)) != hipSuccess) return e;
+  if (lds_l > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(link), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l)) != hipSuccess) return e;
   for (const BatchStep &s : steps) {
     if ((int32_t)s.ep == -1) continue;   // the first row: an empty list, as the zeroed arrays have it
     const uint32_t nact = s.begin + upb[s.begin];
     if ((e = hipMemsetAsync(d_ctr, 0, 4, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL((bg_search_kernel<METRIC, true>), dim3(s.size), dim3(64), lds_a, st, g, s.begin, s.size, s.ep, s.top, scratch_ids, d_flagged, d_ctr,
+    hipLaunchKernelGGL(search_chip, dim3(s.size), dim3(64), lds_a, st, g, s.begin, s.size, s.ep, s.top, scratch_ids, d_flagged, d_ctr,
                        (uint32_t *)nullptr, (size_t)0);
-    hipLaunchKernelGGL((bg_search_kernel<METRIC, false>), dim3(std::min(kBgRerunGrid, s.size)), dim3(64), lds_r, st, g, s.begin, s.size, s.ep, s.top, 0u,
+    hipLaunchKernelGGL(search_mem, dim3(std::min(kBgRerunGrid, s.size)), dim3(64), lds_r, st, g, s.begin, s.size, s.ep, s.top, 0u,
                        d_flagged, d_ctr, d_scratch, gstride);
     hipLaunchKernelGGL((bg_rev_kernel<false>), dim3((s.size + 3) / 4), dim3(256), 0, st, g, s.begin, s.size, s.top, d_rcnt, d_roff, d_rcur, d_rev, rev_cap);
     hipLaunchKernelGGL(bg_scan_kernel, dim3(1), dim3(256), 0, st, d_rcnt, d_roff, s.begin, g.n, nact);
     hipLaunchKernelGGL((bg_rev_kernel<true>), dim3((s.size + 3) / 4), dim3(256), 0, st, g, s.begin, s.size, s.top, d_rcnt, d_roff, d_rcur, d_rev, rev_cap);
     if (marks)   // (before the link kernel, which resets the counts)
       hipLaunchKernelGGL(bga_mark_kernel, dim3(std::min((nact + 255u) / 256u, 4096u)), dim3(256), 0, st, d_rcnt, s.begin, g.n, nact, *marks);
-    hipLaunchKernelGGL((bg_link_kernel<METRIC>), dim3(std::min(nact, 8192u)), dim3(64), lds_l, st, g, s.begin, nact, d_upnode, d_uplevel, d_rcnt, d_roff,
+    hipLaunchKernelGGL(link, dim3(std::min(nact, 8192u)), dim3(64), lds_l, st, g, s.begin, nact, d_upnode, d_uplevel, d_rcnt, d_roff,
                        d_rcur, d_rev, rev_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
@@ -495,7 +840,9 @@ hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint
   hipError_t err = hipSuccess;
   const uint32_t n = in.n, scratch_ids = in.scratch_ids ? in.scratch_ids : kBgScratchIds;
   flagged_rows = 0;
-  if (!gpu_build_supported(in.dim, in.M, in.efc, scratch_ids) || n == 0 || n > 0x7FFFFFF0u) return hipErrorInvalidValue;
+  if (!(in.rq ? gpu_rq_build_supported(in.dim, in.M, in.efc, scratch_ids) : gpu_build_supported(in.dim, in.M, in.efc, scratch_ids)) || n == 0 ||
+      n > 0x7FFFFFF0u)
+    return hipErrorInvalidValue;
   BgDev g{};
   g.n = n; g.dim = in.dim; g.dpad = (in.dim + 3u) & ~3u; g.M = in.M; g.maxM = in.maxM; g.maxM0 = in.maxM0;
   g.s0 = in.maxM0 + 1; g.su = in.maxM + 1; g.efc = in.efc; g.topcap = bg_topcap(in.efc);
@@ -554,7 +901,11 @@ hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint
   g.vec = d_vec; g.l0 = d_l0; g.lu = d_lu; g.upb = d_upb; g.lev = d_lev;
   BG_TRY(hipEventCreate(&e0)); BG_TRY(hipEventCreate(&e1));
   BG_TRY(hipEventRecord(e0, nullptr));
-  if (in.metric == METRIC_L2)
+  if (in.rq && in.metric == METRIC_L2)
+    BG_TRY((bg_run<METRIC_L2, true>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr)));
+  else if (in.rq)
+    BG_TRY((bg_run<METRIC_IP, true>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr)));
+  else if (in.metric == METRIC_L2)
     BG_TRY(bg_run<METRIC_L2>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
   else
     BG_TRY(bg_run<METRIC_IP>(*in.steps, g, upb, scratch_ids, d_flagged, d_ctr, d_scratch, gstride, d_rcnt, d_roff, d_rcur, d_rev, (uint32_t)rev_cap, d_upnode, d_uplevel, nullptr));
@@ -573,6 +924,32 @@ done:
     if (p) (void)hipFree(p);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
+  return err;
+}
+
+// rq_dists over n_pairs pairs of host rows on `device` (hs_debug_rq_raw_dist)
+hipError_t gpu_rq_raw_dist(const float *a, const float *b, size_t n_pairs, uint32_t dim, int metric, int device, float *out) {
+  hipError_t err = hipSuccess;
+  const uint32_t dpad = (dim + 3u) & ~3u;
+  const size_t lds = (size_t)dpad * 4 + 64, bytes = n_pairs * dim * 4;
+  if (dim == 0 || lds > 64 * 1024 || n_pairs > 0x7FFFFFF0u) return hipErrorInvalidValue;
+  if (n_pairs == 0) return hipSuccess;
+  float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
+  BG_TRY(hipSetDevice(device));
+  BG_TRY(hipMalloc((void **)&d_a, bytes));
+  BG_TRY(hipMalloc((void **)&d_b, bytes));
+  BG_TRY(hipMalloc((void **)&d_o, n_pairs * 4));
+  BG_TRY(hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice));
+  BG_TRY(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice));
+  if (metric == METRIC_L2)
+    hipLaunchKernelGGL(rq_dist_debug_kernel<METRIC_L2>, dim3((uint32_t)std::min<size_t>(n_pairs, 4096)), dim3(64), lds, nullptr, d_a, d_b, (uint32_t)n_pairs, dim, dpad, d_o);
+  else
+    hipLaunchKernelGGL(rq_dist_debug_kernel<METRIC_IP>, dim3((uint32_t)std::min<size_t>(n_pairs, 4096)), dim3(64), lds, nullptr, d_a, d_b, (uint32_t)n_pairs, dim, dpad, d_o);
+  BG_TRY(hipGetLastError());
+  BG_TRY(hipMemcpy(out, d_o, n_pairs * 4, hipMemcpyDeviceToHost));
+done:
+  for (void *p : {(void *)d_a, (void *)d_b, (void *)d_o})
+    if (p) (void)hipFree(p);
   return err;
 }
 

@@ -7,6 +7,7 @@
 #include "bf_engine.hpp"
 #include "build_engine.hpp"
 #include "exact_engine.hpp"
+#include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
 #include "rabitq_host.hpp"
@@ -248,6 +249,68 @@ hs_status hs_build_rabitq_hnsw(const float *base, size_t n, size_t dim, int metr
   } catch (std::exception &e) {
     return from_exception(e);
   }
+  return HS_OK;
+}
+
+// The same graph in the batched order: on a device the rq kernels of build_gpu.hip, otherwise -- device -1, or a
+// shape outside the device envelope -- the host twin (host_rq_batch_build.hpp); the same bytes either way.
+hs_status hs_build_rabitq_hnsw_batched(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
+                                       const hs_batch_build_opts *opts, const char *out_path, hs_batch_build_stats *stats) {
+  if (!base || !out_path || n == 0 || dim == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (M < 2) return fail(HS_ERR_INVALID, "M must be >= 2");   // mult = 1 / ln M
+  if (n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "too many rows");
+  if (batch_opts_ok(opts) != HS_OK) return HS_ERR_INVALID;
+  if (opts->device >= 0 && hs_device_count() <= opts->device) return fail(HS_ERR_DEVICE, "no HIP device");
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_batch_build_stats st{};
+  try {
+    RqGraph g;
+    const int threads = std::max(1, (int)opts->threads);
+    if (opts->device >= 0 && gpu_rq_build_supported((uint32_t)dim, (uint32_t)std::min<size_t>(M, 10000), (uint32_t)std::min<size_t>(std::max(ef_construction, M), 0xFFFFFFFFu),
+                                                    (uint32_t)opts->scratch_ids)) {
+      rq_init(g, base, n, dim, (Metric)metric, M, ef_construction);
+      const std::vector<int> lv = draw_levels(n, g.mult, seed);
+      const std::vector<BatchStep> steps = batch_schedule(lv.data(), n, opts->grow_div, opts->batch_max);
+      GpuBuildInput in;
+      in.base = base; in.n = (uint32_t)n; in.dim = (uint32_t)dim; in.metric = metric;
+      in.M = (uint32_t)g.M; in.maxM = (uint32_t)g.maxM; in.maxM0 = (uint32_t)g.maxM0; in.efc = (uint32_t)g.efC;
+      in.levels = lv.data(); in.steps = &steps; in.scratch_ids = (uint32_t)opts->scratch_ids; in.rq = true;
+      std::vector<uint32_t> l0, lu, upb;
+      uint64_t flagged = 0;
+      const hipError_t e = gpu_batch_build(in, opts->device, l0, lu, upb, flagged, &st.kernel_ms);
+      if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("batched build: ") + hipGetErrorString(e));
+      image_from_lists(g, base, nullptr, lv, steps, l0, lu, upb, threads);
+      st.used_gpu = 1; st.batches = steps.size(); st.flagged_rows = flagged;
+    } else {
+      BatchBuildStats bs;
+      rq_batch_build_host(g, base, n, dim, (Metric)metric, M, ef_construction, seed, threads, opts->grow_div, opts->batch_max, &bs);
+      st.batches = bs.batches;
+    }
+    g.save(out_path);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (stats) *stats = st;
+  return HS_OK;
+}
+
+// rabitq_raw_dist over n_pairs pairs of rows: the host text (device -1), or the wavefront recipe of the build kernels on a device.
+hs_status hs_debug_rq_raw_dist(const float *a, const float *b, size_t n_pairs, size_t dim, int metric, int device, float *out) {
+  if (!a || !b || !out || dim == 0) return fail(HS_ERR_INVALID, "bad argument");
+  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host recipe) or a HIP device");
+  if (device < 0) {
+    for (size_t i = 0; i < n_pairs; i++) out[i] = rabitq_raw_dist((Metric)metric, a + i * dim, b + i * dim, dim);
+    return HS_OK;
+  }
+  if (dim > 8192) return fail(HS_ERR_UNSUPPORTED, "hs_debug_rq_raw_dist on a device supports dim <= 8192");
+  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device");
+  const hipError_t e = gpu_rq_raw_dist(a, b, n_pairs, (uint32_t)dim, metric, device, out);
+  if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("rq raw dist: ") + hipGetErrorString(e));
   return HS_OK;
 }
 

@@ -1,51 +1,10 @@
-// host_rq_graph.hpp -- the host side of HNSW-SlimQ's graph: rabitqlib's raw distance, the base graph its HNSW builds (RqGraph)
+// host_rq_graph.hpp -- the host side of HNSW-SlimQ's graph: rabitqlib's raw distance (rq_dist.hpp), the base graph its HNSW builds (RqGraph)
 // and HierarchicalNSWSlimQ::convertFromHNSW's graph passes.  Pinned edge for edge by tests/test_slimq_graph_cpu.py.
 #pragma once
 #include "host_graph.hpp"
+#include "rq_dist.hpp"
 
 namespace hs {
-
-// raw_dist_func_ = euclidean_sqr / dot_product_dis (rabitqlib/utils/space.hpp:226-240): `(v0 - v1).dot(v0 - v1)` and
-// `1 - v0.dot(v1)` through the vendored Eigen's inner product (Eigen/src/Core/InnerProduct.h:113-159) with 16-float packets
-// (the AVX-512 build the parity flags pin): four packet accumulators, the first four packets multiplied, every later one
-// fused-multiply-added (pmadd = _mm512_fmadd_ps), folded 2+=3, 1+=2, 0+=1, then predux = halves 8, 4, (0+2, 1+3), (0+1)
-// (arch/AVX512/PacketMath.h:1456-1461, AVX :1954, SSE :1852-1853); the < 16 tail is a scalar fused chain.  Unlike the Eigen
-// reductions on the SEARCH path this one does not depend on pointer alignment: the operands are expressions.
-inline float rabitq_raw_dist(Metric metric, const float *a, const float *b, size_t d) {
-  const bool l2 = metric == METRIC_L2;
-  auto X = [&](size_t k) { return l2 ? a[k] - b[k] : a[k]; };
-  auto Y = [&](size_t k) { return l2 ? a[k] - b[k] : b[k]; };
-  float res;
-  if (d < 16) {
-    if (d == 0) return l2 ? 0.f : 1.f;
-    res = X(0) * Y(0);
-    for (size_t k = 1; k < d; k++) res = __builtin_fmaf(X(k), Y(k), res);
-  } else {
-    const size_t packet_end = d / 16 * 16, quad_end = d / 64 * 64, np = d / 16, nrem = (packet_end - quad_end) / 16;
-    float acc[4][16];
-    for (size_t p = 0; p < std::min<size_t>(np, 4); p++)
-      for (size_t j = 0; j < 16; j++) acc[p][j] = X(p * 16 + j) * Y(p * 16 + j);
-    if (np >= 4) {
-      for (size_t k = 64; k < quad_end; k += 64)
-        for (size_t p = 0; p < 4; p++)
-          for (size_t j = 0; j < 16; j++) acc[p][j] = __builtin_fmaf(X(k + p * 16 + j), Y(k + p * 16 + j), acc[p][j]);
-      for (size_t p = 0; p < nrem; p++)
-        for (size_t j = 0; j < 16; j++) acc[p][j] = __builtin_fmaf(X(quad_end + p * 16 + j), Y(quad_end + p * 16 + j), acc[p][j]);
-      for (size_t j = 0; j < 16; j++) acc[2][j] = acc[2][j] + acc[3][j];
-    }
-    if (np >= 3)
-      for (size_t j = 0; j < 16; j++) acc[1][j] = acc[1][j] + acc[2][j];
-    if (np >= 2)
-      for (size_t j = 0; j < 16; j++) acc[0][j] = acc[0][j] + acc[1][j];
-    float t8[8], t4[4];
-    for (size_t j = 0; j < 8; j++) t8[j] = acc[0][j] + acc[0][j + 8];
-    for (size_t j = 0; j < 4; j++) t4[j] = t8[j] + t8[j + 4];
-    const float u0 = t4[0] + t4[2], u1 = t4[1] + t4[3];
-    res = u0 + u1;
-    for (size_t k = packet_end; k < d; k++) res = __builtin_fmaf(X(k), Y(k), res);
-  }
-  return l2 ? res : 1 - res;
-}
 
 // The base graph HNSW-SlimQ is converted from: rabitqlib::hnsw::HierarchicalNSW::construct
 // (third_party/rabitqlib/index/hnsw/hnsw.hpp:667-704, add_point :706-825, search_base_layer :827-905,

@@ -19,14 +19,18 @@
 // unmarkDelete, resizeIndex, getDataByLabel, saveIndex (hnswalg.h:689-717, 896-1272, 1248-1376, 748-779).
 // HierarchicalNSWSlim<float> is also the patch server's index: convertFromHNSWWithDiff from a resident
 // HierarchicalNSW<float> and genPatch (hnswalg_slim.h:1110-1751), feeding patchFromStream clients.
+// HierarchicalNSWSlimQ<float> has the strategy's build side too: rabitqlib::hnsw::HierarchicalNSW's constructor,
+// construct and save (third_party/rabitqlib/index/hnsw/hnsw.hpp:427-500, 667-704) and convertFromHNSW(rabitqlib's index).
 // Not provided: updateNeighborProbability other than 1.0, addPoint on Slim / SlimQ indexes, stop conditions.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <fstream>
 #include <queue>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <unordered_set>
 #include <utility>
 #include <vector>
@@ -730,20 +734,133 @@ class BruteforceSearch<float> : public AlgorithmInterface<float> {
   }
 };
 
+}  // namespace hnswlib
+
+// rabitqlib::hnsw::HierarchicalNSW (third_party/rabitqlib/index/hnsw/hnsw.hpp) as the reference's SlimQ strategy uses it
+// (include/strategy/hnsw_slimq_strategy.h:106-127): the constructor, construct() and save().  construct() builds the EDGES, from
+// the raw rows, and keeps the centroid and cluster arguments for HierarchicalNSWSlimQ::convertFromHNSW, which writes the RaBitQ
+// records; total_bits and faster_quant are accepted and not used.  save() writes the graph in hnswlib's saveIndex layout, the file
+// the converters read.  setBuildOnDevice(device, batch_max) (no counterpart in the reference) moves construct() to the batched
+// build on that HIP device (hs_build_rabitq_hnsw_batched); without it construct() is hs_build_rabitq_hnsw on
+// num_threads host threads (0: all of them; 1: the reference's serial construct(), edge for edge).
+namespace rabitqlib {
+enum MetricType : std::uint8_t { METRIC_L2, METRIC_IP };
+using PID = uint32_t;
+namespace hnsw {
+class HierarchicalNSW {
+  size_t n_, dim_, M_, efc_, seed_;
+  int metric_;
+  int build_device_ = -1;
+  size_t build_batch_max_ = 0;
+  hs_batch_build_stats build_stats_{};
+  std::string tmp_path_;                // the graph construct() built
+  std::vector<float> centroids_;
+  std::vector<PID> cluster_ids_;
+  size_t num_clusters_ = 0;
+
+ public:
+  HierarchicalNSW(size_t num_points, size_t dim, size_t /*total_bits*/, size_t M, size_t ef_construction, size_t random_seed = 100,
+                  MetricType metric_type = METRIC_L2)
+      : n_(num_points), dim_(dim), M_(M), efc_(ef_construction), seed_(random_seed), metric_(metric_type == METRIC_IP ? HS_METRIC_IP : HS_METRIC_L2) {}
+  HierarchicalNSW(const HierarchicalNSW &) = delete;
+  HierarchicalNSW &operator=(const HierarchicalNSW &) = delete;
+  ~HierarchicalNSW() { if (!tmp_path_.empty()) unlink(tmp_path_.c_str()); }
+  void setBuildOnDevice(int device, size_t batch_max = 0) { build_device_ = device < 0 ? -1 : device; build_batch_max_ = batch_max; }
+  const hs_batch_build_stats &buildStats() const { return build_stats_; }   // of the last construct() that went through setBuildOnDevice
+  void construct(size_t num_clusters, const float *centroids, size_t num_points, const float *data, const PID *cluster_ids, size_t num_threads = 0,
+                 bool /*faster_quant*/ = false) {
+    if (num_points != n_) throw std::runtime_error("hnswlib_amd: construct() with another number of points than the constructor's");
+    if (!data) throw std::runtime_error("hnswlib_amd: construct() without rows");
+    char tmpl[] = "/tmp/hnswlib_amd_rq_XXXXXX";
+    const int fd = mkstemp(tmpl);
+    if (fd < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
+    close(fd);
+    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
+    tmp_path_ = tmpl;
+    const int threads = num_threads ? (int)num_threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    build_stats_ = hs_batch_build_stats{};
+    if (build_device_ >= 0) {
+      hs_batch_build_opts o{};
+      o.device = build_device_;
+      o.threads = threads;
+      o.batch_max = build_batch_max_;
+      hnswlib::detail::check(hs_build_rabitq_hnsw_batched(data, n_, dim_, metric_, M_, efc_, seed_, &o, tmpl, &build_stats_));
+    } else {
+      hnswlib::detail::check(hs_build_rabitq_hnsw(data, n_, dim_, metric_, M_, efc_, seed_, threads, tmpl));
+    }
+    num_clusters_ = num_clusters;
+    centroids_.assign(centroids, centroids + (centroids ? num_clusters * dim_ : 0));
+    cluster_ids_.assign(cluster_ids, cluster_ids + (cluster_ids ? n_ : 0));
+  }
+  // save (hnsw.hpp:506-560 writes rabitqlib's own layout; here: the saveIndex layout every converter of this library reads)
+  void save(const char *path) const {
+    if (tmp_path_.empty()) throw std::runtime_error("hnswlib_amd: save() before construct()");
+    std::ifstream in(tmp_path_, std::ios::binary);
+    std::ofstream out(path, std::ios::binary);
+    out << in.rdbuf();
+    if (!in || !out) throw std::runtime_error("Cannot open file");
+  }
+  // what convertFromHNSW reads
+  const std::string &graphPath() const { return tmp_path_; }
+  size_t dim() const { return dim_; }
+  int metric() const { return metric_; }
+  size_t numClusters() const { return num_clusters_; }
+  const float *centroids() const { return centroids_.empty() ? nullptr : centroids_.data(); }
+  const PID *clusterIds() const { return cluster_ids_.empty() ? nullptr : cluster_ids_.data(); }
+};
+}  // namespace hnsw
+}  // namespace rabitqlib
+
+namespace hnswlib {
+
 // HierarchicalNSWSlimQ (hnswalg_slimq.h): the RaBitQ-quantised variant.  Same call sequence as the reference's
-// strategy (include/strategy/hnsw_slimq_strategy.h:72,142-156): loadIndex, setDataset, setEf, searchKnn(q, K, result).
+// strategy (include/strategy/hnsw_slimq_strategy.h:72,142-156): loadIndex, setDataset, setEf, searchKnn(q, K, result); and its
+// build side (:53-57, 106-141): the constructor with the pruning parameters, convertFromHNSW(rabitqlib's index), saveIndex.
 template <typename dist_t>
 class HierarchicalNSWSlimQ;
 
 template <>
 class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public detail::DeviceIndex {
+  SpaceInterface<float> *space_ = nullptr;
+  int thr_ = 0;                          // hnswalg_slimq.h's constructor defaults
+  float p0_ = 0.02f, p_ = 0.02f;
+  size_t M0h_ = 32, m0l_ = 8, Mh_ = 16, ml_ = 4;
+  std::string tmp_path_;                 // the SlimQ file convertFromHNSW wrote
+
  public:
-  explicit HierarchicalNSWSlimQ(SpaceInterface<float> *) {}
+  explicit HierarchicalNSWSlimQ(SpaceInterface<float> *s) : space_(s) {}
+  HierarchicalNSWSlimQ(SpaceInterface<float> *s, size_t /*max_elements*/, size_t /*M*/ = 16, size_t /*ef_construction*/ = 200, int threshold_level = 0,
+                       float top_degree_percent0 = 0.02f, float top_degree_percent = 0.02f, size_t top_degree_M0 = 32, size_t low_degree_m0 = 8,
+                       size_t top_degree_M = 16, size_t low_degree_m = 4)
+      : space_(s), thr_(threshold_level), p0_(top_degree_percent0), p_(top_degree_percent), M0h_(top_degree_M0), m0l_(low_degree_m0),
+        Mh_(top_degree_M), ml_(low_degree_m) {}
+  ~HierarchicalNSWSlimQ() { if (!tmp_path_.empty()) unlink(tmp_path_.c_str()); }
+  // convertFromHNSW(hnsw) (hnswalg_slimq.h:1471-1790) on the graph construct() built: the graph passes (hs_convert_slimq_graph), the
+  // RaBitQ records with the centroids and cluster ids construct() was given (hs_convert_slimq), then the result is loaded.
+  void convertFromHNSW(rabitqlib::hnsw::HierarchicalNSW *hnsw, int threads = 8, uint64_t flip_seed = 1) {
+    if (!hnsw || hnsw->graphPath().empty()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs a constructed rabitqlib index");
+    if (!space_) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs the space the index was constructed with");
+    if (!hnsw->centroids()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs the centroids construct() was given");
+    char slim[] = "/tmp/hnswlib_amd_rqslim_XXXXXX", slimq[] = "/tmp/hnswlib_amd_slimq_XXXXXX";
+    const int fd = mkstemp(slim), fq = mkstemp(slimq);
+    if (fd >= 0) close(fd);
+    if (fq >= 0) close(fq);
+    if (fd < 0 || fq < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
+    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
+    tmp_path_ = slimq;
+    hs_status s = hs_convert_slimq_graph(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), thr_, p0_, p_, M0h_, m0l_, Mh_, ml_, threads, slim);
+    if (s == HS_OK)
+      s = hs_convert_slimq(slim, hnsw->metric(), hnsw->dim(), hnsw->centroids(), hnsw->numClusters(), hnsw->clusterIds(), flip_seed, threads, slimq);
+    unlink(slim);
+    detail::check(s);
+    loadIndex(slimq, space_);
+  }
   HierarchicalNSWSlimQ(SpaceInterface<float> *s, const std::string &location, bool /*nmslib*/ = false,
                        size_t max_elements = 0, bool /*allow_replace_deleted*/ = false) {
     loadIndex(location, s, max_elements);
   }
   void loadIndex(const std::string &location, SpaceInterface<float> *s, size_t max_elements_i = 0) {
+    space_ = s;
     load(location, HS_KIND_SLIMQ, s, max_elements_i);
   }
   // setDataset (hnswalg_slimq.h:303-305): the raw rows, indexed by internal id, for the exact re-rank
@@ -761,8 +878,14 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   void addPoint(const void *, labeltype, bool = false) override {
     throw std::runtime_error("HierarchicalNSWSlimQ does not support addPoint");  // hnswalg_slimq.h:298-301
   }
-  void saveIndex(const std::string &) override {
-    throw std::runtime_error("hnswlib_amd: the device index is read-only; the file it was loaded from is unchanged");
+  // saveIndex (hnswalg_slimq.h:1161-1216) after convertFromHNSW: the file it wrote, copied
+  void saveIndex(const std::string &location) override {
+    if (tmp_path_.empty() || path_ != tmp_path_)
+      throw std::runtime_error("hnswlib_amd: the device index is read-only; the file it was loaded from is unchanged");
+    std::ifstream in(tmp_path_, std::ios::binary);
+    std::ofstream out(location, std::ios::binary);
+    out << in.rdbuf();
+    if (!in || !out) throw std::runtime_error("Cannot open file");
   }
   // the priority_queue overloads of the reference print "todo: searchKnn()" and return nothing (:1795-1808)
   std::priority_queue<std::pair<float, labeltype>> searchKnn(const void *, size_t, BaseFilterFunctor * = nullptr) const override {

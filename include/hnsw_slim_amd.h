@@ -742,6 +742,21 @@ hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw
  * row index == internal id.  threads == 1 reproduces the reference's serial construct() edge for edge. */
 hs_status hs_build_rabitq_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
                                size_t seed, int threads, const char *out_path);
+/* The same graph from the batched insertion order of hs_build_hnsw_batched: the same schedule (levels from
+ * std::default_random_engine(seed) with mult = 1 / ln M), phase A against the graph as the batch found it, the writes of
+ * mutually_connect_new_element in ascending id -- with rabitqlib's rules: pair-ordered heaps, Eigen's packet inner product, no
+ * second link to a node that already lists the new one.  batch_max == 1 is the serial construct(): the bytes of
+ * hs_build_rabitq_hnsw(threads = 1).  Any other schedule writes a graph of its own that does not depend on `threads`, on timing or
+ * on where it was built.  device >= 0 builds on that HIP device for M <= 32, max(ef_construction, M) <= 512 and a row that fits the
+ * on-chip memory; anything else, and device == -1, builds on the host twin (used_gpu = 0), the same bytes.  Options and stats as
+ * hs_build_hnsw_batched; refusals as hs_build_rabitq_hnsw.  Labels are the row index. */
+hs_status hs_build_rabitq_hnsw_batched(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
+                                       size_t seed, const hs_batch_build_opts *opts, const char *out_path,
+                                       hs_batch_build_stats *stats /* nullable */);
+/* The distance of that builder alone, for tests: out[i] = raw distance of rows a[i] and b[i] (n_pairs x dim each, host arrays).
+ * device == -1: the host recipe; otherwise the wavefront recipe of the build kernels on that HIP device (dim <= 8192).  The two
+ * agree bit for bit wherever no NaN arises. */
+hs_status hs_debug_rq_raw_dist(const float *a, const float *b, size_t n_pairs, size_t dim, int metric, int device, float *out);
 /* HierarchicalNSWSlimQ::convertFromHNSW's graph passes (hnswalg_slimq.h:1546-1762): hs_convert_slim's passes with SlimQ's own
  * PruneByHeuristic as written (:1334-1362 -- the occlusion test reads the row whose id is the LOOP INDEX, :1349) and rabitqlib's
  * raw distance (:1623, :1706).  Writes a Slim-layout file; feed it to hs_convert_slimq for the quantised index. */
