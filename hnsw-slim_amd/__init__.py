@@ -41,6 +41,7 @@ EXPORTS = [
     "hs_build_hnsw_batched", "hs_build_schedule",
     "hs_index_add_points_batched", "hs_hnsw_resume_batched", "hs_debug_batched_add_changed",
     "hs_build_rabitq_hnsw_batched", "hs_debug_rq_raw_dist",
+    "hs_convert_slimq_graph_gpu", "hs_convert_slimq_gpu", "hs_convert_hnsw_to_slimq", "hs_debug_rq_quantize_rows",
 ]
 
 
@@ -48,6 +49,12 @@ class HsError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(msg)
         self.status = status
+
+
+class HsSlimqConvertStats(ctypes.Structure):
+    _fields_ = [("graph_used_gpu", ctypes.c_int), ("records_used_gpu", ctypes.c_int), ("graph_kernel_ms", ctypes.c_double),
+                ("records_kernel_ms", ctypes.c_double), ("graph_ms", ctypes.c_double), ("records_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
 
 
 class HsInfo(ctypes.Structure):
@@ -231,6 +238,13 @@ def lib():
     L.hs_convert_slim_gpu.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ci, ctypes.c_char_p,
                                       ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.hs_convert_slimq.argtypes = [ctypes.c_char_p, ci, sz, vp, sz, vp, ctypes.c_uint64, ci, ctypes.c_char_p]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_convert_hnsw_to_slimq"):   # (a baseline build in an A/B run may predate these)
+        L.hs_convert_slimq_graph_gpu.argtypes = L.hs_convert_slim_gpu.argtypes
+        L.hs_convert_slimq_gpu.argtypes = [ctypes.c_char_p, ci, sz, vp, sz, vp, ctypes.c_uint64, ci, ci, ctypes.c_char_p, ctypes.POINTER(ci),
+                                           ctypes.POINTER(ctypes.c_double)]
+        L.hs_convert_hnsw_to_slimq.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, vp, sz, vp, ctypes.c_uint64,
+                                               ci, ci, ctypes.c_char_p, ctypes.POINTER(HsSlimqConvertStats)]
+        L.hs_debug_rq_quantize_rows.argtypes = [sz, ci, vp, vp, sz, vp, sz, vp, ci, vp, vp, vp, vp]
     if "HS_LIB" not in os.environ or hasattr(L, "hs_slim_convert_diff"):   # (a baseline build in an A/B run may predate these)
         psz = ctypes.POINTER(sz)
         L.hs_slim_convert_diff.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.POINTER(vp), ctypes.POINTER(ci),
@@ -425,6 +439,16 @@ def convert_slim_gpu(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_le
     _check(lib().hs_convert_slim_gpu(hnsw_path.encode(), metric, dim, threshold_level, top_degree_percent0, top_degree_percent,
                                      top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, device, threads, out_path.encode(),
                                      ctypes.byref(used), ctypes.byref(ms)))
+    return bool(used.value), ms.value
+
+
+def convert_slimq_graph_gpu(hnsw_path, out_path, dim, metric=HS_METRIC_L2, threshold_level=0, top_degree_percent0=0.02,
+                            top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16, low_degree_m=4, device=0, threads=8):
+    """convert_slimq_graph with the per-list work on the GPU; returns (used_gpu, kernel_ms).  Same bytes as convert_slimq_graph."""
+    used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
+    _check(lib().hs_convert_slimq_graph_gpu(hnsw_path.encode(), metric, dim, threshold_level, top_degree_percent0, top_degree_percent,
+                                            top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, device, threads, out_path.encode(),
+                                            ctypes.byref(used), ctypes.byref(ms)))
     return bool(used.value), ms.value
 
 
@@ -783,6 +807,51 @@ def convert_slimq(slim_path, metric, dim, centroids, out_path, cluster_ids=None,
     cid = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, np.uint32)
     _check(lib().hs_convert_slimq(slim_path.encode(), metric, dim, c.ctypes.data, c.shape[0], None if cid is None else cid.ctypes.data,
                                   flip_seed, threads, out_path.encode()))
+
+
+def convert_slimq_gpu(slim_path, metric, dim, centroids, out_path, cluster_ids=None, flip_seed=1, device=0, threads=8):
+    """convert_slimq with the rotation and quantisation of the rows on a HIP device; returns (used_gpu, kernel_ms).  Same bytes."""
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1, dim)
+    cid = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, np.uint32)
+    used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
+    _check(lib().hs_convert_slimq_gpu(slim_path.encode(), metric, dim, c.ctypes.data, c.shape[0], None if cid is None else cid.ctypes.data,
+                                      flip_seed, device, threads, out_path.encode(), ctypes.byref(used), ctypes.byref(ms)))
+    return bool(used.value), ms.value
+
+
+def convert_hnsw_to_slimq(hnsw_path, out_path, dim, centroids, metric=HS_METRIC_L2, cluster_ids=None, flip_seed=1, threshold_level=0,
+                          top_degree_percent0=0.02, top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16,
+                          low_degree_m=4, device=-1, threads=8):
+    """HierarchicalNSWSlimQ::convertFromHNSW in one call, HNSW file in, SlimQ file out, no intermediate file: the bytes of
+    convert_slimq_graph + convert_slimq.  device=-1: on host threads; device>=0: both steps on that HIP device.  Returns the stats as
+    a dict (graph_used_gpu, records_used_gpu, graph_kernel_ms, records_kernel_ms, graph_ms, records_ms, total_ms)."""
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1, dim)
+    cid = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, np.uint32)
+    st = HsSlimqConvertStats()
+    _check(lib().hs_convert_hnsw_to_slimq(hnsw_path.encode(), metric, dim, threshold_level, top_degree_percent0, top_degree_percent,
+                                          top_degree_M0, low_degree_m0, top_degree_M, low_degree_m, c.ctypes.data, c.shape[0],
+                                          None if cid is None else cid.ctypes.data, flip_seed, device, threads, out_path.encode(),
+                                          ctypes.byref(st)))
+    return {k: getattr(st, k) for k, _ in HsSlimqConvertStats._fields_}
+
+
+def debug_rq_quantize_rows(dim, metric, flips, rows, centroids, cluster_ids=None, device=-1, want_rotated=True):
+    """hs_debug_rq_quantize_rows: the data-side quantiser alone on explicit flip bytes -- the host recipe (device=-1) or the kernels of
+    convert_slimq_gpu.  Returns (rotated n x padded or None, cluster uint32[n], codes uint64[n x padded/64], factors float32[n x 3])."""
+    padded = (dim + 63) // 64 * 64
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, dim)
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1, dim)
+    flips = np.ascontiguousarray(flips, np.uint8)
+    if flips.size != 4 * padded // 8:
+        raise HsError(HS_ERR_INVALID, "flips: 4 * padded / 8 bytes")
+    cid = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, np.uint32)
+    n = rows.shape[0]
+    rot = np.empty((n, padded), np.float32) if want_rotated else None
+    cl, codes, fac = np.empty(n, np.uint32), np.empty((n, padded // 64), np.uint64), np.empty((n, 3), np.float32)
+    _check(lib().hs_debug_rq_quantize_rows(dim, metric, flips.ctypes.data, rows.ctypes.data, n, c.ctypes.data, c.shape[0],
+                                           None if cid is None else cid.ctypes.data, device, None if rot is None else rot.ctypes.data,
+                                           cl.ctypes.data, codes.ctypes.data, fac.ctypes.data))
+    return rot, cl, codes, fac
 
 
 def rabitq_default_tconst(padded_dim, seed=1):

@@ -29,6 +29,32 @@ struct ConvertInput {
 hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,
                              double *kernel_ms);
 
+// The same three phases as HierarchicalNSWSlimQ::convertFromHNSW runs them (convert_slimq.hip): every distance rabitqlib's raw
+// distance, the prune SlimQ's own PruneByHeuristic.  The caller has checked gpu_convert_slimq_fits(in.dim) -- the node's row and a
+// union of kCvUnionCap ids fit the kernels' LDS -- and that no source list is longer than in.n.
+bool gpu_convert_slimq_fits(uint32_t dim);
+hipError_t gpu_convert_slimq_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,
+                                   double *kernel_ms);
+
+// The RaBitQ records of n rows (convert_slimq.hip): row r = rows + r * row_stride (floats; the rows of a Slim element array are read
+// in place), zero-padded to padded = dim rounded up to 64 and rotated with the four flip rounds of `flips` (4 * padded / 8 bytes), its
+// cluster = cluster_ids[r] or, without cluster_ids, the nearest raw centroid, then rq_quantize_data against the rotated centroid.
+// Rows are uploaded kRqChunkBytes at a time.  64 <= dim < 4096, ncl >= 1, cluster ids below ncl: the caller's checks.
+static constexpr size_t kRqChunkBytes = size_t(256) << 20;
+struct RqQuantInput {
+  const float *rows = nullptr;
+  size_t row_stride = 0, n = 0, dim = 0;
+  int metric = 0;
+  const uint8_t *flips = nullptr;
+  const float *cent_raw = nullptr;   // ncl x dim
+  size_t ncl = 0;
+  const uint32_t *cluster_ids = nullptr;
+};
+// out_cent_rot: ncl x padded; out_rot (nullable): n x padded; out_cluster: n; out_code: n x padded / 64; out_fac: n x 3 (all host).
+// kernel_ms (nullable): device time of the kernels, summed over the chunks.
+hipError_t gpu_rq_quantize(const RqQuantInput &in, int device, float *out_cent_rot, float *out_rot, uint32_t *out_cluster, uint64_t *out_code,
+                           float *out_fac, double *kernel_ms);
+
 // What the diff kernel of convert_diff.hip compares the new lists against and what it hands back.  In: the resident Slim
 // index's own adjacency (level-0 tiles + upper-level CSR), labels and fp32 rows as they are BEFORE the call, the resident HNSW
 // index's labels, the per-node levels of the HNSW index.  Out, each ascending (compacted on the device): the changed old nodes and

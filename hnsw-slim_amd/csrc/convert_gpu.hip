@@ -22,33 +22,6 @@
 
 namespace hs {
 
-// by-distance std::sort of (nd[j], nid[j]), j < sz, into arr[]: rank sort when libstdc++'s result is the stable order (sz <= 16:
-// pure insertion sort) or no two keys are equal; otherwise the step-for-step emulation on one lane
-__device__ __forceinline__ void cv_sort_by_dist(const uint32_t *nid, const float *nd, uint32_t sz, Pair *arr, int lane) {
-  if (sz <= 64) {
-    const bool act = (uint32_t)lane < sz;
-    const float my_d = act ? nd[lane] : 0.f;
-    const uint32_t my_id = act ? nid[lane] : 0u;
-    uint32_t rank = 0;
-    bool tie = false;
-    for (uint32_t i = 0; i < sz; i++) {
-      const float di = nd[i];
-      rank += (di < my_d || (di == my_d && i < (uint32_t)lane)) ? 1u : 0u;
-      tie = tie || (di == my_d && i != (uint32_t)lane);
-    }
-    const bool anytie = hs_ballot(act && tie) != 0;
-    if (sz <= 16 || !anytie) {
-      if (act) arr[rank] = Pair{my_d, my_id};
-      wave_sync();
-      return;
-    }
-  }
-  for (uint32_t i = lane; i < sz; i += 64) arr[i] = Pair{nd[i], nid[i]};
-  wave_sync();
-  if (lane == 0) (void)std_sort(arr, (long)sz, LessD());
-  wave_sync();
-}
-
 // Every kernel of this file exists once per stride of the pruned / final lists (ConvertInput::keep).  Its body is a device
 // function with the stride as the template parameter KEEP; the kernel `name` runs it with 32 slots per task -- the kernel as it was
 // before the 64-slot stride, same name, same code, so a call with every capacity and budget <= 32 launches what it always did and
@@ -170,36 +143,7 @@ __device__ __forceinline__ void cv_union_tasks(const float *vec, uint32_t dim, c
       if (lane == 0) { atomicAdd(flags, 1u); fin_cnt[t] = 0; }
       continue;
     }
-    uint32_t N = 64;
-    while (N < total) N <<= 1;
-    for (uint32_t i = lane; i < N; i += 64)
-      ids[i] = i < m1 ? nn[(size_t)t * keep + i] : (i < total ? rev[roff[t] + (i - m1)] : 0xFFFFFFFFu);
-    wave_sync();
-    // bitonic sort ascending (std::sort of plain ids: equal keys are equal values, any correct sort gives the same array)
-    for (uint32_t k = 2; k <= N; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        for (uint32_t i = lane; i < N; i += 64) {
-          const uint32_t p = i ^ j;
-          if (p > i) {
-            const uint32_t a = ids[i], b = ids[p];
-            const bool up = (i & k) == 0;
-            if ((a > b) == up) { ids[i] = b; ids[p] = a; }
-          }
-        }
-        wave_sync();
-      }
-    // std::unique
-    uint32_t m = 0;
-    for (uint32_t base = 0; base < total; base += 64) {
-      const uint32_t i = base + lane;
-      const uint32_t x = i < total ? ids[i] : 0u;
-      const bool first = i < total && (i == 0 || ids[i - 1] != x);
-      const unsigned long long fm = hs_ballot(first);
-      wave_sync();
-      if (first) ids[m + __popcll(fm & ((1ull << lane) - 1ull))] = x;   // m + prefix <= i: never overwrites an unread entry of a later chunk
-      m += __popcll(fm);
-      wave_sync();
-    }
+    const uint32_t m = cv_union_ids(nn + (size_t)t * keep, m1, rev + roff[t], total, ids, lane);
     if (m <= limit) {
       if (m <= keep) {   // (keep <= 64: one lane per entry, here and below)
         if ((uint32_t)lane < m) fin[(size_t)t * keep + lane] = ids[lane];
@@ -245,8 +189,9 @@ static hipError_t cv_upload(T **dp, const std::vector<T> &v) {
   return v.empty() ? hipSuccess : hipMemcpy(*dp, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,
-                             double *kernel_ms) {
+// The three phases with the given phase-1 and phase-3 kernels (this file's, or convert_slimq.hip's) and their LDS bytes
+hipError_t cv_run_lists(const ConvertInput &in, int device, CvPruneKernel prune_k, CvUnionKernel union_k, size_t lds1, size_t lds3,
+                        std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host, double *kernel_ms) {
   hipError_t err = hipSuccess;
   needs_host = false;
   const uint32_t nt = (uint32_t)in.t_node.size();
@@ -258,12 +203,7 @@ hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uin
   std::vector<uint32_t> rcnt(nt), roff(nt + 1, 0);
   uint32_t flags = 0;
   const uint32_t keep = in.keep;   // slots per task of nn / fin, entries of kept / kd in LDS
-  const size_t lds1 = (size_t)in.dim * 8 + kCvMaxList * 16 + keep * 8;
-  const size_t lds3 = (size_t)in.dim * 8 + (size_t)kCvUnionCap * 16 + keep * 8;
   const uint32_t grid = 256 * 16;
-  const bool l2 = in.metric == METRIC_L2, wide = keep != 32;
-  const auto prune_k = wide ? (l2 ? cv_prune_kernel_wide<METRIC_L2> : cv_prune_kernel_wide<METRIC_IP>) : (l2 ? cv_prune_kernel<METRIC_L2> : cv_prune_kernel<METRIC_IP>);
-  const auto union_k = wide ? (l2 ? cv_union_kernel_wide<METRIC_L2> : cv_union_kernel_wide<METRIC_IP>) : (l2 ? cv_union_kernel<METRIC_L2> : cv_union_kernel<METRIC_IP>);
   if (nt == 0) return hipSuccess;
   if (keep != 32 && keep != kCvMaxKeep) return hipErrorInvalidValue;
   CV_TRY(hipSetDevice(device));
@@ -305,6 +245,17 @@ done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   return err;
+}
+
+hipError_t gpu_convert_lists(const ConvertInput &in, int device, std::vector<uint32_t> &fin, std::vector<uint32_t> &fin_cnt, bool &needs_host,
+                             double *kernel_ms) {
+  const uint32_t keep = in.keep;
+  const size_t lds1 = (size_t)in.dim * 8 + kCvMaxList * 16 + keep * 8;
+  const size_t lds3 = (size_t)in.dim * 8 + (size_t)kCvUnionCap * 16 + keep * 8;
+  const bool l2 = in.metric == METRIC_L2, wide = keep != 32;
+  const CvPruneKernel prune_k = wide ? (l2 ? cv_prune_kernel_wide<METRIC_L2> : cv_prune_kernel_wide<METRIC_IP>) : (l2 ? cv_prune_kernel<METRIC_L2> : cv_prune_kernel<METRIC_IP>);
+  const CvUnionKernel union_k = wide ? (l2 ? cv_union_kernel_wide<METRIC_L2> : cv_union_kernel_wide<METRIC_IP>) : (l2 ? cv_union_kernel<METRIC_L2> : cv_union_kernel<METRIC_IP>);
+  return cv_run_lists(in, device, prune_k, union_k, lds1, lds3, fin, fin_cnt, needs_host, kernel_ms);
 }
 
 }  // namespace hs

@@ -132,6 +132,36 @@ inline void rq_quantize_data(const float *x, const float *cen, size_t padded, in
   }
 }
 
+// The records of n rows, the host recipe (HierarchicalNSWSlimQ::convertFromHNSW's quantisation loop, hnswalg_slimq.h:1764-1786):
+// the centroids rotated once, then per row (row r = rows + r * row_stride floats) its cluster -- cluster_ids[r], or the nearest RAW
+// centroid when cluster_ids is null, `dd < best` from FLT_MAX so that the first minimum wins --, its rotation and rq_quantize_data
+// against the rotated centroid.  cent_rot: ncl x padded; out_rot (nullable): n x padded; cluster: n; code: n x padded / 64; fac: n x 3.
+// convert_slimq.hip's quantiser kernel is held to this bit for bit.
+inline void rq_quantize_rows_host(const Rotator &rot, int metric, const float *rows, size_t row_stride, size_t n, const float *cent_raw, size_t ncl,
+                                  const uint32_t *cluster_ids, int threads, float *cent_rot, float *out_rot, uint32_t *cluster, uint64_t *code,
+                                  float *fac) {
+  const size_t d = rot.dim, padded = rot.padded;
+  for (size_t c = 0; c < ncl; c++) rot.rotate(cent_raw + c * d, cent_rot + c * padded);
+  std::vector<std::vector<float>> rx(std::max(1, threads), std::vector<float>(padded));
+  parallel_for(n, threads, 64, [&](size_t i, int tid) {
+    const float *row = rows + i * row_stride;
+    uint32_t cid;
+    if (cluster_ids) cid = cluster_ids[i];
+    else {
+      float best = std::numeric_limits<float>::max();
+      cid = 0;
+      for (size_t c = 0; c < ncl; c++) {
+        float dd = rq_l2sqr(row, cent_raw + c * d, d);
+        if (dd < best) { best = dd; cid = (uint32_t)c; }
+      }
+    }
+    cluster[i] = cid;
+    float *y = out_rot ? out_rot + i * padded : rx[tid].data();
+    rot.rotate(row, y);
+    rq_quantize_data(y, cent_rot + cid * padded, padded, metric, code + i * padded / 64, fac + i * 3);
+  });
+}
+
 // Prepared query: everything the estimator needs besides the per-vector record.
 struct RqQuery {
   float delta = 0, vl = 0, k1xsumq = 0;
@@ -321,6 +351,14 @@ struct SlimQGraph {
   // (nearest raw centroid when cluster_ids is null).
   void from_slim(const SlimGraph &s, int metric_, const float *cent_raw, size_t ncl, const uint32_t *cluster_ids,
                  uint64_t flip_seed, int threads) {
+    take_slim(s, metric_, ncl, flip_seed);
+    rq_quantize_rows_host(rot, metric, count ? s.vec(0) : nullptr, s.size_per_el / 4, count, cent_raw, ncl, cluster_ids, threads, centroids.data(), nullptr, cluster.data(),
+                          code.data(), factors.data());
+  }
+  // Everything of from_slim() but the records: header, rotator, levels, labels and blobs of `s`; centroids / cluster / code / factors
+  // sized and left for the caller to fill (from_slim on the host, gpu_rq_quantize on a device).  The rows of `s` lie size_per_el
+  // bytes apart, 24 bytes into each element: a stride of size_per_el / 4 floats from s.vec(0).
+  void take_slim(const SlimGraph &s, int metric_, size_t ncl, uint64_t flip_seed) {
     const size_t n = s.count, d = s.dim;
     count = n; dim = d; padded = rq_padded(d); metric = metric_; num_cluster = ncl;
     maxM = s.maxM; maxM0 = s.maxM0; M = s.M; efC = s.efC; maxlevel = s.maxlevel; threshold_level = s.threshold_level;
@@ -328,27 +366,9 @@ struct SlimQGraph {
     rot.init(d);
     rot.random_flips(flip_seed);
     centroids.resize(ncl * padded);
-    for (size_t c = 0; c < ncl; c++) rot.rotate(cent_raw + c * d, &centroids[c * padded]);
     level.resize(n); label.resize(n); cluster.resize(n); code.resize(n * padded / 64); factors.resize(n * 3);
     blobs = s.blobs;
-    std::vector<std::vector<float>> rx(std::max(1, threads), std::vector<float>(padded));
-    parallel_for(n, threads, 64, [&](size_t i, int tid) {
-      level[i] = s.level(i);
-      label[i] = s.label(i);
-      uint32_t cid;
-      if (cluster_ids) cid = cluster_ids[i];
-      else {
-        float best = std::numeric_limits<float>::max();
-        cid = 0;
-        for (size_t c = 0; c < ncl; c++) {
-          float dd = rq_l2sqr(s.vec(i), cent_raw + c * d, d);
-          if (dd < best) { best = dd; cid = (uint32_t)c; }
-        }
-      }
-      cluster[i] = cid;
-      rot.rotate(s.vec(i), rx[tid].data());
-      rq_quantize_data(rx[tid].data(), &centroids[cid * padded], padded, metric, &code[i * padded / 64], &factors[i * 3]);
-    });
+    for (size_t i = 0; i < n; i++) { level[i] = s.level(i); label[i] = s.label(i); }
   }
 };
 

@@ -118,6 +118,61 @@ __device__ __forceinline__ void rq_dists(const float *vec, uint32_t dim, const f
     if (act && j == 0) nd[r] = METRIC == METRIC_L2 ? res : 1.0f - res;
   }
 }
+
+// The pairwise sibling: rabitq_raw_dist(row a_first + r, row ids[r].id) for r < cnt into pd[0..cnt) (LDS), for pairs that share
+// no query row (HierarchicalNSWSlimQ's PruneByHeuristic measures candidate i against the row whose id is the loop index i).
+// rq_dists' lane mapping and arithmetic term for term, with the row a_first + r read from memory where rq_dists reads qv: four
+// pairs per pass.  IDS: anything with an `.id` member (the sorted (distance, id) pairs).  The caller guarantees a_first + cnt <= n.
+template <int METRIC, class IDS>
+__device__ __forceinline__ void rq_pair_dists(const float *vec, uint32_t dim, uint32_t a_first, const IDS *ids, float *pd, uint32_t cnt, int lane) {
+  const uint32_t j = (uint32_t)lane & 15u, grp = (uint32_t)lane >> 4;
+  const uint32_t np = dim >> 4, packet_end = np << 4, quad_end = (dim >> 6) << 6, nrem = (packet_end - quad_end) >> 4;
+  for (uint32_t base = 0; base < cnt; base += 4) {
+    const uint32_t r = base + grp;
+    const bool act = r < cnt;
+    const uint32_t rr = act ? r : base;
+    const float *qv = vec + (size_t)(a_first + rr) * dim;
+    const float *row = vec + (size_t)ids[rr].id * dim;
+    float res;
+    if (np == 0) {
+      res = rq_term<METRIC>(qv[0], row[0], 0.f, true);
+      for (uint32_t k = 1; k < dim; k++) res = rq_term<METRIC>(qv[k], row[k], res, false);
+    } else {
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
+      {
+        float x[4], q[4];
+#pragma unroll
+        for (uint32_t p = 0; p < 4; p++)
+          if (p < np) { x[p] = row[p * 16 + j]; q[p] = qv[p * 16 + j]; }
+#pragma unroll
+        for (uint32_t p = 0; p < 4; p++)
+          if (p < np) acc[p] = rq_term<METRIC>(q[p], x[p], 0.f, true);
+      }
+      if (np >= 4) {
+        for (uint32_t k = 64; k < quad_end; k += 64) {
+          float x[4], q[4];
+#pragma unroll
+          for (uint32_t p = 0; p < 4; p++) { x[p] = row[k + p * 16 + j]; q[p] = qv[k + p * 16 + j]; }
+#pragma unroll
+          for (uint32_t p = 0; p < 4; p++) acc[p] = rq_term<METRIC>(q[p], x[p], acc[p], false);
+        }
+#pragma unroll
+        for (uint32_t p = 0; p < 3; p++)
+          if (p < nrem) acc[p] = rq_term<METRIC>(qv[quad_end + p * 16 + j], row[quad_end + p * 16 + j], acc[p], false);
+        acc[2] = acc[2] + acc[3];
+      }
+      if (np >= 3) acc[1] = acc[1] + acc[2];
+      if (np >= 2) acc[0] = acc[0] + acc[1];
+      res = acc[0];
+      res = res + dpp_f<0x128>(res);   // row_ror:8
+      res = res + dpp_f<0x124>(res);   // row_ror:4
+      res = res + dpp_f<0x122>(res);   // row_ror:2
+      res = res + dpp_f<0x121>(res);   // row_ror:1
+      for (uint32_t k = packet_end; k < dim; k++) res = rq_term<METRIC>(qv[k], row[k], res, false);
+    }
+    if (act && j == 0) pd[r] = METRIC == METRIC_L2 ? res : 1.0f - res;
+  }
+}
 #endif
 
 }  // namespace hs

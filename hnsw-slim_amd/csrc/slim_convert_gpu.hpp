@@ -122,22 +122,26 @@ inline bool convert_diff_gpu(SlimGraph &s, const VanillaGraph &g, const SlimPara
   });
   return true;
 }
-// convert() with the list-level work on the GPU (convert_gpu.hip).  Returns false when the shape is outside the
-// device path (lists longer than 64 / capacities or degree budgets above 64 ids, or a reverse-edge list that outgrew the on-chip buffers):
-// the caller then runs convert().  kernel_ms: device time of the kernels.
-inline bool convert_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
+// convert() with the list-level work on the GPU: `run` is gpu_convert_lists (convert_gpu.hip) or gpu_convert_slimq_lists
+// (convert_slimq.hip).  Returns false when the shape is outside the device path (lists longer than 64 / capacities or degree budgets
+// above 64 ids, `extra_ok` refusing the task lists, or a reverse-edge list that outgrew the on-chip buffers): the caller then runs the
+// host conversion.  kernel_ms: device time of the kernels.
+typedef hipError_t (*ConvertListsFn)(const ConvertInput &, int, std::vector<uint32_t> &, std::vector<uint32_t> &, bool &, double *);
+inline bool convert_gpu_with(ConvertListsFn run, bool (*extra_ok)(const ConvertInput &), SlimGraph &s, const VanillaGraph &g, const SlimParams &p,
+                             int device, int threads, double *kernel_ms, std::string *err) {
   if (g.maxM0 > 64 || g.maxM > 64 || p.top_M0 > 64 || p.low_m0 > 64 || p.top_M > 64 || p.low_m > 64) return false;
   s.take_header(g, p);
   const size_t n = s.count;
   const std::vector<size_t> thr = SlimGraph::hub_thresholds(g, p);
   ConvertInput in;
   if (!make_convert_input(g, p, thr, s.maxM0, s.maxM, in)) return false;
+  if (extra_ok && !extra_ok(in)) return false;
   std::vector<float> rows(n * s.dim);
   for (size_t i = 0; i < n; i++) memcpy(&rows[i * s.dim], g.vec(i), 4 * s.dim);
   in.vec = rows.data();
   DeviceLists lists{in, {}, {}};
   bool needs_host = false;
-  hipError_t e = gpu_convert_lists(in, device, lists.fin, lists.fin_cnt, needs_host, kernel_ms);
+  hipError_t e = run(in, device, lists.fin, lists.fin_cnt, needs_host, kernel_ms);
   if (e != hipSuccess) {
     if (err) *err = std::string("GPU convert: ") + hipGetErrorString(e);
     return false;
@@ -147,6 +151,23 @@ inline bool convert_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p
   s.blobs.assign(n, {});
   parallel_for(n, threads, 256, [&](size_t i, int) { s.assemble_node(g, i, lists); });
   return true;
+}
+// SlimGraph::convert on the device (convert_gpu.hip)
+inline bool convert_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
+  return convert_gpu_with(gpu_convert_lists, nullptr, s, g, p, device, threads, kernel_ms, err);
+}
+// What the SlimQ kernels need beyond make_convert_input(): a row that fits their LDS, and no source list longer than n -- the
+// prune measures candidate i of a list against row i (slimq_prune.hpp), which must exist.  A graph's lists hold distinct neighbours
+// other than the node itself, so only a damaged file breaks the second; it then takes the host path, which reads the file as it is.
+inline bool cq_input_ok(const ConvertInput &in) {
+  if (!gpu_convert_slimq_fits(in.dim)) return false;
+  for (uint32_t sz : in.t_size)
+    if (sz > in.n) return false;
+  return true;
+}
+// convert_slimq_graph (host_rq_graph.hpp) on the device (convert_slimq.hip)
+inline bool convert_slimq_gpu(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, double *kernel_ms, std::string *err) {
+  return convert_gpu_with(gpu_convert_slimq_lists, cq_input_ok, s, g, p, device, threads, kernel_ms, err);
 }
 
 }  // namespace hs

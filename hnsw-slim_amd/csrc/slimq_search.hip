@@ -34,6 +34,7 @@
 
 #include "heap_emul.hpp"
 #include "rabitq_est.hpp"
+#include "rabitq_rotate.hpp"
 #include "slimq_engine.hpp"
 #include "wave_util.hpp"
 
@@ -237,56 +238,6 @@ __device__ __forceinline__ float est_one(const DevSlimQ &sq, const uint64_t *pla
 }
 
 // ---- query preparation ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void flip_signs(float *y, const uint8_t *f, uint32_t n, int lane) {
-#pragma unroll 1
-  for (uint32_t i = lane; i < n; i += 64)
-    if ((f[i >> 3] >> (i & 7)) & 1) y[i] = -y[i];
-}
-// in-place Walsh-Hadamard over n (power of two) floats in LDS, butterfly stages in ascending stride, then * scale
-__device__ __forceinline__ void fht_lds(float *y, uint32_t n, float scale, int lane) {
-  for (uint32_t h = 1; h < n; h <<= 1) {
-    wave_sync();
-#pragma unroll 1
-    for (uint32_t t = lane; t < n / 2; t += 64) {
-      const uint32_t j = ((t / h) * 2 * h) + (t % h);
-      const float a = y[j], b = y[j + h];
-      y[j] = a + b;
-      y[j + h] = a - b;
-    }
-  }
-  wave_sync();
-#pragma unroll 1
-  for (uint32_t i = lane; i < n; i += 64) y[i] *= scale;
-}
-__device__ __forceinline__ void rotate_lds(const DevSlimQ &sq, float *y, int lane) {
-  const uint32_t P = sq.padded, T = sq.trunc, nb = P / 8;
-  if (T == P) {
-    for (int r = 0; r < 4; r++) {
-      wave_sync();
-      flip_signs(y, sq.flips + r * nb, P, lane);
-      fht_lds(y, T, sq.fht_scale, lane);
-    }
-    wave_sync();
-    return;
-  }
-  for (int r = 0; r < 4; r++) {
-    wave_sync();
-    flip_signs(y, sq.flips + r * nb, P, lane);
-    fht_lds((r & 1) ? y + (P - T) : y, T, sq.fht_scale, lane);
-    wave_sync();
-#pragma unroll 1
-    for (uint32_t i = lane; i < P / 2; i += 64) {  // kacs_walk
-      const float a = y[i], b = y[i + P / 2];
-      y[i] = a + b;
-      y[i + P / 2] = a - b;
-    }
-  }
-  wave_sync();
-#pragma unroll 1
-  for (uint32_t i = lane; i < P; i += 64) y[i] *= 0.25f;
-  wave_sync();
-}
-
 // Per-query preparation record in global memory (prep_words(ncl, padded) u32 words):
 //   [0] delta [1] vl [2] k1xsumq [3] -   [4 .. 4+ncl) g_add per cluster   [align 2] 4 bit planes per 64-dim block (u64)
 __host__ __device__ inline uint32_t prep_planes_off(uint32_t ncl) { return (4 + ncl + 1) & ~1u; }

@@ -826,9 +826,15 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   float p0_ = 0.02f, p_ = 0.02f;
   size_t M0h_ = 32, m0l_ = 8, Mh_ = 16, ml_ = 4;
   std::string tmp_path_;                 // the SlimQ file convertFromHNSW wrote
+  int convert_device_ = -1;
+  hs_slimq_convert_stats convert_stats_{};
 
  public:
   explicit HierarchicalNSWSlimQ(SpaceInterface<float> *s) : space_(s) {}
+  // (no counterpart in the reference) convertFromHNSW on that HIP device: both steps in one call with no file between them
+  // (hs_convert_hnsw_to_slimq); the index it leaves is byte for byte the one the two host calls leave.
+  void setBuildOnDevice(int device) { convert_device_ = device < 0 ? -1 : device; }
+  const hs_slimq_convert_stats &convertStats() const { return convert_stats_; }   // of the last convertFromHNSW that went through setBuildOnDevice
   HierarchicalNSWSlimQ(SpaceInterface<float> *s, size_t /*max_elements*/, size_t /*M*/ = 16, size_t /*ef_construction*/ = 200, int threshold_level = 0,
                        float top_degree_percent0 = 0.02f, float top_degree_percent = 0.02f, size_t top_degree_M0 = 32, size_t low_degree_m0 = 8,
                        size_t top_degree_M = 16, size_t low_degree_m = 4)
@@ -836,7 +842,8 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
         Mh_(top_degree_M), ml_(low_degree_m) {}
   ~HierarchicalNSWSlimQ() { if (!tmp_path_.empty()) unlink(tmp_path_.c_str()); }
   // convertFromHNSW(hnsw) (hnswalg_slimq.h:1471-1790) on the graph construct() built: the graph passes (hs_convert_slimq_graph), the
-  // RaBitQ records with the centroids and cluster ids construct() was given (hs_convert_slimq), then the result is loaded.
+  // RaBitQ records with the centroids and cluster ids construct() was given (hs_convert_slimq), then the result is loaded.  After
+  // setBuildOnDevice: the same two steps on that device, chained in memory.
   void convertFromHNSW(rabitqlib::hnsw::HierarchicalNSW *hnsw, int threads = 8, uint64_t flip_seed = 1) {
     if (!hnsw || hnsw->graphPath().empty()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs a constructed rabitqlib index");
     if (!space_) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs the space the index was constructed with");
@@ -848,6 +855,14 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
     if (fd < 0 || fq < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
     if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
     tmp_path_ = slimq;
+    convert_stats_ = hs_slimq_convert_stats{};
+    if (convert_device_ >= 0) {
+      unlink(slim);
+      detail::check(hs_convert_hnsw_to_slimq(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), thr_, p0_, p_, M0h_, m0l_, Mh_, ml_, hnsw->centroids(),
+                                             hnsw->numClusters(), hnsw->clusterIds(), flip_seed, convert_device_, threads, slimq, &convert_stats_));
+      loadIndex(slimq, space_);
+      return;
+    }
     hs_status s = hs_convert_slimq_graph(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), thr_, p0_, p_, M0h_, m0l_, Mh_, ml_, threads, slim);
     if (s == HS_OK)
       s = hs_convert_slimq(slim, hnsw->metric(), hnsw->dim(), hnsw->centroids(), hnsw->numClusters(), hnsw->clusterIds(), flip_seed, threads, slimq);

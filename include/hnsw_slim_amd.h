@@ -771,6 +771,42 @@ hs_status hs_convert_slimq_graph(const char *hnsw_path, int metric, size_t dim, 
  * centroids: num_cluster x dim raw vectors; cluster_ids: n ids or NULL (= nearest centroid). */
 hs_status hs_convert_slimq(const char *slim_path, int metric, size_t dim, const float *centroids, size_t num_cluster,
                            const uint32_t *cluster_ids, uint64_t flip_seed, int threads, const char *out_path);
+/* ---- HierarchicalNSWSlimQ::convertFromHNSW on a HIP device (csrc/convert_slimq.hip) -----------------------------
+ * hs_convert_slimq_graph with the list-level work on `device`: raw distances, the by-distance std::sort, SlimQ's PruneByHeuristic,
+ * the reverse-edge union and the re-prune; histograms, hub thresholds and the assembly run on `threads` host threads.  The file is
+ * byte-identical to hs_convert_slimq_graph's.  Shapes outside the device path (hs_convert_slim_gpu's: capacities or budgets above
+ * 64, a source list above 64 ids, a union beyond 2048; and a row that does not fit the kernels' on-chip memory, dim > 8112) are
+ * converted on the host; *used_gpu (nullable) says which path ran, *kernel_ms (nullable) the device time. */
+hs_status hs_convert_slimq_graph_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level,
+                                     float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
+                                     size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, int device, int threads,
+                                     const char *out_path, int *used_gpu, double *kernel_ms);
+/* hs_convert_slimq with the rotation and the 1-bit quantisation of every row on `device`, one wavefront per row; rows are uploaded
+ * 256 MiB at a time.  The file is byte-identical to hs_convert_slimq's; refusals as hs_convert_slimq, and HS_ERR_DEVICE without
+ * such a device.  *used_gpu / *kernel_ms (nullable) as above. */
+hs_status hs_convert_slimq_gpu(const char *slim_path, int metric, size_t dim, const float *centroids, size_t num_cluster,
+                               const uint32_t *cluster_ids, uint64_t flip_seed, int device, int threads, const char *out_path,
+                               int *used_gpu, double *kernel_ms);
+/* Both steps in one call, HNSW file in, SlimQ file out, with no intermediate file: the Slim graph stays in memory and feeds the
+ * quantisation.  device == -1: both steps on `threads` host threads; device >= 0: both on that device, each falling back to the
+ * host outside its envelope.  Either way the bytes of hs_convert_slimq_graph followed by hs_convert_slimq.  Refusals as those two. */
+typedef struct hs_slimq_convert_stats {
+  int graph_used_gpu, records_used_gpu;      /* which path each step took */
+  double graph_kernel_ms, records_kernel_ms; /* device time of each step's kernels (0 on the host path) */
+  double graph_ms, records_ms, total_ms;     /* wall clock: graph passes incl. loading the file; records; the whole call incl. the save */
+} hs_slimq_convert_stats;
+hs_status hs_convert_hnsw_to_slimq(const char *hnsw_path, int metric, size_t dim, int threshold_level,
+                                   float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
+                                   size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, const float *centroids,
+                                   size_t num_cluster, const uint32_t *cluster_ids, uint64_t flip_seed, int device, int threads,
+                                   const char *out_path, hs_slimq_convert_stats *stats /* nullable */);
+/* The quantiser alone, on explicit flip bytes (4 * padded / 8), for tests: n rows (n x dim) against num_cluster raw centroids;
+ * cluster_ids NULL = nearest raw centroid, first minimum.  device == -1: the host recipe; otherwise the kernels of
+ * hs_convert_slimq_gpu on that device, bit for bit the same.  out_rotated (nullable): n x padded; out_cluster: n; out_codes:
+ * n x padded / 64; out_factors: n x 3. */
+hs_status hs_debug_rq_quantize_rows(size_t dim, int metric, const uint8_t *flips, const float *rows, size_t n,
+                                    const float *centroids_raw, size_t num_cluster, const uint32_t *cluster_ids, int device,
+                                    float *out_rotated, uint32_t *out_cluster, uint64_t *out_codes, float *out_factors);
 /* quant::faster_config(padded, 4).t_const (rabitqlib/quantization/rabitq.hpp:27-33) with a seeded generator. */
 double hs_rabitq_default_tconst(size_t padded_dim, uint64_t seed);
 
