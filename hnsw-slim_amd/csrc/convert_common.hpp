@@ -60,6 +60,14 @@ __device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const f
   }
 }
 
+// cv_dists as a type: the default distance of cv_prune (build_gpu.hip's flavours are the others)
+struct CvDists {
+  template <int METRIC>
+  static __device__ __forceinline__ void dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
+    cv_dists<METRIC>(vec, dim, qv, nid, nd, cnt, lane);
+  }
+};
+
 // by-distance std::sort of (nd[j], nid[j]), j < sz, into arr[]: rank sort when libstdc++'s result is the stable order (sz <= 16:
 // pure insertion sort) or no two keys are equal; otherwise the step-for-step emulation on one lane
 __device__ __forceinline__ void cv_sort_by_dist(const uint32_t *nid, const float *nd, uint32_t sz, Pair *arr, int lane) {
@@ -89,8 +97,9 @@ __device__ __forceinline__ void cv_sort_by_dist(const uint32_t *nid, const float
 
 // PruneByHeuristic (hnswalg_slim.h:836-865) over arr[0..sz) sorted ascending by distance: a candidate is kept unless a kept
 // neighbour is closer to it than the node itself.  Sequential in the candidates, parallel over the kept set.  This is also the
-// keep loop of getNeighborsByHeuristic2 (hnswalg.h:495-517) once arr[] is in ITS candidate order (diff_prune.hpp).
-template <int METRIC>
+// keep loop of getNeighborsByHeuristic2 (hnswalg.h:495-517) once arr[] is in ITS candidate order (diff_prune.hpp), and of
+// rabitqlib's get_neighbors_by_heuristic2 (hnsw.hpp:1016-1054) with DIST its distance (build_gpu.hip).
+template <int METRIC, class DIST = CvDists>
 __device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
                                              uint32_t *kept, float *kd, int lane, float *keptd = nullptr) {
   uint32_t kc = 0;   // (kept / kd / keptd hold `keep` entries: the caller passes mlim <= keep)
@@ -101,7 +110,7 @@ __device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, con
     if (kc > 0) {
       for (uint32_t i = lane; i < dim; i += 64) qc[i] = vec[(size_t)cid * dim + i];
       wave_sync();
-      cv_dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
+      DIST::template dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
       wave_sync();
       bool bad = false;
       for (uint32_t i = lane; i < kc; i += 64) bad = bad || kd[i] < cd;

@@ -1,5 +1,5 @@
 // rq_dist.hpp -- rabitqlib's raw distance, the one every edge of HNSW-SlimQ's base graph is measured with: the host text
-// (rabitq_raw_dist, the definition) and the same recipe on a wavefront (rq_dists, compiled for the device only), which the batched
+// (rabitq_raw_dist, the definition) and the same recipe on a wavefront (rq_dist_pairs, compiled for the device only), which the batched
 // build of that graph (build_gpu.hip) is held to bit for bit through hs_debug_rq_raw_dist.
 #pragma once
 #include <algorithm>
@@ -63,76 +63,24 @@ __device__ __forceinline__ float rq_term(float q, float x, float acc, bool first
   return first ? X * Y : __builtin_fmaf(X, Y, acc);
 }
 
-// rabitq_raw_dist of the row `qv` (LDS, dim floats) against rows nid[0..cnt) (LDS) of vec into nd[0..cnt) (LDS), one wavefront.
-// Sixteen lanes per row: lane j of the group holds element j of the four packet accumulators, so the wavefront measures four rows
-// per pass and a group reads 64 contiguous bytes per packet.  The folds 2+=3, 1+=2, 0+=1 are lane-local.  predux is a butterfly
-// over the sixteen lanes at distances 8, 4, 2, 1 (rotations within the DPP row: after the step at distance s every value repeats
-// with period s, so a rotation by s / 2 reads what an exchange at that distance would); every add is commutative, hence lane 0
-// -- and every other lane -- ends with the bits of t8 / t4 / (0+2, 1+3) / (0+1).  The tail below a packet, and dim < 16
-// altogether, is the scalar fused chain, run by every lane of the group alike.
-template <int METRIC>
-__device__ __forceinline__ void rq_dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
-  const uint32_t j = (uint32_t)lane & 15u, grp = (uint32_t)lane >> 4;
-  const uint32_t np = dim >> 4, packet_end = np << 4, quad_end = (dim >> 6) << 6, nrem = (packet_end - quad_end) >> 4;
-  for (uint32_t base = 0; base < cnt; base += 4) {
-    const uint32_t r = base + grp;
-    const bool act = r < cnt;
-    const float *row = vec + (size_t)nid[act ? r : base] * dim;
-    float res;
-    if (np == 0) {
-      res = rq_term<METRIC>(qv[0], row[0], 0.f, true);
-      for (uint32_t k = 1; k < dim; k++) res = rq_term<METRIC>(qv[k], row[k], res, false);
-    } else {
-      float acc[4] = {0.f, 0.f, 0.f, 0.f};
-      {
-        float x[4];
-#pragma unroll
-        for (uint32_t p = 0; p < 4; p++)
-          if (p < np) x[p] = row[p * 16 + j];
-#pragma unroll
-        for (uint32_t p = 0; p < 4; p++)
-          if (p < np) acc[p] = rq_term<METRIC>(qv[p * 16 + j], x[p], 0.f, true);
-      }
-      if (np >= 4) {
-        for (uint32_t k = 64; k < quad_end; k += 64) {
-          float x[4];
-#pragma unroll
-          for (uint32_t p = 0; p < 4; p++) x[p] = row[k + p * 16 + j];
-#pragma unroll
-          for (uint32_t p = 0; p < 4; p++) acc[p] = rq_term<METRIC>(qv[k + p * 16 + j], x[p], acc[p], false);
-        }
-#pragma unroll
-        for (uint32_t p = 0; p < 3; p++)
-          if (p < nrem) acc[p] = rq_term<METRIC>(qv[quad_end + p * 16 + j], row[quad_end + p * 16 + j], acc[p], false);
-        acc[2] = acc[2] + acc[3];
-      }
-      if (np >= 3) acc[1] = acc[1] + acc[2];
-      if (np >= 2) acc[0] = acc[0] + acc[1];
-      res = acc[0];
-      res = res + dpp_f<0x128>(res);   // row_ror:8
-      res = res + dpp_f<0x124>(res);   // row_ror:4
-      res = res + dpp_f<0x122>(res);   // row_ror:2
-      res = res + dpp_f<0x121>(res);   // row_ror:1
-      for (uint32_t k = packet_end; k < dim; k++) res = rq_term<METRIC>(qv[k], row[k], res, false);
-    }
-    if (act && j == 0) nd[r] = METRIC == METRIC_L2 ? res : 1.0f - res;
-  }
-}
-
-// The pairwise sibling: rabitq_raw_dist(row a_first + r, row ids[r].id) for r < cnt into pd[0..cnt) (LDS), for pairs that share
-// no query row (HierarchicalNSWSlimQ's PruneByHeuristic measures candidate i against the row whose id is the loop index i).
-// rq_dists' lane mapping and arithmetic term for term, with the row a_first + r read from memory where rq_dists reads qv: four
-// pairs per pass.  IDS: anything with an `.id` member (the sorted (distance, id) pairs).  The caller guarantees a_first + cnt <= n.
-template <int METRIC, class IDS>
-__device__ __forceinline__ void rq_pair_dists(const float *vec, uint32_t dim, uint32_t a_first, const IDS *ids, float *pd, uint32_t cnt, int lane) {
+// The recipe on a wavefront, for cnt pairs: pair r is the row qrow(r) (dim floats, LDS or memory) against the row id(r) of vec, into
+// out[r] (LDS).  QMEM: the query rows are in memory, and their elements are loaded with the row's, ahead of the terms, so that
+// both loads are in flight together; an LDS row is read term by term.  Sixteen lanes per pair: lane j of the group holds element j of the four packet accumulators, so the wavefront
+// measures four pairs per pass and a group reads 64 contiguous bytes per packet.  The folds 2+=3, 1+=2, 0+=1 are lane-local.
+// predux is a butterfly over the sixteen lanes at distances 8, 4, 2, 1 (rotations within the DPP row: after the step at distance s
+// every value repeats with period s, so a rotation by s / 2 reads what an exchange at that distance would); every add is
+// commutative, hence lane 0 -- and every other lane -- ends with the bits of t8 / t4 / (0+2, 1+3) / (0+1).  The tail below a
+// packet, and dim < 16 altogether, is the scalar fused chain, run by every lane of the group alike.
+template <int METRIC, bool QMEM, class QROW, class ID>
+__device__ __forceinline__ void rq_dist_pairs(const float *vec, uint32_t dim, QROW qrow, ID id, float *out, uint32_t cnt, int lane) {
   const uint32_t j = (uint32_t)lane & 15u, grp = (uint32_t)lane >> 4;
   const uint32_t np = dim >> 4, packet_end = np << 4, quad_end = (dim >> 6) << 6, nrem = (packet_end - quad_end) >> 4;
   for (uint32_t base = 0; base < cnt; base += 4) {
     const uint32_t r = base + grp;
     const bool act = r < cnt;
     const uint32_t rr = act ? r : base;
-    const float *qv = vec + (size_t)(a_first + rr) * dim;
-    const float *row = vec + (size_t)ids[rr].id * dim;
+    const float *qv = qrow(rr);
+    const float *row = vec + (size_t)id(rr) * dim;
     float res;
     if (np == 0) {
       res = rq_term<METRIC>(qv[0], row[0], 0.f, true);
@@ -143,18 +91,18 @@ __device__ __forceinline__ void rq_pair_dists(const float *vec, uint32_t dim, ui
         float x[4], q[4];
 #pragma unroll
         for (uint32_t p = 0; p < 4; p++)
-          if (p < np) { x[p] = row[p * 16 + j]; q[p] = qv[p * 16 + j]; }
+          if (p < np) { x[p] = row[p * 16 + j]; if (QMEM) q[p] = qv[p * 16 + j]; }
 #pragma unroll
         for (uint32_t p = 0; p < 4; p++)
-          if (p < np) acc[p] = rq_term<METRIC>(q[p], x[p], 0.f, true);
+          if (p < np) acc[p] = rq_term<METRIC>(QMEM ? q[p] : qv[p * 16 + j], x[p], 0.f, true);
       }
       if (np >= 4) {
         for (uint32_t k = 64; k < quad_end; k += 64) {
           float x[4], q[4];
 #pragma unroll
-          for (uint32_t p = 0; p < 4; p++) { x[p] = row[k + p * 16 + j]; q[p] = qv[k + p * 16 + j]; }
+          for (uint32_t p = 0; p < 4; p++) { x[p] = row[k + p * 16 + j]; if (QMEM) q[p] = qv[k + p * 16 + j]; }
 #pragma unroll
-          for (uint32_t p = 0; p < 4; p++) acc[p] = rq_term<METRIC>(q[p], x[p], acc[p], false);
+          for (uint32_t p = 0; p < 4; p++) acc[p] = rq_term<METRIC>(QMEM ? q[p] : qv[k + p * 16 + j], x[p], acc[p], false);
         }
 #pragma unroll
         for (uint32_t p = 0; p < 3; p++)
@@ -170,8 +118,22 @@ __device__ __forceinline__ void rq_pair_dists(const float *vec, uint32_t dim, ui
       res = res + dpp_f<0x121>(res);   // row_ror:1
       for (uint32_t k = packet_end; k < dim; k++) res = rq_term<METRIC>(qv[k], row[k], res, false);
     }
-    if (act && j == 0) pd[r] = METRIC == METRIC_L2 ? res : 1.0f - res;
+    if (act && j == 0) out[r] = METRIC == METRIC_L2 ? res : 1.0f - res;
   }
+}
+
+// rabitq_raw_dist of the row `qv` (LDS, dim floats) against rows nid[0..cnt) (LDS) of vec into nd[0..cnt) (LDS), one wavefront.
+template <int METRIC>
+__device__ __forceinline__ void rq_dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
+  rq_dist_pairs<METRIC, false>(vec, dim, [=](uint32_t) { return qv; }, [=](uint32_t r) { return nid[r]; }, nd, cnt, lane);
+}
+
+// The pairwise sibling: rabitq_raw_dist(row a_first + r, row ids[r].id) for r < cnt into pd[0..cnt) (LDS), for pairs that share
+// no query row (HierarchicalNSWSlimQ's PruneByHeuristic measures candidate i against the row whose id is the loop index i).
+// IDS: anything with an `.id` member (the sorted (distance, id) pairs).  The caller guarantees a_first + cnt <= n.
+template <int METRIC, class IDS>
+__device__ __forceinline__ void rq_pair_dists(const float *vec, uint32_t dim, uint32_t a_first, const IDS *ids, float *pd, uint32_t cnt, int lane) {
+  rq_dist_pairs<METRIC, true>(vec, dim, [=](uint32_t r) { return vec + (size_t)(a_first + r) * dim; }, [=](uint32_t r) { return ids[r].id; }, pd, cnt, lane);
 }
 #endif
 

@@ -1,5 +1,5 @@
-"""The batched build of HNSW-SlimQ's base graph on the GPU (hs_build_rabitq_hnsw_batched with a device, the rq kernels of
-csrc/build_gpu.hip): the distance alone against the host recipe, bit for bit; whole files against the host twin
+"""The batched build of HNSW-SlimQ's base graph on the GPU (hs_build_rabitq_hnsw_batched with a device, the BgRabitq flavour of the
+kernels of csrc/build_gpu.hip): the distance alone against the host recipe, bit for bit; whole files against the host twin
 (csrc/host_rq_batch_build.hpp); at batch_max = 1 the compiled rabitqlib's edges; against the plain-Python reading of
 tests/rq_batch_build_restated.py, never through the twin; outside the device envelope; the facade's build chain."""
 import os
@@ -116,6 +116,31 @@ def test_twice_in_a_row(hs, tmp_path):
     assert hs.build_rabitq_hnsw_batched(base, a, device=0, **kw)["used_gpu"]
     assert hs.build_rabitq_hnsw_batched(base, b, device=0, **kw)["used_gpu"]
     assert C.read(a) == C.read(b)
+
+
+@pytest.mark.parametrize("scratch_ids", [0, 8192], ids=["default", "scratch8192"])
+def test_both_builders_in_one_process(hs, tmp_path, scratch_ids):
+    """The two builders are instantiations of the same two kernels: hnswlib's build, rabitqlib's, hnswlib's again and a batched add
+    onto the first file, one after the other on one device, each against its host twin.  At scratch_ids = 8192 the on-chip search
+    kernel of either builder asks for more than 64 KiB of LDS, so each instantiation sets its own function attribute."""
+    base, extra = mixture(600, 32, 11), mixture(200, 32, 12)
+    kw = dict(M=8, ef_construction=40)
+    p = {k: str(tmp_path / f"{k}.bin") for k in ("h1", "h1_twin", "rq", "rq_twin", "h2", "add_twin")}
+    assert hs.build_hnsw_batched(base, p["h1"], device=0, scratch_ids=scratch_ids, **kw)["used_gpu"]
+    assert hs.build_rabitq_hnsw_batched(base, p["rq"], device=0, scratch_ids=scratch_ids, **kw)["used_gpu"]
+    assert hs.build_hnsw_batched(base, p["h2"], device=0, scratch_ids=scratch_ids, **kw)["used_gpu"]
+    ix = hs.Index(p["h1"], hs.HS_KIND_HNSW, 32, max_elements=800)
+    ix.seed_levels(100, 600)
+    assert ix.add_points_batched(extra, np.arange(600, 800), device=0, scratch_ids=scratch_ids)["used_gpu"]
+    added = str(tmp_path / "added.bin")
+    ix.save(added)
+    hs.build_hnsw_batched(base, p["h1_twin"], device=-1, threads=16, **kw)
+    hs.build_rabitq_hnsw_batched(base, p["rq_twin"], device=-1, threads=16, **kw)
+    hs.hnsw_resume_batched(p["h1"], p["add_twin"], extra, np.arange(600, 800), max_elements=800, seed=100, drawn=600, threads=16)
+    assert C.read(p["h1"]) == C.read(p["h1_twin"])
+    assert C.read(p["rq"]) == C.read(p["rq_twin"])
+    assert C.read(p["h2"]) == C.read(p["h1"])
+    assert C.read(added) == C.read(p["add_twin"])
 
 
 @pytest.mark.parametrize("name", ["l2_d64", "l2_d112_m32"])
