@@ -42,6 +42,8 @@ EXPORTS = [
     "hs_index_add_points_batched", "hs_hnsw_resume_batched", "hs_debug_batched_add_changed",
     "hs_build_rabitq_hnsw_batched", "hs_debug_rq_raw_dist",
     "hs_convert_slimq_graph_gpu", "hs_convert_slimq_gpu", "hs_convert_hnsw_to_slimq", "hs_debug_rq_quantize_rows",
+    "hs_build_rabitq_hnsw_batched_mem", "hs_graph_load", "hs_graph_save", "hs_graph_info", "hs_graph_free", "hs_graph_convert_slimq",
+    "hs_slimq_index_from_rows", "hs_slimq_index_save", "hs_debug_slimq_arrays", "hs_debug_slimq_arrays_host",
 ]
 
 
@@ -55,6 +57,13 @@ class HsSlimqConvertStats(ctypes.Structure):
     _fields_ = [("graph_used_gpu", ctypes.c_int), ("records_used_gpu", ctypes.c_int), ("graph_kernel_ms", ctypes.c_double),
                 ("records_kernel_ms", ctypes.c_double), ("graph_ms", ctypes.c_double), ("records_ms", ctypes.c_double),
                 ("total_ms", ctypes.c_double)]
+
+
+class HsSlimqParams(ctypes.Structure):   # hs_slimq_params
+    _fields_ = [("threshold_level", ctypes.c_int), ("top_degree_percent0", ctypes.c_float), ("top_degree_percent", ctypes.c_float),
+                ("top_degree_M0", ctypes.c_size_t), ("low_degree_m0", ctypes.c_size_t), ("top_degree_M", ctypes.c_size_t),
+                ("low_degree_m", ctypes.c_size_t), ("centroids", ctypes.c_void_p), ("num_cluster", ctypes.c_size_t),
+                ("cluster_ids", ctypes.c_void_p), ("flip_seed", ctypes.c_uint64)]
 
 
 class HsInfo(ctypes.Structure):
@@ -102,6 +111,11 @@ class HsBatchBuildOpts(ctypes.Structure):    # hs_batch_build_opts
 class HsBatchBuildStats(ctypes.Structure):   # hs_batch_build_stats
     _fields_ = [("used_gpu", _i32), ("reserved", _u32), ("batches", _u64), ("flagged_rows", _u64), ("kernel_ms", ctypes.c_double),
                 ("total_ms", ctypes.c_double)]
+
+
+class HsSlimqPipelineStats(ctypes.Structure):   # hs_slimq_pipeline_stats
+    _fields_ = [("build", HsBatchBuildStats), ("convert", HsSlimqConvertStats), ("resident_ms", ctypes.c_double),
+                ("tile_kernel_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
 
 
 class HsFastShape(ctypes.Structure):  # hs_fast_shape
@@ -245,6 +259,22 @@ def lib():
         L.hs_convert_hnsw_to_slimq.argtypes = [ctypes.c_char_p, ci, sz, ci, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, vp, sz, vp, ctypes.c_uint64,
                                                ci, ci, ctypes.c_char_p, ctypes.POINTER(HsSlimqConvertStats)]
         L.hs_debug_rq_quantize_rows.argtypes = [sz, ci, vp, vp, sz, vp, sz, vp, ci, vp, vp, vp, vp]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_graph_convert_slimq"):   # (a baseline build in an A/B run may predate these)
+        pu64, pu32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+        L.hs_build_rabitq_hnsw_batched_mem.argtypes = [vp, sz, sz, ci, sz, sz, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.POINTER(vp),
+                                                       ctypes.POINTER(HsBatchBuildStats)]
+        L.hs_graph_load.argtypes = [ctypes.c_char_p, ci, sz, ctypes.POINTER(vp)]
+        L.hs_graph_save.argtypes = [vp, ctypes.c_char_p]
+        L.hs_graph_info.argtypes = [vp, pu64, pu64, ctypes.POINTER(ci), pu64, pu64, ctypes.POINTER(ci)]
+        L.hs_graph_free.argtypes = [vp]
+        L.hs_graph_free.restype = None
+        L.hs_graph_convert_slimq.argtypes = [vp, ctypes.POINTER(HsSlimqParams), ci, ci, ctypes.c_char_p, ci, ci, ctypes.POINTER(vp),
+                                             ctypes.POINTER(HsSlimqConvertStats)]
+        L.hs_slimq_index_from_rows.argtypes = [vp, sz, sz, ci, sz, sz, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.POINTER(HsSlimqParams), ci, ci,
+                                               ctypes.POINTER(vp), ctypes.POINTER(HsSlimqPipelineStats)]
+        L.hs_slimq_index_save.argtypes = [vp, ctypes.c_char_p]
+        L.hs_debug_slimq_arrays.argtypes = [vp, ci, vp, sz, ctypes.POINTER(sz), pu32, pu32]
+        L.hs_debug_slimq_arrays_host.argtypes = [ctypes.c_char_p, ci, sz, ci, ci, vp, sz, ctypes.POINTER(sz), pu32, pu32]
     if "HS_LIB" not in os.environ or hasattr(L, "hs_slim_convert_diff"):   # (a baseline build in an A/B run may predate these)
         psz = ctypes.POINTER(sz)
         L.hs_slim_convert_diff.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, sz, sz, sz, sz, ci, ctypes.POINTER(vp), ctypes.POINTER(ci),
@@ -835,6 +865,134 @@ def convert_hnsw_to_slimq(hnsw_path, out_path, dim, centroids, metric=HS_METRIC_
     return {k: getattr(st, k) for k, _ in HsSlimqConvertStats._fields_}
 
 
+class Graph:
+    """hs_graph: an HNSW graph in host memory, what saveIndex would write (build_rabitq_hnsw_batched_mem, Graph.load)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def load(cls, path, dim, metric=HS_METRIC_L2):
+        h = ctypes.c_void_p()
+        _check(lib().hs_graph_load(path.encode(), metric, dim, ctypes.byref(h)))
+        return cls(h)
+
+    def save(self, path):
+        _check(lib().hs_graph_save(self._h, path.encode()))
+
+    def info(self):
+        n, dim, M, efc = (ctypes.c_uint64() for _ in range(4))
+        metric, maxlevel = ctypes.c_int(), ctypes.c_int()
+        _check(lib().hs_graph_info(self._h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(metric), ctypes.byref(M), ctypes.byref(efc),
+                                   ctypes.byref(maxlevel)))
+        return dict(n=n.value, dim=dim.value, metric=metric.value, M=M.value, ef_construction=efc.value, maxlevel=maxlevel.value)
+
+    def close(self):
+        if self._h:
+            lib().hs_graph_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def build_rabitq_hnsw_batched_mem(base, metric=HS_METRIC_L2, M=32, ef_construction=128, seed=100, device=-1, threads=1, grow_div=0,
+                                  batch_max=0, scratch_ids=0):
+    """hs_build_rabitq_hnsw_batched_mem: build_rabitq_hnsw_batched without its file.  Returns (Graph, stats dict); Graph.save writes the
+    bytes build_rabitq_hnsw_batched writes."""
+    base = np.ascontiguousarray(base, np.float32)
+    if base.ndim != 2:
+        raise HsError(HS_ERR_INVALID, "base: rows x dim")
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsBatchBuildStats()
+    h = ctypes.c_void_p()
+    _check(lib().hs_build_rabitq_hnsw_batched_mem(base.ctypes.data, base.shape[0], base.shape[1], metric, M, ef_construction, seed,
+                                                  ctypes.byref(opts), ctypes.byref(h), ctypes.byref(st)))
+    return Graph(h), {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows),
+                      "kernel_ms": st.kernel_ms, "total_ms": st.total_ms}
+
+
+def _slimq_params(dim, centroids, cluster_ids, flip_seed, threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0,
+                  top_degree_M, low_degree_m):
+    """(hs_slimq_params, the arrays it points into -- keep them alive for the call)"""
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1, dim)
+    cid = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, np.uint32)
+    p = HsSlimqParams(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m,
+                      c.ctypes.data, c.shape[0], None if cid is None else cid.ctypes.data, flip_seed)
+    return p, (c, cid)
+
+
+def _stats_dict(st):
+    return {k: getattr(st, k) for k, _ in type(st)._fields_}
+
+
+def _adopt_index(h, dim, metric, device):
+    ix = Index.__new__(Index)
+    ix._h = h
+    ix.kind, ix.dim, ix.metric, ix.device, ix.ef = HS_KIND_SLIMQ, dim, metric, device, 10
+    return ix
+
+
+def graph_convert_slimq(graph, centroids, out_path=None, want_index=False, with_dataset=False, convert_device=-1, index_device=0,
+                        cluster_ids=None, flip_seed=1, threshold_level=0, top_degree_percent0=0.02, top_degree_percent=0.02,
+                        top_degree_M0=32, low_degree_m0=8, top_degree_M=16, low_degree_m=4, threads=8):
+    """hs_graph_convert_slimq: convertFromHNSW of an in-memory Graph into a SlimQ file (out_path), a resident Index (want_index; its
+    fused tiles gathered on the device, with_dataset: the graph's own rows as its re-rank dataset) or both.  Returns (Index or None,
+    the stats dict of convert_hnsw_to_slimq)."""
+    gi = graph.info()
+    p, keep = _slimq_params(gi["dim"], centroids, cluster_ids, flip_seed, threshold_level, top_degree_percent0, top_degree_percent,
+                            top_degree_M0, low_degree_m0, top_degree_M, low_degree_m)
+    st = HsSlimqConvertStats()
+    h = ctypes.c_void_p()
+    _check(lib().hs_graph_convert_slimq(graph._h, ctypes.byref(p), convert_device, threads, None if out_path is None else out_path.encode(),
+                                        index_device, 1 if with_dataset else 0, ctypes.byref(h) if want_index else None, ctypes.byref(st)))
+    del keep
+    return (_adopt_index(h, gi["dim"], gi["metric"], index_device) if want_index else None), _stats_dict(st)
+
+
+def slimq_index_from_rows(base, centroids, metric=HS_METRIC_L2, M=32, ef_construction=128, seed=100, device=0, threads=8, with_dataset=True,
+                          grow_div=0, batch_max=0, scratch_ids=0, cluster_ids=None, flip_seed=1, threshold_level=0,
+                          top_degree_percent0=0.02, top_degree_percent=0.02, top_degree_M0=32, low_degree_m0=8, top_degree_M=16,
+                          low_degree_m=4):
+    """hs_slimq_index_from_rows: rows in, resident SlimQ Index out -- the batched rabitqlib build, convertFromHNSW and the tile
+    assembly on HIP device `device`, no file written or read.  Returns (Index, stats dict with 'build' and 'convert' dicts,
+    resident_ms, tile_kernel_ms, total_ms)."""
+    base = np.ascontiguousarray(base, np.float32)
+    if base.ndim != 2:
+        raise HsError(HS_ERR_INVALID, "base: rows x dim")
+    dim = base.shape[1]
+    p, keep = _slimq_params(dim, centroids, cluster_ids, flip_seed, threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0,
+                            low_degree_m0, top_degree_M, low_degree_m)
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsSlimqPipelineStats()
+    h = ctypes.c_void_p()
+    _check(lib().hs_slimq_index_from_rows(base.ctypes.data, base.shape[0], dim, metric, M, ef_construction, seed, ctypes.byref(opts),
+                                          ctypes.byref(p), threads, 1 if with_dataset else 0, ctypes.byref(h), ctypes.byref(st)))
+    del keep
+    return _adopt_index(h, dim, metric, device), dict(build=_stats_dict(st.build), convert=_stats_dict(st.convert), resident_ms=st.resident_ms,
+                                                      tile_kernel_ms=st.tile_kernel_ms, total_ms=st.total_ms)
+
+
+def debug_slimq_arrays_host(slimq_path, dim, which, metric=HS_METRIC_L2, fused=True):
+    """hs_debug_slimq_arrays_host: rec (which=0), ftile (1) or uptile (2) of a SlimQ file by the host statement of the layout alone.
+    Returns (uint32 words, stride, row_words); an array the index would not have comes back empty with stride 0."""
+    words, st, rw = ctypes.c_size_t(), ctypes.c_uint32(), ctypes.c_uint32()
+    args = (slimq_path.encode(), metric, dim, 1 if fused else 0, which)
+    _check(lib().hs_debug_slimq_arrays_host(*args, None, 0, ctypes.byref(words), ctypes.byref(st), ctypes.byref(rw)))
+    out = np.empty(words.value, np.uint32)
+    _check(lib().hs_debug_slimq_arrays_host(*args, out.ctypes.data, out.size, ctypes.byref(words), ctypes.byref(st), ctypes.byref(rw)))
+    return out, st.value, rw.value
+
+
 def debug_rq_quantize_rows(dim, metric, flips, rows, centroids, cluster_ids=None, device=-1, want_rotated=True):
     """hs_debug_rq_quantize_rows: the data-side quantiser alone on explicit flip bytes -- the host recipe (device=-1) or the kernels of
     convert_slimq_gpu.  Returns (rotated n x padded or None, cluster uint32[n], codes uint64[n x padded/64], factors float32[n x 3])."""
@@ -1236,6 +1394,19 @@ class Index:
         _check(lib().hs_slimq_search_batch(self._h, q.ctypes.data, nq, k, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data,
                                            stats.ctypes.data if want_stats else None))
         return dict(labels=labels, dists=dists, cnt=cnt, stats=stats)
+
+    def save_slimq(self, path):
+        """hs_slimq_index_save: saveIndex of the host image a resident SlimQ index keeps."""
+        _check(lib().hs_slimq_index_save(self._h, path.encode()))
+
+    def debug_slimq_arrays(self, which):
+        """hs_debug_slimq_arrays: rec (which=0), ftile (1) or uptile (2) as they lie on the device.  Returns (uint32 words, stride,
+        row_words); an array the index does not have comes back empty with stride 0."""
+        words, st, rw = ctypes.c_size_t(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().hs_debug_slimq_arrays(self._h, which, None, 0, ctypes.byref(words), ctypes.byref(st), ctypes.byref(rw)))
+        out = np.empty(words.value, np.uint32)
+        _check(lib().hs_debug_slimq_arrays(self._h, which, out.ctypes.data, out.size, ctypes.byref(words), ctypes.byref(st), ctypes.byref(rw)))
+        return out, st.value, rw.value
 
     def labels(self):
         out = np.empty(self.info()["n"], np.uint64)

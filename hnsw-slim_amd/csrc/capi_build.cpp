@@ -12,6 +12,7 @@
 #include "host_update.hpp"
 #include "rabitq_host.hpp"
 #include "slim_convert_gpu.hpp"
+#include "slimq_chain.hpp"
 
 hs_status hs_build_hnsw(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
                         const char *branching_factor, size_t seed, int threads, const char *out_path) {
@@ -254,18 +255,18 @@ hs_status hs_build_rabitq_hnsw(const float *base, size_t n, size_t dim, int metr
 
 // The same graph in the batched order: on a device the rq kernels of build_gpu.hip, otherwise -- device -1, or a
 // shape outside the device envelope -- the host twin (host_rq_batch_build.hpp); the same bytes either way.
-hs_status hs_build_rabitq_hnsw_batched(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
-                                       const hs_batch_build_opts *opts, const char *out_path, hs_batch_build_stats *stats) {
-  if (!base || !out_path || n == 0 || dim == 0) return fail(HS_ERR_INVALID, "bad argument");
+hs_status rq_batched_args_ok(const float *base, size_t n, size_t dim, int metric, size_t M, const hs_batch_build_opts *opts) {
+  if (!base || n == 0 || dim == 0) return fail(HS_ERR_INVALID, "bad argument");
   if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
   if (M < 2) return fail(HS_ERR_INVALID, "M must be >= 2");   // mult = 1 / ln M
   if (n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "too many rows");
   if (batch_opts_ok(opts) != HS_OK) return HS_ERR_INVALID;
   if (opts->device >= 0 && hs_device_count() <= opts->device) return fail(HS_ERR_DEVICE, "no HIP device");
-  const auto t0 = std::chrono::steady_clock::now();
-  hs_batch_build_stats st{};
+  return HS_OK;
+}
+hs_status rq_batched_build_into(RqGraph &g, const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
+                                const hs_batch_build_opts *opts, hs_batch_build_stats &st) {
   try {
-    RqGraph g;
     const int threads = std::max(1, (int)opts->threads);
     if (opts->device >= 0 && gpu_rq_build_supported((uint32_t)dim, (uint32_t)std::min<size_t>(M, 10000), (uint32_t)std::min<size_t>(std::max(ef_construction, M), 0xFFFFFFFFu),
                                                     (uint32_t)opts->scratch_ids)) {
@@ -287,12 +288,25 @@ hs_status hs_build_rabitq_hnsw_batched(const float *base, size_t n, size_t dim, 
       rq_batch_build_host(g, base, n, dim, (Metric)metric, M, ef_construction, seed, threads, opts->grow_div, opts->batch_max, &bs);
       st.batches = bs.batches;
     }
-    g.save(out_path);
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
   } catch (std::exception &e) {
     return from_exception(e);
   }
+  return HS_OK;
+}
+// (the in-memory form, hs_build_rabitq_hnsw_batched_mem in capi_slimq_resident.cpp, followed by hs_graph_save)
+hs_status hs_build_rabitq_hnsw_batched(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
+                                       const hs_batch_build_opts *opts, const char *out_path, hs_batch_build_stats *stats) {
+  if (!out_path) return fail(HS_ERR_INVALID, "bad argument");
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_graph *g = nullptr;
+  hs_batch_build_stats st{};
+  hs_status s = hs_build_rabitq_hnsw_batched_mem(base, n, dim, metric, M, ef_construction, seed, opts, &g, &st);
+  if (s != HS_OK) return s;
+  s = hs_graph_save(g, out_path);
+  hs_graph_free(g);
+  if (s != HS_OK) return s;
   st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (stats) *stats = st;
   return HS_OK;

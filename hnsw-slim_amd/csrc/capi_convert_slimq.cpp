@@ -7,12 +7,21 @@
 #include "host_rq_graph.hpp"
 #include "rabitq_host.hpp"
 #include "slim_convert_gpu.hpp"
+#include "slimq_chain.hpp"
 
 namespace {
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
+// what every entry below is refused for before a file is read (the refusals of hs_convert_slimq_graph / hs_convert_slimq)
+hs_status metric_ok(int metric) {
+  return metric == HS_METRIC_L2 || metric == HS_METRIC_IP ? HS_OK : fail(HS_ERR_INVALID, "bad metric");
+}
+
+}  // namespace
+
+// (the functions from here to the first entry are shared with capi_slimq_resident.cpp: slimq_chain.hpp)
 SlimParams slim_params(int threshold_level, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0,
                        size_t top_degree_M, size_t low_degree_m) {
   SlimParams p;
@@ -21,23 +30,19 @@ SlimParams slim_params(int threshold_level, float top_degree_percent0, float top
   p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
   return p;
 }
-// what every entry below is refused for before a file is read (the refusals of hs_convert_slimq_graph / hs_convert_slimq)
-hs_status metric_ok(int metric) {
-  return metric == HS_METRIC_L2 || metric == HS_METRIC_IP ? HS_OK : fail(HS_ERR_INVALID, "bad metric");
-}
-hs_status records_args_ok(int metric, size_t dim, const float *centroids, size_t num_cluster) {
+hs_status slimq_records_args_ok(int metric, size_t dim, const float *centroids, size_t num_cluster) {
   if (!centroids || num_cluster == 0) return fail(HS_ERR_INVALID, "bad argument");
   if (dim < 64 || dim >= 4096) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports 64 <= dim < 4096");
   if (num_cluster > 0xFFFFFFFFull) return fail(HS_ERR_INVALID, "too many clusters");
   return metric_ok(metric);
 }
-hs_status device_ok(int device) {
+hs_status slimq_device_ok(int device) {
   if (device < 0) return fail(HS_ERR_INVALID, "device: a HIP device");
   return hs_device_count() <= device ? fail(HS_ERR_DEVICE, "no HIP device") : HS_OK;
 }
 
 // The graph passes into `s`: on `device`, or on the host when device < 0 or the shape is outside the device path.
-hs_status graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms) {
+hs_status slimq_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms) {
   bool ok = false;
   double ms = 0.0;
   if (device >= 0) {
@@ -51,7 +56,7 @@ hs_status graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, i
   return HS_OK;
 }
 // The records of `s` into `q` (SlimQGraph::from_slim): on `device`, or on the host when device < 0.
-hs_status records_step(SlimQGraph &q, const SlimGraph &s, int metric, const float *centroids, size_t num_cluster, const uint32_t *cluster_ids,
+hs_status slimq_records_step(SlimQGraph &q, const SlimGraph &s, int metric, const float *centroids, size_t num_cluster, const uint32_t *cluster_ids,
                        uint64_t flip_seed, int device, int threads, int *used_gpu, double *kernel_ms) {
   if (cluster_ids)
     for (size_t i = 0; i < s.count; i++)
@@ -72,20 +77,18 @@ hs_status records_step(SlimQGraph &q, const SlimGraph &s, int metric, const floa
   return HS_OK;
 }
 
-}  // namespace
-
 hs_status hs_convert_slimq_graph_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
                                      float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
                                      size_t low_degree_m, int device, int threads, const char *out_path, int *used_gpu, double *kernel_ms) {
   if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
   hs_status st = metric_ok(metric);
-  if (st == HS_OK) st = device_ok(device);
+  if (st == HS_OK) st = slimq_device_ok(device);
   if (st != HS_OK) return st;
   try {
     VanillaGraph g;
     g.load(hnsw_path, (Metric)metric, dim);
     SlimGraph s;
-    st = graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
+    st = slimq_graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
                     device, threads, used_gpu, kernel_ms);
     if (st != HS_OK) return st;
     s.save(out_path);
@@ -101,14 +104,14 @@ hs_status hs_convert_slimq_gpu(const char *slim_path, int metric, size_t dim, co
                                const uint32_t *cluster_ids, uint64_t flip_seed, int device, int threads, const char *out_path, int *used_gpu,
                                double *kernel_ms) {
   if (!slim_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
-  hs_status st = records_args_ok(metric, dim, centroids, num_cluster);
-  if (st == HS_OK) st = device_ok(device);
+  hs_status st = slimq_records_args_ok(metric, dim, centroids, num_cluster);
+  if (st == HS_OK) st = slimq_device_ok(device);
   if (st != HS_OK) return st;
   try {
     SlimGraph s;
     s.load(slim_path, (Metric)metric, dim);
     SlimQGraph q;
-    st = records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, used_gpu, kernel_ms);
+    st = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, used_gpu, kernel_ms);
     if (st != HS_OK) return st;
     q.save(out_path);
   } catch (std::bad_alloc &) {
@@ -124,10 +127,10 @@ hs_status hs_convert_hnsw_to_slimq(const char *hnsw_path, int metric, size_t dim
                                    size_t low_degree_m, const float *centroids, size_t num_cluster, const uint32_t *cluster_ids,
                                    uint64_t flip_seed, int device, int threads, const char *out_path, hs_slimq_convert_stats *stats) {
   if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
-  hs_status st = records_args_ok(metric, dim, centroids, num_cluster);
+  hs_status st = slimq_records_args_ok(metric, dim, centroids, num_cluster);
   if (st != HS_OK) return st;
   if (device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host path) or a HIP device");
-  if (device >= 0 && (st = device_ok(device)) != HS_OK) return st;
+  if (device >= 0 && (st = slimq_device_ok(device)) != HS_OK) return st;
   const auto t0 = std::chrono::steady_clock::now();
   hs_slimq_convert_stats out{};
   try {
@@ -135,14 +138,14 @@ hs_status hs_convert_hnsw_to_slimq(const char *hnsw_path, int metric, size_t dim
     {
       VanillaGraph g;
       g.load(hnsw_path, (Metric)metric, dim);
-      st = graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
+      st = slimq_graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
                       device, threads, &out.graph_used_gpu, &out.graph_kernel_ms);
       if (st != HS_OK) return st;
     }
     out.graph_ms = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     SlimQGraph q;
-    st = records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, &out.records_used_gpu, &out.records_kernel_ms);
+    st = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, &out.records_used_gpu, &out.records_kernel_ms);
     if (st != HS_OK) return st;
     out.records_ms = ms_since(t1);
     q.save(out_path);
@@ -160,14 +163,14 @@ hs_status hs_debug_rq_quantize_rows(size_t dim, int metric, const uint8_t *flips
                                     size_t num_cluster, const uint32_t *cluster_ids, int device, float *out_rotated, uint32_t *out_cluster,
                                     uint64_t *out_codes, float *out_factors) {
   if (!flips || !rows || !out_cluster || !out_codes || !out_factors) return fail(HS_ERR_INVALID, "bad argument");
-  hs_status st = records_args_ok(metric, dim, centroids_raw, num_cluster);
+  hs_status st = slimq_records_args_ok(metric, dim, centroids_raw, num_cluster);
   if (st != HS_OK) return st;
   if (device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host recipe) or a HIP device");
   if (n > 0xFFFFFFFFull) return fail(HS_ERR_INVALID, "too many rows");
   if (cluster_ids)
     for (size_t i = 0; i < n; i++)
       if (cluster_ids[i] >= num_cluster) return fail(HS_ERR_INVALID, "cluster id out of range");
-  if (device >= 0 && (st = device_ok(device)) != HS_OK) return st;
+  if (device >= 0 && (st = slimq_device_ok(device)) != HS_OK) return st;
   try {
     Rotator rot;
     rot.init(dim);

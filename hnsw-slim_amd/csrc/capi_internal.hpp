@@ -20,6 +20,7 @@
 #include "narrow_rows.hpp"
 #include "host_graph.hpp"
 #include "packed_index.hpp"
+#include "rabitq_host.hpp"
 #include "search_plan.hpp"
 #include "slim_diff.hpp"
 #include "slimq_engine.hpp"
@@ -140,6 +141,9 @@ struct hs_index {
   DevSlimQ sq{};
   bool has_dataset = false;
   uint32_t *trace_ptr = nullptr;   // hs_slimq_trace only
+  // the file image a SlimQ index was made resident from (codes, factors, blobs, labels; no fp32 rows): hs_slimq_index_save writes it
+  std::unique_ptr<SlimQGraph> host_slimq;
+  double resident_ms = 0.0, tile_kernel_ms = 0.0;   // slimq_make_resident: the whole call; its three tile kernels
   uint32_t trace_cap = 0;
 };
 
@@ -187,6 +191,11 @@ std::string unfit_message(size_t row, size_t comp, float v, int fmt);
 hs_status batch_opts_ok(const hs_batch_build_opts *opts);
 // capi_slimq.cpp
 hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, hs_index **out);
+// The one way a SlimQ index becomes resident: the packed graph uploaded, the record fields uploaded as they lie in `q`, records and
+// fused tiles gathered by slimq_tiles.hip; the index keeps `q` as its host image.  hs_index_load of a SlimQ file ends here too.
+hs_status slimq_make_resident(std::unique_ptr<SlimQGraph> q, int device, hs_index **out);
+// hs_slimq_set_dataset with the rows `pitch` bytes apart (the rows of a graph image lie inside its elements)
+hs_status slimq_set_dataset_pitched(hs_index *ix, const void *rows, size_t pitch, size_t n, size_t dim);
 // capi_search.cpp
 hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k, int mode, uint32_t *l32, uint64_t *l64, float *dd,
                      uint32_t *cnt, uint32_t *stats, Pair *raw, uint32_t *rawsz, hipStream_t stream, const FilterUse *fu = nullptr);

@@ -2,8 +2,11 @@
 // host-side RaBitQ exports.
 #include "capi_internal.hpp"
 
+#include <chrono>
+
 #include "rabitq_est.hpp"
 #include "rabitq_host.hpp"
+#include "slimq_tiles.hpp"
 
 static uint32_t next_pow2(uint32_t v) {
   uint32_t p = 1;
@@ -11,97 +14,91 @@ static uint32_t next_pow2(uint32_t v) {
   return p;
 }
 
-// HierarchicalNSWSlimQ::loadIndex (hnswalg_slimq.h:1218-1313): graph -> CSR/tiles, element records -> 16-byte header
-// {f_add, f_rescale, cluster id, f_error} + sign code, rotated centroids and rotator flips as they are.
+// The packed graph of a SlimQ file image: CSR of the CHAL blobs, labels, the header's fields (no rows: they come with setDataset).
+static void pack_slimq(PackedIndex &p, const SlimQGraph &q) {
+  p.kind = HS_KIND_SLIMQ; p.metric = (Metric)q.metric; p.n = q.count; p.dim = q.dim;
+  p.maxlevel = q.maxlevel; p.threshold_level = q.threshold_level; p.enterpoint = q.enterpoint;
+  p.index_size = q.count * 20;   // HierarchicalNSWSlimQ::indexSize() (hnswalg_slimq.h:2047-2057): 20 B per element + blobs
+  for (size_t i = 0; i < q.count; i++) p.index_size += 2 * (size_t)q.level[i] + 4 * (size_t)q.total(i);
+  p.labels = q.label;
+  p.deleted.assign(q.count, 0);
+  p.pack_chal([&](size_t i) { return (int)q.level[i]; }, [&](size_t i) { return (size_t)q.total(i); },
+              [&](size_t i) -> const std::vector<char> & { return q.blobs[i]; });
+}
+
+// HierarchicalNSWSlimQ::loadIndex (hnswalg_slimq.h:1218-1313): the file parse, then the one way to residency.
 hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, hs_index **out) {
-  SlimQGraph q;
+  std::unique_ptr<SlimQGraph> q(new SlimQGraph());
+  try {
+    q->load(src, metric, dim);
+  } catch (std::bad_alloc &) {
+    return fail(HS_ERR_NOMEM, "Not enough memory: loadIndex failed to allocate");
+  } catch (std::exception &e) {
+    return from_exception(e);
+  }
+  return slimq_make_resident(std::move(q), device, out);
+}
+
+// graph -> CSR/tiles (upload), element records -> 16-byte header {f_add, f_rescale, cluster id, f_error} + sign code, the fused
+// level-0 and upper-level tiles (slimq_tiles.hip, layout in slimq_engine.hpp / slimq_tiles.hpp), rotated centroids and rotator flips
+// as they are.  The record fields go up as they lie in the image and are freed once the kernels have read them.
+hs_status slimq_make_resident(std::unique_ptr<SlimQGraph> qp, int device, hs_index **out) {
+  if (!qp || !out) return fail(HS_ERR_INVALID, "null argument");
+  if (hs_device_count() <= device || device < 0) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
+  const auto t0 = std::chrono::steady_clock::now();
+  const SlimQGraph &q = *qp;
   PackedIndex p;
   try {
-    q.load(src, metric, dim);
     if (q.rot.trunc < 64) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports dim >= 64");
-    p.kind = HS_KIND_SLIMQ; p.metric = (Metric)metric; p.n = q.count; p.dim = dim;
-    p.maxlevel = q.maxlevel; p.threshold_level = q.threshold_level; p.enterpoint = q.enterpoint;
-    p.index_size = q.count * 20;   // HierarchicalNSWSlimQ::indexSize() (hnswalg_slimq.h:2047-2057): 20 B per element + blobs
-    for (size_t i = 0; i < q.count; i++) p.index_size += 2 * (size_t)q.level[i] + 4 * (size_t)q.total(i);
-    p.labels = q.label;
-    p.deleted.assign(q.count, 0);
-    p.pack_chal([&](size_t i) { return (int)q.level[i]; }, [&](size_t i) { return (size_t)q.total(i); },
-                [&](size_t i) -> const std::vector<char> & { return q.blobs[i]; });
+    pack_slimq(p, q);
     if (q.count && q.enterpoint >= q.count) return fail(HS_ERR_CORRUPT, "Index seems to be corrupted or unsupported");
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory: loadIndex failed to allocate");
   } catch (std::exception &e) {
     return from_exception(e);
   }
-  hs_index *ix = new hs_index();
+  if (q.count > 0xFFFFFFF0ull || p.up_ptr.size() > 0xFFFFFFF0ull) return fail(HS_ERR_UNSUPPORTED, "SlimQ index too large");
+  std::unique_ptr<hs_index> ix(new hs_index());
   ix->device = device;
-  hs_status s = upload(ix, p);
-  if (s != HS_OK) { delete ix; return s; }
-  const uint32_t nblk = (uint32_t)(q.padded / 64), rw = (4 + 2 * nblk + 3) & ~3u;  // 16-byte multiple
-  std::vector<uint32_t> rec((size_t)q.count * rw);
-  for (size_t i = 0; i < q.count; i++) {
-    uint32_t *r = &rec[i * rw];
-    memcpy(r, &q.factors[i * 3], 4); memcpy(r + 1, &q.factors[i * 3 + 1], 4);
-    r[2] = q.cluster[i];
-    memcpy(r + 3, &q.factors[i * 3 + 2], 4);
-    memcpy(r + 4, &q.code[i * nblk], 8 * nblk);
-  }
+  hs_status s = upload(ix.get(), p);
+  if (s != HS_OK) return s;
+  const uint32_t n = (uint32_t)q.count, rw = slimq_rec_words(q.padded);
   // fused level-0 tiles (see slimq_engine.hpp): 288 GB of HBM buys one dependent access per expansion.
   // HS_SLIMQ_FUSED=0 (debug/test knob) keeps the CSR + record-array layout that wide graphs (degree > 64) fall back to.
   const bool fused = diag_from_env().slimq_fused != 0;   // (read at every load, not once per process)
   const uint32_t stride = fused ? ix->dev.tile_stride : 0;
-  std::vector<uint32_t> ft;
-  if (stride) {
-    ft.assign((size_t)q.count * stride * rw, 0u);
-    for (size_t i = 0; i < q.count; i++) {
-      uint32_t *row = &ft[i * stride * rw];
-      const uint32_t deg = p.row_ptr0[i + 1] - p.row_ptr0[i];
-      for (uint32_t j = 0; j < stride; j++) {
-        uint32_t *r = row + (size_t)j * rw;
-        if (j < deg) {
-          const uint32_t nb = p.cols[p.row_ptr0[i] + j];
-          memcpy(r, &rec[(size_t)nb * rw], 4 * rw);
-          r[3] = nb;
-        } else {
-          r[3] = 0xFFFFFFFFu;
-        }
-      }
-    }
-  }
   // fused upper-level tiles: slot up_base[i] + l - 1 holds level l of node i
-  uint32_t up_stride = 0;
-  std::vector<uint32_t> ut;
+  const uint32_t up_stride = fused ? slimq_up_stride(p.up_ptr) : 0;
+  const size_t rec_words = (size_t)n * rw, ft_words = (size_t)n * stride * rw, ut_words = up_stride ? p.up_ptr.size() * (size_t)up_stride * (rw + 4) : 0;
   {
-    size_t max_up = 0;
-    for (size_t t = 0; t + 1 < p.up_ptr.size(); t++) max_up = std::max<size_t>(max_up, p.up_ptr[t + 1] >= p.up_ptr[t] ? p.up_ptr[t + 1] - p.up_ptr[t] : 0);
-    if (fused && !p.up_ptr.empty() && max_up <= 64) {
-      up_stride = std::max<uint32_t>(16, (uint32_t)((max_up + 15) / 16 * 16));
-      const uint32_t urw = rw + 4;
-      ut.assign(p.up_ptr.size() * (size_t)up_stride * urw, 0u);
-      for (size_t t = 0; t < p.up_ptr.size(); t++)
-        for (uint32_t j = 0; j < up_stride; j++) ut[(t * up_stride + j) * urw + 3] = 0xFFFFFFFFu;
-      for (size_t i = 0; i < q.count; i++) {
-        const uint32_t b = p.up_base[i];
-        if (b == PackedIndex::NONE) continue;
-        for (int l = 1; l <= q.level[i]; l++) {
-          const uint32_t s0 = p.up_ptr[b + l - 1], e0 = p.up_ptr[b + l];
-          for (uint32_t j = 0; j < e0 - s0; j++) {
-            const uint32_t nb = p.cols[s0 + j];
-            uint32_t *r = &ut[((size_t)(b + l - 1) * up_stride + j) * urw];
-            memcpy(r, &rec[(size_t)nb * rw], 4 * rw);
-            r[3] = nb;
-            r[rw] = p.up_base[nb];
-          }
-        }
-      }
-    }
+    DevBuf<float> d_fac;
+    DevBuf<uint32_t> d_cl;
+    DevBuf<uint64_t> d_code;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t e = d_fac.upload(q.factors);
+    if (e == hipSuccess) e = d_cl.upload(q.cluster);
+    if (e == hipSuccess) e = d_code.upload(q.code);
+    if (e == hipSuccess) e = ix->q_rec.alloc(std::max<size_t>(rec_words, 1));
+    if (e == hipSuccess && up_stride) e = ix->q_uptile.alloc(ut_words);
+    if (e == hipSuccess && stride) e = ix->q_ftile.alloc(std::max<size_t>(ft_words, 1));
+    if (e == hipSuccess) e = ix->q_cent.upload(q.centroids);
+    if (e == hipSuccess) e = ix->q_flips.upload(q.rot.flip);
+    if (e == hipSuccess) e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, nullptr);
+    if (e == hipSuccess) e = launch_slimq_records(d_fac.p, d_cl.p, d_code.p, n, (uint32_t)q.padded, ix->q_rec.p, nullptr);
+    if (e == hipSuccess && stride) e = launch_slimq_ftile(ix->q_rec.p, ix->tile0.p, n, stride, rw, ix->q_ftile.p, nullptr);
+    if (e == hipSuccess && up_stride)
+      e = launch_slimq_uptile(ix->q_rec.p, ix->up_ptr.p, (uint32_t)p.up_ptr.size(), ix->cols.p, ix->up_base.p, n, up_stride, rw, ix->q_uptile.p, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev1, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev1);   // the staging arrays are freed below: the kernels must have read them
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("SlimQ upload: ") + hipGetErrorString(e));
+    ix->tile_kernel_ms = ms;
   }
-  hipError_t e = ix->q_rec.upload(rec);
-  if (e == hipSuccess && up_stride) e = ix->q_uptile.upload(ut);
-  if (e == hipSuccess && stride) e = ix->q_ftile.upload(ft);
-  if (e == hipSuccess) e = ix->q_cent.upload(q.centroids);
-  if (e == hipSuccess) e = ix->q_flips.upload(q.rot.flip);
-  if (e != hipSuccess) { delete ix; return fail(HS_ERR_DEVICE, std::string("SlimQ upload: ") + hipGetErrorString(e)); }
   DevSlimQ &d = ix->sq;
   d.rec = ix->q_rec.p; d.ftile = stride ? ix->q_ftile.p : nullptr; d.raw = nullptr;
   d.uptile = up_stride ? ix->q_uptile.p : nullptr; d.up_stride = up_stride;
@@ -109,26 +106,32 @@ hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, h
   d.rec_words = rw; d.padded = (uint32_t)q.padded; d.trunc = (uint32_t)q.rot.trunc; d.ncl = (uint32_t)q.num_cluster;
   d.fht_scale = q.rot.fac;
   d.t_const = rq_default_tconst(q.padded, 1);
-  ix->base_bytes += (rec.size() + ft.size() + ut.size()) * 4 + q.centroids.size() * 4 + q.rot.flip.size();
-  refresh_device_bytes(ix);
-  *out = ix;
+  ix->base_bytes += (rec_words + ft_words + ut_words) * 4 + q.centroids.size() * 4 + q.rot.flip.size();
+  refresh_device_bytes(ix.get());
+  ix->host_slimq = std::move(qp);
+  ix->resident_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  *out = ix.release();
   return HS_OK;
 }
 
 // ---- HNSW-SlimQ ------------------------------------------------------------------------------------------------
-hs_status hs_slimq_set_dataset(hs_index *ix, const float *base, size_t n, size_t dim) {
-  if (!ix || !base) return fail(HS_ERR_INVALID, "null argument");
+hs_status slimq_set_dataset_pitched(hs_index *ix, const void *rows, size_t pitch, size_t n, size_t dim) {
+  if (!ix || !rows) return fail(HS_ERR_INVALID, "null argument");
   if (ix->info.kind != HS_KIND_SLIMQ) return fail(HS_ERR_INVALID, "not a SlimQ index");
   if (n != ix->info.n || dim != ix->info.dim) return fail(HS_ERR_INVALID, "dataset shape does not match the index");
   HIP_TRY(hipSetDevice(ix->device));
   HIP_TRY(ix->vec.alloc(std::max<size_t>(n * dim, 1)));
-  HIP_TRY(hipMemcpy(ix->vec.p, base, n * dim * sizeof(float), hipMemcpyHostToDevice));
+  if (pitch == dim * sizeof(float)) HIP_TRY(hipMemcpy(ix->vec.p, rows, n * dim * sizeof(float), hipMemcpyHostToDevice));
+  else if (n) HIP_TRY(hipMemcpy2D(ix->vec.p, dim * sizeof(float), rows, pitch, dim * sizeof(float), n, hipMemcpyHostToDevice));
   ix->dev.vec = ix->vec.p;
   ix->sq.raw = ix->vec.p;
   ix->has_dataset = true;
   ix->base_bytes += n * dim * 4;
   refresh_device_bytes(ix);
   return HS_OK;
+}
+hs_status hs_slimq_set_dataset(hs_index *ix, const float *base, size_t n, size_t dim) {
+  return slimq_set_dataset_pitched(ix, base, dim * sizeof(float), n, dim);
 }
 hs_status hs_slimq_set_tconst(hs_index *ix, double t_const) {
   if (!ix || !(t_const > 0)) return fail(HS_ERR_INVALID, "bad argument");

@@ -52,6 +52,15 @@ hipError_t launch_slimq_prep(const DevSlimQ &sq, uint32_t dim, int metric, const
                              float *dbg_y, hipStream_t stream);
 size_t slimq_lds_bytes(uint32_t dim, uint32_t padded, uint32_t ncl, uint32_t k, uint32_t hash_slots);
 bool slimq_supported(uint32_t pool_cap);
+// slimq_tiles.hip: rec / ftile / uptile above written on the device, word for word slimq_tiles.hpp's host functions.  All pointers
+// are device arrays; factors n x 3, cluster n, code n x padded/64 as SlimQGraph holds them; tile0 / up_ptr / cols / up_base as
+// upload() left them (`entries` = the length of up_ptr).  Every word of the output is written.  stride, up_stride <= 64.
+hipError_t launch_slimq_records(const float *factors, const uint32_t *cluster, const uint64_t *code, uint32_t n, uint32_t padded, uint32_t *rec,
+                                hipStream_t stream);
+hipError_t launch_slimq_ftile(const uint32_t *rec, const uint32_t *tile0, uint32_t n, uint32_t stride, uint32_t rw, uint32_t *ftile,
+                              hipStream_t stream);
+hipError_t launch_slimq_uptile(const uint32_t *rec, const uint32_t *up_ptr, uint32_t entries, const uint32_t *cols, const uint32_t *up_base,
+                               uint32_t n, uint32_t up_stride, uint32_t rw, uint32_t *uptile, hipStream_t stream);
 hipError_t launch_slimq(const DevIndex &ix, const DevSlimQ &sq, const SlimQArgs &a, hipStream_t stream);
 
 }  // namespace hs

@@ -218,6 +218,17 @@ class DeviceIndex {
     if (row_fmt_ != HS_ROWS_F32) setRowFormat(row_fmt_);
     if (!f32_resident_) setF32Resident(false);
   }
+  // an index made resident without a file (hs_graph_convert_slimq): this object owns it from here on; path() stays empty
+  void adopt(hs_index *h, SpaceInterface<float> *s) {
+    drop_filter_cache();
+    hs_index_free(h_);
+    free_replicas();
+    h_ = h;
+    metric_ = metric_of(s);
+    dim_ = dim_of(s);
+    path_.clear();
+    ef_ = 10;
+  }
   // searchKnn(q, k, isIdAllowed): the functor's answers are cached as a ONE-ROW filter set on the device (hs_filter_set_*), so the
   // second and later calls with the same functor evaluate nothing and upload nothing.  The cache belongs to (functor, loaded index):
   // dropped when the index is reloaded, and when its element count is no longer the one the set was created for (hs_index_patch on
@@ -741,8 +752,9 @@ class BruteforceSearch<float> : public AlgorithmInterface<float> {
 // the raw rows, and keeps the centroid and cluster arguments for HierarchicalNSWSlimQ::convertFromHNSW, which writes the RaBitQ
 // records; total_bits and faster_quant are accepted and not used.  save() writes the graph in hnswlib's saveIndex layout, the file
 // the converters read.  setBuildOnDevice(device, batch_max) (no counterpart in the reference) moves construct() to the batched
-// build on that HIP device (hs_build_rabitq_hnsw_batched); without it construct() is hs_build_rabitq_hnsw on
-// num_threads host threads (0: all of them; 1: the reference's serial construct(), edge for edge).
+// build on that HIP device (hs_build_rabitq_hnsw_batched_mem) and keeps the graph in memory (an hs_graph): save()
+// writes it, and a file exists only once someone asks for graphPath(); without it construct() is hs_build_rabitq_hnsw on
+// num_threads host threads (0: all of them; 1: the reference's serial construct(), edge for edge) into a temporary file.
 namespace rabitqlib {
 enum MetricType : std::uint8_t { METRIC_L2, METRIC_IP };
 using PID = uint32_t;
@@ -753,7 +765,8 @@ class HierarchicalNSW {
   int build_device_ = -1;
   size_t build_batch_max_ = 0;
   hs_batch_build_stats build_stats_{};
-  std::string tmp_path_;                // the graph construct() built
+  mutable std::string tmp_path_;        // the graph construct() built, where it lies in a file
+  hs_graph *graph_ = nullptr;           // ... and where it lies in memory (setBuildOnDevice)
   std::vector<float> centroids_;
   std::vector<PID> cluster_ids_;
   size_t num_clusters_ = 0;
@@ -764,19 +777,20 @@ class HierarchicalNSW {
       : n_(num_points), dim_(dim), M_(M), efc_(ef_construction), seed_(random_seed), metric_(metric_type == METRIC_IP ? HS_METRIC_IP : HS_METRIC_L2) {}
   HierarchicalNSW(const HierarchicalNSW &) = delete;
   HierarchicalNSW &operator=(const HierarchicalNSW &) = delete;
-  ~HierarchicalNSW() { if (!tmp_path_.empty()) unlink(tmp_path_.c_str()); }
+  ~HierarchicalNSW() {
+    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
+    hs_graph_free(graph_);
+  }
   void setBuildOnDevice(int device, size_t batch_max = 0) { build_device_ = device < 0 ? -1 : device; build_batch_max_ = batch_max; }
   const hs_batch_build_stats &buildStats() const { return build_stats_; }   // of the last construct() that went through setBuildOnDevice
   void construct(size_t num_clusters, const float *centroids, size_t num_points, const float *data, const PID *cluster_ids, size_t num_threads = 0,
                  bool /*faster_quant*/ = false) {
     if (num_points != n_) throw std::runtime_error("hnswlib_amd: construct() with another number of points than the constructor's");
     if (!data) throw std::runtime_error("hnswlib_amd: construct() without rows");
-    char tmpl[] = "/tmp/hnswlib_amd_rq_XXXXXX";
-    const int fd = mkstemp(tmpl);
-    if (fd < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
-    close(fd);
     if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
-    tmp_path_ = tmpl;
+    tmp_path_.clear();
+    hs_graph_free(graph_);
+    graph_ = nullptr;
     const int threads = num_threads ? (int)num_threads : (int)std::max(1u, std::thread::hardware_concurrency());
     build_stats_ = hs_batch_build_stats{};
     if (build_device_ >= 0) {
@@ -784,9 +798,11 @@ class HierarchicalNSW {
       o.device = build_device_;
       o.threads = threads;
       o.batch_max = build_batch_max_;
-      hnswlib::detail::check(hs_build_rabitq_hnsw_batched(data, n_, dim_, metric_, M_, efc_, seed_, &o, tmpl, &build_stats_));
+      hnswlib::detail::check(hs_build_rabitq_hnsw_batched_mem(data, n_, dim_, metric_, M_, efc_, seed_, &o, &graph_, &build_stats_));
     } else {
-      hnswlib::detail::check(hs_build_rabitq_hnsw(data, n_, dim_, metric_, M_, efc_, seed_, threads, tmpl));
+      const std::string tmpl = temp_file();
+      tmp_path_ = tmpl;
+      hnswlib::detail::check(hs_build_rabitq_hnsw(data, n_, dim_, metric_, M_, efc_, seed_, threads, tmpl.c_str()));
     }
     num_clusters_ = num_clusters;
     centroids_.assign(centroids, centroids + (centroids ? num_clusters * dim_ : 0));
@@ -794,19 +810,39 @@ class HierarchicalNSW {
   }
   // save (hnsw.hpp:506-560 writes rabitqlib's own layout; here: the saveIndex layout every converter of this library reads)
   void save(const char *path) const {
+    if (graph_) { hnswlib::detail::check(hs_graph_save(graph_, path)); return; }
     if (tmp_path_.empty()) throw std::runtime_error("hnswlib_amd: save() before construct()");
     std::ifstream in(tmp_path_, std::ios::binary);
     std::ofstream out(path, std::ios::binary);
     out << in.rdbuf();
     if (!in || !out) throw std::runtime_error("Cannot open file");
   }
-  // what convertFromHNSW reads
-  const std::string &graphPath() const { return tmp_path_; }
+  bool constructed() const { return graph_ || !tmp_path_.empty(); }
+  const hs_graph *graph() const { return graph_; }              // the graph in memory (null unless setBuildOnDevice built it)
+  const std::string &tempFile() const { return tmp_path_; }     // the temporary file this object holds, "" when it holds none
+  // the graph as a file, for the converters that read one: a graph held in memory is written to a temporary file on first demand
+  const std::string &graphPath() const {
+    if (tmp_path_.empty() && graph_) {
+      const std::string tmpl = temp_file();
+      tmp_path_ = tmpl;
+      hnswlib::detail::check(hs_graph_save(graph_, tmpl.c_str()));
+    }
+    return tmp_path_;
+  }
   size_t dim() const { return dim_; }
   int metric() const { return metric_; }
   size_t numClusters() const { return num_clusters_; }
   const float *centroids() const { return centroids_.empty() ? nullptr : centroids_.data(); }
   const PID *clusterIds() const { return cluster_ids_.empty() ? nullptr : cluster_ids_.data(); }
+
+ private:
+  static std::string temp_file() {
+    char tmpl[] = "/tmp/hnswlib_amd_rq_XXXXXX";
+    const int fd = mkstemp(tmpl);
+    if (fd < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
+    close(fd);
+    return tmpl;
+  }
 };
 }  // namespace hnsw
 }  // namespace rabitqlib
@@ -825,16 +861,19 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   int thr_ = 0;                          // hnswalg_slimq.h's constructor defaults
   float p0_ = 0.02f, p_ = 0.02f;
   size_t M0h_ = 32, m0l_ = 8, Mh_ = 16, ml_ = 4;
-  std::string tmp_path_;                 // the SlimQ file convertFromHNSW wrote
+  std::string tmp_path_;                 // the SlimQ file convertFromHNSW wrote (host path)
+  bool from_graph_ = false;              // convertFromHNSW made the index resident without a file (setBuildOnDevice)
   int convert_device_ = -1;
   hs_slimq_convert_stats convert_stats_{};
 
  public:
   explicit HierarchicalNSWSlimQ(SpaceInterface<float> *s) : space_(s) {}
-  // (no counterpart in the reference) convertFromHNSW on that HIP device: both steps in one call with no file between them
-  // (hs_convert_hnsw_to_slimq); the index it leaves is byte for byte the one the two host calls leave.
+  // (no counterpart in the reference) convertFromHNSW on that HIP device: both steps and the index's tiles there, no file written
+  // or read (hs_graph_convert_slimq); the index it leaves is word for word the one the two host calls and a
+  // load leave, and saveIndex writes their file from the index's host image.
   void setBuildOnDevice(int device) { convert_device_ = device < 0 ? -1 : device; }
   const hs_slimq_convert_stats &convertStats() const { return convert_stats_; }   // of the last convertFromHNSW that went through setBuildOnDevice
+  const std::string &tempFile() const { return tmp_path_; }   // the temporary file this object holds, "" when it holds none
   HierarchicalNSWSlimQ(SpaceInterface<float> *s, size_t /*max_elements*/, size_t /*M*/ = 16, size_t /*ef_construction*/ = 200, int threshold_level = 0,
                        float top_degree_percent0 = 0.02f, float top_degree_percent = 0.02f, size_t top_degree_M0 = 32, size_t low_degree_m0 = 8,
                        size_t top_degree_M = 16, size_t low_degree_m = 4)
@@ -845,24 +884,34 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   // RaBitQ records with the centroids and cluster ids construct() was given (hs_convert_slimq), then the result is loaded.  After
   // setBuildOnDevice: the same two steps on that device, chained in memory.
   void convertFromHNSW(rabitqlib::hnsw::HierarchicalNSW *hnsw, int threads = 8, uint64_t flip_seed = 1) {
-    if (!hnsw || hnsw->graphPath().empty()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs a constructed rabitqlib index");
+    if (!hnsw || !hnsw->constructed()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs a constructed rabitqlib index");
     if (!space_) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs the space the index was constructed with");
     if (!hnsw->centroids()) throw std::runtime_error("hnswlib_amd: convertFromHNSW needs the centroids construct() was given");
+    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
+    tmp_path_.clear();
+    convert_stats_ = hs_slimq_convert_stats{};
+    if (convert_device_ >= 0) {   // in memory all the way: the graph handle (read from the file of a host-built graph), a resident index
+      hs_graph *loaded = nullptr;
+      if (!hnsw->graph()) detail::check(hs_graph_load(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), &loaded));
+      hs_slimq_params p{};
+      p.threshold_level = thr_; p.top_degree_percent0 = p0_; p.top_degree_percent = p_;
+      p.top_degree_M0 = M0h_; p.low_degree_m0 = m0l_; p.top_degree_M = Mh_; p.low_degree_m = ml_;
+      p.centroids = hnsw->centroids(); p.num_cluster = hnsw->numClusters(); p.cluster_ids = hnsw->clusterIds(); p.flip_seed = flip_seed;
+      hs_index *ix = nullptr;
+      const hs_status s = hs_graph_convert_slimq(loaded ? loaded : hnsw->graph(), &p, convert_device_, threads, nullptr, device_, 0, &ix, &convert_stats_);
+      hs_graph_free(loaded);
+      detail::check(s);
+      adopt(ix, space_);
+      from_graph_ = true;
+      return;
+    }
+    from_graph_ = false;
     char slim[] = "/tmp/hnswlib_amd_rqslim_XXXXXX", slimq[] = "/tmp/hnswlib_amd_slimq_XXXXXX";
     const int fd = mkstemp(slim), fq = mkstemp(slimq);
     if (fd >= 0) close(fd);
     if (fq >= 0) close(fq);
     if (fd < 0 || fq < 0) throw std::runtime_error("hnswlib_amd: cannot create a temporary index file");
-    if (!tmp_path_.empty()) unlink(tmp_path_.c_str());
     tmp_path_ = slimq;
-    convert_stats_ = hs_slimq_convert_stats{};
-    if (convert_device_ >= 0) {
-      unlink(slim);
-      detail::check(hs_convert_hnsw_to_slimq(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), thr_, p0_, p_, M0h_, m0l_, Mh_, ml_, hnsw->centroids(),
-                                             hnsw->numClusters(), hnsw->clusterIds(), flip_seed, convert_device_, threads, slimq, &convert_stats_));
-      loadIndex(slimq, space_);
-      return;
-    }
     hs_status s = hs_convert_slimq_graph(hnsw->graphPath().c_str(), hnsw->metric(), hnsw->dim(), thr_, p0_, p_, M0h_, m0l_, Mh_, ml_, threads, slim);
     if (s == HS_OK)
       s = hs_convert_slimq(slim, hnsw->metric(), hnsw->dim(), hnsw->centroids(), hnsw->numClusters(), hnsw->clusterIds(), flip_seed, threads, slimq);
@@ -876,6 +925,7 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   }
   void loadIndex(const std::string &location, SpaceInterface<float> *s, size_t max_elements_i = 0) {
     space_ = s;
+    from_graph_ = false;
     load(location, HS_KIND_SLIMQ, s, max_elements_i);
   }
   // setDataset (hnswalg_slimq.h:303-305): the raw rows, indexed by internal id, for the exact re-rank
@@ -895,6 +945,7 @@ class HierarchicalNSWSlimQ<float> : public AlgorithmInterface<float>, public det
   }
   // saveIndex (hnswalg_slimq.h:1161-1216) after convertFromHNSW: the file it wrote, copied
   void saveIndex(const std::string &location) override {
+    if (from_graph_ && h_) { detail::check(hs_slimq_index_save(h_, location.c_str())); return; }   // the index's host image
     if (tmp_path_.empty() || path_ != tmp_path_)
       throw std::runtime_error("hnswlib_amd: the device index is read-only; the file it was loaded from is unchanged");
     std::ifstream in(tmp_path_, std::ios::binary);

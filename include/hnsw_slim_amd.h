@@ -825,6 +825,65 @@ hs_status hs_rabitq_prepare_query(size_t padded, double t_const, const float *ro
 hs_status hs_rabitq_estimate(size_t padded, const uint64_t *codes, const float *factors, size_t nd, const float *q3,
                              const uint64_t *bins, const float *g_add, const float *g_error, size_t nq, float *out);
 
+/* ---- a resident SlimQ index from rows or a graph, with no file on the way ------------------------------------
+ * hs_graph: an HNSW graph in host memory -- what saveIndex (hnswalg.h:748-779) would write.  hs_build_rabitq_hnsw_batched_mem is
+ * hs_build_rabitq_hnsw_batched without its file (same options, refusals and stats; total_ms without a file write);
+ * hs_graph_save writes the bytes that call writes; hs_graph_load reads any file of that layout. */
+typedef struct hs_graph hs_graph;
+hs_status hs_build_rabitq_hnsw_batched_mem(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
+                                           size_t seed, const hs_batch_build_opts *opts, hs_graph **out,
+                                           hs_batch_build_stats *stats /* nullable */);
+hs_status hs_graph_load(const char *path, int metric, size_t dim, hs_graph **out);
+hs_status hs_graph_save(const hs_graph *g, const char *path);
+/* every output nullable */
+hs_status hs_graph_info(const hs_graph *g, uint64_t *n, uint64_t *dim, int *metric, uint64_t *M, uint64_t *ef_construction, int *maxlevel);
+void hs_graph_free(hs_graph *g);
+
+/* the arguments of hs_convert_hnsw_to_slimq between `dim` and `device` */
+typedef struct hs_slimq_params {
+  int threshold_level;
+  float top_degree_percent0, top_degree_percent;
+  size_t top_degree_M0, low_degree_m0, top_degree_M, low_degree_m;
+  const float *centroids;        /* num_cluster x dim raw vectors */
+  size_t num_cluster;
+  const uint32_t *cluster_ids;   /* n ids or NULL (= nearest centroid) */
+  uint64_t flip_seed;
+} hs_slimq_params;
+/* build + conversion + residency of one hs_slimq_index_from_rows call */
+typedef struct hs_slimq_pipeline_stats {
+  hs_batch_build_stats build;
+  hs_slimq_convert_stats convert;
+  double resident_ms;      /* packing, uploads and the tile kernels (and the dataset upload with with_dataset) */
+  double tile_kernel_ms;   /* the three kernels of slimq_tiles.hip, first to last */
+  double total_ms;
+} hs_slimq_pipeline_stats;
+/* convertFromHNSW of an in-memory graph.  convert_device: -1 = both steps on `threads` host threads, >= 0 = on that device with the
+ * host fallbacks of hs_convert_hnsw_to_slimq.  out_path (nullable): the SlimQ file, byte for byte hs_convert_hnsw_to_slimq's.
+ * out_index (nullable): a resident index on `index_device`, its fused tiles gathered on the device (slimq_tiles.hip); with_dataset
+ * != 0 also makes the graph's own rows its re-rank dataset (row of internal id i, hnswalg_slimq.h:748), as hs_slimq_set_dataset
+ * would.  At least one of the two outputs (HS_ERR_INVALID otherwise).  Refusals are those of hs_convert_hnsw_to_slimq and, with
+ * out_index, of hs_index_load (HS_ERR_DEVICE without that device), all before any work: no file is then written.  stats
+ * (nullable): total_ms includes whatever outputs were asked for. */
+hs_status hs_graph_convert_slimq(const hs_graph *g, const hs_slimq_params *p, int convert_device, int threads, const char *out_path,
+                                 int index_device, int with_dataset, hs_index **out_index, hs_slimq_convert_stats *stats);
+/* rows in, resident index out: hs_build_rabitq_hnsw_batched_mem + hs_graph_convert_slimq in one call; the graph is freed inside.
+ * The build runs on opts->device, the conversion too, and the index lives there (opts->device >= 0: HS_ERR_INVALID otherwise). */
+hs_status hs_slimq_index_from_rows(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
+                                   const hs_batch_build_opts *opts, const hs_slimq_params *p, int threads, int with_dataset,
+                                   hs_index **out_index, hs_slimq_pipeline_stats *stats /* nullable */);
+/* saveIndex (hnswalg_slimq.h:1161-1216) of the host image every resident SlimQ index keeps (codes, factors, blobs, labels; no fp32
+ * rows).  HS_ERR_INVALID for any other index. */
+hs_status hs_slimq_index_save(const hs_index *ix, const char *path);
+/* tests: which = 0 rec, 1 ftile, 2 uptile.  *words = the array's length (0: the index has no such array); copied out when
+ * cap_words suffices (out may be NULL with cap_words 0 to ask).  stride / row_words (nullable): slots per row and words per slot
+ * of it (rec: 1 and rec_words). */
+hs_status hs_debug_slimq_arrays(const hs_index *ix, int which, uint32_t *out, size_t cap_words, size_t *words, uint32_t *stride,
+                                uint32_t *row_words);
+/* the same three arrays from a SlimQ file by the host functions of csrc/slimq_tiles.hpp alone: no device.  fused: what
+ * HS_SLIMQ_FUSED would be. */
+hs_status hs_debug_slimq_arrays_host(const char *slimq_path, int metric, size_t dim, int fused, int which, uint32_t *out, size_t cap_words,
+                                     size_t *words, uint32_t *stride, uint32_t *row_words);
+
 #ifdef __cplusplus
 }
 #endif
