@@ -12,8 +12,11 @@
 // tests/golden/rabitq_ref.npz): rotation, sign codes, query bit planes and the estimator bit for bit; float
 // reductions (Eigen: order depends on alignment / SIMD width, i.e. not even stable across builds of the reference)
 // are DEFINED here as left-to-right fp32 sums and agree with the library to 1e-4 of the value range.  The
-// search loop itself (hnswalg_slimq.h) needs folly to compile: PARITY UNPINNED by a compiled reference, restated
-// from source reading only.
+// search loop itself (hnswalg_slimq.h) needs folly to compile, so no compiled reference pins it.  It is pinned to a second,
+// independent reading of the source instead: tests/slimq_search_restated.py (plain Python: estimate, descent, SearchBuffer,
+// visited array, re-rank, libstdc++ heap array) equals slimq_search below in labels, distance bits, counts, counters and event
+// traces on the hand-made files of tests/slimq_handmade.py (lists past 64 ids, steered ties of the estimates, duplicate ids,
+// n < k, ef 1 .. 1024), and five wrong readings of the source are shown to differ there (tests/test_slimq_handmade_cpu.py).
 #pragma once
 #include "hs_oracle.hpp"
 

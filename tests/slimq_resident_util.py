@@ -3,7 +3,8 @@
 numpy_arrays is an independent reading of the three arrays a resident HNSW-SlimQ index searches -- rec, ftile, uptile -- written from
 the file format (header, elements, CHAL blobs) and the stride rules of DESIGN.md 4q, not from csrc/slimq_tiles.hpp: it
 parses the file with struct / numpy and places every word.  write_slimq writes such a file byte by byte from Python lists, and
-HANDMADE are the small graphs both test files share."""
+HANDMADE are the small graphs both test files share.  The hand-made search cases (slimq_handmade.py) write their files with
+write_slimq too, and the plain-Python reading of the search (slimq_search_restated.py) runs over parse_slimq's fields."""
 import struct
 
 import numpy as np
@@ -15,10 +16,12 @@ def rec_words(padded):
     return (4 + 2 * (padded // 64) + 3) & ~3
 
 
-def write_slimq(path, dim, lists, metric=0, enterpoint=0, ncl=1, seed=0, threshold_level=0):
+def write_slimq(path, dim, lists, metric=0, enterpoint=0, ncl=1, seed=0, threshold_level=0, factors=None, cluster=None, code=None):
     """lists[i] = the neighbour lists of node i, level 0 first (one list per level 0..level(i)); an empty lists[i] (or one whose
     lists are all empty) is written as a node without a blob, with its level kept.  lists[i] may also be (level, []) for a node of
-    that level without a blob.  Records are random but reproducible.  Returns the dict numpy reading should find."""
+    that level without a blob.  Records are random but reproducible; factors (n x 3 f32: f_add, f_rescale, f_error), cluster (n u32)
+    and code (n x padded/64 u64) replace the random ones where given, which changes none of the other bytes.  Returns the dict numpy
+    reading should find."""
     n = len(lists)
     padded = (dim + 63) // 64 * 64
     sbin, sex = padded // 8 + 12, padded * 3 // 8 + 8
@@ -36,11 +39,15 @@ def write_slimq(path, dim, lists, metric=0, enterpoint=0, ncl=1, seed=0, thresho
     hdr += struct.pack("<3Q", 24, 28, 28 + sbin) + struct.pack("<3Q", sbin, sex, 3) + bytes([metric])
     cent = rng.normal(0, 1, (ncl, padded)).astype(np.float32)
     flips = rng.integers(0, 256, 4 * padded // 8, dtype=np.uint8)
-    cluster = rng.integers(0, ncl, n).astype(np.uint32)
-    code = rng.integers(0, 1 << 63, (n, padded // 64), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (n, padded // 64)).astype(np.uint64)
-    factors = rng.normal(0, 3, (n, 3)).astype(np.float32)
+    rnd_cluster = rng.integers(0, ncl, n).astype(np.uint32)
+    rnd_code = rng.integers(0, 1 << 63, (n, padded // 64), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (n, padded // 64)).astype(np.uint64)
+    rnd_factors = rng.normal(0, 3, (n, 3)).astype(np.float32)
+    cluster = rnd_cluster if cluster is None else np.ascontiguousarray(cluster, np.uint32)
+    code = rnd_code if code is None else np.ascontiguousarray(code, np.uint64)
+    factors = rnd_factors if factors is None else np.ascontiguousarray(factors, np.float32)
+    assert cluster.shape == (n,) and code.shape == (n, padded // 64) and factors.shape == (n, 3)
     labels = (np.arange(n, dtype=np.uint64) * np.uint64(3) + np.uint64(1000))
-    body, blobs = b"", b""
+    body, blobs = [], []
     for i in range(n):
         total = sum(len(x) for x in nodes[i])
         el = bytearray(spe)
@@ -48,9 +55,9 @@ def write_slimq(path, dim, lists, metric=0, enterpoint=0, ncl=1, seed=0, thresho
         struct.pack_into("<I", el, 24, int(cluster[i]))
         el[28:28 + padded // 8] = code[i].tobytes()
         el[28 + padded // 8:28 + padded // 8 + 12] = factors[i].tobytes()
-        body += bytes(el)
+        body.append(bytes(el))
         if total == 0:
-            blobs += struct.pack("<I", 0)
+            blobs.append(struct.pack("<I", 0))
             continue
         offs, run = [], 0
         for x in nodes[i][:-1]:
@@ -58,9 +65,9 @@ def write_slimq(path, dim, lists, metric=0, enterpoint=0, ncl=1, seed=0, thresho
             offs.append(run)
         blob = struct.pack(f"<{len(offs)}H", *offs) + b"".join(struct.pack(f"<{len(x)}I", *x) for x in nodes[i])
         assert len(blob) == 2 * levels[i] + 4 * total
-        blobs += struct.pack("<I", len(blob)) + blob
+        blobs.append(struct.pack("<I", len(blob)) + blob)
     with open(path, "wb") as f:
-        f.write(hdr + cent.tobytes() + flips.tobytes() + body + blobs)
+        f.write(b"".join([hdr, cent.tobytes(), flips.tobytes()] + body + blobs))
     return dict(n=n, dim=dim, padded=padded, levels=levels)
 
 
