@@ -23,17 +23,17 @@
 //     loads in flight per lane, compile-time dims for the common shapes; dim % 16 != 0 runs the reference's
 //     SIMD4 / residual recipes one lane per row;
 //   * candidate heap: the reference's raw array in LDS with libstdc++'s push_heap/pop_heap sift sequence
-//     (push: the whole wave in one read/write round; pop: lane 0) -> the expansion order among equal-distance
-//     candidates is the reference's;
+//     (heap_push: the whole wave in one read/write round; heap_pop: lane 0; search_common.hpp) -> the expansion order
+//     among equal-distance candidates is the reference's;
 //   * result set, two kernels:
 //       strict: the reference's raw top_candidates array + libstdc++ heap/nth_element mechanics
-//               (heap_emul.hpp) -> identical array, identical output ORDER, any tie pattern;
+//               (heap_emul.hpp; select_and_write, search_finish.hpp) -> identical array, identical output ORDER, any tie pattern;
 //       fast  : a sorted array held in registers (rank r in lane r%64); a tile's accept decisions are taken at once
 //               from a closed form of the reference's sequential scan and the accepted entries merged in one pass;
 //               which of several equal-distance entries survives/gets selected is then not defined, so for a query
 //               whose k-subset could depend on it (k-th and (k+1)-th distance equal) the logged insertions are
-//               replayed through the libstdc++ mechanics (or, if the log overflowed, the query is flagged ST_HAZARD
-//               and answered by the strict kernel).  Output sorted by distance.
+//               replayed through the libstdc++ mechanics (replay_boundary, search_finish.hpp; or, if the log overflowed,
+//               the query is flagged ST_HAZARD and answered by the strict kernel).  Output sorted by distance.
 //   * a query that outgrows even the global-memory tiers is flagged ST_OVERFLOW and re-run by the strict kernel with
 //     a whole CU's LDS.
 #include <hip/hip_runtime.h>
@@ -47,10 +47,11 @@
 #include "heap_emul.hpp"
 #include "narrow_load.hpp"
 #include "search_common.hpp"
+#include "search_finish.hpp"
+#include "search_tu.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
-
 
 // ---- LDS layouts --------------------------------------------------------------------------------
 struct StrictLds { uint32_t off_q, off_top, off_cand, off_hash, off_nid, off_nd, total; };
@@ -80,24 +81,7 @@ __host__ __device__ inline FastLds fast_layout(uint32_t dim, uint32_t ef, uint32
   l.total = l.off_stage + align_up(ef * 8, 16);
   return l;
 }
-// The build compiles this file twice, side by side: -DHS_TU_METRIC=0 holds the L2 kernels and everything that is not
-// per metric, -DHS_TU_METRIC=1 the inner-product kernels (the kernel instantiations are the build's critical path).
-// Without the macro one translation unit holds both (make asm / prof / asan).
-#if !defined(HS_TU_METRIC)
-#define HS_TU_HAS_L2 1
-#define HS_TU_HAS_IP 1
-#elif HS_TU_METRIC == 0
-#define HS_TU_HAS_L2 1
-#define HS_TU_HAS_IP 0
-#else
-#define HS_TU_HAS_L2 0
-#define HS_TU_HAS_IP 1
-#endif
-// HS_TU_ROWS = 1 | 2 (beam_search_u8.hip / beam_search_f16.hip): the same kernels over the index's narrow copy of the rows, as
-// objects of their own per row format and metric; those hold the narrow entry points and their launchers, nothing else.
-#if !defined(HS_TU_ROWS)
-#define HS_TU_ROWS 0
-#endif
+// (one object per metric and row format, search_tu.hpp: what is not per metric lives in the fp32 L2 object)
 #if HS_TU_HAS_L2 && HS_TU_ROWS == 0
 size_t strict_lds_bytes(uint32_t dim, uint32_t ef, uint32_t cand_cap, uint32_t hash_slots) {
   return strict_layout(dim, ef, cand_cap, hash_slots).total;
@@ -421,18 +405,16 @@ __device__ __forceinline__ void descend(const DevIndex &ix, const SearchArgs &a,
   }
 }
 
-__device__ __forceinline__ void write_stats(const SearchArgs &a, uint32_t qi, const Counters &c) {
-  if (a.stats) {
-    a.stats[qi * 4 + 0] = c.n_dist;
-    a.stats[qi * 4 + 1] = c.n_hops;
-    a.stats[qi * 4 + 2] = c.n_nbr;
-    a.stats[qi * 4 + 3] = a.pass_id;
+// This file's counters into the stats block (search_finish.hpp; sets ST_DONE too)
+__device__ __forceinline__ void write_stats(const SearchArgs &a, uint32_t qi, const Counters &c, uint32_t mark) {
+  write_stats(a, qi, c.n_dist, c.n_hops, c.n_nbr, mark);
 #ifdef HS_PROFILE
+  if (a.stats) {
     // diagnostic build: phase cycles go to a buffer of their own behind the nq x 4 stats block
     unsigned long long *pt = reinterpret_cast<unsigned long long *>(a.stats + (size_t)a.nq * 4) + (size_t)qi * 8;
     for (int i = 0; i < 8; i++) pt[i] = c.t[i];
-#endif
   }
+#endif
 }
 
 // ---- filter sets (engine.hpp FilterArgs) ---------------------------------------------------------------------------------
@@ -462,8 +444,7 @@ __device__ __forceinline__ void refuse_query(const SearchArgs &a, const FilterAr
   if (lane == 0) {
     if (a.out_counts) a.out_counts[qi] = 0;
     Counters c{};
-    write_stats(a, qi, c);
-    a.status[qi] = ST_DONE;
+    write_stats(a, qi, c, a.pass_id);
     atomicAdd(f.bad, 1u);
   }
 }
@@ -607,7 +588,6 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
   uint32_t *hash = reinterpret_cast<uint32_t *>(smem + L.off_hash);
   uint32_t *nid = reinterpret_cast<uint32_t *>(smem + L.off_nid);
   float *nd = reinterpret_cast<float *>(smem + L.off_nd);
-  const uint32_t k = a.k;
   Counters c;
 #ifdef HS_PROFILE
   for (int i = 0; i < 8; i++) c.t[i] = 0;
@@ -672,35 +652,13 @@ __device__ void search_one_strict(const DevIndex &ix, const SearchArgs &a, const
     for (uint32_t i = lane; i < st.top_size; i += 64) a.raw_top[(size_t)qi * a.raw_stride + i] = top[i];
     if (lane == 0) a.raw_size[qi] = st.top_size;
   }
-  // ---- k-selection ----------------------------------------------------------------------------
-  uint32_t ts = st.top_size;
-  if (a.mode == 0) {
-    // std::nth_element(top, top+k, top+size) then result[i] = label(top[i]) (hnswalg_slim.h:2126-2130)
-    if (lane == 0 && ts >= k) nth_element(top, (long)k, (long)ts, LessD());
-  } else {
-    // while (size > k) pop_heap (hnswalg_slim.h:2019-2022, hnswalg.h:1430-1432)
-    if (lane == 0)
-      while (ts > k) {
-        pop_heap(top, (long)ts, LessD());
-        ts--;
-      }
-    ts = min(ts, k);
-  }
-  wave_sync();
-  const uint32_t valid = min(ts, k);
-  for (uint32_t i = lane; i < k; i += 64) {
-    const bool v = i < valid;
-    const Pair p = v ? top[i] : Pair{__builtin_inff(), 0};
-    const uint64_t label = v ? ix.labels[p.id] : ~0ull;
-    if (a.out_labels32) a.out_labels32[(size_t)qi * k + i] = v ? (uint32_t)label : 0xFFFFFFFFu;  // size_t -> tableint truncation (:2129)
-    if (a.out_labels64) a.out_labels64[(size_t)qi * k + i] = label;
-    if (a.out_dists) a.out_dists[(size_t)qi * k + i] = p.d;
-  }
+  // ---- k-selection on the raw heap (search_finish.hpp) ------------------------------------------
+  const uint32_t valid = min(st.top_size, a.k);
+  select_and_write(ix, a, qi, top, st.top_size, valid, lane);
   if (lane == 0) {
     if (a.out_counts) a.out_counts[qi] = valid;
     HS_LAP(c, 7);
-    write_stats(a, qi, c);
-    a.status[qi] = ST_DONE;
+    write_stats(a, qi, c, a.pass_id);
   }
 }
 
@@ -1188,49 +1146,14 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
   if (__builtin_expect((top_size > k && top_key_at<S>(tk, k - 1) == top_key_at<S>(tk, k)) || boundary_tie, 0)) {
     if (lane == 0) atomicAdd(a.counters + 2, 1u);
     if (!tlog || n_log > a.log_cap) return 3;  // log did not fit: the strict kernel re-runs the query
-    Pair *top = reinterpret_cast<Pair *>(hash);
     __threadfence_block();
-    uint32_t ts = 0;
-    for (uint32_t base = 0; base < n_log; base += 64) {
-      const uint32_t m = min(64u, n_log - base);
-      uint2 e = make_uint2(0, 0);
-      if ((uint32_t)lane < m) e = tlog[base + lane];
-      for (uint32_t j = 0; j < m; j++) {
-        const float d = __uint_as_float(__builtin_amdgcn_readlane(e.x, j));
-        const uint32_t nb = __builtin_amdgcn_readlane(e.y, j);
-        if (lane == 0) {
-          top[ts].d = d;  // hnswalg_slim.h:419-423
-          top[ts].id = nb;
-          push_heap(top, (long)ts + 1, LessD());
-          if (ts + 1 > ef) pop_heap(top, (long)ts + 1, LessD());  // :434-448
-        }
-        ts = min(ts + 1, ef);
-      }
-    }
-    if (lane == 0) {
-      if (a.mode == 0) {
-        nth_element(top, (long)k, (long)ts, LessD());  // hnswalg_slim.h:2126-2127
-      } else {
-        uint32_t t2 = ts;
-        while (t2 > k) { pop_heap(top, (long)t2, LessD()); t2--; }  // :2019-2022
-      }
-    }
-    wave_sync();
-    for (uint32_t i = lane; i < k; i += 64) {
-      const Pair p = top[i];
-      const uint64_t label = ix.labels[p.id];
-      if (a.out_labels32) a.out_labels32[(size_t)qi * k + i] = (uint32_t)label;
-      if (a.out_labels64) a.out_labels64[(size_t)qi * k + i] = label;
-      if (a.out_dists) a.out_dists[(size_t)qi * k + i] = p.d;
-    }
+    // Every insertion is logged, so the rebuilt heap holds min(n_log, ef) == top_size entries; the replay is reached with top_size > k,
+    // or after an eviction (boundary_tie), i.e. with top_size == ef >= k: all k slots are valid and nth_element's guard always passes (FULL).
+    replay_boundary<true>(ix, a, qi, reinterpret_cast<Pair *>(hash), tlog, n_log, k, lane);
     if (lane == 0) {
       if (a.out_counts) a.out_counts[qi] = k;
       HS_WALL(c);
-      Counters c1 = c;
-      SearchArgs a1 = a;
-      a1.pass_id = 1;  // answered by the tie replay
-      write_stats(a1, qi, c1);
-      a.status[qi] = ST_DONE;
+      write_stats(a, qi, c, 1u);  // answered by the tie replay
     }
     return 0;
   }
@@ -1250,8 +1173,7 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
     if (a.out_counts) a.out_counts[qi] = valid_n;
     HS_LAP(c, 7);
     HS_WALL(c);
-    write_stats(a, qi, c);
-    a.status[qi] = ST_DONE;
+    write_stats(a, qi, c, a.pass_id);
   }
   return 0;
 }
@@ -1259,26 +1181,11 @@ __device__ int search_one_fast(const DevIndex &ix, const SearchArgs &a, const ui
 // ---- kernels: grid-stride over the queries selected by status ----------------------------------------
 // Each kernel once per row format: hs::strict_kernel / hs::fast_kernel read the resident fp32 rows (ix.vec), hs::*_kernel_u8 /
 // hs::*_kernel_f16 the index's narrow copy, handed over as a kernel argument of its own (DevIndex and SearchArgs are what they
-// were); they differ in nothing else.  What differs between the row formats, all of it:
+// were); they differ in nothing else.  What differs between the row formats: search_tu.hpp, and the rows the search body reads:
 #if HS_TU_ROWS == 0
-#define HS_ROWS_ID f32                 // the launchers' names (engine.hpp HS_LAUNCHER)
-#define HS_KERNEL(name) name           // the kernels' names
-#define HS_ROWS_PARAM                  // their trailing parameter (before FilterArgs in the filter-set form)
-#define HS_ROW_SRC RowSrc<float>()     // the rows the search body reads
-#define HS_ROWS_ARG                    // the launcher's `rows` as that parameter
+#define HS_ROW_SRC RowSrc<float>()
 #else
-#if HS_TU_ROWS == 1
-#define HS_ROWS_ID u8
-#define HS_KERNEL(name) name##_u8
-typedef uint8_t TuRow;
-#else
-#define HS_ROWS_ID f16
-#define HS_KERNEL(name) name##_f16
-typedef _Float16 TuRow;
-#endif
-#define HS_ROWS_PARAM , const TuRow *rows
 #define HS_ROW_SRC RowSrc<TuRow>{rows}
-#define HS_ROWS_ARG , reinterpret_cast<const TuRow *>(rows)
 #endif
 // Each kernel name is an overload pair: (DevIndex, SearchArgs[, rows]) and the filter-set form with FilterArgs behind it.
 #define HS_KFN(k) static_cast<void (*)(DevIndex, SearchArgs HS_ROWS_PARAM)>(k)

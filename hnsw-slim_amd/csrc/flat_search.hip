@@ -13,8 +13,8 @@
 //   * When the minimum is NOT unique (two unexpanded entries at the same distance, or a ghost at lowerBound), the heap's layout
 //     decides, and the layout is history: every hop's accepted entries are logged (8 B each -- the log that also resolves a tie
 //     at the k-th boundary at the end) with a per-hop count, and the heap is replayed, from where the last replay stopped,
-//     through the libstdc++ push_heap / pop_heap mechanics (search_common.hpp) up to now; its root is popped; the search goes
-//     on without the heap.  Replayed pops need no record: a past hop's pop was forced (unique minimum) or came from the heap
+//     through the libstdc++ push_heap / pop_heap mechanics (heap_push / heap_pop, search_common.hpp) up to now; its root is
+//     popped; the search goes on without the heap.  The tie at the k-th boundary at the end: replay_boundary (search_finish.hpp).  Replayed pops need no record: a past hop's pop was forced (unique minimum) or came from the heap
 //     itself.  So the traversal is the reference's on every input, ties included, and a query that never ties never touches
 //     the heap.
 //   * Visited set: 16-byte buckets of 7 x 15-bit remainders of a bijective hash + a 16-bit fill count, any number of buckets
@@ -39,6 +39,8 @@
 #include "heap_emul.hpp"
 #include "narrow_load.hpp"
 #include "search_common.hpp"
+#include "search_finish.hpp"
+#include "search_tu.hpp"
 #include "sorted_insert.hpp"
 #include "wave_util.hpp"
 
@@ -71,27 +73,7 @@ __host__ __device__ inline FlatLds flat_layout(uint32_t dim, uint32_t ef, uint32
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(hs_us2, a), __builtin_bit_cast(hs_us2, b)));
 }
-// order-preserving image of an fp32 distance in int32 (no NaNs): L2 distances are >= +0, whose bit patterns already order
-template <int METRIC>
-__device__ __forceinline__ int dkey(float d) {
-  const int b = (int)__float_as_uint(d);
-  return METRIC == METRIC_L2 ? b : (b ^ ((b >> 31) & 0x7FFFFFFF));
-}
-template <int METRIC>
-__device__ __forceinline__ float key_dist(int k) {
-  return __uint_as_float((uint32_t)(METRIC == METRIC_L2 ? k : (k ^ ((k >> 31) & 0x7FFFFFFF))));
-}
-static constexpr int kFKeyInf = 0x7F800000;       // dkey(+inf)
 static constexpr uint32_t kFDone = 0x80000000u;   // bit 31 of a result-set id: expanded (or padding)
-
-__device__ __forceinline__ int wave_min_i32_f(int v) {
-#define HS_SHR_MINI(ctrl) v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, ctrl, 0xf, 0xf, false))
-  HS_SHR_MINI(0x111); HS_SHR_MINI(0x112); HS_SHR_MINI(0x114); HS_SHR_MINI(0x118);
-#undef HS_SHR_MINI
-  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
-  const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
-  return min(min(r0, r1), min(r2, r3));
-}
 
 // loads in flight per lane for a compile-time dim of D16 sixteen-float steps
 __host__ __device__ constexpr int flat_row_buffer(int d16) {
@@ -244,10 +226,9 @@ __device__ __forceinline__ float flat_dist8(const ROW *vec, uint32_t dim, const 
   }
 }
 
-// The candidate min-heap of search_common.hpp (element i at slot i + 1; same sift decisions as std::push_heap / pop_heap with
-// compare_by_first_rev, hnswalg_slim.h:177-183) with the address spaces spelled out: slots [0, L) in LDS, the rest in the
-// query's scratch region.  (A generic pointer made from an LDS pointer sends this compiler into an illegal V_CMP against
-// src_shared_base -- see wave_util.hpp::lds_cas.)
+// The candidate min-heap of search_common.hpp (element i at slot i + 1; heap_push / heap_pop are the sifts defined there) with the
+// address spaces spelled out: slots [0, L) in LDS, the rest in the query's scratch region.  (A generic pointer made from an LDS
+// pointer sends this compiler into an illegal V_CMP against src_shared_base -- see wave_util.hpp::lds_cas.)
 struct FlatHeap {
   lds_u8 *lds;
   uint2 *glob;   // slot s >= L at glob[s]
@@ -255,72 +236,29 @@ struct FlatHeap {
 };
 typedef uint32_t hs_u2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) hs_u2 lds_u64;
-// T2 = false: every slot touched is known to lie in LDS -> straight-line LDS code (no address tests, no global access)
 template <bool T2>
-__device__ __forceinline__ uint2 fh_get(const FlatHeap &h, uint32_t s) {
+__device__ __forceinline__ uint2 heap_get(const FlatHeap &h, uint32_t s) {
   if (!T2 || s < h.L) { const hs_u2 v = *reinterpret_cast<lds_u64 *>(h.lds + s * 8); return make_uint2(v.x, v.y); }
   return h.glob[s];
 }
 template <bool T2>
-__device__ __forceinline__ void fh_set(const FlatHeap &h, uint32_t s, uint2 v) {
+__device__ __forceinline__ void heap_set(const FlatHeap &h, uint32_t s, uint2 v) {
   if (!T2 || s < h.L) *reinterpret_cast<lds_u64 *>(h.lds + s * 8) = hs_u2{v.x, v.y};
   else h.glob[s] = v;
 }
 template <bool T2>
-__device__ __forceinline__ uint4 fh_get2(const FlatHeap &h, uint32_t s /*even*/) {
+__device__ __forceinline__ uint4 heap_get2(const FlatHeap &h, uint32_t s /*even*/) {
   if (!T2 || s < h.L) { const hs_u4 v = *reinterpret_cast<lds_u128 *>(h.lds + s * 8); return make_uint4(v.x, v.y, v.z, v.w); }
   return *reinterpret_cast<const uint4 *>(&h.glob[s]);
-}
-// std::push_heap: all ancestors of the new slot are known up front, so the whole wave does it in one read and one write round
-template <bool T2>
-__device__ __forceinline__ void fh_push(const FlatHeap &h, uint32_t n /*size incl. new*/, float d, uint32_t id, int lane) {
-  const uint32_t anc = n >> (lane + 1);
-  const bool has = anc != 0 && lane < 31;
-  uint2 p = make_uint2(0, 0);
-  if (has) p = fh_get<T2>(h, anc);
-  const unsigned long long rises = hs_ballot(has && __uint_as_float(p.x) > d);
-  const uint32_t r = __ffsll((long long)~rises) - 1;
-  if ((uint32_t)lane < r) fh_set<T2>(h, n >> lane, p);
-  if ((uint32_t)lane == r) fh_set<T2>(h, n >> r, make_uint2(__float_as_uint(d), id));
-}
-// std::pop_heap (one lane); the popped root was read by the caller beforehand
-template <bool T2>
-__device__ __forceinline__ void fh_pop(const FlatHeap &h, uint32_t n /*size before pop*/) {
-  if (n <= 1) return;
-  const uint2 v = fh_get<T2>(h, n);
-  const uint32_t len = n - 1;
-  uint32_t hole = 0, child = 0;
-  while (child < (len - 1) / 2) {
-    child = 2 * (child + 1);
-    const uint4 two = fh_get2<T2>(h, child);
-    const bool left = __uint_as_float(two.z) > __uint_as_float(two.x);
-    fh_set<T2>(h, hole + 1, left ? make_uint2(two.x, two.y) : make_uint2(two.z, two.w));
-    child = left ? child - 1 : child;
-    hole = child;
-  }
-  if ((len & 1) == 0 && child == (len - 2) / 2) {
-    child = 2 * (child + 1);
-    fh_set<T2>(h, hole + 1, fh_get<T2>(h, child));
-    hole = child - 1;
-  }
-  const float vd = __uint_as_float(v.x);
-  while (hole > 0) {
-    const uint32_t parent = (hole - 1) >> 1;
-    const uint2 p = fh_get<T2>(h, parent + 1);
-    if (!(__uint_as_float(p.x) > vd)) break;
-    fh_set<T2>(h, hole + 1, p);
-    hole = parent;
-  }
-  fh_set<T2>(h, hole + 1, v);
 }
 
 // std::pop_heap by the whole wave, for a heap that lies in LDS: __adjust_heap's walk to the bottom picks, at every node, one of
 // its two children, so lanes 0..6 read the child pairs of the hole, of its children and of its grandchildren in ONE LDS round,
 // a scalar walk over the seven pick bits resolves three levels, and the (up to three) moves go out as one masked write.  A heap
-// of 200 entries is popped in three LDS round trips instead of eight dependent ones.  Same decisions as fh_pop / std::pop_heap.
+// of 200 entries is popped in three LDS round trips instead of eight dependent ones.  Same decisions as heap_pop / std::pop_heap.
 __device__ __forceinline__ void fh_pop_wave(const FlatHeap &h, uint32_t n /*size before pop*/, int lane) {
   if (n <= 1) return;
-  const uint2 v = fh_get<false>(h, n);   // a[n-1] (uniform address: broadcast)
+  const uint2 v = heap_get<false>(h, n);   // a[n-1] (uniform address: broadcast)
   const uint32_t len = n - 1;
   uint32_t hole = 0;
   const uint32_t dl = lane < 1 ? 0u : (lane < 3 ? 1u : 2u);   // depth of this lane's node below the hole
@@ -329,7 +267,7 @@ __device__ __forceinline__ void fh_pop_wave(const FlatHeap &h, uint32_t n /*size
     const uint32_t node = ((hole + 1u) << dl) - 1u + ol;
     const bool two = lane < 7 && 2u * node + 2u < len;   // the node has both children
     uint4 pr = make_uint4(0, 0, 0, 0);
-    if (two) pr = fh_get2<false>(h, 2u * node + 2u);   // a[2 node + 1], a[2 node + 2]
+    if (two) pr = heap_get2<false>(h, 2u * node + 2u);   // a[2 node + 1], a[2 node + 2]
     const bool right = !(__uint_as_float(pr.z) > __uint_as_float(pr.x));   // comp(a[child], a[child-1]) false: take a[child]
     const unsigned long long vm = hs_ballot(two), rm = hs_ballot(two && right);
     uint32_t l = 0, path = 0, last = 0;
@@ -342,17 +280,17 @@ __device__ __forceinline__ void fh_pop_wave(const FlatHeap &h, uint32_t n /*size
     }
     if (path == 0) break;
     const uint32_t child = 2u * node + 1u + (right ? 1u : 0u);
-    if (lane < 7 && ((path >> lane) & 1u)) fh_set<false>(h, node + 1u, right ? make_uint2(pr.z, pr.w) : make_uint2(pr.x, pr.y));
+    if (lane < 7 && ((path >> lane) & 1u)) heap_set<false>(h, node + 1u, right ? make_uint2(pr.z, pr.w) : make_uint2(pr.x, pr.y));
     hole = __builtin_amdgcn_readlane(child, last);
     if (!open) break;
   }
   if ((len & 1u) == 0 && hole == (len - 2u) / 2u) {   // a last node with a left child only
-    const uint2 c = fh_get<false>(h, 2u * hole + 2u);
-    if (lane == 0) fh_set<false>(h, hole + 1u, c);
+    const uint2 c = heap_get<false>(h, 2u * hole + 2u);
+    if (lane == 0) heap_set<false>(h, hole + 1u, c);
     hole = 2u * hole + 1u;
   }
   wave_sync();
-  fh_push<false>(h, hole + 1u, __uint_as_float(v.x), v.y, lane);   // __push_heap(first, hole, top = 0, value)
+  heap_push<false>(h, hole + 1u, __uint_as_float(v.x), v.y, lane);   // __push_heap(first, hole, top = 0, value)
 }
 
 // The lazy candidate heap brought up to date and its root popped (see the file header): state = the reference's candidate_set
@@ -411,7 +349,7 @@ __device__ HS_FLAT_SYNC_ATTR FlatSyncOut flat_heap_sync(FlatSync f) {
   if (h_idx == 0) {   // candidate_set = {entry} (hnswalg_slim.h:327-332)
     const uint2 e = log_at(0);
     cand_size = 1;
-    fh_push<false>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
+    heap_push<false>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
     wave_sync();
     h_idx = 1;
   }
@@ -420,7 +358,7 @@ __device__ HS_FLAT_SYNC_ATTR FlatSyncOut flat_heap_sync(FlatSync f) {
   while (hq < hop0) {   // per past hop: pop (:353-354), then that hop's pushes (:408-411)
     if (hp == hq) {
       if (cand_size < heap_lds_slots) fh_pop_wave(cand, cand_size, lane);
-      else if (lane == 0) fh_pop<true>(cand, cand_size);
+      else if (lane == 0) heap_pop<true>(cand, cand_size);
       cand_size--;
       hp++;
       wave_sync();
@@ -435,8 +373,8 @@ __device__ HS_FLAT_SYNC_ATTR FlatSyncOut flat_heap_sync(FlatSync f) {
     for (uint32_t q = 0; q < np; q++) {
       const uint2 e = log_at(h_idx);
       cand_size++;
-      if (in_lds) fh_push<false>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
-      else fh_push<true>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
+      if (in_lds) heap_push<false>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
+      else heap_push<true>(cand, cand_size, __uint_as_float(e.x), e.y, lane);
       wave_sync();
       h_idx++;
     }
@@ -444,14 +382,14 @@ __device__ HS_FLAT_SYNC_ATTR FlatSyncOut flat_heap_sync(FlatSync f) {
   }
   bool stop = rc != 0 || cand_size == 0;
   if (!stop) {
-    const uint2 root = fh_get<false>(cand, 1);
+    const uint2 root = heap_get<false>(cand, 1);
     const uint32_t rkey_bits = uni(root.x);
     if (dkey<METRIC>(__uint_as_float(rkey_bits)) > lb) {   // :340
       stop = true;
     } else {
       next_id = uni(root.y);
       if (cand_size < heap_lds_slots) fh_pop_wave(cand, cand_size, lane);
-      else if (lane == 0) fh_pop<true>(cand, cand_size);
+      else if (lane == 0) heap_pop<true>(cand, cand_size);
       cand_size--;
       hp++;
       wave_sync();
@@ -630,7 +568,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
           const uint32_t rid = __shfl(pr.x, (int)(j < m ? j : base), 64);
           const float d = flat_dist8<METRIC, D16>(rows, dim, qv, rid, s8);
           const int ky = (s8 == OWN && j < m) ? dkey<METRIC>(d) : INT_MAX;
-          const int mn = wave_min_i32_f(ky);
+          const int mn = wave_min_i32(ky);
           if (mn < best_key) {
             best_key = mn;
             best_at = base + ((uint32_t)(__ffsll((long long)hs_ballot(ky == mn)) - 1) >> 3);
@@ -657,7 +595,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
   unsigned long long inr[S];   // lanes whose slot-s rank is below ef
 #pragma unroll
   for (int s = 0; s < S; s++) {
-    tk[s] = kFKeyInf;
+    tk[s] = kKeyInf;
     ti[s] = kFDone;
     inr[s] = hs_ballot((uint32_t)(lane * S + s) < ef);
   }
@@ -710,7 +648,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       any |= um[s];
     }
     r.any = any != 0;
-    r.p = 0; r.slot = 0; r.key = kFKeyInf; r.id = 0; r.same = 0;
+    r.p = 0; r.slot = 0; r.key = kKeyInf; r.id = 0; r.same = 0;
     if (any) {
       const int p = __ffsll((long long)any) - 1;
       int u_key = __builtin_amdgcn_readlane(tk[S - 1], p);
@@ -811,7 +749,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       const bool act = j < cnt;
       const uint32_t rid = nid[act ? j : base];   // idle groups re-read the pass's first row (cache hit) and discard
       const float d = flat_dist8<METRIC, D16>(rows, dim, qv, rid, s8);   // :395-396
-      const int my_key = (s8 == OWN && act) ? dkey<METRIC>(d) : kFKeyInf;
+      const int my_key = (s8 == OWN && act) ? dkey<METRIC>(d) : kKeyInf;
 #ifdef HS_FLAT_DIAG
       asm volatile("s_nop 0" : : "v"(my_key) : "memory");
       HS_DIAG_LAP(3);
@@ -824,7 +762,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       int b_lane = -1;
       if (base + 8 >= cnt && ghost_key != lb) {
         const Near u = nearest();
-        int mk = min(my_key, __builtin_amdgcn_update_dpp(kFKeyInf, my_key, 0x118, 0xf, 0xf, false));   // row_shr:8: owner lanes 8 apart
+        int mk = min(my_key, __builtin_amdgcn_update_dpp(kKeyInf, my_key, 0x118, 0xf, 0xf, false));   // row_shr:8: owner lanes 8 apart
         const int b_key = min(min(__builtin_amdgcn_readlane(mk, OWN + 8), __builtin_amdgcn_readlane(mk, OWN + 24)),
                               min(__builtin_amdgcn_readlane(mk, OWN + 40), __builtin_amdgcn_readlane(mk, OWN + 56)));
         const bool b_ok = b_key < lb;
@@ -902,7 +840,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
           // below.)  A branch of its own, taken by the few sets with ef == 64 S: as one condition among the others the compiler
           // evaluates all of this with scalar selects on every insertion of every set.
           if (__builtin_expect(exact_fit, 0)) {
-            if (ek != kFKeyInf && lb == ek) {   // an entry left the set at exactly the new bound
+            if (ek != kKeyInf && lb == ek) {   // an entry left the set at exactly the new bound
               btie = true;
               if ((int)ei >= 0) ghost_key = ek;   // ... unexpanded: the reference may still pop it
             }
@@ -919,7 +857,7 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       }
       HS_DIAG_LAP(4);
     }
-    if (!exact_fit && n_acc_hop != 0 && lb != kFKeyInf) {
+    if (!exact_fit && n_acc_hop != 0 && lb != kKeyInf) {
       // entries evicted at exactly the bound sit right behind rank ef - 1 for as long as the bound does not move: one of them
       // decides the answer when ef == k (btie), an unexpanded one is still a candidate of the reference (ghost)
       unsigned long long eq = 0, un = 0;
@@ -970,50 +908,13 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
   } else {
     if (lane == 0) atomicAdd(a.counters + 2, 1u);
     __threadfence_block();
-    Pair *top = reinterpret_cast<Pair *>((unsigned char *)smem + L.off_vis);
-    uint32_t ts = 0;
-    for (uint32_t base = 0; base < n_log; base += 64) {
-      const uint32_t mm = min(64u, n_log - base);
-      uint2 e = make_uint2(0, 0);
-      if ((uint32_t)lane < mm) e = tlog[base + lane];
-      for (uint32_t j = 0; j < mm; j++) {
-        const float d = __uint_as_float(__builtin_amdgcn_readlane(e.x, j));
-        const uint32_t nbj = __builtin_amdgcn_readlane(e.y, j);
-        if (lane == 0) {
-          top[ts].d = d;
-          top[ts].id = nbj;
-          push_heap(top, (long)ts + 1, LessD());
-          if (ts + 1 > ef) pop_heap(top, (long)ts + 1, LessD());
-        }
-        ts = min(ts + 1, ef);
-      }
-    }
-    if (lane == 0) {
-      if (a.mode == 0) {
-        if (ts >= k) nth_element(top, (long)k, (long)ts, LessD());
-      } else {
-        uint32_t t2 = ts;
-        while (t2 > k) { pop_heap(top, (long)t2, LessD()); t2--; }
-      }
-    }
-    wave_sync();
-    for (uint32_t i = lane; i < k; i += 64) {
-      const bool v = i < valid_n;
-      const Pair p = v ? top[i] : Pair{__builtin_inff(), 0};
-      const uint64_t label = v ? ix.labels[p.id] : ~0ull;
-      if (a.out_labels32) a.out_labels32[(size_t)qi * k + i] = v ? (uint32_t)label : 0xFFFFFFFFu;
-      if (a.out_labels64) a.out_labels64[(size_t)qi * k + i] = label;
-      if (a.out_dists) a.out_dists[(size_t)qi * k + i] = p.d;
-    }
+    replay_boundary(ix, a, qi, reinterpret_cast<Pair *>((unsigned char *)smem + L.off_vis), tlog, n_log, valid_n, lane);   // (search_finish.hpp)
   }
   if (lane == 0) {
     if (a.out_counts) a.out_counts[qi] = valid_n;
-    if (a.stats) {
-      a.stats[qi * 4 + 0] = n_dist;
-      a.stats[qi * 4 + 1] = n_hops;
-      a.stats[qi * 4 + 2] = n_nbr;
-      a.stats[qi * 4 + 3] = replay ? 1u : a.pass_id;
+    write_stats(a, qi, n_dist, n_hops, n_nbr, replay ? 1u : a.pass_id);
 #ifdef HS_FLAT_DIAG
+    if (a.stats) {
       uint32_t *dg = a.stats + (size_t)a.nq * 4 + qi * 16;
       dg[4] = (uint32_t)diag_t0;                                          // start, 100 MHz ticks (low word)
       dg[5] = diag_sync_ticks;                                            // ticks spent inside heap replays
@@ -1023,36 +924,19 @@ __device__ int search_one_flat(const DevIndex &ix, const SearchArgs &a, const ui
       dg[1] = diag_syncs;
       dg[2] = diag_replayed;
       dg[3] = ovf_n | (v2.spilled ? 0x10000u : 0u) | (v2.n2 << 17);
-#endif
     }
-    a.status[qi] = ST_DONE;
+#endif
   }
   return 0;
 }
 
 // The entry point, once per row format: hs::flat_kernel reads the resident fp32 rows (ix.vec), hs::flat_kernel_u8 /
 // hs::flat_kernel_f16 the index's narrow copy (hs_index_set_row_format), handed over as a kernel argument of its own; they differ in
-// nothing else.  Each is compiled as objects of its own (HS_TU_ROWS = 0 | 1 | 2 beside HS_TU_METRIC: Makefile) so that a kernel
-// trace shows them as separate rows.  What differs between the row formats, all of it:
-#if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
-#define HS_ROWS_ID f32               // the launchers' names (engine.hpp HS_LAUNCHER)
-#define HS_KERNEL(name) name         // the kernel's name
-#define HS_ROWS_PARAM                // its trailing parameter
-#define HS_ROWS_READ ix.vec          // the rows the search body reads
-#define HS_ROWS_ARG                  // the launcher's `rows` as that parameter
+// nothing else.  What differs between the row formats: search_tu.hpp, and the rows the search body reads:
+#if HS_TU_ROWS == 0
+#define HS_ROWS_READ ix.vec
 #else
-#if HS_TU_ROWS == 1
-#define HS_ROWS_ID u8
-#define HS_KERNEL(name) name##_u8
-typedef uint8_t TuRow;
-#else
-#define HS_ROWS_ID f16
-#define HS_KERNEL(name) name##_f16
-typedef _Float16 TuRow;
-#endif
-#define HS_ROWS_PARAM , const TuRow *rows
 #define HS_ROWS_READ rows
-#define HS_ROWS_ARG , reinterpret_cast<const TuRow *>(rows)
 #endif
 template <int METRIC, int S, int D16>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(flat_waves(S, D16)))) HS_KERNEL(flat_kernel)(DevIndex ix, SearchArgs a HS_ROWS_PARAM) {
@@ -1099,11 +983,11 @@ static hipError_t flat_launch_s(const DevIndex &ix, const SearchArgs &a, const v
   }
 }
 
-#if !defined(HS_TU_ROWS) || HS_TU_ROWS == 0
+#if HS_TU_ROWS == 0
 // Parity/debug: a sequence of candidate_set operations through this file's heap code (one wavefront; 1024 slots in LDS, the rest
 // in `spill`).  ops: 3 words each {0 = push | 1 = pop, key bits, id}; out_heap: the final array (2 words per element); out_pops:
 // the root each pop removed; out_n[0] = final size, out_n[1] = pops.
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+#if HS_TU_HAS_L2
 __global__ void __launch_bounds__(64) flat_heap_ops_kernel(const uint32_t *ops, uint32_t n_ops, uint2 *spill, uint2 *out_heap, uint2 *out_pops,
                                                             uint32_t *out_n, int wave_pop, uint32_t lds_slots) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -1117,19 +1001,19 @@ __global__ void __launch_bounds__(64) flat_heap_ops_kernel(const uint32_t *ops, 
     const uint32_t kind = uni(ops[3 * i]), key = uni(ops[3 * i + 1]), id = uni(ops[3 * i + 2]);
     if (kind == 0) {
       size++;
-      if (size < h.L) fh_push<false>(h, size, __uint_as_float(key), id, lane);
-      else fh_push<true>(h, size, __uint_as_float(key), id, lane);
+      if (size < h.L) heap_push<false>(h, size, __uint_as_float(key), id, lane);
+      else heap_push<true>(h, size, __uint_as_float(key), id, lane);
     } else if (size > 0) {
-      const uint2 root = fh_get<true>(h, 1);
+      const uint2 root = heap_get<true>(h, 1);
       if (lane == 0) out_pops[pops] = root;
       pops++;
       if (wave_pop && size < h.L) fh_pop_wave(h, size, lane);
-      else if (lane == 0) { if (size < h.L) fh_pop<false>(h, size); else fh_pop<true>(h, size); }
+      else if (lane == 0) { if (size < h.L) heap_pop<false>(h, size); else heap_pop<true>(h, size); }
       size--;
     }
     wave_sync();
   }
-  for (uint32_t s = lane; s < size; s += 64) out_heap[s] = fh_get<true>(h, s + 1);
+  for (uint32_t s = lane; s < size; s += 64) out_heap[s] = heap_get<true>(h, s + 1);
   if (lane == 0) { out_n[0] = size; out_n[1] = pops; }
 }
 hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, uint2 *d_heap, uint2 *d_pops, uint32_t *d_n, int wave_pop,
@@ -1139,7 +1023,7 @@ hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, 
 }
 #endif
 
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+#if HS_TU_HAS_L2
 bool flatk_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
   return ix.tile0 != nullptr && (ix.maxlevel == 0 || ix.uptile != nullptr) && ix.threshold_level == 0 && !ix.has_deleted && ix.n > 0 &&
          ix.n < kFDone && (ix.dim & 15u) == 0 && ef >= k && ef <= 512 && k <= 64;
@@ -1154,12 +1038,12 @@ size_t flatk_lds_bytes(uint32_t dim, uint32_t ef, uint32_t nb) { return flat_lay
 #endif
 
 // This object's launchers (engine.hpp), one per metric it holds.  (No filter-set form: launch_search refuses a filter set.)
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+#if HS_TU_HAS_L2
 hipError_t HS_LAUNCHER(flat, HS_ROWS_ID, l2)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *) {
   return flat_launch_s<METRIC_L2>(ix, a, rows, stream);
 }
 #endif
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
+#if HS_TU_HAS_IP
 hipError_t HS_LAUNCHER(flat, HS_ROWS_ID, ip)(const DevIndex &ix, const SearchArgs &a, const void *rows, hipStream_t stream, const FilterArgs *) {
   return flat_launch_s<METRIC_IP>(ix, a, rows, stream);
 }

@@ -12,7 +12,7 @@
 //     replaces one instance of it (the first lane whose column tops out at it bubbles the new key in) -- the reference's
 //     push_heap + pop_heap as far as any decision can see.  Ids come back at the end from the insertion log, and a query
 //     whose k-subset depends on the layout of the reference's heap (equal keys across the k-th boundary) replays the log
-//     through the libstdc++ mechanics, as the fast kernel does;
+//     through the libstdc++ mechanics (replay_boundary, search_finish.hpp: the function the fast and flat kernels call);
 //   * no nd[] / staging arrays in LDS: the new distances and ids of a hop stay in two registers until they are pushed.
 // Serves bare (no delete marks / filter) indexes with level-0 and upper-level tiles, threshold_level 0, dim % 16 == 0,
 // k <= 64, ef <= 256; everything else runs the fast / strict kernels.
@@ -30,6 +30,8 @@
 #include "engine.hpp"
 #include "heap_emul.hpp"
 #include "search_common.hpp"
+#include "search_finish.hpp"
+#include "search_tu.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
@@ -45,30 +47,6 @@ __host__ __device__ inline LeanLds lean_layout(uint32_t dim, uint32_t ef, uint32
   l.off_nd = l.off_nid + 64 * 4;
   l.total = l.off_nd + 64 * 4;
   return l;
-}
-
-// order-preserving image of an fp32 value in int32 (no NaNs here): comparisons and min / max become integer operations
-__device__ __forceinline__ int fkey(float d) {
-  const int b = (int)__float_as_uint(d);
-  return b ^ ((b >> 31) & 0x7FFFFFFF);
-}
-static constexpr int kKeyInf = 0x7F800000;   // fkey(+inf)
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#define HS_SHR_MAXI(ctrl) v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, ctrl, 0xf, 0xf, false))
-  HS_SHR_MAXI(0x111); HS_SHR_MAXI(0x112); HS_SHR_MAXI(0x114); HS_SHR_MAXI(0x118);
-#undef HS_SHR_MAXI
-  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
-  const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
-  return max(max(r0, r1), max(r2, r3));
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#define HS_SHR_MINI(ctrl) v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, ctrl, 0xf, 0xf, false))
-  HS_SHR_MINI(0x111); HS_SHR_MINI(0x112); HS_SHR_MINI(0x114); HS_SHR_MINI(0x118);
-#undef HS_SHR_MINI
-  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
-  const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
-  return min(min(r0, r1), min(r2, r3));
 }
 
 // Distances query (LDS) -> rows nid[0..cnt) (LDS); lane j < cnt receives the distance of row j.  8 lanes per row: lane s of a
@@ -255,7 +233,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
   }
   if (lane == 0) tlog[0] = make_uint2(__float_as_uint(curdist), cur);
   {   // top_candidates = {(curdist, cur)}
-    const int kc = fkey(curdist);
+    const int kc = dkey<METRIC>(curdist);
     if (lane == 0) {
       int c = kc;
 #pragma unroll
@@ -270,7 +248,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
   int rc = entry_marked ? 0 : 1;
   while (rc == 0) {
     if (__builtin_expect(cand_size == 0 && pending == 0, 0)) break;
-    if (__builtin_expect(fkey(next_d) > (n_acc >= ef ? lb_key : rmax_key), 0)) break;   // :340 candidate distance > lowerBound
+    if (__builtin_expect(dkey<METRIC>(next_d) > (n_acc >= ef ? lb_key : rmax_key), 0)) break;   // :340 candidate distance > lowerBound
     uint32_t id = kNone;
     if ((uint32_t)lane < stride) id = ix.tile0[(size_t)next_id * stride + lane];   // the node's whole level-0 list: one aligned tile
     n_hops++;
@@ -280,7 +258,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
       pending &= pending - 1;
       cand_size++;
 #ifdef HS_LEAN_NO_T2
-      cand_push_t<false>(cand, cand_size, __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), j)), __builtin_amdgcn_readlane(my_id, j), lane);
+      heap_push<false>(cand, cand_size, __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), j)), __builtin_amdgcn_readlane(my_id, j), lane);
 #else
       cand_push(cand, cand_size, __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_d), j)), __builtin_amdgcn_readlane(my_id, j), lane);
 #endif
@@ -309,7 +287,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
     // row loads go out first; pop_heap (:353-354) re-heapifies the LDS array while they are in flight
     auto pop_hook = [&]() {
 #ifdef HS_LEAN_NO_T2
-      if (lane == 0) cand_pop_t<false>(cand, cand_size);
+      if (lane == 0) heap_pop<false>(cand, cand_size);
 #else
       if (lane == 0) cand_pop(cand, cand_size);
 #endif
@@ -323,7 +301,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
     wave_sync();
     my_id = (uint32_t)lane < cnt ? nid[lane] : 0;
     // ---- accept (:403-452), adjacency order.  lowerBound only falls, so a candidate that fails it now never passes later.
-    const int my_key = (uint32_t)lane < cnt ? fkey(my_d) : kKeyInf;
+    const int my_key = (uint32_t)lane < cnt ? dkey<METRIC>(my_d) : kKeyInf;
     unsigned long long todo = hs_ballot(my_key < lb_key);
     float best_d = FLT_MAX;
     uint32_t best_id = 0;
@@ -400,7 +378,7 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
     const uint32_t idx = base + lane;
     uint2 e = make_uint2(0, 0);
     if (idx < n_acc) e = tlog[idx];
-    const bool mt = idx < n_acc && fkey(__uint_as_float(e.x)) <= kth;
+    const bool mt = idx < n_acc && dkey<METRIC>(__uint_as_float(e.x)) <= kth;
     const unsigned long long mb = hs_ballot(mt);
     const uint32_t at = nm + __popcll(mb & ((1ull << lane) - 1ull));
     if (mt && at < 64) { nd[at] = __uint_as_float(e.x); nid[at] = e.y; }
@@ -432,54 +410,13 @@ __device__ int search_one_lean(const DevIndex &ix, const SearchArgs &a, const ui
 #ifdef HS_LEAN_NO_REPLAY
     return 3;
 #endif
-    // the reference's result heap rebuilt exactly: the logged insertions replayed through libstdc++'s push_heap / pop_heap
-    // (hnswalg_slim.h:419-448) and the final nth_element (:2126) or pop_heap loop (:2019-2022), in the (dead by now) visited-set area
+    // the reference's result heap rebuilt from the log (search_finish.hpp), in the (dead by now) visited-set area
     if (lane == 0) atomicAdd(a.counters + 2, 1u);
-    Pair *top = reinterpret_cast<Pair *>(hash);
-    uint32_t ts = 0;
-    for (uint32_t base = 0; base < n_acc; base += 64) {
-      const uint32_t mm = min(64u, n_acc - base);
-      uint2 e = make_uint2(0, 0);
-      if ((uint32_t)lane < mm) e = tlog[base + lane];
-      for (uint32_t j = 0; j < mm; j++) {
-        const float d = __uint_as_float(__builtin_amdgcn_readlane(e.x, j));
-        const uint32_t nb = __builtin_amdgcn_readlane(e.y, j);
-        if (lane == 0) {
-          top[ts].d = d;
-          top[ts].id = nb;
-          push_heap(top, (long)ts + 1, LessD());
-          if (ts + 1 > ef) pop_heap(top, (long)ts + 1, LessD());
-        }
-        ts = min(ts + 1, ef);
-      }
-    }
-    if (lane == 0) {
-      if (a.mode == 0) {
-        if (ts >= k) nth_element(top, (long)k, (long)ts, LessD());
-      } else {
-        uint32_t t2 = ts;
-        while (t2 > k) { pop_heap(top, (long)t2, LessD()); t2--; }
-      }
-    }
-    wave_sync();
-    for (uint32_t i = lane; i < k; i += 64) {
-      const bool v = i < valid_n;
-      const Pair p = v ? top[i] : Pair{__builtin_inff(), 0};
-      const uint64_t label = v ? ix.labels[p.id] : ~0ull;
-      if (a.out_labels32) a.out_labels32[(size_t)qi * k + i] = v ? (uint32_t)label : 0xFFFFFFFFu;
-      if (a.out_labels64) a.out_labels64[(size_t)qi * k + i] = label;
-      if (a.out_dists) a.out_dists[(size_t)qi * k + i] = p.d;
-    }
+    replay_boundary(ix, a, qi, reinterpret_cast<Pair *>(hash), tlog, n_acc, valid_n, lane);
   }
   if (lane == 0) {
     if (a.out_counts) a.out_counts[qi] = valid_n;
-    if (a.stats) {
-      a.stats[qi * 4 + 0] = n_dist;
-      a.stats[qi * 4 + 1] = n_hops;
-      a.stats[qi * 4 + 2] = n_nbr;
-      a.stats[qi * 4 + 3] = replay ? 1u : a.pass_id;
-    }
-    a.status[qi] = ST_DONE;
+    write_stats(a, qi, n_dist, n_hops, n_nbr, replay ? 1u : a.pass_id);
   }
   return 0;
 }
@@ -513,7 +450,7 @@ static hipError_t lean_launch_s(const DevIndex &ix, const SearchArgs &a, hipStre
   return lean_launch_d<METRIC, 0>(ix, a, stream);
 }
 
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 0
+#if HS_TU_HAS_L2
 bool lean_supported(const DevIndex &ix, uint32_t ef, uint32_t k) {
   return ix.tile0 != nullptr && (ix.maxlevel == 0 || ix.uptile != nullptr) && ix.threshold_level == 0 && !ix.has_deleted && ix.n > 0 &&
          (ix.dim & 15u) == 0 && ef >= k && ef <= 256 && k <= 64;
@@ -526,7 +463,7 @@ hipError_t HS_LAUNCHER(lean, f32, l2)(const DevIndex &ix, const SearchArgs &a, c
   return lean_launch_s<METRIC_L2>(ix, a, stream);
 }
 #endif
-#if !defined(HS_TU_METRIC) || HS_TU_METRIC == 1
+#if HS_TU_HAS_IP
 hipError_t HS_LAUNCHER(lean, f32, ip)(const DevIndex &ix, const SearchArgs &a, const void *, hipStream_t stream, const FilterArgs *) {
   return lean_launch_s<METRIC_IP>(ix, a, stream);
 }

@@ -1,6 +1,6 @@
-// search_common.hpp -- device structures shared by the one-query-per-wavefront search kernels (beam_search.hip, lean_search.hip):
-// the exact two-tier visited set and the candidate min-heap with libstdc++ sift mechanics; and the launch helper of all three
-// kernel files (flat_search.hip too).
+// search_common.hpp -- device structures shared by the one-query-per-wavefront search kernels (beam_search.hip, lean_search.hip,
+// flat_search.hip): the exact two-tier visited set, the candidate min-heap's sifts with libstdc++ mechanics (one definition over
+// the heap types of all three), the int32 key image of a distance, and the launch helper.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -174,24 +174,26 @@ __device__ __forceinline__ bool vis_mark_one(Visited &v, uint32_t id, const Sear
 // region of global memory: a query whose heap outgrows its LDS share keeps going (its deepest heap levels
 // pay L2 latency) instead of being thrown away.  Same sift decisions as std::push_heap / pop_heap with
 // compare_by_first_rev (hnswalg_slim.h:177-183).
+// The sifts (heap_push, heap_pop) are written once, over any heap type H that provides heap_get<T2> / heap_set<T2> /
+// heap_get2<T2>(h, slot): CandHeap here (generic pointers), FlatHeap in flat_search.hip (LDS address-space pointers).
+// T2 = false: every slot touched is known to lie in LDS -> LDS-only code (no address tests, no global access, so no vmcnt
+// wait is generated and the row loads in flight around the pop stay in flight).
 struct CandHeap {
-  uint2 *lds, *glob;
+  uint2 *lds, *glob;   // slot s >= L at glob[s - L]
   uint32_t L;  // LDS slots
 };
-// T2 = false: the heap is known to fit its LDS share -> LDS-only code (no global access, so no vmcnt wait
-// is generated and the row loads in flight around the pop stay in flight).
 template <bool T2>
-__device__ __forceinline__ uint2 ch_get(const CandHeap &h, uint32_t s) {
+__device__ __forceinline__ uint2 heap_get(const CandHeap &h, uint32_t s) {
   if (!T2) return h.lds[s];
   return s < h.L ? h.lds[s] : h.glob[s - h.L];
 }
 template <bool T2>
-__device__ __forceinline__ void ch_set(const CandHeap &h, uint32_t s, uint2 v) {
+__device__ __forceinline__ void heap_set(const CandHeap &h, uint32_t s, uint2 v) {
   if (!T2 || s < h.L) h.lds[s] = v;
   else h.glob[s - h.L] = v;
 }
 template <bool T2>
-__device__ __forceinline__ uint4 ch_get2(const CandHeap &h, uint32_t s /*even*/) {
+__device__ __forceinline__ uint4 heap_get2(const CandHeap &h, uint32_t s /*even*/) {
   if (!T2) return *reinterpret_cast<const uint4 *>(&h.lds[s]);
   return s < h.L ? *reinterpret_cast<const uint4 *>(&h.lds[s]) : *reinterpret_cast<const uint4 *>(&h.glob[s - h.L]);
 }
@@ -200,55 +202,70 @@ __device__ __forceinline__ uint4 ch_get2(const CandHeap &h, uint32_t s /*even*/)
 // consecutive ancestor that compares strictly greater.  All ancestors of slot n-1 are known up front
 // ((n >> t) - 1 for t = 1, 2, ...), so the whole wave does it in one read and one write round: lane t-1
 // reads ancestor t, a ballot finds where the rise stops, the passed ancestors each move one level down.
-template <bool T2>
-__device__ __forceinline__ void cand_push_t(const CandHeap &h, uint32_t n /*size incl. new*/, float d, uint32_t id, int lane) {
+template <bool T2, class H>
+__device__ __forceinline__ void heap_push(const H &h, uint32_t n /*size incl. new*/, float d, uint32_t id, int lane) {
   const uint32_t anc = n >> (lane + 1);          // (index + 1) of this lane's ancestor; 0 = beyond the root
   const bool has = anc != 0 && lane < 31;
   uint2 p = make_uint2(0, 0);
-  if (has) p = ch_get<T2>(h, anc);               // element anc-1 lives at slot anc
+  if (has) p = heap_get<T2>(h, anc);             // element anc-1 lives at slot anc
   const unsigned long long rises = hs_ballot(has && __uint_as_float(p.x) > d);
   const uint32_t r = __ffsll((long long)~rises) - 1;  // number of consecutive ancestors passed
-  if ((uint32_t)lane < r) ch_set<T2>(h, n >> lane, p);  // ancestor t moves to the path node below it ((n >> (t-1)) - 1)
-  if ((uint32_t)lane == r) ch_set<T2>(h, n >> r, make_uint2(__float_as_uint(d), id));
-}
-__device__ __forceinline__ void cand_push(const CandHeap &h, uint32_t n, float d, uint32_t id, int lane) {
-  if (__builtin_expect(n < h.L, 1)) cand_push_t<false>(h, n, d, id, lane);  // slot n is the deepest slot touched
-  else cand_push_t<true>(h, n, d, id, lane);
+  if ((uint32_t)lane < r) heap_set<T2>(h, n >> lane, p);  // ancestor t moves to the path node below it ((n >> (t-1)) - 1)
+  if ((uint32_t)lane == r) heap_set<T2>(h, n >> r, make_uint2(__float_as_uint(d), id));
 }
 // std::pop_heap (one lane).  Returns nothing; the popped root was read by the caller beforehand.
-template <bool T2>
-__device__ __forceinline__ void cand_pop_t(const CandHeap &h, uint32_t n /*size before pop*/) {
+template <bool T2, class H>
+__device__ __forceinline__ void heap_pop(const H &h, uint32_t n /*size before pop*/) {
   if (n <= 1) return;
-  const uint2 v = ch_get<T2>(h, n);  // a[n-1]
+  const uint2 v = heap_get<T2>(h, n);  // a[n-1]
   const uint32_t len = n - 1;
   uint32_t hole = 0, child = 0;
   while (child < (len - 1) / 2) {
     child = 2 * (child + 1);
-    const uint4 two = ch_get2<T2>(h, child);  // a[child-1], a[child]
+    const uint4 two = heap_get2<T2>(h, child);  // a[child-1], a[child]
     const bool left = __uint_as_float(two.z) > __uint_as_float(two.x);  // comp(a[child], a[child-1])
-    ch_set<T2>(h, hole + 1, left ? make_uint2(two.x, two.y) : make_uint2(two.z, two.w));
+    heap_set<T2>(h, hole + 1, left ? make_uint2(two.x, two.y) : make_uint2(two.z, two.w));
     child = left ? child - 1 : child;
     hole = child;
   }
   if ((len & 1) == 0 && child == (len - 2) / 2) {
     child = 2 * (child + 1);
-    ch_set<T2>(h, hole + 1, ch_get<T2>(h, child));  // a[child-1]
+    heap_set<T2>(h, hole + 1, heap_get<T2>(h, child));  // a[child-1]
     hole = child - 1;
   }
   const float vd = __uint_as_float(v.x);
   while (hole > 0) {
     const uint32_t parent = (hole - 1) >> 1;
-    const uint2 p = ch_get<T2>(h, parent + 1);
+    const uint2 p = heap_get<T2>(h, parent + 1);
     if (!(__uint_as_float(p.x) > vd)) break;
-    ch_set<T2>(h, hole + 1, p);
+    heap_set<T2>(h, hole + 1, p);
     hole = parent;
   }
-  ch_set<T2>(h, hole + 1, v);
+  heap_set<T2>(h, hole + 1, v);
+}
+// (CandHeap's callers: the deepest slot touched, n, says whether the LDS-only form will do)
+__device__ __forceinline__ void cand_push(const CandHeap &h, uint32_t n, float d, uint32_t id, int lane) {
+  if (__builtin_expect(n < h.L, 1)) heap_push<false>(h, n, d, id, lane);
+  else heap_push<true>(h, n, d, id, lane);
 }
 __device__ __forceinline__ void cand_pop(const CandHeap &h, uint32_t n) {
-  if (__builtin_expect(n < h.L, 1)) cand_pop_t<false>(h, n);
-  else cand_pop_t<true>(h, n);
+  if (__builtin_expect(n < h.L, 1)) heap_pop<false>(h, n);
+  else heap_pop<true>(h, n);
 }
+
+// Order-preserving image of an fp32 distance in int32 (no NaNs): comparisons and min / max become integer operations.  Inner-product
+// distances (1 - <q, x>) take both signs, so the magnitude bits of a negative value are flipped; L2 distances are sums of squares,
+// >= +0 (never -0: the accumulators start at +0), whose bit patterns already order -- there the fold would change no bit.
+template <int METRIC>
+__device__ __forceinline__ int dkey(float d) {
+  const int b = (int)__float_as_uint(d);
+  return METRIC == METRIC_L2 ? b : (b ^ ((b >> 31) & 0x7FFFFFFF));
+}
+template <int METRIC>
+__device__ __forceinline__ float key_dist(int k) {
+  return __uint_as_float((uint32_t)(METRIC == METRIC_L2 ? k : (k ^ ((k >> 31) & 0x7FFFFFFF))));
+}
+static constexpr int kKeyInf = 0x7F800000;   // dkey(+inf)
 
 __device__ __forceinline__ void flag_query(const SearchArgs &a, uint32_t qi, uint32_t status, uint32_t counter, int lane) {
   if (lane == 0) {

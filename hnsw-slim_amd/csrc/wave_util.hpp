@@ -1,8 +1,9 @@
-// wave_util.hpp -- wavefront-level device helpers shared by beam_search.hip and slimq_search.hip (gfx950, wave64).
+// wave_util.hpp -- wavefront-level device helpers shared by the search kernel files (gfx950, wave64).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <climits>
 #include <cstdint>
 
 #include "dist_recipe.hpp"
@@ -70,6 +71,24 @@ __device__ __forceinline__ float wave_min_f32(float v) {
   const float r0 = __uint_as_float(__builtin_amdgcn_readlane(b, 15)), r1 = __uint_as_float(__builtin_amdgcn_readlane(b, 31));
   const float r2 = __uint_as_float(__builtin_amdgcn_readlane(b, 47)), r3 = __uint_as_float(__builtin_amdgcn_readlane(b, 63));
   return fminf(fminf(r0, r1), fminf(r2, r3));
+}
+
+// The same for int32 keys (search_common.hpp dkey), and the maximum: lanes outside a row's shift see the identity.
+__device__ __forceinline__ int wave_min_i32(int v) {
+#define HS_SHR_MINI(ctrl) v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, ctrl, 0xf, 0xf, false))
+  HS_SHR_MINI(0x111); HS_SHR_MINI(0x112); HS_SHR_MINI(0x114); HS_SHR_MINI(0x118);
+#undef HS_SHR_MINI
+  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
+  const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
+  return min(min(r0, r1), min(r2, r3));
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+#define HS_SHR_MAXI(ctrl) v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, ctrl, 0xf, 0xf, false))
+  HS_SHR_MAXI(0x111); HS_SHR_MAXI(0x112); HS_SHR_MAXI(0x114); HS_SHR_MAXI(0x118);
+#undef HS_SHR_MAXI
+  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
+  const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
+  return max(max(r0, r1), max(r2, r3));
 }
 
 template <int METRIC>

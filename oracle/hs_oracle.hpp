@@ -344,6 +344,7 @@ struct Counters {
   uint32_t max_cand = 0;    // peak size of the candidate heap
   uint32_t n_tie_evict = 0; // level-0 evictions from a full result heap whose key equals the new worst kept one: which of the
                             // equal entries stays is then decided by the heap's layout (test premise, not a reference quantity)
+  bool last_evict_tie = false;  // ... and whether the LAST such eviction was one: the result array then still holds its equal
 };
 
 struct cmp_max { bool operator()(const pairfi &a, const pairfi &b) const { return a.first < b.first; } };  // slim.h:169-175
@@ -399,7 +400,8 @@ inline void beam_level0(const Index &ix, const float *q, size_t ef, bool bare_bo
         }
         while (s.top.size() > ef) {                                // :434-448
           std::pop_heap(s.top.begin(), s.top.end(), cmp_max());
-          if (s.top.size() > 1 && s.top.back().first == s.top.front().first) c.n_tie_evict++;
+          c.last_evict_tie = s.top.size() > 1 && s.top.back().first == s.top.front().first;
+          if (c.last_evict_tie) c.n_tie_evict++;
           s.top.pop_back();
         }
         if (!s.top.empty()) lowerBound = s.top.front().first;      // :450-452

@@ -123,10 +123,13 @@ int hso_search_pq(void *p, const float *q, size_t nq, size_t k, float *out_d, ui
 
 // Test premise, not a reference quantity: per query, the level-0 evictions from a full result heap whose key equals the new worst
 // kept key (Counters::n_tie_evict) -- the event an ef == k search's answer hangs on.  pq = 0: the (q, k, tableint*) overload of a
-// Slim index, 1: the priority_queue overloads (either kind).  out: nq u32.
+// Slim index, 1: the priority_queue overloads (either kind).  out: nq u32.  pq | 2: instead of the count, 1 where the query's LAST
+// eviction was such a one (the final result array then holds an entry equal to one it lost), else 0.
 int hso_tie_evictions(void *p, const float *q, size_t nq, size_t k, int pq, uint32_t *out, int threads) {
   auto *h = (Handle *)p;
   int rc = 0;
+  const bool last = (pq & 2) != 0;
+  pq &= 1;
   if (!pq && h->kind == 0) { g_err = "hso_tie_evictions: the id-array overload exists on Slim indexes only"; return 1; }
   size_t dim = h->kind == 0 ? h->v.dim : h->s.dim;
 #pragma omp parallel num_threads(threads > 0 ? threads : 1)
@@ -140,7 +143,7 @@ int hso_tie_evictions(void *p, const float *q, size_t nq, size_t k, int pq, uint
         SlimResult r = !pq ? slim_search_ids(h->s, q + i * dim, k, s, ids.data())
                        : h->kind == 0 ? vanilla_search_pq(h->v, q + i * dim, k, s, res)
                                       : slim_search_pq(h->s, q + i * dim, k, s, res, h->mark_ep != 0);
-        out[i] = r.c.n_tie_evict;
+        out[i] = last ? (r.c.last_evict_tie ? 1u : 0u) : r.c.n_tie_evict;
       } catch (std::exception &e) {
 #pragma omp critical
         { g_err = e.what(); rc = 1; }

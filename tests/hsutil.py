@@ -396,12 +396,13 @@ class OracleIndex:
             raise RuntimeError(self.o.err())
         return dict(labels=out, raw_d=rd, raw_i=ri, raw_sz=rs, counters=cn)
 
-    def tie_evictions(self, q, k, pq, threads=1):
+    def tie_evictions(self, q, k, pq, threads=1, last=False):
         """Per query, the evictions from a full result heap whose key equals the new worst kept key, in search_pq (pq=True) or
-        search_ids (pq=False, Slim only): what an ef == k search's answer hangs on (a test premise, not a reference quantity)."""
+        search_ids (pq=False, Slim only): what an ef == k search's answer hangs on (a test premise, not a reference quantity).
+        last=True: instead of the count, 1 where the query's last eviction was such a one."""
         q = np.ascontiguousarray(q, np.float32)
         out = np.zeros(q.shape[0], np.uint32)
-        if self.o.L.hso_tie_evictions(self.h, q.ctypes.data, q.shape[0], k, 1 if pq else 0, out.ctypes.data, threads):
+        if self.o.L.hso_tie_evictions(self.h, q.ctypes.data, q.shape[0], k, (1 if pq else 0) | (2 if last else 0), out.ctypes.data, threads):
             raise RuntimeError(self.o.err())
         return out
 

@@ -1,4 +1,4 @@
-"""The flat kernel's candidate-heap code (csrc/flat_search.hip: fh_push, fh_pop, fh_pop_wave) against a step-for-step Python
+"""The flat kernel's candidate-heap code (csrc/search_common.hpp: heap_push, heap_pop, in the flat kernel's FlatHeap instantiation; csrc/flat_search.hip: fh_pop_wave) against a step-for-step Python
 restatement of libstdc++'s std::push_heap / std::pop_heap with compare_by_first_rev (hnswalg_slim.h:177-183), on tie-heavy
 operation sequences: the array layout after every sequence and every popped root must be identical."""
 import random

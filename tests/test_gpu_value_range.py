@@ -5,7 +5,7 @@ The rest of the suite runs on integers 0..255, mixtures with |x| in the tens, or
 between 1 and 1e6, IP distances all in [0, 2] or all far below zero.  Here (tests/value_range.py) one base draw is multiplied by a
 power of two, exactly, so that
   * ip_cross: 1 - <q, x> changes sign inside one query's result array -- the sign-folded int32 key images of the flat and lean
-    kernels (dkey<METRIC_IP>, fkey) order a set that holds both signs;
+    kernels (dkey<METRIC_IP>) order a set that holds both signs;
   * l2_subnormal: every product, partial sum and distance is a subnormal float -- the packed-f32 multiplies and adds, the fma chains,
     the DPP reductions and cross-lane sums keep them, as the reference compiled without fast-math does;
   * large: distances above 2^100 next to the FLT_MAX sentinels and reduction identities;
