@@ -117,36 +117,6 @@ int hs_device_count(void) {
   return n;
 }
 
-// upper-level tiles for the greedy descent (see engine.hpp): slot t = up_ptr entry t, {neighbour id, the neighbour's up_base}
-static std::vector<uint32_t> build_uptile(const PackedIndex &p, uint32_t &up_stride) {
-  up_stride = 0;
-  std::vector<uint32_t> ut;
-  size_t max_up = 0;
-  for (size_t t = 0; t + 1 < p.up_ptr.size(); t++)
-    if (p.up_ptr[t + 1] > p.up_ptr[t]) max_up = std::max<size_t>(max_up, p.up_ptr[t + 1] - p.up_ptr[t]);
-  if (p.up_ptr.empty() || max_up > 64) return ut;
-  up_stride = std::max<uint32_t>(16, (uint32_t)((max_up + 15) / 16 * 16));
-  ut.assign(p.up_ptr.size() * (size_t)up_stride * 2, 0xFFFFFFFFu);
-  // a node with L upper levels owns L+1 consecutive up_ptr entries (L list starts + one terminator), in id order
-  std::vector<uint32_t> owners;
-  for (size_t i = 0; i < p.n; i++)
-    if (p.up_base[i] != PackedIndex::NONE) owners.push_back((uint32_t)i);
-  for (size_t o = 0; o < owners.size(); o++) {
-    const uint32_t b0 = p.up_base[owners[o]];
-    const uint32_t end = o + 1 < owners.size() ? p.up_base[owners[o + 1]] : (uint32_t)p.up_ptr.size();
-    for (uint32_t t = b0; t + 1 < end; t++) {
-      const uint32_t s0 = p.up_ptr[t], e0 = p.up_ptr[t + 1];
-      for (uint32_t j = 0; j < e0 - s0; j++) {
-        const uint32_t nb = p.cols[s0 + j];
-        ut[((size_t)t * up_stride + j) * 2] = nb;
-        ut[((size_t)t * up_stride + j) * 2 + 1] = p.up_base[nb];
-      }
-    }
-  }
-  return ut;
-}
-uint32_t tile_stride_for(size_t max_deg0) { return max_deg0 <= 64 ? std::max<uint32_t>(16, (uint32_t)((max_deg0 + 15) / 16 * 16)) : 0; }
-
 // the graph-structure arrays that are small next to the vectors and tiles: uploaded whole (also after every call that changed
 // nodes, write_changed), and with them what the host keeps of `p`: the label / mark mirrors, the mark counters, hs_info
 hs_status upload_small(hs_index *ix, const PackedIndex &p) {
@@ -160,7 +130,7 @@ hs_status upload_small(hs_index *ix, const PackedIndex &p) {
   DevIndex &d = ix->dev;
   d.row_ptr0 = ix->row_ptr0.p; d.cols = ix->cols.p; d.up_base = ix->up_base.p; d.up_ptr = ix->up_ptr.p;
   d.uptile = up_stride ? reinterpret_cast<const uint2 *>(ix->uptile.p) : nullptr; d.up_stride = up_stride;
-  d.ep_base = p.n ? p.up_base[p.enterpoint] : 0xFFFFFFFFu;
+  d.ep_base = ep_base_of(p);
   d.n = (uint32_t)p.n; d.dim = (uint32_t)p.dim; d.maxlevel = p.maxlevel; d.threshold_level = p.threshold_level;
   d.enterpoint = p.enterpoint; d.kind = p.kind; d.metric = p.metric;
   ix->host_labels = p.labels;
@@ -187,13 +157,10 @@ hs_status upload(hs_index *ix, const PackedIndex &p) {
     hs_status ns = upload_narrow_from_host(ix, p.vec.data(), p.n, p.dim, cap);
     if (ns != HS_OK) return ns;
   }
-  // level-0 adjacency tiles: node i's ids padded with 0xFFFFFFFF to a fixed, 64-byte-multiple stride
+  // level-0 adjacency tiles (host_tiles.hpp)
   const uint32_t stride = tile_stride_for(p.max_deg0);
   if (stride) {
-    std::vector<uint32_t> tile((size_t)p.n * stride, 0xFFFFFFFFu);
-    for (size_t i = 0; i < p.n; i++)
-      std::copy(p.cols.begin() + p.row_ptr0[i], p.cols.begin() + p.row_ptr0[i + 1], tile.begin() + i * stride);
-    HIP_TRY(upload_cap(ix->tile0, tile, cap * stride));
+    HIP_TRY(upload_cap(ix->tile0, build_tile0(p, stride), cap * stride));
   }
   HIP_TRY(upload_cap(ix->labels, p.labels, cap));
   HIP_TRY(upload_cap(ix->deleted, p.deleted, cap));
@@ -208,7 +175,6 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
                            int narrow_fmt = ROWS_F32) {
   if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
-  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   PackedIndex p;
   std::unique_ptr<SlimGraph> keep_slim;
   std::unique_ptr<VanillaGraph> keep_vanilla;
@@ -233,6 +199,8 @@ static hs_status load_from(const BinSource &src, int kind, int metric, size_t di
   } catch (std::exception &e) {
     return from_exception(e);
   }
+  // only now: a hostile file is refused as such (the loaders ran index_check.hpp) on a machine without a device too
+  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   hs_index *ix = new hs_index();
   ix->device = device;
   if (keep_slim) { ix->cap_rows = max_elements; ix->host_slim = std::move(keep_slim); }
@@ -265,7 +233,7 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
     new_count = r.pod<uint64_t>();
     const uint64_t n_old = r.pod<uint64_t>(), n_new = r.pod<uint64_t>();
     if (new_count > ix->cap_rows || new_count < g.count || n_old + n_new > (1ull << 32)) return fail(HS_ERR_CAPACITY, "patch exceeds max_elements");
-    // stage the records first: a malformed stream must leave the index untouched
+    // stage the records first: a refused stream leaves the index untouched -- the device arrays AND the host image, byte for byte
     struct Rec { uint32_t id; char head[16]; std::vector<char> blob; std::vector<char> vec; bool is_new; };
     std::vector<Rec> recs((size_t)(n_old + n_new));
     for (size_t i = 0; i < recs.size(); i++) {
@@ -276,8 +244,8 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
       const uint32_t nsz = r.pod<uint32_t>();
       int32_t level; uint32_t total;
       memcpy(&level, rc.head, 4); memcpy(&total, rc.head + 4, 4);
-      if (rc.id >= new_count || level < 0 || level > 64 || (nsz != 0 && nsz != 2 * (uint32_t)level + 4 * total))
-        return fail(HS_ERR_CORRUPT, "Index seems to be corrupted or unsupported");
+      if (rc.id >= new_count || level < 0 || level > 64 || (nsz != 2 * (uint64_t)level + 4 * (uint64_t)total && !(nsz == 0 && total == 0)))
+        return fail(HS_ERR_CORRUPT, kCorruptText);
       rc.blob.resize(nsz);
       if (nsz) r.bytes(rc.blob.data(), nsz);
       if (to_add && rc.is_new) { rc.vec.resize(dim * 4); r.bytes(rc.vec.data(), dim * 4); }
@@ -291,6 +259,27 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
         const size_t j = first_unfit(v.data(), dim, ix->row_fmt);
         if (j < dim) return fail(HS_ERR_UNSUPPORTED, "patch refused: " + unfit_message(rc.id, j, v[j], ix->row_fmt));
       }
+    // The image as it would stand after the records, checked whole (index_check.hpp) before a byte of it changes: a staged record
+    // answers for its node (the last one of an id, as the writes below), the image for every other, the zeroed element for a node
+    // beyond the old count that has no record.  One pass over the lists, as the repacking below is.
+    {
+      static const std::vector<char> none;
+      std::vector<int64_t> rec_of(new_count, -1);
+      for (size_t i = 0; i < recs.size(); i++) rec_of[recs[i].id] = (int64_t)i;
+      auto head = [&](size_t i, size_t at) -> uint32_t {
+        uint32_t v = 0;
+        if (rec_of[i] >= 0) memcpy(&v, recs[(size_t)rec_of[i]].head + at, 4);
+        else if (i < g.count) memcpy(&v, g.el((uint32_t)i) + at, 4);
+        return v;
+      };
+      auto blob_of = [&](size_t i) -> const std::vector<char> & {
+        if (rec_of[i] >= 0) return head(i, 4) == 0 ? none : recs[(size_t)rec_of[i]].blob;
+        return i < g.count ? g.blobs[i] : none;
+      };
+      if (check_chal(new_count, g.enterpoint, g.maxlevel, g.threshold_level, [&](size_t i) { return (int)(int32_t)head(i, 0); },
+                     [&](size_t i) { return (size_t)head(i, 4); }, blob_of, /*unlisted_ok=*/true))   // (a chunk of a diff: P7's exception)
+        return fail(HS_ERR_CORRUPT, kCorruptText);
+    }
     g.elements.resize(new_count * spe, 0);
     g.blobs.resize(new_count);
     for (Rec &rc : recs) {
@@ -326,9 +315,28 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
   if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
   if (n && enterpoint >= n) return fail(HS_ERR_INVALID, "enter point out of range");
-  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   PackedIndex p;
   try {
+    {   // the preconditions of index_check.hpp on the caller's arrays, before anything is packed from them
+      std::vector<size_t> first(n);
+      size_t t = 0;
+      for (size_t i = 0; i < n; i++) {
+        if (levels[i] < 0 || levels[i] > maxlevel) return fail(HS_ERR_INVALID, "level out of range");
+        first[i] = t;
+        t += (size_t)levels[i] + 1;
+      }
+      auto level_of = [&](size_t i) { return (int)levels[i]; };
+      const char *bad = check_entry(n, enterpoint, maxlevel, kind == HS_KIND_SLIM ? threshold_level : 0, true, level_of);
+      if (!bad)
+        bad = check_lists(n, level_of, [](size_t) { return true; }, [&](size_t i, int l, const uint32_t *&ids, size_t &cnt) {
+          const uint64_t s0 = list_ptr[first[i] + l], e0 = list_ptr[first[i] + l + 1];
+          if (e0 < s0) return false;
+          ids = list_ids + s0;
+          cnt = e0 - s0;
+          return true;
+        });
+      if (bad) return fail(HS_ERR_INVALID, bad);
+    }
     p.kind = kind; p.metric = (Metric)metric; p.n = n; p.dim = dim;
     p.maxlevel = maxlevel; p.threshold_level = kind == HS_KIND_SLIM ? threshold_level : 0; p.enterpoint = enterpoint;
     p.vec.assign(vectors, vectors + n * dim);
@@ -376,6 +384,7 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory");
   }
+  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   hs_index *ix = new hs_index();
   ix->device = device;
   hs_status s = upload(ix, p);

@@ -20,6 +20,7 @@
 #include "narrow_rows.hpp"
 #include "host_graph.hpp"
 #include "packed_index.hpp"
+#include "host_tiles.hpp"
 #include "rabitq_host.hpp"
 #include "search_plan.hpp"
 #include "slim_diff.hpp"
@@ -172,7 +173,6 @@ hs_status fail(hs_status s, const std::string &msg);
 hs_status from_exception(const std::exception &e);
 hs_status upload(hs_index *ix, const PackedIndex &p);
 hs_status upload_small(hs_index *ix, const PackedIndex &p);
-uint32_t tile_stride_for(size_t max_deg0);
 hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out);
 // capi_resident.cpp
 // The device side of a call that changed the host image (packed as `p`, without rows; row_of(i) reads row i of the image): `changed`

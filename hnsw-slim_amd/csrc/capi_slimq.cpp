@@ -44,20 +44,23 @@ hs_status load_slimq(const BinSource &src, int metric, size_t dim, int device, h
 // as they are.  The record fields go up as they lie in the image and are freed once the kernels have read them.
 hs_status slimq_make_resident(std::unique_ptr<SlimQGraph> qp, int device, hs_index **out) {
   if (!qp || !out) return fail(HS_ERR_INVALID, "null argument");
-  if (hs_device_count() <= device || device < 0) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   const auto t0 = std::chrono::steady_clock::now();
   const SlimQGraph &q = *qp;
   PackedIndex p;
   try {
     if (q.rot.trunc < 64) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports dim >= 64");
+    if (q.check()) return fail(HS_ERR_CORRUPT, kCorruptText);   // index_check.hpp: the image may come from a conversion, not a file
+    for (uint32_t c : q.cluster)   // g_add[cluster] in the kernel's estimate (slimq_search.hip)
+      if (c >= q.num_cluster) return fail(HS_ERR_CORRUPT, kCorruptText);
     pack_slimq(p, q);
-    if (q.count && q.enterpoint >= q.count) return fail(HS_ERR_CORRUPT, "Index seems to be corrupted or unsupported");
   } catch (std::bad_alloc &) {
     return fail(HS_ERR_NOMEM, "Not enough memory: loadIndex failed to allocate");
   } catch (std::exception &e) {
     return from_exception(e);
   }
   if (q.count > 0xFFFFFFF0ull || p.up_ptr.size() > 0xFFFFFFF0ull) return fail(HS_ERR_UNSUPPORTED, "SlimQ index too large");
+  // only now: a hostile image is refused as such on a machine without a device too
+  if (hs_device_count() <= device || device < 0) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
   std::unique_ptr<hs_index> ix(new hs_index());
   ix->device = device;
   hs_status s = upload(ix.get(), p);
@@ -102,7 +105,7 @@ hs_status slimq_make_resident(std::unique_ptr<SlimQGraph> qp, int device, hs_ind
   DevSlimQ &d = ix->sq;
   d.rec = ix->q_rec.p; d.ftile = stride ? ix->q_ftile.p : nullptr; d.raw = nullptr;
   d.uptile = up_stride ? ix->q_uptile.p : nullptr; d.up_stride = up_stride;
-  d.ep_base = q.count ? p.up_base[q.enterpoint] : 0xFFFFFFFFu; d.cent = ix->q_cent.p; d.flips = ix->q_flips.p;
+  d.ep_base = ep_base_of(p); d.cent = ix->q_cent.p; d.flips = ix->q_flips.p;
   d.rec_words = rw; d.padded = (uint32_t)q.padded; d.trunc = (uint32_t)q.rot.trunc; d.ncl = (uint32_t)q.num_cluster;
   d.fht_scale = q.rot.fac;
   d.t_const = rq_default_tconst(q.padded, 1);

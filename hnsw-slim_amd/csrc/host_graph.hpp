@@ -26,6 +26,7 @@
 
 #include "dist_recipe.hpp"
 #include "host_parallel.hpp"
+#include "index_check.hpp"
 
 namespace hs {
 
@@ -453,10 +454,22 @@ struct VanillaGraph {
       }
     }
     if (r.in.tellg() != total) throw std::runtime_error("Index seems to be corrupted or unsupported");  // :835-836
+    if (check()) throw std::runtime_error(kCorruptText);   // before any caller indexes with an id, a count or a level of the file
     locks.reset(new std::mutex[std::max<size_t>(max_elements, count)]);
     level_gen = std::default_random_engine();
   }
   size_t num_deleted() const { size_t c = 0; for (size_t i = 0; i < count; i++) c += deleted(i); return c; }
+  // The first precondition of index_check.hpp this image violates, nullptr when it is safe to pack and to search.
+  const char *check() const {
+    auto level_of = [&](size_t i) { return levels[i]; };
+    if (const char *bad = check_entry(count, enterpoint, maxlevel, 0, true, level_of)) return bad;
+    return check_lists(count, level_of, [](size_t) { return true; }, [&](size_t i, int l, const uint32_t *&ids, size_t &cnt) {
+      const uint32_t *ll = list_at((uint32_t)i, l);
+      cnt = cnt_of(ll);
+      ids = ll + 1;
+      return cnt <= (l ? maxM : maxM0);
+    });
+  }
 };
 
 
@@ -647,11 +660,17 @@ struct SlimGraph {
     blobs.assign(count, {});
     for (size_t i = 0; i < count; i++) {
       uint32_t sz = r.pod<uint32_t>();
-      if (sz == 0 || total(i) == 0) continue;
-      if (sz != 2 * (uint32_t)level(i) + 4 * total(i)) throw std::runtime_error("Index seems to be corrupted or unsupported");
+      if (total(i) == 0) continue;   // no blob follows (save() above; hnswalg_slim.h:745-748)
+      if (level(i) < 0 || sz != 2 * (uint64_t)level(i) + 4 * (uint64_t)total(i)) throw std::runtime_error("Index seems to be corrupted or unsupported");
       blobs[i].resize(sz);
       r.bytes(blobs[i].data(), sz);
     }
+    if (check()) throw std::runtime_error(kCorruptText);   // before any caller indexes with an id, an offset or a level of the file
+  }
+  // The first precondition of index_check.hpp this image violates, nullptr when it is safe to pack and to search.
+  const char *check() const {
+    return check_chal(count, enterpoint, maxlevel, threshold_level, [&](size_t i) { return (int)level((uint32_t)i); },
+                      [&](size_t i) { return (size_t)total((uint32_t)i); }, [&](size_t i) -> const std::vector<char> & { return blobs[i]; });
   }
 };
 

@@ -86,16 +86,8 @@ struct PackedIndex {
   template <class LF, class TF, class BF>
   void pack_chal(LF level_of, TF total_of, BF blob_of) {
     row_ptr0.assign(n + 1, 0); up_base.assign(n, NONE); up_ptr.clear(); cols.clear();
-    auto slice = [&](size_t i, int lvl, const uint32_t *&ids, size_t &cnt) {
-      const int L = level_of(i);
-      const std::vector<char> &blob = blob_of(i);
-      const uint16_t *off = (const uint16_t *)blob.data();
-      size_t s = lvl == 0 ? 0 : off[lvl - 1];
-      size_t e = lvl == L ? total_of(i) : off[lvl];
-      if (e < s || e > total_of(i) || blob.size() < 2 * (size_t)L + 4 * (size_t)total_of(i))
-        throw std::runtime_error("Index seems to be corrupted or unsupported");
-      ids = (const uint32_t *)(blob.data() + 2 * (size_t)L) + s;
-      cnt = e - s;
+    auto slice = [&](size_t i, int lvl, const uint32_t *&ids, size_t &cnt) {   // (index_check.hpp P5: the one copy of the offsets test)
+      if (!chal_slice(level_of(i), total_of(i), blob_of(i), lvl, ids, cnt)) throw std::runtime_error(kCorruptText);
     };
     for (size_t i = 0; i < n; i++) {
       if (!blob_of(i).empty()) {

@@ -337,11 +337,18 @@ struct SlimQGraph {
     blobs.assign(count, {});
     for (size_t i = 0; i < count; i++) {
       const uint32_t sz = r.pod<uint32_t>();
-      if (sz == 0 || totals[i] == 0) continue;
-      if (sz != 2 * (uint32_t)level[i] + 4 * totals[i]) throw std::runtime_error("Index seems to be corrupted or unsupported");
+      if (totals[i] == 0) continue;   // no blob follows (save() above)
+      if (level[i] < 0 || sz != 2 * (uint64_t)level[i] + 4 * (uint64_t)totals[i]) throw std::runtime_error("Index seems to be corrupted or unsupported");
       blobs[i].resize(sz);
       r.bytes(blobs[i].data(), sz);
     }
+    if (check()) throw std::runtime_error(kCorruptText);   // before any caller indexes with an id, an offset or a level of the file
+  }
+  // The first precondition of index_check.hpp this image violates, nullptr when it is safe to pack and to search (a graph that
+  // reaches slimq_make_resident from a conversion and not from a file is checked there).
+  const char *check() const {
+    return check_chal(count, enterpoint, maxlevel, threshold_level, [&](size_t i) { return (int)level[i]; },
+                      [&](size_t i) { return (size_t)total(i); }, [&](size_t i) -> const std::vector<char> & { return blobs[i]; });
   }
 
   // CPU harness: take the graph of a HierarchicalNSWSlim file as it is and quantise its vectors.  (The reference

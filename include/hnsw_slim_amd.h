@@ -26,7 +26,10 @@ typedef struct hs_index hs_index;
 typedef enum {
   HS_OK = 0,
   HS_ERR_IO = 1,          /* "Cannot open file"                         hnswalg.h:785, hnswalg_slim.h:757 */
-  HS_ERR_CORRUPT = 2,     /* "Index seems to be corrupted or unsupported" hnswalg.h:823-836 */
+  HS_ERR_CORRUPT = 2,     /* "Index seems to be corrupted or unsupported" hnswalg.h:823-836.  Also every file, conversion input and
+                           * patch stream whose graph would send a kernel out of bounds (the preconditions of csrc/index_check.hpp:
+                           * ids, list counts and offsets, levels, enter point, level ownership).  Guaranteed: a refused input has
+                           * reached no device array, and an index it was meant for, host image included, is exactly as before. */
   HS_ERR_NOMEM = 3,       /* "Not enough memory: ..."                   hnswalg_slim.h:785-788 */
   HS_ERR_INVALID = 4,     /* bad argument                                */
   HS_ERR_UNSUPPORTED = 5, /* e.g. SlimQ with dim < 64, brute force k > 64  */
@@ -83,7 +86,11 @@ hs_status hs_index_load_mem(const void *bytes, size_t len, int kind, int metric,
  * nothing at all.  The lists are stored as given and answered as the reference answers them: its visited array skips the later
  * occurrences at level 0 (hnswalg.h:392-393), its upper-level descent has no visited array and evaluates a repeated id again
  * (:1389-1415), and the counters say so.  (An index with a level-0 list that repeats an id is served by the fast / strict kernels, never
- * by the flat kernel: hs_plan_in.has_dup0.)  n == 0 is an index without elements: every search on it returns count 0. */
+ * by the flat kernel: hs_plan_in.has_dup0.)  n == 0 is an index without elements: every search on it returns count 0.
+ * What the arrays must satisfy (csrc/index_check.hpp; HS_ERR_INVALID otherwise, before anything is uploaded, no index created):
+ * 0 <= levels[i] <= maxlevel, enterpoint < n, levels[enterpoint] >= maxlevel >= 0, threshold_level >= 0, list_ptr non-decreasing,
+ * every id < n, and every id in a level-l list (l >= 1) names a node of level >= l.  The arrays are checked before the device is
+ * asked for: without a device, bad arrays report HS_ERR_INVALID and good ones HS_ERR_DEVICE. */
 hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, const float *vectors, const uint64_t *labels,
                                     const uint8_t *deleted, const int32_t *levels, const uint64_t *list_ptr,
                                     const uint32_t *list_ids, uint32_t enterpoint, int32_t maxlevel, int32_t threshold_level,
@@ -94,7 +101,12 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
  * (new node) | u32 neighborsSize | blob | the vector (new node, to_add).  Applies to a HS_KIND_SLIM index that was loaded with
  * max_elements > its element count (the reference needs the same room, hnswalg_slim.h:784).  Only the changed nodes' rows of the
  * vectors and level-0 tiles are rewritten in HBM; the small structure arrays are rebuilt.  Like the reference, the stream
- * does not move the enter point.  Not to be called while a search on this index is in flight. */
+ * does not move the enter point.  Not to be called while a search on this index is in flight.
+ * The records are staged and the image as it would stand after them is checked whole (csrc/index_check.hpp: a staged record answers
+ * for its node, the image for every other; a chunk of a diff may name new nodes whose records come in a later chunk: until then they
+ * have no lists, which every kernel tests) before a byte changes.  A refused stream (HS_ERR_CORRUPT, HS_ERR_CAPACITY,
+ * HS_ERR_UNSUPPORTED) has reached no device array and leaves the host image byte for byte as it was: hs_slim_index_save, the next
+ * patch and hs_slim_convert_diff work from the unchanged image. */
 hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add);
 /* ---- live updates of a resident vanilla index: addPoint, markDelete, unmarkDelete, saveIndex, getDataByLabel ----------------
  * A HS_KIND_HNSW index loaded with max_elements > its element count keeps its host image (as a patchable Slim index does) and

@@ -40,20 +40,23 @@ def parse_vanilla(raw):
     rows = l0[:, off_data:off_data + 4 * dim].copy().view(np.float32)
     labels = l0[:, label_off:label_off + 8].copy().view(np.uint64)[:, 0]
     per = 4 + 4 * maxM
-    lists = []
+    lists, counts = [], []
     for i in range(count):
         (sz,) = struct.unpack_from("<I", raw, pos)
         pos += 4
         assert sz % per == 0
-        node = [ids0[i, :cnt0[i]].copy()]
+        node, cnts = [ids0[i, :cnt0[i]].copy()], [int(cnt0[i])]
         for lv in range(sz // per):
             (c,) = struct.unpack_from("<H", raw, pos + lv * per)
-            node.append(np.frombuffer(raw, np.uint32, c, pos + lv * per + 4).copy())
+            cnts.append(c)
+            node.append(np.frombuffer(raw, np.uint32, min(c, maxM), pos + lv * per + 4).copy())
         pos += sz
         lists.append(node)
+        counts.append(cnts)
     assert pos == len(raw)
-    return dict(count=count, dim=dim, maxlevel=maxlevel, enterpoint=ep, maxM=maxM, maxM0=maxM0, M=M, efC=efC, lists=lists, labels=labels,
-                rows=rows, marks=marks)
+    # counts[node][level]: the count words as the file holds them; a list is cut at its block's capacity (maxM0 / maxM ids)
+    return dict(count=count, dim=dim, maxlevel=maxlevel, enterpoint=ep, maxM=maxM, maxM0=maxM0, M=M, efC=efC, lists=lists, counts=counts,
+                labels=labels, rows=rows, marks=marks)
 
 
 def write_slim(g, threshold_level=0, has_deleted=None, garbage_seed=12345):
@@ -102,23 +105,25 @@ def parse_slim(raw, dim):
     pos += n * spe
     level = el[:, 0:4].copy().view(np.int32)[:, 0]
     total = el[:, 4:8].copy().view(np.uint32)[:, 0]
-    lists = []
+    lists, offsets = [], []
     for i in range(n):
         (sz,) = struct.unpack_from("<I", raw, pos)
         pos += 4
         L, T = int(level[i]), int(total[i])
-        assert sz == 2 * L + 4 * T
+        assert T == 0 or sz == 2 * L + 4 * T   # the size word of a node without neighbours is not used: no blob follows it (:745-748)
         if sz == 0 or T == 0:
             lists.append([np.zeros(0, np.uint32) for _ in range(L + 1)])
+            offsets.append(None)
             continue
         off = np.frombuffer(raw, np.uint16, L, pos).astype(np.int64)
+        offsets.append(off)
         ids = np.frombuffer(raw, np.uint32, T, pos + 2 * L)
         pos += sz
         bounds = [0] + list(off) + [T]
         lists.append([ids[bounds[l]:bounds[l + 1]].copy() for l in range(L + 1)])
     assert pos == len(raw)
     return dict(count=n, dim=dim, maxlevel=hdr[6], threshold_level=hdr[7], enterpoint=hdr[8], maxM=hdr[9], maxM0=hdr[10], M=hdr[11],
-                efC=hdr[12], has_deleted=hdr[13], level=level, lists=lists, labels=el[:, 8:16].copy().view(np.uint64)[:, 0],
+                efC=hdr[12], has_deleted=hdr[13], level=level, total=total, offsets=offsets, lists=lists, labels=el[:, 8:16].copy().view(np.uint64)[:, 0],
                 rows=el[:, 24:].copy().view(np.float32))
 
 
@@ -149,7 +154,7 @@ def parse_slimq(raw):
     for i in range(n):
         (sz,) = struct.unpack_from("<I", raw, pos)
         pos += 4
-        assert sz == 2 * int(level[i]) + 4 * int(total[i])
+        assert total[i] == 0 or sz == 2 * int(level[i]) + 4 * int(total[i])   # (as in parse_slim)
         if sz and total[i]:
             blobs.append(bytes(raw[pos:pos + sz]))
             pos += sz
