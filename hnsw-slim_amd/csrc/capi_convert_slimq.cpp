@@ -1,35 +1,15 @@
 // capi_convert_slimq.cpp -- the C ABI (include/hnsw_slim_amd.h): HierarchicalNSWSlimQ::convertFromHNSW with its two steps on a
 // device (convert_slimq.hip) -- the graph passes, the RaBitQ records -- each beside its host form, and the two chained in memory.
+// (The file-to-file graph passes, hs_convert_slimq_graph_gpu, stand with the other three converters of that frame in capi_build.cpp.)
 #include "capi_internal.hpp"
-
-#include <chrono>
 
 #include "host_rq_graph.hpp"
 #include "rabitq_host.hpp"
 #include "slim_convert_gpu.hpp"
 #include "slimq_chain.hpp"
 
-namespace {
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-// what every entry below is refused for before a file is read (the refusals of hs_convert_slimq_graph / hs_convert_slimq)
-hs_status metric_ok(int metric) {
-  return metric == HS_METRIC_L2 || metric == HS_METRIC_IP ? HS_OK : fail(HS_ERR_INVALID, "bad metric");
-}
-
-}  // namespace
-
-// (the functions from here to the first entry are shared with capi_slimq_resident.cpp: slimq_chain.hpp)
-SlimParams slim_params(int threshold_level, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0,
-                       size_t top_degree_M, size_t low_degree_m) {
-  SlimParams p;
-  p.threshold_level = threshold_level;
-  p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
-  p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
-  return p;
-}
+// (the functions from here to the first entry are shared with capi_build.cpp and capi_slimq_resident.cpp: slimq_chain.hpp)
+// what every records entry is refused for before a file is read (the refusals of hs_convert_slimq)
 hs_status slimq_records_args_ok(int metric, size_t dim, const float *centroids, size_t num_cluster) {
   if (!centroids || num_cluster == 0) return fail(HS_ERR_INVALID, "bad argument");
   if (dim < 64 || dim >= 4096) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports 64 <= dim < 4096");
@@ -38,22 +18,34 @@ hs_status slimq_records_args_ok(int metric, size_t dim, const float *centroids, 
 }
 hs_status slimq_device_ok(int device) {
   if (device < 0) return fail(HS_ERR_INVALID, "device: a HIP device");
-  return hs_device_count() <= device ? fail(HS_ERR_DEVICE, "no HIP device") : HS_OK;
+  return device_ok(device, false);
 }
 
-// The graph passes into `s`: on `device`, or on the host when device < 0 or the shape is outside the device path.
-hs_status slimq_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms) {
+// The graph passes of a step into `s`: `on_device` ran them when it returns true; when it returns false without an error text the shape
+// is outside the device path and `on_host` runs them.
+template <class OnDevice, class OnHost>
+static hs_status graph_step(bool try_device, OnDevice &&on_device, OnHost &&on_host, int *used_gpu, double *kernel_ms) {
   bool ok = false;
   double ms = 0.0;
-  if (device >= 0) {
+  if (try_device) {
     std::string err;
-    ok = convert_slimq_gpu(s, g, p, device, threads, &ms, &err);
+    ok = on_device(&ms, &err);
     if (!ok && !err.empty()) return fail(HS_ERR_DEVICE, err);
   }
-  if (!ok) convert_slimq_graph(s, g, p, threads);
+  if (!ok) on_host();
   if (used_gpu) *used_gpu = ok ? 1 : 0;
   if (kernel_ms) *kernel_ms = ok ? ms : 0.0;
   return HS_OK;
+}
+// Slim's graph passes: on `device`, or on the host when the shape is outside the device path.
+hs_status slim_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms) {
+  return graph_step(true, [&](double *ms, std::string *err) { return convert_gpu(s, g, p, device, threads, ms, err); },
+                    [&] { s.convert(g, p, threads); }, used_gpu, kernel_ms);
+}
+// SlimQ's graph passes: on `device`, or on the host when device < 0 or the shape is outside the device path.
+hs_status slimq_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms) {
+  return graph_step(device >= 0, [&](double *ms, std::string *err) { return convert_slimq_gpu(s, g, p, device, threads, ms, err); },
+                    [&] { convert_slimq_graph(s, g, p, threads); }, used_gpu, kernel_ms);
 }
 // The records of `s` into `q` (SlimQGraph::from_slim): on `device`, or on the host when device < 0.
 hs_status slimq_records_step(SlimQGraph &q, const SlimGraph &s, int metric, const float *centroids, size_t num_cluster, const uint32_t *cluster_ids,
@@ -77,29 +69,6 @@ hs_status slimq_records_step(SlimQGraph &q, const SlimGraph &s, int metric, cons
   return HS_OK;
 }
 
-hs_status hs_convert_slimq_graph_gpu(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
-                                     float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0, size_t top_degree_M,
-                                     size_t low_degree_m, int device, int threads, const char *out_path, int *used_gpu, double *kernel_ms) {
-  if (!hnsw_path || !out_path) return fail(HS_ERR_INVALID, "bad argument");
-  hs_status st = metric_ok(metric);
-  if (st == HS_OK) st = slimq_device_ok(device);
-  if (st != HS_OK) return st;
-  try {
-    VanillaGraph g;
-    g.load(hnsw_path, (Metric)metric, dim);
-    SlimGraph s;
-    st = slimq_graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
-                    device, threads, used_gpu, kernel_ms);
-    if (st != HS_OK) return st;
-    s.save(out_path);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
-}
-
 hs_status hs_convert_slimq_gpu(const char *slim_path, int metric, size_t dim, const float *centroids, size_t num_cluster,
                                const uint32_t *cluster_ids, uint64_t flip_seed, int device, int threads, const char *out_path, int *used_gpu,
                                double *kernel_ms) {
@@ -107,19 +76,15 @@ hs_status hs_convert_slimq_gpu(const char *slim_path, int metric, size_t dim, co
   hs_status st = slimq_records_args_ok(metric, dim, centroids, num_cluster);
   if (st == HS_OK) st = slimq_device_ok(device);
   if (st != HS_OK) return st;
-  try {
+  return guarded([&] {
     SlimGraph s;
     s.load(slim_path, (Metric)metric, dim);
     SlimQGraph q;
-    st = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, used_gpu, kernel_ms);
-    if (st != HS_OK) return st;
+    const hs_status rs = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, used_gpu, kernel_ms);
+    if (rs != HS_OK) return rs;
     q.save(out_path);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 hs_status hs_convert_hnsw_to_slimq(const char *hnsw_path, int metric, size_t dim, int threshold_level, float top_degree_percent0,
@@ -131,32 +96,28 @@ hs_status hs_convert_hnsw_to_slimq(const char *hnsw_path, int metric, size_t dim
   if (st != HS_OK) return st;
   if (device < -1) return fail(HS_ERR_INVALID, "device: -1 (the host path) or a HIP device");
   if (device >= 0 && (st = slimq_device_ok(device)) != HS_OK) return st;
-  const auto t0 = std::chrono::steady_clock::now();
-  hs_slimq_convert_stats out{};
-  try {
+  return guarded([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    hs_slimq_convert_stats out{};
     SlimGraph s;
     {
       VanillaGraph g;
       g.load(hnsw_path, (Metric)metric, dim);
-      st = slimq_graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
-                      device, threads, &out.graph_used_gpu, &out.graph_kernel_ms);
-      if (st != HS_OK) return st;
+      const hs_status gs = slimq_graph_step(s, g, slim_params(threshold_level, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m),
+                                            device, threads, &out.graph_used_gpu, &out.graph_kernel_ms);
+      if (gs != HS_OK) return gs;
     }
     out.graph_ms = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     SlimQGraph q;
-    st = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, &out.records_used_gpu, &out.records_kernel_ms);
-    if (st != HS_OK) return st;
+    const hs_status rs = slimq_records_step(q, s, metric, centroids, num_cluster, cluster_ids, flip_seed, device, threads, &out.records_used_gpu, &out.records_kernel_ms);
+    if (rs != HS_OK) return rs;
     out.records_ms = ms_since(t1);
     q.save(out_path);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  out.total_ms = ms_since(t0);
-  if (stats) *stats = out;
-  return HS_OK;
+    out.total_ms = ms_since(t0);
+    if (stats) *stats = out;
+    return HS_OK;
+  });
 }
 
 hs_status hs_debug_rq_quantize_rows(size_t dim, int metric, const uint8_t *flips, const float *rows, size_t n, const float *centroids_raw,
@@ -171,7 +132,7 @@ hs_status hs_debug_rq_quantize_rows(size_t dim, int metric, const uint8_t *flips
     for (size_t i = 0; i < n; i++)
       if (cluster_ids[i] >= num_cluster) return fail(HS_ERR_INVALID, "cluster id out of range");
   if (device >= 0 && (st = slimq_device_ok(device)) != HS_OK) return st;
-  try {
+  return guarded([&] {
     Rotator rot;
     rot.init(dim);
     memcpy(rot.flip.data(), flips, rot.flip.size());
@@ -186,10 +147,6 @@ hs_status hs_debug_rq_quantize_rows(size_t dim, int metric, const uint8_t *flips
       const hipError_t e = gpu_rq_quantize(in, device, cent_rot.data(), out_rotated, out_cluster, out_codes, out_factors, nullptr);
       if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("GPU quantise: ") + hipGetErrorString(e));
     }
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }

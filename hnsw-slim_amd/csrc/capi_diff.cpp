@@ -16,13 +16,6 @@ struct hs_slim_diff {
   uint64_t gen = 0;                 // made_on->slim_gen when the diff was made
 };
 
-static SlimParams diff_params(float pct0, float pct, size_t top_M0, size_t low_m0, size_t top_M, size_t low_m) {
-  SlimParams p;
-  p.top_pct0 = pct0; p.top_pct = pct;
-  p.top_M0 = top_M0; p.low_m0 = low_m0; p.top_M = top_M; p.low_m = low_m;
-  return p;
-}
-
 hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0,
                                size_t low_degree_m0, size_t top_degree_M, size_t low_degree_m, int threads, hs_slim_diff **out, int *used_gpu,
                                double *kernel_ms) {
@@ -39,25 +32,25 @@ hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_
   if (s.maxM != g.maxM || s.maxM0 != g.maxM0) return fail(HS_ERR_INVALID, "convertFromHNSWWithDiff: the two indexes differ in maxM / maxM0");
   if (g.count < s.count) return fail(HS_ERR_INVALID, "convertFromHNSWWithDiff: the vanilla index holds fewer elements than the Slim index");
   if (g.count > slim->cap_rows) return fail(HS_ERR_CAPACITY, "convertFromHNSWWithDiff: the vanilla index's element count exceeds the Slim index's max_elements");
-  const size_t dim = g.dim;
-  // an index with narrow rows takes only rows its format represents: every row the call would write is checked before anything
-  // changes -- on the device path the rows the diff kernel found to differ, on the host path after a compare of all rows
-  std::string unfit;
-  auto fits = [&](uint32_t i) {
-    const size_t j = first_unfit(g.vec(i), dim, slim->row_fmt);
-    if (j < dim) unfit = "convertFromHNSWWithDiff refused: " + unfit_message(i, j, g.vec(i)[j], slim->row_fmt);
-    return j >= dim;
-  };
-  const std::function<bool(const std::vector<uint32_t> &)> accept = [&](const std::vector<uint32_t> &stale) {
-    for (uint32_t i : stale)
-      if (!fits(i)) return false;
-    return true;
-  };
-  const SlimParams p = diff_params(top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m);
-  std::unique_ptr<hs_slim_diff> df(new hs_slim_diff());
-  bool gpu = false, same_device = false;
-  double ms = 0.0;
-  try {
+  return guarded("Not enough memory: convertFromHNSW failed to allocate linklist", [&] {
+    const size_t dim = g.dim;
+    // an index with narrow rows takes only rows its format represents: every row the call would write is checked before anything
+    // changes -- on the device path the rows the diff kernel found to differ, on the host path after a compare of all rows
+    std::string unfit;
+    auto fits = [&](uint32_t i) {
+      const size_t j = first_unfit(g.vec(i), dim, slim->row_fmt);
+      if (j < dim) unfit = "convertFromHNSWWithDiff refused: " + unfit_message(i, j, g.vec(i)[j], slim->row_fmt);
+      return j >= dim;
+    };
+    const std::function<bool(const std::vector<uint32_t> &)> accept = [&](const std::vector<uint32_t> &stale) {
+      for (uint32_t i : stale)
+        if (!fits(i)) return false;
+      return true;
+    };
+    const SlimParams p = slim_params(0, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m);
+    std::unique_ptr<hs_slim_diff> df(new hs_slim_diff());
+    bool gpu = false, same_device = false;
+    double ms = 0.0;
     if (!slim->slim_lookup_built) {
       for (size_t i = 0; i < s.count; i++) slim->slim_lookup.map[s.label((uint32_t)i)] = (uint32_t)i;
       slim->slim_lookup_built = true;
@@ -87,31 +80,23 @@ hs_status hs_slim_convert_diff(hs_index *slim, hs_index *hnsw, float top_degree_
       convert_diff(s, g, p, threads, slim->slim_lookup.map, df->d);
       slim->slim_lookup.mismatch_valid = false;
     }
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory: convertFromHNSW failed to allocate linklist");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  slim->slim_gen++;
-  // a call that changed no node and no header field touches nothing on the device; otherwise `dirty` are the nodes whose tile, row
-  // or label changed, `stale` those of them that carry a row -- copied from the HNSW index's resident rows when both share a device
-  if (!df->d.dirty.empty() || slim->info.n != s.count || slim->info.enterpoint != s.enterpoint || slim->info.maxlevel != s.maxlevel ||
-      (slim->info.has_deleted != 0) != s.has_deleted) {
-    PackedIndex pk;
-    try {
+    slim->slim_gen++;
+    // a call that changed no node and no header field touches nothing on the device; otherwise `dirty` are the nodes whose tile, row
+    // or label changed, `stale` those of them that carry a row -- copied from the HNSW index's resident rows when both share a device
+    if (!df->d.dirty.empty() || slim->info.n != s.count || slim->info.enterpoint != s.enterpoint || slim->info.maxlevel != s.maxlevel ||
+        (slim->info.has_deleted != 0) != s.has_deleted) {
+      PackedIndex pk;
       pk.from_slim(s, false);
-    } catch (std::exception &e) {
-      return from_exception(e);
+      hs_status ws = write_changed(slim, pk, [&s](uint32_t i) { return s.vec(i); }, df->d.dirty, df->d.stale, same_device ? hnsw->vec.p : nullptr);
+      if (ws != HS_OK) return ws;
     }
-    hs_status ws = write_changed(slim, pk, [&s](uint32_t i) { return s.vec(i); }, df->d.dirty, df->d.stale, same_device ? hnsw->vec.p : nullptr);
-    if (ws != HS_OK) return ws;
-  }
-  if (used_gpu) *used_gpu = gpu ? 1 : 0;
-  if (kernel_ms) *kernel_ms = gpu ? ms : 0.0;
-  df->made_on = slim;
-  df->gen = slim->slim_gen;
-  *out = df.release();
-  return HS_OK;
+    if (used_gpu) *used_gpu = gpu ? 1 : 0;
+    if (kernel_ms) *kernel_ms = gpu ? ms : 0.0;
+    df->made_on = slim;
+    df->gen = slim->slim_gen;
+    *out = df.release();
+    return HS_OK;
+  });
 }
 
 hs_status hs_slim_diff_info(const hs_slim_diff *d, size_t *count, size_t *n_old, size_t *n_new, size_t *n_reprune) {
@@ -154,18 +139,14 @@ static hs_status hand_out(const std::string &bytes, void *buf, size_t cap, size_
 hs_status hs_slim_diff_stream(const hs_slim_diff *d, const hs_index *slim, void *buf, size_t cap, size_t *len) {
   const SlimGraph *g = diff_image(d, slim);
   if (!g) return HS_ERR_INVALID;
-  try {
-    return hand_out(diff_stream(*g, d->d), buf, cap, len);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  }
+  return guarded([&] { return hand_out(diff_stream(*g, d->d), buf, cap, len); });
 }
 
 hs_status hs_slim_diff_next(hs_slim_diff *d, const hs_index *slim, size_t limit, int to_add, void *buf, size_t cap, size_t *len,
                             size_t *old_written, size_t *new_written, int *finished) {
   const SlimGraph *g = diff_image(d, slim);
   if (!g) return HS_ERR_INVALID;
-  try {
+  return guarded([&] {
     size_t io = d->d.ind_old, in = d->d.ind_new, ow = 0, nw = 0;
     std::string bytes(24, '\0');
     const uint32_t fin = gen_patch(*g, d->d, io, in, bytes, ow, nw, limit, to_add != 0);
@@ -177,10 +158,8 @@ hs_status hs_slim_diff_next(hs_slim_diff *d, const hs_index *slim, size_t limit,
     if (old_written) *old_written = ow;
     if (new_written) *new_written = nw;
     if (finished) *finished = (int)fin;
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 void hs_slim_diff_free(hs_slim_diff *d) { delete d; }
@@ -189,12 +168,10 @@ hs_status hs_slim_index_save(const hs_index *slim, const char *path) {
   if (!slim || !path) return fail(HS_ERR_INVALID, "null argument");
   if (slim->info.kind != HS_KIND_SLIM || !slim->host_slim)
     return fail(HS_ERR_INVALID, "index holds no Slim host image to save: load a Slim index with max_elements > its element count");
-  try {
+  return guarded([&] {
     slim->host_slim->save(path);
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw_path, int metric, size_t dim, int threshold_level,
@@ -203,9 +180,9 @@ hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw
                                      const char *out_stream_path, hs_slim_diff **out) {
   if (out) *out = nullptr;
   if (!hnsw_path || !out_slim_path) return fail(HS_ERR_INVALID, "bad argument");
-  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
-  try {
+  return guarded([&] {
     VanillaGraph g;
     g.load(hnsw_path, (Metric)metric, dim);
     std::unique_ptr<hs_slim_diff> df(new hs_slim_diff());
@@ -223,7 +200,7 @@ hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw
       s.take_header(g, hp);
       s.count = 0;
     }
-    convert_diff(s, g, diff_params(top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m), threads,
+    convert_diff(s, g, slim_params(0, top_degree_percent0, top_degree_percent, top_degree_M0, low_degree_m0, top_degree_M, low_degree_m), threads,
                    lookup, df->d);
     s.save(out_slim_path);
     if (out_stream_path) {
@@ -233,10 +210,6 @@ hs_status hs_slim_convert_diff_files(const char *old_slim_path, const char *hnsw
       o.write(bytes.data(), bytes.size());
     }
     if (out) *out = df.release();
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }

@@ -4,19 +4,7 @@
 
 #include <cstdio>
 
-static thread_local std::string g_err;
-hs_status fail(hs_status s, const std::string &msg) {
-  g_err = msg;
-  return s;
-}
-hs_status from_exception(const std::exception &e) {
-  std::string m = e.what();
-  if (m == "Cannot open file") return fail(HS_ERR_IO, m);
-  if (m.find("corrupted") != std::string::npos) return fail(HS_ERR_CORRUPT, m);
-  if (m.find("Not enough memory") != std::string::npos) return fail(HS_ERR_NOMEM, m);
-  if (m.find("supports dim") != std::string::npos || m.find("SlimQ supports") != std::string::npos) return fail(HS_ERR_UNSUPPORTED, m);
-  return fail(HS_ERR_INVALID, m);
-}
+static constexpr const char *kLoadNomem = "Not enough memory: loadIndex failed to allocate";
 
 template <typename T>
 static hipError_t upload_cap(DevBuf<T> &b, const std::vector<T> &v, size_t cap) {
@@ -170,46 +158,49 @@ hs_status upload(hs_index *ix, const PackedIndex &p) {
   return upload_small(ix, p);
 }
 
-// narrow_fmt != ROWS_F32 (hs_index_load_narrow): the index starts without fp32 rows, its rows uploaded in that format only
+// The end of every loader: the device test, a new index, `prepare` on it, the upload of `p`.
+template <class Prepare>
+static hs_status upload_new(const PackedIndex &p, int device, hs_index **out, Prepare &&prepare) {
+  if (device_ok(device, true) != HS_OK) return HS_ERR_DEVICE;
+  std::unique_ptr<hs_index> ix(new hs_index());
+  ix->device = device;
+  prepare(*ix);
+  const hs_status s = upload(ix.get(), p);
+  if (s != HS_OK) return s;
+  *out = ix.release();
+  return HS_OK;
+}
+
+// narrow_fmt != ROWS_F32 (hs_index_load_narrow): the index starts without fp32 rows, its rows uploaded in that format only.
+// Throws what the loaders throw: the three exported loaders run it inside their guard.
 static hs_status load_from(const BinSource &src, int kind, int metric, size_t dim, size_t max_elements, int device, hs_index **out,
                            int narrow_fmt = ROWS_F32) {
-  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
   PackedIndex p;
   std::unique_ptr<SlimGraph> keep_slim;
   std::unique_ptr<VanillaGraph> keep_vanilla;
-  try {
-    if (kind == HS_KIND_HNSW) {
-      std::unique_ptr<VanillaGraph> g(new VanillaGraph());
-      g->load(src, (Metric)metric, dim, max_elements);
-      p.from_vanilla(*g);
-      if (max_elements > g->count) keep_vanilla = std::move(g);   // room for addPoint (hs_index_add_points), a file for hs_index_save
-    } else if (kind == HS_KIND_SLIM) {
-      std::unique_ptr<SlimGraph> g(new SlimGraph());
-      g->load(src, (Metric)metric, dim);
-      p.from_slim(*g);
-      if (max_elements > g->count) keep_slim = std::move(g);   // room for patchFromStream (hnswalg_slim.h:760, 784)
-    } else if (kind == HS_KIND_SLIMQ) {
-      return load_slimq(src, metric, dim, device, out);
-    } else {
-      return fail(HS_ERR_INVALID, "bad index kind");
-    }
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory: loadIndex failed to allocate");
-  } catch (std::exception &e) {
-    return from_exception(e);
+  if (kind == HS_KIND_HNSW) {
+    std::unique_ptr<VanillaGraph> g(new VanillaGraph());
+    g->load(src, (Metric)metric, dim, max_elements);
+    p.from_vanilla(*g);
+    if (max_elements > g->count) keep_vanilla = std::move(g);   // room for addPoint (hs_index_add_points), a file for hs_index_save
+  } else if (kind == HS_KIND_SLIM) {
+    std::unique_ptr<SlimGraph> g(new SlimGraph());
+    g->load(src, (Metric)metric, dim);
+    p.from_slim(*g);
+    if (max_elements > g->count) keep_slim = std::move(g);   // room for patchFromStream (hnswalg_slim.h:760, 784)
+  } else if (kind == HS_KIND_SLIMQ) {
+    return load_slimq(src, metric, dim, device, out);
+  } else {
+    return fail(HS_ERR_INVALID, "bad index kind");
   }
   // only now: a hostile file is refused as such (the loaders ran index_check.hpp) on a machine without a device too
-  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
-  hs_index *ix = new hs_index();
-  ix->device = device;
-  if (keep_slim) { ix->cap_rows = max_elements; ix->host_slim = std::move(keep_slim); }
-  if (keep_vanilla) { ix->cap_rows = max_elements; ix->host_vanilla = std::move(keep_vanilla); }
-  if (narrow_fmt != ROWS_F32) { ix->row_fmt = narrow_fmt; ix->f32_resident = false; }
-  hs_status s = upload(ix, p);
-  if (s != HS_OK) { delete ix; return s; }
-  *out = ix;
-  return HS_OK;
+  return upload_new(p, device, out, [&](hs_index &ix) {
+    if (keep_slim) { ix.cap_rows = max_elements; ix.host_slim = std::move(keep_slim); }
+    if (keep_vanilla) { ix.cap_rows = max_elements; ix.host_vanilla = std::move(keep_vanilla); }
+    if (narrow_fmt != ROWS_F32) { ix.row_fmt = narrow_fmt; ix.f32_resident = false; }
+  });
 }
 
 // patchFromStream(std::istream &in, bool to_add) (hnswalg_slim.h:2292-2340) on a device-resident index.  Stream, as the
@@ -228,7 +219,7 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
   const size_t spe = g.size_per_el, dim = g.dim;
   std::vector<uint32_t> changed, added;
   size_t new_count = 0;
-  try {
+  return guarded("Not enough memory: patchFromStream failed to allocate linklist", [&] {
     BinReader r(BinSource(bytes, len));
     new_count = r.pod<uint64_t>();
     const uint64_t n_old = r.pod<uint64_t>(), n_new = r.pod<uint64_t>();
@@ -291,18 +282,10 @@ hs_status hs_index_patch(hs_index *ix, const void *bytes, size_t len, int to_add
       (rc.is_new ? added : changed).push_back(rc.id);
     }
     g.count = new_count;
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory: patchFromStream failed to allocate linklist");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  PackedIndex p;
-  try {
+    PackedIndex p;
     p.from_slim(g, false);
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, changed, added);
+    return write_changed(ix, p, [&g](uint32_t i) { return g.vec(i); }, changed, added);
+  });
 }
 
 // An index the host has already parsed: node i owns levels[i] + 1 consecutive neighbour lists (level 0 first),
@@ -312,11 +295,11 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
                                     uint32_t enterpoint, int32_t maxlevel, int32_t threshold_level, int device, hs_index **out) {
   if (!out || (n && (!vectors || !levels || !list_ptr || !list_ids))) return fail(HS_ERR_INVALID, "null argument");
   if (kind != HS_KIND_HNSW && kind != HS_KIND_SLIM) return fail(HS_ERR_INVALID, "bad index kind");
-  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
   if (n && enterpoint >= n) return fail(HS_ERR_INVALID, "enter point out of range");
-  PackedIndex p;
-  try {
+  return guarded([&] {
+    PackedIndex p;
     {   // the preconditions of index_check.hpp on the caller's arrays, before anything is packed from them
       std::vector<size_t> first(n);
       size_t t = 0;
@@ -381,28 +364,20 @@ hs_status hs_index_from_host_arrays(int kind, int metric, size_t n, size_t dim, 
     }
     if (p.cols.size() >= PackedIndex::NONE) return fail(HS_ERR_INVALID, "adjacency too large for 32-bit CSR offsets");
     p.index_size = 16 * n + 4 * p.cols.size();
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  }
-  if (hs_device_count() <= device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
-  hs_index *ix = new hs_index();
-  ix->device = device;
-  hs_status s = upload(ix, p);
-  if (s != HS_OK) { delete ix; return s; }
-  *out = ix;
-  return HS_OK;
+    return upload_new(p, device, out, [](hs_index &) {});
+  });
 }
 
 hs_status hs_index_load(const char *path, int kind, int metric, size_t dim, size_t max_elements, int device,
                         hs_index **out) {
   if (!path || !out) return fail(HS_ERR_INVALID, "null argument");
-  return load_from(BinSource(path), kind, metric, dim, max_elements, device, out);
+  return guarded(kLoadNomem, [&] { return load_from(BinSource(path), kind, metric, dim, max_elements, device, out); });
 }
 
 hs_status hs_index_load_mem(const void *bytes, size_t len, int kind, int metric, size_t dim, size_t max_elements, int device,
                             hs_index **out) {
   if (!bytes || !out) return fail(HS_ERR_INVALID, "null argument");
-  return load_from(BinSource(bytes, len), kind, metric, dim, max_elements, device, out);
+  return guarded(kLoadNomem, [&] { return load_from(BinSource(bytes, len), kind, metric, dim, max_elements, device, out); });
 }
 
 void hs_index_free(hs_index *ix) {
@@ -439,24 +414,26 @@ hs_status hs_index_set_row_format(hs_index *ix, int format) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
   if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
-  if (format != ROWS_F32 && (ix->info.dim & 15) != 0)
-    return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(ix->info.dim) + ")");
-  if (format == ix->row_fmt) return HS_OK;
-  if (!ix->f32_resident)   // every other format is converted from the fp32 rows
-    return fail(HS_ERR_INVALID, "the index holds no fp32 rows: restore the fp32 rows first (hs_index_set_f32_resident(ix, 1))");
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
-  DevBuf<uint8_t> fresh;
-  if (format != ROWS_F32) {
-    hs_status s = build_narrow(ix, format, fresh);   // into a buffer of its own: a refusal leaves the index exactly as it was
-    if (s != HS_OK) return s;
-  }
-  ix->narrow.release();
-  std::swap(ix->narrow.p, fresh.p);
-  std::swap(ix->narrow.n, fresh.n);
-  ix->row_fmt = format;
-  refresh_device_bytes(ix);
-  return HS_OK;
+  return guarded([&] {
+    if (format != ROWS_F32 && (ix->info.dim & 15) != 0)
+      return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(ix->info.dim) + ")");
+    if (format == ix->row_fmt) return HS_OK;
+    if (!ix->f32_resident)   // every other format is converted from the fp32 rows
+      return fail(HS_ERR_INVALID, "the index holds no fp32 rows: restore the fp32 rows first (hs_index_set_f32_resident(ix, 1))");
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
+    DevBuf<uint8_t> fresh;
+    if (format != ROWS_F32) {
+      hs_status s = build_narrow(ix, format, fresh);   // into a buffer of its own: a refusal leaves the index exactly as it was
+      if (s != HS_OK) return s;
+    }
+    ix->narrow.release();
+    std::swap(ix->narrow.p, fresh.p);
+    std::swap(ix->narrow.n, fresh.n);
+    ix->row_fmt = format;
+    refresh_device_bytes(ix);
+    return HS_OK;
+  });
 }
 int hs_index_row_format(const hs_index *ix) { return ix ? ix->row_fmt : ROWS_F32; }
 
@@ -464,21 +441,23 @@ hs_status hs_index_set_f32_resident(hs_index *ix, int on) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (!on && ix->row_fmt == ROWS_F32) return fail(HS_ERR_INVALID, "the fp32 rows are the only rows of this index: hs_index_set_row_format first");
   if ((on != 0) == ix->f32_resident) return HS_OK;
-  HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
-  const size_t n = ix->info.n, dim = ix->info.dim;
-  if (on) {
-    HIP_TRY(ix->vec.alloc(std::max<size_t>(std::max<size_t>(ix->cap_rows, n) * dim, 1)));
-    HIP_TRY(launch_narrow_widen(ix->narrow.p, ix->vec.p, ix->row_fmt, 0, (uint32_t)n, (uint32_t)dim, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    ix->dev.vec = ix->vec.p;
-  } else {
-    ix->vec.release();
-    ix->dev.vec = nullptr;
-  }
-  ix->f32_resident = on != 0;
-  refresh_device_bytes(ix);
-  return HS_OK;
+  return guarded([&] {
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());   // no search may be in flight on this index while its rows change
+    const size_t n = ix->info.n, dim = ix->info.dim;
+    if (on) {
+      HIP_TRY(ix->vec.alloc(std::max<size_t>(std::max<size_t>(ix->cap_rows, n) * dim, 1)));
+      HIP_TRY(launch_narrow_widen(ix->narrow.p, ix->vec.p, ix->row_fmt, 0, (uint32_t)n, (uint32_t)dim, nullptr));
+      HIP_TRY(hipDeviceSynchronize());
+      ix->dev.vec = ix->vec.p;
+    } else {
+      ix->vec.release();
+      ix->dev.vec = nullptr;
+    }
+    ix->f32_resident = on != 0;
+    refresh_device_bytes(ix);
+    return HS_OK;
+  });
 }
 int hs_index_f32_resident(const hs_index *ix) { return ix ? (ix->f32_resident ? 1 : 0) : 1; }
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad) {
@@ -502,8 +481,10 @@ hs_status hs_index_load_narrow(const char *path, int kind, int metric, size_t di
   *out = nullptr;
   if (format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
   if (kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
-  if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(dim) + ")");
-  return load_from(BinSource(path), kind, metric, dim, max_elements, device, out, format);
+  return guarded(kLoadNomem, [&] {
+    if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(dim) + ")");
+    return load_from(BinSource(path), kind, metric, dim, max_elements, device, out, format);
+  });
 }
 
 hs_status hs_labels(const hs_index *ix, uint64_t *out_labels) {

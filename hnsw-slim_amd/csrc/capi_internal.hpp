@@ -1,10 +1,14 @@
-// capi_internal.hpp -- what the C ABI's translation units (capi_*.cpp) share: error reporting, the device buffer, the index
-// and filter-set objects behind the opaque handles, and the few functions that cross files.  No CPU search path exists in this
-// library: without a HIP device every search call returns HS_ERR_DEVICE.
+// capi_internal.hpp -- what the C ABI's translation units (capi_*.cpp) share: error reporting and the guard (capi_guard.hpp), the
+// device buffer, the index and filter-set objects behind the opaque handles, the shared refusals, and the few functions that cross
+// files.  No CPU search path exists in this library: without a HIP device every search call returns HS_ERR_DEVICE.
+// The rule for an exported entry: if its body can throw -- it allocates, builds a string, touches a container or calls into host_*.hpp --
+// it runs inside one guarded(...) at the entry itself (capi_guard.hpp), and the functions below it let exceptions pass; a refusal
+// that more than one entry reports is a function here.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -16,6 +20,7 @@
 #include <vector>
 
 #include "../../include/hnsw_slim_amd.h"
+#include "capi_guard.hpp"
 #include "engine.hpp"
 #include "narrow_rows.hpp"
 #include "host_graph.hpp"
@@ -166,11 +171,45 @@ struct FilterUse {
 static constexpr const char *kBatchedAddMarksRefusal =
     "batched add refused: the index holds delete marks (the batched insertion has no deleted-element branches); use hs_index_add_points";
 
-// The functions that cross files (shared between the library's own objects, not exported).
+// ---- the refusals and small helpers more than one entry uses: one text, one definition (error reporting: capi_guard.hpp) ----------
 #pragma GCC visibility push(hidden)
-// capi_index.cpp; the calling thread's last error text (hs_last_error) is one thread-local there
-hs_status fail(hs_status s, const std::string &msg);
-hs_status from_exception(const std::exception &e);
+inline hs_status metric_ok(int metric) {
+  return metric == HS_METRIC_L2 || metric == HS_METRIC_IP ? HS_OK : fail(HS_ERR_INVALID, "bad metric");
+}
+// search_path: the text of the entries that would search on the device (an index, brute force); the builders and converters use the short one
+inline hs_status device_ok(int device, bool search_path) {
+  if (hs_device_count() > device) return HS_OK;
+  return fail(HS_ERR_DEVICE, search_path ? "no HIP device (this library has no CPU search path)" : "no HIP device");
+}
+// addPoint's label refusals for new points, on a file (hs_hnsw_resume*) and on a resident index (hs_index_add_points*): a label the
+// graph holds (has_label), a label twice in the call
+template <class HasLabel>
+hs_status labels_new_ok(HasLabel &&has_label, const uint64_t *labels, size_t count) {
+  std::unordered_map<uint64_t, size_t> seen;
+  seen.reserve(count);
+  for (size_t i = 0; i < count; i++) {
+    if (has_label(labels[i]))
+      return fail(HS_ERR_UNSUPPORTED, "label " + std::to_string(labels[i]) + " (row " + std::to_string(i) + ") already exists: updatePoint is not supported");
+    auto ins = seen.emplace(labels[i], i);
+    if (!ins.second)
+      return fail(HS_ERR_INVALID, "label " + std::to_string(labels[i]) + " appears twice in the call (rows " + std::to_string(ins.first->second) + " and " + std::to_string(i) + ")");
+  }
+  return HS_OK;
+}
+inline SlimParams slim_params(int threshold_level, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0,
+                              size_t top_degree_M, size_t low_degree_m) {
+  SlimParams p;
+  p.threshold_level = threshold_level;
+  p.top_pct0 = top_degree_percent0; p.top_pct = top_degree_percent;
+  p.top_M0 = top_degree_M0; p.low_m0 = low_degree_m0; p.top_M = top_degree_M; p.low_m = low_degree_m;
+  return p;
+}
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The functions that cross files (shared between the library's own objects, not exported).
+// capi_index.cpp
 hs_status upload(hs_index *ix, const PackedIndex &p);
 hs_status upload_small(hs_index *ix, const PackedIndex &p);
 hs_status build_narrow(hs_index *ix, int fmt, DevBuf<uint8_t> &out);

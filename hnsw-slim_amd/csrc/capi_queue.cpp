@@ -211,66 +211,71 @@ static hs_status relay(int st, const std::string &msg) { return st == HS_OK ? HS
 hs_status hs_queue_create(hs_index *ix, size_t k, int mode, size_t max_queries, int slots, const hs_filter_set *fs, hs_queue **out) {
   if (!out) return fail(HS_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (!ix) return fail(HS_ERR_INVALID, "null index");
-  if (k == 0) return fail(HS_ERR_INVALID, "k must be > 0");
-  if (mode != HS_MODE_SLIM_IDS && mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "bad mode");
-  if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_INVALID, "SlimQ index: a search queue serves HNSW and Slim indexes");
-  if (mode == HS_MODE_SLIM_IDS && ix->info.kind != HS_KIND_SLIM)
-    return fail(HS_ERR_INVALID, "HS_MODE_SLIM_IDS needs a Slim index (searchKnn(q,k,tableint*) exists on HierarchicalNSWSlim only)");
-  if (max_queries == 0 || max_queries > kQueueMaxQueries) return fail(HS_ERR_INVALID, "max_queries: 1.." + std::to_string(kQueueMaxQueries));
-  if (slots < 1 || slots > kQueueMaxSlots) return fail(HS_ERR_INVALID, "slots: 1.." + std::to_string(kQueueMaxSlots));
-  if (k > 0xFFFFFFFFu / 8 / max_queries) return fail(HS_ERR_INVALID, "k too large");
-  if (fs) {
-    if (mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "a queue under a filter set answers in HS_MODE_PQ (as hs_search_batch_filter_set)");
-    if (ix->info.kind == HS_KIND_SLIM && ix->info.threshold_level != 0)
-      return fail(HS_ERR_UNSUPPORTED, "filtered search on a Slim index with threshold_level > 0 is not supported");
-    if (fs->device != ix->device)
-      return fail(HS_ERR_INVALID, "the filter set lives on device " + std::to_string(fs->device) + ", the index on device " + std::to_string(ix->device));
-    if (fs->n != ix->info.n)
-      return fail(HS_ERR_INVALID, "the filter set was created for " + std::to_string(fs->n) + " elements, the index holds " + std::to_string(ix->info.n));
-  }
-  HIP_TRY(hipSetDevice(ix->device));
-  std::unique_ptr<hs_queue> q(new hs_queue());
-  HipBackend &be = q->be;
-  be.ix = ix; be.fs = fs; be.k = k; be.dim = ix->info.dim; be.max_q = max_queries; be.mode = mode;
-  const char *knob = getenv("HS_QUEUE_IN_PLACE");
-  be.in_place = !(knob && knob[0] == '0');
-  const bool ids = mode == HS_MODE_SLIM_IDS;
-  const size_t m = max_queries, dim = be.dim;
-  be.slots.resize(slots);
-  be.slabs.resize(slots + 1);
-  for (Slot &s : be.slots) {
-    HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    HIP_TRY(s.q.alloc(m * dim));
-    if (fs) HIP_TRY(s.foq.alloc(m));
-    if (ids) HIP_TRY(s.l32.alloc(m * k));
-    else HIP_TRY(s.l64.alloc(m * k));
-    HIP_TRY(s.dd.alloc(m * k));
-    HIP_TRY(s.cnt.alloc(m));
-    HIP_TRY(s.stats.alloc(m * 4));
-    q->device_bytes += (s.q.n + s.dd.n + s.foq.n + s.l32.n + s.cnt.n + s.stats.n) * 4 + s.l64.n * 8;
-  }
-  for (Slab &b : be.slabs) {
-    HIP_TRY(b.q.alloc(m * dim * 4));
-    if (fs) HIP_TRY(b.foq.alloc(m * 4));
-    if (ids) HIP_TRY(b.l32.alloc(m * k * 4));
-    else HIP_TRY(b.l64.alloc(m * k * 8));
-    HIP_TRY(b.dd.alloc(m * k * 4));
-    HIP_TRY(b.cnt.alloc(m * 4));
-    HIP_TRY(b.stats.alloc(m * 16));
-    HIP_TRY(b.first_row.alloc((m + 1) * 4));
-    HIP_TRY(b.entries.alloc(m * sizeof(SegEntry)));
-  }
-  q->core.reset(new SearchQueueCore<HipBackend>(be, max_queries, slots));
-  *out = q.release();
-  return HS_OK;
+  return guarded([&] {
+    if (!ix) return fail(HS_ERR_INVALID, "null index");
+    if (k == 0) return fail(HS_ERR_INVALID, "k must be > 0");
+    if (mode != HS_MODE_SLIM_IDS && mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "bad mode");
+    if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_INVALID, "SlimQ index: a search queue serves HNSW and Slim indexes");
+    if (mode == HS_MODE_SLIM_IDS && ix->info.kind != HS_KIND_SLIM)
+      return fail(HS_ERR_INVALID, "HS_MODE_SLIM_IDS needs a Slim index (searchKnn(q,k,tableint*) exists on HierarchicalNSWSlim only)");
+    if (max_queries == 0 || max_queries > kQueueMaxQueries) return fail(HS_ERR_INVALID, "max_queries: 1.." + std::to_string(kQueueMaxQueries));
+    if (slots < 1 || slots > kQueueMaxSlots) return fail(HS_ERR_INVALID, "slots: 1.." + std::to_string(kQueueMaxSlots));
+    if (k > 0xFFFFFFFFu / 8 / max_queries) return fail(HS_ERR_INVALID, "k too large");
+    if (fs) {
+      if (mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "a queue under a filter set answers in HS_MODE_PQ (as hs_search_batch_filter_set)");
+      if (ix->info.kind == HS_KIND_SLIM && ix->info.threshold_level != 0)
+        return fail(HS_ERR_UNSUPPORTED, "filtered search on a Slim index with threshold_level > 0 is not supported");
+      if (fs->device != ix->device)
+        return fail(HS_ERR_INVALID, "the filter set lives on device " + std::to_string(fs->device) + ", the index on device " + std::to_string(ix->device));
+      if (fs->n != ix->info.n)
+        return fail(HS_ERR_INVALID, "the filter set was created for " + std::to_string(fs->n) + " elements, the index holds " + std::to_string(ix->info.n));
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    std::unique_ptr<hs_queue> q(new hs_queue());
+    HipBackend &be = q->be;
+    be.ix = ix; be.fs = fs; be.k = k; be.dim = ix->info.dim; be.max_q = max_queries; be.mode = mode;
+    const char *knob = getenv("HS_QUEUE_IN_PLACE");
+    be.in_place = !(knob && knob[0] == '0');
+    const bool ids = mode == HS_MODE_SLIM_IDS;
+    const size_t m = max_queries, dim = be.dim;
+    be.slots.resize(slots);
+    be.slabs.resize(slots + 1);
+    for (Slot &s : be.slots) {
+      HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+      HIP_TRY(s.q.alloc(m * dim));
+      if (fs) HIP_TRY(s.foq.alloc(m));
+      if (ids) HIP_TRY(s.l32.alloc(m * k));
+      else HIP_TRY(s.l64.alloc(m * k));
+      HIP_TRY(s.dd.alloc(m * k));
+      HIP_TRY(s.cnt.alloc(m));
+      HIP_TRY(s.stats.alloc(m * 4));
+      q->device_bytes += (s.q.n + s.dd.n + s.foq.n + s.l32.n + s.cnt.n + s.stats.n) * 4 + s.l64.n * 8;
+    }
+    for (Slab &b : be.slabs) {
+      HIP_TRY(b.q.alloc(m * dim * 4));
+      if (fs) HIP_TRY(b.foq.alloc(m * 4));
+      if (ids) HIP_TRY(b.l32.alloc(m * k * 4));
+      else HIP_TRY(b.l64.alloc(m * k * 8));
+      HIP_TRY(b.dd.alloc(m * k * 4));
+      HIP_TRY(b.cnt.alloc(m * 4));
+      HIP_TRY(b.stats.alloc(m * 16));
+      HIP_TRY(b.first_row.alloc((m + 1) * 4));
+      HIP_TRY(b.entries.alloc(m * sizeof(SegEntry)));
+    }
+    q->core.reset(new SearchQueueCore<HipBackend>(be, max_queries, slots));
+    *out = q.release();
+    return HS_OK;
+  });
 }
 
 void hs_queue_free(hs_queue *q) {
   if (!q) return;
-  std::string msg;
-  (void)q->core->drain(&msg);
+  (void)guarded([&] {   // (what the last launches report has nobody left to read it)
+    std::string msg;
+    (void)q->core->drain(&msg);
+    return HS_OK;
+  });
   delete q;
 }
 
@@ -296,37 +301,38 @@ static hs_status queue_submit(hs_queue *q, bool device, const float *queries, si
 
 hs_status hs_queue_submit(hs_queue *q, const float *queries, size_t nq, const uint32_t *filter_of_query, uint32_t *out_labels32,
                           uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, uint32_t *stats, uint64_t *ticket) {
-  return queue_submit(q, false, queries, nq, filter_of_query, out_labels32, out_labels64, out_dists, out_counts, stats, nullptr, ticket);
+  return guarded([&] { return queue_submit(q, false, queries, nq, filter_of_query, out_labels32, out_labels64, out_dists, out_counts, stats, nullptr, ticket); });
 }
 
 hs_status hs_queue_submit_dev(hs_queue *q, const float *d_queries, size_t nq, const uint32_t *d_filter_of_query, uint32_t *d_out_labels32,
                               uint64_t *d_out_labels64, float *d_out_dists, uint32_t *d_out_counts, uint32_t *d_stats, void *stream,
                               uint64_t *ticket) {
-  return queue_submit(q, true, d_queries, nq, d_filter_of_query, d_out_labels32, d_out_labels64, d_out_dists, d_out_counts, d_stats, stream, ticket);
+  return guarded([&] {
+    return queue_submit(q, true, d_queries, nq, d_filter_of_query, d_out_labels32, d_out_labels64, d_out_dists, d_out_counts, d_stats, stream, ticket);
+  });
 }
 
+// flush / wait / join_stream / drain: one call into the core, its status and text relayed
+template <class Call>
+static hs_status core_call(hs_queue *q, Call &&call) {
+  if (!q) return fail(HS_ERR_INVALID, "null argument");
+  return guarded([&] {
+    std::string msg;
+    const int st = call(*q->core, &msg);
+    return relay(st, msg);
+  });
+}
 hs_status hs_queue_flush(hs_queue *q) {
-  if (!q) return fail(HS_ERR_INVALID, "null argument");
-  std::string msg;
-  return relay(q->core->flush(&msg), msg);
+  return core_call(q, [](SearchQueueCore<HipBackend> &c, std::string *msg) { return c.flush(msg); });
 }
-
 hs_status hs_queue_wait(hs_queue *q, uint64_t ticket) {
-  if (!q) return fail(HS_ERR_INVALID, "null argument");
-  std::string msg;
-  return relay(q->core->wait(ticket, &msg), msg);
+  return core_call(q, [=](SearchQueueCore<HipBackend> &c, std::string *msg) { return c.wait(ticket, msg); });
 }
-
 hs_status hs_queue_join_stream(hs_queue *q, uint64_t ticket, void *stream) {
-  if (!q) return fail(HS_ERR_INVALID, "null argument");
-  std::string msg;
-  return relay(q->core->join_stream(ticket, stream, &msg), msg);
+  return core_call(q, [=](SearchQueueCore<HipBackend> &c, std::string *msg) { return c.join_stream(ticket, stream, msg); });
 }
-
 hs_status hs_queue_drain(hs_queue *q) {
-  if (!q) return fail(HS_ERR_INVALID, "null argument");
-  std::string msg;
-  return relay(q->core->drain(&msg), msg);
+  return core_call(q, [](SearchQueueCore<HipBackend> &c, std::string *msg) { return c.drain(msg); });
 }
 
 hs_status hs_queue_info(const hs_queue *q, struct hs_queue_info *out) {

@@ -134,33 +134,35 @@ hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k, int mo
 
 hs_status hs_search_check(hs_index *ix, void *stream) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
-  uint32_t c[13];   // [12]: queries of filter-set searches whose filter index was outside the set
-  HIP_TRY(hipSetDevice(ix->device));
-  hs_index::StreamWs *w = ix->stream_ws((hipStream_t)stream);
-  if (!w->counters.p) {   // no kernel was launched on this stream; the padding outputs of an empty index may still be on their way
+  return guarded([&] {
+    uint32_t c[13];   // [12]: queries of filter-set searches whose filter index was outside the set
+    HIP_TRY(hipSetDevice(ix->device));
+    hs_index::StreamWs *w = ix->stream_ws((hipStream_t)stream);
+    if (!w->counters.p) {   // no kernel was launched on this stream; the padding outputs of an empty index may still be on their way
+      HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+      return HS_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(c, w->counters.p, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, sizeof(c), (hipStream_t)stream));   // read and cleared: see search_dev_group
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    // learn the scratch sizes from the data: if more than 1% of a batch overflowed in the first passes,
+    // later batches start with twice the visited-set slots / candidate capacity.
+    const size_t nq = std::max<size_t>(w->last_nq, 1);
+    w->last_nq = 0;
+    if (diag().verbose) fprintf(stderr, "[hs check] nq %zu: visited overflow %u, candidate overflow %u, tie replays %u, visited-set spills %u | pass 2: %u %u | grow_hash %u grow_cand %u\n",
+                         nq, c[0], c[1], c[2], c[3], c[8], c[9], ix->grow_hash, ix->grow_cand);
+    if ((size_t)c[3] * 10 > nq && ix->grow_hash < 8 && !ix->user_hash_slots) ix->grow_hash++;
+    if ((size_t)(c[1] + c[5]) * 100 > nq && ix->grow_cand < 4 && !ix->user_cand_cap) ix->grow_cand++;
+    if (c[12] > 0)
+      return fail(HS_ERR_INVALID, std::to_string(c[12]) + " queries named a filter index outside the filter set (count 0 returned for them)");
+    if (ix->info.kind == HS_KIND_SLIMQ) {
+      if (c[8] > 0) return fail(HS_ERR_CAPACITY, std::to_string(c[8]) + " queries expanded more nodes than the 64 KiB on-chip set holds");
+      return HS_OK;
+    }
+    if (c[8] + c[9] > 0)
+      return fail(HS_ERR_CAPACITY, std::to_string(c[8] + c[9]) + " queries exhausted even a whole CU's on-chip scratch");
     return HS_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(c, w->counters.p, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipMemsetAsync(w->counters.p, 0, sizeof(c), (hipStream_t)stream));   // read and cleared: see search_dev_group
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  // learn the scratch sizes from the data: if more than 1% of a batch overflowed in the first passes,
-  // later batches start with twice the visited-set slots / candidate capacity.
-  const size_t nq = std::max<size_t>(w->last_nq, 1);
-  w->last_nq = 0;
-  if (diag().verbose) fprintf(stderr, "[hs check] nq %zu: visited overflow %u, candidate overflow %u, tie replays %u, visited-set spills %u | pass 2: %u %u | grow_hash %u grow_cand %u\n",
-                       nq, c[0], c[1], c[2], c[3], c[8], c[9], ix->grow_hash, ix->grow_cand);
-  if ((size_t)c[3] * 10 > nq && ix->grow_hash < 8 && !ix->user_hash_slots) ix->grow_hash++;
-  if ((size_t)(c[1] + c[5]) * 100 > nq && ix->grow_cand < 4 && !ix->user_cand_cap) ix->grow_cand++;
-  if (c[12] > 0)
-    return fail(HS_ERR_INVALID, std::to_string(c[12]) + " queries named a filter index outside the filter set (count 0 returned for them)");
-  if (ix->info.kind == HS_KIND_SLIMQ) {
-    if (c[8] > 0) return fail(HS_ERR_CAPACITY, std::to_string(c[8]) + " queries expanded more nodes than the 64 KiB on-chip set holds");
-    return HS_OK;
-  }
-  if (c[8] + c[9] > 0)
-    return fail(HS_ERR_CAPACITY, std::to_string(c[8] + c[9]) + " queries exhausted even a whole CU's on-chip scratch");
-  return HS_OK;
+  });
 }
 
 // Parity/debug: the launch plan as a function of its inputs alone (no device), and those inputs for a live index
@@ -178,7 +180,7 @@ hs_status hs_debug_plan_input(const hs_index *ix, size_t k, size_t nq, int has_f
 
 hs_status hs_debug_fast_shape(int metric, uint64_t dim, uint64_t ef, uint64_t k, int bare, hs_fast_shape *out) {
   if (!out) return fail(HS_ERR_INVALID, "null argument");
-  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   const uint64_t run_ef = std::max(ef, k);   // the search runs with max(ef, k)
   if (dim == 0 || dim > UINT32_MAX || run_ef == 0 || run_ef > 512) return fail(HS_ERR_INVALID, "no fast-kernel shape: dim = 0 or max(ef, k) outside 1..512");
   const FastShape s = fast_shape(metric, (uint32_t)dim, (uint32_t)run_ef, (uint32_t)k, bare != 0);
@@ -190,20 +192,22 @@ hs_status hs_debug_heap_ops(const uint32_t *ops, size_t n_ops, int wave_pop, uin
                             uint32_t *out_n) {
   if (!ops || !out_heap || !out_pops || !out_n) return fail(HS_ERR_INVALID, "null argument");
   if (lds_slots < 2 || lds_slots > 8192 || (lds_slots & 1)) return fail(HS_ERR_INVALID, "lds_slots: even, 2..8192");
-  DevBuf<uint32_t> d_ops, d_n;
-  DevBuf<uint2> d_spill, d_heap, d_pops;
-  HIP_TRY(d_ops.alloc(std::max<size_t>(3 * n_ops, 1)));
-  HIP_TRY(d_n.alloc(2));
-  HIP_TRY(d_spill.alloc(n_ops + 2));
-  HIP_TRY(d_heap.alloc(n_ops + 2));
-  HIP_TRY(d_pops.alloc(n_ops + 2));
-  HIP_TRY(hipMemcpy(d_ops.p, ops, 3 * n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(flat_heap_ops(d_ops.p, (uint32_t)n_ops, d_spill.p, d_heap.p, d_pops.p, d_n.p, wave_pop, lds_slots, nullptr));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out_n, d_n.p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_heap, d_heap.p, (size_t)out_n[0] * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_pops, d_pops.p, (size_t)out_n[1] * 8, hipMemcpyDeviceToHost));
-  return HS_OK;
+  return guarded([&] {
+    DevBuf<uint32_t> d_ops, d_n;
+    DevBuf<uint2> d_spill, d_heap, d_pops;
+    HIP_TRY(d_ops.alloc(std::max<size_t>(3 * n_ops, 1)));
+    HIP_TRY(d_n.alloc(2));
+    HIP_TRY(d_spill.alloc(n_ops + 2));
+    HIP_TRY(d_heap.alloc(n_ops + 2));
+    HIP_TRY(d_pops.alloc(n_ops + 2));
+    HIP_TRY(hipMemcpy(d_ops.p, ops, 3 * n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(flat_heap_ops(d_ops.p, (uint32_t)n_ops, d_spill.p, d_heap.p, d_pops.p, d_n.p, wave_pop, lds_slots, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_n, d_n.p, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_heap, d_heap.p, (size_t)out_n[0] * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_pops, d_pops.p, (size_t)out_n[1] * 8, hipMemcpyDeviceToHost));
+    return HS_OK;
+  });
 }
 
 hs_status hs_search_batch_dev(hs_index *ix, const float *d_queries, size_t nq, size_t k, int mode,
@@ -211,8 +215,9 @@ hs_status hs_search_batch_dev(hs_index *ix, const float *d_queries, size_t nq, s
                               uint32_t *d_out_counts, uint32_t *d_stats, void *stream) {
   if (mode == HS_MODE_SLIM_IDS && !d_out_labels32) return fail(HS_ERR_INVALID, "out_labels32 required");
   if (mode == HS_MODE_PQ && (!d_out_labels64 || !d_out_dists || !d_out_counts)) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
-  return search_dev(ix, d_queries, nq, k, mode, d_out_labels32, d_out_labels64, d_out_dists, d_out_counts, d_stats,
-                    nullptr, nullptr, (hipStream_t)stream);
+  return guarded([&] {
+    return search_dev(ix, d_queries, nq, k, mode, d_out_labels32, d_out_labels64, d_out_dists, d_out_counts, d_stats, nullptr, nullptr, (hipStream_t)stream);
+  });
 }
 
 // H2D of the queries, the search, D2H of the requested outputs: all enqueued on `stream`, no host synchronisation.  The
@@ -326,7 +331,7 @@ hs_status hs_search_batch_async(hs_index *ix, const float *queries, size_t nq, s
   if (mode == HS_MODE_SLIM_IDS && !out_labels32) return fail(HS_ERR_INVALID, "out_labels32 required");
   if (mode == HS_MODE_PQ && (!out_labels64 || !out_dists || !out_counts)) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
   if (mode != HS_MODE_SLIM_IDS && mode != HS_MODE_PQ) return fail(HS_ERR_INVALID, "bad mode");
-  return search_async(ix, queries, nq, k, mode, out_labels32, out_labels64, out_dists, out_counts, stats, (hipStream_t)stream);
+  return guarded([&] { return search_async(ix, queries, nq, k, mode, out_labels32, out_labels64, out_dists, out_counts, stats, (hipStream_t)stream); });
 }
 void *hs_host_alloc(size_t bytes) {
   void *p = nullptr;
@@ -342,8 +347,7 @@ hs_status hs_search_batch(hs_index *ix, const float *queries, size_t nq, size_t 
                           uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, uint32_t *stats) {
   if (mode == HS_MODE_SLIM_IDS && !out_labels32) return fail(HS_ERR_INVALID, "out_labels32 required");
   if (mode == HS_MODE_PQ && (!out_labels64 || !out_dists || !out_counts)) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
-  return search_host(ix, queries, nq, k, mode, out_labels32, out_labels64, out_dists, out_counts, stats, nullptr,
-                     nullptr, nullptr);
+  return guarded([&] { return search_host(ix, queries, nq, k, mode, out_labels32, out_labels64, out_dists, out_counts, stats, nullptr, nullptr, nullptr); });
 }
 
 // The reference tests "!isMarkedDeleted(id) && (*isIdAllowed)(label)" together wherever a filter is consulted
@@ -356,23 +360,22 @@ hs_status hs_search_batch_filtered(hs_index *ix, const float *queries, size_t nq
   if (!out_labels64 || !out_dists || !out_counts) return fail(HS_ERR_INVALID, "out_labels64/out_dists/out_counts required");
   if (ix->info.kind == HS_KIND_SLIM && ix->info.threshold_level != 0)
     return fail(HS_ERR_UNSUPPORTED, "filtered search on a Slim index with threshold_level > 0 is not supported");
-  HIP_TRY(hipSetDevice(ix->device));
-  const size_t n = ix->info.n;
-  std::vector<uint8_t> excl(std::max<size_t>(n, 1));
-  for (size_t i = 0; i < n; i++) excl[i] = (ix->host_deleted[i] || !allowed[i]) ? 1 : 0;
-  HIP_TRY(ix->wexcl.ensure(excl.size()));
-  HIP_TRY(hipMemcpy(ix->wexcl.p, excl.data(), excl.size(), hipMemcpyHostToDevice));
-  const DevIndex saved = ix->dev;
-  ix->dev.deleted = ix->wexcl.p;
-  ix->dev.has_deleted = 1;
-  hs_status s = search_host(ix, queries, nq, k, HS_MODE_PQ, nullptr, out_labels64, out_dists, out_counts, stats, nullptr,
-                            nullptr, nullptr);
-  ix->dev = saved;
-  return s;
+  return guarded([&] {
+    HIP_TRY(hipSetDevice(ix->device));
+    const size_t n = ix->info.n;
+    std::vector<uint8_t> excl(std::max<size_t>(n, 1));
+    for (size_t i = 0; i < n; i++) excl[i] = (ix->host_deleted[i] || !allowed[i]) ? 1 : 0;
+    HIP_TRY(ix->wexcl.ensure(excl.size()));
+    HIP_TRY(hipMemcpy(ix->wexcl.p, excl.data(), excl.size(), hipMemcpyHostToDevice));
+    const Restore put_back([ix, saved = ix->dev] { ix->dev = saved; });
+    ix->dev.deleted = ix->wexcl.p;
+    ix->dev.has_deleted = 1;
+    return search_host(ix, queries, nq, k, HS_MODE_PQ, nullptr, out_labels64, out_dists, out_counts, stats, nullptr, nullptr, nullptr);
+  });
 }
 
 hs_status hs_search_batch_raw(hs_index *ix, const float *queries, size_t nq, size_t k, int mode, float *raw_dists,
                               uint32_t *raw_ids, uint32_t *raw_sizes, uint32_t *stats) {
   if (!raw_dists || !raw_ids || !raw_sizes) return fail(HS_ERR_INVALID, "raw outputs required");
-  return search_host(ix, queries, nq, k, mode, nullptr, nullptr, nullptr, nullptr, stats, raw_dists, raw_ids, raw_sizes);
+  return guarded([&] { return search_host(ix, queries, nq, k, mode, nullptr, nullptr, nullptr, nullptr, stats, raw_dists, raw_ids, raw_sizes); });
 }

@@ -1,16 +1,10 @@
 // capi_slimq_resident.cpp -- the C ABI (include/hnsw_slim_amd.h): a resident HNSW-SlimQ index from rows or a graph with no file on the
 // way -- the in-memory graph handle, convertFromHNSW of it into a file and / or a resident index, the whole chain from rows, saveIndex
 // of a resident index's host image, and the debug views of its three record arrays beside their host statement (slimq_tiles.hpp).
-#include <chrono>
-
 #include "slimq_chain.hpp"
 #include "slimq_tiles.hpp"
 
 namespace {
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // what hs_graph_convert_slimq is refused for, before any work
 hs_status convert_args_ok(const hs_graph *g, const hs_slimq_params *p, int convert_device, const char *out_path, int index_device, hs_index **out_index) {
@@ -22,13 +16,14 @@ hs_status convert_args_ok(const hs_graph *g, const hs_slimq_params *p, int conve
   if (convert_device >= 0 && (st = slimq_device_ok(convert_device)) != HS_OK) return st;
   if (out_index) {
     if (index_device < 0) return fail(HS_ERR_INVALID, "index_device: a HIP device");
-    if (hs_device_count() <= index_device) return fail(HS_ERR_DEVICE, "no HIP device (this library has no CPU search path)");
+    if (device_ok(index_device, true) != HS_OK) return HS_ERR_DEVICE;
   }
   return HS_OK;
 }
 
 // The chain on in-memory objects: graph passes, records, then the file and / or the resident index.  resident_ms (nullable): packing,
 // uploads, tile kernels and the dataset upload.  rows (nullable): the graph's rows as one contiguous array, where the caller has one.
+// (Throws what the converters throw: the two entries that call it guard.)
 hs_status convert_graph(const RqGraph &g, const hs_slimq_params *p, int convert_device, int threads, const char *out_path, int index_device,
                         int with_dataset, const float *rows, hs_index **out_index, hs_slimq_convert_stats *stats, double *resident_ms,
                         double *tile_kernel_ms) {
@@ -36,7 +31,7 @@ hs_status convert_graph(const RqGraph &g, const hs_slimq_params *p, int convert_
   hs_slimq_convert_stats out{};
   const int metric = (int)g.metric;
   std::unique_ptr<SlimQGraph> q(new SlimQGraph());
-  try {
+  {
     SlimGraph s;
     hs_status st = slimq_graph_step(s, g, slim_params(p->threshold_level, p->top_degree_percent0, p->top_degree_percent, p->top_degree_M0, p->low_degree_m0,
                                                       p->top_degree_M, p->low_degree_m),
@@ -49,10 +44,6 @@ hs_status convert_graph(const RqGraph &g, const hs_slimq_params *p, int convert_
     if (st != HS_OK) return st;
     out.records_ms = ms_since(t1);
     if (out_path) q->save(out_path);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
   }
   if (out_index) {
     const auto t2 = std::chrono::steady_clock::now();
@@ -80,46 +71,37 @@ hs_status hs_build_rabitq_hnsw_batched_mem(const float *base, size_t n, size_t d
   if (!out) return fail(HS_ERR_INVALID, "bad argument");
   hs_status s = rq_batched_args_ok(base, n, dim, metric, M, opts);
   if (s != HS_OK) return s;
-  const auto t0 = std::chrono::steady_clock::now();
-  hs_batch_build_stats st{};
-  std::unique_ptr<hs_graph> g;
-  try {
-    g.reset(new hs_graph());
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  }
-  s = rq_batched_build_into(g->g, base, n, dim, metric, M, ef_construction, seed, opts, st);
-  if (s != HS_OK) return s;
-  st.total_ms = ms_since(t0);
-  if (stats) *stats = st;
-  *out = g.release();
-  return HS_OK;
+  return guarded([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    hs_batch_build_stats st{};
+    std::unique_ptr<hs_graph> g(new hs_graph());
+    s = rq_batched_build_into(g->g, base, n, dim, metric, M, ef_construction, seed, opts, st);
+    if (s != HS_OK) return s;
+    st.total_ms = ms_since(t0);
+    if (stats) *stats = st;
+    *out = g.release();
+    return HS_OK;
+  });
 }
 
 hs_status hs_graph_load(const char *path, int metric, size_t dim, hs_graph **out) {
   if (!path || !out) return fail(HS_ERR_INVALID, "bad argument");
-  if (metric != HS_METRIC_L2 && metric != HS_METRIC_IP) return fail(HS_ERR_INVALID, "bad metric");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
-  try {
+  return guarded([&] {
     std::unique_ptr<hs_graph> g(new hs_graph());
     g->g.load(path, (Metric)metric, dim);
     *out = g.release();
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 hs_status hs_graph_save(const hs_graph *g, const char *path) {
   if (!g || !path) return fail(HS_ERR_INVALID, "bad argument");
-  try {
+  return guarded([&] {
     g->g.save(path);
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 hs_status hs_graph_info(const hs_graph *g, uint64_t *n, uint64_t *dim, int *metric, uint64_t *M, uint64_t *ef_construction, int *maxlevel) {
@@ -139,7 +121,7 @@ hs_status hs_graph_convert_slimq(const hs_graph *g, const hs_slimq_params *p, in
                                  int index_device, int with_dataset, hs_index **out_index, hs_slimq_convert_stats *stats) {
   const hs_status st = convert_args_ok(g, p, convert_device, out_path, index_device, out_index);
   if (st != HS_OK) return st;
-  return convert_graph(g->g, p, convert_device, threads, out_path, index_device, with_dataset, nullptr, out_index, stats, nullptr, nullptr);
+  return guarded([&] { return convert_graph(g->g, p, convert_device, threads, out_path, index_device, with_dataset, nullptr, out_index, stats, nullptr, nullptr); });
 }
 
 hs_status hs_slimq_index_from_rows(const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
@@ -150,34 +132,29 @@ hs_status hs_slimq_index_from_rows(const float *base, size_t n, size_t dim, int 
   if (s != HS_OK) return s;
   if (opts->device < 0) return fail(HS_ERR_INVALID, "hs_slimq_index_from_rows: opts->device is the HIP device the index will live on");
   if ((s = slimq_records_args_ok(metric, dim, p->centroids, p->num_cluster)) != HS_OK) return s;
-  const auto t0 = std::chrono::steady_clock::now();
-  hs_slimq_pipeline_stats out{};
-  std::unique_ptr<hs_graph> g;
-  try {
-    g.reset(new hs_graph());
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  }
-  s = rq_batched_build_into(g->g, base, n, dim, metric, M, ef_construction, seed, opts, out.build);
-  if (s != HS_OK) return s;
-  out.build.total_ms = ms_since(t0);
-  // (labels are row indexes and internal ids in this graph: `base` is the dataset by internal id)
-  s = convert_graph(g->g, p, opts->device, threads, nullptr, opts->device, with_dataset, base, out_index, &out.convert, &out.resident_ms, &out.tile_kernel_ms);
-  if (s != HS_OK) return s;
-  out.total_ms = ms_since(t0);
-  if (stats) *stats = out;
-  return HS_OK;
+  return guarded([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    hs_slimq_pipeline_stats out{};
+    std::unique_ptr<hs_graph> g(new hs_graph());
+    s = rq_batched_build_into(g->g, base, n, dim, metric, M, ef_construction, seed, opts, out.build);
+    if (s != HS_OK) return s;
+    out.build.total_ms = ms_since(t0);
+    // (labels are row indexes and internal ids in this graph: `base` is the dataset by internal id)
+    s = convert_graph(g->g, p, opts->device, threads, nullptr, opts->device, with_dataset, base, out_index, &out.convert, &out.resident_ms, &out.tile_kernel_ms);
+    if (s != HS_OK) return s;
+    out.total_ms = ms_since(t0);
+    if (stats) *stats = out;
+    return HS_OK;
+  });
 }
 
 hs_status hs_slimq_index_save(const hs_index *ix, const char *path) {
   if (!ix || !path) return fail(HS_ERR_INVALID, "null argument");
   if (!ix->host_slimq) return fail(HS_ERR_INVALID, "not a SlimQ index");
-  try {
+  return guarded([&] {
     ix->host_slimq->save(path);
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
-  return HS_OK;
+    return HS_OK;
+  });
 }
 
 // hands `v` (or its length alone) to a debug caller
@@ -203,14 +180,16 @@ hs_status hs_debug_slimq_arrays(const hs_index *ix, int which, uint32_t *out, si
   if (which == 2 && d.uptile) { src = d.uptile; st = d.up_stride; rw = d.rec_words + 4; len = ix->up_ptr.n * (size_t)st * rw; }
   if (stride) *stride = st;
   if (row_words) *row_words = rw;
-  if (len) HIP_TRY(hipSetDevice(ix->device));
-  return give_words(nullptr, src, len, out, cap_words, words);
+  return guarded([&] {
+    if (len) HIP_TRY(hipSetDevice(ix->device));
+    return give_words(nullptr, src, len, out, cap_words, words);
+  });
 }
 
 hs_status hs_debug_slimq_arrays_host(const char *slimq_path, int metric, size_t dim, int fused, int which, uint32_t *out, size_t cap_words,
                                      size_t *words, uint32_t *stride, uint32_t *row_words) {
   if (!slimq_path || which < 0 || which > 2) return fail(HS_ERR_INVALID, "bad argument");
-  try {
+  return guarded([&] {
     SlimQGraph q;
     q.load(BinSource(slimq_path), metric, dim);
     if (q.rot.trunc < 64) return fail(HS_ERR_UNSUPPORTED, "SlimQ supports dim >= 64");
@@ -234,9 +213,5 @@ hs_status hs_debug_slimq_arrays_host(const char *slimq_path, int metric, size_t 
     if (stride) *stride = st;
     if (row_words) *row_words = w;
     return give_words(which == 0 ? rec.data() : arr.data(), nullptr, which == 0 ? rec.size() : arr.size(), out, cap_words, words);
-  } catch (std::bad_alloc &) {
-    return fail(HS_ERR_NOMEM, "Not enough memory");
-  } catch (std::exception &e) {
-    return from_exception(e);
-  }
+  });
 }

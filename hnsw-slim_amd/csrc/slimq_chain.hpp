@@ -16,11 +16,11 @@ hs_status rq_batched_args_ok(const float *base, size_t n, size_t dim, int metric
 hs_status rq_batched_build_into(RqGraph &g, const float *base, size_t n, size_t dim, int metric, size_t M, size_t ef_construction, size_t seed,
                                 const hs_batch_build_opts *opts, hs_batch_build_stats &st);
 // capi_convert_slimq.cpp
-SlimParams slim_params(int threshold_level, float top_degree_percent0, float top_degree_percent, size_t top_degree_M0, size_t low_degree_m0,
-                       size_t top_degree_M, size_t low_degree_m);
 hs_status slimq_records_args_ok(int metric, size_t dim, const float *centroids, size_t num_cluster);
 hs_status slimq_device_ok(int device);
-// The graph passes into `s`: on `device`, or on the host when device < 0 or the shape is outside the device path.
+// Slim's graph passes into `s`: on `device`, or on the host when the shape is outside the device path.
+hs_status slim_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms);
+// SlimQ's graph passes into `s`: on `device`, or on the host when device < 0 or the shape is outside the device path.
 hs_status slimq_graph_step(SlimGraph &s, const VanillaGraph &g, const SlimParams &p, int device, int threads, int *used_gpu, double *kernel_ms);
 // The records of `s` into `q` (SlimQGraph::from_slim): on `device`, or on the host when device < 0.
 hs_status slimq_records_step(SlimQGraph &q, const SlimGraph &s, int metric, const float *centroids, size_t num_cluster, const uint32_t *cluster_ids,
