@@ -33,6 +33,7 @@ EXPORTS = [
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
     "hs_index_exact_search", "hs_index_exact_search_dev",
+    "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
@@ -215,6 +216,10 @@ def lib():
         L.hs_queue_drain.argtypes = [vp]
         L.hs_queue_info.argtypes = [vp, ctypes.POINTER(HsQueueInfo)]
     L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_exact_search_screened.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_screened_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_exact_screen_stats.argtypes = [vp, vp, vp, vp]
+    L.hs_debug_exact_screen_margin.argtypes = [ci, sz, ctypes.c_float, ctypes.c_float, vp]
     L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
     L.hs_index_seed_levels.argtypes = [vp, sz, sz]
     L.hs_index_mark_deleted.argtypes = [vp, vp, sz, ci]
@@ -810,6 +815,14 @@ def debug_heap_ops(ops, wave_pop=True, lds_slots=1024):
     _check(lib().hs_debug_heap_ops(arr.ctypes.data, n, 1 if wave_pop else 0, lds_slots, heap.ctypes.data, pops.ctypes.data, cnt.ctypes.data))
     f = lambda a, m: [(float(a[i, 0:1].view(np.float32)[0]), int(a[i, 1])) for i in range(m)]
     return f(heap, int(cnt[0])), f(pops, int(cnt[1]))
+
+
+def exact_screen_margin(metric, dim, qn2, xn2):
+    """hs_debug_exact_screen_margin (host only): the screened exact search's bound e on |screened distance - recipe distance| from the
+    fp32 squared norms of a query and a row; +inf where the screen does not decide."""
+    out = ctypes.c_float()
+    _check(lib().hs_debug_exact_screen_margin(metric, dim, float(qn2), float(xn2), ctypes.byref(out)))
+    return np.float32(out.value)
 
 
 def brute_force(base, queries, k, metric=HS_METRIC_L2, labels=None, device=0):
@@ -1452,6 +1465,9 @@ class Index:
         """hs_index_exact_search: exact k-NN over the rows this index holds (fp32 or its narrow copy), under its delete marks and,
         with a FilterSet `fs`, query i under filter filter_of_query[i].  labels / dists nq x k ascending by (dist, label), ~0 / +inf
         beyond cnt[i].  ef, exact order and capacity settings do not apply."""
+        return self._exact_host(lib().hs_index_exact_search, queries, k, fs, filter_of_query)
+
+    def _exact_host(self, entry, queries, k, fs, filter_of_query):
         q = np.ascontiguousarray(queries, np.float32)
         nq = q.shape[0]
         foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
@@ -1460,9 +1476,27 @@ class Index:
         labels = np.empty((nq, k), np.uint64)
         dists = np.empty((nq, k), np.float32)
         cnt = np.empty(nq, np.uint32)
-        _check(lib().hs_index_exact_search(self._h, None if fs is None else fs._h, q.ctypes.data, nq, k,
-                                           None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
+        _check(entry(self._h, None if fs is None else fs._h, q.ctypes.data, nq, k,
+                     None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
         return dict(labels=labels, dists=dists, cnt=cnt)
+
+    def exact_search_screened(self, queries, k, fs=None, filter_of_query=None):
+        """hs_index_exact_search_screened: exact_search's answers bit for bit, by an MFMA screen with a proven margin, a re-rank in
+        the reference's arithmetic and, per query, the scan where the screen cannot decide.  exact_screen_stats() tells which."""
+        return self._exact_host(lib().hs_index_exact_search_screened, queries, k, fs, filter_of_query)
+
+    def exact_search_screened_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_screened_dev: exact_search_dev's arguments; asynchronous, pair with check(stream)."""
+        _check(lib().hs_index_exact_search_screened_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                                        None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                                        d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_screen_stats(self):
+        """hs_index_exact_screen_stats of the last screened call: dict(screened, fell_back, reranked_rows); zeros when it was handed to
+        the scan whole."""
+        v = (ctypes.c_uint64 * 3)()
+        _check(lib().hs_index_exact_screen_stats(self._h, ctypes.byref(v, 0), ctypes.byref(v, 8), ctypes.byref(v, 16)))
+        return dict(screened=int(v[0]), fell_back=int(v[1]), reranked_rows=int(v[2]))
 
     def exact_search_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
         """hs_index_exact_search_dev: device tensors (queries f32 nq x d, labels int64 nq x k, dists f32 nq x k, counts int32 nq,

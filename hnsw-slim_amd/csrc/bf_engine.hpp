@@ -17,5 +17,8 @@ hipError_t launch_brute_force(const float *base, const uint64_t *labels, uint32_
 // nruns <= 1024 (what bf_partial_bytes plans: grid_x * 4)
 hipError_t launch_bf_merge(const void *partial, uint32_t nq, uint32_t k, uint32_t nruns, uint64_t *out_labels, float *out_dists,
                            uint32_t *out_counts, hipStream_t stream);
+// the merge for a subset found on the device: block i < *count serves query subset[i]; every other query's outputs stay untouched
+hipError_t launch_bf_merge_subset(const void *partial, uint32_t nq, uint32_t k, uint32_t nruns, const uint32_t *subset, const uint32_t *count,
+                                  uint64_t *out_labels, float *out_dists, uint32_t *out_counts, hipStream_t stream);
 
 }  // namespace hs

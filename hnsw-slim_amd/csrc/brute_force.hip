@@ -124,9 +124,8 @@ __global__ void __launch_bounds__(64 * kWaves) bf_scan_general_kernel(const floa
 }
 
 // one wave per query: k rounds of a k-way merge over the sorted runs
-__global__ void __launch_bounds__(64) bf_merge_kernel(const BfEntry *partial, uint32_t nq, uint32_t k, uint32_t nruns, uint64_t *out_labels,
-                                                      float *out_dists, uint32_t *out_counts) {
-  const uint32_t qi = blockIdx.x;
+__device__ __forceinline__ void bf_merge_query(const BfEntry *partial, uint32_t qi, uint32_t k, uint32_t nruns, uint64_t *out_labels,
+                                               float *out_dists, uint32_t *out_counts) {
   const int lane = threadIdx.x;
   const BfEntry *runs = partial + (size_t)qi * nruns * k;
   // lane owns runs lane, lane+64, ...; head[j] = next unread entry of its j-th run (at most 16 runs per lane here)
@@ -170,6 +169,17 @@ __global__ void __launch_bounds__(64) bf_merge_kernel(const BfEntry *partial, ui
   for (uint32_t i = found + lane; i < k; i += 64) { out_labels[(size_t)qi * k + i] = ~0ull; out_dists[(size_t)qi * k + i] = INFINITY; }
   if (lane == 0 && out_counts) out_counts[qi] = found;
 }
+__global__ void __launch_bounds__(64) bf_merge_kernel(const BfEntry *partial, uint32_t nq, uint32_t k, uint32_t nruns, uint64_t *out_labels,
+                                                      float *out_dists, uint32_t *out_counts) {
+  bf_merge_query(partial, blockIdx.x, k, nruns, out_labels, out_dists, out_counts);
+}
+// the same for the first *count queries that `subset` names (exact_screen.hip's fallback): the other queries' outputs are left alone
+__global__ void __launch_bounds__(64) bf_merge_subset_kernel(const BfEntry *partial, uint32_t nq, uint32_t k, uint32_t nruns, const uint32_t *subset,
+                                                             const uint32_t *count, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) {
+  if (blockIdx.x >= *count) return;
+  const uint32_t qi = subset[blockIdx.x];
+  if (qi < nq) bf_merge_query(partial, qi, k, nruns, out_labels, out_dists, out_counts);
+}
 
 size_t bf_partial_bytes(uint32_t n, uint32_t nq, uint32_t k, uint32_t *grid_x, uint32_t *rows_per_block) {
   // enough row chunks to fill the chip (256 CUs) for small query counts, at most 256 runs per query (16 per merge lane / 4 waves)
@@ -209,6 +219,14 @@ hipError_t launch_bf_merge(const void *partial, uint32_t nq, uint32_t k, uint32_
                            uint32_t *out_counts, hipStream_t stream) {
   if (nruns > 16 * 64) return hipErrorInvalidValue;   // 16 runs per merge lane
   hipLaunchKernelGGL(bf_merge_kernel, dim3(nq), dim3(64), 0, stream, (const BfEntry *)partial, nq, k, nruns, out_labels, out_dists, out_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_bf_merge_subset(const void *partial, uint32_t nq, uint32_t k, uint32_t nruns, const uint32_t *subset, const uint32_t *count,
+                                  uint64_t *out_labels, float *out_dists, uint32_t *out_counts, hipStream_t stream) {
+  if (nruns > 16 * 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bf_merge_subset_kernel, dim3(nq), dim3(64), 0, stream, (const BfEntry *)partial, nq, k, nruns, subset, count, out_labels, out_dists,
+                     out_counts);
   return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 #include "bf_engine.hpp"
 #include "build_engine.hpp"
 #include "exact_engine.hpp"
+#include "exact_screen_engine.hpp"
+#include "exact_screen_margin.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -412,10 +414,12 @@ static hs_status exact_use_ok(const hs_index *ix, const hs_filter_set *fs, const
 }
 
 // d_order (nullable): per launch group, a permutation of the group's own query indices.
+// screened: through exact_screen.hip where its envelope holds (dim % 16 == 0 and a tile that fits the on-chip memory), the scan otherwise.
 static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d_q, size_t nq, size_t k, const uint32_t *d_foq,
-                           const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+                           const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream, bool want_screen = false) {
   HIP_TRY(hipSetDevice(ix->device));
   hs_index::StreamWs *w = ix->stream_ws(stream);
+  const bool screened = want_screen && xs_supported((uint32_t)ix->info.dim, (uint32_t)k);
   if (w->counters.n < 48) {   // (as search_dev_group: sticky until hs_search_check reads and clears them)
     HIP_TRY(w->counters.ensure(48));
     HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
@@ -424,7 +428,20 @@ static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d
   const int fmt = ix->row_fmt;
   const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
   const size_t dim = ix->info.dim;
-  ix->last_kernel = (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+  ix->last_kernel = screened ? xs_kernel_name(fmt)
+                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+  const size_t gq = std::min(kExactGroupQueries, nq);
+  if (screened) {
+    HIP_TRY(w->xs_norms.ensure((size_t)ix->dev.n + gq));
+    HIP_TRY(w->xs_state.ensure(kXsStateWords + 2 * gq));
+    size_t cand = 16;   // the largest any group of the call needs: a full group and the last one
+    for (size_t m : {gq, nq - (nq - 1) / kExactGroupQueries * kExactGroupQueries}) {
+      uint32_t gx, rpb;
+      cand = std::max(cand, xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &gx, &rpb));
+    }
+    HIP_TRY(w->xs_cand.ensure(cand));
+    HIP_TRY(launch_exact_screen_norms(ix->dev, rows, fmt, w->xs_norms.p, stream));
+  }
   for (size_t off = 0; off < nq; off += kExactGroupQueries) {
     const size_t m = std::min(kExactGroupQueries, nq - off);
     ExactArgs a{};
@@ -435,7 +452,22 @@ static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d
     a.out_labels = l64 + off * k; a.out_dists = dd + off * k; a.out_counts = cnt ? cnt + off : nullptr;
     FilterArgs fa{};
     if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
-    HIP_TRY(launch_exact_search(ix->dev, rows, fmt, a, fs ? &fa : nullptr, stream));
+    if (!screened) {
+      HIP_TRY(launch_exact_search(ix->dev, rows, fmt, a, fs ? &fa : nullptr, stream));
+      continue;
+    }
+    ScreenArgs sa{};
+    sa.x = a;
+    sa.first_group = off == 0;
+    xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &sa.grid_x, &sa.rows_per_block);
+    sa.xnorm2 = w->xs_norms.p; sa.qnorm2 = w->xs_norms.p + ix->dev.n;
+    sa.cand = w->xs_cand.p;
+    sa.state = w->xs_state.p; sa.qflag = w->xs_state.p + kXsStateWords; sa.fb_order = sa.qflag + gq;
+    HIP_TRY(launch_exact_screen(ix->dev, rows, fmt, sa, fs ? &fa : nullptr, stream));
+  }
+  if (want_screen) {   // (the plain entries leave the last screened call's stats alone)
+    ix->xs_last = screened ? w : nullptr;
+    ix->xs_last_nq = nq;
   }
   return HS_OK;
 }
@@ -450,8 +482,8 @@ hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const
   });
 }
 
-hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
-                                const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k, const uint32_t *filter_of_query,
+                            uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
   return guarded([&] {
     hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
     if (s != HS_OK) return s;
@@ -480,7 +512,7 @@ hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const flo
       HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
       HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
     }
-    s = exact_dev(ix, fs, w->aq.p, nq, k, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->al64.p, w->adist.p, w->acnt.p, nullptr);
+    s = exact_dev(ix, fs, w->aq.p, nq, k, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened);
     if (s != HS_OK) return s;
     HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, nq * k * 4, hipMemcpyDeviceToHost, nullptr));
@@ -488,6 +520,47 @@ hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const flo
     HIP_TRY(hipStreamSynchronize(nullptr));
     return HS_OK;
   });
+}
+
+hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false);
+}
+
+// ---- the same answers by screen, re-rank and fallback (exact_screen.hip) -------------------------------------------------------
+hs_status hs_index_exact_search_screened(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                         const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+}
+hs_status hs_index_exact_search_screened_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                             const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                             uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream, true);
+  });
+}
+hs_status hs_index_exact_screen_stats(hs_index *ix, uint64_t *screened, uint64_t *fell_back, uint64_t *reranked_rows) {
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  return guarded([&] {
+    uint32_t st[kXsStateWords] = {};
+    if (ix->xs_last) {
+      HIP_TRY(hipSetDevice(ix->device));
+      HIP_TRY(hipMemcpy(st, ix->xs_last->xs_state.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    if (screened) *screened = ix->xs_last ? ix->xs_last_nq - st[1] : 0;
+    if (fell_back) *fell_back = st[1];
+    if (reranked_rows) *reranked_rows = (uint64_t)st[2] | ((uint64_t)st[3] << 32);
+    return HS_OK;
+  });
+}
+hs_status hs_debug_exact_screen_margin(int metric, size_t dim, float qnorm2, float xnorm2, float *out) {
+  if (!out) return fail(HS_ERR_INVALID, "null argument");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
+  if (dim == 0 || dim > 4096) return fail(HS_ERR_INVALID, "dim: 1 to 4096");
+  *out = exact_screen_margin(metric == HS_METRIC_IP, (uint32_t)dim, qnorm2, xnorm2);
+  return HS_OK;
 }
 
 hs_status hs_convert_slimq(const char *slim_path, int metric, size_t dim, const float *centroids, size_t num_cluster,

@@ -122,8 +122,15 @@ struct hs_index {
     DevBuf<uint32_t> afoq;              // hs_search_batch_filter_set: the per-query filter indices of the call in flight
     DevBuf<uint8_t> xruns;              // hs_index_exact_search: the sorted runs between the scan and the merge
     DevBuf<uint32_t> xorder;            // hs_index_exact_search (host entry): the queries grouped by filter
+    // hs_index_exact_search_screened (exact_screen.hip): row and query norms; the candidate lists between screen and re-rank; the
+    // state words (exact_screen_engine.hpp), then per query of a launch group its fallback flag and the fallback's order
+    DevBuf<float> xs_norms;
+    DevBuf<uint8_t> xs_cand;
+    DevBuf<uint32_t> xs_state;
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
+  StreamWs *xs_last = nullptr;   // hs_index_exact_screen_stats: the workspace of the last screened call (null: none, or it was delegated)
+  uint64_t xs_last_nq = 0;
   std::mutex ws_mu;
   StreamWs *stream_ws(hipStream_t st) {
     std::lock_guard<std::mutex> g(ws_mu);

@@ -28,5 +28,10 @@ size_t exact_lds_bytes(uint32_t dim, uint32_t k);
 // rows / fmt: ROWS_F32 reads ix.vec (rows ignored; dim % 16 != 0 takes the one-lane-per-row recipes), ROWS_U8 / ROWS_F16 read `rows`,
 // the index's narrow copy (dim % 16 == 0).  Labels come from ix.labels.  Nothing synchronises: the scan and the merge are enqueued.
 hipError_t launch_exact_search(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, hipStream_t stream);
+// The same for a subset found on the device (exact_screen.hip's fallback): a.order (device, a.nq words) names the *count queries to
+// serve in its first *count words and holds 0xFFFFFFFF in the others; only those queries' outputs are written.  The launch is sized
+// by a.nq, so nothing is read back: a tile whose slots name no query skips every row.
+hipError_t launch_exact_search_subset(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, const uint32_t *count,
+                                      hipStream_t stream);
 
 }  // namespace hs

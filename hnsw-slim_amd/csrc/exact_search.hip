@@ -255,7 +255,8 @@ size_t exact_lds_bytes(uint32_t dim, uint32_t k) {
   return (((size_t)kQT * dim * 4 + 15) & ~(size_t)15) + (size_t)kWaves * kQT * k * sizeof(BfEntry) + (kWaves * kQT + 2 * kQT) * 4;
 }
 
-hipError_t launch_exact_search(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, hipStream_t stream) {
+// The scan alone: the sorted runs of every slot that names a query, left in a.partial for a merge.
+static hipError_t launch_exact_scan(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, hipStream_t stream) {
   const size_t lds = exact_lds_bytes(ix.dim, a.k);
   if (lds > 160 * 1024) return hipErrorInvalidValue;   // the query tile no longer fits the CU's LDS
   const bool general = (ix.dim & 15u) != 0;
@@ -279,9 +280,21 @@ hipError_t launch_exact_search(const DevIndex &ix, const void *rows, int fmt, co
   sa.n = ix.n; sa.dim = ix.dim; sa.nq = a.nq; sa.k = a.k; sa.rows_per_block = a.rows_per_block;
   const dim3 grid(a.grid_x, (a.nq + kQT - 1) / kQT);
   hipLaunchKernelGGL(kern, grid, dim3(64 * kWaves), lds, stream, sa);
-  hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_search(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, hipStream_t stream) {
+  const hipError_t e = launch_exact_scan(ix, rows, fmt, a, f, stream);
   if (e != hipSuccess) return e;
   return launch_bf_merge(a.partial, a.nq, a.k, a.grid_x * kWaves, a.out_labels, a.out_dists, a.out_counts, stream);
+}
+
+hipError_t launch_exact_search_subset(const DevIndex &ix, const void *rows, int fmt, const ExactArgs &a, const FilterArgs *f, const uint32_t *count,
+                                      hipStream_t stream) {
+  if (!a.order || !count) return hipErrorInvalidValue;
+  const hipError_t e = launch_exact_scan(ix, rows, fmt, a, f, stream);
+  if (e != hipSuccess) return e;
+  return launch_bf_merge_subset(a.partial, a.nq, a.k, a.grid_x * kWaves, a.order, count, a.out_labels, a.out_dists, a.out_counts, stream);
 }
 
 }  // namespace hs

@@ -295,15 +295,19 @@ class DeviceIndex {
     uint32_t cnt = 0;
     const uint32_t row = 0;
     const hs_filter_set *fs = f ? filter_row_set(f) : nullptr;
-    check(hs_index_exact_search(h_, fs, (const float *)q, 1, k, f ? &row : nullptr, labels.data(), dists.data(), &cnt));
+    check((exact_screened_ ? hs_index_exact_search_screened : hs_index_exact_search)(h_, fs, (const float *)q, 1, k, f ? &row : nullptr, labels.data(),
+                                                                                   dists.data(), &cnt));
     for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);
     return result;
   }
   // every row of `queries` in one launch; out_* nq x k ascending by (dist, label), UINT64_MAX / +inf beyond out_counts[q] (nullable)
   void exact_batch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) const {
     if (!h_) throw std::runtime_error("hnswlib_amd: no index loaded");
-    check(hs_index_exact_search(h_, nullptr, queries, nq, k, nullptr, out_labels, out_dists, out_counts));
+    check((exact_screened_ ? hs_index_exact_search_screened : hs_index_exact_search)(h_, nullptr, queries, nq, k, nullptr, out_labels, out_dists, out_counts));
   }
+  // searchKnnExact / searchKnnExactBatch through hs_index_exact_search_screened: the same answers bit for bit, the distances of all
+  // but a few rows per query from the matrix cores (off by default)
+  bool exact_screened_ = false;
 };
 }  // namespace detail
 
@@ -527,6 +531,8 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     ensure_built();
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
   }
+  // the two calls above through the screened entry (hs_index_exact_search_screened): the same answers; off by default
+  void setExactScreened(bool on) { exact_screened_ = on; }
   // Batched searchKnn: nq x dim queries; out_labels / out_dists nq x k (unused slots: UINT64_MAX / +inf).
   void searchKnnBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists,
                       uint32_t *out_counts) const {
@@ -682,6 +688,8 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
   }
+  // the two calls above through the screened entry (hs_index_exact_search_screened): the same answers; off by default
+  void setExactScreened(bool on) { exact_screened_ = on; }
   // searchKnn(q, k, tableint* result): hnswalg_slim.h:2030-2131.  k labels; same k-subset as the reference,
   // sorted by distance (call setExactOrder(true) to also reproduce the reference's array order).
   void searchKnn(const void *query_data, size_t k, tableint *result) const {

@@ -587,6 +587,29 @@ hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const
                                     const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
                                     uint32_t *d_out_counts, void *stream);
 
+/* ---- the same answers, screened on the matrix cores -------------------------------------------------------------------
+ * hs_index_exact_search[_dev]'s arguments, refusals and outputs -- labels, fp32 distance bits, counts and padding are identical for
+ * every input -- by another route (csrc/exact_screen.hip): an MFMA distance with a proven error margin rules out all
+ * but a few rows per query, those are re-ranked in the reference's arithmetic, and a query the screen cannot decide (a non-finite
+ * norm or interval, such as an L2 distance that overflows; more near-ties than its candidate lists hold) is answered by the scan
+ * above, enqueued behind the re-rank for those queries only.  Nothing is read back between the passes.
+ * Screened: dim % 16 == 0 (dim <= 4096, k <= 64 as for the scan); a tile of 64 queries that does not fit the on-chip memory whole is
+ * staged in slices of 128 values.  Every other call the scan accepts (dim % 16 != 0) is handed to it whole.
+ * hs_last_kernel: hs::xs_screen_kernel, hs::xs_screen_kernel_u8 or hs::xs_screen_kernel_f16 (the scan's name when handed over).
+ * The host entry groups the queries by filter before it forms tiles of 64. */
+hs_status hs_index_exact_search_screened(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                         const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+hs_status hs_index_exact_search_screened_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                             const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                             uint32_t *d_out_counts, void *stream);
+/* The last screened call on this index: queries the screen and re-rank answered, queries that fell back to the scan, rows re-ranked.
+ * All zero after a screened call that was handed to the scan whole; hs_index_exact_search[_dev] leaves them as they are.  Valid after the host entry returns; after the _dev entry once
+ * hs_search_check has returned for its stream.  Each pointer may be NULL. */
+hs_status hs_index_exact_screen_stats(hs_index *ix, uint64_t *screened, uint64_t *fell_back, uint64_t *reranked_rows);
+/* Debug: the screen's margin e with |screened distance - recipe distance| <= e (csrc/exact_screen_margin.hpp; host only), from the
+ * fp32 squared norms of query and row.  +inf: the screen does not decide such a pair. */
+hs_status hs_debug_exact_screen_margin(int metric, size_t dim, float qnorm2, float xnorm2, float *out);
+
 /* ---- harness (CPU, not accelerated): produce index files in the reference's formats ------------ */
 /* HierarchicalNSW ctor + addPoint loop + saveIndex: hnswalg.h:85-159, 1248-1376, 748-779.
  * labels = row index; threads==1 reproduces the reference's serial build byte for byte. */

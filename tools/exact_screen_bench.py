@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""exact_screen_bench.py -- hs_index_exact_search_dev against hs_index_exact_search_screened_dev on the bench's rows and queries
+(headline_data seeds 123 / 456: 1M x 128, 10 000 queries, k = 10).  ONE index in ONE process, both entries warmed, then alternated
+old, new, old, new for three rounds; HIP-event time per call, median of `--reps`; outputs compared bit for bit before any timing.
+
+  1. unfiltered over fp32 rows      2. unfiltered over the u8 copy      3. eight filters that allow 1 %, queries grouped by filter
+
+The spread of the old entry's own rounds is the noise: a difference counts only where it lies outside it.  By default the index is the
+bench's cached one; --ring puts the same rows under a ring graph instead (the exact entries read rows, labels and marks, never the
+graph), which spares a fresh machine the HNSW build.  Output: the log on stdout.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from bench import prepare_cached  # noqa: E402
+from hsutil import headline_data, load_product  # noqa: E402
+
+N, D, NQ, K, PER = 1_000_000, 128, 10_000, 10, 8
+
+
+def log(*a):
+    print(*a, flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--ring", action="store_true", help="the bench's rows under a ring graph: no HNSW build")
+    ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
+    args = ap.parse_args()
+    import torch
+    torch.cuda.init()
+    hs = load_product()
+    dev = torch.device("cuda", 0)
+    if args.ring:
+        ids = np.arange(N, dtype=np.uint32)
+        ix = hs.Index.from_csr(hs.HS_KIND_SLIM, hs.HS_METRIC_L2, headline_data(N, D, 123), np.zeros(N, np.int32), np.arange(N + 1, dtype=np.uint64),
+                               (ids + 1) % N, 0, 0)
+        log("index: the bench's rows under a ring graph")
+    else:
+        idir = args.index_dir or prepare_cached(N, D, 1, hs)[0]
+        ix = hs.Index(os.path.join(idir, "slim.bin"), hs.HS_KIND_SLIM, D, hs.HS_METRIC_L2)
+        log(f"index: {os.path.basename(idir)}")
+    q = headline_data(NQ, D, 456)
+
+    def outputs():
+        return (torch.zeros((NQ, K), dtype=torch.int64, device=dev), torch.zeros((NQ, K), dtype=torch.float32, device=dev),
+                torch.zeros(NQ, dtype=torch.int32, device=dev))
+
+    def timed(fn):
+        ts = []
+        for _ in range(args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ix.check()
+        return float(np.median(ts))
+
+    result = {}
+
+    def compare(name, dq, kernel, **kw):
+        o_old, o_new = outputs(), outputs()
+        old = lambda: ix.exact_search_dev(dq, K, *o_old, **kw)            # noqa: E731
+        new = lambda: ix.exact_search_screened_dev(dq, K, *o_new, **kw)   # noqa: E731
+        old(); new(); ix.check()
+        assert ix.last_kernel() == kernel, ix.last_kernel()
+        for a, b, what in zip(o_old, o_new, ("labels", "dists", "counts")):
+            assert torch.equal(a, b), f"{name}: {what} differ"
+        st = ix.exact_screen_stats()
+        rows = dict(old=[], new=[])
+        for rnd in range(args.rounds):
+            for side, fn in (("old", old), ("new", new)):
+                rows[side].append(timed(fn))
+                log(f"{name} round {rnd} {side}: {rows[side][-1]:.3f} ms per {NQ}-query call (median of {args.reps})")
+        o, n = rows["old"], rows["new"]
+        spread = (max(o) - min(o)) / np.median(o) * 100
+        spread_new = (max(n) - min(n)) / np.median(n) * 100
+        delta = (np.median(n) / np.median(o) - 1) * 100
+        log(f"{name}: outputs identical | scan {np.median(o):.3f} ms ({', '.join(f'{x:.3f}' for x in o)}, spread {spread:.2f} %) | screened "
+            f"{np.median(n):.3f} ms ({', '.join(f'{x:.3f}' for x in n)}, spread {spread_new:.2f} %) | screened / scan {delta:+.2f} % -> "
+            + ("inside the spread: no difference shown" if abs(delta) <= max(spread, spread_new) else "outside the spread")
+            + f" | fell_back {st['fell_back']}, reranked_rows {st['reranked_rows']} ({st['reranked_rows'] / max(st['screened'], 1):.2f} per screened query)")
+        result[name] = dict(scan_ms=o, screened_ms=n, **st)
+
+    dq = torch.from_numpy(q).to(dev)
+    compare("fp32 rows", dq, "hs::xs_screen_kernel")
+    rng = np.random.default_rng(3)
+    fs = hs.FilterSet.create(ix, PER)
+    fs.write(0, (rng.random((PER, N)) < 0.01).astype(np.uint8))
+    foq = np.sort((np.arange(NQ) % PER).astype(np.int32), kind="stable")   # grouped by filter
+    compare("1 % allowed, grouped by filter", dq, "hs::xs_screen_kernel", fs=fs, d_filter_of_query=torch.from_numpy(foq).to(dev))
+    ix.set_row_format(hs.HS_ROWS_U8)
+    compare("u8 rows", dq, "hs::xs_screen_kernel_u8")
+    log("RESULT " + json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main() or 0)
