@@ -39,7 +39,7 @@ EXPORTS = [
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
     "hs_queue_create", "hs_queue_free", "hs_queue_submit", "hs_queue_submit_dev", "hs_queue_flush", "hs_queue_wait",
     "hs_queue_join_stream", "hs_queue_drain", "hs_queue_info",
-    "hs_build_hnsw_batched", "hs_build_schedule",
+    "hs_build_hnsw_batched", "hs_build_schedule", "hs_build_hnsw_batched_rows",
     "hs_index_add_points_batched", "hs_hnsw_resume_batched", "hs_debug_batched_add_changed",
     "hs_build_rabitq_hnsw_batched", "hs_debug_rq_raw_dist",
     "hs_convert_slimq_graph_gpu", "hs_convert_slimq_gpu", "hs_convert_hnsw_to_slimq", "hs_debug_rq_quantize_rows",
@@ -240,6 +240,8 @@ def lib():
         L.hs_build_hnsw_batched.argtypes = [vp, vp, sz, sz, ci, sz, sz, ctypes.c_char_p, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.c_char_p,
                                             ctypes.POINTER(HsBatchBuildStats)]
         L.hs_build_schedule.argtypes = [sz, sz, ctypes.c_char_p, sz, sz, sz, sz, vp, vp, vp, ctypes.POINTER(sz)]
+    if "HS_LIB" not in os.environ or hasattr(L, "hs_build_hnsw_batched_rows"):
+        L.hs_build_hnsw_batched_rows.argtypes = [vp, ci] + L.hs_build_hnsw_batched.argtypes[1:]
     if "HS_LIB" not in os.environ or hasattr(L, "hs_index_add_points_batched"):
         L.hs_index_add_points_batched.argtypes = [vp, vp, vp, sz, ctypes.POINTER(HsBatchBuildOpts), ctypes.POINTER(HsBatchBuildStats)]
         L.hs_debug_batched_add_changed.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -313,9 +315,14 @@ def lib():
     return L
 
 
+def last_error():
+    """hs_last_error: the message of the calling thread's last refused call."""
+    return lib().hs_last_error().decode()
+
+
 def _check(rc):
     if rc != HS_OK:
-        raise HsError(rc, lib().hs_last_error().decode())
+        raise HsError(rc, last_error())
 
 
 def device_count():
@@ -354,6 +361,32 @@ def build_hnsw_batched(base, out_path, metric=HS_METRIC_L2, M=16, ef_constructio
     _check(lib().hs_build_hnsw_batched(base.ctypes.data, lab.ctypes.data if lab is not None else None, base.shape[0], base.shape[1], metric, M,
                                        ef_construction, str(branching_factor).encode(), seed, ctypes.byref(opts), out_path.encode(),
                                        ctypes.byref(st)))
+    return {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows), "kernel_ms": st.kernel_ms,
+            "total_ms": st.total_ms}
+
+
+def build_hnsw_batched_rows(base, out_path, metric=HS_METRIC_L2, M=16, ef_construction=200, branching_factor="4", seed=100, device=-1, threads=1,
+                            grow_div=0, batch_max=0, scratch_ids=0, labels=None, row_format=None):
+    """hs_build_hnsw_batched_rows: build_hnsw_batched from rows held as np.uint8 or np.float16, read at that width on the
+    device; the file is build_hnsw_batched's for base.astype(np.float32), byte for byte.  row_format: from the dtype unless given.
+    Returns the same stats dict."""
+    base = np.ascontiguousarray(base)
+    if row_format is None:
+        row_format = {np.dtype(np.uint8): HS_ROWS_U8, np.dtype(np.float16): HS_ROWS_F16}.get(base.dtype)
+        if row_format is None:
+            raise HsError(HS_ERR_INVALID, "base: np.uint8 or np.float16 rows (fp32 rows: build_hnsw_batched)")
+    if base.ndim != 2:
+        raise HsError(HS_ERR_INVALID, "base: rows x dim")
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, np.uint64)
+        if lab.shape != (base.shape[0],):
+            raise HsError(HS_ERR_INVALID, "labels: one per row")
+    opts = HsBatchBuildOpts(device, threads, grow_div, batch_max, scratch_ids)
+    st = HsBatchBuildStats()
+    _check(lib().hs_build_hnsw_batched_rows(base.ctypes.data if base.size else None, row_format, lab.ctypes.data if lab is not None else None,
+                                            base.shape[0], base.shape[1], metric, M, ef_construction, str(branching_factor).encode(), seed,
+                                            ctypes.byref(opts), out_path.encode(), ctypes.byref(st)))
     return {"used_gpu": bool(st.used_gpu), "batches": int(st.batches), "flagged_rows": int(st.flagged_rows), "kernel_ms": st.kernel_ms,
             "total_ms": st.total_ms}
 

@@ -15,7 +15,8 @@ static constexpr uint32_t kBgMaxEfc = 512;
 static constexpr uint32_t kBgScratchIds = 4096;  // default on-chip share of one row: visited ids (candidates: half of it)
 
 struct GpuBuildInput {
-  const float *base = nullptr;   // n x dim (host)
+  const void *base = nullptr;    // n x dim (host), row-major, elements of `rows`
+  int rows = 0;                  // ROWS_F32, or ROWS_U8 / ROWS_F16 in natural order (hnswlib's flavour only)
   uint32_t n = 0, dim = 0;
   int metric = 0;
   uint32_t M = 0, maxM = 0, maxM0 = 0, efc = 0;   // as VanillaGraph::init leaves them

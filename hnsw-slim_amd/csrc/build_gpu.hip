@@ -23,6 +23,10 @@
 //   bga_mark_kernel    marks the lists of the old nodes that have incoming ids; after the last batch bga_count / bga_scan /
 //                      bga_scatter compact the marked lists in ascending order and bga_gather_kernel packs their slots and the
 //                      new nodes' slots into one dense buffer: what changed comes back, not everything.
+// Rows of u8 / fp16 (hs_build_hnsw_batched_rows): the row array's element type is a member of the flavour, and the two
+// kernels that read rows are compiled once more per narrow type by build_gpu_u8.hip / build_gpu_f16.hip (HS_BG_ROWS = 1 | 2), which
+// include this file up to those kernels and hold nothing else: objects of their own, built without the packed fp32 operations, whose
+// kernels a trace shows as hs::bg_search_kernel_u8 / _f16 and hs::bg_link_kernel_u8 / _f16.  The fp32 object is what it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,7 +35,21 @@
 #include "build_engine.hpp"
 #include "convert_common.hpp"
 #include "diff_prune.hpp"
+#include "narrow_rows.hpp"
 #include "rq_dist.hpp"
+
+#if !defined(HS_BG_ROWS)
+#define HS_BG_ROWS 0
+#endif
+#if HS_BG_ROWS == 0
+#define HS_BG_KERNEL(name) name
+#elif HS_BG_ROWS == 1
+#define HS_BG_KERNEL(name) name##_u8
+namespace hs { typedef uint8_t BgTuRow; }
+#else
+#define HS_BG_KERNEL(name) name##_f16
+namespace hs { typedef _Float16 BgTuRow; }
+#endif
 
 namespace hs {
 
@@ -40,7 +58,7 @@ static constexpr uint32_t kBgRerunGrid = 128;      // workgroups (and scratch ar
 static constexpr uint32_t kBgLdsLimit = 160 * 1024;
 
 struct BgDev {
-  const float *vec;
+  const void *vec;               // n x dim elements of the flavour's Row type, row-major
   uint32_t *l0, *lu;             // level-0 lists (s0 words each), upper lists (su words each)
   const uint32_t *upb, *lev;     // per node: first upper slot, level
   uint32_t n, dim, dpad, M, maxM, maxM0, s0, su, efc, topcap;
@@ -49,6 +67,8 @@ struct BgDev {
 __device__ __forceinline__ uint32_t *bg_list(const BgDev &g, uint32_t u, uint32_t level) {
   return level == 0 ? g.l0 + (size_t)u * g.s0 : g.lu + ((size_t)g.upb[u] + level - 1) * g.su;
 }
+template <class F>
+__device__ __forceinline__ const typename F::Row *bg_rows(const BgDev &g) { return static_cast<const typename F::Row *>(g.vec); }
 __device__ __forceinline__ uint32_t bg_task(const BgDev &g, uint32_t u, uint32_t level) { return cv_task_of(u, level, g.n, g.upb); }
 
 // ascending sort of arr[0..N) (N a power of two, padding entries behind every candidate); BEFORE()(a, b): a comes before b
@@ -91,20 +111,24 @@ __device__ __forceinline__ void bg_sort_top(Pair *topq, uint32_t topn, int lane)
 //   kKeptD             the keep loop records the kept distances (an LDS array of its own)
 //   kLinkCap           entries of the link kernel's arr / nid / nd: {new id} + a full list
 //   kSkipNamed         the link step leaves a list alone that already names the new id
+//   Row                the element type of the row array (BgDev::vec): what dists and the copies of a row into LDS read
 struct H2Before { __device__ __forceinline__ bool operator()(const Pair &a, const Pair &b) const { return h2_before(a, b); } };
 
 // hnswlib (hnswalg.h): both heaps compare distances only (CompareByFirst), so libstdc++'s push / pop mechanics decide among equal
 // distances; the candidate heap holds negated distances.  getNeighborsByHeuristic2 (:481-523) does nothing below M entries;
 // otherwise the candidates by (distance ascending, id descending), the keep loop, the kept entries re-emplaced and popped
-// (diff_prune.hpp).  sz <= 63 link candidates (kBgMaxM), one per lane.
-struct BgHnswlib {
+// (diff_prune.hpp).  sz <= 63 link candidates (kBgMaxM), one per lane.  ROW: fp32, or u8 / fp16 in natural order -- widened exactly
+// where they are read (build_rows.hpp), so every distance and therefore every decision is that of the fp32 build of the widened rows.
+template <class ROW>
+struct BgHnswlibRows {
+  using Row = ROW;
   static constexpr bool kKeptD = true, kSkipNamed = false;
   static constexpr uint32_t kLinkCap = 64;
   using TopCmp = LessD;
   using CandCmp = LessD;
   static __device__ __forceinline__ float cand_key(float d) { return -d; }
   template <int METRIC>
-  static __device__ __forceinline__ void dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
+  static __device__ __forceinline__ void dists(const ROW *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
     cv_dists<METRIC>(vec, dim, qv, nid, nd, cnt, lane);
   }
   static __device__ __forceinline__ void pop_order(Pair *arr, const uint32_t *kept, const float *keptd, uint32_t kc, int lane) {
@@ -123,7 +147,7 @@ struct BgHnswlib {
       return topn;
     }
     bg_sort_top<H2Before>(topq, topn, lane);
-    const uint32_t kc = cv_prune<METRIC, BgHnswlib>(g.vec, g.dim, topq, topn, g.M, qc, kept, kd, lane, keptd);
+    const uint32_t kc = cv_prune<METRIC, BgHnswlibRows>(bg_rows<BgHnswlibRows>(g), g.dim, topq, topn, g.M, qc, kept, kd, lane, keptd);
     pop_order(topq, kept, keptd, kc, lane);
     return kc;
   }
@@ -135,6 +159,7 @@ struct BgHnswlib {
     if (act) arr[rank] = mine;
   }
 };
+struct BgHnswlib : BgHnswlibRows<float> {};   // (a name of its own: the fp32 kernels' symbols are what they were)
 
 // rabitqlib (hnsw.hpp; RqGraph, host_rq_graph.hpp), at M up to 32: every distance is rq_dists (rq_dist.hpp); both heaps order
 // (distance, id) pairs (:33-36) -- a total order, so libstdc++'s heap mechanics decide nothing and any correct heap or sort serves.
@@ -145,6 +170,7 @@ __device__ __forceinline__ bool rq_less(const Pair &a, const Pair &b) { return a
 struct RqLess { __device__ __forceinline__ bool operator()(const Pair &a, const Pair &b) const { return rq_less(a, b); } };      // maxheap
 struct RqGreater { __device__ __forceinline__ bool operator()(const Pair &a, const Pair &b) const { return rq_less(b, a); } };   // minheap
 struct BgRabitq {
+  using Row = float;
   static constexpr bool kKeptD = false, kSkipNamed = true;   // (hnsw.hpp:973-980)
   static constexpr uint32_t kLinkCap = 128;
   using TopCmp = RqLess;
@@ -160,7 +186,7 @@ struct BgRabitq {
   template <int METRIC>
   static __device__ __forceinline__ uint32_t select(const BgDev &g, Pair *topq, uint32_t topn, float *qc, uint32_t *kept, float *keptd, float *kd, int lane) {
     bg_sort_top<RqLess>(topq, topn, lane);
-    if (topn >= g.M) return cv_prune<METRIC, BgRabitq>(g.vec, g.dim, topq, topn, g.M, qc, kept, kd, lane);
+    if (topn >= g.M) return cv_prune<METRIC, BgRabitq>(bg_rows<BgRabitq>(g), g.dim, topq, topn, g.M, qc, kept, kd, lane);
     if ((uint32_t)lane < topn) kept[lane] = topq[lane].id;
     return topn;
   }
@@ -224,11 +250,19 @@ static_assert(bg_lds_is<BgHnswlib>(128, 200, 4096, 53504, 3328) && bg_lds_is<BgR
 static_assert(bg_lds_is<BgHnswlib>(768, 128, 4096, 58624, 8448) && bg_lds_is<BgRabitq>(768, 128, 4096, 58368, 9216), "LDS layout");
 static_assert(bg_lds_is<BgHnswlib>(960, 512, 8192, 115456, 9984) && bg_lds_is<BgRabitq>(960, 512, 8192, 115200, 10752), "LDS layout");
 
+// The kernels that read rows -- the search kernel (ONCHIP and its re-run) and the link kernel -- of one flavour, metric and row
+// type, as the host driver launches them; the narrow objects hand theirs out by metric.
+typedef void (*BgSearchFn)(BgDev, uint32_t, uint32_t, uint32_t, int32_t, uint32_t, uint32_t *, uint32_t *, uint32_t *, size_t);
+typedef void (*BgLinkFn)(BgDev, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t *, uint32_t);
+struct BgKernels { BgSearchFn search, rerun; BgLinkFn link; };
+BgKernels bg_kernels_u8(int metric);    // build_gpu_u8.hip
+BgKernels bg_kernels_f16(int metric);   // build_gpu_f16.hip
+
 // ---- phase A ------------------------------------------------------------------------------------------------------------------------
 // ONCHIP: grid = the rows of the batch.  Otherwise: the flagged rows, kBgRerunGrid workgroups, scratch area `blockIdx.x` of gscratch
 // ((n + 31) / 32 bitmap words, then n candidate pairs).  ctr[0]: flagged rows of this batch, ctr[1]: of the build.
 template <class F, int METRIC, bool ONCHIP>
-__global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, uint32_t count, uint32_t ep, int32_t top, uint32_t scratch_ids,
+__global__ void __launch_bounds__(64) HS_BG_KERNEL(bg_search_kernel)(BgDev g, uint32_t begin, uint32_t count, uint32_t ep, int32_t top, uint32_t scratch_ids,
                                                        uint32_t *flagged, uint32_t *ctr, uint32_t *gscratch, size_t gstride) {
   extern __shared__ __align__(16) unsigned char smem[];
   const BgSearchLds<F, unsigned char *> lds(smem, g.dpad, g.topcap, scratch_ids);
@@ -245,6 +279,7 @@ __global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, 
   uint32_t *bitmap = gscratch + (size_t)blockIdx.x * gstride;                   // !ONCHIP
   Pair *cand = ONCHIP ? bg_lds<Pair>(lds.cand) : reinterpret_cast<Pair *>(bitmap + (((size_t)g.n + 31) / 32 + 1) / 2 * 2);
   const uint32_t candcap = ONCHIP ? scratch_ids / 2 : g.n;
+  const typename F::Row *vec = bg_rows<F>(g);
   const int lane = threadIdx.x;
   const uint32_t nrows = ONCHIP ? count : min(ctr[0], count);
   for (uint32_t r = blockIdx.x; r < nrows; r += gridDim.x) {
@@ -252,13 +287,13 @@ __global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, 
     if (p < begin || p >= begin + count) continue;
     const uint32_t lp = g.lev[p];
     wave_sync();
-    for (uint32_t i = lane; i < g.dim; i += 64) qv[i] = g.vec[(size_t)p * g.dim + i];
+    for (uint32_t i = lane; i < g.dim; i += 64) qv[i] = row_widen(vec[(size_t)p * g.dim + i]);
     uint32_t cur = ep;
     wave_sync();
     if ((int32_t)lp < top) {   // the greedy walk of the upper levels (hnswalg.h:1300-1326 / hnsw.hpp:733-760)
       if (lane == 0) nid[0] = cur;
       wave_sync();
-      F::template dists<METRIC>(g.vec, g.dim, qv, nid, nd, 1, lane);
+      F::template dists<METRIC>(vec, g.dim, qv, nid, nd, 1, lane);
       wave_sync();
       float curdist = nd[0];
       for (int32_t level = top; level > (int32_t)lp; level--) {
@@ -270,7 +305,7 @@ __global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, 
           wave_sync();
           if ((uint32_t)lane < cnt) nid[lane] = min(l[1 + lane], begin - 1);
           wave_sync();
-          F::template dists<METRIC>(g.vec, g.dim, qv, nid, nd, cnt, lane);
+          F::template dists<METRIC>(vec, g.dim, qv, nid, nd, cnt, lane);
           wave_sync();
           for (uint32_t i = 0; i < cnt; i++) {   // every lane the same walk over LDS
             const float d = nd[i];
@@ -291,7 +326,7 @@ __global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, 
       if (lane == 0) nid[0] = cur;
       if (!ONCHIP) __syncthreads();   // (one wavefront per workgroup: orders the bitmap's plain stores before its atomics)
       wave_sync();
-      F::template dists<METRIC>(g.vec, g.dim, qv, nid, nd, 1, lane);
+      F::template dists<METRIC>(vec, g.dim, qv, nid, nd, 1, lane);
       wave_sync();
       uint32_t topn = 1, candn = 1, nvis = 1;
       float lower = nd[0];
@@ -336,7 +371,7 @@ __global__ void __launch_bounds__(64) bg_search_kernel(BgDev g, uint32_t begin, 
         nvis += nnew;
         if (ONCHIP && nvis > scratch_ids) { ok = false; break; }
         wave_sync();
-        F::template dists<METRIC>(g.vec, g.dim, qv, nid, nd, nnew, lane);
+        F::template dists<METRIC>(vec, g.dim, qv, nid, nd, nnew, lane);
         wave_sync();
         uint32_t ovf = 0;
         if (lane == 0) {
@@ -402,6 +437,7 @@ __global__ void __launch_bounds__(256) bg_rev_kernel(BgDev g, uint32_t begin, ui
 // active task i -> task: the level-0 lists of the nodes below `begin`, then their upper lists
 __device__ __forceinline__ uint32_t bg_active(uint32_t i, uint32_t begin, uint32_t n) { return i < begin ? i : n + (i - begin); }
 
+#if HS_BG_ROWS == 0   // (the scan reads no row: the fp32 object's alone)
 // exclusive scan over the 256 threads of the workgroup: the sum of the threads before this one; thread 0 hands the sum of all to `total`
 template <class TOTAL>
 __device__ __forceinline__ uint32_t bg_scan256(uint32_t sum, TOTAL total) {
@@ -426,11 +462,12 @@ __global__ void __launch_bounds__(256) bg_scan_kernel(const uint32_t *rcnt, uint
   sum = bg_scan256(sum, [](uint32_t) {});
   for (uint32_t i = lo; i < hi; i++) { const uint32_t a = bg_active(i, begin, n); roff[a] = sum; sum += rcnt[a]; }
 }
+#endif
 
 // ---- phase B: the reverse links ------------------------------------------------------------------------------------------------------
 // up_node / up_level: node and level of upper slot j (task n + j)
 template <class F, int METRIC>
-__global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, uint32_t nact, const uint32_t *up_node, const uint32_t *up_level,
+__global__ void __launch_bounds__(64) HS_BG_KERNEL(bg_link_kernel)(BgDev g, uint32_t begin, uint32_t nact, const uint32_t *up_node, const uint32_t *up_level,
                                                      uint32_t *rcnt, const uint32_t *roff, uint32_t *rcur, uint32_t *rev, uint32_t rev_cap) {
   extern __shared__ __align__(16) unsigned char smem[];
   const BgLinkLds<F, unsigned char *> lds(smem, g.dpad);
@@ -444,6 +481,7 @@ __global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, ui
   float *kd = bg_lds<float>(lds.kd);
   uint32_t *curl = bg_lds<uint32_t>(lds.curl);
   uint32_t *inc = bg_lds<uint32_t>(lds.inc);
+  const typename F::Row *vec = bg_rows<F>(g);
   const int lane = threadIdx.x;
   for (uint32_t i = blockIdx.x; i < nact; i += gridDim.x) {
     const uint32_t task = bg_active(i, begin, g.n);
@@ -496,18 +534,18 @@ __global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, ui
         continue;
       }
       if (!have_row) {
-        for (uint32_t c = lane; c < g.dim; c += 64) qv[c] = g.vec[(size_t)u * g.dim + c];
+        for (uint32_t c = lane; c < g.dim; c += 64) qv[c] = row_widen(vec[(size_t)u * g.dim + c]);
         have_row = true;
       }
       const uint32_t sz = cnt + 1;   // < kLinkCap: {p} + the full list
       if (lane == 0) nid[0] = p;
       if ((uint32_t)lane < cnt) nid[1 + lane] = curl[lane];
       wave_sync();
-      F::template dists<METRIC>(g.vec, g.dim, qv, nid, nd, sz, lane);
+      F::template dists<METRIC>(vec, g.dim, qv, nid, nd, sz, lane);
       wave_sync();
       F::rank_sort(nid, nd, sz, arr, lane);
       wave_sync();
-      const uint32_t kc = cv_prune<METRIC, F>(g.vec, g.dim, arr, sz, lim, qc, kept, kd, lane, keptd);
+      const uint32_t kc = cv_prune<METRIC, F>(vec, g.dim, arr, sz, lim, qc, kept, kd, lane, keptd);
       F::pop_order(arr, kept, keptd, kc, lane);
       wave_sync();
       if ((uint32_t)lane < kc) curl[lane] = F::selected(arr, kept, kc - 1 - lane);   // pop order; what it does not overwrite stays
@@ -518,6 +556,17 @@ __global__ void __launch_bounds__(64) bg_link_kernel(BgDev g, uint32_t begin, ui
     if (lane == 0) { lst[0] = cnt; rcnt[task] = 0; rcur[task] = 0; }
   }
 }
+
+template <class F, int METRIC>
+static BgKernels bg_kernels() {
+  return BgKernels{HS_BG_KERNEL(bg_search_kernel)<F, METRIC, true>, HS_BG_KERNEL(bg_search_kernel)<F, METRIC, false>, HS_BG_KERNEL(bg_link_kernel)<F, METRIC>};
+}
+#if HS_BG_ROWS != 0
+// a narrow object ends here: its kernels, by metric
+BgKernels HS_BG_KERNEL(bg_kernels)(int metric) {
+  return metric == METRIC_L2 ? bg_kernels<BgHnswlibRows<BgTuRow>, METRIC_L2>() : bg_kernels<BgHnswlibRows<BgTuRow>, METRIC_IP>();
+}
+#else
 
 // hs_debug_rq_raw_dist: pair i is a[i] against b[i]; the row is measured five times in one call of rq_dists, so that pairs land in
 // every sixteen-lane group and in the second pass.
@@ -709,20 +758,21 @@ static hipError_t bg_allow_lds(K kernel, size_t bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <class F, int METRIC>
-static hipError_t bg_run_as(const BgWork &w, const std::vector<BatchStep> &steps, hipStream_t st, const BgMarks *marks) {
+// F: the flavour whose LDS layouts the kernels of `k` use (a narrow row type keeps BgHnswlib's: the rows in LDS are fp32)
+template <class F>
+static hipError_t bg_run_as(const BgWork &w, const std::vector<BatchStep> &steps, hipStream_t st, const BgMarks *marks, const BgKernels &k) {
   const BgDev &g = w.g;
   const size_t lds_a = bg_search_lds<F>(g.dpad, g.efc, w.scratch_ids), lds_r = bg_search_lds<F>(g.dpad, g.efc, 0), lds_l = bg_link_lds<F>(g.dpad);
-  BG_TRY(bg_allow_lds(bg_search_kernel<F, METRIC, true>, lds_a));
-  BG_TRY(bg_allow_lds(bg_search_kernel<F, METRIC, false>, lds_r));
-  BG_TRY(bg_allow_lds(bg_link_kernel<F, METRIC>, lds_l));
+  BG_TRY(bg_allow_lds(k.search, lds_a));
+  BG_TRY(bg_allow_lds(k.rerun, lds_r));
+  BG_TRY(bg_allow_lds(k.link, lds_l));
   for (const BatchStep &s : steps) {
     if ((int32_t)s.ep == -1) continue;   // the first row: an empty list, as the zeroed arrays have it
     const uint32_t nact = s.begin + w.h_upb[s.begin];
     BG_TRY(hipMemsetAsync(w.ctr.p, 0, 4, st));
-    hipLaunchKernelGGL((bg_search_kernel<F, METRIC, true>), dim3(s.size), dim3(64), lds_a, st, g, s.begin, s.size, s.ep, s.top, w.scratch_ids,
+    hipLaunchKernelGGL(k.search, dim3(s.size), dim3(64), lds_a, st, g, s.begin, s.size, s.ep, s.top, w.scratch_ids,
                        w.flagged.p, w.ctr.p, (uint32_t *)nullptr, (size_t)0);
-    hipLaunchKernelGGL((bg_search_kernel<F, METRIC, false>), dim3(std::min(kBgRerunGrid, s.size)), dim3(64), lds_r, st, g, s.begin, s.size, s.ep,
+    hipLaunchKernelGGL(k.rerun, dim3(std::min(kBgRerunGrid, s.size)), dim3(64), lds_r, st, g, s.begin, s.size, s.ep,
                        s.top, 0u, w.flagged.p, w.ctr.p, w.scratch.p, w.gstride);
     hipLaunchKernelGGL((bg_rev_kernel<false>), dim3((s.size + 3) / 4), dim3(256), 0, st, g, s.begin, s.size, s.top, w.rcnt.p, w.roff.p, w.rcur.p,
                        w.rev.p, w.rev_cap);
@@ -731,24 +781,32 @@ static hipError_t bg_run_as(const BgWork &w, const std::vector<BatchStep> &steps
                        w.rev.p, w.rev_cap);
     if (marks)   // (before the link kernel, which resets the counts)
       hipLaunchKernelGGL(bga_mark_kernel, dim3(std::min((nact + 255u) / 256u, 4096u)), dim3(256), 0, st, w.rcnt.p, s.begin, g.n, nact, *marks);
-    hipLaunchKernelGGL((bg_link_kernel<F, METRIC>), dim3(std::min(nact, 8192u)), dim3(64), lds_l, st, g, s.begin, nact, w.upnode.p, w.uplevel.p,
+    hipLaunchKernelGGL(k.link, dim3(std::min(nact, 8192u)), dim3(64), lds_l, st, g, s.begin, nact, w.upnode.p, w.uplevel.p,
                        w.rcnt.p, w.roff.p, w.rcur.p, w.rev.p, w.rev_cap);
     BG_TRY(hipGetLastError());
   }
   return hipSuccess;
 }
-// the batches of `steps` on stream `st`: the one place that turns metric and flavour into an instantiation
-static hipError_t bg_run(const BgWork &w, const std::vector<BatchStep> &steps, int metric, bool rq, hipStream_t st, const BgMarks *marks = nullptr) {
-  if (rq) return metric == METRIC_L2 ? bg_run_as<BgRabitq, METRIC_L2>(w, steps, st, marks) : bg_run_as<BgRabitq, METRIC_IP>(w, steps, st, marks);
-  return metric == METRIC_L2 ? bg_run_as<BgHnswlib, METRIC_L2>(w, steps, st, marks) : bg_run_as<BgHnswlib, METRIC_IP>(w, steps, st, marks);
+// the batches of `steps` on stream `st`: the one place that turns metric, flavour and row type (ROWS_*: what w.g.vec holds; the
+// narrow types for hnswlib's flavour only) into an instantiation
+static hipError_t bg_run(const BgWork &w, const std::vector<BatchStep> &steps, int metric, bool rq, int rows, hipStream_t st,
+                         const BgMarks *marks = nullptr) {
+  const bool l2 = metric == METRIC_L2;
+  if (rq)
+    return l2 ? bg_run_as<BgRabitq>(w, steps, st, marks, bg_kernels<BgRabitq, METRIC_L2>())
+              : bg_run_as<BgRabitq>(w, steps, st, marks, bg_kernels<BgRabitq, METRIC_IP>());
+  const BgKernels k = rows == ROWS_U8 ? bg_kernels_u8(metric) : rows == ROWS_F16 ? bg_kernels_f16(metric)
+                      : l2 ? bg_kernels<BgHnswlib, METRIC_L2>() : bg_kernels<BgHnswlib, METRIC_IP>();
+  return bg_run_as<BgHnswlib>(w, steps, st, marks, k);
 }
 
 hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint32_t> &lists0, std::vector<uint32_t> &lists_up,
                            std::vector<uint32_t> &upb, uint64_t &flagged_rows, double *kernel_ms) {
   const uint32_t n = in.n, scratch_ids = in.scratch_ids ? in.scratch_ids : kBgScratchIds;
   flagged_rows = 0;
+  const size_t esize = in.rows == ROWS_F32 ? sizeof(float) : narrow_width(in.rows);   // bytes of one element of in.base
   if (!(in.rq ? gpu_rq_build_supported(in.dim, in.M, in.efc, scratch_ids) : gpu_build_supported(in.dim, in.M, in.efc, scratch_ids)) || n == 0 ||
-      n > 0x7FFFFFF0u)
+      n > 0x7FFFFFF0u || esize == 0 || (in.rq && in.rows != ROWS_F32))
     return hipErrorInvalidValue;
   upb.assign((size_t)n + 1, 0);
   std::vector<uint32_t> lev(n);
@@ -756,16 +814,16 @@ hipError_t gpu_batch_build(const GpuBuildInput &in, int device, std::vector<uint
   BgDev shape{};
   shape.n = n; shape.dim = in.dim; shape.M = in.M; shape.maxM = in.maxM; shape.maxM0 = in.maxM0; shape.efc = in.efc;
   BgWork w;
-  BgBuf<float> d_vec;
+  BgBuf<uint8_t> d_vec;   // the rows as they lie at in.base: n x dim x 4, 2 or 1 bytes
   uint32_t ctr[2] = {0, 0};
   BG_TRY(hipSetDevice(device));
   BG_TRY(bg_work_init(w, shape, scratch_ids, lev.data(), upb, *in.steps, nullptr, nullptr));
-  BG_TRY(d_vec.alloc((size_t)n * in.dim));
-  BG_TRY(d_vec.upload(in.base, (size_t)n * in.dim));
+  BG_TRY(d_vec.alloc((size_t)n * in.dim * esize));
+  BG_TRY(d_vec.upload(static_cast<const uint8_t *>(in.base), (size_t)n * in.dim * esize));
   BG_TRY(hipDeviceSynchronize());
   w.g.vec = d_vec.p;
   BG_TRY(hipEventRecord(w.e0, nullptr));
-  BG_TRY(bg_run(w, *in.steps, in.metric, in.rq, nullptr));
+  BG_TRY(bg_run(w, *in.steps, in.metric, in.rq, in.rows, nullptr));
   BG_TRY(hipEventRecord(w.e1, nullptr));
   BG_TRY(hipEventSynchronize(w.e1));
   if (kernel_ms) { float ms = 0.f; BG_TRY(hipEventElapsedTime(&ms, w.e0, w.e1)); *kernel_ms = ms; }
@@ -834,7 +892,7 @@ hipError_t gpu_batch_add(const GpuAddInput &in, int device, GpuAddOutput &out) {
   w.g.vec = in.d_vec;
   const BgMarks marks{d_mark.p, n0, nup0};
   BG_TRY(hipEventRecord(w.e0, nullptr));
-  BG_TRY(bg_run(w, *in.steps, in.metric, false, nullptr, &marks));
+  BG_TRY(bg_run(w, *in.steps, in.metric, false, ROWS_F32, nullptr, &marks));
   hipLaunchKernelGGL(bga_count_kernel, dim3((nw + 3) / 4), dim3(256), 0, nullptr, d_mark.p, nold, d_counts.p);
   hipLaunchKernelGGL(bga_scan_kernel, dim3(1), dim3(256), 0, nullptr, d_counts.p, nw, w.ctr.p + 2);
   hipLaunchKernelGGL(bga_scatter_kernel, dim3((nw + 3) / 4), dim3(256), 0, nullptr, d_mark.p, nold, n0, n, d_counts.p, d_ids.p);
@@ -857,5 +915,6 @@ hipError_t gpu_batch_add(const GpuAddInput &in, int device, GpuAddOutput &out) {
   out.slots.swap(buf);
   return hipSuccess;
 }
+#endif   // HS_BG_ROWS == 0
 
 }  // namespace hs

@@ -42,15 +42,27 @@ hs_status batch_opts_ok(const hs_batch_build_opts *opts) {
   return HS_OK;
 }
 
-// The device build's lists into the image VanillaGraph::save writes: rows and labels as begin_insert lays them out, the level-0 lists
-// in front of them, the upper lists per node, entry point and top level as the schedule ends.
-static void image_from_lists(VanillaGraph &g, const float *base, const uint64_t *labels, const std::vector<int> &lv, const std::vector<BatchStep> &steps,
+// Rows of format `fmt` (ROWS_*: fp32, or u8 / fp16 in natural order) as fp32: both widenings are exact.  dst: 4-byte aligned.
+template <class T>
+static void widen_to(const void *src, size_t first, size_t count, float *dst) {
+  const T *s = static_cast<const T *>(src) + first;
+  for (size_t i = 0; i < count; i++) dst[i] = (float)s[i];
+}
+static void rows_as_f32(const void *src, int fmt, size_t first, size_t count, float *dst) {
+  if (fmt == ROWS_U8) widen_to<uint8_t>(src, first, count, dst);
+  else if (fmt == ROWS_F16) widen_to<_Float16>(src, first, count, dst);
+  else memcpy(dst, static_cast<const float *>(src) + first, 4 * count);
+}
+
+// The device build's lists into the image VanillaGraph::save writes: rows (fp32, whatever format they were built from) and labels as
+// begin_insert lays them out, the level-0 lists in front of them, the upper lists per node, entry point and top level as the schedule ends.
+static void image_from_lists(VanillaGraph &g, const void *base, int fmt, const uint64_t *labels, const std::vector<int> &lv, const std::vector<BatchStep> &steps,
                              const std::vector<uint32_t> &l0, const std::vector<uint32_t> &lu, const std::vector<uint32_t> &upb, int threads) {
   const size_t n = g.max_elements, s0 = g.maxM0 + 1, su = g.maxM + 1;
   parallel_for(n, threads, 1024, [&](size_t i, int) {
     char *e = g.el((uint32_t)i);
     memcpy(e, l0.data() + i * s0, g.size_links0);
-    memcpy(e + g.offsetData, base + i * g.dim, 4 * g.dim);
+    rows_as_f32(base, fmt, i * g.dim, g.dim, reinterpret_cast<float *>(e + g.offsetData));   // (every offset of an element is a multiple of 4)
     const uint64_t lab = labels ? labels[i] : i;
     memcpy(e + g.label_offset, &lab, 8);
     g.levels[i] = lv[i];
@@ -68,26 +80,28 @@ static void image_from_lists(VanillaGraph &g, const float *base, const uint64_t 
 // The batched build on a device, for both graph flavours (rq: rabitqlib's builder, whose labels are the row index -- labels null):
 // levels and schedule as the host twin draws them, the kernels of build_gpu.hip, the lists laid into the image of `g`, which the
 // caller has initialised for n rows (g.init / rq_init) after its own support test.
-static hs_status batched_build_on_device(VanillaGraph &g, bool rq, const float *base, const uint64_t *labels, size_t n, size_t seed,
+static hs_status batched_build_on_device(VanillaGraph &g, bool rq, const void *base, int fmt, const uint64_t *labels, size_t n, size_t seed,
                                          const hs_batch_build_opts *opts, hs_batch_build_stats &st) {
   const std::vector<int> lv = draw_levels(n, g.mult, seed);
   const std::vector<BatchStep> steps = batch_schedule(lv.data(), n, opts->grow_div, opts->batch_max);
   GpuBuildInput in;
-  in.base = base; in.n = (uint32_t)n; in.dim = (uint32_t)g.dim; in.metric = (int)g.metric;
+  in.base = base; in.rows = fmt; in.n = (uint32_t)n; in.dim = (uint32_t)g.dim; in.metric = (int)g.metric;
   in.M = (uint32_t)g.M; in.maxM = (uint32_t)g.maxM; in.maxM0 = (uint32_t)g.maxM0; in.efc = (uint32_t)g.efC;
   in.levels = lv.data(); in.steps = &steps; in.scratch_ids = (uint32_t)opts->scratch_ids; in.rq = rq;
   std::vector<uint32_t> l0, lu, upb;
   uint64_t flagged = 0;
   const hipError_t e = gpu_batch_build(in, opts->device, l0, lu, upb, flagged, &st.kernel_ms);
   if (e != hipSuccess) return fail(HS_ERR_DEVICE, std::string("batched build: ") + hipGetErrorString(e));
-  image_from_lists(g, base, labels, lv, steps, l0, lu, upb, std::max(1, (int)opts->threads));
+  image_from_lists(g, base, fmt, labels, lv, steps, l0, lu, upb, std::max(1, (int)opts->threads));
   st.used_gpu = 1; st.batches = steps.size(); st.flagged_rows = flagged;
   return HS_OK;
 }
 
-hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
-                                const char *branching_factor, size_t seed, const hs_batch_build_opts *opts, const char *out_path,
-                                hs_batch_build_stats *stats) {
+// hs_build_hnsw_batched and hs_build_hnsw_batched_rows: the refusals of their arguments, then the build from rows of format `fmt`
+// (throws what the builders throw: the two entries guard).  The device reads the rows as they lie at `base`; the host twin reads
+// fp32 rows, the caller's or their widening.
+static hs_status batched_args_ok(const void *base, size_t n, size_t dim, int metric, size_t M, const char *branching_factor,
+                                 const hs_batch_build_opts *opts, const char *out_path) {
   if (!base || !out_path || !branching_factor || n == 0) return fail(HS_ERR_INVALID, "bad argument");
   if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0) return fail(HS_ERR_INVALID, "dim must be > 0");
@@ -95,28 +109,67 @@ hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels, size_
   if (n > 0x7FFFFFF0u) return fail(HS_ERR_INVALID, "too many rows");
   if (batch_opts_ok(opts) != HS_OK) return HS_ERR_INVALID;
   if (opts->device >= 0 && device_ok(opts->device, false) != HS_OK) return HS_ERR_DEVICE;
+  return HS_OK;
+}
+static hs_status batched_build_file(const void *base, int fmt, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M,
+                                    size_t ef_construction, const char *branching_factor, size_t seed, const hs_batch_build_opts *opts,
+                                    const char *out_path, hs_batch_build_stats *stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  hs_batch_build_stats st{};
+  VanillaGraph g;
+  bool on_device = false;
+  if (opts->device >= 0) {
+    g.init(n, dim, (Metric)metric, M, ef_construction, branching_factor);
+    on_device = gpu_build_supported((uint32_t)dim, (uint32_t)g.M, (uint32_t)g.efC, (uint32_t)opts->scratch_ids);
+  }
+  if (on_device) {
+    const hs_status s = batched_build_on_device(g, false, base, fmt, labels, n, seed, opts, st);
+    if (s != HS_OK) return s;
+  } else {
+    std::vector<float> wide;
+    if (fmt != ROWS_F32) {
+      wide.resize(n * dim);
+      rows_as_f32(base, fmt, 0, n * dim, wide.data());
+    }
+    const float *rows = fmt != ROWS_F32 ? wide.data() : static_cast<const float *>(base);
+    BatchBuildStats bs;
+    batch_build_host(g, rows, n, dim, (Metric)metric, M, ef_construction, branching_factor, seed, std::max(1, (int)opts->threads), labels, opts->grow_div,
+                     opts->batch_max, &bs);
+    st.batches = bs.batches;
+  }
+  g.save(out_path);
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return HS_OK;
+}
+hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M, size_t ef_construction,
+                                const char *branching_factor, size_t seed, const hs_batch_build_opts *opts, const char *out_path,
+                                hs_batch_build_stats *stats) {
+  const hs_status ok = batched_args_ok(base, n, dim, metric, M, branching_factor, opts, out_path);
+  if (ok != HS_OK) return ok;
   return guarded([&] {
-    const auto t0 = std::chrono::steady_clock::now();
-    hs_batch_build_stats st{};
-    VanillaGraph g;
-    bool on_device = false;
-    if (opts->device >= 0) {
-      g.init(n, dim, (Metric)metric, M, ef_construction, branching_factor);
-      on_device = gpu_build_supported((uint32_t)dim, (uint32_t)g.M, (uint32_t)g.efC, (uint32_t)opts->scratch_ids);
+    return batched_build_file(base, ROWS_F32, labels, n, dim, metric, M, ef_construction, branching_factor, seed, opts, out_path, stats);
+  });
+}
+// The same build from u8 / fp16 rows in natural order: on a device the narrow instantiations of the two row-reading
+// kernels; the file is hs_build_hnsw_batched's for the widened rows, byte for byte.
+hs_status hs_build_hnsw_batched_rows(const void *base, int row_format, const uint64_t *labels, size_t n, size_t dim, int metric, size_t M,
+                                     size_t ef_construction, const char *branching_factor, size_t seed, const hs_batch_build_opts *opts,
+                                     const char *out_path, hs_batch_build_stats *stats) {
+  if (row_format != ROWS_F16 && row_format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
+  const hs_status ok = batched_args_ok(base, n, dim, metric, M, branching_factor, opts, out_path);
+  if (ok != HS_OK) return ok;
+  return guarded([&] {
+    if (row_format == ROWS_F16) {   // NaN and +-inf (exponent all ones) are outside the format's contract, as for an index's narrow copy
+      const uint16_t *w = static_cast<const uint16_t *>(base);
+      for (size_t i = 0; i < n * dim; i++)
+        if ((w[i] & 0x7C00u) == 0x7C00u) {
+          float v;
+          rows_as_f32(base, ROWS_F16, i, 1, &v);
+          return fail(HS_ERR_UNSUPPORTED, unfit_message(i / dim, i % dim, v, ROWS_F16));
+        }
     }
-    if (on_device) {
-      const hs_status s = batched_build_on_device(g, false, base, labels, n, seed, opts, st);
-      if (s != HS_OK) return s;
-    } else {
-      BatchBuildStats bs;
-      batch_build_host(g, base, n, dim, (Metric)metric, M, ef_construction, branching_factor, seed, std::max(1, (int)opts->threads), labels, opts->grow_div,
-                       opts->batch_max, &bs);
-      st.batches = bs.batches;
-    }
-    g.save(out_path);
-    st.total_ms = ms_since(t0);
-    if (stats) *stats = st;
-    return HS_OK;
+    return batched_build_file(base, row_format, labels, n, dim, metric, M, ef_construction, branching_factor, seed, opts, out_path, stats);
   });
 }
 
@@ -294,7 +347,7 @@ hs_status rq_batched_build_into(RqGraph &g, const float *base, size_t n, size_t 
   if (opts->device >= 0 && gpu_rq_build_supported((uint32_t)dim, (uint32_t)std::min<size_t>(M, 10000), (uint32_t)std::min<size_t>(std::max(ef_construction, M), 0xFFFFFFFFu),
                                                   (uint32_t)opts->scratch_ids)) {
     rq_init(g, base, n, dim, (Metric)metric, M, ef_construction);
-    return batched_build_on_device(g, true, base, nullptr, n, seed, opts, st);
+    return batched_build_on_device(g, true, base, ROWS_F32, nullptr, n, seed, opts, st);
   }
   BatchBuildStats bs;
   rq_batch_build_host(g, base, n, dim, (Metric)metric, M, ef_construction, seed, std::max(1, (int)opts->threads), opts->grow_div, opts->batch_max, &bs);

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "build_rows.hpp"
 #include "dist_recipe.hpp"
 #include "heap_emul.hpp"
 #include "wave_util.hpp"
@@ -22,9 +23,10 @@ static constexpr uint32_t kCvUnionCap = 2048;  // own list + reverse edges of on
 // the pruned (nn) and final (fin) lists of one call and the entries of the kernels' kept / keptd / kd arrays in LDS, 32 or kCvMaxKeep.
 // A wavefront handles a kept or final list with one lane per entry, which holds because keep <= 64.
 
-// distances query (LDS, dim floats) -> rows nid[0..cnt) (LDS) into nd[0..cnt) (LDS)
-template <int METRIC>
-__device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
+// distances query (LDS, dim floats) -> rows nid[0..cnt) (LDS) into nd[0..cnt) (LDS).  ROW: the element type of the row array (fp32
+// everywhere but the batched build over u8 / fp16 rows; build_rows.hpp: what a lane loads, and its exact widening)
+template <int METRIC, class ROW>
+__device__ __forceinline__ void cv_dists(const ROW *vec, uint32_t dim, const float *qv, const uint32_t *nid, float *nd, uint32_t cnt, int lane) {
   if ((dim & 15u) == 0) {
     const int sub = lane & 3, grp = lane >> 2;
     const uint32_t steps = dim >> 4;
@@ -33,17 +35,17 @@ __device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const f
       const uint32_t j = base + grp;
       const bool act = j < cnt;
       const uint32_t id = nid[act ? j : base];
-      const float4 *row = reinterpret_cast<const float4 *>(vec + (size_t)id * dim) + sub;
+      const ROW *row = vec + (size_t)id * dim + 4 * sub;
       float acc[4] = {0.f, 0.f, 0.f, 0.f};
       for (uint32_t r0 = 0; r0 < steps; r0 += 8) {
         const uint32_t nb = min(8u, steps - r0);
-        float4 buf[8];
+        RowQuad<ROW> buf[8];
 #pragma unroll
         for (uint32_t i = 0; i < 8; i++)
-          if (i < nb) buf[i] = row[(r0 + i) * 4];
+          if (i < nb) buf[i].load(row + (r0 + i) * 16);
 #pragma unroll
         for (uint32_t i = 0; i < 8; i++)
-          if (i < nb) step4<METRIC>(acc, qq[(r0 + i) * 4], buf[i]);
+          if (i < nb) step4<METRIC>(acc, qq[(r0 + i) * 4], buf[i].widen());
       }
       bool owner;
       const float r = lane4_reduce<METRIC>(acc, sub, owner);
@@ -53,7 +55,7 @@ __device__ __forceinline__ void cv_dists(const float *vec, uint32_t dim, const f
     for (uint32_t base = 0; base < cnt; base += 64) {
       const uint32_t j = base + lane;
       if (j < cnt) {
-        const float *row = vec + (size_t)nid[j] * dim;
+        const auto row = row_read(vec + (size_t)nid[j] * dim);
         nd[j] = METRIC == METRIC_L2 ? l2_general(qv, row, dim) : ip_general(qv, row, dim);
       }
     }
@@ -99,8 +101,8 @@ __device__ __forceinline__ void cv_sort_by_dist(const uint32_t *nid, const float
 // neighbour is closer to it than the node itself.  Sequential in the candidates, parallel over the kept set.  This is also the
 // keep loop of getNeighborsByHeuristic2 (hnswalg.h:495-517) once arr[] is in ITS candidate order (diff_prune.hpp), and of
 // rabitqlib's get_neighbors_by_heuristic2 (hnsw.hpp:1016-1054) with DIST its distance (build_gpu.hip).
-template <int METRIC, class DIST = CvDists>
-__device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
+template <int METRIC, class DIST = CvDists, class ROW = float>
+__device__ __forceinline__ uint32_t cv_prune(const ROW *vec, uint32_t dim, const Pair *arr, uint32_t sz, uint32_t mlim, float *qc /*LDS dim*/,
                                              uint32_t *kept, float *kd, int lane, float *keptd = nullptr) {
   uint32_t kc = 0;   // (kept / kd / keptd hold `keep` entries: the caller passes mlim <= keep)
   for (uint32_t t = 0; t < sz && kc < mlim; t++) {
@@ -108,7 +110,7 @@ __device__ __forceinline__ uint32_t cv_prune(const float *vec, uint32_t dim, con
     const uint32_t cid = uni(arr[t].id);
     bool good = true;
     if (kc > 0) {
-      for (uint32_t i = lane; i < dim; i += 64) qc[i] = vec[(size_t)cid * dim + i];
+      for (uint32_t i = lane; i < dim; i += 64) qc[i] = row_widen(vec[(size_t)cid * dim + i]);
       wave_sync();
       DIST::template dists<METRIC>(vec, dim, qc, kept, kd, kc, lane);
       wave_sync();

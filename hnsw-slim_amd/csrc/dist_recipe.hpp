@@ -61,7 +61,10 @@ inline float ip_row16(const float *q, const float *x, size_t d) {
 // (:166-190: 4 lane accumulators, TmpRes[0..3] summed left to right); dim>16 -> SIMD16 on the first dim/16*16
 // elements + scalar L2Sqr on the rest (:149-160); dim>4 -> SIMD4 + scalar rest (:192-205); else scalar (:6-20).
 // One thread does a whole row: usable per lane on the device (runtime-dim kernels) and by the host builder.
-HS_HD float l2_part16(const float *q, const float *x, uint32_t d16) {
+// X, the row: anything that reads element i as a float by x[i] and moves on by x + k -- a const float *, or a widening read of a
+// narrower row (build_rows.hpp); the arithmetic is the same text on the widened values.
+template <class X>
+HS_HD float l2_part16(const float *q, X x, uint32_t d16) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // Device (rare, runtime-dim path): one lane accumulator at a time -- the same additions in the same order (acc_j over
   // the steps, then acc_0 + acc_1 + ... left to right) with two live registers instead of sixteen, so that this
@@ -92,7 +95,8 @@ HS_HD float l2_part16(const float *q, const float *x, uint32_t d16) {
   return r;
 #endif
 }
-HS_HD float l2_part4(const float *q, const float *x, uint32_t d4) {
+template <class X>
+HS_HD float l2_part4(const float *q, X x, uint32_t d4) {
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   for (uint32_t s = 0; s < d4; s += 4) {
 #pragma unroll
@@ -104,7 +108,8 @@ HS_HD float l2_part4(const float *q, const float *x, uint32_t d4) {
   }
   return ((acc[0] + acc[1]) + acc[2]) + acc[3];
 }
-HS_HD float l2_scalar(const float *q, const float *x, uint32_t d) {
+template <class X>
+HS_HD float l2_scalar(const float *q, X x, uint32_t d) {
   float r = 0.f;
   for (uint32_t i = 0; i < d; i++) {
     const float t = q[i] - x[i];
@@ -113,7 +118,8 @@ HS_HD float l2_scalar(const float *q, const float *x, uint32_t d) {
   }
   return r;
 }
-HS_HD float l2_general(const float *q, const float *x, uint32_t d) {
+template <class X>
+HS_HD float l2_general(const float *q, X x, uint32_t d) {
   if ((d & 15u) == 0) return l2_part16(q, x, d);
   if ((d & 3u) == 0) return l2_part4(q, x, d);
   if (d > 16) {
@@ -136,7 +142,8 @@ HS_HD float l2_general(const float *q, const float *x, uint32_t d) {
 // right); dim>16 -> SIMD16 on the first dim/16*16 elements + scalar InnerProduct on the rest, 1-(res+tail) (:311-322);
 // dim>4 -> SIMD4 + scalar rest (:324-337); else scalar (:6-19).  One accumulator chain at a time (the chains are
 // independent, so the values are those of the vector code) -- small register footprint on the device.
-HS_HD float ip_quad16(const float *q, const float *x, uint32_t d16, uint32_t j) {  // (a_j+a_{j+8}) + (a_{j+4}+a_{j+12})
+template <class X>
+HS_HD float ip_quad16(const float *q, X x, uint32_t d16, uint32_t j) {  // (a_j+a_{j+8}) + (a_{j+4}+a_{j+12})
   float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;  // lane accumulators j, j+4, j+8, j+12 of the SIMD16 loop (FMA)
 #pragma unroll 1
   for (uint32_t s = 0; s < d16; s += 16) {
@@ -149,7 +156,8 @@ HS_HD float ip_quad16(const float *q, const float *x, uint32_t d16, uint32_t j) 
   const float hi = v1 + v3;
   return lo + hi;
 }
-HS_HD float ip_part16(const float *q, const float *x, uint32_t d16) {  // _mm512_reduce_add_ps order
+template <class X>
+HS_HD float ip_part16(const float *q, X x, uint32_t d16) {  // _mm512_reduce_add_ps order
   float e = 0.f, o = 0.f;
 #pragma unroll 1
   for (uint32_t j = 0; j < 2; j++) {
@@ -160,7 +168,8 @@ HS_HD float ip_part16(const float *q, const float *x, uint32_t d16) {  // _mm512
   }
   return e + o;
 }
-HS_HD float ip_part4(const float *q, const float *x, uint32_t d4) {  // InnerProductSIMD4ExtAVX, d4 % 4 == 0
+template <class X>
+HS_HD float ip_part4(const float *q, X x, uint32_t d4) {  // InnerProductSIMD4ExtAVX, d4 % 4 == 0
   const uint32_t d16 = d4 & ~15u;
   float sum = 0.f;
 #pragma unroll 1
@@ -187,7 +196,8 @@ HS_HD float ip_part4(const float *q, const float *x, uint32_t d4) {  // InnerPro
   }
   return sum;
 }
-HS_HD float ip_scalar(const float *q, const float *x, uint32_t d) {
+template <class X>
+HS_HD float ip_scalar(const float *q, X x, uint32_t d) {
   float r = 0.f;
   for (uint32_t i = 0; i < d; i++) {
     const float p = q[i] * x[i];
@@ -195,7 +205,8 @@ HS_HD float ip_scalar(const float *q, const float *x, uint32_t d) {
   }
   return r;
 }
-HS_HD float ip_general(const float *q, const float *x, uint32_t d) {  // the distance: 1 - <q,x>
+template <class X>
+HS_HD float ip_general(const float *q, X x, uint32_t d) {  // the distance: 1 - <q,x>
   if ((d & 15u) == 0) return 1.0f - ip_part16(q, x, d);
   if ((d & 3u) == 0) return 1.0f - ip_part4(q, x, d);
   if (d > 16) {

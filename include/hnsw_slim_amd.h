@@ -646,6 +646,17 @@ typedef struct hs_batch_build_stats {
 hs_status hs_build_hnsw_batched(const float *base, const uint64_t *labels /* nullable: the row index */, size_t n, size_t dim, int metric,
                                 size_t M, size_t ef_construction, const char *branching_factor, size_t seed,
                                 const hs_batch_build_opts *opts, const char *out_path, hs_batch_build_stats *stats /* nullable */);
+/* The same build from rows held as u8 or fp16.  base: n x dim values in natural (row-major) order, uint8_t for
+ * HS_ROWS_U8, IEEE binary16 words for HS_ROWS_F16 -- the caller's array as it lies, not the lane-major layout of hs_rows_to_narrow.
+ * The file is the one hs_build_hnsw_batched writes for (float)base, byte for byte, rows stored as fp32; options, schedule, stats and
+ * used_gpu as there.  On a device the rows are uploaded and read at their own width (a quarter / half of the fp32 bytes) by narrow
+ * instantiations of the build's kernels, at every dim the fp32 build serves; device == -1 or a shape outside the device path widens on
+ * the host and runs the host twin.  HS_ERR_INVALID: row_format HS_ROWS_F32 (hs_build_hnsw_batched is that entry) or unknown.
+ * HS_ERR_UNSUPPORTED, nothing built: an fp16 row that holds NaN or +-inf (the message names the row). */
+hs_status hs_build_hnsw_batched_rows(const void *base, int row_format /* HS_ROWS_U8 | HS_ROWS_F16 */, const uint64_t *labels /* nullable */,
+                                     size_t n, size_t dim, int metric, size_t M, size_t ef_construction, const char *branching_factor,
+                                     size_t seed, const hs_batch_build_opts *opts, const char *out_path,
+                                     hs_batch_build_stats *stats /* nullable */);
 /* Host only.  The schedule hs_build_hnsw_batched follows for these parameters: *n_batches batches, and for batch b < cap its size
  * (sizes[b]) and the entry point (0xFFFFFFFF: none yet) and top level (-1) before it (entry_points[b], top_levels[b]); the three
  * arrays are nullable and hold `cap` entries. */
