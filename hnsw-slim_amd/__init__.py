@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("HS_LIB", os.path.join(_HERE, "libhnsw_slim_amd.so")) 
 HS_KIND_HNSW, HS_KIND_SLIM, HS_KIND_SLIMQ = 0, 1, 2
 HS_METRIC_L2, HS_METRIC_IP = 0, 1
 HS_MODE_SLIM_IDS, HS_MODE_PQ = 0, 1
-HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8 = 0, 1, 2   # hs_row_format (narrow rows: Index.set_row_format)
+HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8, HS_ROWS_I8 = 0, 1, 2, 3   # hs_row_format (narrow rows: Index.set_row_format)
 HS_OK, HS_ERR_IO, HS_ERR_CORRUPT, HS_ERR_NOMEM, HS_ERR_INVALID, HS_ERR_UNSUPPORTED, HS_ERR_DEVICE, HS_ERR_CAPACITY = range(8)
 
 EXPORTS = [
@@ -594,7 +594,7 @@ def slim_convert_diff_files(old_slim_path, hnsw_path, out_slim_path, dim, metric
 
 def rows_representable(rows, fmt):
     """hs_rows_representable (host only): None when every value of `rows` (n x dim fp32) is exactly representable in the row
-    format `fmt` (HS_ROWS_U8: integers 0..255; HS_ROWS_F16: finite fp16 values), else the index of the first row that is not."""
+    format `fmt` (HS_ROWS_U8: integers 0..255; HS_ROWS_I8: integers -128..127; HS_ROWS_F16: finite fp16 values), else the index of the first row that is not."""
     r = np.ascontiguousarray(rows, np.float32)
     r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
     bad = ctypes.c_uint64(0)
@@ -604,12 +604,12 @@ def rows_representable(rows, fmt):
 
 def rows_to_narrow(rows, fmt, out=None):
     """hs_rows_to_narrow (host only): `rows` (n x dim fp32, dim % 16 == 0) in the row format `fmt` and the lane-major layout of the
-    device copy -- (narrow, first_bad): narrow is n x dim uint8 (HS_ROWS_U8) or float16 (HS_ROWS_F16), first_bad None when every
+    device copy -- (narrow, first_bad): narrow is n x dim uint8 (HS_ROWS_U8), int8 (HS_ROWS_I8) or float16 (HS_ROWS_F16), first_bad None when every
     value is representable, else the first row that is not (nothing is written from there on; `out`, when given, is the array
     that is filled)."""
     r = np.ascontiguousarray(rows, np.float32)
     r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
-    dt = np.uint8 if int(fmt) == HS_ROWS_U8 else np.float16
+    dt = {HS_ROWS_U8: np.uint8, HS_ROWS_I8: np.int8}.get(int(fmt), np.float16)
     if out is None:
         out = np.zeros(r.shape, dt)
     assert out.dtype == dt and out.shape == r.shape and out.flags.c_contiguous
@@ -1207,7 +1207,7 @@ class Index:
 
     @classmethod
     def load_narrow(cls, path, kind, dim, fmt, metric=HS_METRIC_L2, max_elements=0, device=0):
-        """hs_index_load_narrow: the index of `path` with its rows on the device in `fmt` (HS_ROWS_U8 / HS_ROWS_F16) only -- what
+        """hs_index_load_narrow: the index of `path` with its rows on the device in `fmt` (HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16) only -- what
         Index(path, ...) + set_row_format(fmt) + set_f32_resident(False) gives, without the fp32 array ever being allocated."""
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
@@ -1367,7 +1367,7 @@ class Index:
         _check(lib().hs_set_ef(self._h, int(ef)))
 
     def set_row_format(self, fmt):
-        """hs_index_set_row_format: HS_ROWS_U8 / HS_ROWS_F16 build a narrow copy of the rows that the flat kernel then reads
+        """hs_index_set_row_format: HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16 build a narrow copy of the rows that the flat kernel then reads
         (HsError HS_ERR_UNSUPPORTED, index unchanged, when a stored value is not exactly representable); HS_ROWS_F32 drops it.
         No answer changes."""
         _check(lib().hs_index_set_row_format(self._h, int(fmt)))

@@ -482,7 +482,7 @@ static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d
   const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
   const size_t dim = ix->info.dim;
   ix->last_kernel = screened ? xs_kernel_name(fmt)
-                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_I8 ? "hs::exact_scan_kernel_i8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
   const size_t gq = std::min(kExactGroupQueries, nq);
   if (screened) {
     HIP_TRY(w->xs_norms.ensure((size_t)ix->dev.n + gq));

@@ -14,6 +14,7 @@ static hipError_t upload_cap(DevBuf<T> &b, const std::vector<T> &v, size_t cap) 
 }
 
 // ---- narrow rows ------------------------------------------------------------------------------------------------------------
+static bool is_narrow_format(int fmt) { return fmt == ROWS_F16 || fmt == ROWS_U8 || fmt == ROWS_I8; }
 template <typename T>
 static size_t first_unfit(const float *x, size_t count) {
   for (size_t i = 0; i < count; i++)
@@ -21,9 +22,12 @@ static size_t first_unfit(const float *x, size_t count) {
   return count;
 }
 size_t first_unfit(const float *x, size_t count, int fmt) {
-  return fmt == ROWS_U8 ? first_unfit<uint8_t>(x, count) : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : count;
+  return fmt == ROWS_U8 ? first_unfit<uint8_t>(x, count) : fmt == ROWS_I8 ? first_unfit<int8_t>(x, count)
+         : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : count;
 }
-static const char *row_format_name(int fmt) { return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : "HS_ROWS_F32"; }
+static const char *row_format_name(int fmt) {
+  return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_I8 ? "HS_ROWS_I8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : "HS_ROWS_F32";
+}
 std::string unfit_message(size_t row, size_t comp, float v, int fmt) {
   char val[64];
   snprintf(val, sizeof val, "%.9g", (double)v);
@@ -68,8 +72,9 @@ static size_t rows_to_narrow_t(const float *rows, size_t n, size_t dim, T *out) 
   return n;
 }
 static size_t rows_to_narrow_host(const float *rows, size_t n, size_t dim, int fmt, void *out) {
-  return fmt == ROWS_U8 ? rows_to_narrow_t<uint8_t>(rows, n, dim, static_cast<uint8_t *>(out))
-                        : rows_to_narrow_t<_Float16>(rows, n, dim, static_cast<_Float16 *>(out));
+  return fmt == ROWS_U8   ? rows_to_narrow_t<uint8_t>(rows, n, dim, static_cast<uint8_t *>(out))
+         : fmt == ROWS_I8 ? rows_to_narrow_t<int8_t>(rows, n, dim, static_cast<int8_t *>(out))
+                          : rows_to_narrow_t<_Float16>(rows, n, dim, static_cast<_Float16 *>(out));
 }
 // The narrow copy of an index WITHOUT resident fp32 rows, (re)built from host rows: allocated for `cap` rows, converted on the
 // host and uploaded in chunks of at most kNarrowStageBytes -- the fp32 array never exists on the device.
@@ -412,7 +417,7 @@ hs_status hs_index_info(const hs_index *ix, hs_info *out) {
 
 hs_status hs_index_set_row_format(hs_index *ix, int format) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
-  if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
+  if (format != ROWS_F32 && !is_narrow_format(format)) return fail(HS_ERR_INVALID, "bad row format");
   if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
   return guarded([&] {
     if (format != ROWS_F32 && (ix->info.dim & 15) != 0)
@@ -462,14 +467,14 @@ hs_status hs_index_set_f32_resident(hs_index *ix, int on) {
 int hs_index_f32_resident(const hs_index *ix) { return ix ? (ix->f32_resident ? 1 : 0) : 1; }
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad) {
   if (!first_bad || (n && dim && !rows)) return fail(HS_ERR_INVALID, "null argument");
-  if (format != ROWS_F32 && format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format");
+  if (format != ROWS_F32 && !is_narrow_format(format)) return fail(HS_ERR_INVALID, "bad row format");
   *first_bad = dim ? first_unfit(rows, n * dim, format) / dim : n;
   return HS_OK;
 }
 
 hs_status hs_rows_to_narrow(const float *rows, size_t n, size_t dim, int format, void *out, uint64_t *first_bad) {
   if (!first_bad || (n && dim && (!rows || !out))) return fail(HS_ERR_INVALID, "null argument");
-  if (format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
+  if (!is_narrow_format(format)) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
   if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0");
   *first_bad = dim ? rows_to_narrow_host(rows, n, dim, format, out) : n;
   return HS_OK;
@@ -479,7 +484,7 @@ hs_status hs_index_load_narrow(const char *path, int kind, int metric, size_t di
                                hs_index **out) {
   if (!path || !out) return fail(HS_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (format != ROWS_F16 && format != ROWS_U8) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
+  if (!is_narrow_format(format)) return fail(HS_ERR_INVALID, "bad row format (HS_ROWS_U8 or HS_ROWS_F16)");
   if (kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "narrow rows: a SlimQ index has no flat-kernel rows");
   return guarded(kLoadNomem, [&] {
     if ((dim & 15) != 0) return fail(HS_ERR_UNSUPPORTED, "narrow rows need dim % 16 == 0 (the flat kernel does not serve dim " + std::to_string(dim) + ")");

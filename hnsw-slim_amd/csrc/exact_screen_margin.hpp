@@ -9,6 +9,8 @@
 // the 1 / (1 - d u) of the gamma bounds.  The term (d + 8) 2^-120 covers products and inputs lost to underflow or flushed to zero.
 // +inf -- "cannot decide", the query falls back to the scan -- when a norm is not finite or so large that the recipe may overflow
 // where the screen does not (S or P above 2^125).
+// Sign does not enter: the rounding bounds are stated on sum |q_i| |x_i| <= |q| |x| <= S / 2 and on the squares, the premises on the
+// norms and dim alone, so the bound serves rows with negative values (fp32, fp16 and i8 rows) as it serves u8 rows.
 #pragma once
 #include "hd.hpp"
 

@@ -31,6 +31,11 @@ __device__ inline uint32_t pack4_u8(const float *x, uint32_t o, uint32_t dim) {
   for (uint32_t b = 0; b < 4; b++) w |= (uint32_t)narrow_cast<uint8_t>(x[narrow_source(o + b, dim)]) << (8 * b);
   return w;
 }
+__device__ inline uint32_t pack4_i8(const float *x, uint32_t o, uint32_t dim) {
+  uint32_t w = 0;
+  for (uint32_t b = 0; b < 4; b++) w |= (uint32_t)(uint8_t)narrow_cast<int8_t>(x[narrow_source(o + b, dim)]) << (8 * b);
+  return w;
+}
 __device__ inline uint32_t pack2_f16(const float *x, uint32_t o, uint32_t dim) {
   uint32_t w = 0;
   for (uint32_t b = 0; b < 2; b++) {
@@ -64,10 +69,11 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
         for (uint32_t c = lane; c < a.dim; c += 64) dst[c] = x[c];
       }
     }
-    if (a.narrow) {   // dim % 16 == 0 (hs_index_set_row_format): a row is a whole number of 32-bit words in both formats
-      if (a.fmt == ROWS_U8) {
+    if (a.narrow) {   // dim % 16 == 0 (hs_index_set_row_format): a row is a whole number of 32-bit words in every format
+      if (a.fmt == ROWS_U8 || a.fmt == ROWS_I8) {
         uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a.narrow) + (size_t)id * a.dim);
-        for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_u8(x, 4 * w, a.dim);
+        if (a.fmt == ROWS_U8) for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_u8(x, 4 * w, a.dim);
+        else for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_i8(x, 4 * w, a.dim);
       } else {
         uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<_Float16 *>(a.narrow) + (size_t)id * a.dim);
         for (uint32_t w = lane; w < a.dim / 2; w += 64) dst[w] = pack2_f16(x, 2 * w, a.dim);
@@ -84,7 +90,7 @@ hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream) {
   if (a.nrec == 0) return hipSuccess;
   if (!a.stage || !a.labels || !a.deleted || a.first_row > a.nrec) return hipErrorInvalidValue;
   if (a.tile0 && (a.stride == 0 || (a.stride & 15u) != 0 || a.stride > 64)) return hipErrorInvalidValue;
-  if (a.narrow && ((a.dim & 15u) != 0 || (a.fmt != ROWS_U8 && a.fmt != ROWS_F16))) return hipErrorInvalidValue;
+  if (a.narrow && ((a.dim & 15u) != 0 || (a.fmt != ROWS_U8 && a.fmt != ROWS_I8 && a.fmt != ROWS_F16))) return hipErrorInvalidValue;
   const uint32_t per = kUpdateBlock / 64;
   hipLaunchKernelGGL(index_update_kernel, dim3((a.nrec + per - 1) / per), dim3(kUpdateBlock), 0, stream, a);
   return hipGetLastError();

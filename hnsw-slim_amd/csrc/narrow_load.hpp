@@ -1,4 +1,4 @@
-// narrow_load.hpp -- device-side reads of an index's narrow (u8 / fp16) row copy: which rows a kernel instantiation reads, and
+// narrow_load.hpp -- device-side reads of an index's narrow (u8 / i8 / fp16) row copy: which rows a kernel instantiation reads, and
 // the exact widening of stored element pairs.  Shared by flat_search.hip (8 lanes per row) and beam_search.hip (4 lanes per row).
 // Layout and conversion: narrow_rows.hpp / narrow_rows.hip.
 #pragma once
@@ -18,12 +18,13 @@ typedef uint32_t hs_u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 typedef _Float16 hs_h2 __attribute__((ext_vector_type(2)));
 
 // The rows a strict / fast kernel instantiation reads.  ROW = float: the resident fp32 rows, taken from the DevIndex (the struct is
-// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / _Float16: the base of the
+// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / int8_t / _Float16: the base of the
 // narrow copy, a kernel argument of its own (DevIndex keeps its layout).
 template <typename ROW> struct RowSrc { const ROW *p; };
 template <> struct RowSrc<float> {};
 
-// element pair i of a lane's chunk, widened: a u8 pair is half a dword (v_cvt_f32_ubyteN), an f16 pair one dword (v_cvt_f32_f16)
+// element pair i of a lane's chunk, widened: a u8 or i8 pair is half a dword (v_cvt_f32_ubyteN; i8 below), an f16 pair one dword
+// (v_cvt_f32_f16)
 __device__ __forceinline__ hs_f2 narrow_pair(const uint8_t *, const uint32_t *dw, int i) {
   const uint32_t w = dw[i >> 1] >> ((i & 1) * 16);
   return hs_f2{(float)(w & 0xFFu), (float)((w >> 8) & 0xFFu)};
@@ -32,9 +33,22 @@ __device__ __forceinline__ hs_f2 narrow_pair(const _Float16 *, const uint32_t *d
   const hs_h2 h = __builtin_bit_cast(hs_h2, dw[i]);
   return hs_f2{(float)h.x, (float)h.y};
 }
+// A signed byte (two's complement, narrow_rows.hpp) has no v_cvt_f32_ubyteN.  Neither a v_bfe_i32 in front of the conversion nor a
+// biased byte with a subtract behind it is needed on gfx950: the conversion's sub-dword operand select extends the sign itself,
+//   v_cvt_f32_i32_sdwa v, sext(w) src0_sel:BYTE_n
+// which is what the compiler makes of (float)(int8_t)(w >> 8 n): one instruction per element, as for u8.  Exact: the operand is
+// the integer the byte stands for, |v| <= 128 < 2^24, and every such integer is an fp32 value.
+__device__ __forceinline__ hs_f2 i8_pair(uint32_t h) { return hs_f2{(float)(int)(int8_t)h, (float)(int)(int8_t)(h >> 8)}; }   // bytes 0 and 1 of h
+__device__ __forceinline__ hs_f2 narrow_pair(const int8_t *, const uint32_t *dw, int i) {
+  const uint32_t w = dw[i >> 1];
+  return (i & 1) ? hs_f2{(float)(int)(int8_t)(w >> 16), (float)((int)w >> 24)} : i8_pair(w);
+}
 __device__ __forceinline__ hs_f2 narrow_pair_at(const uint8_t *chunk, uint32_t i) {
   const uint32_t w = *reinterpret_cast<const unsigned short *>(chunk + 2 * i);
   return hs_f2{(float)(w & 0xFFu), (float)(w >> 8)};
+}
+__device__ __forceinline__ hs_f2 narrow_pair_at(const int8_t *chunk, uint32_t i) {
+  return i8_pair(*reinterpret_cast<const unsigned short *>(chunk + 2 * i));
 }
 __device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t i) {
   const hs_h2 h = *reinterpret_cast<const hs_h2 *>(chunk + 2 * i);
@@ -43,7 +57,7 @@ __device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t 
 
 // One round of a lane's chunk at a runtime dim: up to eight consecutive element pairs, held as they were loaded and widened on use.
 // load(c, nb, nw): pairs [0, nw) -- nw = 0, 4 or 8, at most nb, and only where c is dword aligned -- arrive in one 16-byte load
-// (u8: eight pairs; fp16: four, so two loads for eight) or one 8-byte load (u8: four pairs); pairs [nw, nb) in one load each
+// (u8 / i8: eight pairs; fp16: four, so two loads for eight) or one 8-byte load (u8 / i8: four pairs); pairs [nw, nb) in one load each
 // (2 / 4 bytes).  Nothing beyond pair nb is touched.  pair(i, nw) widens pair i < nb, with the nw that load() was given.
 template <typename ROW> struct NarrowRound;
 template <> struct NarrowRound<uint8_t> {
@@ -67,6 +81,15 @@ template <> struct NarrowRound<uint8_t> {
   __device__ __forceinline__ hs_f2 pair(uint32_t i, uint32_t nw) const {
     const uint32_t h = i < nw ? w[i >> 1] >> ((i & 1u) * 16u) : p[i];
     return hs_f2{(float)(h & 0xFFu), (float)((h >> 8) & 0xFFu)};
+  }
+};
+// i8: the bytes arrive as the u8 round's do (the same 16-, 8- and 2-byte loads); only the widening differs
+template <> struct NarrowRound<int8_t> : NarrowRound<uint8_t> {
+  __device__ __forceinline__ void load(const int8_t *c, uint32_t nb, uint32_t nw) {
+    NarrowRound<uint8_t>::load(reinterpret_cast<const uint8_t *>(c), nb, nw);
+  }
+  __device__ __forceinline__ hs_f2 pair(uint32_t i, uint32_t nw) const {
+    return i8_pair(i < nw ? w[i >> 1] >> ((i & 1u) * 16u) : p[i]);
   }
 };
 template <> struct NarrowRound<_Float16> {

@@ -8,8 +8,12 @@
 
 namespace hs {
 
-enum : int { ROWS_F32 = 0, ROWS_F16 = 1, ROWS_U8 = 2 };   // hs_row_format
-inline size_t narrow_width(int fmt) { return fmt == ROWS_U8 ? 1 : fmt == ROWS_F16 ? 2 : 0; }
+enum : int { ROWS_F32 = 0, ROWS_F16 = 1, ROWS_U8 = 2, ROWS_I8 = 3 };   // hs_row_format
+inline size_t narrow_width(int fmt) { return fmt == ROWS_U8 || fmt == ROWS_I8 ? 1 : fmt == ROWS_F16 ? 2 : 0; }
+// The stored form of every format is the value itself in the format's own encoding: u8 the unsigned byte, i8 the two's complement
+// byte (no bias: what a caller's int8 array holds is what the copy holds), f16 the IEEE half.  Every place that writes or reads a
+// narrow row -- the pack kernel, the record kernel of the live updates, hs_index_patch, hs_rows_to_narrow, hs_index_get_row,
+// hs_index_load_narrow -- goes through narrow_cast and a plain widening conversion of T.
 
 // slot of element j of a row in its narrow row (lane-major: see narrow_rows.hip)
 __host__ __device__ inline uint32_t narrow_slot(uint32_t j, uint32_t dim) {
@@ -20,15 +24,23 @@ __host__ __device__ inline uint32_t narrow_slot(uint32_t j, uint32_t dim) {
 template <typename T> __host__ __device__ inline T narrow_cast(float x);
 // (an out-of-range or NaN value must not reach the float -> integer conversion, which is undefined for it)
 template <> __host__ __device__ inline uint8_t narrow_cast<uint8_t>(float x) { return (x >= 0.0f && x <= 255.0f) ? (uint8_t)x : (uint8_t)0; }
+template <> __host__ __device__ inline int8_t narrow_cast<int8_t>(float x) { return (x >= -128.0f && x <= 127.0f) ? (int8_t)(int)x : (int8_t)0; }
 template <> __host__ __device__ inline _Float16 narrow_cast<_Float16>(float x) { return (_Float16)x; }   // round to nearest even, overflow -> inf
 
-// Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255; f16: every finite fp16 value, subnormals
-// included.  -0.0f passes in both (-0.0f == 0.0f; u8 stores 0 and reads back +0.0f, f16 keeps the sign), and reading +0 for -0
-// cannot change a distance: in the L2 recipe t = q - x gives t * t = +0 for every sign combination of zero operands and the
-// same t for q != 0; in the IP recipe the product q * x is +-0 either way and a +-0 added to an accumulator that started at +0
-// (fma(q, x, acc): +0 + -0 = +0 in round-to-nearest) leaves it bit-identical.
+// Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255; i8: the integers -128 .. 127; f16: every
+// finite fp16 value, subnormals included.  -0.0f passes in all (-0.0f == 0.0f; u8 and i8 store 0 and read back +0.0f, f16 keeps
+// the sign), and reading +0 for -0 cannot change a distance: in the L2 recipe t = q - x gives t * t = +0 for every sign
+// combination of zero operands and the same t for q != 0; in the IP recipe the product q * x is +-0 either way and a +-0 added to
+// an accumulator that started at +0 (fma(q, x, acc): +0 + -0 = +0 in round-to-nearest) leaves it bit-identical.
+// With i8 other elements of the row may be negative, so the IP accumulator may be negative or may pass through zero; the argument
+// does not lean on its sign.  The swap changes only the term of the zero element, from one signed zero to the other.  Adding a
+// zero of either sign to acc != 0 returns acc.  An accumulator that is zero is +0: it starts at +0, a sum of a zero term and +0 is
+// +0, an exact cancellation of non-zero operands rounds to +0 in round-to-nearest, and nothing underflows to a zero (q, acc and so
+// q * x + acc for an integer x are multiples of 2^-149); -0 arises only from -0 + -0, which needs an accumulator that already is
+// -0.  So acc stays bit-identical at the swapped step and hence at every later one.
 template <typename T> __host__ __device__ inline bool narrow_fits(float x);
 template <> __host__ __device__ inline bool narrow_fits<uint8_t>(float x) { return x >= 0.0f && x <= 255.0f && (float)(uint8_t)x == x; }
+template <> __host__ __device__ inline bool narrow_fits<int8_t>(float x) { return x >= -128.0f && x <= 127.0f && (float)(int8_t)(int)x == x; }
 template <> __host__ __device__ inline bool narrow_fits<_Float16>(float x) {
   const float y = (float)(_Float16)x;
   return y == x && y - y == 0.0f;   // (y - y is NaN for +-inf)

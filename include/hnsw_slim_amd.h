@@ -181,9 +181,10 @@ hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t
 hs_status hs_index_resize(hs_index *ix, size_t new_max_elements);
 
 /* ---- narrow rows (no counterpart in the reference) -------------------------------------------------------------------
- * Besides the resident fp32 rows an index can hold a u8 or fp16 copy of them, and the flat kernel -- the default kernel of every
- * bare index -- then reads that copy (hs::flat_kernel_u8 / hs::flat_kernel_f16) and a quarter / half of the row bytes.  The copy must
- * represent every stored value exactly: u8 -> fp32 and fp16 -> fp32 are exact, the query stays fp32 and the distance is the same
+ * Besides the resident fp32 rows an index can hold a u8, i8 or fp16 copy of them, and the flat kernel -- the default kernel of every
+ * bare index -- then reads that copy (hs::flat_kernel_u8 / _i8 / _f16) and a quarter / half of the row bytes.  HS_ROWS_I8 holds the
+ * integers -128 .. 127 as two's complement bytes (what int8 embedding models return; no bias, so inner products are the caller's).
+ * The copy must represent every stored value exactly: u8 -> fp32, i8 -> fp32 and fp16 -> fp32 are exact, the query stays fp32 and the distance is the same
  * fp32 recipe in the same order, so distances, labels, counters and tie behaviour are bit-identical to HS_ROWS_F32.  It is an
  * explicit call because it is a contract on the data: it costs device memory (one value of the format per value of the fp32 array's
  * row capacity: max(n, max_elements) x dim x 1 or 2 bytes, included in hs_info.device_bytes while it exists) and a later
@@ -192,9 +193,9 @@ hs_status hs_index_resize(hs_index *ix, size_t new_max_elements);
  * every other kernel (strict / fast: filters, delete marks, exact order, ef > 512, threshold_level > 0, the re-run pass,
  * hs_search_batch_raw) reads the fp32 rows.  After hs_index_set_f32_resident(ix, 0) the fp32 rows are gone and EVERY search
  * kernel reads the copy: the kernel choice stays what it was and the narrow twin of the chosen kernel is launched
- * (hs::flat_kernel_u8 / _f16, hs::fast_kernel_u8 / _f16, hs::strict_kernel_u8 / _f16, the re-run pass included), with the same
- * bits in every output.  The index then occupies a quarter (u8) or half (fp16) of the row bytes instead of 5/4 or 3/2 of them. */
-typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2 } hs_row_format;
+ * (hs::flat_kernel_u8 / _i8 / _f16, hs::fast_kernel_u8 / _i8 / _f16, hs::strict_kernel_u8 / _i8 / _f16, the re-run pass included), with
+ * the same bits in every output.  The index then occupies a quarter (u8, i8) or half (fp16) of the row bytes instead of 5/4 or 3/2 of them. */
+typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2, HS_ROWS_I8 = 3 } hs_row_format;
 /* Builds (or, for HS_ROWS_F32, drops) the narrow copy of the rows on the index's device.  Not to be called while a search on this
  * index is in flight (as hs_index_patch).  HS_ERR_UNSUPPORTED, index left exactly as it was, when a stored value is not
  * representable (the message names the first offending row and the value), for a SlimQ index, and for dim % 16 != 0 (the flat
@@ -202,11 +203,11 @@ typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2 } hs_row_format;
 hs_status hs_index_set_row_format(hs_index *ix, int format);
 int hs_index_row_format(const hs_index *ix);
 /* Host only, no device: *first_bad = n when every value of rows[n x dim] is representable in `format`, else the index of the
- * first row that is not.  Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255 (and -0.0f, read back
- * as +0.0f, which cannot change a distance); fp16: every finite fp16 value, subnormals included. */
+ * first row that is not.  Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255, i8: the integers -128 .. 127 (and, in
+ * both, -0.0f, read back as +0.0f, which cannot change a distance); fp16: every finite fp16 value, subnormals included. */
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad);
 /* on = 0: free the resident fp32 rows of an index that holds a narrow copy; from then on EVERY search kernel reads the copy.
- * on = 1: re-create them from the copy (widening is exact; a u8 index reads +0.0f where -0.0f was stored).
+ * on = 1: re-create them from the copy (widening is exact; a u8 or i8 index reads +0.0f where -0.0f was stored).
  * hs_info.device_bytes falls / rises by exactly max(n, max_elements) x dim x 4.  Both are idempotent.  on = 0 on an index in
  * HS_ROWS_F32 format is HS_ERR_INVALID.  While the fp32 rows are absent hs_index_set_row_format to any OTHER format (HS_ROWS_F32
  * included) is HS_ERR_INVALID, index untouched: restore the fp32 rows first.  hs_index_patch works in both states (the patched
@@ -216,9 +217,9 @@ hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int for
  * flight (as hs_index_patch). */
 hs_status hs_index_set_f32_resident(hs_index *ix, int on);
 int hs_index_f32_resident(const hs_index *ix);
-/* Host only, no device: out[n x dim] of `format` (HS_ROWS_U8: bytes, HS_ROWS_F16: IEEE half words) in the lane-major layout of
+/* Host only, no device: out[n x dim] of `format` (HS_ROWS_U8: bytes, HS_ROWS_I8: two's complement bytes, HS_ROWS_F16: IEEE half words) in the lane-major layout of
  * the device copy, out[r * dim + s * (dim / 8) + 2 i + e] = rows[r][16 i + 2 s + e]; *first_bad as hs_rows_representable;
- * nothing is written beyond row *first_bad.  HS_ERR_INVALID for a format other than U8 / F16, HS_ERR_UNSUPPORTED for
+ * nothing is written beyond row *first_bad.  HS_ERR_INVALID for a format other than U8 / I8 / F16, HS_ERR_UNSUPPORTED for
  * dim % 16 != 0. */
 hs_status hs_rows_to_narrow(const float *rows, size_t n, size_t dim, int format, void *out, uint64_t *first_bad);
 /* hs_index_load, but the rows go to the device in `format` only: the result equals load + set_row_format(format) +
