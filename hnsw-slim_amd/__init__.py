@@ -34,6 +34,7 @@ EXPORTS = [
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
     "hs_index_exact_search", "hs_index_exact_search_dev",
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
+    "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
@@ -220,6 +221,10 @@ def lib():
     L.hs_index_exact_search_screened_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_screen_stats.argtypes = [vp, vp, vp, vp]
     L.hs_debug_exact_screen_margin.argtypes = [ci, sz, ctypes.c_float, ctypes.c_float, vp]
+    L.hs_index_exact_search_q8.argtypes = [vp, vp, vp, ci, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_q8_dev.argtypes = [vp, vp, vp, ci, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_debug_exact_screen_q8_interval.argtypes = [ci, sz, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.hs_debug_exact_q8_pack_order.argtypes = [sz, vp]
     L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
     L.hs_index_seed_levels.argtypes = [vp, sz, sz]
     L.hs_index_mark_deleted.argtypes = [vp, vp, sz, ci]
@@ -848,6 +853,21 @@ def debug_heap_ops(ops, wave_pop=True, lds_slots=1024):
     _check(lib().hs_debug_heap_ops(arr.ctypes.data, n, 1 if wave_pop else 0, lds_slots, heap.ctypes.data, pops.ctypes.data, cnt.ctypes.data))
     f = lambda a, m: [(float(a[i, 0:1].view(np.float32)[0]), int(a[i, 1])) for i in range(m)]
     return f(heap, int(cnt[0])), f(pops, int(cnt[1]))
+
+
+def exact_screen_q8_interval(metric, dim, value, qn2, xn2):
+    """hs_debug_exact_screen_q8_interval (host only): (a, e) of the integer screen for the exact integer distance `value` (L2: squared
+    distance, IP: inner product) and the integer squared norms of query and row; e == 0 where the fp32 recipe is exact."""
+    a, e = ctypes.c_float(), ctypes.c_float()
+    _check(lib().hs_debug_exact_screen_q8_interval(metric, dim, int(value), int(qn2), int(xn2), ctypes.byref(a), ctypes.byref(e)))
+    return np.float32(a.value), np.float32(e.value)
+
+
+def exact_q8_pack_order(dim):
+    """hs_debug_exact_q8_pack_order (host only): out[p] = the element of a byte query that hs_index_exact_search_q8 puts at byte p."""
+    out = np.empty(dim, np.uint32)
+    _check(lib().hs_debug_exact_q8_pack_order(dim, out.ctypes.data))
+    return out
 
 
 def exact_screen_margin(metric, dim, qn2, xn2):
@@ -1523,6 +1543,35 @@ class Index:
         _check(lib().hs_index_exact_search_screened_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
                                                         None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
                                                         d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_search_q8(self, queries, k, fs=None, filter_of_query=None, query_format=None):
+        """hs_index_exact_search_q8: exact_search's answers for the same queries widened to fp32, bit for bit, for uint8 / int8 queries
+        over an index whose narrow copy has that format; the distance of every pair comes exact from the integer matrix cores.  The
+        format is the array's dtype (query_format overrides it: the C entry's refusals)."""
+        q = np.ascontiguousarray(queries)
+        if query_format is None:
+            if q.dtype not in (np.uint8, np.int8):
+                raise HsError(HS_ERR_INVALID, f"exact_search_q8 takes uint8 or int8 queries, not {q.dtype}")
+            query_format = HS_ROWS_U8 if q.dtype == np.uint8 else HS_ROWS_I8
+        nq = q.shape[0]
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels, dists, cnt = np.empty((nq, k), np.uint64), np.empty((nq, k), np.float32), np.empty(nq, np.uint32)
+        _check(lib().hs_index_exact_search_q8(self._h, None if fs is None else fs._h, q.ctypes.data, query_format, nq, k,
+                                              None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
+        return dict(labels=labels, dists=dists, cnt=cnt)
+
+    def exact_search_q8_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_q8_dev: exact_search_screened_dev's arguments with a uint8 / int8 query tensor; asynchronous, pair with
+        check(stream)."""
+        name = str(d_queries.dtype)
+        if name not in ("torch.uint8", "torch.int8"):
+            raise HsError(HS_ERR_INVALID, f"exact_search_q8_dev takes uint8 or int8 queries, not {name}")
+        _check(lib().hs_index_exact_search_q8_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(),
+                                                  HS_ROWS_U8 if name == "torch.uint8" else HS_ROWS_I8, d_queries.shape[0], k,
+                                                  None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                                  d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
 
     def exact_screen_stats(self):
         """hs_index_exact_screen_stats of the last screened call: dict(screened, fell_back, reranked_rows); zeros when it was handed to

@@ -7,6 +7,7 @@
 #include "exact_engine.hpp"
 #include "exact_screen_engine.hpp"
 #include "exact_screen_margin.hpp"
+#include "exact_screen_q8_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -535,10 +536,79 @@ hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const
   });
 }
 
-static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k, const uint32_t *filter_of_query,
+// ---- byte queries over byte rows (exact_screen_q8.hip) ------------------------------------------------------------------------
+// What the byte-query entries refuse beyond exact_use_ok.
+static hs_status exact_q8_use_ok(const hs_index *ix, int query_format) {
+  if (query_format != HS_ROWS_U8 && query_format != HS_ROWS_I8) return fail(HS_ERR_INVALID, kQ8QueryFormatRefusal);
+  if (ix->row_fmt == ROWS_F32 || !ix->narrow.p) return fail(HS_ERR_INVALID, kQ8NoNarrowRefusal);
+  if (ix->row_fmt != query_format) return fail(HS_ERR_INVALID, kQ8FormatMismatchRefusal);
+  return HS_OK;
+}
+
+// exact_dev's arguments with the queries as bytes of the rows' format.  A shape the integer kernel does not take is widened and handed
+// to the fp32 screen.
+static hs_status exact_q8_dev(hs_index *ix, const hs_filter_set *fs, const void *d_q, int qfmt, size_t nq, size_t k, const uint32_t *d_foq,
+                              const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  const size_t dim = ix->info.dim;
+  const int fmt = ix->row_fmt;
+  if (!xq_supported(fmt, (uint32_t)dim, (uint32_t)k)) {
+    HIP_TRY(w->xq_wide.ensure(nq * dim));
+    HIP_TRY(launch_exact_q8_widen(d_q, qfmt, nq * dim, w->xq_wide.p, stream));
+    return exact_dev(ix, fs, w->xq_wide.p, nq, k, d_foq, d_order, l64, dd, cnt, stream, true);
+  }
+  if (w->counters.n < 48) {   // (as exact_dev)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  const void *rows = ix->narrow.p;
+  ix->last_kernel = xq_kernel_name(fmt);
+  const size_t gq = std::min(kExactGroupQueries, nq);
+  const size_t row_bytes = ((size_t)ix->dev.n * sizeof(XqRow) + 15) / 16 * 16;
+  HIP_TRY(w->xq_info.ensure(row_bytes + gq * sizeof(XqQuery)));
+  HIP_TRY(w->xq_packed.ensure(gq * dim));
+  HIP_TRY(w->xq_wide.ensure(gq * dim));
+  HIP_TRY(w->xs_state.ensure(kXsStateWords + 2 * gq));
+  size_t cand = 16;   // the largest any group of the call needs: a full group and the last one
+  for (size_t m : {gq, nq - (nq - 1) / kExactGroupQueries * kExactGroupQueries}) {
+    uint32_t gx, rpb;
+    cand = std::max(cand, xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &gx, &rpb));
+  }
+  HIP_TRY(w->xs_cand.ensure(cand));
+  XqRow *rinfo = reinterpret_cast<XqRow *>(w->xq_info.p);
+  HIP_TRY(launch_exact_q8_rownorms(ix->dev, rows, fmt, rinfo, stream));
+  for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+    const size_t m = std::min(kExactGroupQueries, nq - off);
+    ScreenArgs sa{};
+    const size_t bytes = bf_partial_bytes(ix->dev.n, (uint32_t)m, (uint32_t)k, &sa.x.grid_x, &sa.x.rows_per_block);
+    HIP_TRY(w->xruns.ensure(std::max<size_t>(bytes, 16)));
+    sa.x.queries = w->xq_wide.p; sa.x.nq = (uint32_t)m; sa.x.k = (uint32_t)k; sa.x.order = d_order ? d_order + off : nullptr;
+    sa.x.partial = w->xruns.p;
+    sa.x.out_labels = l64 + off * k; sa.x.out_dists = dd + off * k; sa.x.out_counts = cnt ? cnt + off : nullptr;
+    FilterArgs fa{};
+    if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+    sa.first_group = off == 0;
+    xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &sa.grid_x, &sa.rows_per_block);
+    sa.cand = w->xs_cand.p;
+    sa.state = w->xs_state.p; sa.qflag = w->xs_state.p + kXsStateWords; sa.fb_order = sa.qflag + gq;
+    XqArgs qa{};
+    qa.queries = static_cast<const uint8_t *>(d_q) + off * dim;
+    qa.packed = w->xq_packed.p; qa.wide = w->xq_wide.p;
+    qa.qinfo = reinterpret_cast<XqQuery *>(w->xq_info.p + row_bytes); qa.rinfo = rinfo;
+    HIP_TRY(launch_exact_screen_q8(ix->dev, rows, fmt, sa, qa, fs ? &fa : nullptr, stream));
+  }
+  ix->xs_last = w;
+  ix->xs_last_nq = nq;
+  return HS_OK;
+}
+
+// qfmt: the element type of `queries` -- ROWS_F32, or ROWS_U8 / ROWS_I8 for the byte-query entry (which is always screened).
+static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *queries, int qfmt, size_t nq, size_t k, const uint32_t *filter_of_query,
                             uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
   return guarded([&] {
     hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
+    if (s == HS_OK && qfmt != ROWS_F32) s = exact_q8_use_ok(ix, qfmt);
     if (s != HS_OK) return s;
     if (fs)
       for (size_t i = 0; i < nq; i++)
@@ -549,8 +619,14 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const float *
     HIP_TRY(hipSetDevice(ix->device));
     hs_index::StreamWs *w = ix->stream_ws(nullptr);
     const size_t dim = ix->info.dim;
-    HIP_TRY(w->aq.ensure(nq * dim)); HIP_TRY(w->al64.ensure(nq * k)); HIP_TRY(w->adist.ensure(nq * k)); HIP_TRY(w->acnt.ensure(nq));
-    HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(w->al64.ensure(nq * k)); HIP_TRY(w->adist.ensure(nq * k)); HIP_TRY(w->acnt.ensure(nq));
+    if (qfmt == ROWS_F32) {
+      HIP_TRY(w->aq.ensure(nq * dim));
+      HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    } else {
+      HIP_TRY(w->xq_in.ensure(nq * dim));
+      HIP_TRY(hipMemcpyAsync(w->xq_in.p, queries, nq * dim, hipMemcpyHostToDevice, nullptr));
+    }
     std::vector<uint32_t> order;   // (outlives the asynchronous copy: the call synchronises before it returns)
     if (fs) {
       // queries of one filter into the same tiles: a tile skips the rows that none of its filters allows
@@ -565,7 +641,9 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const float *
       HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
       HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
     }
-    s = exact_dev(ix, fs, w->aq.p, nq, k, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened);
+    const uint32_t *d_foq = fs ? w->afoq.p : nullptr, *d_order = fs ? w->xorder.p : nullptr;
+    s = qfmt == ROWS_F32 ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
+                         : exact_q8_dev(ix, fs, w->xq_in.p, qfmt, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr);
     if (s != HS_OK) return s;
     HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, nq * k * 4, hipMemcpyDeviceToHost, nullptr));
@@ -577,13 +655,13 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const float *
 
 hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
                                 const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
-  return exact_host(ix, fs, queries, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false);
+  return exact_host(ix, fs, queries, ROWS_F32, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false);
 }
 
 // ---- the same answers by screen, re-rank and fallback (exact_screen.hip) -------------------------------------------------------
 hs_status hs_index_exact_search_screened(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
                                          const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
-  return exact_host(ix, fs, queries, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+  return exact_host(ix, fs, queries, ROWS_F32, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
 }
 hs_status hs_index_exact_search_screened_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
                                              const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
@@ -613,6 +691,36 @@ hs_status hs_debug_exact_screen_margin(int metric, size_t dim, float qnorm2, flo
   if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
   if (dim == 0 || dim > 4096) return fail(HS_ERR_INVALID, "dim: 1 to 4096");
   *out = exact_screen_margin(metric == HS_METRIC_IP, (uint32_t)dim, qnorm2, xnorm2);
+  return HS_OK;
+}
+
+// ---- the same answers for byte queries, screened on the integer matrix cores (exact_screen_q8.hip) -----------------------------
+hs_status hs_index_exact_search_q8(hs_index *ix, const hs_filter_set *fs, const void *queries, int query_format, size_t nq, size_t k,
+                                   const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  if (query_format == HS_ROWS_F32) return fail(HS_ERR_INVALID, kQ8QueryFormatRefusal);   // (exact_host reads it as "fp32 queries")
+  return exact_host(ix, fs, queries, query_format, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+}
+hs_status hs_index_exact_search_q8_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, int query_format, size_t nq, size_t k,
+                                       const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                       uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+    if (s == HS_OK) s = exact_q8_use_ok(ix, query_format);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_q8_dev(ix, fs, d_queries, query_format, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+  });
+}
+hs_status hs_debug_exact_screen_q8_interval(int metric, size_t dim, int32_t value, uint32_t qnorm2, uint32_t xnorm2, float *out_a, float *out_e) {
+  if (!out_a || !out_e) return fail(HS_ERR_INVALID, "null argument");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
+  if (dim == 0 || dim > 4096) return fail(HS_ERR_INVALID, "dim: 1 to 4096");
+  *out_e = exact_screen_q8_interval(metric == HS_METRIC_IP, (uint32_t)dim, value, qnorm2, xnorm2, out_a);
+  return HS_OK;
+}
+hs_status hs_debug_exact_q8_pack_order(size_t dim, uint32_t *out) {
+  if (!out) return fail(HS_ERR_INVALID, "null argument");
+  if (dim == 0 || dim > 4096 || (dim & 15)) return fail(HS_ERR_INVALID, "dim: a multiple of 16, at most 4096");
+  for (size_t p = 0; p < dim; p++) out[p] = narrow_elem((uint32_t)p, (uint32_t)dim);
   return HS_OK;
 }
 

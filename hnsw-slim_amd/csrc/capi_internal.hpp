@@ -127,6 +127,10 @@ struct hs_index {
     DevBuf<float> xs_norms;
     DevBuf<uint8_t> xs_cand;
     DevBuf<uint32_t> xs_state;
+    // hs_index_exact_search_q8 (exact_screen_q8.hip): the caller's bytes (host entry), a group's queries in slot order and as fp32
+    // (the hand-over: all of them as fp32), and the integers per row and per query of a group
+    DevBuf<uint8_t> xq_in, xq_packed, xq_info;
+    DevBuf<float> xq_wide;
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
   StreamWs *xs_last = nullptr;   // hs_index_exact_screen_stats: the workspace of the last screened call (null: none, or it was delegated)
@@ -177,6 +181,13 @@ struct FilterUse {
 // The batched add takes no index with delete marks, on the device or on the host twin.
 static constexpr const char *kBatchedAddMarksRefusal =
     "batched add refused: the index holds delete marks (the batched insertion has no deleted-element branches); use hs_index_add_points";
+
+// hs_index_exact_search_q8[_dev]: byte queries meet byte rows of their own format.
+static constexpr const char *kQ8NoNarrowRefusal =
+    "exact search with byte queries refused: the index holds no u8 / i8 copy of its rows (hs_index_set_row_format)";
+static constexpr const char *kQ8FormatMismatchRefusal =
+    "exact search with byte queries refused: query_format is not the format of the index's narrow copy";
+static constexpr const char *kQ8QueryFormatRefusal = "exact search with byte queries refused: query_format must be HS_ROWS_U8 or HS_ROWS_I8";
 
 // ---- the refusals and small helpers more than one entry uses: one text, one definition (error reporting: capi_guard.hpp) ----------
 #pragma GCC visibility push(hidden)

@@ -35,16 +35,10 @@
 
 namespace hs {
 
-static constexpr uint32_t kXsNoSlot = 0xFFFFFFFFu;
 static constexpr uint32_t kXsMerge = 2048;   // entries the re-rank gathers per query
 static constexpr uint32_t kXsKeep = 512;     // rows it re-ranks per query
 
-struct XsCand { float hi, lo; uint32_t row; };   // 12 bytes
 typedef float xs_f16v __attribute__((ext_vector_type(16)));
-
-__host__ __device__ inline uint32_t xs_cap(uint32_t k) { return k + kXsSlack; }
-// candidate workspace: nq x nruns lists of cap entries, then nq x nruns sizes
-__host__ __device__ inline size_t xs_hdr_offset(uint32_t nq, uint32_t nruns, uint32_t cap) { return (size_t)nq * nruns * cap * sizeof(XsCand); }
 
 // ---- norms -------------------------------------------------------------------------------------------------------------------
 // 16 lanes per vector, 16 vectors per workgroup; a narrow row is summed in the order it is stored.
@@ -128,27 +122,6 @@ template <> struct XsChunk<_Float16> {
     return make_float4(a.x, a.y, b.x, b.y);
   }
 };
-
-// One survivor into a list sorted by hi (lane 0 only).  A full list first drops what its bound has ruled out since; an insertion into
-// a full list of live entries flags the query.
-__device__ __forceinline__ void xs_insert(XsCand *L, uint32_t *sz, float *U, uint32_t *flag, uint32_t k, uint32_t cap, float hi, float lo, uint32_t row) {
-  if (*flag || !(lo <= *U)) return;
-  uint32_t n = *sz;
-  if (n == cap) {
-    const float u = *U;
-    uint32_t w = 0;
-    for (uint32_t i = 0; i < n; i++)
-      if (L[i].lo <= u) L[w++] = L[i];
-    n = w;
-    if (n == cap) { *flag = 1; return; }
-  }
-  uint32_t pos = n;
-  while (pos > 0 && hi < L[pos - 1].hi) { L[pos] = L[pos - 1]; pos--; }
-  L[pos] = XsCand{hi, lo, row};
-  n++;
-  *sz = n;
-  *U = n >= k ? L[k - 1].hi : INFINITY;
-}
 
 // Positions [p0, p0 + len) of the tile's queries into LDS in operand layout: [len / 8][2][64 queries][4].
 template <typename ROW>
@@ -560,8 +533,7 @@ hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, co
   if (!rows && ix.n) return hipErrorInvalidDevicePointer;
   const bool l2 = ix.metric == METRIC_L2;
   hipError_t e;
-  hipLaunchKernelGGL(xs_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, a.state, a.qflag, a.fb_order, nq, a.first_group ? 1u : 0u);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_exact_screen_init(a, stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(xs_norms_kernel<float>, dim3((nq + 15) / 16), dim3(256), 0, stream, a.x.queries, nq, dim, a.qnorm2);
   if ((e = hipGetLastError()) != hipSuccess) return e;
 
@@ -588,7 +560,18 @@ hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, co
   sa.n = ix.n; sa.dim = dim; sa.nq = nq; sa.k = k; sa.cap = xs_cap(k); sa.rows_per_block = a.rows_per_block; sa.slice = slice;
   hipLaunchKernelGGL(screen, dim3(a.grid_x, (nq + kXsTile - 1) / kXsTile), dim3(256), lds, stream, sa);
   if ((e = hipGetLastError()) != hipSuccess) return e;
+  return launch_exact_screen_finish(ix, rows, fmt, a, f, stream);
+}
 
+hipError_t launch_exact_screen_init(const ScreenArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(xs_init_kernel, dim3((a.x.nq + 255) / 256), dim3(256), 0, stream, a.state, a.qflag, a.fb_order, a.x.nq, a.first_group ? 1u : 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_screen_finish(const DevIndex &ix, const void *rows, int fmt, const ScreenArgs &a, const FilterArgs *f, hipStream_t stream) {
+  const uint32_t dim = ix.dim, nq = a.x.nq, k = a.x.k;
+  const bool l2 = ix.metric == METRIC_L2;
+  hipError_t e;
   void (*rerank)(const XsRerank) = fmt == ROWS_U8    ? (l2 ? xs_rerank_kernel_u8<METRIC_L2> : xs_rerank_kernel_u8<METRIC_IP>)
                                    : fmt == ROWS_I8  ? (l2 ? xs_rerank_kernel_i8<METRIC_L2> : xs_rerank_kernel_i8<METRIC_IP>)
                                    : fmt == ROWS_F16 ? (l2 ? xs_rerank_kernel_f16<METRIC_L2> : xs_rerank_kernel_f16<METRIC_IP>)

@@ -13,6 +13,36 @@ static constexpr uint32_t kXsTile = 64;       // queries per workgroup tile
 static constexpr uint32_t kXsSlack = 16;      // a candidate list holds k + kXsSlack entries
 static constexpr uint32_t kXsStateWords = 8;  // state[0]: flagged queries of the launch group, [1]: of the call, [2..3]: re-ranked rows (u64)
 
+static constexpr uint32_t kXsNoSlot = 0xFFFFFFFFu;
+
+// What the screens (exact_screen.hip, exact_screen_q8.hip) hand to the re-rank: per (query, row chunk, unit parity) a list of rows
+// whose distance interval [lo, hi] the chunk's bound has not ruled out.
+struct XsCand { float hi, lo; uint32_t row; };   // 12 bytes
+__host__ __device__ inline uint32_t xs_cap(uint32_t k) { return k + kXsSlack; }
+// candidate workspace: nq x nruns lists of cap entries, then nq x nruns sizes
+__host__ __device__ inline size_t xs_hdr_offset(uint32_t nq, uint32_t nruns, uint32_t cap) { return (size_t)nq * nruns * cap * sizeof(XsCand); }
+
+// One survivor into a list sorted by hi (lane 0 only).  A full list first drops what its bound has ruled out since; an insertion into
+// a full list of live entries flags the query.
+__device__ __forceinline__ void xs_insert(XsCand *L, uint32_t *sz, float *U, uint32_t *flag, uint32_t k, uint32_t cap, float hi, float lo, uint32_t row) {
+  if (*flag || !(lo <= *U)) return;
+  uint32_t n = *sz;
+  if (n == cap) {
+    const float u = *U;
+    uint32_t w = 0;
+    for (uint32_t i = 0; i < n; i++)
+      if (L[i].lo <= u) L[w++] = L[i];
+    n = w;
+    if (n == cap) { *flag = 1; return; }
+  }
+  uint32_t pos = n;
+  while (pos > 0 && hi < L[pos - 1].hi) { L[pos] = L[pos - 1]; pos--; }
+  L[pos] = XsCand{hi, lo, row};
+  n++;
+  *sz = n;
+  *U = n >= k ? L[k - 1].hi : INFINITY;
+}
+
 // One launch group.  x: the exact scan's arguments -- queries, outputs, `order` (the screen's tile slots, nullable), and the
 // fallback's workspace and geometry (partial, grid_x, rows_per_block as bf_partial_bytes plans them).
 struct ScreenArgs {
@@ -39,5 +69,9 @@ hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int f
 // Query norms, screen, re-rank, fallback of one group: all enqueued, nothing read back.  rows / fmt as launch_exact_search.
 hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, const ScreenArgs &a, const FilterArgs *f, hipStream_t stream);
 const char *xs_kernel_name(int fmt);
+// The two ends of a group that every screen shares: the clearing of state, flags and fallback order ahead of it; behind it the re-rank
+// of the lists in `a.cand` over a.x.queries and the scan of the flagged queries.
+hipError_t launch_exact_screen_init(const ScreenArgs &a, hipStream_t stream);
+hipError_t launch_exact_screen_finish(const DevIndex &ix, const void *rows, int fmt, const ScreenArgs &a, const FilterArgs *f, hipStream_t stream);
 
 }  // namespace hs

@@ -31,4 +31,43 @@ HS_HD float exact_screen_margin(int metric_ip, uint32_t dim, float qn2, float xn
   return 8.f * c * s + tiny;
 }
 
+// The integer screen of exact_screen_q8.hip: rows and queries are bytes, v is the exact integer L2 distance D or inner
+// product P (int32 at dim <= 4096), qn / xn the exact integer squared norms of the true values.  Returns e and writes a with
+// |a - r| <= e for the recipe's r:
+//   L2, D < 2^24         a = (float)D exactly, e = 0: every partial sum of the recipe is a sum of squares of integers, an integer
+//                        <= D, so each fp32 operation is exact in any order, fused or not, and r = D.
+//   IP, qn xn < 2^48     a = 1 - (float)P exactly, e = 0: every partial sum is an integer bounded by sum |q_i x_i| <= |q| |x| < 2^24,
+//                        so the sum is P exactly, and 1 - P, an integer of magnitude <= 2^24, is exact as well.
+//   otherwise            a = fl(D) or fl(1 - fl(P)), e = exact_screen_margin over (float)qn, (float)xn.  That margin bounds
+//                        |a' - r| for an fp32 screen a' by E_recipe + E_screen', E_recipe <= (2 d + 4) u S (L2), (d + 2) u (P' + 1) (IP,
+//                        P' = |q| |x|) the recipe's own rounding and E_screen' of the same size.  The integer screen's error is one or two
+//                        roundings:  L2  |fl(D) - D| <= u D <= 2 u S;  IP  |a - (1 - P)| <= u |P| + u |1 - fl(P)| <= 2 u (P' + 1) (1 + u).
+//                        So |a - r| <= E_recipe + 2 u S <= (2 d + 6) u S < (4 d + 7) u S, and (d + 4) u (P' + 1) <= (2 d + 2) u (P' + 1)
+//                        for d >= 2; the norms, one rounding off their integers, sit inside the factor of two the margin keeps.
+HS_HD float exact_screen_q8_interval(int metric_ip, uint32_t dim, int32_t v, uint32_t qn, uint32_t xn, float *a) {
+  if (metric_ip) {
+    *a = 1.f - (float)v;
+    if ((uint64_t)qn * (uint64_t)xn < (1ull << 48)) return 0.f;
+  } else {
+    *a = (float)v;
+    if (v < (1 << 24)) return 0.f;
+  }
+  return exact_screen_margin(metric_ip, dim, (float)qn, (float)xn);
+}
+
+// The smallest lo = fl(a - e) any pair of the inexact regime can have for a query of squared norm qn against rows of squared norm
+// <= xn_max; +inf when no pair of the query can be inexact.  Every operation involved is monotone, so evaluating at the extreme
+// arguments bounds every pair:  L2  a >= 2^24 and e <= e(xn_max);  IP  fl(P) <= pmax, a float >= |q| sqrt(xn_max), and e <= e(xn_max).
+// Below this value the screen's integer pre-test alone decides (exact_screen_q8.hip, xq_threshold).
+HS_HD float exact_screen_q8_inexact_floor(int metric_ip, uint32_t dim, uint32_t qn, uint32_t xn_max) {
+  const float e = exact_screen_margin(metric_ip, dim, (float)qn, (float)xn_max);
+  if (metric_ip) {
+    if ((uint64_t)qn * (uint64_t)xn_max < (1ull << 48)) return __builtin_inff();
+    const float pmax = (float)(__builtin_sqrt((double)qn * (double)xn_max) * 1.000001 + 1.0);
+    return (1.f - pmax) - e;
+  }
+  if (2ull * ((uint64_t)qn + (uint64_t)xn_max) < (1ull << 24)) return __builtin_inff();   // D <= 2 (|q|^2 + |x|^2)
+  return 16777216.f - e;
+}
+
 }  // namespace hs

@@ -20,6 +20,11 @@ __host__ __device__ inline uint32_t narrow_slot(uint32_t j, uint32_t dim) {
   const uint32_t i = j >> 4, s = (j >> 1) & 7u, e = j & 1u;
   return s * (dim >> 3) + 2u * i + e;
 }
+// the element a narrow row holds in slot p: the inverse of narrow_slot (dim % 16 == 0)
+__host__ __device__ inline uint32_t narrow_elem(uint32_t p, uint32_t dim) {
+  const uint32_t per = dim >> 3, s = p / per, rem = p - s * per;
+  return 16u * (rem >> 1) + 2u * s + (rem & 1u);
+}
 
 template <typename T> __host__ __device__ inline T narrow_cast(float x);
 // (an out-of-range or NaN value must not reach the float -> integer conversion, which is undefined for it)

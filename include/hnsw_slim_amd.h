@@ -611,6 +611,26 @@ hs_status hs_index_exact_screen_stats(hs_index *ix, uint64_t *screened, uint64_t
  * fp32 squared norms of query and row.  +inf: the screen does not decide such a pair. */
 hs_status hs_debug_exact_screen_margin(int metric, size_t dim, float qnorm2, float xnorm2, float *out);
 
+/* ---- the same answers for byte queries, screened on the integer matrix cores -------------------------------------------
+ * queries: nq x dim bytes in natural order, query_format HS_ROWS_U8 or HS_ROWS_I8 -- the format of the index's narrow copy.  Labels,
+ * fp32 distance bits, counts and padding are those of hs_index_exact_search for the same queries widened to fp32, for every input,
+ * under delete marks and filter sets included (csrc/exact_screen_q8.hip): the integer MFMA gives the exact distance of
+ * every pair, the re-rank of the survivors and the fallback are the screened entry's.  hs_index_exact_screen_stats reports the call.
+ * HS_ERR_INVALID: a query_format other than the two; an index without a u8 / i8 copy of its rows; a copy of another format; the rest
+ * as hs_index_exact_search.  dim % 32 != 0 is widened on the device and handed to hs_index_exact_search_screened's route.
+ * hs_last_kernel: hs::xq_screen_kernel_u8 or hs::xq_screen_kernel_i8 (the name of what ran when handed over). */
+hs_status hs_index_exact_search_q8(hs_index *ix, const hs_filter_set *fs, const void *queries, int query_format, size_t nq, size_t k,
+                                   const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+hs_status hs_index_exact_search_q8_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, int query_format, size_t nq, size_t k,
+                                       const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                       uint32_t *d_out_counts, void *stream);
+/* Debug: the interval of the integer screen (csrc/exact_screen_margin.hpp, exact_screen_q8_interval; host only) for the exact integer
+ * distance `value` (L2: the squared distance, IP: the inner product) and the integer squared norms of query and row: *out_a the
+ * screened value, *out_e its margin -- 0 where the recipe's fp32 arithmetic is exact. */
+hs_status hs_debug_exact_screen_q8_interval(int metric, size_t dim, int32_t value, uint32_t qnorm2, uint32_t xnorm2, float *out_a, float *out_e);
+/* Debug: out[p] = the element of a query that the pack kernel puts at byte p (host only; dim % 16 == 0): the order a narrow row is stored in. */
+hs_status hs_debug_exact_q8_pack_order(size_t dim, uint32_t *out);
+
 /* ---- harness (CPU, not accelerated): produce index files in the reference's formats ------------ */
 /* HierarchicalNSW ctor + addPoint loop + saveIndex: hnswalg.h:85-159, 1248-1376, 748-779.
  * labels = row index; threads==1 reproduces the reference's serial build byte for byte. */

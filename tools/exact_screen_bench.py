@@ -5,6 +5,9 @@ old, new, old, new for three rounds; HIP-event time per call, median of `--reps`
 
   1. unfiltered over fp32 rows      2. unfiltered over the u8 copy      3. eight filters that allow 1 %, queries grouped by filter
 
+With --q8 the comparison is instead hs_index_exact_search_screened_dev against hs_index_exact_search_q8_dev (byte queries, the integer
+matrix cores: csrc/exact_screen_q8.hip) over the u8 copy of the same index, in the same process and the same alternation.
+
 The spread of the old entry's own rounds is the noise: a difference counts only where it lies outside it.  By default the index is the
 bench's cached one; --ring puts the same rows under a ring graph instead (the exact entries read rows, labels and marks, never the
 graph), which spares a fresh machine the HNSW build.  Output: the log on stdout.
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ring", action="store_true", help="the bench's rows under a ring graph: no HNSW build")
+    ap.add_argument("--q8", action="store_true", help="the fp32 screen against the byte-query entry over u8 rows, nothing else")
     ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
     args = ap.parse_args()
     import torch
@@ -69,10 +73,12 @@ def main():
 
     result = {}
 
-    def compare(name, dq, kernel, **kw):
+    def compare(name, dq, kernel, q8=None, **kw):
         o_old, o_new = outputs(), outputs()
         old = lambda: ix.exact_search_dev(dq, K, *o_old, **kw)            # noqa: E731
         new = lambda: ix.exact_search_screened_dev(dq, K, *o_new, **kw)   # noqa: E731
+        if q8 is not None:   # the fp32 screen is the old side, the byte-query entry the new one
+            old, new = new, lambda: ix.exact_search_q8_dev(q8, K, *o_old, **kw)   # noqa: E731
         old(); new(); ix.check()
         assert ix.last_kernel() == kernel, ix.last_kernel()
         for a, b, what in zip(o_old, o_new, ("labels", "dists", "counts")):
@@ -87,13 +93,20 @@ def main():
         spread = (max(o) - min(o)) / np.median(o) * 100
         spread_new = (max(n) - min(n)) / np.median(n) * 100
         delta = (np.median(n) / np.median(o) - 1) * 100
-        log(f"{name}: outputs identical | scan {np.median(o):.3f} ms ({', '.join(f'{x:.3f}' for x in o)}, spread {spread:.2f} %) | screened "
-            f"{np.median(n):.3f} ms ({', '.join(f'{x:.3f}' for x in n)}, spread {spread_new:.2f} %) | screened / scan {delta:+.2f} % -> "
+        so, sn = ("screened", "q8") if q8 is not None else ("scan", "screened")
+        log(f"{name}: outputs identical | {so} {np.median(o):.3f} ms ({', '.join(f'{x:.3f}' for x in o)}, spread {spread:.2f} %) | {sn} "
+            f"{np.median(n):.3f} ms ({', '.join(f'{x:.3f}' for x in n)}, spread {spread_new:.2f} %) | {sn} / {so} {delta:+.2f} % -> "
             + ("inside the spread: no difference shown" if abs(delta) <= max(spread, spread_new) else "outside the spread")
             + f" | fell_back {st['fell_back']}, reranked_rows {st['reranked_rows']} ({st['reranked_rows'] / max(st['screened'], 1):.2f} per screened query)")
-        result[name] = dict(scan_ms=o, screened_ms=n, **st)
+        result[name] = {so + "_ms": o, sn + "_ms": n, **st}
 
     dq = torch.from_numpy(q).to(dev)
+    if args.q8:
+        ix.set_row_format(hs.HS_ROWS_U8)
+        assert np.array_equal(q, q.astype(np.uint8)), "the bench's queries are bytes"
+        compare("u8 rows, byte queries", dq, "hs::xq_screen_kernel_u8", q8=torch.from_numpy(q.astype(np.uint8)).to(dev))
+        log("RESULT " + json.dumps(result))
+        return 0
     compare("fp32 rows", dq, "hs::xs_screen_kernel")
     rng = np.random.default_rng(3)
     fs = hs.FilterSet.create(ix, PER)
