@@ -35,6 +35,7 @@ EXPORTS = [
     "hs_index_exact_search", "hs_index_exact_search_dev",
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
+    "hs_index_exact_search_f16", "hs_index_exact_search_f16_dev", "hs_debug_exact_screen_f16_margin",
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
@@ -225,6 +226,9 @@ def lib():
     L.hs_index_exact_search_q8_dev.argtypes = [vp, vp, vp, ci, sz, sz, vp, vp, vp, vp, vp]
     L.hs_debug_exact_screen_q8_interval.argtypes = [ci, sz, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.hs_debug_exact_q8_pack_order.argtypes = [sz, vp]
+    L.hs_index_exact_search_f16.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_f16_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_debug_exact_screen_f16_margin.argtypes = [ci, sz, ctypes.c_float, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, vp]
     L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
     L.hs_index_seed_levels.argtypes = [vp, sz, sz]
     L.hs_index_mark_deleted.argtypes = [vp, vp, sz, ci]
@@ -868,6 +872,15 @@ def exact_q8_pack_order(dim):
     out = np.empty(dim, np.uint32)
     _check(lib().hs_debug_exact_q8_pack_order(dim, out.ctypes.data))
     return out
+
+
+def exact_screen_f16_margin(metric, dim, qn2, xn2, q_subnormals=0, x_subnormals=0):
+    """hs_debug_exact_screen_f16_margin (host only): the bound e of the half-precision screen from the fp32 squared norms and the
+    numbers of subnormal halves of query and row; both zero: exact_screen_margin's value."""
+    out = ctypes.c_float()
+    _check(lib().hs_debug_exact_screen_f16_margin(metric, dim, ctypes.c_float(float(qn2)), ctypes.c_float(float(xn2)), int(q_subnormals),
+                                                  int(x_subnormals), ctypes.byref(out)))
+    return np.float32(out.value)
 
 
 def exact_screen_margin(metric, dim, qn2, xn2):
@@ -1572,6 +1585,30 @@ class Index:
                                                   HS_ROWS_U8 if name == "torch.uint8" else HS_ROWS_I8, d_queries.shape[0], k,
                                                   None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
                                                   d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_search_f16(self, queries, k, fs=None, filter_of_query=None):
+        """hs_index_exact_search_f16: exact_search's answers for the same queries widened to fp32, bit for bit, for float16 queries over
+        an index whose narrow copy is HS_ROWS_F16; the screen runs on the half-precision matrix cores."""
+        q = np.ascontiguousarray(queries)
+        if q.dtype != np.float16:
+            raise HsError(HS_ERR_INVALID, f"exact_search_f16 takes float16 queries, not {q.dtype}")
+        nq = q.shape[0]
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels, dists, cnt = np.empty((nq, k), np.uint64), np.empty((nq, k), np.float32), np.empty(nq, np.uint32)
+        _check(lib().hs_index_exact_search_f16(self._h, None if fs is None else fs._h, q.ctypes.data, nq, k,
+                                               None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
+        return dict(labels=labels, dists=dists, cnt=cnt)
+
+    def exact_search_f16_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_f16_dev: exact_search_screened_dev's arguments with a float16 query tensor; asynchronous, pair with
+        check(stream)."""
+        if str(d_queries.dtype) != "torch.float16":
+            raise HsError(HS_ERR_INVALID, f"exact_search_f16_dev takes float16 queries, not {d_queries.dtype}")
+        _check(lib().hs_index_exact_search_f16_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                                   None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                                   d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
 
     def exact_screen_stats(self):
         """hs_index_exact_screen_stats of the last screened call: dict(screened, fell_back, reranked_rows); zeros when it was handed to

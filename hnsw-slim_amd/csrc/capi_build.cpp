@@ -7,6 +7,7 @@
 #include "exact_engine.hpp"
 #include "exact_screen_engine.hpp"
 #include "exact_screen_margin.hpp"
+#include "exact_screen_f16q_engine.hpp"
 #include "exact_screen_q8_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
@@ -603,12 +604,81 @@ static hs_status exact_q8_dev(hs_index *ix, const hs_filter_set *fs, const void 
   return HS_OK;
 }
 
-// qfmt: the element type of `queries` -- ROWS_F32, or ROWS_U8 / ROWS_I8 for the byte-query entry (which is always screened).
+// ---- fp16 queries over fp16 rows (exact_screen_f16q.hip) ----------------------------------------------------------------------
+// exact_host's code for "the queries are halves": not a row format of the byte-query entry, which keeps refusing HS_ROWS_F16.
+static constexpr int kQueriesF16 = -16;
+
+// What the fp16-query entries refuse beyond exact_use_ok.  No index of dim % 16 != 0 can hold a narrow copy (hs_index_set_row_format):
+// such a call is handed over whatever rows the index has.
+static hs_status exact_f16q_use_ok(const hs_index *ix) {
+  if ((ix->info.dim & 15) == 0 && (ix->row_fmt != ROWS_F16 || !ix->narrow.p)) return fail(HS_ERR_INVALID, kF16QNoCopyRefusal);
+  return HS_OK;
+}
+
+// exact_dev's arguments with the queries as halves.  A shape the half-precision kernel does not take is widened and handed to the
+// route the fp32 queries take.
+static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const void *d_q, size_t nq, size_t k, const uint32_t *d_foq,
+                                const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  const size_t dim = ix->info.dim;
+  if (!xh_supported(ix->row_fmt, (uint32_t)dim, (uint32_t)k)) {
+    HIP_TRY(w->xq_wide.ensure(nq * dim));
+    HIP_TRY(launch_exact_f16q_widen(d_q, nq * dim, w->xq_wide.p, stream));
+    return exact_dev(ix, fs, w->xq_wide.p, nq, k, d_foq, d_order, l64, dd, cnt, stream, true);
+  }
+  if (w->counters.n < 48) {   // (as exact_dev)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  const void *rows = ix->narrow.p;
+  ix->last_kernel = xh_kernel_name();
+  const size_t gq = std::min(kExactGroupQueries, nq);
+  const size_t row_bytes = ((size_t)ix->dev.n * sizeof(XhInfo) + 15) / 16 * 16;
+  HIP_TRY(w->xq_info.ensure(row_bytes + gq * sizeof(XhInfo)));
+  HIP_TRY(w->xq_packed.ensure(gq * dim * 2));
+  HIP_TRY(w->xq_wide.ensure(gq * dim));
+  HIP_TRY(w->xs_state.ensure(kXsStateWords + 2 * gq));
+  size_t cand = 16;   // the largest any group of the call needs: a full group and the last one
+  for (size_t m : {gq, nq - (nq - 1) / kExactGroupQueries * kExactGroupQueries}) {
+    uint32_t gx, rpb;
+    cand = std::max(cand, xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &gx, &rpb));
+  }
+  HIP_TRY(w->xs_cand.ensure(cand));
+  XhInfo *rinfo = reinterpret_cast<XhInfo *>(w->xq_info.p);
+  HIP_TRY(launch_exact_f16q_rowinfo(ix->dev, rows, rinfo, stream));
+  for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+    const size_t m = std::min(kExactGroupQueries, nq - off);
+    ScreenArgs sa{};
+    const size_t bytes = bf_partial_bytes(ix->dev.n, (uint32_t)m, (uint32_t)k, &sa.x.grid_x, &sa.x.rows_per_block);
+    HIP_TRY(w->xruns.ensure(std::max<size_t>(bytes, 16)));
+    sa.x.queries = w->xq_wide.p; sa.x.nq = (uint32_t)m; sa.x.k = (uint32_t)k; sa.x.order = d_order ? d_order + off : nullptr;
+    sa.x.partial = w->xruns.p;
+    sa.x.out_labels = l64 + off * k; sa.x.out_dists = dd + off * k; sa.x.out_counts = cnt ? cnt + off : nullptr;
+    FilterArgs fa{};
+    if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+    sa.first_group = off == 0;
+    xs_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, &sa.grid_x, &sa.rows_per_block);
+    sa.cand = w->xs_cand.p;
+    sa.state = w->xs_state.p; sa.qflag = w->xs_state.p + kXsStateWords; sa.fb_order = sa.qflag + gq;
+    XhArgs qa{};
+    qa.queries = static_cast<const uint16_t *>(d_q) + off * dim;
+    qa.packed = reinterpret_cast<uint16_t *>(w->xq_packed.p); qa.wide = w->xq_wide.p;
+    qa.qinfo = reinterpret_cast<XhInfo *>(w->xq_info.p + row_bytes); qa.rinfo = rinfo;
+    HIP_TRY(launch_exact_screen_f16q(ix->dev, rows, sa, qa, fs ? &fa : nullptr, stream));
+  }
+  ix->xs_last = w;
+  ix->xs_last_nq = nq;
+  return HS_OK;
+}
+
+// qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 for the fp16-query entry
+// (both always screened).
 static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *queries, int qfmt, size_t nq, size_t k, const uint32_t *filter_of_query,
                             uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
   return guarded([&] {
     hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
-    if (s == HS_OK && qfmt != ROWS_F32) s = exact_q8_use_ok(ix, qfmt);
+    if (s == HS_OK && qfmt != ROWS_F32) s = qfmt == kQueriesF16 ? exact_f16q_use_ok(ix) : exact_q8_use_ok(ix, qfmt);
     if (s != HS_OK) return s;
     if (fs)
       for (size_t i = 0; i < nq; i++)
@@ -624,8 +694,9 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
       HIP_TRY(w->aq.ensure(nq * dim));
       HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
     } else {
-      HIP_TRY(w->xq_in.ensure(nq * dim));
-      HIP_TRY(hipMemcpyAsync(w->xq_in.p, queries, nq * dim, hipMemcpyHostToDevice, nullptr));
+      const size_t qbytes = nq * dim * (qfmt == kQueriesF16 ? 2 : 1);
+      HIP_TRY(w->xq_in.ensure(qbytes));
+      HIP_TRY(hipMemcpyAsync(w->xq_in.p, queries, qbytes, hipMemcpyHostToDevice, nullptr));
     }
     std::vector<uint32_t> order;   // (outlives the asynchronous copy: the call synchronises before it returns)
     if (fs) {
@@ -642,8 +713,9 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
       HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
     }
     const uint32_t *d_foq = fs ? w->afoq.p : nullptr, *d_order = fs ? w->xorder.p : nullptr;
-    s = qfmt == ROWS_F32 ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
-                         : exact_q8_dev(ix, fs, w->xq_in.p, qfmt, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr);
+    s = qfmt == ROWS_F32      ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
+        : qfmt == kQueriesF16 ? exact_f16q_dev(ix, fs, w->xq_in.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr)
+                              : exact_q8_dev(ix, fs, w->xq_in.p, qfmt, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr);
     if (s != HS_OK) return s;
     HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, nq * k * 4, hipMemcpyDeviceToHost, nullptr));
@@ -721,6 +793,29 @@ hs_status hs_debug_exact_q8_pack_order(size_t dim, uint32_t *out) {
   if (!out) return fail(HS_ERR_INVALID, "null argument");
   if (dim == 0 || dim > 4096 || (dim & 15)) return fail(HS_ERR_INVALID, "dim: a multiple of 16, at most 4096");
   for (size_t p = 0; p < dim; p++) out[p] = narrow_elem((uint32_t)p, (uint32_t)dim);
+  return HS_OK;
+}
+
+// ---- the same answers for fp16 queries, screened on the half-precision matrix cores (exact_screen_f16q.hip) -------------------
+hs_status hs_index_exact_search_f16(hs_index *ix, const hs_filter_set *fs, const void *queries, size_t nq, size_t k,
+                                    const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, kQueriesF16, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+}
+hs_status hs_index_exact_search_f16_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
+                                        const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                        uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+    if (s == HS_OK) s = exact_f16q_use_ok(ix);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_f16q_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+  });
+}
+hs_status hs_debug_exact_screen_f16_margin(int metric, size_t dim, float qnorm2, float xnorm2, uint32_t q_subnormals, uint32_t x_subnormals, float *out) {
+  if (!out) return fail(HS_ERR_INVALID, "null argument");
+  if (metric_ok(metric) != HS_OK) return HS_ERR_INVALID;
+  if (dim == 0 || dim > 4096) return fail(HS_ERR_INVALID, "dim: 1 to 4096");
+  *out = exact_screen_f16_margin(metric == HS_METRIC_IP, (uint32_t)dim, qnorm2, xnorm2, q_subnormals, x_subnormals);
   return HS_OK;
 }
 

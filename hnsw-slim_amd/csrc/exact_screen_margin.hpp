@@ -70,4 +70,66 @@ HS_HD float exact_screen_q8_inexact_floor(int metric_ip, uint32_t dim, uint32_t 
   return 16777216.f - e;
 }
 
+// The half-precision screen of exact_screen_f16q.hip: rows and queries are IEEE halves, the dot product p comes from
+// v_mfma_f32_32x32x16_f16, the norms qn2, xn2 from fp32 sums of the widened values, a is formed as above.  A product of two halves is
+// exact in fp32 (11 x 11 significand bits, exponents in [-48, 32]), so all of the screen's error is in additions.  Nothing is assumed
+// of the matrix pipeline but that each of its additions errs by at most one ulp (2 u relative), in any order:
+//   L2  recipe |r - D| <= 2 gamma_(d+2) S;  screen: the norms (d - 1) u S (exact squares) plus one rounding of their sum, the dot
+//       |p - q.x| <= 2 d u sum |q_i x_i| <= d u S and doubled exactly, the last subtraction <= 2 u S:  |a - r| <= (5 d + 8) u S.
+//   IP  recipe (d + 2) u (P + 1);  screen 2 d u P + u |1 - p|:  |a - r| <= (3 d + 3) u (P + 1).
+// So 4r's two expressions stand, with a factor 8 (d + 8) / (5 d + 8) >= 1.6 resp. 4 (d + 8) / (3 d + 3) >= 1.33 to spare instead of
+// about two.  That factor still pays for everything formed in fp32: qn2 and xn2 are off |q|^2, |x|^2 by at most d u relative, so
+// fl(qn2 + xn2) >= S (1 - (d + 1) u) and fl(sqrt qn2) fl(sqrt xn2) >= P (1 - (d + 3) u); e itself takes three roundings, lo and hi one
+// each of at most u (|a| + e) <= 2.1 u S: together below (d + 9) u of e's argument, against the 0.6 resp. 0.33 of it left over -- at
+// d = 4096, 8 (d + 8) (1 - (d + 9) u) = 32824 > 5 d + 8 + 5 = 20493, and 4 (d + 8) (1 - (d + 9) u) = 16412 > 3 d + 3 + 3 = 12294; at
+// d = 16, 191 > 93 and 95 > 54.  The constants are 4r's: nothing is lowered.
+// Subnormal halves: whether the matrix pipeline reads them or flushes them to zero is not established, so the margin holds either
+// way.  A flushed operand loses at most 2^-14 |other_i| of p at its position; with mq, mx the numbers of nonzero elements of magnitude
+// below 2^-14 in q and x, Cauchy-Schwarz bounds the lost part of p by
+//   lost = 2^-14 (sqrt(mx) |q| + sqrt(mq) |x|) + min(mq, mx) 2^-28
+// (the last term a position where both are subnormal, counted once more than needed).  e grows by lost (IP) or 2 lost (L2), formed
+// from the fp32 norms and scaled by 1 + 2^-10 against their d u and its own roundings.  mq == mx == 0 returns exact_screen_margin's
+// value itself, bit for bit: ordinary data pays nothing, and the screen's pre-test (below) leans on that.
+// No underflow beyond that: a nonzero product is at least 2^-48, a sum at most 2^44.  +inf as above.
+HS_HD float exact_screen_f16_margin(int metric_ip, uint32_t dim, float qn2, float xn2, uint32_t mq, uint32_t mx) {
+  const float e = exact_screen_margin(metric_ip, dim, qn2, xn2);
+  if ((mq | mx) == 0u) return e;
+  const float lost = 6.1035156e-5f * (__builtin_sqrtf((float)mx) * __builtin_sqrtf(qn2) + __builtin_sqrtf((float)mq) * __builtin_sqrtf(xn2)) +
+                     (float)(mq < mx ? mq : mx) * 3.7252903e-9f;   // 2^-14, 2^-28
+  return e + (metric_ip ? 1.0009766f : 2.0019531f) * lost;         // (1 + 2^-10), 2 (1 + 2^-10)
+}
+
+// The pre-test of exact_screen_f16q.hip: one FMA and one compare per accumulator element that may only OVER-admit -- what passes still
+// meets the full test lo <= U, so a pair the pre-test drops must be one the full test drops.  It serves pairs with mq == mx == 0 and
+// finite norms (everything else goes to the full test), where lo = fl(a - e) with e = exact_screen_margin.  With |p| <= 1.01 |q| |x|
+// (the dot's own error bound) every rounding below is relative to at most 2.1 S resp. 1.01 (P' + 1), P' = fl(sqrt qn2) fl(sqrt xn2):
+//   L2  lo >= (qn2 + xn2) - 2 p - [u + 4.3 u (1 + u)] (qn2 + xn2) - e (1 + u),  e (1 + u) <= 8 c (qn2 + xn2) (1 + u)^4 + 2 tiny
+//          >= (qn2 + xn2) (1 - kL) - 2 p - 2 tiny,   kL = 8 (d + 9) u
+//   IP  lo >= 1 - p - (P' + 1) kI - 3 tiny,          kI = 4 (d + 9) u
+// In floats, with w = 1 - 8 (d + 10) u (exact) and up(t) = fl(t + 2^-20 |t|) >= t + 14 u |t| (it outweighs the rounding of t):
+//   L2  row share  xlo = fl(fl(xn2 w) - 4 tiny) <= xn2 (1 - kL) - 2 tiny;  query share qlo = fl(qn2 w) <= qn2 (1 - kL);
+//       bound      T = up(fl(U - qlo)) >= U - qlo;                          pre = fl(xlo - 2 p)       (one FMA)
+//   IP  row share  sx = fl(sqrt xn2), the very value e is formed from;     query share g = -(up(fl(kI' sq)) + tiny), kI' = 4 (d + 10) u;
+//       bound      T = up(fl(up(fl(U - 1)) + kI')) >= U - 1 + kI + 3 tiny;  pre = fl(g sx - p)        (one FMA)
+// If lo <= U then, in real numbers, xlo - 2 p <= U - qlo <= T resp. g sx - p <= -kI P' - p <= U - 1 + kI + 3 tiny <= T; rounding is
+// monotone and T is a float, so pre <= T as well.  Hence pre > T implies lo > U: the pair could not have entered the list.  The test is
+// written !(pre > T) so that a NaN passes; U = +inf (a list below k rows) gives T = +inf by the same arithmetic.
+HS_HD float exact_screen_f16_up(float t) { return __builtin_fmaf(__builtin_fabsf(t), 9.5367432e-7f, t); }
+// the row's operand of the FMA: L2 xlo, IP sx
+HS_HD float exact_screen_f16_pre_row(int metric_ip, uint32_t dim, float xn2) {
+  if (metric_ip) return __builtin_sqrtf(xn2);
+  const float w = 1.f - (float)(dim + 10u) * 4.7683716e-7f;   // 8 (d + 10) 2^-24, exact
+  return xn2 * w - 4.f * ((float)(dim + 8u) * 7.5231638e-37f);
+}
+// the query's share: L2 qlo, IP g
+HS_HD float exact_screen_f16_pre_query(int metric_ip, uint32_t dim, float qn2) {
+  if (metric_ip) return -(exact_screen_f16_up((float)(dim + 10u) * 2.3841858e-7f * __builtin_sqrtf(qn2)) + (float)(dim + 8u) * 7.5231638e-37f);
+  return qn2 * (1.f - (float)(dim + 10u) * 4.7683716e-7f);
+}
+// the bound a list with k-th hi U sets for the query (share: exact_screen_f16_pre_query)
+HS_HD float exact_screen_f16_pre_bound(int metric_ip, uint32_t dim, float U, float share) {
+  if (metric_ip) return exact_screen_f16_up(exact_screen_f16_up(U - 1.f) + (float)(dim + 10u) * 2.3841858e-7f);
+  return exact_screen_f16_up(U - share);
+}
+
 }  // namespace hs

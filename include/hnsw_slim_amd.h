@@ -631,6 +631,26 @@ hs_status hs_debug_exact_screen_q8_interval(int metric, size_t dim, int32_t valu
 /* Debug: out[p] = the element of a query that the pack kernel puts at byte p (host only; dim % 16 == 0): the order a narrow row is stored in. */
 hs_status hs_debug_exact_q8_pack_order(size_t dim, uint32_t *out);
 
+/* ---- the same answers for fp16 queries, screened on the half-precision matrix cores ------------------------------------
+ * queries: nq x dim IEEE half words in natural order, over an index whose narrow copy is HS_ROWS_F16.  Labels, fp32 distance bits,
+ * counts and padding are those of hs_index_exact_search for the same queries widened to fp32, for every input, under delete marks and
+ * filter sets included (csrc/exact_screen_f16q.hip): v_mfma_f32_32x32x16_f16 screens with 4r's margin, the re-rank of the
+ * survivors and the fallback are the screened entry's.  Queries that hold NaN, +-inf or subnormal halves are not refused: their
+ * interval is not finite or their margin grows, and the fallback or the re-rank gives the scan's answer.
+ * hs_index_exact_screen_stats reports the call.
+ * HS_ERR_INVALID: an index of dim % 16 == 0 without an fp16 copy of its rows; the rest as hs_index_exact_search.  dim % 16 != 0 (no
+ * index of such a dim can hold a narrow copy) is widened on the device and handed to hs_index_exact_search_screened's route.
+ * hs_last_kernel: hs::xh_screen_kernel (the name of what ran when handed over). */
+hs_status hs_index_exact_search_f16(hs_index *ix, const hs_filter_set *fs, const void *queries, size_t nq, size_t k,
+                                    const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+hs_status hs_index_exact_search_f16_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
+                                        const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                        uint32_t *d_out_counts, void *stream);
+/* Debug: the margin of the half-precision screen (csrc/exact_screen_margin.hpp, exact_screen_f16_margin; host only) from the fp32
+ * squared norms of query and row and the numbers of their nonzero elements of magnitude below 2^-14.  Both counts zero: the value of
+ * hs_debug_exact_screen_margin, bit for bit. */
+hs_status hs_debug_exact_screen_f16_margin(int metric, size_t dim, float qnorm2, float xnorm2, uint32_t q_subnormals, uint32_t x_subnormals, float *out);
+
 /* ---- harness (CPU, not accelerated): produce index files in the reference's formats ------------ */
 /* HierarchicalNSW ctor + addPoint loop + saveIndex: hnswalg.h:85-159, 1248-1376, 748-779.
  * labels = row index; threads==1 reproduces the reference's serial build byte for byte. */

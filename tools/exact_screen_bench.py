@@ -6,7 +6,9 @@ old, new, old, new for three rounds; HIP-event time per call, median of `--reps`
   1. unfiltered over fp32 rows      2. unfiltered over the u8 copy      3. eight filters that allow 1 %, queries grouped by filter
 
 With --q8 the comparison is instead hs_index_exact_search_screened_dev against hs_index_exact_search_q8_dev (byte queries, the integer
-matrix cores: csrc/exact_screen_q8.hip) over the u8 copy of the same index, in the same process and the same alternation.
+matrix cores: csrc/exact_screen_q8.hip) over the u8 copy of the same index, in the same process and the same alternation.  With --f16q
+it is hs_index_exact_search_screened_dev against hs_index_exact_search_f16_dev (fp16 queries, the half-precision matrix cores:
+csrc/exact_screen_f16q.hip) over the fp16 copy; the bench's integers 0 .. 255 are exact halves.
 
 The spread of the old entry's own rounds is the noise: a difference counts only where it lies outside it.  By default the index is the
 bench's cached one; --ring puts the same rows under a ring graph instead (the exact entries read rows, labels and marks, never the
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ring", action="store_true", help="the bench's rows under a ring graph: no HNSW build")
     ap.add_argument("--q8", action="store_true", help="the fp32 screen against the byte-query entry over u8 rows, nothing else")
+    ap.add_argument("--f16q", action="store_true", help="the fp32 screen against the fp16-query entry over fp16 rows, nothing else")
     ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
     args = ap.parse_args()
     import torch
@@ -73,12 +76,14 @@ def main():
 
     result = {}
 
-    def compare(name, dq, kernel, q8=None, **kw):
+    def compare(name, dq, kernel, q8=None, f16=None, **kw):
         o_old, o_new = outputs(), outputs()
         old = lambda: ix.exact_search_dev(dq, K, *o_old, **kw)            # noqa: E731
         new = lambda: ix.exact_search_screened_dev(dq, K, *o_new, **kw)   # noqa: E731
         if q8 is not None:   # the fp32 screen is the old side, the byte-query entry the new one
             old, new = new, lambda: ix.exact_search_q8_dev(q8, K, *o_old, **kw)   # noqa: E731
+        if f16 is not None:   # likewise, the fp16-query entry the new side
+            old, new = new, lambda: ix.exact_search_f16_dev(f16, K, *o_old, **kw)   # noqa: E731
         old(); new(); ix.check()
         assert ix.last_kernel() == kernel, ix.last_kernel()
         for a, b, what in zip(o_old, o_new, ("labels", "dists", "counts")):
@@ -93,7 +98,7 @@ def main():
         spread = (max(o) - min(o)) / np.median(o) * 100
         spread_new = (max(n) - min(n)) / np.median(n) * 100
         delta = (np.median(n) / np.median(o) - 1) * 100
-        so, sn = ("screened", "q8") if q8 is not None else ("scan", "screened")
+        so, sn = ("screened", "q8") if q8 is not None else ("screened", "f16q") if f16 is not None else ("scan", "screened")
         log(f"{name}: outputs identical | {so} {np.median(o):.3f} ms ({', '.join(f'{x:.3f}' for x in o)}, spread {spread:.2f} %) | {sn} "
             f"{np.median(n):.3f} ms ({', '.join(f'{x:.3f}' for x in n)}, spread {spread_new:.2f} %) | {sn} / {so} {delta:+.2f} % -> "
             + ("inside the spread: no difference shown" if abs(delta) <= max(spread, spread_new) else "outside the spread")
@@ -105,6 +110,12 @@ def main():
         ix.set_row_format(hs.HS_ROWS_U8)
         assert np.array_equal(q, q.astype(np.uint8)), "the bench's queries are bytes"
         compare("u8 rows, byte queries", dq, "hs::xq_screen_kernel_u8", q8=torch.from_numpy(q.astype(np.uint8)).to(dev))
+        log("RESULT " + json.dumps(result))
+        return 0
+    if args.f16q:
+        ix.set_row_format(hs.HS_ROWS_F16)
+        assert np.array_equal(q, q.astype(np.float16).astype(np.float32)), "the bench's queries are exact halves"
+        compare("fp16 rows, fp16 queries", dq, "hs::xh_screen_kernel", f16=torch.from_numpy(q.astype(np.float16)).to(dev))
         log("RESULT " + json.dumps(result))
         return 0
     compare("fp32 rows", dq, "hs::xs_screen_kernel")
