@@ -484,7 +484,7 @@ static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d
   const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
   const size_t dim = ix->info.dim;
   ix->last_kernel = screened ? xs_kernel_name(fmt)
-                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_I8 ? "hs::exact_scan_kernel_i8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_I8 ? "hs::exact_scan_kernel_i8" : fmt == ROWS_BF16 ? "hs::exact_scan_kernel_bf16" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
   const size_t gq = std::min(kExactGroupQueries, nq);
   if (screened) {
     HIP_TRY(w->xs_norms.ensure((size_t)ix->dev.n + gq));
@@ -604,27 +604,45 @@ static hs_status exact_q8_dev(hs_index *ix, const hs_filter_set *fs, const void 
   return HS_OK;
 }
 
-// ---- fp16 queries over fp16 rows (exact_screen_f16q.hip) ----------------------------------------------------------------------
-// exact_host's code for "the queries are halves": not a row format of the byte-query entry, which keeps refusing HS_ROWS_F16.
-static constexpr int kQueriesF16 = -16;
+// ---- fp16 queries over fp16 rows (exact_screen_f16q.hip), bf16 queries over bf16 rows (exact_screen_bf16q.hip) ----------------
+// exact_host's codes for "the queries are halves" / "bf16 words": not row formats of the byte-query entry, which keeps refusing both.
+static constexpr int kQueriesF16 = -16, kQueriesBF16 = -17;
+static bool half_queries(int qfmt) { return qfmt == kQueriesF16 || qfmt == kQueriesBF16; }
+// the launch entries of the two objects, which are one source (exact_screen_f16q_engine.hpp)
+struct HalfScreen {
+  int rows;
+  const char *refusal;
+  decltype(&xh_supported) supported;
+  decltype(&xh_kernel_name) kernel_name;
+  decltype(&launch_exact_f16q_rowinfo) rowinfo;
+  decltype(&launch_exact_f16q_widen) widen;
+  decltype(&launch_exact_screen_f16q) screen;
+};
+static const HalfScreen &half_screen(int qfmt) {
+  static const HalfScreen f16{ROWS_F16, kF16QNoCopyRefusal, xh_supported, xh_kernel_name, launch_exact_f16q_rowinfo, launch_exact_f16q_widen, launch_exact_screen_f16q};
+  static const HalfScreen bf16{ROWS_BF16, kBF16QNoCopyRefusal, xb_supported, xb_kernel_name, launch_exact_bf16q_rowinfo, launch_exact_bf16q_widen, launch_exact_screen_bf16q};
+  return qfmt == kQueriesBF16 ? bf16 : f16;
+}
 
 // What the fp16-query entries refuse beyond exact_use_ok.  No index of dim % 16 != 0 can hold a narrow copy (hs_index_set_row_format):
 // such a call is handed over whatever rows the index has.
-static hs_status exact_f16q_use_ok(const hs_index *ix) {
-  if ((ix->info.dim & 15) == 0 && (ix->row_fmt != ROWS_F16 || !ix->narrow.p)) return fail(HS_ERR_INVALID, kF16QNoCopyRefusal);
+static hs_status exact_f16q_use_ok(const hs_index *ix, int qfmt = kQueriesF16) {
+  const HalfScreen &hsc = half_screen(qfmt);
+  if ((ix->info.dim & 15) == 0 && (ix->row_fmt != hsc.rows || !ix->narrow.p)) return fail(HS_ERR_INVALID, hsc.refusal);
   return HS_OK;
 }
 
-// exact_dev's arguments with the queries as halves.  A shape the half-precision kernel does not take is widened and handed to the
-// route the fp32 queries take.
+// exact_dev's arguments with the queries as halves (qfmt = kQueriesBF16: as bf16 words).  A shape the 16-bit kernel does not take is
+// widened and handed to the route the fp32 queries take.
 static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const void *d_q, size_t nq, size_t k, const uint32_t *d_foq,
-                                const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+                                const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream, int qfmt = kQueriesF16) {
+  const HalfScreen &hsc = half_screen(qfmt);
   HIP_TRY(hipSetDevice(ix->device));
   hs_index::StreamWs *w = ix->stream_ws(stream);
   const size_t dim = ix->info.dim;
-  if (!xh_supported(ix->row_fmt, (uint32_t)dim, (uint32_t)k)) {
+  if (!hsc.supported(ix->row_fmt, (uint32_t)dim, (uint32_t)k)) {
     HIP_TRY(w->xq_wide.ensure(nq * dim));
-    HIP_TRY(launch_exact_f16q_widen(d_q, nq * dim, w->xq_wide.p, stream));
+    HIP_TRY(hsc.widen(d_q, nq * dim, w->xq_wide.p, stream));
     return exact_dev(ix, fs, w->xq_wide.p, nq, k, d_foq, d_order, l64, dd, cnt, stream, true);
   }
   if (w->counters.n < 48) {   // (as exact_dev)
@@ -632,7 +650,7 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
     HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
   }
   const void *rows = ix->narrow.p;
-  ix->last_kernel = xh_kernel_name();
+  ix->last_kernel = hsc.kernel_name();
   const size_t gq = std::min(kExactGroupQueries, nq);
   const size_t row_bytes = ((size_t)ix->dev.n * sizeof(XhInfo) + 15) / 16 * 16;
   HIP_TRY(w->xq_info.ensure(row_bytes + gq * sizeof(XhInfo)));
@@ -646,7 +664,7 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
   }
   HIP_TRY(w->xs_cand.ensure(cand));
   XhInfo *rinfo = reinterpret_cast<XhInfo *>(w->xq_info.p);
-  HIP_TRY(launch_exact_f16q_rowinfo(ix->dev, rows, rinfo, stream));
+  HIP_TRY(hsc.rowinfo(ix->dev, rows, rinfo, stream));
   for (size_t off = 0; off < nq; off += kExactGroupQueries) {
     const size_t m = std::min(kExactGroupQueries, nq - off);
     ScreenArgs sa{};
@@ -665,20 +683,20 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
     qa.queries = static_cast<const uint16_t *>(d_q) + off * dim;
     qa.packed = reinterpret_cast<uint16_t *>(w->xq_packed.p); qa.wide = w->xq_wide.p;
     qa.qinfo = reinterpret_cast<XhInfo *>(w->xq_info.p + row_bytes); qa.rinfo = rinfo;
-    HIP_TRY(launch_exact_screen_f16q(ix->dev, rows, sa, qa, fs ? &fa : nullptr, stream));
+    HIP_TRY(hsc.screen(ix->dev, rows, sa, qa, fs ? &fa : nullptr, stream));
   }
   ix->xs_last = w;
   ix->xs_last_nq = nq;
   return HS_OK;
 }
 
-// qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 for the fp16-query entry
-// (both always screened).
+// qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 / kQueriesBF16 for the
+// fp16- and bf16-query entries (all always screened).
 static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *queries, int qfmt, size_t nq, size_t k, const uint32_t *filter_of_query,
                             uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
   return guarded([&] {
     hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
-    if (s == HS_OK && qfmt != ROWS_F32) s = qfmt == kQueriesF16 ? exact_f16q_use_ok(ix) : exact_q8_use_ok(ix, qfmt);
+    if (s == HS_OK && qfmt != ROWS_F32) s = half_queries(qfmt) ? exact_f16q_use_ok(ix, qfmt) : exact_q8_use_ok(ix, qfmt);
     if (s != HS_OK) return s;
     if (fs)
       for (size_t i = 0; i < nq; i++)
@@ -694,7 +712,7 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
       HIP_TRY(w->aq.ensure(nq * dim));
       HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
     } else {
-      const size_t qbytes = nq * dim * (qfmt == kQueriesF16 ? 2 : 1);
+      const size_t qbytes = nq * dim * (half_queries(qfmt) ? 2 : 1);
       HIP_TRY(w->xq_in.ensure(qbytes));
       HIP_TRY(hipMemcpyAsync(w->xq_in.p, queries, qbytes, hipMemcpyHostToDevice, nullptr));
     }
@@ -714,7 +732,7 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
     }
     const uint32_t *d_foq = fs ? w->afoq.p : nullptr, *d_order = fs ? w->xorder.p : nullptr;
     s = qfmt == ROWS_F32      ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
-        : qfmt == kQueriesF16 ? exact_f16q_dev(ix, fs, w->xq_in.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr)
+        : half_queries(qfmt) ? exact_f16q_dev(ix, fs, w->xq_in.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, qfmt)
                               : exact_q8_dev(ix, fs, w->xq_in.p, qfmt, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr);
     if (s != HS_OK) return s;
     HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, nq * k * 8, hipMemcpyDeviceToHost, nullptr));
@@ -809,6 +827,21 @@ hs_status hs_index_exact_search_f16_dev(hs_index *ix, const hs_filter_set *fs, c
     if (s == HS_OK) s = exact_f16q_use_ok(ix);
     if (s != HS_OK || nq == 0) return s;
     return exact_f16q_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+  });
+}
+// ---- and for bf16 queries over bf16 rows, on the bf16 matrix cores (exact_screen_bf16q.hip) ------------------------------------
+hs_status hs_index_exact_search_bf16(hs_index *ix, const hs_filter_set *fs, const void *queries, size_t nq, size_t k,
+                                     const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, kQueriesBF16, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+}
+hs_status hs_index_exact_search_bf16_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
+                                         const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                         uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+    if (s == HS_OK) s = exact_f16q_use_ok(ix, kQueriesBF16);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_f16q_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream, kQueriesBF16);
   });
 }
 hs_status hs_debug_exact_screen_f16_margin(int metric, size_t dim, float qnorm2, float xnorm2, uint32_t q_subnormals, uint32_t x_subnormals, float *out) {

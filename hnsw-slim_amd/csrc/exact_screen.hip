@@ -13,7 +13,7 @@
 // xs_screen_kernel  a workgroup of 4 waves, a tile of 64 queries, a chunk of rows.  The tile sits in LDS as fp32 in operand layout:
 //                   one 16-byte read gives a lane the query values of four MFMA steps.  Wave (b, p) owns the 32 queries of half b
 //                   and the 32-row units of parity p: one 32 x 32 accumulator block per unit, rows straight from global memory into
-//                   the other operand (16 bytes of fp32, 4 of u8 / i8, 8 of fp16 per lane and four steps, the next load in flight under the
+//                   the other operand (16 bytes of fp32, 4 of u8 / i8, 8 of fp16 / bf16 per lane and four steps, the next load in flight under the
 //                   MFMAs).  The k index may be permuted freely as long as both operands agree, so the narrow copy is read in the
 //                   order it is stored and the tile is staged in that order.  Epilogue per accumulator element: a, e, lo, hi,
 //                   admission as exact_search.hip's, lo <= U_q; the few survivors go through a ballot into the (parity, query)
@@ -119,6 +119,17 @@ template <> struct XsChunk<_Float16> {
   }
   __device__ __forceinline__ float4 wide() const {
     const hs_f2 a = narrow_pair((const _Float16 *)nullptr, w, 0), b = narrow_pair((const _Float16 *)nullptr, w, 1);
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+};
+template <> struct XsChunk<hs_bf16> {
+  uint32_t w[2];
+  __device__ __forceinline__ void load(const hs_bf16 *row, uint32_t h, uint32_t cc) {
+    const uint2 v = reinterpret_cast<const uint2 *>(row)[2 * cc + h];
+    w[0] = v.x; w[1] = v.y;
+  }
+  __device__ __forceinline__ float4 wide() const {
+    const hs_f2 a = bf16_pair(w[0]), b = bf16_pair(w[1]);
     return make_float4(a.x, a.y, b.x, b.y);
   }
 };
@@ -302,6 +313,11 @@ __global__ void __launch_bounds__(256) xs_screen_kernel_i8(const XsScan a) {
   xs_screen_body<METRIC, int8_t, NU>(a, smem);
 }
 template <int METRIC, int NU>
+__global__ void __launch_bounds__(256) xs_screen_kernel_bf16(const XsScan a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  xs_screen_body<METRIC, hs_bf16, NU>(a, smem);
+}
+template <int METRIC, int NU>
 __global__ void __launch_bounds__(256) xs_screen_kernel_f16(const XsScan a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   xs_screen_body<METRIC, _Float16, NU>(a, smem);
@@ -483,6 +499,11 @@ __global__ void __launch_bounds__(64) xs_rerank_kernel_i8(const XsRerank a) {
   xs_rerank_body<METRIC, int8_t>(a, reinterpret_cast<float *>(smem));
 }
 template <int METRIC>
+__global__ void __launch_bounds__(64) xs_rerank_kernel_bf16(const XsRerank a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  xs_rerank_body<METRIC, hs_bf16>(a, reinterpret_cast<float *>(smem));
+}
+template <int METRIC>
 __global__ void __launch_bounds__(64) xs_rerank_kernel_f16(const XsRerank a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   xs_rerank_body<METRIC, _Float16>(a, reinterpret_cast<float *>(smem));
@@ -511,7 +532,7 @@ size_t xs_plan(uint32_t n, uint32_t nq, uint32_t k, uint32_t *grid_x, uint32_t *
   return xs_hdr_offset(nq, gx * 2, xs_cap(k)) + (size_t)nq * gx * 2 * sizeof(uint32_t);
 }
 const char *xs_kernel_name(int fmt) {
-  return fmt == ROWS_U8 ? "hs::xs_screen_kernel_u8" : fmt == ROWS_I8 ? "hs::xs_screen_kernel_i8" : fmt == ROWS_F16 ? "hs::xs_screen_kernel_f16" : "hs::xs_screen_kernel";
+  return fmt == ROWS_U8 ? "hs::xs_screen_kernel_u8" : fmt == ROWS_I8 ? "hs::xs_screen_kernel_i8" : fmt == ROWS_BF16 ? "hs::xs_screen_kernel_bf16" : fmt == ROWS_F16 ? "hs::xs_screen_kernel_f16" : "hs::xs_screen_kernel";
 }
 
 hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int fmt, float *xnorm2, hipStream_t stream) {
@@ -521,6 +542,7 @@ hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int f
   const dim3 g((ix.n + 15) / 16);
   if (fmt == ROWS_U8) hipLaunchKernelGGL(xs_norms_kernel<uint8_t>, g, dim3(256), 0, stream, static_cast<const uint8_t *>(rows), ix.n, ix.dim, xnorm2);
   else if (fmt == ROWS_I8) hipLaunchKernelGGL(xs_norms_kernel<int8_t>, g, dim3(256), 0, stream, static_cast<const int8_t *>(rows), ix.n, ix.dim, xnorm2);
+  else if (fmt == ROWS_BF16) hipLaunchKernelGGL(xs_norms_kernel<hs_bf16>, g, dim3(256), 0, stream, static_cast<const hs_bf16 *>(rows), ix.n, ix.dim, xnorm2);
   else if (fmt == ROWS_F16) hipLaunchKernelGGL(xs_norms_kernel<_Float16>, g, dim3(256), 0, stream, static_cast<const _Float16 *>(rows), ix.n, ix.dim, xnorm2);
   else hipLaunchKernelGGL(xs_norms_kernel<float>, g, dim3(256), 0, stream, static_cast<const float *>(rows), ix.n, ix.dim, xnorm2);
   return hipGetLastError();
@@ -542,6 +564,7 @@ hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, co
 #define HS_XS_PICK(NU)                                                                                                       \
   screen = fmt == ROWS_U8    ? (l2 ? xs_screen_kernel_u8<METRIC_L2, NU> : xs_screen_kernel_u8<METRIC_IP, NU>)                  \
            : fmt == ROWS_I8  ? (l2 ? xs_screen_kernel_i8<METRIC_L2, NU> : xs_screen_kernel_i8<METRIC_IP, NU>)                  \
+           : fmt == ROWS_BF16 ? (l2 ? xs_screen_kernel_bf16<METRIC_L2, NU> : xs_screen_kernel_bf16<METRIC_IP, NU>)             \
            : fmt == ROWS_F16 ? (l2 ? xs_screen_kernel_f16<METRIC_L2, NU> : xs_screen_kernel_f16<METRIC_IP, NU>)                \
                              : (l2 ? xs_screen_kernel<METRIC_L2, NU> : xs_screen_kernel<METRIC_IP, NU>)
   if (slice >= dim) HS_XS_PICK(1);
@@ -574,6 +597,7 @@ hipError_t launch_exact_screen_finish(const DevIndex &ix, const void *rows, int 
   hipError_t e;
   void (*rerank)(const XsRerank) = fmt == ROWS_U8    ? (l2 ? xs_rerank_kernel_u8<METRIC_L2> : xs_rerank_kernel_u8<METRIC_IP>)
                                    : fmt == ROWS_I8  ? (l2 ? xs_rerank_kernel_i8<METRIC_L2> : xs_rerank_kernel_i8<METRIC_IP>)
+                                   : fmt == ROWS_BF16 ? (l2 ? xs_rerank_kernel_bf16<METRIC_L2> : xs_rerank_kernel_bf16<METRIC_IP>)
                                    : fmt == ROWS_F16 ? (l2 ? xs_rerank_kernel_f16<METRIC_L2> : xs_rerank_kernel_f16<METRIC_IP>)
                                                      : (l2 ? xs_rerank_kernel<METRIC_L2> : xs_rerank_kernel<METRIC_IP>);
   XsRerank ra{};

@@ -33,7 +33,27 @@
 
 namespace hs {
 
+// What the element type decides, all of it.  exact_screen_bf16q.hip compiles this file once more with HS_XH_BF16 set, for bf16 queries
+// over bf16 rows, under names of its own (xb_*); without the macro every line below expands to what it was.
+#if !defined(HS_XH_BF16)
 typedef _Float16 xh_h8 __attribute__((ext_vector_type(8)));
+#define XH_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
+#define XH_ROWS ROWS_F16
+#define XH_KERNEL_NAME "hs::xh_screen_kernel"
+#define XH_SUBNORMALS 1   // elements the pipeline may flush enter the margin by their count (exact_screen_f16_margin)
+__device__ __forceinline__ float xh_wide(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+#define XH_MARGIN(ip, dim, qn2, xn2, mq, mx) exact_screen_f16_margin(ip, dim, qn2, xn2, mq, mx)
+#define XH_QUERY_TO_FULL_TEST(ip, qn2) false
+#else
+typedef __bf16 xh_h8 __attribute__((ext_vector_type(8)));
+#define XH_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
+#define XH_ROWS ROWS_BF16
+#define XH_KERNEL_NAME "hs::xb_screen_kernel"
+#define XH_SUBNORMALS 0   // exact_screen_margin covers them as it stands (exact_screen_margin.hpp, "The bf16 screen"): nothing is counted
+__device__ __forceinline__ float xh_wide(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+#define XH_MARGIN(ip, dim, qn2, xn2, mq, mx) exact_screen_margin(ip, dim, qn2, xn2)
+#define XH_QUERY_TO_FULL_TEST(ip, qn2) exact_screen_bf16_pre_skip(ip, qn2)
+#endif
 typedef float xh_f16v __attribute__((ext_vector_type(16)));
 
 static constexpr uint32_t kXhWhole = 256;   // a tile up to this many positions (32 KiB) is staged once, where it fits beside the lists
@@ -43,7 +63,7 @@ static constexpr int kXhSliceUnits = 2;     // units a wave carries per slice (N
 // a nonzero half of magnitude below 2^-14
 __device__ __forceinline__ uint32_t xh_is_sub(uint16_t bits) {
   const uint32_t m = bits & 0x7FFFu;
-  return m != 0u && m < 0x0400u;
+  return XH_SUBNORMALS && m != 0u && m < 0x0400u;
 }
 
 // ---- per row and per query ----------------------------------------------------------------------------------------------------
@@ -56,7 +76,7 @@ __global__ void __launch_bounds__(256) xh_rowinfo_kernel(const uint16_t *rows, u
     const uint16_t *x = rows + (size_t)r * dim;
     for (uint32_t i = l; i < dim; i += 16) {
       const uint16_t b = x[i];
-      const float e = (float)__builtin_bit_cast(_Float16, b);
+      const float e = xh_wide(b);
       s = __builtin_fmaf(e, e, s);
       c += xh_is_sub(b);
     }
@@ -71,7 +91,7 @@ __global__ void __launch_bounds__(256) xh_rowinfo_kernel(const uint16_t *rows, u
 
 __global__ void __launch_bounds__(256) xh_widen_kernel(const uint16_t *src, size_t count, float *dst) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < count) dst[i] = (float)__builtin_bit_cast(_Float16, src[i]);
+  if (i < count) dst[i] = xh_wide(src[i]);
 }
 
 // One wave per query, four queries per workgroup.
@@ -84,12 +104,12 @@ __global__ void __launch_bounds__(256) xh_pack_kernel(const uint16_t *q, uint32_
     const uint16_t b = src[narrow_elem(p, dim)];   // what slot p of a narrow row holds
     packed[(size_t)qi * dim + p] = b;
     c += xh_is_sub(b);
-    wide[(size_t)qi * dim + p] = (float)__builtin_bit_cast(_Float16, src[p]);
+    wide[(size_t)qi * dim + p] = xh_wide(src[p]);
   }
   // the norm over the slot order, 16 lanes as xs_norms_kernel (each quarter of the wave forms the same sum)
   float s = 0.f;
   for (uint32_t i = lane & 15u; i < dim; i += 16) {
-    const float e = (float)__builtin_bit_cast(_Float16, src[narrow_elem(i, dim)]);
+    const float e = xh_wide(src[narrow_elem(i, dim)]);
     s = __builtin_fmaf(e, e, s);
   }
 #pragma unroll
@@ -129,7 +149,7 @@ __device__ __forceinline__ void xh_steps(xh_f16v &acc, const unsigned char *x, u
     else if (xnext) xh_load(nxt, xnext, nnext);
 #pragma unroll
     for (int i = 0; i < 4; i++)
-      if (t0 + i < nsteps) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qA[(size_t)(t0 + i) * 2 * kXsTile], cur.v[i], acc, 0, 0, 0);
+      if (t0 + i < nsteps) acc = XH_MFMA(qA[(size_t)(t0 + i) * 2 * kXsTile], cur.v[i], acc, 0, 0, 0);
     cur = nxt;
   }
 }
@@ -227,7 +247,9 @@ __device__ __forceinline__ void xh_screen_body(const XhScan &a, unsigned char *s
     XhInfo ri{0.f, 0u};
     if (row < a.n) ri = a.rinfo[row];
     const float xrow = exact_screen_f16_pre_row(IP, dim, ri.norm);
-    const bool full = ri.sub != 0u;   // (a row's norm is finite: its halves are)
+    // (fp16: a row's norm is finite, its halves are.  bf16: it may be huge or +inf, and the row still takes the pre-test, which stays
+    //  sound -- exact_screen_margin.hpp, "Rows of huge norm")
+    const bool full = XH_SUBNORMALS && ri.sub != 0u;
 #pragma unroll
     for (int v = 0; v < 16; v++) {
       const uint32_t tl = 8u * (v >> 2) + 4u * h + (v & 3), li = lbase + tl;
@@ -239,7 +261,7 @@ __device__ __forceinline__ void xh_screen_body(const XhScan &a, unsigned char *s
       // the full test: the interval of the pair, lo <= U
       const float qq = qn[32 * b + tl];
       const float av = !IP ? (qq + ri.norm) - 2.f * dot : 1.f - dot;
-      const float e = exact_screen_f16_margin(IP, dim, qq, ri.norm, qsub[32 * b + tl], ri.sub);
+      const float e = XH_MARGIN(IP, dim, qq, ri.norm, qsub[32 * b + tl], ri.sub);
       const float lo = av - e, hi = av + e;
       const bool fin = (lo - lo == 0.f) && (hi - hi == 0.f);
       const bool adm = pass && slot_f[32 * b + tl] != kXsNoSlot;
@@ -254,7 +276,7 @@ __device__ __forceinline__ void xh_screen_body(const XhScan &a, unsigned char *s
           const uint32_t sl = 8u * (v >> 2) + 4u * ((uint32_t)l >> 5) + (v & 3), lj_i = lbase + sl, s = 32 * b + sl;
           xs_insert(lists + (size_t)lj_i * cap, sizes + lj_i, ub + lj_i, lflag + lj_i, k, cap, hj, lj, base + ((uint32_t)l & 31u));
           const float qs = qn[s];
-          const bool qfull = qsub[s] != 0u || !(qs - qs == 0.f);
+          const bool qfull = (XH_SUBNORMALS && qsub[s] != 0u) || !(qs - qs == 0.f) || XH_QUERY_TO_FULL_TEST(IP, qs);
           thr[lj_i] = qfull ? INFINITY : exact_screen_f16_pre_bound(IP, dim, ub[lj_i], qsh[s]);
         }
         wave_sync();
@@ -351,13 +373,13 @@ __global__ void __launch_bounds__(256) xh_screen_kernel(const XhScan a) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-bool xh_supported(int fmt, uint32_t dim, uint32_t k) { return fmt == ROWS_F16 && dim != 0 && (dim & 15u) == 0 && dim <= 4096 && k >= 1 && k <= 64; }
+bool xh_supported(int fmt, uint32_t dim, uint32_t k) { return fmt == XH_ROWS && dim != 0 && (dim & 15u) == 0 && dim <= 4096 && k >= 1 && k <= 64; }
 static size_t xh_lds_for(uint32_t slice, uint32_t k) {
   return (size_t)kXsTile * slice * 2 + 5 * kXsTile * 4 + 4 * 2 * kXsTile * 4 + (size_t)2 * kXsTile * xs_cap(k) * sizeof(XsCand);
 }
 uint32_t xh_slice(uint32_t dim, uint32_t k) { return dim <= kXhWhole && xh_lds_for(dim, k) <= 160 * 1024 ? dim : kXhSlice; }
 size_t xh_screen_lds_bytes(uint32_t dim, uint32_t k) { return xh_lds_for(xh_slice(dim, k), k); }
-const char *xh_kernel_name() { return "hs::xh_screen_kernel"; }
+const char *xh_kernel_name() { return XH_KERNEL_NAME; }
 
 hipError_t launch_exact_f16q_rowinfo(const DevIndex &ix, const void *rows, XhInfo *rinfo, hipStream_t stream) {
   if (!ix.n) return hipSuccess;
@@ -374,7 +396,7 @@ hipError_t launch_exact_f16q_widen(const void *src, size_t count, float *dst, hi
 
 hipError_t launch_exact_screen_f16q(const DevIndex &ix, const void *rows, const ScreenArgs &a, const XhArgs &q, const FilterArgs *f, hipStream_t stream) {
   const uint32_t dim = ix.dim, nq = a.x.nq, k = a.x.k;
-  if (!xh_supported(ROWS_F16, dim, k) || nq == 0 || a.x.queries != q.wide) return hipErrorInvalidValue;
+  if (!xh_supported(XH_ROWS, dim, k) || nq == 0 || a.x.queries != q.wide) return hipErrorInvalidValue;
   if (!rows && ix.n) return hipErrorInvalidDevicePointer;
   const bool l2 = ix.metric == METRIC_L2;
   hipError_t e;
@@ -398,7 +420,7 @@ hipError_t launch_exact_screen_f16q(const DevIndex &ix, const void *rows, const 
   sa.n = ix.n; sa.dim = dim; sa.nq = nq; sa.k = k; sa.cap = xs_cap(k); sa.rows_per_block = a.rows_per_block; sa.slice = slice;
   hipLaunchKernelGGL(screen, dim3(a.grid_x, (nq + kXsTile - 1) / kXsTile), dim3(256), lds, stream, sa);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return launch_exact_screen_finish(ix, rows, ROWS_F16, a, f, stream);
+  return launch_exact_screen_finish(ix, rows, XH_ROWS, a, f, stream);
 }
 
 }  // namespace hs

@@ -35,4 +35,14 @@ hipError_t launch_exact_f16q_widen(const void *src, size_t count, float *dst, hi
 // Pack, screen, re-rank, fallback of one group (geometry: xs_plan); all enqueued, nothing read back.
 hipError_t launch_exact_screen_f16q(const DevIndex &ix, const void *rows, const ScreenArgs &a, const XhArgs &q, const FilterArgs *f, hipStream_t stream);
 
+// The same five for bf16 queries over bf16 rows (ROWS_BF16; exact_screen_bf16q.hip, DESIGN.md 4v: v_mfma_f32_32x32x16_bf16).  XhArgs
+// and XhInfo serve both: `queries` and `packed` are then bf16 words, and XhInfo.sub is zero (the bf16 margin counts nothing).
+bool xb_supported(int fmt, uint32_t dim, uint32_t k);
+uint32_t xb_slice(uint32_t dim, uint32_t k);
+size_t xb_screen_lds_bytes(uint32_t dim, uint32_t k);
+const char *xb_kernel_name();
+hipError_t launch_exact_bf16q_rowinfo(const DevIndex &ix, const void *rows, XhInfo *rinfo, hipStream_t stream);
+hipError_t launch_exact_bf16q_widen(const void *src, size_t count, float *dst, hipStream_t stream);
+hipError_t launch_exact_screen_bf16q(const DevIndex &ix, const void *rows, const ScreenArgs &a, const XhArgs &q, const FilterArgs *f, hipStream_t stream);
+
 }  // namespace hs

@@ -132,4 +132,45 @@ HS_HD float exact_screen_f16_pre_bound(int metric_ip, uint32_t dim, float U, flo
   return exact_screen_f16_up(U - share);
 }
 
+// The bf16 screen of exact_screen_bf16q.hip: rows and queries are bf16 values -- fp32 values whose low 16 bits are zero
+// -- the dot product p comes from v_mfma_f32_32x32x16_bf16, the norms from fp32 sums of the widened values, a is formed as above.  Its
+// margin is exact_screen_margin itself; there is no function of its own, and the argument is this.
+// Rounding.  A product of two bf16 values has 8 x 8 = 16 significand bits, so it is exact in fp32 wherever it does not underflow, and the
+// fp16 screen's accounting holds word for word under the same premise (each addition of the pipeline errs by at most one ulp, in any
+// order):  L2 |a - r| <= (5 d + 8) u S,  IP (3 d + 3) u (P + 1),  with the same factors to spare and the same (d + 9) u of them spent on
+// S, P, e, lo and hi being formed in fp32.  No overflow where e is finite: S <= 2^125 resp. P <= 2^125 bound every product and, with the
+// additions' error, every partial sum below 2^126.
+// Underflow.  This is where bf16 is not fp16: the exponents are fp32's, so a product may fall below 2^-126, and a nonzero input may lie
+// below 2^-126 (the bf16 subnormals k 2^-133) and be flushed to zero by the pipeline.  Whether any of that is flushed is not established,
+// so every case is charged its worst absolute error, added to the relative bounds above:
+//   a product below 2^-126, rounded to a subnormal or flushed          < 2^-126 per position, d 2^-126 in p
+//   a sum of the pipeline that lands below 2^-126 and is flushed       < 2^-126 per addition (unflushed it is exact), d 2^-126 in p
+//   an input below 2^-126 read as zero                                 its product, < 2^-126 |other_i|; over a vector, by
+//                                                                      Cauchy-Schwarz, < 2^-126 sqrt(d) (|q| + |x|) in p
+//   the squares of the two norms and the recipe's own terms            < 2^-126 each, 3 d 2^-126 together (already 4r's)
+// With sqrt(d) <= 64 and t <= 1 + t^2, |q| + |x| <= 2 + S.  L2 doubles p:
+//   extra(L2) <= 7 d 2^-126 + 2^-125 sqrt(d) (2 + S) <= (7 d + 4 sqrt(d)) 2^-126 + 2^-119 S <= 11 d 2^-126 + 2^-95 u S.
+// The first part is below (d + 8) 2^-120 = 64 (d + 8) 2^-126, the `tiny` term of exact_screen_margin; the second is 2^-95 of one u S
+// where more than 90 u S are spare (at d = 16; more above).  IP: e is finite only for finite norms, so |q|, |x| < 2^64 and
+//   extra(IP) <= 4 d 2^-126 + 2^-126 sqrt(d) 2^65 <= (d + 8) 2^-120 + 2^-55,
+// and 2^-55 is 2^-31 of one u (P + 1), P + 1 >= 1, where more than 40 u (P + 1) are spare.  So the expression of exact_screen_margin --
+// (d + 8) 2^-120 included, nothing added -- bounds |a - r| for every (S, P) at which it is finite.  Overflow needs no term: S or P above
+// 2^125 gives +inf above and the query falls back, as does a query that holds NaN or +-inf (its norm is not finite).
+// The pre-test carries over, with one guard.  Its proof is about float arithmetic on the very p the full test uses -- lo <= U implies
+// pre <= T whatever p's error -- and uses of the data only |p| <= 1.01 |q| |x|, so that the roundings of a stay relative to 2.1 S resp.
+// 1.01 (P' + 1).  Here |p| <= 1.01 |q| |x| + extra.  IP: extra <= 2^-55 beside P' + 1 >= 1, far inside the 4 u (P' + 1) between kI' and
+// kI.  L2: extra <= 2^-118 + 2^-119 S is small beside S only while S is not itself tiny, so a query with qn2 < 2^-40 skips the pre-test
+// (every pair of it meets the full test); with S >= qn2 >= 2^-40, extra <= 2^-77 S, far inside the 7 u S between w and 1 - kL.  Products
+// of the pre-test's own floats that underflow (xn2 w for a tiny row) err by at most 2^-149, inside the 2 tiny its row share gives away.
+// Rows of huge norm.  The pre-test above is stated for finite norms, and a query whose norm is not finite takes the full test; a bf16
+// ROW, though, may hold 2^64 and more, so xn2 may exceed 2^125 or be +inf while the row still takes the pre-test (nothing is counted per
+// row).  The full test of such a pair has e = +inf, sets the fallback flag and admits nothing, so dropping the pair is right only if
+// the flag is not needed -- that is, if the pair's true value r is above U, U finite.  L2: xlo = fl(xn2 w - 4 tiny) is +inf or at least
+// 2^124, pre = fl(xlo - 2 p) is +inf, huge, or NaN (p = +-inf or NaN); NaN passes, and pre > T happens only for finite T, where the real
+// inequality of the proof (lo <= U implies xlo - 2 p <= T, with the real-valued lo = r - e' for any e' the relative bounds give) still
+// reads r > U: the row is farther than the k-th upper bound by the same argument as for finite norms, overflow of xn2 to +inf only
+// raising xlo.  IP: g <= 0 and sx = +inf or huge give pre = -inf, NaN or a value below -kI P' - p, so !(pre > T) holds and the pair
+// passes to the full test, which flags the query.  Either way no pair is dropped whose full test would have changed the answer.
+HS_HD bool exact_screen_bf16_pre_skip(int metric_ip, float qn2) { return !metric_ip && qn2 < 9.0949470e-13f; }   // 2^-40
+
 }  // namespace hs

@@ -142,6 +142,15 @@ __device__ __forceinline__ float flat_dist8(const ROW *vec, uint32_t dim, const 
       if constexpr ((NDW & 1) != 0) dw[NDW - 1] = cp[NDW - 1];
 #pragma unroll
       for (int i = 0; i < D16; i++) {
+        // bf16: the widening is integer arithmetic (narrow_load.hpp), which the compiler sinks with the FMAs below the last barrier --
+        // sixty query pairs live at once, 176 .. 276 B of scratch per lane for IP.  An empty statement that takes the accumulator in
+        // and out ties a group's arithmetic in front of the next barrier: no instruction, no scratch, 136 .. 156 VGPRs.
+        if constexpr (std::is_same<ROW, hs_bf16>::value)
+          if (D16 > 8 && i % 8 == 0 && i > 0) {
+            float ax = acc.x, ay = acc.y;
+            asm volatile("" : "+v"(ax), "+v"(ay));
+            acc = hs_f2{ax, ay};
+          }
         if (D16 > 8 && i % 8 == 0) __builtin_amdgcn_sched_barrier(0);   // (as for the fp32 rows: the query's LDS reads stay near their use)
         step(qq[i * 8], narrow_pair((const ROW *)nullptr, dw, i));
       }

@@ -44,6 +44,9 @@ __device__ inline uint32_t pack2_f16(const float *x, uint32_t o, uint32_t dim) {
   }
   return w;
 }
+__device__ inline uint32_t pack2_bf16(const float *x, uint32_t o, uint32_t dim) {
+  return (uint32_t)narrow_cast<hs_bf16>(x[narrow_source(o, dim)]).w | ((uint32_t)narrow_cast<hs_bf16>(x[narrow_source(o + 1, dim)]).w << 16);
+}
 
 __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -76,7 +79,8 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
         else for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_i8(x, 4 * w, a.dim);
       } else {
         uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<_Float16 *>(a.narrow) + (size_t)id * a.dim);
-        for (uint32_t w = lane; w < a.dim / 2; w += 64) dst[w] = pack2_f16(x, 2 * w, a.dim);
+        if (a.fmt == ROWS_F16) for (uint32_t w = lane; w < a.dim / 2; w += 64) dst[w] = pack2_f16(x, 2 * w, a.dim);
+        else for (uint32_t w = lane; w < a.dim / 2; w += 64) dst[w] = pack2_bf16(x, 2 * w, a.dim);
       }
     }
   }
@@ -90,7 +94,7 @@ hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream) {
   if (a.nrec == 0) return hipSuccess;
   if (!a.stage || !a.labels || !a.deleted || a.first_row > a.nrec) return hipErrorInvalidValue;
   if (a.tile0 && (a.stride == 0 || (a.stride & 15u) != 0 || a.stride > 64)) return hipErrorInvalidValue;
-  if (a.narrow && ((a.dim & 15u) != 0 || (a.fmt != ROWS_U8 && a.fmt != ROWS_I8 && a.fmt != ROWS_F16))) return hipErrorInvalidValue;
+  if (a.narrow && ((a.dim & 15u) != 0 || !is_narrow_format(a.fmt))) return hipErrorInvalidValue;
   const uint32_t per = kUpdateBlock / 64;
   hipLaunchKernelGGL(index_update_kernel, dim3((a.nrec + per - 1) / per), dim3(kUpdateBlock), 0, stream, a);
   return hipGetLastError();

@@ -1,4 +1,4 @@
-// narrow_load.hpp -- device-side reads of an index's narrow (u8 / i8 / fp16) row copy: which rows a kernel instantiation reads, and
+// narrow_load.hpp -- device-side reads of an index's narrow (u8 / i8 / fp16 / bf16) row copy: which rows a kernel instantiation reads, and
 // the exact widening of stored element pairs.  Shared by flat_search.hip (8 lanes per row) and beam_search.hip (4 lanes per row).
 // Layout and conversion: narrow_rows.hpp / narrow_rows.hip.
 #pragma once
@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "engine.hpp"
+#include "narrow_rows.hpp"
 #include "wave_util.hpp"
 
 namespace hs {
@@ -18,7 +19,7 @@ typedef uint32_t hs_u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 typedef _Float16 hs_h2 __attribute__((ext_vector_type(2)));
 
 // The rows a strict / fast kernel instantiation reads.  ROW = float: the resident fp32 rows, taken from the DevIndex (the struct is
-// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / int8_t / _Float16: the base of the
+// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / int8_t / _Float16 / hs_bf16: the base of the
 // narrow copy, a kernel argument of its own (DevIndex keeps its layout).
 template <typename ROW> struct RowSrc { const ROW *p; };
 template <> struct RowSrc<float> {};
@@ -43,6 +44,13 @@ __device__ __forceinline__ hs_f2 narrow_pair(const int8_t *, const uint32_t *dw,
   const uint32_t w = dw[i >> 1];
   return (i & 1) ? hs_f2{(float)(int)(int8_t)(w >> 16), (float)((int)w >> 24)} : i8_pair(w);
 }
+// A bf16 pair is one dword w, the low element in its low half word: the fp32 values are w << 16 and w & 0xFFFF0000, reinterpreted --
+// one VALU instruction per element (v_lshlrev_b32, v_and_b32) and no v_cvt.  Exact by construction: a bf16 element IS the upper half of
+// an fp32 value whose lower half is zero (narrow_rows.hpp), so the register holds the very bit pattern the fp32 row holds.  No
+// conversion runs, hence no rounding and no denormal mode: a subnormal (below 2^-126) and -0 arrive as the fp32 kernel reads them, and
+// what the recipe then does with them is the fp32 kernel's own arithmetic.
+__device__ __forceinline__ hs_f2 bf16_pair(uint32_t w) { return hs_f2{__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u)}; }
+__device__ __forceinline__ hs_f2 narrow_pair(const hs_bf16 *, const uint32_t *dw, int i) { return bf16_pair(dw[i]); }
 __device__ __forceinline__ hs_f2 narrow_pair_at(const uint8_t *chunk, uint32_t i) {
   const uint32_t w = *reinterpret_cast<const unsigned short *>(chunk + 2 * i);
   return hs_f2{(float)(w & 0xFFu), (float)(w >> 8)};
@@ -54,10 +62,13 @@ __device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t 
   const hs_h2 h = *reinterpret_cast<const hs_h2 *>(chunk + 2 * i);
   return hs_f2{(float)h.x, (float)h.y};
 }
+__device__ __forceinline__ hs_f2 narrow_pair_at(const hs_bf16 *chunk, uint32_t i) {
+  return bf16_pair(*reinterpret_cast<const uint32_t *>(chunk + 2 * i));
+}
 
 // One round of a lane's chunk at a runtime dim: up to eight consecutive element pairs, held as they were loaded and widened on use.
 // load(c, nb, nw): pairs [0, nw) -- nw = 0, 4 or 8, at most nb, and only where c is dword aligned -- arrive in one 16-byte load
-// (u8 / i8: eight pairs; fp16: four, so two loads for eight) or one 8-byte load (u8 / i8: four pairs); pairs [nw, nb) in one load each
+// (u8 / i8: eight pairs; fp16 / bf16: four, so two loads for eight) or one 8-byte load (u8 / i8: four pairs); pairs [nw, nb) in one load each
 // (2 / 4 bytes).  Nothing beyond pair nb is touched.  pair(i, nw) widens pair i < nb, with the nw that load() was given.
 template <typename ROW> struct NarrowRound;
 template <> struct NarrowRound<uint8_t> {
@@ -114,6 +125,13 @@ template <> struct NarrowRound<_Float16> {
     const hs_h2 h = __builtin_bit_cast(hs_h2, w[i]);
     return hs_f2{(float)h.x, (float)h.y};
   }
+};
+// bf16: the half words arrive as the fp16 round's do (the same 16- and 4-byte loads); only the widening differs
+template <> struct NarrowRound<hs_bf16> : NarrowRound<_Float16> {
+  __device__ __forceinline__ void load(const hs_bf16 *c, uint32_t nb, uint32_t nw) {
+    NarrowRound<_Float16>::load(reinterpret_cast<const _Float16 *>(c), nb, nw);
+  }
+  __device__ __forceinline__ hs_f2 pair(uint32_t i, uint32_t) const { return bf16_pair(w[i]); }
 };
 
 }  // namespace hs
