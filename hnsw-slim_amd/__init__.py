@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("HS_LIB", os.path.join(_HERE, "libhnsw_slim_amd.so")) 
 HS_KIND_HNSW, HS_KIND_SLIM, HS_KIND_SLIMQ = 0, 1, 2
 HS_METRIC_L2, HS_METRIC_IP = 0, 1
 HS_MODE_SLIM_IDS, HS_MODE_PQ = 0, 1
-HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8, HS_ROWS_I8, HS_ROWS_BF16 = 0, 1, 2, 3, 4   # hs_row_format (narrow rows: Index.set_row_format)
+HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8, HS_ROWS_I8, HS_ROWS_BF16, HS_ROWS_F8 = 0, 1, 2, 3, 4, 5   # hs_row_format (narrow rows: Index.set_row_format)
 HS_OK, HS_ERR_IO, HS_ERR_CORRUPT, HS_ERR_NOMEM, HS_ERR_INVALID, HS_ERR_UNSUPPORTED, HS_ERR_DEVICE, HS_ERR_CAPACITY = range(8)
 
 EXPORTS = [
@@ -36,7 +36,7 @@ EXPORTS = [
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
     "hs_index_exact_search_f16", "hs_index_exact_search_f16_dev", "hs_debug_exact_screen_f16_margin",
-    "hs_index_exact_search_bf16", "hs_index_exact_search_bf16_dev",
+    "hs_index_exact_search_bf16", "hs_index_exact_search_bf16_dev", "hs_index_exact_search_f8", "hs_index_exact_search_f8_dev",
     "hs_index_add_points", "hs_index_seed_levels", "hs_index_mark_deleted", "hs_index_save", "hs_index_get_row", "hs_index_capacity",
     "hs_index_deleted_count", "hs_hnsw_resume",
     "hs_index_set_replace_deleted", "hs_index_upsert_points", "hs_index_resize", "hs_hnsw_replay",
@@ -231,6 +231,8 @@ def lib():
     L.hs_index_exact_search_f16_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_search_bf16.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_bf16_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_exact_search_f8.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_f8_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_debug_exact_screen_f16_margin.argtypes = [ci, sz, ctypes.c_float, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, vp]
     L.hs_index_add_points.argtypes = [vp, vp, vp, sz, ci]
     L.hs_index_seed_levels.argtypes = [vp, sz, sz]
@@ -607,7 +609,7 @@ def slim_convert_diff_files(old_slim_path, hnsw_path, out_slim_path, dim, metric
 def rows_representable(rows, fmt):
     """hs_rows_representable (host only): None when every value of `rows` (n x dim fp32) is exactly representable in the row
     format `fmt` (HS_ROWS_U8: integers 0..255; HS_ROWS_I8: integers -128..127; HS_ROWS_F16: finite fp16 values;
-    HS_ROWS_BF16: finite fp32 values whose low 16 bits are zero), else the index of the first row that is not."""
+    HS_ROWS_BF16: finite fp32 values whose low 16 bits are zero; HS_ROWS_F8: the 254 finite OCP E4M3 values), else the index of the first row that is not."""
     r = np.ascontiguousarray(rows, np.float32)
     r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
     bad = ctypes.c_uint64(0)
@@ -617,13 +619,13 @@ def rows_representable(rows, fmt):
 
 def rows_to_narrow(rows, fmt, out=None):
     """hs_rows_to_narrow (host only): `rows` (n x dim fp32, dim % 16 == 0) in the row format `fmt` and the lane-major layout of the
-    device copy -- (narrow, first_bad): narrow is n x dim uint8 (HS_ROWS_U8), int8 (HS_ROWS_I8), float16 (HS_ROWS_F16) or uint16
-    bf16 words (HS_ROWS_BF16), first_bad None when every
+    device copy -- (narrow, first_bad): narrow is n x dim uint8 (HS_ROWS_U8), int8 (HS_ROWS_I8), float16 (HS_ROWS_F16), uint16
+    bf16 words (HS_ROWS_BF16) or uint8 E4M3 bytes (HS_ROWS_F8), first_bad None when every
     value is representable, else the first row that is not (nothing is written from there on; `out`, when given, is the array
     that is filled)."""
     r = np.ascontiguousarray(rows, np.float32)
     r = r.reshape(r.shape[0], -1) if r.ndim != 2 else r
-    dt = {HS_ROWS_U8: np.uint8, HS_ROWS_I8: np.int8, HS_ROWS_BF16: np.uint16}.get(int(fmt), np.float16)
+    dt = {HS_ROWS_U8: np.uint8, HS_ROWS_I8: np.int8, HS_ROWS_BF16: np.uint16, HS_ROWS_F8: np.uint8}.get(int(fmt), np.float16)
     if out is None:
         out = np.zeros(r.shape, dt)
     assert out.dtype == dt and out.shape == r.shape and out.flags.c_contiguous
@@ -1245,7 +1247,7 @@ class Index:
 
     @classmethod
     def load_narrow(cls, path, kind, dim, fmt, metric=HS_METRIC_L2, max_elements=0, device=0):
-        """hs_index_load_narrow: the index of `path` with its rows on the device in `fmt` (HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16 / HS_ROWS_BF16) only -- what
+        """hs_index_load_narrow: the index of `path` with its rows on the device in `fmt` (HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16 / HS_ROWS_BF16 / HS_ROWS_F8) only -- what
         Index(path, ...) + set_row_format(fmt) + set_f32_resident(False) gives, without the fp32 array ever being allocated."""
         self = cls.__new__(cls)
         self._h = ctypes.c_void_p()
@@ -1405,7 +1407,7 @@ class Index:
         _check(lib().hs_set_ef(self._h, int(ef)))
 
     def set_row_format(self, fmt):
-        """hs_index_set_row_format: HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16 / HS_ROWS_BF16 build a narrow copy of the rows that the flat kernel then reads
+        """hs_index_set_row_format: HS_ROWS_U8 / HS_ROWS_I8 / HS_ROWS_F16 / HS_ROWS_BF16 / HS_ROWS_F8 build a narrow copy of the rows that the flat kernel then reads
         (HsError HS_ERR_UNSUPPORTED, index unchanged, when a stored value is not exactly representable); HS_ROWS_F32 drops it.
         No answer changes."""
         _check(lib().hs_index_set_row_format(self._h, int(fmt)))
@@ -1615,6 +1617,30 @@ class Index:
         _check(lib().hs_index_exact_search_bf16_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
                                                     None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
                                                     d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_search_f8(self, queries, k, fs=None, filter_of_query=None):
+        """hs_index_exact_search_f8: exact_search's answers for the same queries widened to fp32, bit for bit, for fp8 queries -- a
+        uint8 array of OCP E4M3 bytes -- over an index whose narrow copy is HS_ROWS_F8; the screen runs on the fp8 matrix cores."""
+        q = np.ascontiguousarray(queries)
+        if q.dtype != np.uint8:
+            raise HsError(HS_ERR_INVALID, f"exact_search_f8 takes E4M3 bytes as uint8, not {q.dtype}")
+        nq = q.shape[0]
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        labels, dists, cnt = np.empty((nq, k), np.uint64), np.empty((nq, k), np.float32), np.empty(nq, np.uint32)
+        _check(lib().hs_index_exact_search_f8(self._h, None if fs is None else fs._h, q.ctypes.data, nq, k,
+                                              None if foq is None else foq.ctypes.data, labels.ctypes.data, dists.ctypes.data, cnt.ctypes.data))
+        return dict(labels=labels, dists=dists, cnt=cnt)
+
+    def exact_search_f8_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_f8_dev: exact_search_screened_dev's arguments with a uint8 query tensor of E4M3 bytes; asynchronous,
+        pair with check(stream)."""
+        if str(d_queries.dtype) != "torch.uint8":
+            raise HsError(HS_ERR_INVALID, f"exact_search_f8_dev takes E4M3 bytes as uint8, not {d_queries.dtype}")
+        _check(lib().hs_index_exact_search_f8_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                                  None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                                  d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
 
     def exact_search_f16(self, queries, k, fs=None, filter_of_query=None):
         """hs_index_exact_search_f16: exact_search's answers for the same queries widened to fp32, bit for bit, for float16 queries over

@@ -8,6 +8,7 @@
 #include "exact_screen_engine.hpp"
 #include "exact_screen_margin.hpp"
 #include "exact_screen_f16q_engine.hpp"
+#include "exact_screen_f8q_engine.hpp"
 #include "exact_screen_q8_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
@@ -484,7 +485,7 @@ static hs_status exact_dev(hs_index *ix, const hs_filter_set *fs, const float *d
   const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
   const size_t dim = ix->info.dim;
   ix->last_kernel = screened ? xs_kernel_name(fmt)
-                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_I8 ? "hs::exact_scan_kernel_i8" : fmt == ROWS_BF16 ? "hs::exact_scan_kernel_bf16" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
+                    : (dim & 15) ? "hs::exact_scan_general_kernel" : fmt == ROWS_U8 ? "hs::exact_scan_kernel_u8" : fmt == ROWS_I8 ? "hs::exact_scan_kernel_i8" : fmt == ROWS_BF16 ? "hs::exact_scan_kernel_bf16" : fmt == ROWS_F8 ? "hs::exact_scan_kernel_f8" : fmt == ROWS_F16 ? "hs::exact_scan_kernel_f16" : "hs::exact_scan_kernel";
   const size_t gq = std::min(kExactGroupQueries, nq);
   if (screened) {
     HIP_TRY(w->xs_norms.ensure((size_t)ix->dev.n + gq));
@@ -604,13 +605,16 @@ static hs_status exact_q8_dev(hs_index *ix, const hs_filter_set *fs, const void 
   return HS_OK;
 }
 
-// ---- fp16 queries over fp16 rows (exact_screen_f16q.hip), bf16 queries over bf16 rows (exact_screen_bf16q.hip) ----------------
-// exact_host's codes for "the queries are halves" / "bf16 words": not row formats of the byte-query entry, which keeps refusing both.
-static constexpr int kQueriesF16 = -16, kQueriesBF16 = -17;
-static bool half_queries(int qfmt) { return qfmt == kQueriesF16 || qfmt == kQueriesBF16; }
-// the launch entries of the two objects, which are one source (exact_screen_f16q_engine.hpp)
+// ---- fp16 queries over fp16 rows (exact_screen_f16q.hip), bf16 queries over bf16 rows (exact_screen_bf16q.hip), fp8 queries over
+// fp8 rows (exact_screen_f8q.hip) -------------------------------------------------------------------------------------------------
+// exact_host's codes for "the queries are halves" / "bf16 words" / "E4M3 bytes": not row formats of the byte-query entry, which keeps
+// refusing all three.
+static constexpr int kQueriesF16 = -16, kQueriesBF16 = -17, kQueriesF8 = -8;
+static bool half_queries(int qfmt) { return qfmt == kQueriesF16 || qfmt == kQueriesBF16 || qfmt == kQueriesF8; }
+// the launch entries of the three objects (exact_screen_f16q_engine.hpp, exact_screen_f8q_engine.hpp: one interface)
 struct HalfScreen {
   int rows;
+  size_t width;   // bytes per query element
   const char *refusal;
   decltype(&xh_supported) supported;
   decltype(&xh_kernel_name) kernel_name;
@@ -619,9 +623,10 @@ struct HalfScreen {
   decltype(&launch_exact_screen_f16q) screen;
 };
 static const HalfScreen &half_screen(int qfmt) {
-  static const HalfScreen f16{ROWS_F16, kF16QNoCopyRefusal, xh_supported, xh_kernel_name, launch_exact_f16q_rowinfo, launch_exact_f16q_widen, launch_exact_screen_f16q};
-  static const HalfScreen bf16{ROWS_BF16, kBF16QNoCopyRefusal, xb_supported, xb_kernel_name, launch_exact_bf16q_rowinfo, launch_exact_bf16q_widen, launch_exact_screen_bf16q};
-  return qfmt == kQueriesBF16 ? bf16 : f16;
+  static const HalfScreen f16{ROWS_F16, 2, kF16QNoCopyRefusal, xh_supported, xh_kernel_name, launch_exact_f16q_rowinfo, launch_exact_f16q_widen, launch_exact_screen_f16q};
+  static const HalfScreen bf16{ROWS_BF16, 2, kBF16QNoCopyRefusal, xb_supported, xb_kernel_name, launch_exact_bf16q_rowinfo, launch_exact_bf16q_widen, launch_exact_screen_bf16q};
+  static const HalfScreen f8{ROWS_F8, 1, kF8QNoCopyRefusal, xf_supported, xf_kernel_name, launch_exact_f8q_rowinfo, launch_exact_f8q_widen, launch_exact_screen_f8q};
+  return qfmt == kQueriesBF16 ? bf16 : qfmt == kQueriesF8 ? f8 : f16;
 }
 
 // What the fp16-query entries refuse beyond exact_use_ok.  No index of dim % 16 != 0 can hold a narrow copy (hs_index_set_row_format):
@@ -680,7 +685,7 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
     sa.cand = w->xs_cand.p;
     sa.state = w->xs_state.p; sa.qflag = w->xs_state.p + kXsStateWords; sa.fb_order = sa.qflag + gq;
     XhArgs qa{};
-    qa.queries = static_cast<const uint16_t *>(d_q) + off * dim;
+    qa.queries = static_cast<const unsigned char *>(d_q) + off * dim * hsc.width;
     qa.packed = reinterpret_cast<uint16_t *>(w->xq_packed.p); qa.wide = w->xq_wide.p;
     qa.qinfo = reinterpret_cast<XhInfo *>(w->xq_info.p + row_bytes); qa.rinfo = rinfo;
     HIP_TRY(hsc.screen(ix->dev, rows, sa, qa, fs ? &fa : nullptr, stream));
@@ -690,8 +695,8 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
   return HS_OK;
 }
 
-// qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 / kQueriesBF16 for the
-// fp16- and bf16-query entries (all always screened).
+// qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 / kQueriesBF16 / kQueriesF8 for the
+// fp16-, bf16- and fp8-query entries (all always screened).
 static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *queries, int qfmt, size_t nq, size_t k, const uint32_t *filter_of_query,
                             uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
   return guarded([&] {
@@ -712,7 +717,7 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
       HIP_TRY(w->aq.ensure(nq * dim));
       HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
     } else {
-      const size_t qbytes = nq * dim * (half_queries(qfmt) ? 2 : 1);
+      const size_t qbytes = nq * dim * (half_queries(qfmt) ? half_screen(qfmt).width : 1);
       HIP_TRY(w->xq_in.ensure(qbytes));
       HIP_TRY(hipMemcpyAsync(w->xq_in.p, queries, qbytes, hipMemcpyHostToDevice, nullptr));
     }
@@ -842,6 +847,21 @@ hs_status hs_index_exact_search_bf16_dev(hs_index *ix, const hs_filter_set *fs, 
     if (s == HS_OK) s = exact_f16q_use_ok(ix, kQueriesBF16);
     if (s != HS_OK || nq == 0) return s;
     return exact_f16q_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream, kQueriesBF16);
+  });
+}
+// ---- and for fp8 (E4M3) queries over fp8 rows, on the fp8 matrix cores (exact_screen_f8q.hip) --------------------------------------
+hs_status hs_index_exact_search_f8(hs_index *ix, const hs_filter_set *fs, const void *queries, size_t nq, size_t k,
+                                   const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, kQueriesF8, nq, k, filter_of_query, out_labels64, out_dists, out_counts, true);
+}
+hs_status hs_index_exact_search_f8_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
+                                       const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                       uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
+    if (s == HS_OK) s = exact_f16q_use_ok(ix, kQueriesF8);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_f16q_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream, kQueriesF8);
   });
 }
 hs_status hs_debug_exact_screen_f16_margin(int metric, size_t dim, float qnorm2, float xnorm2, uint32_t q_subnormals, uint32_t x_subnormals, float *out) {

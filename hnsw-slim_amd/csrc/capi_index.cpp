@@ -22,10 +22,11 @@ static size_t first_unfit(const float *x, size_t count) {
 }
 size_t first_unfit(const float *x, size_t count, int fmt) {
   return fmt == ROWS_U8 ? first_unfit<uint8_t>(x, count) : fmt == ROWS_I8 ? first_unfit<int8_t>(x, count)
-         : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : fmt == ROWS_BF16 ? first_unfit<hs_bf16>(x, count) : count;
+         : fmt == ROWS_F16 ? first_unfit<_Float16>(x, count) : fmt == ROWS_BF16 ? first_unfit<hs_bf16>(x, count)
+         : fmt == ROWS_F8 ? first_unfit<hs_f8>(x, count) : count;
 }
 static const char *row_format_name(int fmt) {
-  return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_I8 ? "HS_ROWS_I8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : fmt == ROWS_BF16 ? "HS_ROWS_BF16" : "HS_ROWS_F32";
+  return fmt == ROWS_U8 ? "HS_ROWS_U8" : fmt == ROWS_I8 ? "HS_ROWS_I8" : fmt == ROWS_F16 ? "HS_ROWS_F16" : fmt == ROWS_BF16 ? "HS_ROWS_BF16" : fmt == ROWS_F8 ? "HS_ROWS_F8" : "HS_ROWS_F32";
 }
 std::string unfit_message(size_t row, size_t comp, float v, int fmt) {
   char val[64];
@@ -74,6 +75,7 @@ static size_t rows_to_narrow_host(const float *rows, size_t n, size_t dim, int f
   return fmt == ROWS_U8   ? rows_to_narrow_t<uint8_t>(rows, n, dim, static_cast<uint8_t *>(out))
          : fmt == ROWS_I8 ? rows_to_narrow_t<int8_t>(rows, n, dim, static_cast<int8_t *>(out))
          : fmt == ROWS_BF16 ? rows_to_narrow_t<hs_bf16>(rows, n, dim, static_cast<hs_bf16 *>(out))
+         : fmt == ROWS_F8 ? rows_to_narrow_t<hs_f8>(rows, n, dim, static_cast<hs_f8 *>(out))
                           : rows_to_narrow_t<_Float16>(rows, n, dim, static_cast<_Float16 *>(out));
 }
 // The narrow copy of an index WITHOUT resident fp32 rows, (re)built from host rows: allocated for `cap` rows, converted on the

@@ -129,7 +129,7 @@ struct hs_index {
     DevBuf<uint32_t> xs_state;
     // hs_index_exact_search_q8 (exact_screen_q8.hip): the caller's bytes (host entry), a group's queries in slot order and as fp32
     // (the hand-over: all of them as fp32), and the integers per row and per query of a group; hs_index_exact_search_f16
-    // (exact_screen_f16q.hip) uses the same four for its halves and its norms and subnormal counts, hs_index_exact_search_bf16 for its bf16 words
+    // (exact_screen_f16q.hip) uses the same four for its halves and its norms and subnormal counts, hs_index_exact_search_bf16 for its bf16 words, hs_index_exact_search_f8 for its bytes
     DevBuf<uint8_t> xq_in, xq_packed, xq_info;
     DevBuf<float> xq_wide;
   };
@@ -195,6 +195,9 @@ static constexpr const char *kF16QNoCopyRefusal =
 // hs_index_exact_search_bf16[_dev]: bf16 queries meet bf16 rows.
 static constexpr const char *kBF16QNoCopyRefusal =
     "exact search with bf16 queries refused: the index holds no bf16 copy of its rows (hs_index_set_row_format)";
+// hs_index_exact_search_f8[_dev]: fp8 queries meet fp8 rows.
+static constexpr const char *kF8QNoCopyRefusal =
+    "exact search with fp8 queries refused: the index holds no fp8 copy of its rows (hs_index_set_row_format)";
 
 // ---- the refusals and small helpers more than one entry uses: one text, one definition (error reporting: capi_guard.hpp) ----------
 #pragma GCC visibility push(hidden)

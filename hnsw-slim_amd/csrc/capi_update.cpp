@@ -304,6 +304,7 @@ hs_status hs_index_get_row(hs_index *ix, uint64_t label, float *out) {
       const size_t o = narrow_slot((uint32_t)j, (uint32_t)dim);
       if (ix->row_fmt == ROWS_U8) out[j] = (float)raw[o];
       else if (ix->row_fmt == ROWS_I8) out[j] = (float)(int8_t)raw[o];
+      else if (ix->row_fmt == ROWS_F8) out[j] = (float)hs_f8{raw[o]};
       else if (ix->row_fmt == ROWS_BF16) { hs_bf16 h; memcpy(&h, raw.data() + 2 * o, 2); out[j] = (float)h; }
       else { _Float16 h; memcpy(&h, raw.data() + 2 * o, 2); out[j] = (float)h; }
     }

@@ -123,7 +123,7 @@ hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, 
 
 // ---- launching a search kernel ----------------------------------------------------------------------------------------------
 // launch_search (search_launch.cpp) is the one way in: the kernel family (hs_plan_family) over rows of format row_fmt (ROWS_F32:
-// ix.vec; ROWS_U8 | ROWS_I8 | ROWS_F16 | ROWS_BF16: narrow_rows, the index's copy of ix.vec in the lane-major layout of narrow_rows.hip), metric ix.metric.
+// ix.vec; ROWS_U8 | ROWS_I8 | ROWS_F16 | ROWS_BF16 | ROWS_F8: narrow_rows, the index's copy of ix.vec in the lane-major layout of narrow_rows.hip), metric ix.metric.
 // f != null: the search runs under that filter set -- the !bare_bone branches whether or not the index has delete marks
 // (hnswalg.h:1421, hnswalg_slim.h:1884); strict and fast kernels only.  It launches nothing and returns
 //   hipErrorInvalidDevicePointer  when the row array the kernel would read is null and the index is not empty (an index may drop
@@ -133,7 +133,7 @@ hipError_t flat_heap_ops(const uint32_t *d_ops, uint32_t n_ops, uint2 *d_spill, 
 // Behind it is a table [family][row format][metric] of launchers, one per (family, row format, metric), each defined by the
 // object that holds its kernels (beam_search.hip: strict and fast; flat_search.hip: flat; lean_search.hip: lean), each computing
 // its LDS size from its own layout function and picking the instantiation for the shape.  HS_LAUNCHER names them -- here, where
-// they are defined, and in the table -- with rows = f32 | u8 | i8 | f16 | bf16 and metric = l2 | ip.
+// they are defined, and in the table -- with rows = f32 | u8 | i8 | f16 | bf16 | f8 and metric = l2 | ip.
 using SearchLauncher = hipError_t (*)(const DevIndex &, const SearchArgs &, const void *rows, hipStream_t, const FilterArgs *);
 hipError_t launch_search(int family, int row_fmt, const DevIndex &ix, const SearchArgs &a, const void *narrow_rows, hipStream_t stream,
                          const FilterArgs *f);
@@ -142,10 +142,10 @@ hipError_t launch_search(int family, int row_fmt, const DevIndex &ix, const Sear
 #define HS_LAUNCHERS(family, rows) HS_LAUNCHER(family, rows, l2), HS_LAUNCHER(family, rows, ip)
 std::remove_pointer_t<SearchLauncher> HS_LAUNCHERS(strict, f32), HS_LAUNCHERS(strict, f16), HS_LAUNCHERS(strict, u8), HS_LAUNCHERS(strict, i8),
     HS_LAUNCHERS(fast, f32), HS_LAUNCHERS(fast, f16), HS_LAUNCHERS(fast, u8), HS_LAUNCHERS(fast, i8), HS_LAUNCHERS(flat, f32), HS_LAUNCHERS(flat, f16),
-    HS_LAUNCHERS(flat, u8), HS_LAUNCHERS(flat, i8), HS_LAUNCHERS(strict, bf16), HS_LAUNCHERS(fast, bf16), HS_LAUNCHERS(flat, bf16), HS_LAUNCHERS(lean, f32);
+    HS_LAUNCHERS(flat, u8), HS_LAUNCHERS(flat, i8), HS_LAUNCHERS(strict, bf16), HS_LAUNCHERS(fast, bf16), HS_LAUNCHERS(flat, bf16), HS_LAUNCHERS(strict, f8), HS_LAUNCHERS(fast, f8), HS_LAUNCHERS(flat, f8), HS_LAUNCHERS(lean, f32);
 
-// Narrow rows (narrow_rows.hip): launch_narrow_convert fills rows [row0, row0 + nrows) of the index's u8 / i8 / fp16 / bf16 copy (fmt = ROWS_U8
-// | ROWS_I8 | ROWS_F16 | ROWS_BF16) from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to the smallest row that holds a value the format cannot
+// Narrow rows (narrow_rows.hip): launch_narrow_convert fills rows [row0, row0 + nrows) of the index's u8 / i8 / fp16 / bf16 / fp8 copy (fmt = ROWS_U8
+// | ROWS_I8 | ROWS_F16 | ROWS_BF16 | ROWS_F8) from d_vec and lowers *d_first_bad (preset to 0xFFFFFFFF) to the smallest row that holds a value the format cannot
 // represent.  launch_narrow_widen is the inverse of the conversion: rows [row0, row0 + nrows) of d_vec from the copy (exact).
 hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint32_t row0, uint32_t nrows, uint32_t dim, uint32_t *d_first_bad,
                                  hipStream_t stream);

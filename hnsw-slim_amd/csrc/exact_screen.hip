@@ -13,7 +13,7 @@
 // xs_screen_kernel  a workgroup of 4 waves, a tile of 64 queries, a chunk of rows.  The tile sits in LDS as fp32 in operand layout:
 //                   one 16-byte read gives a lane the query values of four MFMA steps.  Wave (b, p) owns the 32 queries of half b
 //                   and the 32-row units of parity p: one 32 x 32 accumulator block per unit, rows straight from global memory into
-//                   the other operand (16 bytes of fp32, 4 of u8 / i8, 8 of fp16 / bf16 per lane and four steps, the next load in flight under the
+//                   the other operand (16 bytes of fp32, 4 of u8 / i8 / fp8, 8 of fp16 / bf16 per lane and four steps, the next load in flight under the
 //                   MFMAs).  The k index may be permuted freely as long as both operands agree, so the narrow copy is read in the
 //                   order it is stored and the tile is staged in that order.  Epilogue per accumulator element: a, e, lo, hi,
 //                   admission as exact_search.hip's, lo <= U_q; the few survivors go through a ballot into the (parity, query)
@@ -108,6 +108,14 @@ template <> struct XsChunk<int8_t> {
   __device__ __forceinline__ void load(const int8_t *row, uint32_t h, uint32_t cc) { w = reinterpret_cast<const uint32_t *>(row)[2 * cc + h]; }
   __device__ __forceinline__ float4 wide() const {
     const hs_f2 a = narrow_pair((const int8_t *)nullptr, &w, 0), b = narrow_pair((const int8_t *)nullptr, &w, 1);
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+};
+template <> struct XsChunk<hs_f8> {
+  uint32_t w;
+  __device__ __forceinline__ void load(const hs_f8 *row, uint32_t h, uint32_t cc) { w = reinterpret_cast<const uint32_t *>(row)[2 * cc + h]; }
+  __device__ __forceinline__ float4 wide() const {
+    const hs_f2 a = f8_pair(w, false), b = f8_pair(w, true);
     return make_float4(a.x, a.y, b.x, b.y);
   }
 };
@@ -318,6 +326,11 @@ __global__ void __launch_bounds__(256) xs_screen_kernel_bf16(const XsScan a) {
   xs_screen_body<METRIC, hs_bf16, NU>(a, smem);
 }
 template <int METRIC, int NU>
+__global__ void __launch_bounds__(256) xs_screen_kernel_f8(const XsScan a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  xs_screen_body<METRIC, hs_f8, NU>(a, smem);
+}
+template <int METRIC, int NU>
 __global__ void __launch_bounds__(256) xs_screen_kernel_f16(const XsScan a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   xs_screen_body<METRIC, _Float16, NU>(a, smem);
@@ -504,6 +517,11 @@ __global__ void __launch_bounds__(64) xs_rerank_kernel_bf16(const XsRerank a) {
   xs_rerank_body<METRIC, hs_bf16>(a, reinterpret_cast<float *>(smem));
 }
 template <int METRIC>
+__global__ void __launch_bounds__(64) xs_rerank_kernel_f8(const XsRerank a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  xs_rerank_body<METRIC, hs_f8>(a, reinterpret_cast<float *>(smem));
+}
+template <int METRIC>
 __global__ void __launch_bounds__(64) xs_rerank_kernel_f16(const XsRerank a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   xs_rerank_body<METRIC, _Float16>(a, reinterpret_cast<float *>(smem));
@@ -532,7 +550,7 @@ size_t xs_plan(uint32_t n, uint32_t nq, uint32_t k, uint32_t *grid_x, uint32_t *
   return xs_hdr_offset(nq, gx * 2, xs_cap(k)) + (size_t)nq * gx * 2 * sizeof(uint32_t);
 }
 const char *xs_kernel_name(int fmt) {
-  return fmt == ROWS_U8 ? "hs::xs_screen_kernel_u8" : fmt == ROWS_I8 ? "hs::xs_screen_kernel_i8" : fmt == ROWS_BF16 ? "hs::xs_screen_kernel_bf16" : fmt == ROWS_F16 ? "hs::xs_screen_kernel_f16" : "hs::xs_screen_kernel";
+  return fmt == ROWS_U8 ? "hs::xs_screen_kernel_u8" : fmt == ROWS_I8 ? "hs::xs_screen_kernel_i8" : fmt == ROWS_BF16 ? "hs::xs_screen_kernel_bf16" : fmt == ROWS_F8 ? "hs::xs_screen_kernel_f8" : fmt == ROWS_F16 ? "hs::xs_screen_kernel_f16" : "hs::xs_screen_kernel";
 }
 
 hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int fmt, float *xnorm2, hipStream_t stream) {
@@ -543,6 +561,7 @@ hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int f
   if (fmt == ROWS_U8) hipLaunchKernelGGL(xs_norms_kernel<uint8_t>, g, dim3(256), 0, stream, static_cast<const uint8_t *>(rows), ix.n, ix.dim, xnorm2);
   else if (fmt == ROWS_I8) hipLaunchKernelGGL(xs_norms_kernel<int8_t>, g, dim3(256), 0, stream, static_cast<const int8_t *>(rows), ix.n, ix.dim, xnorm2);
   else if (fmt == ROWS_BF16) hipLaunchKernelGGL(xs_norms_kernel<hs_bf16>, g, dim3(256), 0, stream, static_cast<const hs_bf16 *>(rows), ix.n, ix.dim, xnorm2);
+  else if (fmt == ROWS_F8) hipLaunchKernelGGL(xs_norms_kernel<hs_f8>, g, dim3(256), 0, stream, static_cast<const hs_f8 *>(rows), ix.n, ix.dim, xnorm2);
   else if (fmt == ROWS_F16) hipLaunchKernelGGL(xs_norms_kernel<_Float16>, g, dim3(256), 0, stream, static_cast<const _Float16 *>(rows), ix.n, ix.dim, xnorm2);
   else hipLaunchKernelGGL(xs_norms_kernel<float>, g, dim3(256), 0, stream, static_cast<const float *>(rows), ix.n, ix.dim, xnorm2);
   return hipGetLastError();
@@ -565,6 +584,7 @@ hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, co
   screen = fmt == ROWS_U8    ? (l2 ? xs_screen_kernel_u8<METRIC_L2, NU> : xs_screen_kernel_u8<METRIC_IP, NU>)                  \
            : fmt == ROWS_I8  ? (l2 ? xs_screen_kernel_i8<METRIC_L2, NU> : xs_screen_kernel_i8<METRIC_IP, NU>)                  \
            : fmt == ROWS_BF16 ? (l2 ? xs_screen_kernel_bf16<METRIC_L2, NU> : xs_screen_kernel_bf16<METRIC_IP, NU>)             \
+           : fmt == ROWS_F8  ? (l2 ? xs_screen_kernel_f8<METRIC_L2, NU> : xs_screen_kernel_f8<METRIC_IP, NU>)                  \
            : fmt == ROWS_F16 ? (l2 ? xs_screen_kernel_f16<METRIC_L2, NU> : xs_screen_kernel_f16<METRIC_IP, NU>)                \
                              : (l2 ? xs_screen_kernel<METRIC_L2, NU> : xs_screen_kernel<METRIC_IP, NU>)
   if (slice >= dim) HS_XS_PICK(1);
@@ -598,6 +618,7 @@ hipError_t launch_exact_screen_finish(const DevIndex &ix, const void *rows, int 
   void (*rerank)(const XsRerank) = fmt == ROWS_U8    ? (l2 ? xs_rerank_kernel_u8<METRIC_L2> : xs_rerank_kernel_u8<METRIC_IP>)
                                    : fmt == ROWS_I8  ? (l2 ? xs_rerank_kernel_i8<METRIC_L2> : xs_rerank_kernel_i8<METRIC_IP>)
                                    : fmt == ROWS_BF16 ? (l2 ? xs_rerank_kernel_bf16<METRIC_L2> : xs_rerank_kernel_bf16<METRIC_IP>)
+                                   : fmt == ROWS_F8  ? (l2 ? xs_rerank_kernel_f8<METRIC_L2> : xs_rerank_kernel_f8<METRIC_IP>)
                                    : fmt == ROWS_F16 ? (l2 ? xs_rerank_kernel_f16<METRIC_L2> : xs_rerank_kernel_f16<METRIC_IP>)
                                                      : (l2 ? xs_rerank_kernel<METRIC_L2> : xs_rerank_kernel<METRIC_IP>);
   XsRerank ra{};

@@ -173,4 +173,32 @@ HS_HD float exact_screen_f16_pre_bound(int metric_ip, uint32_t dim, float U, flo
 // passes to the full test, which flags the query.  Either way no pair is dropped whose full test would have changed the answer.
 HS_HD bool exact_screen_bf16_pre_skip(int metric_ip, float qn2) { return !metric_ip && qn2 < 9.0949470e-13f; }   // 2^-40
 
+// The fp8 screen of exact_screen_f8q.hip: rows and queries are OCP E4M3 bytes, the dot product p comes from
+// v_mfma_f32_32x32x64_f8f6f4 (both operands E4M3, unscaled), the norms from fp32 sums of the widened values, a is formed as above.
+// Products.  An E4M3 value is +-m 2^e with a 4-bit significand m (subnormals: 3 bits), 2^-9 <= |v| <= 448.  A product of two has at
+// most 8 significand bits and magnitude in [2^-18, 448^2 = 200704]: exact in fp32, never subnormal there, never near overflow.
+// Only the accumulation rounds.  So the fp16 screen's accounting holds word for word under the same premise (each addition of the
+// pipeline errs by at most one ulp, in any order):  L2 |a - r| <= (5 d + 8) u S,  IP (3 d + 3) u (P + 1), with the same factors to
+// spare and the same (d + 9) u of them spent on S, P, e, lo and hi being formed in fp32.  Range: |q.x| <= d 448^2 < 2^30 and the norms
+// are below 2^30 at d <= 4096, every partial sum with them; a nonzero partial sum is a multiple of 2^-18, so nothing underflows.  The
+// recipe's own squares (t = q - x is a multiple of 2^-9, t^2 of 2^-18) and products do not underflow either, so exact_screen_margin's
+// (d + 8) 2^-120 term is not drawn on at all.  Hence exact_screen_margin covers the screen as it stands whenever the pipeline reads
+// every input byte as the value it encodes.
+// Subnormal bytes.  Whether the matrix pipeline reads the E4M3 subnormals (+-k 2^-9, k = 1 .. 7, exponent field 0) or flushes them to
+// zero could not be established without a measurement that this margin must not depend on, so -- as for the fp16 screen -- the
+// margin holds either way and the counted term is added: a flushed operand loses at most 2^-6 |other_i| of p at its position, and
+// with mq, mx the numbers of subnormal bytes in q and x Cauchy-Schwarz bounds the lost part of p by
+//   lost = 2^-6 (sqrt(mx) |q| + sqrt(mq) |x|) + min(mq, mx) 2^-12.
+// e grows by lost (IP) or 2 lost (L2), scaled by 1 + 2^-10 as in exact_screen_f16_margin.  mq == mx == 0 returns exact_screen_margin's
+// value bit for bit, which is what the pre-test (above) is stated for: it serves the pairs without subnormal bytes and with finite
+// norms, everything else takes the full test, and its proof uses of the data only |p| <= 1.01 |q| |x|, which the rounding bound gives.
+// A query that holds a NaN byte has a NaN norm: e = +inf and the query falls back.  There are no infinities in the format.
+HS_HD float exact_screen_f8_margin(int metric_ip, uint32_t dim, float qn2, float xn2, uint32_t mq, uint32_t mx) {
+  const float e = exact_screen_margin(metric_ip, dim, qn2, xn2);
+  if ((mq | mx) == 0u) return e;
+  const float lost = 0.015625f * (__builtin_sqrtf((float)mx) * __builtin_sqrtf(qn2) + __builtin_sqrtf((float)mq) * __builtin_sqrtf(xn2)) +
+                     (float)(mq < mx ? mq : mx) * 2.4414062e-4f;   // 2^-6, 2^-12
+  return e + (metric_ip ? 1.0009766f : 2.0019531f) * lost;         // (1 + 2^-10), 2 (1 + 2^-10)
+}
+
 }  // namespace hs

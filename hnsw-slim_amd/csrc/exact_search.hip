@@ -1,5 +1,5 @@
 // exact_search.hip -- exact k-NN over the rows a resident index already holds, in the format it holds them (fp32, or the u8 / i8 /
-// fp16 / bf16 narrow copy), under the index's delete marks and, optionally, a filter set with one filter per query.
+// fp16 / bf16 / fp8 narrow copy), under the index's delete marks and, optionally, a filter set with one filter per query.
 //
 // The answer of query i is the min(k, #candidates) lexicographically smallest (dist, label) pairs over its candidates: the
 // internal ids that are not marked deleted and, when a filter set is named, whose bit is set in the query's filter row -- the
@@ -224,6 +224,11 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((target("no-packed-
   exact_scan_body<METRIC, hs_bf16>(a, smem);
 }
 template <int METRIC>
+__global__ void __launch_bounds__(64 * kWaves) __attribute__((target("no-packed-fp32-ops"))) exact_scan_kernel_f8(const ExactScan a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  exact_scan_body<METRIC, hs_f8>(a, smem);
+}
+template <int METRIC>
 __global__ void __launch_bounds__(64 * kWaves) exact_scan_kernel_f16(const ExactScan a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   exact_scan_body<METRIC, _Float16>(a, smem);
@@ -281,6 +286,7 @@ static hipError_t launch_exact_scan(const DevIndex &ix, const void *rows, int fm
       : fmt == ROWS_U8 ? (l2 ? exact_scan_kernel_u8<METRIC_L2> : exact_scan_kernel_u8<METRIC_IP>)
       : fmt == ROWS_I8 ? (l2 ? exact_scan_kernel_i8<METRIC_L2> : exact_scan_kernel_i8<METRIC_IP>)
       : fmt == ROWS_BF16 ? (l2 ? exact_scan_kernel_bf16<METRIC_L2> : exact_scan_kernel_bf16<METRIC_IP>)
+      : fmt == ROWS_F8 ? (l2 ? exact_scan_kernel_f8<METRIC_L2> : exact_scan_kernel_f8<METRIC_IP>)
       : fmt == ROWS_F16 ? (l2 ? exact_scan_kernel_f16<METRIC_L2> : exact_scan_kernel_f16<METRIC_IP>)
                         : (l2 ? exact_scan_kernel<METRIC_L2> : exact_scan_kernel<METRIC_IP>);
   if (lds > 48 * 1024) {

@@ -36,6 +36,11 @@ __device__ inline uint32_t pack4_i8(const float *x, uint32_t o, uint32_t dim) {
   for (uint32_t b = 0; b < 4; b++) w |= (uint32_t)(uint8_t)narrow_cast<int8_t>(x[narrow_source(o + b, dim)]) << (8 * b);
   return w;
 }
+__device__ inline uint32_t pack4_f8(const float *x, uint32_t o, uint32_t dim) {
+  uint32_t w = 0;
+  for (uint32_t b = 0; b < 4; b++) w |= (uint32_t)narrow_cast<hs_f8>(x[narrow_source(o + b, dim)]).w << (8 * b);
+  return w;
+}
 __device__ inline uint32_t pack2_f16(const float *x, uint32_t o, uint32_t dim) {
   uint32_t w = 0;
   for (uint32_t b = 0; b < 2; b++) {
@@ -48,7 +53,10 @@ __device__ inline uint32_t pack2_bf16(const float *x, uint32_t o, uint32_t dim) 
   return (uint32_t)narrow_cast<hs_bf16>(x[narrow_source(o, dim)]).w | ((uint32_t)narrow_cast<hs_bf16>(x[narrow_source(o + 1, dim)]).w << 16);
 }
 
-__global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a) {
+// F8: the record kernel of an index whose narrow copy is fp8 (ROWS_F8), an entry of its own so that hs::index_update_kernel -- the
+// record kernel of every other format, fp32 included -- compiles to what it was.
+template <bool F8>
+__device__ __forceinline__ void index_update_body(UpdateArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = blockIdx.x * (kUpdateBlock / 64) + (threadIdx.x >> 6);
   if (r >= a.nrec) return;
@@ -73,7 +81,10 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
       }
     }
     if (a.narrow) {   // dim % 16 == 0 (hs_index_set_row_format): a row is a whole number of 32-bit words in every format
-      if (a.fmt == ROWS_U8 || a.fmt == ROWS_I8) {
+      if constexpr (F8) {
+        uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a.narrow) + (size_t)id * a.dim);
+        for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_f8(x, 4 * w, a.dim);
+      } else if (a.fmt == ROWS_U8 || a.fmt == ROWS_I8) {
         uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a.narrow) + (size_t)id * a.dim);
         if (a.fmt == ROWS_U8) for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_u8(x, 4 * w, a.dim);
         else for (uint32_t w = lane; w < a.dim / 4; w += 64) dst[w] = pack4_i8(x, 4 * w, a.dim);
@@ -89,6 +100,8 @@ __global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a
     a.deleted[id] = (uint8_t)(head[1] & 1u);
   }
 }
+__global__ void __launch_bounds__(kUpdateBlock) index_update_kernel(UpdateArgs a) { index_update_body<false>(a); }
+__global__ void __launch_bounds__(kUpdateBlock) index_update_kernel_f8(UpdateArgs a) { index_update_body<true>(a); }
 
 hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream) {
   if (a.nrec == 0) return hipSuccess;
@@ -96,7 +109,7 @@ hipError_t launch_index_update(const UpdateArgs &a, hipStream_t stream) {
   if (a.tile0 && (a.stride == 0 || (a.stride & 15u) != 0 || a.stride > 64)) return hipErrorInvalidValue;
   if (a.narrow && ((a.dim & 15u) != 0 || !is_narrow_format(a.fmt))) return hipErrorInvalidValue;
   const uint32_t per = kUpdateBlock / 64;
-  hipLaunchKernelGGL(index_update_kernel, dim3((a.nrec + per - 1) / per), dim3(kUpdateBlock), 0, stream, a);
+  hipLaunchKernelGGL(a.narrow && a.fmt == ROWS_F8 ? index_update_kernel_f8 : index_update_kernel, dim3((a.nrec + per - 1) / per), dim3(kUpdateBlock), 0, stream, a);
   return hipGetLastError();
 }
 

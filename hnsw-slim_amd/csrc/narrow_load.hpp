@@ -1,4 +1,4 @@
-// narrow_load.hpp -- device-side reads of an index's narrow (u8 / i8 / fp16 / bf16) row copy: which rows a kernel instantiation reads, and
+// narrow_load.hpp -- device-side reads of an index's narrow (u8 / i8 / fp16 / bf16 / fp8) row copy: which rows a kernel instantiation reads, and
 // the exact widening of stored element pairs.  Shared by flat_search.hip (8 lanes per row) and beam_search.hip (4 lanes per row).
 // Layout and conversion: narrow_rows.hpp / narrow_rows.hip.
 #pragma once
@@ -19,7 +19,7 @@ typedef uint32_t hs_u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 typedef _Float16 hs_h2 __attribute__((ext_vector_type(2)));
 
 // The rows a strict / fast kernel instantiation reads.  ROW = float: the resident fp32 rows, taken from the DevIndex (the struct is
-// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / int8_t / _Float16 / hs_bf16: the base of the
+// empty, so the fp32 kernels carry no extra argument and compile to what they were).  ROW = uint8_t / int8_t / _Float16 / hs_bf16 / hs_f8: the base of the
 // narrow copy, a kernel argument of its own (DevIndex keeps its layout).
 template <typename ROW> struct RowSrc { const ROW *p; };
 template <> struct RowSrc<float> {};
@@ -51,6 +51,21 @@ __device__ __forceinline__ hs_f2 narrow_pair(const int8_t *, const uint32_t *dw,
 // what the recipe then does with them is the fp32 kernel's own arithmetic.
 __device__ __forceinline__ hs_f2 bf16_pair(uint32_t w) { return hs_f2{__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u)}; }
 __device__ __forceinline__ hs_f2 narrow_pair(const hs_bf16 *, const uint32_t *dw, int i) { return bf16_pair(dw[i]); }
+// An fp8 (E4M3) pair is half a dword, as a u8 pair: v_cvt_pk_f32_fp8 widens both elements of the selected half word in ONE instruction
+// (the u8 / i8 kernels spend one conversion per element).  Exact: every E4M3 value, subnormals included, is a normal fp32 value, so no
+// denormal mode enters; 0x80 gives -0.0f.  (hs_f8's own operator float is the decode on the bits the host uses; the two agree on all
+// 256 bytes -- tests/test_gpu_f8_rows.py.)
+// HS_F8_SINGLE (set by an object before this header): one v_cvt_f32_fp8 per element instead, for the kernels in which the aligned
+// register pair of the packed form costs scratch (flat_search_f8.hip); the same values.
+__device__ __forceinline__ hs_f2 f8_pair(uint32_t w, bool hi) {
+#ifdef HS_F8_SINGLE
+  return hi ? hs_f2{__builtin_amdgcn_cvt_f32_fp8((int)w, 2), __builtin_amdgcn_cvt_f32_fp8((int)w, 3)}
+            : hs_f2{__builtin_amdgcn_cvt_f32_fp8((int)w, 0), __builtin_amdgcn_cvt_f32_fp8((int)w, 1)};
+#else
+  return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+#endif
+}
+__device__ __forceinline__ hs_f2 narrow_pair(const hs_f8 *, const uint32_t *dw, int i) { return f8_pair(dw[i >> 1], i & 1); }
 __device__ __forceinline__ hs_f2 narrow_pair_at(const uint8_t *chunk, uint32_t i) {
   const uint32_t w = *reinterpret_cast<const unsigned short *>(chunk + 2 * i);
   return hs_f2{(float)(w & 0xFFu), (float)(w >> 8)};
@@ -61,6 +76,9 @@ __device__ __forceinline__ hs_f2 narrow_pair_at(const int8_t *chunk, uint32_t i)
 __device__ __forceinline__ hs_f2 narrow_pair_at(const _Float16 *chunk, uint32_t i) {
   const hs_h2 h = *reinterpret_cast<const hs_h2 *>(chunk + 2 * i);
   return hs_f2{(float)h.x, (float)h.y};
+}
+__device__ __forceinline__ hs_f2 narrow_pair_at(const hs_f8 *chunk, uint32_t i) {
+  return f8_pair(*reinterpret_cast<const unsigned short *>(chunk + 2 * i), false);
 }
 __device__ __forceinline__ hs_f2 narrow_pair_at(const hs_bf16 *chunk, uint32_t i) {
   return bf16_pair(*reinterpret_cast<const uint32_t *>(chunk + 2 * i));
@@ -101,6 +119,15 @@ template <> struct NarrowRound<int8_t> : NarrowRound<uint8_t> {
   }
   __device__ __forceinline__ hs_f2 pair(uint32_t i, uint32_t nw) const {
     return i8_pair(i < nw ? w[i >> 1] >> ((i & 1u) * 16u) : p[i]);
+  }
+};
+// fp8: the bytes arrive as the u8 round's do; a pair is widened by one v_cvt_pk_f32_fp8
+template <> struct NarrowRound<hs_f8> : NarrowRound<uint8_t> {
+  __device__ __forceinline__ void load(const hs_f8 *c, uint32_t nb, uint32_t nw) {
+    NarrowRound<uint8_t>::load(reinterpret_cast<const uint8_t *>(c), nb, nw);
+  }
+  __device__ __forceinline__ hs_f2 pair(uint32_t i, uint32_t nw) const {
+    return f8_pair(i < nw ? w[i >> 1] >> ((i & 1u) * 16u) : p[i], false);   // (the half word first, as the u8 round: one conversion, not one per source)
   }
 };
 template <> struct NarrowRound<_Float16> {

@@ -1,6 +1,6 @@
 // narrow_rows.hip -- the narrow copy of an index's rows (hs_index_set_row_format): layout, device conversion with the
 // representability check, and its inverse (widening, exact).  The kernels that search over the copy are the narrow objects of
-// flat_search.hip and beam_search.hip (flat_search_u8.hip, flat_search_i8.hip, beam_search_f16.hip, flat_search_bf16.hip, ...), reached through launch_search (engine.hpp).
+// flat_search.hip and beam_search.hip (flat_search_u8.hip, flat_search_i8.hip, beam_search_f16.hip, flat_search_bf16.hip, flat_search_f8.hip, ...), reached through launch_search (engine.hpp).
 //
 // Layout (narrow_rows.hpp narrow_slot): row r occupies dim elements at r * dim, lane-major for the flat kernel's 8 lanes per row,
 //   narrow[r * dim + s * (dim / 8) + 2 i + e] = x[r][16 i + 2 s + e]      s = 0..7, i = 0..dim/16 - 1, e = 0..1
@@ -39,11 +39,12 @@ hipError_t launch_narrow_convert(const float *d_vec, void *d_out, int fmt, uint3
   return fmt == ROWS_U8   ? convert_t<uint8_t>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream)
          : fmt == ROWS_I8 ? convert_t<int8_t>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream)
          : fmt == ROWS_BF16 ? convert_t<hs_bf16>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream)
+         : fmt == ROWS_F8 ? convert_t<hs_f8>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream)
                           : convert_t<_Float16>(d_vec, d_out, row0, nrows, dim, d_first_bad, stream);
 }
 
 // The inverse: one thread per element of rows [row0, row0 + nrows) of the fp32 array, read from its lane-major slot (u8 -> fp32, i8 ->
-// fp32, fp16 -> fp32 and bf16 -> fp32 are exact; a -0.0f that went into a u8 or i8 copy comes back as +0.0f).
+// fp32, fp16 -> fp32, bf16 -> fp32 and fp8 -> fp32 are exact; a -0.0f that went into a u8 or i8 copy comes back as +0.0f).
 template <typename T>
 __global__ void __launch_bounds__(256) narrow_widen_kernel(const T *rows, float *vec, uint32_t row0, uint32_t nrows, uint32_t dim) {
   const uint64_t total = (uint64_t)nrows * dim;
@@ -64,6 +65,7 @@ hipError_t launch_narrow_widen(const void *d_rows, float *d_vec, int fmt, uint32
   return fmt == ROWS_U8   ? widen_t<uint8_t>(d_rows, d_vec, row0, nrows, dim, stream)
          : fmt == ROWS_I8 ? widen_t<int8_t>(d_rows, d_vec, row0, nrows, dim, stream)
          : fmt == ROWS_BF16 ? widen_t<hs_bf16>(d_rows, d_vec, row0, nrows, dim, stream)
+         : fmt == ROWS_F8 ? widen_t<hs_f8>(d_rows, d_vec, row0, nrows, dim, stream)
                           : widen_t<_Float16>(d_rows, d_vec, row0, nrows, dim, stream);
 }
 

@@ -7,16 +7,16 @@
 
 namespace hs {
 
-// [hs_plan_family][ROWS_*][metric].  (The row formats in ROWS_* order -- f32, f16, u8, i8, bf16 -- which is not the kernel files' HS_TU_ROWS.)
+// [hs_plan_family][ROWS_*][metric].  (The row formats in ROWS_* order -- f32, f16, u8, i8, bf16, f8 -- which is not the kernel files' HS_TU_ROWS.)
 static constexpr SearchLauncher kLaunchers[4][kRowFormats][2] = {
-    /* HS_PLAN_FLAT   */ {{HS_LAUNCHERS(flat, f32)}, {HS_LAUNCHERS(flat, f16)}, {HS_LAUNCHERS(flat, u8)}, {HS_LAUNCHERS(flat, i8)}, {HS_LAUNCHERS(flat, bf16)}},
-    /* HS_PLAN_LEAN   */ {{HS_LAUNCHERS(lean, f32)}, {}, {}, {}, {}},   // (no narrow twin)
-    /* HS_PLAN_FAST   */ {{HS_LAUNCHERS(fast, f32)}, {HS_LAUNCHERS(fast, f16)}, {HS_LAUNCHERS(fast, u8)}, {HS_LAUNCHERS(fast, i8)}, {HS_LAUNCHERS(fast, bf16)}},
-    /* HS_PLAN_STRICT */ {{HS_LAUNCHERS(strict, f32)}, {HS_LAUNCHERS(strict, f16)}, {HS_LAUNCHERS(strict, u8)}, {HS_LAUNCHERS(strict, i8)}, {HS_LAUNCHERS(strict, bf16)}},
+    /* HS_PLAN_FLAT   */ {{HS_LAUNCHERS(flat, f32)}, {HS_LAUNCHERS(flat, f16)}, {HS_LAUNCHERS(flat, u8)}, {HS_LAUNCHERS(flat, i8)}, {HS_LAUNCHERS(flat, bf16)}, {HS_LAUNCHERS(flat, f8)}},
+    /* HS_PLAN_LEAN   */ {{HS_LAUNCHERS(lean, f32)}, {}, {}, {}, {}, {}},   // (no narrow twin)
+    /* HS_PLAN_FAST   */ {{HS_LAUNCHERS(fast, f32)}, {HS_LAUNCHERS(fast, f16)}, {HS_LAUNCHERS(fast, u8)}, {HS_LAUNCHERS(fast, i8)}, {HS_LAUNCHERS(fast, bf16)}, {HS_LAUNCHERS(fast, f8)}},
+    /* HS_PLAN_STRICT */ {{HS_LAUNCHERS(strict, f32)}, {HS_LAUNCHERS(strict, f16)}, {HS_LAUNCHERS(strict, u8)}, {HS_LAUNCHERS(strict, i8)}, {HS_LAUNCHERS(strict, bf16)}, {HS_LAUNCHERS(strict, f8)}},
 };
 static_assert(HS_PLAN_FLAT == 0 && HS_PLAN_LEAN == 1 && HS_PLAN_FAST == 2 && HS_PLAN_STRICT == 3, "the table's rows are in hs_plan_family order");
-static_assert(ROWS_F32 == 0 && ROWS_F16 == 1 && ROWS_U8 == 2 && ROWS_I8 == 3 && ROWS_BF16 == 4 && METRIC_L2 == 0 && METRIC_IP == 1, "the table's columns are in ROWS_* / Metric order");
-// every cell but the lean kernel's eight narrow ones holds a launcher (one that no object defines does not link)
+static_assert(ROWS_F32 == 0 && ROWS_F16 == 1 && ROWS_U8 == 2 && ROWS_I8 == 3 && ROWS_BF16 == 4 && ROWS_F8 == 5 && METRIC_L2 == 0 && METRIC_IP == 1, "the table's columns are in ROWS_* / Metric order");
+// every cell but the lean kernel's ten narrow ones holds a launcher (one that no object defines does not link)
 static constexpr bool table_complete() {
   for (int fam = 0; fam < 4; fam++)
     for (int fmt = 0; fmt < kRowFormats; fmt++)

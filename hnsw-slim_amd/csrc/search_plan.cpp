@@ -33,11 +33,11 @@ const Diag &diag() {
 }
 
 const char *kernel_name(int family, int rows) {
-  static const char *const names[4][5] = {
-      {"hs::flat_kernel", "hs::flat_kernel_f16", "hs::flat_kernel_u8", "hs::flat_kernel_i8", "hs::flat_kernel_bf16"},
-      {"hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel"},   // (no narrow twin: never planned over narrow rows)
-      {"hs::fast_kernel", "hs::fast_kernel_f16", "hs::fast_kernel_u8", "hs::fast_kernel_i8", "hs::fast_kernel_bf16"},
-      {"hs::strict_kernel", "hs::strict_kernel_f16", "hs::strict_kernel_u8", "hs::strict_kernel_i8", "hs::strict_kernel_bf16"},
+  static const char *const names[4][6] = {
+      {"hs::flat_kernel", "hs::flat_kernel_f16", "hs::flat_kernel_u8", "hs::flat_kernel_i8", "hs::flat_kernel_bf16", "hs::flat_kernel_f8"},
+      {"hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel", "hs::lean_kernel"},   // (no narrow twin: never planned over narrow rows)
+      {"hs::fast_kernel", "hs::fast_kernel_f16", "hs::fast_kernel_u8", "hs::fast_kernel_i8", "hs::fast_kernel_bf16", "hs::fast_kernel_f8"},
+      {"hs::strict_kernel", "hs::strict_kernel_f16", "hs::strict_kernel_u8", "hs::strict_kernel_i8", "hs::strict_kernel_bf16", "hs::strict_kernel_f8"},
   };
   return names[family][rows];
 }

@@ -16,7 +16,7 @@
 #define HS_TU_HAS_IP 1
 #endif
 
-// HS_TU_ROWS = 1 | 2 | 3 | 4 (the *_u8.hip / *_f16.hip / *_i8.hip / *_bf16.hip files): the same kernels over the index's narrow copy of the rows
+// HS_TU_ROWS = 1 | 2 | 3 | 4 | 5 (the *_u8.hip / *_f16.hip / *_i8.hip / *_bf16.hip / *_f8.hip files): the same kernels over the index's narrow copy of the rows
 // (hs_index_set_row_format), as objects of their own per row format and metric so that a kernel trace shows them as separate rows;
 // those hold the narrow entry points and their launchers, nothing else.  The narrow kernels take the rows as a kernel argument of
 // their own (DevIndex and SearchArgs are what they were).  What differs between the row formats, all of it, beside the expression
@@ -42,11 +42,16 @@ namespace hs { typedef _Float16 TuRow; }
 #define HS_ROWS_ID i8
 #define HS_KERNEL(name) name##_i8
 namespace hs { typedef int8_t TuRow; }
-#else
+#elif HS_TU_ROWS == 4
 #include "narrow_rows.hpp"
 #define HS_ROWS_ID bf16
 #define HS_KERNEL(name) name##_bf16
 namespace hs { typedef hs_bf16 TuRow; }
+#else
+#include "narrow_rows.hpp"
+#define HS_ROWS_ID f8
+#define HS_KERNEL(name) name##_f8
+namespace hs { typedef hs_f8 TuRow; }
 #endif
 #define HS_ROWS_PARAM , const TuRow *rows
 #define HS_ROWS_ARG , reinterpret_cast<const TuRow *>(rows)

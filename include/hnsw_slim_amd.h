@@ -181,12 +181,15 @@ hs_status hs_index_upsert_points(hs_index *ix, const float *rows, const uint64_t
 hs_status hs_index_resize(hs_index *ix, size_t new_max_elements);
 
 /* ---- narrow rows (no counterpart in the reference) -------------------------------------------------------------------
- * Besides the resident fp32 rows an index can hold a u8, i8, fp16 or bf16 copy of them, and the flat kernel -- the default kernel of every
- * bare index -- then reads that copy (hs::flat_kernel_u8 / _i8 / _f16 / _bf16) and a quarter / half of the row bytes.  HS_ROWS_I8 holds the
+ * Besides the resident fp32 rows an index can hold a u8, i8, fp16, bf16 or fp8 copy of them, and the flat kernel -- the default kernel of every
+ * bare index -- then reads that copy (hs::flat_kernel_u8 / _i8 / _f16 / _bf16 / _f8) and a quarter / half of the row bytes.  HS_ROWS_I8 holds the
  * integers -128 .. 127 as two's complement bytes (what int8 embedding models return; no bias, so inner products are the caller's).
  * HS_ROWS_BF16 holds the upper 16 bits of fp32 values whose lower 16 bits are zero (what a bfloat16 model returns): fp32's exponent
  * range, so values fp16 refuses -- above 65504, finer than 2^-24 -- fit; widening is a shift, no conversion runs.
- * The copy must represent every stored value exactly: u8 -> fp32, i8 -> fp32, fp16 -> fp32 and bf16 -> fp32 are exact, the query stays fp32 and the distance is the same
+ * HS_ROWS_F8 holds OCP E4M3 bytes (1 sign, 4 exponent bits of bias 7, 3 fraction bits; no infinities, 0x7F / 0xFF are NaN, subnormals
+ * k 2^-9, largest value 448): what a real-valued embedding quantised to one byte is stored as; the kernels widen two elements per
+ * v_cvt_pk_f32_fp8.
+ * The copy must represent every stored value exactly: u8 -> fp32, i8 -> fp32, fp16 -> fp32, bf16 -> fp32 and fp8 -> fp32 are exact, the query stays fp32 and the distance is the same
  * fp32 recipe in the same order, so distances, labels, counters and tie behaviour are bit-identical to HS_ROWS_F32.  It is an
  * explicit call because it is a contract on the data: it costs device memory (one value of the format per value of the fp32 array's
  * row capacity: max(n, max_elements) x dim x 1 or 2 bytes, included in hs_info.device_bytes while it exists) and a later
@@ -195,9 +198,9 @@ hs_status hs_index_resize(hs_index *ix, size_t new_max_elements);
  * every other kernel (strict / fast: filters, delete marks, exact order, ef > 512, threshold_level > 0, the re-run pass,
  * hs_search_batch_raw) reads the fp32 rows.  After hs_index_set_f32_resident(ix, 0) the fp32 rows are gone and EVERY search
  * kernel reads the copy: the kernel choice stays what it was and the narrow twin of the chosen kernel is launched
- * (hs::flat_kernel_u8 / _i8 / _f16 / _bf16, hs::fast_kernel_..., hs::strict_kernel_... likewise, the re-run pass included), with
- * the same bits in every output.  The index then occupies a quarter (u8, i8) or half (fp16, bf16) of the row bytes instead of 5/4 or 3/2 of them. */
-typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2, HS_ROWS_I8 = 3, HS_ROWS_BF16 = 4 } hs_row_format;
+ * (hs::flat_kernel_u8 / _i8 / _f16 / _bf16 / _f8, hs::fast_kernel_..., hs::strict_kernel_... likewise, the re-run pass included), with
+ * the same bits in every output.  The index then occupies a quarter (u8, i8, fp8) or half (fp16, bf16) of the row bytes instead of 5/4 or 3/2 of them. */
+typedef enum { HS_ROWS_F32 = 0, HS_ROWS_F16 = 1, HS_ROWS_U8 = 2, HS_ROWS_I8 = 3, HS_ROWS_BF16 = 4, HS_ROWS_F8 = 5 } hs_row_format;
 /* Builds (or, for HS_ROWS_F32, drops) the narrow copy of the rows on the index's device.  Not to be called while a search on this
  * index is in flight (as hs_index_patch).  HS_ERR_UNSUPPORTED, index left exactly as it was, when a stored value is not
  * representable (the message names the first offending row and the value), for a SlimQ index, and for dim % 16 != 0 (the flat
@@ -207,7 +210,8 @@ int hs_index_row_format(const hs_index *ix);
 /* Host only, no device: *first_bad = n when every value of rows[n x dim] is representable in `format`, else the index of the
  * first row that is not.  Representable: x == (float)(T)x, NaN and +-inf never -- u8: the integers 0 .. 255, i8: the integers -128 .. 127 (and, in
  * both, -0.0f, read back as +0.0f, which cannot change a distance); fp16: every finite fp16 value, subnormals included;
- * bf16: every finite fp32 value whose low 16 bits are zero, subnormals and -0.0f (which keeps its sign, as in fp16) included. */
+ * bf16: every finite fp32 value whose low 16 bits are zero, subnormals and -0.0f (which keeps its sign, as in fp16) included;
+ * fp8: the 254 finite E4M3 values, subnormals and -0.0f (stored as 0x80, sign kept) included -- not 449, not 2^-10, not a midpoint. */
 hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int format, uint64_t *first_bad);
 /* on = 0: free the resident fp32 rows of an index that holds a narrow copy; from then on EVERY search kernel reads the copy.
  * on = 1: re-create them from the copy (widening is exact; a u8 or i8 index reads +0.0f where -0.0f was stored).
@@ -220,9 +224,9 @@ hs_status hs_rows_representable(const float *rows, size_t n, size_t dim, int for
  * flight (as hs_index_patch). */
 hs_status hs_index_set_f32_resident(hs_index *ix, int on);
 int hs_index_f32_resident(const hs_index *ix);
-/* Host only, no device: out[n x dim] of `format` (HS_ROWS_U8: bytes, HS_ROWS_I8: two's complement bytes, HS_ROWS_F16: IEEE half words, HS_ROWS_BF16: bf16 words) in the lane-major layout of
+/* Host only, no device: out[n x dim] of `format` (HS_ROWS_U8: bytes, HS_ROWS_I8: two's complement bytes, HS_ROWS_F16: IEEE half words, HS_ROWS_BF16: bf16 words, HS_ROWS_F8: E4M3 bytes) in the lane-major layout of
  * the device copy, out[r * dim + s * (dim / 8) + 2 i + e] = rows[r][16 i + 2 s + e]; *first_bad as hs_rows_representable;
- * nothing is written beyond row *first_bad.  HS_ERR_INVALID for a format other than U8 / I8 / F16 / BF16, HS_ERR_UNSUPPORTED for
+ * nothing is written beyond row *first_bad.  HS_ERR_INVALID for a format other than U8 / I8 / F16 / BF16 / F8, HS_ERR_UNSUPPORTED for
  * dim % 16 != 0. */
 hs_status hs_rows_to_narrow(const float *rows, size_t n, size_t dim, int format, void *out, uint64_t *first_bad);
 /* hs_index_load, but the rows go to the device in `format` only: the result equals load + set_row_format(format) +
@@ -666,6 +670,21 @@ hs_status hs_index_exact_search_bf16(hs_index *ix, const hs_filter_set *fs, cons
 hs_status hs_index_exact_search_bf16_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
                                          const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
                                          uint32_t *d_out_counts, void *stream);
+/* ---- the same answers for fp8 (OCP E4M3) queries, screened on the fp8 matrix cores ------------------------------------------
+ * queries: nq x dim E4M3 bytes in natural order, over an index whose narrow copy is HS_ROWS_F8.  Arguments, outputs and refusals are
+ * hs_index_exact_search_f16's: labels, fp32 distance bits, counts and padding are those of hs_index_exact_search for the same queries
+ * widened to fp32, for every input, under delete marks and filter sets included (csrc/exact_screen_f8q.hip):
+ * v_mfma_f32_32x32x64_f8f6f4 screens 64 positions per instruction with 4r's margin plus a counted term for subnormal bytes the
+ * pipeline may flush; the re-rank and the fallback are the screened entry's.  A query that holds a NaN byte (0x7F, 0xFF) is not
+ * refused: its interval is not finite and the fallback gives the scan's answer.  hs_index_exact_screen_stats reports the call.
+ * HS_ERR_INVALID: an index of dim % 16 == 0 without an fp8 copy of its rows; the rest as hs_index_exact_search.  dim % 16 != 0 is widened
+ * on the device and handed to hs_index_exact_search_screened's route.
+ * hs_last_kernel: hs::xf_screen_kernel (the name of what ran when handed over). */
+hs_status hs_index_exact_search_f8(hs_index *ix, const hs_filter_set *fs, const void *queries, size_t nq, size_t k,
+                                   const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+hs_status hs_index_exact_search_f8_dev(hs_index *ix, const hs_filter_set *fs, const void *d_queries, size_t nq, size_t k,
+                                       const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                       uint32_t *d_out_counts, void *stream);
 /* Debug: the margin of the half-precision screen (csrc/exact_screen_margin.hpp, exact_screen_f16_margin; host only) from the fp32
  * squared norms of query and row and the numbers of their nonzero elements of magnitude below 2^-14.  Both counts zero: the value of
  * hs_debug_exact_screen_margin, bit for bit. */

@@ -8,7 +8,10 @@ old, new, old, new for three rounds; HIP-event time per call, median of `--reps`
 With --q8 the comparison is instead hs_index_exact_search_screened_dev against hs_index_exact_search_q8_dev (byte queries, the integer
 matrix cores: csrc/exact_screen_q8.hip) over the u8 copy of the same index, in the same process and the same alternation.  With --f16q
 it is hs_index_exact_search_screened_dev against hs_index_exact_search_f16_dev (fp16 queries, the half-precision matrix cores:
-csrc/exact_screen_f16q.hip) over the fp16 copy; the bench's integers 0 .. 255 are exact halves.
+csrc/exact_screen_f16q.hip) over the fp16 copy; the bench's integers 0 .. 255 are exact halves.  With --f8q it is
+hs_index_exact_search_screened_dev against hs_index_exact_search_f8_dev (fp8 E4M3 queries, the fp8 matrix cores:
+csrc/exact_screen_f8q.hip) over the fp8 copy of the bench's rows scaled by 1 / 8 and rounded to the nearest E4M3 value (0 .. 31.875 on a
+grid of at most 2: both screens read the same rounded rows); always under the ring graph, since the cached index holds the unrounded rows.
 
 The spread of the old entry's own rounds is the noise: a difference counts only where it lies outside it.  By default the index is the
 bench's cached one; --ring puts the same rows under a ring graph instead (the exact entries read rows, labels and marks, never the
@@ -30,6 +33,15 @@ from hsutil import headline_data, load_product  # noqa: E402
 N, D, NQ, K, PER = 1_000_000, 128, 10_000, 10, 8
 
 
+def e4m3_of_bench(x):
+    """(bytes, values): the bench's integers 0 .. 255, scaled by 1 / 8, as the nearest non-negative E4M3 byte and what it decodes to"""
+    b = np.arange(0x7F)
+    t = np.where(b >> 3 == 0, (b & 7) * 2.0 ** -9, (1 + (b & 7) / 8) * 2.0 ** ((b >> 3) - 7.0))
+    lut = np.abs(np.arange(256)[:, None] / 8 - t[None, :]).argmin(1).astype(np.uint8)
+    byt = lut[x.astype(np.int64)]
+    return byt, t.astype(np.float32)[byt]
+
+
 def log(*a):
     print(*a, flush=True)
 
@@ -41,15 +53,17 @@ def main():
     ap.add_argument("--ring", action="store_true", help="the bench's rows under a ring graph: no HNSW build")
     ap.add_argument("--q8", action="store_true", help="the fp32 screen against the byte-query entry over u8 rows, nothing else")
     ap.add_argument("--f16q", action="store_true", help="the fp32 screen against the fp16-query entry over fp16 rows, nothing else")
+    ap.add_argument("--f8q", action="store_true", help="the fp32 screen against the fp8-query entry over fp8 rows (ring graph), nothing else")
     ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
     hs = load_product()
     dev = torch.device("cuda", 0)
-    if args.ring:
+    if args.ring or args.f8q:
         ids = np.arange(N, dtype=np.uint32)
-        ix = hs.Index.from_csr(hs.HS_KIND_SLIM, hs.HS_METRIC_L2, headline_data(N, D, 123), np.zeros(N, np.int32), np.arange(N + 1, dtype=np.uint64),
+        base = headline_data(N, D, 123)
+        ix = hs.Index.from_csr(hs.HS_KIND_SLIM, hs.HS_METRIC_L2, e4m3_of_bench(base)[1] if args.f8q else base, np.zeros(N, np.int32), np.arange(N + 1, dtype=np.uint64),
                                (ids + 1) % N, 0, 0)
         log("index: the bench's rows under a ring graph")
     else:
@@ -76,7 +90,7 @@ def main():
 
     result = {}
 
-    def compare(name, dq, kernel, q8=None, f16=None, **kw):
+    def compare(name, dq, kernel, q8=None, f16=None, f8=None, **kw):
         o_old, o_new = outputs(), outputs()
         old = lambda: ix.exact_search_dev(dq, K, *o_old, **kw)            # noqa: E731
         new = lambda: ix.exact_search_screened_dev(dq, K, *o_new, **kw)   # noqa: E731
@@ -84,6 +98,8 @@ def main():
             old, new = new, lambda: ix.exact_search_q8_dev(q8, K, *o_old, **kw)   # noqa: E731
         if f16 is not None:   # likewise, the fp16-query entry the new side
             old, new = new, lambda: ix.exact_search_f16_dev(f16, K, *o_old, **kw)   # noqa: E731
+        if f8 is not None:   # likewise, the fp8-query entry
+            old, new = new, lambda: ix.exact_search_f8_dev(f8, K, *o_old, **kw)   # noqa: E731
         old(); new(); ix.check()
         assert ix.last_kernel() == kernel, ix.last_kernel()
         for a, b, what in zip(o_old, o_new, ("labels", "dists", "counts")):
@@ -98,7 +114,7 @@ def main():
         spread = (max(o) - min(o)) / np.median(o) * 100
         spread_new = (max(n) - min(n)) / np.median(n) * 100
         delta = (np.median(n) / np.median(o) - 1) * 100
-        so, sn = ("screened", "q8") if q8 is not None else ("screened", "f16q") if f16 is not None else ("scan", "screened")
+        so, sn = ("screened", "q8") if q8 is not None else ("screened", "f16q") if f16 is not None else ("screened", "f8q") if f8 is not None else ("scan", "screened")
         log(f"{name}: outputs identical | {so} {np.median(o):.3f} ms ({', '.join(f'{x:.3f}' for x in o)}, spread {spread:.2f} %) | {sn} "
             f"{np.median(n):.3f} ms ({', '.join(f'{x:.3f}' for x in n)}, spread {spread_new:.2f} %) | {sn} / {so} {delta:+.2f} % -> "
             + ("inside the spread: no difference shown" if abs(delta) <= max(spread, spread_new) else "outside the spread")
@@ -116,6 +132,12 @@ def main():
         ix.set_row_format(hs.HS_ROWS_F16)
         assert np.array_equal(q, q.astype(np.float16).astype(np.float32)), "the bench's queries are exact halves"
         compare("fp16 rows, fp16 queries", dq, "hs::xh_screen_kernel", f16=torch.from_numpy(q.astype(np.float16)).to(dev))
+        log("RESULT " + json.dumps(result))
+        return 0
+    if args.f8q:
+        ix.set_row_format(hs.HS_ROWS_F8)
+        qb, qv = e4m3_of_bench(q)
+        compare("fp8 rows, fp8 queries", torch.from_numpy(qv).to(dev), "hs::xf_screen_kernel", f8=torch.from_numpy(qb).to(dev))
         log("RESULT " + json.dumps(result))
         return 0
     compare("fp32 rows", dq, "hs::xs_screen_kernel")
