@@ -32,7 +32,7 @@ EXPORTS = [
     "hs_index_set_f32_resident", "hs_index_f32_resident", "hs_rows_to_narrow", "hs_index_load_narrow",
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
-    "hs_index_exact_search", "hs_index_exact_search_dev",
+    "hs_index_exact_search", "hs_index_exact_search_dev", "hs_index_exact_search_wide", "hs_index_exact_search_wide_dev",
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
     "hs_index_exact_search_f16", "hs_index_exact_search_f16_dev", "hs_debug_exact_screen_f16_margin",
@@ -219,6 +219,8 @@ def lib():
         L.hs_queue_drain.argtypes = [vp]
         L.hs_queue_info.argtypes = [vp, ctypes.POINTER(HsQueueInfo)]
     L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_exact_search_wide.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.hs_index_exact_search_wide_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_search_screened.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_screened_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_screen_stats.argtypes = [vp, vp, vp, vp]
@@ -1680,6 +1682,16 @@ class Index:
         _check(lib().hs_index_exact_search_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
                                                None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
                                                d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_search_wide(self, queries, k, fs=None, filter_of_query=None):
+        """hs_index_exact_search_wide: exact_search's arguments and answer for 1 <= k <= 1024 (k <= 64 is exact_search itself)."""
+        return self._exact_host(lib().hs_index_exact_search_wide, queries, k, fs, filter_of_query)
+
+    def exact_search_wide_dev(self, d_queries, k, d_labels, d_dists, d_counts=None, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_search_wide_dev: exact_search_dev's arguments with 1 <= k <= 1024; asynchronous, pair with check(stream)."""
+        _check(lib().hs_index_exact_search_wide_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
+                                                    None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
+                                                    d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
 
     def search_raw(self, queries, k, mode=HS_MODE_SLIM_IDS):
         q = np.ascontiguousarray(queries, np.float32)

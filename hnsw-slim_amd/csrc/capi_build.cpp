@@ -10,6 +10,7 @@
 #include "exact_screen_f16q_engine.hpp"
 #include "exact_screen_f8q_engine.hpp"
 #include "exact_screen_q8_engine.hpp"
+#include "exact_wide_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -450,15 +451,20 @@ static constexpr size_t kExactGroupQueries = 262144;
 
 // Everything an exact search is refused for on the host, before anything is launched.
 static hs_status exact_use_ok(const hs_index *ix, const hs_filter_set *fs, const void *queries, const void *filter_of_query, size_t nq,
-                              size_t k, const void *out_labels64, const void *out_dists) {
+                              size_t k, const void *out_labels64, const void *out_dists, bool wide = false) {
+  // (the wide entries' limit needs no index: refused first, so that it is reachable without one)
+  if (wide && (k == 0 || k > kWideMaxK)) return fail(HS_ERR_UNSUPPORTED, "exact search (wide) supports 1 <= k <= 1024");
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   if (!queries || !out_labels64 || !out_dists) return fail(HS_ERR_INVALID, "null argument");
   if ((fs != nullptr) != (filter_of_query != nullptr)) return fail(HS_ERR_INVALID, "a filter set and filter_of_query go together: both or neither");
   if (ix->info.kind == HS_KIND_SLIMQ) return fail(HS_ERR_UNSUPPORTED, "exact search on a SlimQ index is not supported (its rows are RaBitQ records)");
   if (ix->info.dim > 4096) return fail(HS_ERR_UNSUPPORTED, "exact search supports dim <= 4096");
-  if (k == 0 || k > 64) return fail(HS_ERR_UNSUPPORTED, "exact search supports 1 <= k <= 64");
-  if (exact_lds_bytes((uint32_t)ix->info.dim, (uint32_t)k) > kLdsPerCU)
-    return fail(HS_ERR_UNSUPPORTED, "exact search: a tile of 8 queries of dim " + std::to_string(ix->info.dim) + " with k = " + std::to_string(k) + " does not fit the on-chip memory");
+  // up to 64 the wide entries are the scan's; above, every dim <= 4096 has a tile that fits (xw_tile: 72 KB for two queries of dim 4096, k = 1024)
+  if (!wide || k <= 64) {
+    if (k == 0 || k > 64) return fail(HS_ERR_UNSUPPORTED, "exact search supports 1 <= k <= 64");
+    if (exact_lds_bytes((uint32_t)ix->info.dim, (uint32_t)k) > kLdsPerCU)
+      return fail(HS_ERR_UNSUPPORTED, "exact search: a tile of 8 queries of dim " + std::to_string(ix->info.dim) + " with k = " + std::to_string(k) + " does not fit the on-chip memory");
+  }
   if (nq > 0x7FFFFFFFu) return fail(HS_ERR_INVALID, "nq too large");
   if (fs) {
     if (fs->device != ix->device)
@@ -535,6 +541,47 @@ hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const
     hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists);
     if (s != HS_OK || nq == 0) return s;
     return exact_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
+  });
+}
+
+// ---- 64 < k <= 1024 (exact_wide.hip) --------------------------------------------------------------------------------------------
+// exact_dev's arguments; k <= 64 is exact_dev's own call.
+static hs_status exact_wide_dev(hs_index *ix, const hs_filter_set *fs, const float *d_q, size_t nq, size_t k, const uint32_t *d_foq,
+                                const uint32_t *d_order, uint64_t *l64, float *dd, uint32_t *cnt, hipStream_t stream) {
+  if (k <= 64) return exact_dev(ix, fs, d_q, nq, k, d_foq, d_order, l64, dd, cnt, stream);
+  HIP_TRY(hipSetDevice(ix->device));
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  if (w->counters.n < 48) {   // (as exact_dev)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  const int fmt = ix->row_fmt;
+  const void *rows = fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr;
+  const size_t dim = ix->info.dim;
+  const uint32_t qt = xw_tile((uint32_t)dim, (uint32_t)k);
+  ix->last_kernel = xw_kernel_name((uint32_t)dim, fmt);
+  for (size_t off = 0; off < nq; off += kExactGroupQueries) {
+    const size_t m = std::min(kExactGroupQueries, nq - off);
+    ExactArgs a{};
+    const size_t bytes = xw_plan(ix->dev.n, (uint32_t)m, (uint32_t)k, qt, &a.grid_x, &a.rows_per_block);
+    HIP_TRY(w->xruns.ensure(std::max<size_t>(bytes, 16)));
+    a.queries = d_q + off * dim; a.nq = (uint32_t)m; a.k = (uint32_t)k; a.order = d_order ? d_order + off : nullptr;
+    a.partial = w->xruns.p;
+    a.out_labels = l64 + off * k; a.out_dists = dd + off * k; a.out_counts = cnt ? cnt + off : nullptr;
+    FilterArgs fa{};
+    if (fs) fa = FilterArgs{fs->bits.p, d_foq + off, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+    HIP_TRY(launch_exact_wide(ix->dev, rows, fmt, a, fs ? &fa : nullptr, stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_index_exact_search_wide_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                         const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                         uint32_t *d_out_counts, void *stream) {
+  return guarded([&] {
+    hs_status s = exact_use_ok(ix, fs, d_queries, d_filter_of_query, nq, k, d_out_labels64, d_out_dists, true);
+    if (s != HS_OK || nq == 0) return s;
+    return exact_wide_dev(ix, fs, d_queries, nq, k, d_filter_of_query, nullptr, d_out_labels64, d_out_dists, d_out_counts, (hipStream_t)stream);
   });
 }
 
@@ -698,9 +745,9 @@ static hs_status exact_f16q_dev(hs_index *ix, const hs_filter_set *fs, const voi
 // qfmt: the element type of `queries` -- ROWS_F32; ROWS_U8 / ROWS_I8 for the byte-query entry, kQueriesF16 / kQueriesBF16 / kQueriesF8 for the
 // fp16-, bf16- and fp8-query entries (all always screened).
 static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *queries, int qfmt, size_t nq, size_t k, const uint32_t *filter_of_query,
-                            uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened) {
+                            uint64_t *out_labels64, float *out_dists, uint32_t *out_counts, bool screened, bool wide = false) {
   return guarded([&] {
-    hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists);
+    hs_status s = exact_use_ok(ix, fs, queries, filter_of_query, nq, k, out_labels64, out_dists, wide);
     if (s == HS_OK && qfmt != ROWS_F32) s = half_queries(qfmt) ? exact_f16q_use_ok(ix, qfmt) : exact_q8_use_ok(ix, qfmt);
     if (s != HS_OK) return s;
     if (fs)
@@ -736,7 +783,8 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
       HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
     }
     const uint32_t *d_foq = fs ? w->afoq.p : nullptr, *d_order = fs ? w->xorder.p : nullptr;
-    s = qfmt == ROWS_F32      ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
+    s = wide                  ? exact_wide_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr)
+        : qfmt == ROWS_F32    ? exact_dev(ix, fs, w->aq.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, screened)
         : half_queries(qfmt) ? exact_f16q_dev(ix, fs, w->xq_in.p, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr, qfmt)
                               : exact_q8_dev(ix, fs, w->xq_in.p, qfmt, nq, k, d_foq, d_order, w->al64.p, w->adist.p, w->acnt.p, nullptr);
     if (s != HS_OK) return s;
@@ -751,6 +799,11 @@ static hs_status exact_host(hs_index *ix, const hs_filter_set *fs, const void *q
 hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
                                 const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
   return exact_host(ix, fs, queries, ROWS_F32, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false);
+}
+
+hs_status hs_index_exact_search_wide(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                     const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
+  return exact_host(ix, fs, queries, ROWS_F32, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false, true);
 }
 
 // ---- the same answers by screen, re-rank and fallback (exact_screen.hip) -------------------------------------------------------

@@ -595,6 +595,25 @@ hs_status hs_index_exact_search_dev(hs_index *ix, const hs_filter_set *fs, const
                                     const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
                                     uint32_t *d_out_counts, void *stream);
 
+/* ---- the same answers for k up to 1024 ----------------------------------------------------------------------------------
+ * hs_index_exact_search[_dev]'s arguments, candidates, refusals and outputs with 1 <= k <= 1024 (the largest result set any search
+ * of this library returns): ground truth for recall@100, or a few hundred exact candidates to re-rank.  Every row format, both
+ * metrics, every dim the scan serves; labels, counts, padding and the fp32 bits of every distance are what hs_index_exact_search
+ * would give if its lists were that long.  The answer is a function of the candidate set alone: ties on the distance go to the
+ * smaller label whatever order the rows are scanned in.
+ * k <= 64 is hs_index_exact_search's own call (and kernel).  Above that csrc/exact_wide.hip scans with one list per
+ * (workgroup, query): admitted rows are appended to a buffer in on-chip memory and folded into the kept list by bitonic networks.
+ * HS_ERR_UNSUPPORTED: k == 0 or k > 1024 ("exact search (wide) supports 1 <= k <= 1024"), and whatever hs_index_exact_search
+ * refuses for other reasons (the tile narrows from 8 to 4 or 2 queries with k and dim, so every dim <= 4096 fits).  Workspace per stream: at most
+ * 64 KiB * k between the scan and its merge, none from 2049 queries on.
+ * hs_last_kernel: hs::exact_wide_kernel, _u8, _i8, _f16, _bf16 or _f8 by the rows' format (hs::exact_wide_general_kernel for
+ * dim % 16 != 0). */
+hs_status hs_index_exact_search_wide(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
+                                     const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts);
+hs_status hs_index_exact_search_wide_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, size_t k,
+                                         const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
+                                         uint32_t *d_out_counts, void *stream);
+
 /* ---- the same answers, screened on the matrix cores -------------------------------------------------------------------
  * hs_index_exact_search[_dev]'s arguments, refusals and outputs -- labels, fp32 distance bits, counts and padding are identical for
  * every input -- by another route (csrc/exact_screen.hip): an MFMA distance with a proven error margin rules out all

@@ -9,6 +9,8 @@ cached 1M x 128 index and query seed of bench.py, 10 000 queries, k = 10.  ONE l
   3. filters that allow 50 % / 10 % / 1 % of the ids, eight different filters per selectivity: the scan with the queries grouped by
      filter (tiles of one filter: a tile skips what its filter excludes) and with the filters interleaved (every tile holds all
      eight), and recall@10 of hs_search_batch_filter_set at the bench's ef against the exact answer.
+  --wide K [K ...]: instead of the above, hs_index_exact_search_wide_dev at each K alternated with hs_index_exact_search_dev at
+     k = 64 (the yardstick), three rounds, over fp32 and over u8 rows; the first 64 positions compared with the scan's.
 Output: the log on stdout.
 """
 import argparse
@@ -38,6 +40,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
+    ap.add_argument("--wide", type=int, nargs="+", default=[], metavar="K",
+                    help="this leg alone: exact_search_wide at each K alternated with exact_search at k = 64, over fp32 and over u8 rows")
     args = ap.parse_args()
     import torch
     torch.cuda.init()   # (torch's bundled HIP runtime opens the device before the product's does, as in bench.py)
@@ -73,6 +77,35 @@ def main():
             ts.append(e0.elapsed_time(e1))
         ix.check()
         return float(np.median(ts)), float(min(ts))
+
+    # ---- --wide: hs_index_exact_search_wide_dev at each K against the scan at k = 64, its nearest existing workload -----------------
+    if args.wide:
+        def outs(k):
+            return (torch.zeros((NQ, k), dtype=torch.int64, device=dev), torch.zeros((NQ, k), dtype=torch.float32, device=dev),
+                    torch.zeros(NQ, dtype=torch.int32, device=dev))
+
+        res = {}
+        for fmt_name in ("HS_ROWS_F32", "HS_ROWS_U8"):
+            ix.set_row_format(getattr(hs, fmt_name))
+            o64 = outs(64)
+            legs = [(64, lambda: ix.exact_search_dev(dq, 64, *o64))]
+            for k in args.wide:
+                ok = outs(k)
+                legs.append((k, lambda k=k, ok=ok: ix.exact_search_wide_dev(dq, k, *ok)))
+                legs[-1][1](); legs[0][1](); ix.check()
+                assert torch.equal(ok[0][:, :64], o64[0]) and torch.equal(ok[1][:, :64], o64[1]), f"k = {k}: the first 64 differ from the scan's"
+            ms = {k: [] for k, _ in legs}
+            for rnd in range(args.rounds):
+                for k, fn in legs:
+                    med, mn = timed(fn, args.reps)
+                    ms[k].append(med)
+                    log(f"{fmt_name} round {rnd} k = {k}: {med:.3f} ms per {NQ}-query call (median of {args.reps}, min {mn:.3f})")
+            y = float(np.median(ms[64]))
+            log(f"{fmt_name}: exact_search k = 64 {y:.3f} ms (spread of its rounds {(max(ms[64]) - min(ms[64])) / y * 100:.2f} %) | "
+                + " | ".join(f"exact_search_wide k = {k} {np.median(ms[k]):.3f} ms = {np.median(ms[k]) / y:.2f} x" for k in args.wide))
+            res[fmt_name] = ms
+        log("RESULT " + json.dumps(dict(wide=res)))
+        return 0
 
     # ---- 1. unfiltered, fp32: the exhaustive scan over a second copy against the scan over the index's own rows -----------------
     base_t = torch.from_numpy(np.load(os.path.join(idir, "base.npy"))).to(dev)
