@@ -33,6 +33,7 @@ EXPORTS = [
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
     "hs_index_exact_search", "hs_index_exact_search_dev", "hs_index_exact_search_wide", "hs_index_exact_search_wide_dev",
+    "hs_index_exact_range", "hs_index_exact_range_dev",
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
     "hs_index_exact_search_f16", "hs_index_exact_search_f16_dev", "hs_debug_exact_screen_f16_margin",
@@ -221,6 +222,8 @@ def lib():
     L.hs_index_exact_search_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_search_wide.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_wide_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.hs_index_exact_range.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+    L.hs_index_exact_range_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_screened.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_screened_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_screen_stats.argtypes = [vp, vp, vp, vp]
@@ -1692,6 +1695,40 @@ class Index:
         _check(lib().hs_index_exact_search_wide_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], k,
                                                     None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.data_ptr(),
                                                     d_dists.data_ptr(), d_counts.data_ptr() if d_counts is not None else None, stream))
+
+    def exact_range(self, queries, radius, fs=None, filter_of_query=None, cap=None):
+        """hs_index_exact_range: every candidate of exact_search with dist <= radius (a scalar or one per query), as
+        (offsets, labels, dists): query i's results at [offsets[i], offsets[i + 1]), ascending by (dist, label).  cap=None starts
+        with room for 64 results per query and, on HS_ERR_CAPACITY, calls once more with cap = offsets[-1]; an explicit cap is
+        used as given and HS_ERR_CAPACITY raised, the error carrying the offsets as `.offsets`."""
+        q = np.ascontiguousarray(queries, np.float32)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)))
+        foq = None if filter_of_query is None else np.ascontiguousarray(filter_of_query, np.uint32)
+        if foq is not None and foq.shape != (nq,):
+            raise HsError(HS_ERR_INVALID, "filter_of_query: one filter index per query")
+        offsets = np.zeros(nq + 1, np.uint64)
+        for room in ((64 * nq, None) if cap is None else (cap,)):
+            room = int(offsets[-1]) if room is None else int(room)
+            labels, dists = np.empty(max(room, 1), np.uint64), np.empty(max(room, 1), np.float32)
+            st = lib().hs_index_exact_range(self._h, None if fs is None else fs._h, q.ctypes.data, nq, r.ctypes.data,
+                                            None if foq is None else foq.ctypes.data, room, offsets.ctypes.data, labels.ctypes.data, dists.ctypes.data)
+            if st != HS_ERR_CAPACITY:
+                break
+        if st != HS_OK:
+            e = HsError(st, last_error())
+            e.offsets = offsets
+            raise e
+        total = int(offsets[-1])
+        return offsets, labels[:total], dists[:total]
+
+    def exact_range_dev(self, d_queries, d_radius, d_offsets, d_labels, d_dists, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_range_dev: device tensors (queries f32 nq x d, radius f32 nq, offsets int64 nq + 1, labels int64 cap,
+        dists f32 cap with cap = d_labels.numel()) + HIP stream; asynchronous, pair with check(stream), which raises
+        HS_ERR_CAPACITY when offsets[-1] > cap (nothing was written to labels / dists then)."""
+        _check(lib().hs_index_exact_range_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], d_radius.data_ptr(),
+                                              None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.numel(),
+                                              d_offsets.data_ptr(), d_labels.data_ptr(), d_dists.data_ptr(), stream))
 
     def search_raw(self, queries, k, mode=HS_MODE_SLIM_IDS):
         q = np.ascontiguousarray(queries, np.float32)

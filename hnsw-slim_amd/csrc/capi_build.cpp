@@ -11,6 +11,7 @@
 #include "exact_screen_f8q_engine.hpp"
 #include "exact_screen_q8_engine.hpp"
 #include "exact_wide_engine.hpp"
+#include "exact_range_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -804,6 +805,109 @@ hs_status hs_index_exact_search(hs_index *ix, const hs_filter_set *fs, const flo
 hs_status hs_index_exact_search_wide(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, size_t k,
                                      const uint32_t *filter_of_query, uint64_t *out_labels64, float *out_dists, uint32_t *out_counts) {
   return exact_host(ix, fs, queries, ROWS_F32, nq, k, filter_of_query, out_labels64, out_dists, out_counts, false, true);
+}
+
+// ---- every row within a radius (exact_range.hip) ---------------------------------------------------------------------------------
+static hs_status range_use_ok(const hs_index *ix, const hs_filter_set *fs, const void *queries, const void *radius, const void *filter_of_query,
+                              size_t nq, size_t cap, const void *out_offsets, const void *out_labels64, const void *out_dists) {
+  // (what needs no index comes first, so that it is reachable without one)
+  if (!radius || !out_offsets) return fail(HS_ERR_INVALID, "null argument (radius, out_offsets)");
+  if (!ix) return fail(HS_ERR_INVALID, "null index");
+  if (cap && (!out_labels64 || !out_dists)) return fail(HS_ERR_INVALID, "null argument");
+  // the rest is the scan's at k = 1 (the outputs were looked at above: cap == 0 may come without them)
+  return exact_use_ok(ix, fs, queries, filter_of_query, nq, 1, out_offsets, out_offsets);
+}
+
+// The call's workspace on `stream` and the arguments both passes share; a.cap and the outputs are the caller's to set.
+static hs_status range_args(hs_index *ix, const hs_filter_set *fs, const float *d_q, const float *d_radius, size_t nq, const uint32_t *d_foq,
+                            const uint32_t *d_order, uint64_t *d_offsets, hipStream_t stream, RangeArgs &a, FilterArgs &fa) {
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  if (w->counters.n < 48) {   // (as exact_dev)
+    HIP_TRY(w->counters.ensure(48));
+    HIP_TRY(hipMemsetAsync(w->counters.p, 0, 48 * sizeof(uint32_t), stream));
+  }
+  ix->last_kernel = xr_kernel_name((uint32_t)ix->info.dim, ix->row_fmt);
+  a = RangeArgs{};
+  a.queries = d_q; a.radius = d_radius; a.nq = (uint32_t)nq; a.order = d_order;
+  xr_plan(ix->dev.n, (uint32_t)nq, &a.chunks, &a.rows_per_chunk);
+  HIP_TRY(w->xr_counts.ensure(std::max<size_t>(nq * a.chunks, 1)));
+  HIP_TRY(w->xr_bases.ensure(std::max<size_t>(nq * a.chunks, 1)));
+  a.counts = w->xr_counts.p; a.bases = w->xr_bases.p; a.out_offsets = d_offsets;
+  a.over = w->counters.p + 13;
+  fa = FilterArgs{};
+  if (fs) fa = FilterArgs{fs->bits.p, d_foq, w->counters.p + 12, (uint32_t)fs->row_words, (uint32_t)fs->nf};
+  return HS_OK;
+}
+// the narrow copy where the index has one (as exact_dev)
+static const void *range_rows(const hs_index *ix) { return ix->row_fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr; }
+
+hs_status hs_index_exact_range_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                                   const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                                   float *d_out_dists, void *stream) {
+  return guarded([&] {
+    hs_status s = range_use_ok(ix, fs, d_queries, d_radius, d_filter_of_query, nq, cap, d_out_offsets, d_out_labels64, d_out_dists);
+    if (s != HS_OK) return s;
+    HIP_TRY(hipSetDevice(ix->device));
+    RangeArgs a;
+    FilterArgs fa;
+    s = range_args(ix, fs, d_queries, d_radius, nq, d_filter_of_query, nullptr, d_out_offsets, (hipStream_t)stream, a, fa);
+    if (s != HS_OK) return s;
+    a.cap = cap; a.out_labels = d_out_labels64; a.out_dists = d_out_dists;
+    HIP_TRY(launch_exact_range_count(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, (hipStream_t)stream));
+    HIP_TRY(launch_exact_range_fill(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, (hipStream_t)stream));
+    return HS_OK;
+  });
+}
+
+hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius,
+                               const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets, uint64_t *out_labels64, float *out_dists) {
+  return guarded([&] {
+    hs_status s = range_use_ok(ix, fs, queries, radius, filter_of_query, nq, cap, out_offsets, out_labels64, out_dists);
+    if (s != HS_OK) return s;
+    if (fs)
+      for (size_t i = 0; i < nq; i++)
+        if (filter_of_query[i] >= fs->nf)
+          return fail(HS_ERR_INVALID, "query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) + " of a set of " + std::to_string(fs->nf));
+    if (nq == 0) {
+      out_offsets[0] = 0;
+      return HS_OK;
+    }
+    if (device_ok(ix->device, true) != HS_OK) return HS_ERR_DEVICE;
+    HIP_TRY(hipSetDevice(ix->device));
+    hs_index::StreamWs *w = ix->stream_ws(nullptr);
+    const size_t dim = ix->info.dim;
+    HIP_TRY(w->aq.ensure(nq * dim)); HIP_TRY(w->xr_radius.ensure(nq)); HIP_TRY(w->xr_off.ensure(nq + 1));
+    HIP_TRY(hipMemcpyAsync(w->aq.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(w->xr_radius.p, radius, nq * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    std::vector<uint32_t> order;   // (outlives the asynchronous copy: the call synchronises before it returns)
+    if (fs) {
+      // queries of one filter into the same tiles: a tile skips the rows that none of its filters allows
+      order.resize(nq);
+      for (size_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return filter_of_query[x] < filter_of_query[y]; });
+      HIP_TRY(w->afoq.ensure(nq)); HIP_TRY(w->xorder.ensure(nq));
+      HIP_TRY(hipMemcpyAsync(w->afoq.p, filter_of_query, nq * 4, hipMemcpyHostToDevice, nullptr));
+      HIP_TRY(hipMemcpyAsync(w->xorder.p, order.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
+    }
+    RangeArgs a;
+    FilterArgs fa;
+    s = range_args(ix, fs, w->aq.p, w->xr_radius.p, nq, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->xr_off.p, nullptr, a, fa);
+    if (s != HS_OK) return s;
+    HIP_TRY(launch_exact_range_count(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    HIP_TRY(hipMemcpyAsync(out_offsets, w->xr_off.p, (nq + 1) * 8, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    const uint64_t total = out_offsets[nq];
+    if (total > cap)   // refused up front: the fill is not launched
+      return fail(HS_ERR_CAPACITY, "exact range: " + std::to_string(total) + " results, cap " + std::to_string(cap) + " (out_offsets is written: call again with cap >= the total)");
+    if (total == 0) return HS_OK;
+    HIP_TRY(w->al64.ensure(total)); HIP_TRY(w->adist.ensure(total));
+    a.cap = total; a.out_labels = w->al64.p; a.out_dists = w->adist.p;
+    HIP_TRY(launch_exact_range_fill(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, total * 8, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, total * 4, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return HS_OK;
+  });
 }
 
 // ---- the same answers by screen, re-rank and fallback (exact_screen.hip) -------------------------------------------------------

@@ -132,6 +132,10 @@ struct hs_index {
     // (exact_screen_f16q.hip) uses the same four for its halves and its norms and subnormal counts, hs_index_exact_search_bf16 for its bf16 words, hs_index_exact_search_f8 for its bytes
     DevBuf<uint8_t> xq_in, xq_packed, xq_info;
     DevBuf<float> xq_wide;
+    // hs_index_exact_range (exact_range.hip): the count matrix and its exclusive scan, nq x chunks each; the host entry's radii and offsets
+    DevBuf<uint32_t> xr_counts;
+    DevBuf<uint64_t> xr_bases, xr_off;
+    DevBuf<float> xr_radius;
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
   StreamWs *xs_last = nullptr;   // hs_index_exact_screen_stats: the workspace of the last screened call (null: none, or it was delegated)

@@ -135,7 +135,7 @@ hs_status search_dev(hs_index *ix, const float *d_q, size_t nq, size_t k, int mo
 hs_status hs_search_check(hs_index *ix, void *stream) {
   if (!ix) return fail(HS_ERR_INVALID, "null index");
   return guarded([&] {
-    uint32_t c[13];   // [12]: queries of filter-set searches whose filter index was outside the set
+    uint32_t c[14];   // [12]: queries of filter-set searches whose filter index was outside the set; [13]: an exact range search whose results exceeded cap
     HIP_TRY(hipSetDevice(ix->device));
     hs_index::StreamWs *w = ix->stream_ws((hipStream_t)stream);
     if (!w->counters.p) {   // no kernel was launched on this stream; the padding outputs of an empty index may still be on their way
@@ -155,6 +155,7 @@ hs_status hs_search_check(hs_index *ix, void *stream) {
     if ((size_t)(c[1] + c[5]) * 100 > nq && ix->grow_cand < 4 && !ix->user_cand_cap) ix->grow_cand++;
     if (c[12] > 0)
       return fail(HS_ERR_INVALID, std::to_string(c[12]) + " queries named a filter index outside the filter set (count 0 returned for them)");
+    if (c[13] > 0) return fail(HS_ERR_CAPACITY, "an exact range search found more results than cap (nothing was written; out_offsets holds the total)");
     if (ix->info.kind == HS_KIND_SLIMQ) {
       if (c[8] > 0) return fail(HS_ERR_CAPACITY, std::to_string(c[8]) + " queries expanded more nodes than the 64 KiB on-chip set holds");
       return HS_OK;

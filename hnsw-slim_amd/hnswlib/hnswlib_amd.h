@@ -300,6 +300,27 @@ class DeviceIndex {
     for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);
     return result;
   }
+  // Every candidate of exact_pq within `radius` (hs_index_exact_range), ascending by (dist, label).  A first call with room for 64
+  // results; when the index holds more, the call's offsets name the total and a second call takes them all.
+  std::vector<std::pair<float, labeltype>> exact_range(const void *q, float radius, BaseFilterFunctor *f) const {
+    std::vector<std::pair<float, labeltype>> result;
+    if (!h_) return result;
+    const uint32_t row = 0;
+    const hs_filter_set *fs = f ? filter_row_set(f) : nullptr;
+    uint64_t off[2] = {0, 0};
+    std::vector<uint64_t> labels(64);
+    std::vector<float> dists(64);
+    hs_status s = hs_index_exact_range(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
+    if (s == HS_ERR_CAPACITY) {
+      labels.resize(off[1]);
+      dists.resize(off[1]);
+      s = hs_index_exact_range(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
+    }
+    check(s);
+    result.reserve(off[1]);
+    for (uint64_t i = 0; i < off[1]; i++) result.emplace_back(dists[i], (labeltype)labels[i]);
+    return result;
+  }
   // every row of `queries` in one launch; out_* nq x k ascending by (dist, label), UINT64_MAX / +inf beyond out_counts[q] (nullable)
   void exact_batch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts) const {
     if (!h_) throw std::runtime_error("hnswlib_amd: no index loaded");
@@ -527,6 +548,11 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     ensure_built();
     return exact_pq(query_data, k, isIdAllowed);
   }
+  // every element within `radius` of the query, exactly (detail::DeviceIndex::exact_range): ascending by (dist, label)
+  std::vector<std::pair<float, labeltype>> searchRangeExact(const void *query_data, float radius, BaseFilterFunctor *isIdAllowed = nullptr) const {
+    ensure_built();
+    return exact_range(query_data, radius, isIdAllowed);
+  }
   void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
     ensure_built();
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
@@ -684,6 +710,10 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   // Exact answers over the same resident rows (detail::DeviceIndex::exact_pq / exact_batch): ground truth without a second copy.
   std::priority_queue<std::pair<float, labeltype>> searchKnnExact(const void *query_data, size_t k, BaseFilterFunctor *isIdAllowed = nullptr) const {
     return exact_pq(query_data, k, isIdAllowed);
+  }
+  // every element within `radius` of the query, exactly (detail::DeviceIndex::exact_range): ascending by (dist, label)
+  std::vector<std::pair<float, labeltype>> searchRangeExact(const void *query_data, float radius, BaseFilterFunctor *isIdAllowed = nullptr) const {
+    return exact_range(query_data, radius, isIdAllowed);
   }
   void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);

@@ -614,6 +614,40 @@ hs_status hs_index_exact_search_wide_dev(hs_index *ix, const hs_filter_set *fs, 
                                          const uint32_t *d_filter_of_query, uint64_t *d_out_labels64, float *d_out_dists,
                                          uint32_t *d_out_counts, void *stream);
 
+/* ---- every row within a radius -------------------------------------------------------------------------------------------
+ * Exact range search: for query i every candidate with dist <= radius[i], in CSR form.  Ground truth for an epsilon stop
+ * condition, near-duplicate detection, a re-rank stage with an absolute cut-off: questions for which no k can be fixed in advance.
+ * Candidates of query i are hs_index_exact_search's: internal ids below n that are not marked deleted and, with `fs`, that filter
+ * row filter_of_query[i] allows.  The distance is the index's metric by the fp32 recipes every other path uses: its bits are
+ * those hs_index_exact_search returns for the same pair, on every row format (an index that holds both copies scans the narrow
+ * one), and no matrix or dot-product instruction computes a distance that is compared or returned.  A candidate is a result iff
+ * dist <= radius[i] as an fp32 comparison: a NaN radius, or one below every distance, gives an empty result; radius[i] = +inf
+ * returns every candidate, L2 distances that overflowed to +inf included; a radius equal to an achieved distance includes that row.
+ * Results of query i lie at [out_offsets[i], out_offsets[i + 1]) of out_labels64 / out_dists, ascending by (dist, label):
+ * out_offsets[0] = 0, out_offsets[nq] is the total.  The answer is a function of the candidate set alone.
+ * Capacity: out_labels64 and out_dists hold `cap` entries (they may be null when cap == 0).  out_offsets is always written in
+ * full.  If the total exceeds cap nothing is written to out_labels64 / out_dists and the call returns HS_ERR_CAPACITY with the
+ * total in the message: read it from out_offsets[nq], reallocate, call again.  cap == total succeeds.
+ * Refusals: hs_index_exact_search's (null arguments, fs without filter_of_query or the reverse, a filter set of another n or
+ * device, a host filter index >= nf, a SlimQ index, dim > 4096), and HS_ERR_INVALID for a null radius or out_offsets.  nq == 0
+ * returns HS_OK with out_offsets[0] = 0.  Queries are grouped by filter before tiles of 8 are formed.
+ * csrc/exact_range.hip: a count pass, an exclusive scan, a fill pass that recomputes the distances, and a sort of
+ * each query's segment -- in on-chip memory up to 2048 results, by a slow in-place network on device memory beyond.  Two distance
+ * passes, no screened variant.  Workspace per stream: 12 bytes per (query, row chunk), at most 64 chunks.
+ * hs_last_kernel: hs::exact_range_kernel, _u8, _i8, _f16, _bf16 or _f8 by the rows' format (hs::exact_range_general_kernel for
+ * dim % 16 != 0). */
+hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius /* nq */,
+                               const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets /* nq + 1 */,
+                               uint64_t *out_labels64 /* cap */, float *out_dists /* cap */);
+/* device pointers + HIP stream; asynchronous: pair with hs_search_check(ix, stream).  Tiles are formed in the order given.  The
+ * call cannot refuse a total above cap up front: its fill and sort kernels read the total on the device, write nothing to
+ * d_out_labels64 / d_out_dists when it exceeds cap, and raise a flag that hs_search_check reports as HS_ERR_CAPACITY
+ * (d_out_offsets is complete either way).  A device filter index >= nf: an empty result for that query and HS_ERR_INVALID from
+ * the check, as for hs_index_exact_search_dev. */
+hs_status hs_index_exact_range_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                                   const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                                   float *d_out_dists, void *stream);
+
 /* ---- the same answers, screened on the matrix cores -------------------------------------------------------------------
  * hs_index_exact_search[_dev]'s arguments, refusals and outputs -- labels, fp32 distance bits, counts and padding are identical for
  * every input -- by another route (csrc/exact_screen.hip): an MFMA distance with a proven error margin rules out all

@@ -11,6 +11,9 @@ cached 1M x 128 index and query seed of bench.py, 10 000 queries, k = 10.  ONE l
      eight), and recall@10 of hs_search_batch_filter_set at the bench's ef against the exact answer.
   --wide K [K ...]: instead of the above, hs_index_exact_search_wide_dev at each K alternated with hs_index_exact_search_dev at
      k = 64 (the yardstick), three rounds, over fp32 and over u8 rows; the first 64 positions compared with the scan's.
+  --range K [K ...]: instead of the above, hs_index_exact_range_dev with each query's K-th exact distance as its radius (taken
+     from hs_index_exact_search_wide_dev) alternated with hs_index_exact_search_dev at k = 64, three rounds, over fp32 and over
+     u8 rows; the first K results of every query compared with the wide answer.
 Output: the log on stdout.
 """
 import argparse
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--index-dir", default="", help="index files of bench.py --index-dir instead of the user cache directory")
     ap.add_argument("--wide", type=int, nargs="+", default=[], metavar="K",
                     help="this leg alone: exact_search_wide at each K alternated with exact_search at k = 64, over fp32 and over u8 rows")
+    ap.add_argument("--range", type=int, nargs="+", default=[], metavar="K", dest="range_k",
+                    help="this leg alone: exact_range with the K-th exact distance as each query's radius alternated with exact_search at k = 64")
     args = ap.parse_args()
     import torch
     torch.cuda.init()   # (torch's bundled HIP runtime opens the device before the product's does, as in bench.py)
@@ -105,6 +110,48 @@ def main():
                 + " | ".join(f"exact_search_wide k = {k} {np.median(ms[k]):.3f} ms = {np.median(ms[k]) / y:.2f} x" for k in args.wide))
             res[fmt_name] = ms
         log("RESULT " + json.dumps(dict(wide=res)))
+        return 0
+
+    # ---- --range: hs_index_exact_range_dev at the K-th distance against the scan at k = 64 --------------------------------------------
+    if args.range_k:
+        res = {}
+        for fmt_name in ("HS_ROWS_F32", "HS_ROWS_U8"):
+            ix.set_row_format(getattr(hs, fmt_name))
+            o64 = (torch.zeros((NQ, 64), dtype=torch.int64, device=dev), torch.zeros((NQ, 64), dtype=torch.float32, device=dev),
+                   torch.zeros(NQ, dtype=torch.int32, device=dev))
+            legs = [(64, lambda: ix.exact_search_dev(dq, 64, *o64))]
+            totals = {}
+            for k in args.range_k:
+                wl, wd = torch.zeros((NQ, k), dtype=torch.int64, device=dev), torch.zeros((NQ, k), dtype=torch.float32, device=dev)
+                ix.exact_search_wide_dev(dq, k, wl, wd)
+                ix.check()
+                radius = wd[:, k - 1].contiguous()
+                off = torch.zeros(NQ + 1, dtype=torch.int64, device=dev)
+                ix.exact_range_dev(dq, radius, off, torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+                try:
+                    ix.check()   # (the sizing call: HS_ERR_CAPACITY is the expected answer, the offsets are complete)
+                except hs.HsError as e:
+                    assert e.status == hs.HS_ERR_CAPACITY
+                total = totals[k] = int(off[-1])
+                ol, od = torch.zeros(total, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.float32, device=dev)
+                legs.append((k, lambda radius=radius, off=off, ol=ol, od=od: ix.exact_range_dev(dq, radius, off, ol, od)))
+                legs[-1][1](); ix.check()
+                assert total >= NQ * k and bool((off[1:] - off[:-1] >= k).all())
+                head = off[:-1, None] + torch.arange(k, device=dev)[None]
+                assert torch.equal(ol[head], wl) and torch.equal(od[head], wd), f"k = {k}: the first k of a segment differ from the wide answer"
+            ms = {k: [] for k, _ in legs}
+            for rnd in range(args.rounds):
+                for k, fn in legs:
+                    med, mn = timed(fn, args.reps)
+                    ms[k].append(med)
+                    log(f"{fmt_name} round {rnd} {'exact_search k = 64' if k == 64 and fn is legs[0][1] else f'exact_range at the {k}-th distance'}: "
+                        f"{med:.3f} ms per {NQ}-query call (median of {args.reps}, min {mn:.3f})")
+            y = float(np.median(ms[64]))
+            log(f"{fmt_name} ({ix.last_kernel()}): exact_search k = 64 {y:.3f} ms (spread of its rounds {(max(ms[64]) - min(ms[64])) / y * 100:.2f} %) | "
+                + " | ".join(f"exact_range K = {k} ({totals[k]} results) {np.median(ms[k]):.3f} ms = {np.median(ms[k]) / y:.2f} x "
+                             f"(spread {(max(ms[k]) - min(ms[k])) / np.median(ms[k]) * 100:.2f} %)" for k in args.range_k))
+            res[fmt_name] = dict(ms=ms, totals=totals)
+        log("RESULT " + json.dumps(dict(range=res)))
         return 0
 
     # ---- 1. unfiltered, fp32: the exhaustive scan over a second copy against the scan over the index's own rows -----------------
