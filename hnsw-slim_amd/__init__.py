@@ -18,6 +18,7 @@ HS_KIND_HNSW, HS_KIND_SLIM, HS_KIND_SLIMQ = 0, 1, 2
 HS_METRIC_L2, HS_METRIC_IP = 0, 1
 HS_MODE_SLIM_IDS, HS_MODE_PQ = 0, 1
 HS_ROWS_F32, HS_ROWS_F16, HS_ROWS_U8, HS_ROWS_I8, HS_ROWS_BF16, HS_ROWS_F8 = 0, 1, 2, 3, 4, 5   # hs_row_format (narrow rows: Index.set_row_format)
+HS_EXACT_RANGE_SCREEN_LIST = 1024   # survivors per query that Index.exact_range_screened's screen lists before the query falls back
 HS_OK, HS_ERR_IO, HS_ERR_CORRUPT, HS_ERR_NOMEM, HS_ERR_INVALID, HS_ERR_UNSUPPORTED, HS_ERR_DEVICE, HS_ERR_CAPACITY = range(8)
 
 EXPORTS = [
@@ -33,7 +34,7 @@ EXPORTS = [
     "hs_filter_row_words", "hs_filter_pack", "hs_filter_set_create", "hs_filter_set_free", "hs_filter_set_write", "hs_filter_set_write_bits",
     "hs_filter_set_write_dev", "hs_filter_set_read", "hs_filter_set_info", "hs_search_batch_filter_set", "hs_search_batch_filter_set_dev",
     "hs_index_exact_search", "hs_index_exact_search_dev", "hs_index_exact_search_wide", "hs_index_exact_search_wide_dev",
-    "hs_index_exact_range", "hs_index_exact_range_dev",
+    "hs_index_exact_range", "hs_index_exact_range_dev", "hs_index_exact_range_screened", "hs_index_exact_range_screened_dev",
     "hs_index_exact_search_screened", "hs_index_exact_search_screened_dev", "hs_index_exact_screen_stats", "hs_debug_exact_screen_margin",
     "hs_index_exact_search_q8", "hs_index_exact_search_q8_dev", "hs_debug_exact_screen_q8_interval", "hs_debug_exact_q8_pack_order",
     "hs_index_exact_search_f16", "hs_index_exact_search_f16_dev", "hs_debug_exact_screen_f16_margin",
@@ -224,6 +225,8 @@ def lib():
     L.hs_index_exact_search_wide_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_range.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
     L.hs_index_exact_range_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    L.hs_index_exact_range_screened.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+    L.hs_index_exact_range_screened_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_screened.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.hs_index_exact_search_screened_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.hs_index_exact_screen_stats.argtypes = [vp, vp, vp, vp]
@@ -1701,6 +1704,15 @@ class Index:
         (offsets, labels, dists): query i's results at [offsets[i], offsets[i + 1]), ascending by (dist, label).  cap=None starts
         with room for 64 results per query and, on HS_ERR_CAPACITY, calls once more with cap = offsets[-1]; an explicit cap is
         used as given and HS_ERR_CAPACITY raised, the error carrying the offsets as `.offsets`."""
+        return self._exact_range_host(lib().hs_index_exact_range, queries, radius, fs, filter_of_query, cap)
+
+    def exact_range_screened(self, queries, radius, fs=None, filter_of_query=None, cap=None):
+        """hs_index_exact_range_screened: exact_range's arguments and answer, bit for bit, by an MFMA screen against the radius, a
+        re-rank of the survivors in the reference's arithmetic and, per query, exact_range's passes where the screen cannot decide.
+        exact_screen_stats() tells which."""
+        return self._exact_range_host(lib().hs_index_exact_range_screened, queries, radius, fs, filter_of_query, cap)
+
+    def _exact_range_host(self, entry, queries, radius, fs, filter_of_query, cap):
         q = np.ascontiguousarray(queries, np.float32)
         nq = q.shape[0]
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)))
@@ -1711,8 +1723,8 @@ class Index:
         for room in ((64 * nq, None) if cap is None else (cap,)):
             room = int(offsets[-1]) if room is None else int(room)
             labels, dists = np.empty(max(room, 1), np.uint64), np.empty(max(room, 1), np.float32)
-            st = lib().hs_index_exact_range(self._h, None if fs is None else fs._h, q.ctypes.data, nq, r.ctypes.data,
-                                            None if foq is None else foq.ctypes.data, room, offsets.ctypes.data, labels.ctypes.data, dists.ctypes.data)
+            st = entry(self._h, None if fs is None else fs._h, q.ctypes.data, nq, r.ctypes.data,
+                       None if foq is None else foq.ctypes.data, room, offsets.ctypes.data, labels.ctypes.data, dists.ctypes.data)
             if st != HS_ERR_CAPACITY:
                 break
         if st != HS_OK:
@@ -1729,6 +1741,12 @@ class Index:
         _check(lib().hs_index_exact_range_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0], d_radius.data_ptr(),
                                               None if d_filter_of_query is None else d_filter_of_query.data_ptr(), d_labels.numel(),
                                               d_offsets.data_ptr(), d_labels.data_ptr(), d_dists.data_ptr(), stream))
+
+    def exact_range_screened_dev(self, d_queries, d_radius, d_offsets, d_labels, d_dists, fs=None, d_filter_of_query=None, stream=0):
+        """hs_index_exact_range_screened_dev: exact_range_dev's arguments and answer; asynchronous, pair with check(stream)."""
+        _check(lib().hs_index_exact_range_screened_dev(self._h, None if fs is None else fs._h, d_queries.data_ptr(), d_queries.shape[0],
+                                                       d_radius.data_ptr(), None if d_filter_of_query is None else d_filter_of_query.data_ptr(),
+                                                       d_labels.numel(), d_offsets.data_ptr(), d_labels.data_ptr(), d_dists.data_ptr(), stream))
 
     def search_raw(self, queries, k, mode=HS_MODE_SLIM_IDS):
         q = np.ascontiguousarray(queries, np.float32)

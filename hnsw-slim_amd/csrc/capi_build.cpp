@@ -12,6 +12,7 @@
 #include "exact_screen_q8_engine.hpp"
 #include "exact_wide_engine.hpp"
 #include "exact_range_engine.hpp"
+#include "exact_range_screen_engine.hpp"
 #include "host_rq_batch_build.hpp"
 #include "host_rq_graph.hpp"
 #include "host_update.hpp"
@@ -841,9 +842,34 @@ static hs_status range_args(hs_index *ix, const hs_filter_set *fs, const float *
 // the narrow copy where the index has one (as exact_dev)
 static const void *range_rows(const hs_index *ix) { return ix->row_fmt != ROWS_F32 ? (const void *)ix->narrow.p : nullptr; }
 
-hs_status hs_index_exact_range_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
-                                   const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
-                                   float *d_out_dists, void *stream) {
+// The screened route's workspace on the call's stream behind range_args: norms, state words, flags, fallback order, cursors, lists.
+static hs_status range_screen_args(hs_index *ix, size_t nq, hipStream_t stream, const RangeArgs &a, RangeScreenArgs &sa) {
+  hs_index::StreamWs *w = ix->stream_ws(stream);
+  HIP_TRY(w->xs_norms.ensure((size_t)ix->dev.n + nq));
+  HIP_TRY(w->xs_state.ensure(kXsStateWords + 3 * nq));
+  HIP_TRY(w->xrs_lists.ensure(xrs_list_words((uint32_t)nq)));
+  sa = RangeScreenArgs{};
+  sa.r = a;
+  sa.xnorm2 = w->xs_norms.p; sa.qnorm2 = w->xs_norms.p + ix->dev.n;
+  xrs_plan(ix->dev.n, (uint32_t)nq, &sa.grid_y, &sa.rows_per_block);
+  sa.state = w->xs_state.p; sa.qflag = w->xs_state.p + kXsStateWords; sa.fb_order = sa.qflag + nq; sa.cursor = sa.fb_order + nq;
+  sa.lists = w->xrs_lists.p;
+  ix->last_kernel = xrs_kernel_name(ix->row_fmt);
+  return HS_OK;
+}
+// want_screen: through exact_range_screen.hip where its envelope holds (dim % 16 == 0), the two passes of exact_range.hip otherwise.
+static bool range_screened(hs_index *ix, size_t nq, hipStream_t stream, bool want_screen) {
+  const bool screened = want_screen && nq != 0 && xrs_supported((uint32_t)ix->info.dim);
+  if (want_screen) {   // (the plain entries leave the last screened call's stats alone)
+    ix->xs_last = screened ? ix->stream_ws(stream) : nullptr;
+    ix->xs_last_nq = nq;
+  }
+  return screened;
+}
+
+static hs_status range_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                           const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                           float *d_out_dists, void *stream, bool want_screen) {
   return guarded([&] {
     hs_status s = range_use_ok(ix, fs, d_queries, d_radius, d_filter_of_query, nq, cap, d_out_offsets, d_out_labels64, d_out_dists);
     if (s != HS_OK) return s;
@@ -853,14 +879,23 @@ hs_status hs_index_exact_range_dev(hs_index *ix, const hs_filter_set *fs, const 
     s = range_args(ix, fs, d_queries, d_radius, nq, d_filter_of_query, nullptr, d_out_offsets, (hipStream_t)stream, a, fa);
     if (s != HS_OK) return s;
     a.cap = cap; a.out_labels = d_out_labels64; a.out_dists = d_out_dists;
+    if (range_screened(ix, nq, (hipStream_t)stream, want_screen)) {
+      RangeScreenArgs sa;
+      s = range_screen_args(ix, nq, (hipStream_t)stream, a, sa);
+      if (s != HS_OK) return s;
+      HIP_TRY(launch_exact_range_screen_count(ix->dev, range_rows(ix), ix->row_fmt, sa, fs ? &fa : nullptr, (hipStream_t)stream));
+      HIP_TRY(launch_exact_range_screen_fill(ix->dev, range_rows(ix), ix->row_fmt, sa, fs ? &fa : nullptr, (hipStream_t)stream));
+      return HS_OK;
+    }
     HIP_TRY(launch_exact_range_count(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, (hipStream_t)stream));
     HIP_TRY(launch_exact_range_fill(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, (hipStream_t)stream));
     return HS_OK;
   });
 }
 
-hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius,
-                               const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets, uint64_t *out_labels64, float *out_dists) {
+static hs_status range_host(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius,
+                            const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets, uint64_t *out_labels64, float *out_dists,
+                            bool want_screen) {
   return guarded([&] {
     hs_status s = range_use_ok(ix, fs, queries, radius, filter_of_query, nq, cap, out_offsets, out_labels64, out_dists);
     if (s != HS_OK) return s;
@@ -893,7 +928,15 @@ hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const floa
     FilterArgs fa;
     s = range_args(ix, fs, w->aq.p, w->xr_radius.p, nq, fs ? w->afoq.p : nullptr, fs ? w->xorder.p : nullptr, w->xr_off.p, nullptr, a, fa);
     if (s != HS_OK) return s;
-    HIP_TRY(launch_exact_range_count(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    const bool screened = range_screened(ix, nq, nullptr, want_screen);
+    RangeScreenArgs sa;
+    if (screened) {
+      s = range_screen_args(ix, nq, nullptr, a, sa);
+      if (s != HS_OK) return s;
+      HIP_TRY(launch_exact_range_screen_count(ix->dev, range_rows(ix), ix->row_fmt, sa, fs ? &fa : nullptr, nullptr));
+    } else {
+      HIP_TRY(launch_exact_range_count(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    }
     HIP_TRY(hipMemcpyAsync(out_offsets, w->xr_off.p, (nq + 1) * 8, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     const uint64_t total = out_offsets[nq];
@@ -901,13 +944,39 @@ hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const floa
       return fail(HS_ERR_CAPACITY, "exact range: " + std::to_string(total) + " results, cap " + std::to_string(cap) + " (out_offsets is written: call again with cap >= the total)");
     if (total == 0) return HS_OK;
     HIP_TRY(w->al64.ensure(total)); HIP_TRY(w->adist.ensure(total));
-    a.cap = total; a.out_labels = w->al64.p; a.out_dists = w->adist.p;
-    HIP_TRY(launch_exact_range_fill(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    if (screened) {
+      sa.r.cap = total; sa.r.out_labels = w->al64.p; sa.r.out_dists = w->adist.p;
+      HIP_TRY(launch_exact_range_screen_fill(ix->dev, range_rows(ix), ix->row_fmt, sa, fs ? &fa : nullptr, nullptr));
+    } else {
+      a.cap = total; a.out_labels = w->al64.p; a.out_dists = w->adist.p;
+      HIP_TRY(launch_exact_range_fill(ix->dev, range_rows(ix), ix->row_fmt, a, fs ? &fa : nullptr, nullptr));
+    }
     HIP_TRY(hipMemcpyAsync(out_labels64, w->al64.p, total * 8, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipMemcpyAsync(out_dists, w->adist.p, total * 4, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return HS_OK;
   });
+}
+
+hs_status hs_index_exact_range_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                                   const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                                   float *d_out_dists, void *stream) {
+  return range_dev(ix, fs, d_queries, nq, d_radius, d_filter_of_query, cap, d_out_offsets, d_out_labels64, d_out_dists, stream, false);
+}
+hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius,
+                               const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets, uint64_t *out_labels64, float *out_dists) {
+  return range_host(ix, fs, queries, nq, radius, filter_of_query, cap, out_offsets, out_labels64, out_dists, false);
+}
+// ---- the same answers by screen, re-rank and fallback (exact_range_screen.hip) -----------------------------------------------
+hs_status hs_index_exact_range_screened_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                                            const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                                            float *d_out_dists, void *stream) {
+  return range_dev(ix, fs, d_queries, nq, d_radius, d_filter_of_query, cap, d_out_offsets, d_out_labels64, d_out_dists, stream, true);
+}
+hs_status hs_index_exact_range_screened(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius,
+                                        const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets, uint64_t *out_labels64,
+                                        float *out_dists) {
+  return range_host(ix, fs, queries, nq, radius, filter_of_query, cap, out_offsets, out_labels64, out_dists, true);
 }
 
 // ---- the same answers by screen, re-rank and fallback (exact_screen.hip) -------------------------------------------------------

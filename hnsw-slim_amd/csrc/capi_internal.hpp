@@ -136,6 +136,9 @@ struct hs_index {
     DevBuf<uint32_t> xr_counts;
     DevBuf<uint64_t> xr_bases, xr_off;
     DevBuf<float> xr_radius;
+    // hs_index_exact_range_screened (exact_range_screen.hip): per query 2 x HS_EXACT_RANGE_SCREEN_LIST words -- the survivors' row ids,
+    // then the kept rows' distances; its norms and state words share xs_norms / xs_state with the screened k-NN
+    DevBuf<uint32_t> xrs_lists;
   };
   std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;
   StreamWs *xs_last = nullptr;   // hs_index_exact_screen_stats: the workspace of the last screened call (null: none, or it was delegated)

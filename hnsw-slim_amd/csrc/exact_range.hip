@@ -45,6 +45,7 @@ struct RangeScan {
   const uint8_t *deleted;    // null: the index has no delete marks
   const float *queries, *radius;
   const uint32_t *order;     // nullable
+  const uint32_t *live;      // nullable: the first *live slots of `order` name queries; a tile beyond them returns at once
   uint32_t *counts;          // nq x gridDim.y: written by the count pass, read by the fill pass
   const uint64_t *bases;     // nq x gridDim.y (fill)
   const uint64_t *total;     // out_offsets + nq (fill)
@@ -236,10 +237,15 @@ __device__ __forceinline__ bool xr_fill_refused(const RangeScan &a, int tid) {
   return true;
 }
 
+// A subset found on the device (exact_range_screen.hip's fallback): the slots at and beyond *a.live name no query, so the tile has
+// nothing to count or fill (the whole workgroup takes the same way).  Without a.live every tile runs.
+__device__ __forceinline__ bool xr_tile_idle(const RangeScan &a) { return a.live && blockIdx.x * kQT >= *a.live; }
+
 template <int METRIC, typename ROW, bool FILL>
 __device__ __forceinline__ void xr_scan_body(const RangeScan &a, unsigned char *smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (FILL && xr_fill_refused(a, tid)) return;
+  if (xr_tile_idle(a)) return;
   const RangeLds s = xr_stage<FILL>(a, smem, tid);
   const uint32_t r0 = blockIdx.y * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
   for (uint32_t u = (r0 >> 5) + wave; u * 32 < r1; u += kWaves) xr_unit<METRIC, ROW, FILL>(a, s, u, r0, lane);
@@ -267,6 +273,7 @@ __global__ void __launch_bounds__(kRangeThreads) exact_range_general_kernel(cons
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (FILL && xr_fill_refused(a, tid)) return;
+  if (xr_tile_idle(a)) return;
   const RangeLds s = xr_stage<FILL>(a, smem, tid);
   const uint32_t dim = a.dim;
   const uint32_t r0 = blockIdx.y * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
@@ -406,7 +413,7 @@ static hipError_t xr_launch_scan(const DevIndex &ix, const void *rows, int fmt, 
   }
   RangeScan sa{};
   sa.rows = rows; sa.labels = ix.labels; sa.deleted = ix.has_deleted ? ix.deleted : nullptr;
-  sa.queries = a.queries; sa.radius = a.radius; sa.order = a.order;
+  sa.queries = a.queries; sa.radius = a.radius; sa.order = a.order; sa.live = a.live;
   sa.counts = a.counts; sa.bases = a.bases; sa.total = a.out_offsets + a.nq;
   sa.cap = a.cap; sa.out_labels = a.out_labels; sa.out_dists = a.out_dists; sa.over = a.over;
   if (f) sa.f = *f;

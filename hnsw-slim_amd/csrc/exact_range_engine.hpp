@@ -19,6 +19,8 @@ struct RangeArgs {
   const float *radius;      // nq
   uint32_t nq;
   const uint32_t *order;    // nullable: a permutation of [0, nq) -- tile slot s serves query order[s]; outputs stay at the query's own position
+  const uint32_t *live;     // nullable (device): with `order`, only its first *live slots name queries (0xFFFFFFFF behind them) and only
+                            // those queries' counts and results are written; tiles beyond them return at once.  Null: every tile runs
   uint32_t chunks, rows_per_chunk;   // xr_plan
   uint32_t *counts;         // nq x chunks: hits of (query, chunk)
   uint64_t *bases;          // nq x chunks: where the hits of (query, chunk) start in the outputs

@@ -66,6 +66,8 @@ bool xs_supported(uint32_t dim, uint32_t k);
 size_t xs_plan(uint32_t n, uint32_t nq, uint32_t k, uint32_t *grid_x, uint32_t *rows_per_block);
 // |x|^2 of every row the index holds, once per call, ahead of its launch groups.
 hipError_t launch_exact_screen_norms(const DevIndex &ix, const void *rows, int fmt, float *xnorm2, hipStream_t stream);
+// |q|^2 of nq fp32 queries by the same kernel.
+hipError_t launch_exact_screen_qnorms(const float *queries, uint32_t nq, uint32_t dim, float *qnorm2, hipStream_t stream);
 // Query norms, screen, re-rank, fallback of one group: all enqueued, nothing read back.  rows / fmt as launch_exact_search.
 hipError_t launch_exact_screen(const DevIndex &ix, const void *rows, int fmt, const ScreenArgs &a, const FilterArgs *f, hipStream_t stream);
 const char *xs_kernel_name(int fmt);

@@ -300,8 +300,9 @@ class DeviceIndex {
     for (uint32_t i = 0; i < cnt; i++) result.emplace(dists[i], (labeltype)labels[i]);
     return result;
   }
-  // Every candidate of exact_pq within `radius` (hs_index_exact_range), ascending by (dist, label).  A first call with room for 64
-  // results; when the index holds more, the call's offsets name the total and a second call takes them all.
+  // Every candidate of exact_pq within `radius` (hs_index_exact_range; hs_index_exact_range_screened after setExactScreened(true)),
+  // ascending by (dist, label).  A first call with room for 64 results; when the index holds more, the call's offsets name the total
+  // and a second call takes them all.
   std::vector<std::pair<float, labeltype>> exact_range(const void *q, float radius, BaseFilterFunctor *f) const {
     std::vector<std::pair<float, labeltype>> result;
     if (!h_) return result;
@@ -310,11 +311,12 @@ class DeviceIndex {
     uint64_t off[2] = {0, 0};
     std::vector<uint64_t> labels(64);
     std::vector<float> dists(64);
-    hs_status s = hs_index_exact_range(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
+    const auto entry = exact_screened_ ? hs_index_exact_range_screened : hs_index_exact_range;
+    hs_status s = entry(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
     if (s == HS_ERR_CAPACITY) {
       labels.resize(off[1]);
       dists.resize(off[1]);
-      s = hs_index_exact_range(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
+      s = entry(h_, fs, (const float *)q, 1, &radius, f ? &row : nullptr, labels.size(), off, labels.data(), dists.data());
     }
     check(s);
     result.reserve(off[1]);
@@ -557,7 +559,7 @@ class HierarchicalNSW<float> : public AlgorithmInterface<float>, public detail::
     ensure_built();
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
   }
-  // the two calls above through the screened entry (hs_index_exact_search_screened): the same answers; off by default
+  // the calls above through the screened entries (hs_index_exact_search_screened, hs_index_exact_range_screened): the same answers; off by default
   void setExactScreened(bool on) { exact_screened_ = on; }
   // Batched searchKnn: nq x dim queries; out_labels / out_dists nq x k (unused slots: UINT64_MAX / +inf).
   void searchKnnBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists,
@@ -718,7 +720,7 @@ class HierarchicalNSWSlim<float> : public AlgorithmInterface<float>, public deta
   void searchKnnExactBatch(const float *queries, size_t nq, size_t k, uint64_t *out_labels, float *out_dists, uint32_t *out_counts = nullptr) const {
     exact_batch(queries, nq, k, out_labels, out_dists, out_counts);
   }
-  // the two calls above through the screened entry (hs_index_exact_search_screened): the same answers; off by default
+  // the calls above through the screened entries (hs_index_exact_search_screened, hs_index_exact_range_screened): the same answers; off by default
   void setExactScreened(bool on) { exact_screened_ = on; }
   // searchKnn(q, k, tableint* result): hnswalg_slim.h:2030-2131.  k labels; same k-subset as the reference,
   // sorted by distance (call setExactOrder(true) to also reproduce the reference's array order).

@@ -633,7 +633,7 @@ hs_status hs_index_exact_search_wide_dev(hs_index *ix, const hs_filter_set *fs, 
  * returns HS_OK with out_offsets[0] = 0.  Queries are grouped by filter before tiles of 8 are formed.
  * csrc/exact_range.hip: a count pass, an exclusive scan, a fill pass that recomputes the distances, and a sort of
  * each query's segment -- in on-chip memory up to 2048 results, by a slow in-place network on device memory beyond.  Two distance
- * passes, no screened variant.  Workspace per stream: 12 bytes per (query, row chunk), at most 64 chunks.
+ * passes over every (query, row) pair; hs_index_exact_range_screened below gives the same answers by a screen.  Workspace per stream: 12 bytes per (query, row chunk), at most 64 chunks.
  * hs_last_kernel: hs::exact_range_kernel, _u8, _i8, _f16, _bf16 or _f8 by the rows' format (hs::exact_range_general_kernel for
  * dim % 16 != 0). */
 hs_status hs_index_exact_range(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius /* nq */,
@@ -670,6 +670,31 @@ hs_status hs_index_exact_screen_stats(hs_index *ix, uint64_t *screened, uint64_t
 /* Debug: the screen's margin e with |screened distance - recipe distance| <= e (csrc/exact_screen_margin.hpp; host only), from the
  * fp32 squared norms of query and row.  +inf: the screen does not decide such a pair. */
 hs_status hs_debug_exact_screen_margin(int metric, size_t dim, float qnorm2, float xnorm2, float *out);
+
+/* ---- every row within a radius, screened on the matrix cores --------------------------------------------------------------
+ * hs_index_exact_range[_dev]'s arguments, refusals and outputs -- offsets, labels, fp32 distance bits, ordering, the capacity rule
+ * and the HS_ERR_CAPACITY behaviour of either entry are identical for every input -- by another route (csrc/exact_range_screen.hip,
+ * DESIGN.md 4z): the fp32 MFMA distance of hs_index_exact_search_screened with its proven margin rules out every row whose lower
+ * bound lies above the query's radius; the survivors, at most HS_EXACT_RANGE_SCREEN_LIST per query, are re-ranked in the recipe's
+ * arithmetic and kept iff dist <= radius[i]; a query the screen cannot decide (a non-finite norm or interval, such as an L2 distance
+ * that overflows; more survivors than its list holds, such as radius = +inf over a larger index) is answered by the two passes of
+ * hs_index_exact_range, enqueued behind the re-rank for those queries only.  Whether a query falls back depends on the number of its
+ * survivors alone, not on the order they arrived in.  Nothing is read back between the passes of the _dev entry; the host entry
+ * reads the offsets once, as hs_index_exact_range does.
+ * Screened: dim % 16 == 0 (dim <= 4096); a tile of 64 queries stays in on-chip memory whole up to dim 624 and is staged in slices of
+ * 128 values beyond.  dim % 16 != 0 is handed to hs_index_exact_range's route whole.  hs_index_exact_screen_stats reports the call
+ * (reranked_rows: the listed rows of the queries that did not fall back); all zero when it was handed over.
+ * Workspace per stream: 8 * HS_EXACT_RANGE_SCREEN_LIST + 16 bytes per query, 4 bytes per row of the index, and
+ * hs_index_exact_range's 12 bytes per (query, row chunk).
+ * hs_last_kernel: hs::xrs_screen_kernel, _u8, _i8, _f16, _bf16 or _f8 by the rows' format (the scan's name when handed over).
+ * The host entry groups the queries by filter before it forms tiles of 64. */
+#define HS_EXACT_RANGE_SCREEN_LIST 1024
+hs_status hs_index_exact_range_screened(hs_index *ix, const hs_filter_set *fs, const float *queries, size_t nq, const float *radius /* nq */,
+                                        const uint32_t *filter_of_query, size_t cap, uint64_t *out_offsets /* nq + 1 */,
+                                        uint64_t *out_labels64 /* cap */, float *out_dists /* cap */);
+hs_status hs_index_exact_range_screened_dev(hs_index *ix, const hs_filter_set *fs, const float *d_queries, size_t nq, const float *d_radius,
+                                            const uint32_t *d_filter_of_query, size_t cap, uint64_t *d_out_offsets, uint64_t *d_out_labels64,
+                                            float *d_out_dists, void *stream);
 
 /* ---- the same answers for byte queries, screened on the integer matrix cores -------------------------------------------
  * queries: nq x dim bytes in natural order, query_format HS_ROWS_U8 or HS_ROWS_I8 -- the format of the index's narrow copy.  Labels,

@@ -13,7 +13,9 @@ cached 1M x 128 index and query seed of bench.py, 10 000 queries, k = 10.  ONE l
      k = 64 (the yardstick), three rounds, over fp32 and over u8 rows; the first 64 positions compared with the scan's.
   --range K [K ...]: instead of the above, hs_index_exact_range_dev with each query's K-th exact distance as its radius (taken
      from hs_index_exact_search_wide_dev) alternated with hs_index_exact_search_dev at k = 64, three rounds, over fp32 and over
-     u8 rows; the first K results of every query compared with the wide answer.
+     u8 rows; the first K results of every query compared with the wide answer.  hs_index_exact_range_screened_dev takes the same
+     radii in the same rounds, right behind the entry it is held against; its three outputs are compared with that entry's byte for
+     byte, and its fell_back / reranked_rows stats are logged.
 Output: the log on stdout.
 """
 import argparse
@@ -120,7 +122,7 @@ def main():
             o64 = (torch.zeros((NQ, 64), dtype=torch.int64, device=dev), torch.zeros((NQ, 64), dtype=torch.float32, device=dev),
                    torch.zeros(NQ, dtype=torch.int32, device=dev))
             legs = [(64, lambda: ix.exact_search_dev(dq, 64, *o64))]
-            totals = {}
+            totals, stats = {}, {}
             for k in args.range_k:
                 wl, wd = torch.zeros((NQ, k), dtype=torch.int64, device=dev), torch.zeros((NQ, k), dtype=torch.float32, device=dev)
                 ix.exact_search_wide_dev(dq, k, wl, wd)
@@ -139,18 +141,31 @@ def main():
                 assert total >= NQ * k and bool((off[1:] - off[:-1] >= k).all())
                 head = off[:-1, None] + torch.arange(k, device=dev)[None]
                 assert torch.equal(ol[head], wl) and torch.equal(od[head], wd), f"k = {k}: the first k of a segment differ from the wide answer"
+                so, sl, sd = torch.zeros_like(off), torch.zeros_like(ol), torch.zeros_like(od)
+                legs.append((f"screened {k}", lambda radius=radius, so=so, sl=sl, sd=sd: ix.exact_range_screened_dev(dq, radius, so, sl, sd)))
+                legs[-1][1](); ix.check()
+                assert torch.equal(so, off) and torch.equal(sl, ol) and torch.equal(sd, od), f"k = {k}: the screened entry differs from exact_range"
+                stats[k] = ix.exact_screen_stats()
+                log(f"{fmt_name} exact_range_screened at the {k}-th distance ({ix.last_kernel()}): {total} results, {stats[k]}")
             ms = {k: [] for k, _ in legs}
             for rnd in range(args.rounds):
                 for k, fn in legs:
                     med, mn = timed(fn, args.reps)
                     ms[k].append(med)
-                    log(f"{fmt_name} round {rnd} {'exact_search k = 64' if k == 64 and fn is legs[0][1] else f'exact_range at the {k}-th distance'}: "
+                    what = "exact_search k = 64" if fn is legs[0][1] else f"exact_range_screened at the {k.split()[1]}-th distance" if isinstance(k, str) \
+                        else f"exact_range at the {k}-th distance"
+                    log(f"{fmt_name} round {rnd} {what}: "
                         f"{med:.3f} ms per {NQ}-query call (median of {args.reps}, min {mn:.3f})")
             y = float(np.median(ms[64]))
-            log(f"{fmt_name} ({ix.last_kernel()}): exact_search k = 64 {y:.3f} ms (spread of its rounds {(max(ms[64]) - min(ms[64])) / y * 100:.2f} %) | "
+            log(f"{fmt_name}: exact_search k = 64 {y:.3f} ms (spread of its rounds {(max(ms[64]) - min(ms[64])) / y * 100:.2f} %) | "
                 + " | ".join(f"exact_range K = {k} ({totals[k]} results) {np.median(ms[k]):.3f} ms = {np.median(ms[k]) / y:.2f} x "
                              f"(spread {(max(ms[k]) - min(ms[k])) / np.median(ms[k]) * 100:.2f} %)" for k in args.range_k))
-            res[fmt_name] = dict(ms=ms, totals=totals)
+            for k in args.range_k:
+                old, new = ms[k], ms[f"screened {k}"]
+                log(f"{fmt_name} K = {k}: exact_range {np.median(old):.3f} ms (rounds {old}, spread {(max(old) - min(old)) / np.median(old) * 100:.2f} %) | "
+                    f"exact_range_screened {np.median(new):.3f} ms (rounds {new}, spread {(max(new) - min(new)) / np.median(new) * 100:.2f} %) = "
+                    f"{np.median(new) / np.median(old):.3f} x | fell_back {stats[k]['fell_back']}, reranked_rows {stats[k]['reranked_rows']}")
+            res[fmt_name] = dict(ms=ms, totals=totals, stats=stats)
         log("RESULT " + json.dumps(dict(range=res)))
         return 0
 
